@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- headline benchmark of the MI355X MSM / NTT backend (BASELINE.json metric).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--log-n 24] [--no-cpu] [--no-ntt]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--log-n 24] [--dump-outputs DIR] [--full [--no-cpu] [--no-ntt] ...]
     python bench.py --gpus N                       # N > 1 launched bare: re-executes itself under torch.distributed.run (one rank per GPU)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P bench.py --gpus N ...
     python bench.py --gpus N --transport mctx      # ONE process, zl_ctx_create_multi + zl_msm_sharded / zl_ntt_sharded (RCCL inside the library)
@@ -11,7 +11,18 @@ scalars already resident in HBM, through the C ABI (zl_msm_batch_partial_dev / z
 `value` is what multi_scalar_mul(bases, scalars) is.  Every timed step is checked exactly at full size against (sum s_i k_i) G
 (the bases have known discrete logs).  With N > 1 every rank owns its own shard of
 bases/scalars (weak scaling), the per-rank partial sums (512 B) are all-gathered over RCCL and folded
-on every rank (zl_partials_sum).  Rank 0 prints ONE JSON line.  Extra objects on that line:
+on every rank (zl_partials_sum).  Rank 0 prints ONE JSON line.
+
+A plain run (no --full) does only what the headline needs: inputs, gate, W warm-up steps, EXACTLY K timed steps (each checked), the line.
+Its line carries metric / value / unit / higher_is_better / dtype / ms_per_step (= wall time of the K timed steps / K) and the config; the
+objects below are null or absent.  --full runs every other leg as well (the --no-* options pick among them).
+
+--dump-outputs DIR writes what the timed path returned for its LAST timed step, on rank 0 (N > 1: the folded all-rank result):
+  msm_xy.npy        float64 (2, 12): the affine x and y of the result point, each as 12 little-endian 32-bit words (exact in float64)
+  msm_infinity.npy  float64 (1,): 1.0 if the result is the point at infinity
+The inputs depend on the arguments only (fixed seeds), so two builds can be compared output for output.
+
+Extra objects on the line of a --full run:
   roofline      HBM roofline of the dominant kernel (k_msm_accumulate): algorithmic bytes (128 B / point, SURVEY.md
                 §8d) / its HIP-event duration on the backend's stream, vs 8 TB/s; .int_alu = the integer-multiply roofline
                 that actually binds; .traffic = PMC bytes of the same configuration (profiles/)
@@ -386,6 +397,15 @@ def _self_launch(n_gpus: int):
     os.execv(sys.executable, cmd)
 
 
+def dump_outputs(out_dir: str, result) -> None:
+    """--dump-outputs: the (xy, inf) of the last timed step as float64 arrays (module docstring); 32-bit words keep every value exact."""
+    xy, inf = result
+    os.makedirs(out_dir, exist_ok=True)
+    words = np.ascontiguousarray(np.asarray(xy, dtype=np.uint64)).view(np.uint32).astype(np.float64).reshape(2, -1)
+    np.save(os.path.join(out_dir, "msm_xy.npy"), words)
+    np.save(os.path.join(out_dir, "msm_infinity.npy"), np.array([float(inf)], dtype=np.float64))
+
+
 class Run:
     """what every leg needs: the backend of this rank, its device, and the process group (if any)"""
 
@@ -451,10 +471,11 @@ class MsmInputs:
         self.R.torch.cuda.empty_cache()
 
 
-def msm_leg(R: Run, inp: MsmInputs, steps: int, warmup: int, pipelined: bool, solo: bool, what: str):
+def msm_leg(R: Run, inp: MsmInputs, steps: int, warmup: int, pipelined: bool, solo: bool, what: str, latency: bool = True):
     """Gate (exact, full size, both scalar vectors, single call + pipelined batch + all ranks) -> `warmup` untimed steps -> EXACTLY `steps`
     timed steps between barriers, max over ranks -> every timed step checked exactly.  solo (N > 1): the same `steps` local MSMs on
-    rank 0 alone while the other ranks wait: the N = 1 reference of the same per-GPU size for interference_ratio (= the weak-scaling efficiency of a fixed-shard leg)."""
+    rank 0 alone while the other ranks wait: the N = 1 reference of the same per-GPU size for interference_ratio (= the weak-scaling efficiency of a fixed-shard leg).
+    latency: one more un-pipelined call after the timed steps (single_call_*; None without it).  last_result = (xy, inf) of the last timed step."""
     from openzl_amd.sharded import fold_partials, sharded_msm, sharded_msm_batch
 
     be, n, h, d_vecs, curve = R.be, inp.n, inp.h, inp.d_vecs, inp.curve
@@ -518,15 +539,17 @@ def msm_leg(R: Run, inp: MsmInputs, steps: int, warmup: int, pipelined: bool, so
         if inf_i or not (np.asarray(xy_i) == inp.exp_all[i % 2]).all():
             fail("timed step")
     elapsed = R.max_over_ranks([elapsed])[0]
-    # latency of one un-pipelined MSM call, for the record
-    R.torch.cuda.synchronize()
-    t1 = time.perf_counter()
-    be.msm_partial_dev(h, d_vecs[0].data_ptr(), n)
-    single_ms = (time.perf_counter() - t1) * 1e3
-    single_dev = be.last_timing()
+    single_ms = single_dev_ms = None
+    if latency:
+        # latency of one un-pipelined MSM call, for the record
+        R.torch.cuda.synchronize()
+        t1 = time.perf_counter()
+        be.msm_partial_dev(h, d_vecs[0].data_ptr(), n)
+        single_ms = (time.perf_counter() - t1) * 1e3
+        single_dev_ms = float(be.last_timing().total_ms)
     out = {"elapsed": elapsed, "ms_per_step": elapsed / steps * 1e3, "dom_ms": float(np.mean(dom_ms)), "tot_ms": float(np.mean(tot_ms)),
            "window_bits": int(tm.window_bits), "entries": float(tm.entries), "pipelined": pipelined,
-           "single_call_latency_ms": single_ms, "single_call_device_ms": float(single_dev.total_ms)}
+           "single_call_latency_ms": single_ms, "single_call_device_ms": single_dev_ms, "last_result": results[-1]}
     if solo and R.world > 1:
         # the same per-GPU work on ONE GPU with the others idle (rank 0, same process, same inputs, no collective): the N = 1 reference
         R.barrier()
@@ -752,10 +775,11 @@ def config2_leg(R: Run):
         inp.free()
 
 
-def mctx_run(args, devices, log_n, ntt_log_m, steps, warmup, g16_k=None):
+def mctx_run(args, devices, log_n, ntt_log_m, steps, warmup, g16_k=None, solo=True, dump_dir=""):
     """ONE process, G devices: zl_ctx_create_multi (RCCL communicator inside the library when the devices are distinct) + zl_msm_sharded
     (complete local Pippenger per device on its own host thread -> ncclAllGather of the partials -> fold) and zl_ntt_sharded (cross step ->
-    grouped ncclSend / ncclRecv all-to-all -> local transform).  Returns the result dict; every MSM result is checked exactly."""
+    grouped ncclSend / ncclRecv all-to-all -> local transform).  Returns the result dict; every MSM result is checked exactly.
+    solo: time rank 0's MSM alone too (interference_ratio); dump_dir: --dump-outputs of the last timed step."""
     import torch
     from openzl_amd import ZL_BLS12_381
     from openzl_amd.backend import MultiBackend
@@ -794,16 +818,20 @@ def mctx_run(args, devices, log_n, ntt_log_m, steps, warmup, g16_k=None):
         for i, (xy, inf) in enumerate(res):
             if inf or not (np.asarray(xy) == exp[i % 2]).all():
                 raise SystemExit("zl_msm_sharded self-check failed (timed step)")
-        # the same per-GPU MSM on rank 0's ctx alone (single calls, as zl_msm_sharded issues them)
-        t1 = time.perf_counter()
-        for i in range(steps):
-            mb.ranks[0].msm_partial_dev(hs[0], d_s[0][i % 2].data_ptr(), n)
-        solo = (time.perf_counter() - t1) / steps
+        if dump_dir:
+            dump_outputs(dump_dir, res[-1])
+        solo_s = None
+        if solo:
+            # the same per-GPU MSM on rank 0's ctx alone (single calls, as zl_msm_sharded issues them)
+            t1 = time.perf_counter()
+            for i in range(steps):
+                mb.ranks[0].msm_partial_dev(hs[0], d_s[0][i % 2].data_ptr(), n)
+            solo_s = (time.perf_counter() - t1) / steps
         out = {"transport": "mctx: one process, zl_ctx_create_multi + zl_msm_sharded / zl_ntt_sharded (include/zl_backend.h)", "n_gpus": G, "devices": list(devices),
                "rccl_ranks": G if mb.uses_rccl else 0, "exchange": "RCCL (ncclCommInitAll; ncclAllGather / grouped ncclSend+ncclRecv)" if mb.uses_rccl else
                "virtual ranks sharing a device: device-to-device copies with the same data movement pattern (RCCL refuses duplicate devices)",
                "msm": {"points_per_gpu": n, "points_total": float(n) * G, "steps": steps, "ms_per_step": el / steps * 1e3, "points_per_s": float(n) * G * steps / el,
-                       "single_gpu_ms_per_step": solo * 1e3, "interference_ratio": solo / (el / steps), "checked_exactly": True,
+                       "single_gpu_ms_per_step": solo_s * 1e3 if solo else None, "interference_ratio": solo_s / (el / steps) if solo else None, "checked_exactly": True,
                        "issued_as": "separate zl_msm_sharded calls (not pipelined)"}}
         for hh, r in zip(hs, mb.ranks):
             r.bases_free(hh)
@@ -898,7 +926,9 @@ def main_mctx(args):
     if not torch.cuda.is_available():
         raise SystemExit("bench.py needs a GPU: the HIP backend has no CPU fallback")
     devices = [int(x) for x in args.mctx_devices.split(",")] if args.mctx_devices else list(range(args.gpus))
-    res = mctx_run(args, devices, args.log_n, 0 if args.no_ntt else args.ntt_log_n, args.steps, args.warmup)
+    # a plain run: the sharded MSM steps only; --full adds the solo reference, the sharded NTT and the sharded proof
+    res = mctx_run(args, devices, args.log_n, 0 if args.no_ntt or not args.full else args.ntt_log_n, args.steps, args.warmup,
+                   g16_k=None if args.full else 0, solo=args.full, dump_dir=args.dump_outputs)
     m = res["msm"]
     line = {"metric": "MSM points/sec (BLS12-381 G1)", "value": m["points_per_s"], "unit": "points/s", "n_gpus": len(devices), "steps": args.steps, "warmup": args.warmup,
             "ms_per_step": m["ms_per_step"], "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "u32", "data": "synthetic",
@@ -913,7 +943,7 @@ def mctx_child(args, devices, timeout_s=240):
 
     env = {k: v for k, v in os.environ.items() if k not in _TORCHRUN_ENV}
     cmd = [sys.executable, os.path.abspath(__file__), "--transport", "mctx", "--gpus", str(len(devices)), "--mctx-devices", ",".join(str(d) for d in devices),
-           "--log-n", str(min(args.log_n, 22)), "--ntt-log-n", str(min(args.ntt_log_n, 22)), "--steps", str(max(2, min(args.steps, 6))), "--warmup", "1"]
+           "--log-n", str(min(args.log_n, 22)), "--ntt-log-n", str(min(args.ntt_log_n, 22)), "--steps", str(max(2, min(args.steps, 6))), "--warmup", "1", "--full"]
     # (2^22 points / elements per device: the child generates every device's inputs itself, one after the other; the point of this leg is the
     #  library's own RCCL exchange, whose cost does not depend on the shard size)
     if args.no_ntt:
@@ -956,6 +986,9 @@ def main():
     ap.add_argument("--no-pcie", action="store_true", help="skip the host-scalar leg (pcie_inclusive): rocprofv3 runs of the headline keep only the headline's own accumulation launches")
     ap.add_argument("--no-live-traffic", action="store_true", help="do not measure roofline.traffic in this run (four child processes under rocprofv3 --pmc after the timed legs, ~70 s); the committed PMC passes of the same configuration are quoted instead")
     ap.add_argument("--dry-run", action="store_true", help="print the legs a `--gpus N` run executes, the per-rank HBM plan and the expected wall time, and exit (no GPU, no process group)")
+    ap.add_argument("--full", action="store_true", help="run every leg besides the headline (CPU baselines, NTT, Groth16, configs, rooflines, scaling legs, ...); "
+                                                         "a plain run only times the headline's steps")
+    ap.add_argument("--dump-outputs", metavar="DIR", default="", help="write the result of the last timed step as DIR/<name>.npy (float64)")
     args = ap.parse_args()
 
     if args.dry_run:
@@ -1008,7 +1041,7 @@ def main():
         be.set_msm_window(args.window)
     n = 1 << args.log_n
     R = Run(args, torch, dist, be, dev, rank, world)
-    if rank == 0 and world == 1:
+    if args.full and rank == 0 and world == 1:
         oracle_native()  # before the first leg that loads the oracle
 
     leg_errors = {}
@@ -1035,15 +1068,16 @@ def main():
     inp = MsmInputs(R, n, 0)
     h, k64, vecs, d_vecs, exp_xy = inp.h, inp.k64, inp.vecs, inp.d_vecs, inp.exp_xy
     t_generate = inp.t_generate
-    head = msm_leg(R, inp, args.steps, args.warmup, not args.no_pipeline, True, "headline")
+    head = msm_leg(R, inp, args.steps, args.warmup, not args.no_pipeline, args.full, "headline", latency=args.full)
     elapsed, pipelined, single_ms = head["elapsed"], head["pipelined"], head["single_call_latency_ms"]
-    tm = be.last_timing()
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, head["last_result"])
     # effective shader clock while the dominant kernel runs: a sleeping one-wave-per-XCD probe on its own stream (include/zl_backend_test.h) spans one more pipelined
     # batch of four steps, ~90 % of which is the accumulation (the rest: the sorts and tails between two accumulations); every step checked like the timed ones.
     # (Round 5 read the clock inside a clock-reading build of the kernel, k_msm_accumulate_clk; that kernel now exists in -DZL_MEASURE builds only -- VERDICT r5
     # item 7 -- and tools/clock_probe.py still uses it there: profiles/r05_clock_probe_2_24.log has both readings side by side.)
     acc_clock = None
-    if rank == 0:
+    if args.full and rank == 0:
         try:
             from openzl_amd.backend import hook_clock_probe_launch, hook_clock_probe_read
             cnt = 4
@@ -1064,7 +1098,7 @@ def main():
             acc_clock = {"error": f"{type(e).__name__}: {e}"}
     _dbg_c2("after headline")
     scaling_model = None
-    if rank == 0 and world == 1 and not args.no_configs and args.log_n >= 22:
+    if args.full and rank == 0 and world == 1 and not args.no_configs and args.log_n >= 22:
         def _leg_scaling_model():
             nonlocal scaling_model
             scaling_model = scaling_model_leg(R, inp, head)
@@ -1095,7 +1129,7 @@ def main():
         pcie_info = {"ms_per_msm": float(np.min(ts)) * 1e3, "points_per_s": n / float(np.min(ts)),
                      "note": "zl_msm: scalars copied from pageable host memory (32 B/point over PCIe) + all kernels + result D2H, bases resident"}
 
-    if rank == 0 and world == 1 and not args.no_pcie:
+    if args.full and rank == 0 and world == 1 and not args.no_pcie:
         _guard("pcie_info", _leg_pcie_info)
 
     skew_info = None
@@ -1122,7 +1156,7 @@ def main():
                              "in two stages; exactness of these paths: tests/test_gpu_msm.py (skewed cases), tests/test_gpu_msm_fuzz.py"}
         del d2
 
-    if rank == 0 and world == 1 and not args.no_skew:
+    if args.full and rank == 0 and world == 1 and not args.no_skew:
         _guard("skew_info", _leg_skew_info)
 
     # ---- fixed-key mode, reported beside the headline: table of 2^(c w) P_i built once per key (a Groth16 proving key is static) -------
@@ -1166,7 +1200,7 @@ def main():
                     "bases (a Groth16 proving key).  Same exact full-size checks as the headline.  NOT `value`: multi_scalar_mul(bases, scalars) has no per-key state.",
         }
 
-    if args.fixed_key >= 0 and rank == 0 and world == 1 and not args.window:
+    if args.full and args.fixed_key >= 0 and rank == 0 and world == 1 and not args.window:
         _guard("fixed_info", _leg_fixed_info)
 
     ntt_info = None
@@ -1251,7 +1285,7 @@ def main():
         }
         del dx
 
-    if not args.no_ntt:
+    if args.full and not args.no_ntt:
         _guard("ntt_info", _leg_ntt_info)
 
     g16_info = None
@@ -1385,7 +1419,7 @@ def main():
                 kx.close()
                 cx.close()
 
-    if args.groth16_k > 0 and rank == 0 and world == 1:
+    if args.full and args.groth16_k > 0 and rank == 0 and world == 1:
         _guard("g16_info", _leg_g16_info)
 
     cpu = None
@@ -1393,12 +1427,12 @@ def main():
         nonlocal cpu
         cpu = cpu_baseline(be, h, k64, s_host, exp_xy[0], args.cpu_threads, args.log_n)
 
-    if not args.no_cpu and rank == 0 and world == 1:
+    if args.full and not args.no_cpu and rank == 0 and world == 1:
         _guard("cpu", _leg_cpu)
 
     # ---- BASELINE configs 1, 2, 4 on the N = 1 line (3 = ntt, 5 = groth16 above) -------------------------------------------------------------
     configs = {}
-    if rank == 0 and world == 1 and not args.no_configs:
+    if args.full and rank == 0 and world == 1 and not args.no_configs:
         def _leg_c1():
             configs["1"] = config1_leg(R, args.no_cpu)
 
@@ -1435,7 +1469,7 @@ def main():
         traffic_src = None
         traffic_how = None
         under_prof = any(k.startswith(("ROCP_", "ROCPROF")) for k in os.environ)  # (a rocprofv3 run of this file: no profiler inside the profiler)
-        if world == 1 and not args.no_live_traffic and not under_prof:
+        if args.full and world == 1 and not args.no_live_traffic and not under_prof:
             # measured NOW, after every timed leg: child processes under rocprofv3 --pmc (live_pmc_traffic); any failure falls back to the committed passes below
             try:
                 t_live, det = live_pmc_traffic("msm", args.log_n)
@@ -1487,9 +1521,10 @@ def main():
                                           "consecutive steps alternate between two scalar vectors" if pipelined else "separate calls",
                        "single_call_latency_ms": single_ms, "single_call_device_ms": head["single_call_device_ms"],
                        "bases_generate_s": t_generate,
-                       "result_check": "every timed step equals (sum s_i k_i) G exactly at full size (known discrete logs); the CPU oracle's MSM of the "
-                                       "complete input equals it too (cpu_baseline.parity_full_size)"},
-            "roofline": {"bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": achieved / HBM_PEAK_GBS,
+                       "result_check": "every timed step equals (sum s_i k_i) G exactly at full size (known discrete logs)" + ("; the CPU oracle's MSM of the "
+                                       "complete input equals it too (cpu_baseline.parity_full_size)" if cpu is not None else "")},
+            # (the roofline's int_alu peak and traffic take runs of their own: --full only)
+            "roofline": None if not args.full else {"bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": achieved / HBM_PEAK_GBS,
                          "traffic": traffic, "traffic_unit": ("bytes per launch, 2 x FETCH_SIZE + WRITE_SIZE (the guide's gfx950 correction: FETCH_SIZE tallies 128-B requests at 64 B); " + traffic_how["how"]) if traffic_how else
                                          f"bytes per launch, 2 x FETCH_SIZE + WRITE_SIZE (the guide's gfx950 correction: FETCH_SIZE tallies 128-B requests at 64 B), from the committed PMC passes of this configuration "
                                          f"(profiles/{traffic_src or 'r04_pmc_traffic.json'}; --no-live-traffic, N > 1 or a failed live pass: see leg_errors); null for any other configuration",
@@ -1537,7 +1572,7 @@ def main():
         dog.start()
         if rank == 0:
             line["scaling_legs"] = {"weak": scaling_entry(R, "weak", f"2^{args.log_n} points per GPU (the headline)", n, head, args.steps)}
-        if not args.no_configs:
+        if args.full and not args.no_configs:
             # BASELINE config 4 (2^26 points over the ranks; 2^23 per GPU at N = 8) and strong scaling (2^24 points over the ranks):
             # own inputs per leg, same gate / exact checks / barriers as the headline, plus the single-GPU reference of the same shard size
             for name, log_total in (("config4", args.config4_log_total), ("strong", args.strong_log_total)):
@@ -1556,7 +1591,7 @@ def main():
                     ent = {"error": "a rank failed (see stderr)"}
                 if rank == 0:
                     line["scaling_legs"][name] = ent
-        if args.groth16_k > 0:
+        if args.full and args.groth16_k > 0:
             # constraints/s at N GPUs: independent proofs, one per GPU (replicas: a proof does not shard), max-over-ranks time
             try:
                 n_c, t_prove = groth16_replica_leg(be, torch, args.groth16_k)
@@ -1572,7 +1607,7 @@ def main():
                                        "prove_ms": tt[0] * 1e3, "constraints_per_s": world * tt[2] / tt[0], "verified": True}
                 else:
                     line["groth16"] = {"error": "a rank failed (see stderr)"}
-        if is_nccl and not args.no_ntt and (world & (world - 1)) == 0 and world <= 16:
+        if args.full and is_nccl and not args.no_ntt and (world & (world - 1)) == 0 and world <= 16:
             try:
                 dinfo = distributed_ntt_leg(be, dist, torch, dev, rank, world, args.ntt_log_n)
             except Exception as e:  # noqa: BLE001 -- reported in the JSON line, the headline number stands
@@ -1586,7 +1621,7 @@ def main():
         if rank != 0:
             dog.cancel()
             return
-        if not args.no_mctx:
+        if args.full and not args.no_mctx:
             # the C-ABI transport (one process, zl_ctx_create_multi: ncclCommInitAll inside the library) timed once, in a child process
             devs = list(range(world)) if is_nccl else [g % torch.cuda.device_count() for g in range(world)]
             time.sleep(1.0)
@@ -1600,7 +1635,7 @@ def main():
         coll = {"backend": dist.get_backend(), "ranks": dist.get_world_size(), "tensors": "device (RCCL)" if is_nccl else "host (gloo)",
                 "all_gather_into_tensor": "headline gate + every timed step, exact", "barrier_and_all_reduce_max": "timed region"}
         try:
-            if is_nccl:
+            if args.full and is_nccl:
                 coll["all_to_all_single"] = distributed_ntt_leg(be, dist, torch, dev, 0, 1, min(args.ntt_log_n, 20))
         except Exception as e:  # noqa: BLE001
             coll["all_to_all_single"] = {"error": f"{type(e).__name__}: {e}"}
@@ -1659,28 +1694,29 @@ def dry_run_plan(args) -> dict:
 
     pick_c = lambda lg: 19 if lg >= 24 else (18 if lg >= 23 else (17 if lg >= 21 else 16))  # noqa: E731 -- zl_pick_window's choices at these sizes
     K, Wm = args.steps, args.warmup
+    full = args.full  # a plain run is the headline alone
     legs, hbm = [], {}
     head_ms = msm_ms(args.log_n)
     legs.append({"leg": "headline (weak)", "per_gpu_points": n, "steps": K, "warmup": Wm, "collectives": "barrier x2, all_gather_into_tensor of K x 512 B per rank, all_reduce MAX" if N > 1 else "none",
                  "setup_s": round(0.11 * n / (1 << 24) * 2 + 0.6, 2), "timed_ms": round(K * head_ms, 1), "gate_and_warmup_ms": round((2 + 3 + Wm + (2 if N > 1 else 0)) * head_ms * 1.06, 1),
-                 "solo_reference_on_rank0_ms": round(K * head_ms, 1) if N > 1 else 0})
+                 "solo_reference_on_rank0_ms": round(K * head_ms, 1) if N > 1 and full else 0})
     hbm["bases (Affine, 128 B/point)"] = 128 * n
     hbm["two scalar vectors (32 B/point each)"] = 64 * n
     hbm["msm pipeline scratch"] = _msm_scratch_bytes(n, args.window or pick_c(args.log_n))
-    if N > 1 and not args.no_configs:
+    if full and N > 1 and not args.no_configs:
         for name, log_total in (("config4", args.config4_log_total), ("strong", args.strong_log_total)):
             lg = max(10, log_total - (N.bit_length() - 1))
             t = msm_ms(lg)
             legs.append({"leg": name, "total_points": 1 << log_total, "per_gpu_points": 1 << lg, "steps": K, "collectives": "as the headline", "timed_ms": round(K * t, 1),
                          "gate_and_warmup_ms": round((7 + Wm) * t * 1.06, 1), "solo_reference_on_rank0_ms": round(K * t, 1),
                          **({"t1_whole_input_on_rank0_ms": round((K + 4) * msm_ms(log_total), 1), "rank0_extra_hbm": 192 * (1 << log_total)} if name == "strong" else {})})
-    if N == 1 and not args.no_configs:
+    if full and N == 1 and not args.no_configs:
         legs.append({"leg": "scaling_model + configs 1 / 2 / 4 (N = 1 only)", "timed_ms": round(8 * (msm_ms(21) + msm_ms(22) + msm_ms(23)) + 400, 1)})
-    if N == 1:
+    if full and N == 1:
         legs.append({"leg": "pcie_inclusive, msm_fixed_key (c = %d table: %d x the base memory), msm_skewed_scalars (N = 1 only)" % (args.fixed_key, (256 + args.fixed_key - 1) // max(1, args.fixed_key)),
                      "timed_ms": round(4 * 44 + 4 * 33 + 3000 + 6 * 40, 1)})
         hbm["fixed-key table (freed after its leg)"] = 128 * n * ((256 + args.fixed_key - 1) // max(1, args.fixed_key)) if args.fixed_key > 0 else 0
-    if not args.no_ntt:
+    if full and not args.no_ntt:
         ln = args.ntt_log_n
         legs.append({"leg": "ntt replicas", "log_n": ln, "transforms": 2 * 16 + 16, "timed_ms": round(24 * ntt_ms * 2.0 ** (ln - 24), 1), "collectives": "all_reduce MAX" if N > 1 else "none"})
         hbm["ntt vector + scratch (32 + 40 B/element)"] = 72 << ln
@@ -1689,13 +1725,13 @@ def dry_run_plan(args) -> dict:
             legs.append({"leg": "ntt distributed", "log_n": ln + N.bit_length() - 1, "exchange": "one all_to_all_single per transform: %d MiB sent per GPU" % ((32 << ln) * (N - 1) // N >> 20),
                          "transforms": 8, "timed_ms": round(8 * (ntt_ms / 2 * 2.0 ** (ln - 24) + (32 << ln) / 50e9 * 1e3 + 0.3), 1)})
             hbm["distributed ntt: exchange buffer"] = 32 << ln
-    if args.groth16_k > 0:
+    if full and args.groth16_k > 0:
         cons = 234 * args.groth16_k + 1  # Poseidon arity-2 chain: 234 constraints per hash (tests/groth16_util.py)
         dom = 1 << max(1, (cons).bit_length())
         legs.append({"leg": "groth16 " + ("replicas (one independent proof per GPU)" if N > 1 else "config 5 + small circuits + BN254"), "constraints": cons, "domain": dom,
                      "host_synthesis_and_setup_s": round(2.0 * cons / 958465 + 0.3, 2), "proofs": 10, "timed_ms": round(10 * g16_ms * cons / 958465 + 5, 1)})
         hbm["groth16: proving key (5 queries + window tables) + R1CS CSR + witness-map vectors"] = int(cons * (128 * 3 * 14 + 256 * 17 + 3 * 3 * 12 + 7 * 40))
-    if N > 1 and not args.no_mctx:
+    if full and N > 1 and not args.no_mctx:
         legs.append({"leg": "mctx (child process of rank 0 after the ranks released their GPUs: zl_ctx_create_multi, ncclCommInitAll inside the library)", "timed_ms": round(6 * msm_ms(args.log_n) + 8 * ntt_ms + 3000, 1)})
     total_hbm = sum(v["total"] if isinstance(v, dict) else v for v in hbm.values())
     wall = sum(l.get("timed_ms", 0) + l.get("gate_and_warmup_ms", 0) + l.get("solo_reference_on_rank0_ms", 0) + l.get("t1_whole_input_on_rank0_ms", 0) for l in legs) / 1e3

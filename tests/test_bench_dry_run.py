@@ -16,7 +16,7 @@ def _plan(*extra):
 
 
 def test_dry_run_eight_gpus():
-    d = _plan("--gpus", "8")
+    d = _plan("--gpus", "8", "--full")
     assert d["dry_run"] is True and d["nothing_was_run"] is True and d["n_gpus"] == 8 and "torch.distributed.run" in d["launch"]
     legs = [l["leg"] for l in d["legs_in_order"]]
     assert legs[0].startswith("headline") and "config4" in legs and "strong" in legs and any(l.startswith("ntt distributed") for l in legs) and any(l.startswith("mctx") for l in legs)
@@ -29,7 +29,7 @@ def test_dry_run_eight_gpus():
 
 
 def test_dry_run_single_gpu_and_small():
-    d = _plan("--gpus", "1", "--log-n", "20", "--ntt-log-n", "20", "--groth16-k", "64")
+    d = _plan("--gpus", "1", "--log-n", "20", "--ntt-log-n", "20", "--groth16-k", "64", "--full")
     assert d["n_gpus"] == 1 and d["launch"] == "python bench.py"
     assert not any(l["leg"] in ("config4", "strong") for l in d["legs_in_order"])
     assert d["hbm_total_per_rank_gb"] < 20
@@ -48,3 +48,26 @@ def test_host_cores_respects_affinity_and_cgroup_quota():
             assert n <= max(1, int(q) // int(per))
     except FileNotFoundError:
         pass
+
+
+def test_dry_run_plain_is_the_headline_alone():
+    """without --full a run times the headline's steps and nothing else"""
+    d = _plan("--gpus", "8")
+    assert [l["leg"] for l in d["legs_in_order"]] == ["headline (weak)"]
+    assert d["legs_in_order"][0]["solo_reference_on_rank0_ms"] == 0
+
+
+def test_dump_outputs_is_exact(tmp_path):
+    """--dump-outputs: the result point as float64 32-bit words, which convert back to the same uint64 limbs"""
+    import numpy as np
+
+    sys.path.insert(0, ROOT)
+    import bench
+
+    rng = np.random.Generator(np.random.PCG64(5))
+    xy = rng.integers(0, 1 << 64, size=12, dtype=np.uint64)
+    bench.dump_outputs(str(tmp_path / "out"), (xy, 0))
+    w = np.load(tmp_path / "out" / "msm_xy.npy")
+    inf = np.load(tmp_path / "out" / "msm_infinity.npy")
+    assert w.dtype == np.float64 and w.shape == (2, 12) and inf.dtype == np.float64 and inf.tolist() == [0.0]
+    assert (w.reshape(-1).astype(np.uint64).astype(np.uint32).view(np.uint64) == xy).all()

@@ -18,7 +18,7 @@ def _line(out: str) -> dict:
 
 
 def test_bench_single_gpu_small():
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--log-n", "16", "--ntt-log-n", "14", "--groth16-k", "4", "--steps", "3", "--warmup", "1"],
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--log-n", "16", "--ntt-log-n", "14", "--groth16-k", "4", "--steps", "3", "--warmup", "1", "--full"],
                        capture_output=True, text=True, timeout=600, cwd=ROOT)
     assert r.returncode == 0, r.stderr[-3000:]
     d = _line(r.stdout)
@@ -51,11 +51,34 @@ def test_bench_single_gpu_small():
     assert nrf["traffic_detail"]["how"].startswith("measured in this run") and nrf["traffic"] >= 64.0 * (1 << 14)
 
 
+def test_bench_plain_run_and_dump_outputs(tmp_path):
+    """A plain run (no --full) is the headline alone: the headline fields, no secondary object; --dump-outputs writes the last timed step's
+    result, and two runs with the same arguments write the same arrays."""
+    import numpy as np
+
+    dumps = []
+    for i in range(2):
+        out = tmp_path / f"run{i}"
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--log-n", "16", "--steps", "3", "--warmup", "1", "--dump-outputs", str(out)],
+                           capture_output=True, text=True, timeout=600, cwd=ROOT)
+        assert r.returncode == 0, r.stderr[-3000:]
+        d = _line(r.stdout)
+        assert d["unit"] == "points/s" and d["value"] > 0 and d["steps"] == 3 and d["warmup"] == 1 and d["higher_is_better"] is True and d["dtype"] == "u32"
+        assert abs(d["ms_per_step"] - (1 << 16) / d["value"] * 1e3) < 1e-6 * d["ms_per_step"]  # value = points of the K steps / their wall time
+        for key in ("roofline", "cpu_baseline", "pcie_inclusive", "msm_fixed_key", "msm_skewed_scalars", "ntt", "groth16", "configs", "scaling_model"):
+            assert d[key] is None, key
+        assert "leg_errors" not in d
+        xy, inf = np.load(out / "msm_xy.npy"), np.load(out / "msm_infinity.npy")
+        assert xy.dtype == np.float64 and xy.shape == (2, 12) and inf.tolist() == [0.0] and (xy >= 0).all() and (xy < 2.0 ** 32).all() and xy.any()
+        dumps.append(xy)
+    assert (dumps[0] == dumps[1]).all()
+
+
 def test_bench_scaling_model():
     """N = 1 at 2^22: the line carries the single-GPU times of the 2^21 prefix (exact) and the model's fields; the 2^24-specific efficiencies need the
     full size and are exercised by the driver's default run."""
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--log-n", "22", "--steps", "3", "--warmup", "1", "--no-ntt", "--groth16-k", "0", "--no-cpu", "--no-skew",
-                        "--fixed-key", "-1", "--no-live-traffic"], capture_output=True, text=True, timeout=900, cwd=ROOT)
+                        "--fixed-key", "-1", "--no-live-traffic", "--full"], capture_output=True, text=True, timeout=900, cwd=ROOT)
     assert r.returncode == 0, r.stderr[-3000:]
     d = _line(r.stdout)
     m = d["scaling_model"]
@@ -85,7 +108,7 @@ def _check_two_rank_line(d):
 
 
 _SMALL_N2 = ["--gpus", "2", "--log-n", "16", "--ntt-log-n", "14", "--groth16-k", "4", "--steps", "2", "--warmup", "1", "--config4-log-total", "18",
-             "--strong-log-total", "16"]
+             "--strong-log-total", "16", "--full"]
 
 
 def test_bench_two_ranks_gloo_one_gpu():
@@ -110,7 +133,7 @@ def test_bench_bare_launch_self_execs_under_torchrun():
 def test_bench_mctx_transport_virtual_ranks():
     """--transport mctx: ONE process, zl_ctx_create_multi + zl_msm_sharded / zl_ntt_sharded; 4 virtual ranks on GPU 0 (RCCL needs distinct devices)."""
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--transport", "mctx", "--gpus", "4", "--mctx-devices", "0,0,0,0", "--log-n", "14",
-                        "--ntt-log-n", "12", "--steps", "2", "--warmup", "1"], capture_output=True, text=True, timeout=600, cwd=ROOT)
+                        "--ntt-log-n", "12", "--steps", "2", "--warmup", "1", "--full"], capture_output=True, text=True, timeout=600, cwd=ROOT)
     assert r.returncode == 0, r.stderr[-3000:]
     d = _line(r.stdout)
     assert d["n_gpus"] == 4 and d["value"] > 0 and d["mctx"]["rccl_ranks"] == 0 and d["mctx"]["msm"]["checked_exactly"] is True
@@ -125,7 +148,7 @@ def test_bench_one_rank_nccl_group_runs_every_collective():
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT", "ZL_DIST_BACKEND")}
     env["ZL_FORCE_COLLECTIVE"] = "1"
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--log-n", "18", "--ntt-log-n", "16", "--groth16-k", "0", "--steps", "3", "--warmup", "1", "--no-cpu",
-                        "--no-configs", "--no-skew", "--no-pcie", "--fixed-key", "-1", "--no-live-traffic"], capture_output=True, text=True, timeout=600, cwd=ROOT, env=env)
+                        "--no-configs", "--no-skew", "--no-pcie", "--fixed-key", "-1", "--no-live-traffic", "--full"], capture_output=True, text=True, timeout=600, cwd=ROOT, env=env)
     assert r.returncode == 0, r.stderr[-3000:]
     d = _line(r.stdout)
     c = d["collective"]

@@ -17,5 +17,5 @@ echo "== quad lanes sweep at 2^16 / 2^20 (queues 8)"
 for ql in 0 16384 65536 262144; do echo "ZL_TUNE_QUAD_LANES=$ql"; GPU_MAX_HW_QUEUES=8 ZL_TUNE_QUAD_LANES=$ql SIZES=16,20 python tools/small_lat.py msm 2>&1 | grep "^MSM bls"; done
 for q in 4 8; do
   echo "== headline, GPU_MAX_HW_QUEUES=$q"
-  GPU_MAX_HW_QUEUES=$q python bench.py --steps 10 --warmup 2 --no-configs 2>/dev/null | python -c "import sys,json; d=json.loads(sys.stdin.read().strip().splitlines()[-1]); print(d['ms_per_step'], d.get('groth16',{}).get('prove_ms'), d.get('ntt',{}).get('ms_per_transform'))"
+  GPU_MAX_HW_QUEUES=$q python bench.py --full --steps 10 --warmup 2 --no-configs 2>/dev/null | python -c "import sys,json; d=json.loads(sys.stdin.read().strip().splitlines()[-1]); print(d['ms_per_step'], d.get('groth16',{}).get('prove_ms'), d.get('ntt',{}).get('ms_per_transform'))"
 done

@@ -18,7 +18,7 @@ done
 done
 unset ZL_TUNE_PHASED_MIN_LOG
 cat $out
-python bench.py --no-cpu --no-configs --no-ntt --no-skew --fixed-key -1 2>/dev/null | tail -1 > gpurun_out/bench_g16.json
+python bench.py --full --no-cpu --no-configs --no-ntt --no-skew --fixed-key -1 2>/dev/null | tail -1 > "$(dirname "$out")/bench_g16.json"
 python - <<'PY'
 import json
 d=json.loads(open('gpurun_out/bench_g16.json').read())

@@ -12,7 +12,7 @@ done
 done
 unset PRE_LEGS
 python tools/host_msm.py 24 6 2>&1 | grep host >> $out
-python bench.py --no-cpu --no-configs --no-skew --fixed-key -1 2>/dev/null | tail -1 > gpurun_out/bench_g16.json
+python bench.py --full --no-cpu --no-configs --no-skew --fixed-key -1 2>/dev/null | tail -1 > "$(dirname "$out")/bench_g16.json"
 python - <<'PY' >> $out
 import json
 d=json.loads(open('gpurun_out/bench_g16.json').read())

@@ -17,7 +17,7 @@ for lib in tools/libzl_prev.so openzl_amd/libzl_backend.so; do
   ZL_BACKEND_LIB=$PWD/$lib BATCH=6 python tools/msm_sweep.py 20 22 24 2>&1 | grep "2^" >> $out
   ZL_BACKEND_LIB=$PWD/$lib PRE=20 python tools/msm_sweep.py 20 2>&1 | grep "2^" >> $out
   ZL_BACKEND_LIB=$PWD/$lib CURVE=bn254 ITERS=10 python tools/g16_one.py 4096 2>&1 | grep "prove k=" >> $out
-  ZL_BACKEND_LIB=$PWD/$lib python bench.py --no-cpu --no-configs --no-ntt --groth16-k 0 --fixed-key -1 2>/dev/null | tail -1 | python -c "import json,sys; d=json.loads(sys.stdin.read()); print('bench value ms', d['ms_per_step'], 'skewed ms', d['msm_skewed_scalars']['ms_per_step'], 'pcie', d['pcie_inclusive']['ms_per_msm'])" >> $out
+  ZL_BACKEND_LIB=$PWD/$lib python bench.py --full --no-cpu --no-configs --no-ntt --groth16-k 0 --fixed-key -1 2>/dev/null | tail -1 | python -c "import json,sys; d=json.loads(sys.stdin.read()); print('bench value ms', d['ms_per_step'], 'skewed ms', d['msm_skewed_scalars']['ms_per_step'], 'pcie', d['pcie_inclusive']['ms_per_msm'])" >> $out
 done
 cat $out
 TL_MIN_US=150 bash tools/ab/r4_g16_tl.sh > /dev/null 2>&1

@@ -10,7 +10,7 @@ for rep in 1 2; do
 done
 cat $L
 python -m pytest tests/test_gpu_bench_smoke.py -q -m gpu -x -k "one_rank or sharded_helpers" 2>&1 | tail -15
-python bench.py --no-configs --groth16-k 0 --no-skew --fixed-key -1 --no-cpu > $O/bench_quick.json 2> $O/bench_quick.err; tail -3 $O/bench_quick.err; python - <<'PY'
+python bench.py --full --no-configs --groth16-k 0 --no-skew --fixed-key -1 --no-cpu > $O/bench_quick.json 2> $O/bench_quick.err; tail -3 $O/bench_quick.err; python - <<'PY'
 import json
 d = json.loads([l for l in open("gpurun_out/r5/bench_quick.json") if l.startswith("{")][-1])
 print(json.dumps(d["roofline"]["int_alu"], indent=1)[:2500])

@@ -7,7 +7,7 @@ mkdir -p $O
 cd /tmp && export TMPDIR=/tmp && cd $R
 dbof() { find $1 -name "*.db" | head -1; }
 timeout 1500 python -m pytest tests -m gpu -x -q 2>&1 | tail -5 > $O/gpu_tests.log
-python bench.py > $O/r06_bench_mid.json 2> $O/bench.err
+python bench.py --full > $O/r06_bench_mid.json 2> $O/bench.err
 rocprofv3 --kernel-trace --stats -d $O/p6 -o t -- python tools/msm_sweep.py --g2 20 > $O/g2_sweep.log 2>&1
 python tools/prof_summary.py $(dbof $O/p6) > $O/r06_kernel_stats_g2_2_20.txt
 rocprofv3 --kernel-trace --stats -d $O/p5 -o t -- python tools/g16_one.py > $O/g16_one.log 2>&1

@@ -21,7 +21,7 @@ rocprofv3 --pmc WRITE_SIZE --kernel-trace -d $O/pw3 -o w -f csv -- python tools/
 python tools/pmc_fold.py ntt $(csvof $O/pf3) $(csvof $O/pw3) 24 > $O/r02_pmc_traffic_ntt.json
 cp $O/r02_pmc_traffic.json $O/r02_pmc_traffic_ntt.json profiles/
 # ---- kernel stats ------------------------------------------------------------------------------------------------------------------
-rocprofv3 --kernel-trace --stats -d $O/p1 -o t -- python bench.py > $O/r02_bench_under_rocprof.json 2> $O/bench_under_rocprof.err
+rocprofv3 --kernel-trace --stats -d $O/p1 -o t -- python bench.py --full > $O/r02_bench_under_rocprof.json 2> $O/bench_under_rocprof.err
 python tools/prof_summary.py $(dbof $O/p1) > $O/r02_kernel_stats_bench_default.txt
 # the headline leg alone (no fixed-key / skewed / NTT / Groth16 / CPU legs): every big k_msm_accumulate launch in this trace is one timed or warm-up step of `value`,
 # so the table's big_avg_us is directly comparable with roofline.kernel_ms of the JSON line written by the same command
@@ -38,8 +38,8 @@ python tools/prof_summary.py $(dbof $O/p5) > $O/r02_kernel_stats_groth16.txt
 rocprofv3 --kernel-trace --stats -d $O/p6 -o t -- python tools/msm_sweep.py --g2 20 > $O/g2_sweep.log 2>&1
 python tools/prof_summary.py $(dbof $O/p6) > $O/r02_kernel_stats_g2_2_20.txt
 # ---- bench lines and sweeps --------------------------------------------------------------------------------------------------------
-python bench.py > $O/r02_bench_final.json 2> $O/bench.err
-ZL_DIST_BACKEND=gloo python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29533 bench.py --gpus 2 --steps 2 --warmup 1 --log-n 20 --ntt-log-n 20 --groth16-k 64 > $O/r02_bench_2rank_gloo_1gpu.json 2> $O/bench_2rank.err
+python bench.py --full > $O/r02_bench_final.json 2> $O/bench.err
+ZL_DIST_BACKEND=gloo python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29533 bench.py --full --gpus 2 --steps 2 --warmup 1 --log-n 20 --ntt-log-n 20 --groth16-k 64 > $O/r02_bench_2rank_gloo_1gpu.json 2> $O/bench_2rank.err
 BATCH=6 CS=16,18,19,20 python tools/msm_sweep.py 16 18 20 22 24 > $O/r02_msm_sweep_plain.log 2>&1
 PRE=20,22 BATCH=6 python tools/msm_sweep.py 24 > $O/r02_msm_sweep_fixed_key.log 2>&1
 python tools/msm_sweep.py --g2 16 20 > $O/r02_msm_sweep_g2.log 2>&1

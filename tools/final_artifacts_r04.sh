@@ -22,7 +22,7 @@ python tools/pmc_fold.py ntt $(csvof $O/pf3) $(csvof $O/pw3) 24 > $O/r04_pmc_tra
 mkdir -p profiles; cp $O/r04_pmc_traffic.json $O/r04_pmc_traffic_ntt.json profiles/
 if [ "${1:-all}" = "pmc" ]; then rm -rf $O/pf $O/pw $O/pf2 $O/pw2 $O/pf3 $O/pw3; cat $O/r04_pmc_traffic.json | head -c 600; exit 0; fi
 # ---- kernel stats ------------------------------------------------------------------------------------------------------------------
-rocprofv3 --kernel-trace --stats -d $O/p1 -o t -- python bench.py > $O/r04_bench_under_rocprof.json 2> $O/bench_under_rocprof.err
+rocprofv3 --kernel-trace --stats -d $O/p1 -o t -- python bench.py --full > $O/r04_bench_under_rocprof.json 2> $O/bench_under_rocprof.err
 python tools/prof_summary.py $(dbof $O/p1) > $O/r04_kernel_stats_bench_default.txt
 # the headline leg alone (no fixed-key / skewed / NTT / Groth16 / CPU / configs legs): every big k_msm_accumulate launch in this trace is one timed or warm-up step of `value`,
 # so the table's big_avg_us is directly comparable with roofline.kernel_ms of the JSON line written by the same command
@@ -40,9 +40,9 @@ python tools/timeline.py $(dbof $O/p5) 1500 1 200 > $O/r04_g16_timeline.txt 2>&1
 rocprofv3 --kernel-trace --stats -d $O/p6 -o t -- python tools/msm_sweep.py --g2 20 > $O/g2_sweep.log 2>&1
 python tools/prof_summary.py $(dbof $O/p6) > $O/r04_kernel_stats_g2_2_20.txt
 # ---- bench lines and sweeps --------------------------------------------------------------------------------------------------------
-python bench.py > $O/r04_bench_final.json 2> $O/bench.err
-ZL_DIST_BACKEND=gloo python bench.py --gpus 2 --steps 2 --warmup 1 --log-n 20 --ntt-log-n 20 --groth16-k 64 --config4-log-total 22 --strong-log-total 20 > $O/r04_bench_2rank_gloo_1gpu.json 2> $O/bench_2rank.err
-python bench.py --transport mctx --gpus 4 --mctx-devices 0,0,0,0 --log-n 20 --ntt-log-n 18 --steps 3 --warmup 1 > $O/r04_bench_mctx_4_virtual_ranks.json 2> $O/bench_mctx.err
+python bench.py --full > $O/r04_bench_final.json 2> $O/bench.err
+ZL_DIST_BACKEND=gloo python bench.py --full --gpus 2 --steps 2 --warmup 1 --log-n 20 --ntt-log-n 20 --groth16-k 64 --config4-log-total 22 --strong-log-total 20 > $O/r04_bench_2rank_gloo_1gpu.json 2> $O/bench_2rank.err
+python bench.py --full --transport mctx --gpus 4 --mctx-devices 0,0,0,0 --log-n 20 --ntt-log-n 18 --steps 3 --warmup 1 > $O/r04_bench_mctx_4_virtual_ranks.json 2> $O/bench_mctx.err
 BATCH=6 CS=16,18,19,20 python tools/msm_sweep.py 16 18 20 22 24 > $O/r04_msm_sweep_plain.log 2>&1
 PRE=20,22 BATCH=6 python tools/msm_sweep.py 24 > $O/r04_msm_sweep_fixed_key.log 2>&1
 python tools/msm_sweep.py --g2 16 20 > $O/r04_msm_sweep_g2.log 2>&1
