@@ -111,6 +111,9 @@ def load_library(path: Optional[str] = None):
     L.zl_groth16_prove.argtypes = [vp, C.POINTER(G16PkC), C.POINTER(R1csC), u64p, u64p, u64p, C.POINTER(G16ProofC)]
     L.zl_groth16_prove_sharded.argtypes = [vp, C.POINTER(G16PkC), C.POINTER(G16ShardC), C.c_uint64, u64p, C.c_uint, u64p, u64p, C.POINTER(G16ProofC)]
     L.zl_groth16_last_h.argtypes = [vp, u64p, C.c_size_t]
+    L.zl_r1cs_upload.argtypes = [vp, C.c_int, C.POINTER(R1csC), C.POINTER(C.c_uint64)]
+    L.zl_r1cs_free.argtypes = [vp, C.c_uint64]
+    L.zl_groth16_prove_resident.argtypes = [vp, C.POINTER(G16PkC), C.c_uint64, u64p, C.c_uint, u64p, u64p, C.POINTER(G16ProofC)]
     L.zl_circuit_poseidon_chain.argtypes = [C.c_int, C.c_uint32, u64p, u64p, C.POINTER(vp)]
     L.zl_circuit_free.argtypes = [vp]
     L.zl_circuit_free.restype = None
@@ -180,6 +183,39 @@ def load_library(path: Optional[str] = None):
 def _p64(a: np.ndarray):
     assert a.dtype == np.uint64 and a.flags["C_CONTIGUOUS"], "need contiguous uint64"
     return a.ctypes.data_as(u64p)
+
+
+def _r1cs_struct(r1cs: dict):
+    """R1csC over r1cs's arrays + the contiguous copies it points into (keep them alive for the call)"""
+    cs = R1csC()
+    cs.n_constraints, cs.n_instance, cs.n_witness = r1cs["n_constraints"], r1cs["n_instance"], r1cs["n_witness"]
+    keep = []
+    for m, key in enumerate("ABC"):
+        ptr, col, val = (np.ascontiguousarray(x, dtype=t) for x, t in zip(r1cs[key], (np.uint32, np.uint32, np.uint64)))
+        keep += [ptr, col, val]
+        cs.row_ptr[m] = ptr.ctypes.data_as(C.POINTER(C.c_uint32))
+        cs.col[m] = col.ctypes.data_as(C.POINTER(C.c_uint32))
+        cs.val[m] = val.ctypes.data_as(u64p)
+    return cs, keep
+
+
+def _pk_struct(curve: int, pk: dict):
+    pkc = G16PkC()
+    pkc.curve = curve
+    keep = []
+    for k in ("a_query", "b_g1_query", "h_query", "l_query", "b_g2_query"):
+        setattr(pkc, k, pk[k])
+    for k in ("alpha_g1", "beta_g1", "delta_g1", "beta_g2", "delta_g2"):
+        arr = np.ascontiguousarray(pk[k], dtype=np.uint64)
+        keep.append(arr)
+        setattr(pkc, k, arr.ctypes.data_as(u64p))
+    return pkc, keep
+
+
+def _proof_tuple(curve: int, proof: "G16ProofC"):
+    nq = FQ_LIMBS[curve]
+    return (np.array(proof.a[: 2 * nq], dtype=np.uint64), proof.a_inf, np.array(proof.b[: 4 * nq], dtype=np.uint64), proof.b_inf,
+            np.array(proof.c[: 2 * nq], dtype=np.uint64), proof.c_inf)
 
 
 class Backend:
@@ -348,35 +384,32 @@ class Backend:
         """pk: {'a_query','b_g1_query','h_query','l_query','b_g2_query': handles, 'alpha_g1','beta_g1','delta_g1','beta_g2',
         'delta_g2': uint64 arrays}; r1cs: {'n_constraints','n_instance','n_witness', 'A'/'B'/'C': (ptr u32, col u32, val (nnz,4) u64)}.
         Returns (a, a_inf, b, b_inf, c, c_inf) as canonical affine limb arrays."""
-        cs = R1csC()
-        cs.n_constraints, cs.n_instance, cs.n_witness = r1cs["n_constraints"], r1cs["n_instance"], r1cs["n_witness"]
-        keep = []
-        for m, key in enumerate("ABC"):
-            ptr, col, val = r1cs[key]
-            ptr = np.ascontiguousarray(ptr, dtype=np.uint32)
-            col = np.ascontiguousarray(col, dtype=np.uint32)
-            val = np.ascontiguousarray(val, dtype=np.uint64)
-            keep += [ptr, col, val]
-            cs.row_ptr[m] = ptr.ctypes.data_as(C.POINTER(C.c_uint32))
-            cs.col[m] = col.ctypes.data_as(C.POINTER(C.c_uint32))
-            cs.val[m] = val.ctypes.data_as(u64p)
-        pkc = G16PkC()
-        pkc.curve = curve
-        for k in ("a_query", "b_g1_query", "h_query", "l_query", "b_g2_query"):
-            setattr(pkc, k, pk[k])
-        for k in ("alpha_g1", "beta_g1", "delta_g1", "beta_g2", "delta_g2"):
-            arr = np.ascontiguousarray(pk[k], dtype=np.uint64)
-            keep.append(arr)
-            setattr(pkc, k, arr.ctypes.data_as(u64p))
+        cs, keep = _r1cs_struct(r1cs)
+        pkc, keep_pk = _pk_struct(curve, pk)
         proof = G16ProofC()
         z = np.ascontiguousarray(assignment, dtype=np.uint64)
         self._check(self.L.zl_groth16_prove(self._ctx, C.byref(pkc), C.byref(cs), _p64(z), _p64(np.ascontiguousarray(r)),
                                             _p64(np.ascontiguousarray(s)), C.byref(proof)), "zl_groth16_prove")
-        nq = FQ_LIMBS[curve]
-        a = np.array(proof.a[: 2 * nq], dtype=np.uint64)
-        b = np.array(proof.b[: 4 * nq], dtype=np.uint64)
-        c = np.array(proof.c[: 2 * nq], dtype=np.uint64)
-        return a, proof.a_inf, b, proof.b_inf, c, proof.c_inf
+        return _proof_tuple(curve, proof)
+
+    def r1cs_upload(self, curve: int, r1cs: dict) -> int:
+        """zl_r1cs_upload: the constraint matrices (r1cs as for groth16_prove) resident on this ctx's device; returns the handle"""
+        cs, keep = _r1cs_struct(r1cs)
+        h = C.c_uint64()
+        self._check(self.L.zl_r1cs_upload(self._ctx, curve, C.byref(cs), C.byref(h)), "zl_r1cs_upload")
+        return h.value
+
+    def r1cs_free(self, handle: int):
+        self._check(self.L.zl_r1cs_free(self._ctx, handle), "zl_r1cs_free")
+
+    def groth16_prove_resident(self, curve: int, pk: dict, r1cs_handle: int, assignment: np.ndarray, r: np.ndarray, s: np.ndarray, flags: int = 0):
+        """zl_groth16_prove_resident over matrices from r1cs_upload; flags: ZL_MONT = the assignment is in Montgomery form.  Returns what groth16_prove does."""
+        pkc, keep_pk = _pk_struct(curve, pk)
+        proof = G16ProofC()
+        z = np.ascontiguousarray(assignment, dtype=np.uint64)
+        self._check(self.L.zl_groth16_prove_resident(self._ctx, C.byref(pkc), r1cs_handle, _p64(z), flags, _p64(np.ascontiguousarray(r)),
+                                                     _p64(np.ascontiguousarray(s)), C.byref(proof)), "zl_groth16_prove_resident")
+        return _proof_tuple(curve, proof)
 
     def groth16_last_h(self, n: int) -> np.ndarray:
         out = np.zeros((n, 4), dtype=np.uint64)
