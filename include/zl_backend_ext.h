@@ -131,6 +131,22 @@ int zl_ctx_drop_lanes(zl_ctx* ctx);
 /* e(P, Q) in GT after the final exponentiation: 12 canonical Fq coefficients (BLS12-381: 12 x 6 u64, BN254: 12 x 4 u64) of the
  * polynomial in w, Fq12 = Fq[w]/(w^12 - 2 w^6 + 2) (BLS12-381) or (w^12 - 18 w^6 + 82) (BN254) */
 int zl_pairing(zl_curve_t curve, const uint64_t* p_xy, const uint64_t* q_xy, uint64_t* out12);
+/* prod_i e(P_i, Q_i) after ONE final exponentiation: 12 canonical Fq coefficients, exactly what zl_pairing returns for n = 1
+ * (ark_ec::PairingEngine::product_of_pairings, used by plugins/arkworks/src/pairing.rs:47-90).  ps_xy: n G1 points (x||y canonical),
+ * qs_xy: n G2 points (x.c0||x.c1||y.c0||y.c1); all-zero = infinity, contributes 1.  Miller loops on the device, final exponentiation on the host.
+ * ZL_ENOTCURVE when the Miller product is zero (inputs outside the pairing groups), as zl_pairing. */
+int zl_pairing_product(zl_ctx* ctx, zl_curve_t curve, const uint64_t* ps_xy, const uint64_t* qs_xy, size_t n, uint64_t* out12);
+/* Groth16::verify for `count` proofs against one key in one random linear combination:
+ *   prod_i e(rho_i A_i, B_i) * e(-sum_i rho_i C_i, delta) * e(-sum_i rho_i IC_i, gamma) * e(-(sum_i rho_i) alpha, beta) == 1,
+ * IC_i = gamma_abc[0] + sum_j x_ij gamma_abc[j+1], so the last three pairs are shared by the whole batch (count + 3 Miller loops, one final exponentiation).
+ * rho_i: nonzero 128-bit scalars from SplitMix64(*seed), or from the OS (getrandom) when seed == NULL.  A seed the prover can predict voids soundness:
+ * pass NULL in production.  public_inputs: count x n_public x 4 u64 canonical (without the leading ONE).
+ * *ok = 1 iff every proof verifies.  ok_each (optional, count bytes): per-proof verdicts, each equal to what zl_groth16_verify returns for that proof;
+ * computed from the batch when it accepts, by per-proof products (device Miller loops, host final exponentiations) when it rejects.
+ * A proof with A or B at infinity is invalid, as in zl_groth16_verify.  n_public + 1 != the key's gamma_abc length: ZL_EINVAL.  count == 0: *ok = 1.
+ * rho_i A_i is formed on the device (inside the Miller loops' input kernel), sum_i rho_i C_i is a device MSM, sum_i rho_i x_ij mod r and IC on the host. */
+int zl_groth16_verify_batch(zl_ctx* ctx, const zl_g16_keys* k, const uint64_t* public_inputs, size_t n_public, const zl_g16_proof* proofs,
+                            size_t count, const uint64_t* seed, int* ok, uint8_t* ok_each);
 
 /* ---- wire formats: arkworks 0.3 CanonicalSerialize, compressed (replaces proof_as_bytes / HasSerialization,
  * /root/reference/plugins/arkworks/src/groth16.rs:68-107).  x little-endian, flags in the top two bits of the last byte

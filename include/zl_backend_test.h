@@ -86,6 +86,18 @@ int zl_test_clock_probe_read(zl_ctx* ctx, double* out);
  * the lock-step Miller loops of Groth16::verify (csrc/zl_pairing.h miller_multi), 12 canonical Fq coefficients as zl_pairing. */
 int zl_test_pairing_product(zl_curve_t curve, size_t n, const uint64_t* ps_xy, const uint64_t* qs_xy, uint64_t* out12);
 
+/* The device Miller loops of zl_pairing_product, one value per pair: out = n x 12 canonical Fq coefficients (BLS12-381: 12 x 6 u64, BN254: 12 x 4 u64).
+ * These are Miller values times subfield factors (openzl_amd/csrc/zl_pairing_dev.hip): only their final exponentiation is defined. */
+int zl_test_miller_dev(zl_ctx* ctx, zl_curve_t curve, size_t n, const uint64_t* ps_xy, const uint64_t* qs_xy, uint64_t* out);
+/* The host Engine::final_exp of 12 canonical coefficients (in12 -> out12); ZL_ENOTCURVE for a zero input. */
+int zl_test_final_exp(zl_curve_t curve, const uint64_t* in12, uint64_t* out12);
+/* zl_groth16_verify_batch's random linear combination computed entirely on the host (lock-step Engine::multi_pairing, host scalar multiplications), against
+ * a verifying key given as points: alpha_g1 (x||y), beta_g2 / gamma_g2 / delta_g2 (x.c0||x.c1||y.c0||y.c1), gamma_abc (n_public + 1 G1 points).  Same rho
+ * derivation, rules and outputs as zl_groth16_verify_batch. */
+int zl_test_verify_batch_host(zl_curve_t curve, const uint64_t* alpha_g1, const uint64_t* beta_g2, const uint64_t* gamma_g2, const uint64_t* delta_g2,
+                              const uint64_t* gamma_abc, size_t n_public, const zl_g16_proof* proofs, const uint64_t* public_inputs, size_t count,
+                              const uint64_t* seed, int* ok, uint8_t* ok_each);
+
 #ifdef __cplusplus
 }
 #endif

@@ -6,4 +6,4 @@ bench; it never falls back to a CPU implementation: without the HIP library or w
 """
 from .backend import Backend, MultiBackend, BackendError, load_library, CURVES, ZL_BLS12_381, ZL_BN254, ZL_G1, ZL_G2  # noqa: F401
 from .backend import ZL_MONT, ZL_COSET, ZL_INVERSE, ZL_CHECK  # noqa: F401
-from .backend import Circuit, Groth16Keys, poseidon_permute, pairing  # noqa: F401
+from .backend import Circuit, Groth16Keys, poseidon_permute, pairing, pairing_product  # noqa: F401

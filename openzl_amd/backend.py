@@ -31,7 +31,7 @@ ABI_SYMBOLS = [
     "zl_ctx_create_multi", "zl_mctx_destroy", "zl_mctx_size", "zl_mctx_ctx", "zl_mctx_uses_rccl", "zl_mctx_last_rccl_error", "zl_msm_sharded", "zl_ntt_sharded",
     "zl_point_bytes", "zl_point_to_bytes", "zl_point_from_bytes", "zl_groth16_proof_bytes", "zl_groth16_proof_to_bytes", "zl_groth16_proof_from_bytes",
     "zl_point_bytes_uncompressed", "zl_point_to_bytes_uncompressed", "zl_point_from_bytes_uncompressed", "zl_groth16_keys_to_bytes", "zl_groth16_keys_from_bytes", "zl_groth16_keys_parse",
-    "zl_groth16_vk_to_bytes",
+    "zl_groth16_vk_to_bytes", "zl_pairing_product", "zl_groth16_verify_batch",
 ]
 
 
@@ -131,6 +131,8 @@ def load_library(path: Optional[str] = None):
     L.zl_ctx_drop_lanes.argtypes = [vp]
     L.zl_groth16_verify.argtypes = [vp, u64p, C.c_size_t, C.POINTER(G16ProofC), C.POINTER(C.c_int)]
     L.zl_pairing.argtypes = [C.c_int, u64p, u64p, u64p]
+    L.zl_pairing_product.argtypes = [vp, C.c_int, u64p, u64p, C.c_size_t, u64p]
+    L.zl_groth16_verify_batch.argtypes = [vp, vp, u64p, C.c_size_t, C.POINTER(G16ProofC), C.c_size_t, u64p, C.POINTER(C.c_int), u8p]
     L.zl_point_bytes.argtypes = [C.c_int, C.c_int]
     L.zl_point_bytes.restype = C.c_size_t
     L.zl_point_to_bytes.argtypes = [C.c_int, C.c_int, u64p, C.c_uint8, u8p]
@@ -164,6 +166,10 @@ def load_library(path: Optional[str] = None):
     L.zl_test_fp28_op.argtypes = [vp, C.c_int, u32p, C.c_size_t, u32p]
     L.zl_test_fp28_bn_op.argtypes = [vp, C.c_int, u32p, C.c_size_t, u32p]
     L.zl_test_pairing_product.argtypes = [C.c_int, C.c_size_t, u64p, u64p, u64p]
+    L.zl_test_miller_dev.argtypes = [vp, C.c_int, C.c_size_t, u64p, u64p, u64p]
+    L.zl_test_final_exp.argtypes = [C.c_int, u64p, u64p]
+    L.zl_test_verify_batch_host.argtypes = [C.c_int, u64p, u64p, u64p, u64p, u64p, C.c_size_t, C.POINTER(G16ProofC), u64p, C.c_size_t, u64p,
+                                            C.POINTER(C.c_int), u8p]
     L.zl_test_point_op.argtypes = [vp, C.c_int, C.c_int, C.c_int, u32p, C.c_size_t, u32p]
     L.zl_test_circuit_tweak.argtypes = [vp]
     L.zl_test_fq_mul_rate.argtypes = [vp, C.c_int, C.c_int, C.POINTER(C.c_double)]
@@ -258,6 +264,20 @@ class Backend:
             self.close()
         except Exception:
             pass
+
+    def pairing_product(self, curve: int, ps: np.ndarray, qs: np.ndarray) -> np.ndarray:
+        """prod_i e(P_i, Q_i) (ark's product_of_pairings) as 12 canonical Fq coefficients: device Miller loops, one host final exponentiation.
+        ps: (n, 2 FQ64) G1 points x||y, qs: (n, 4 FQ64) G2 points x.c0||x.c1||y.c0||y.c1, canonical u64 words; all-zero = infinity."""
+        nq = FQ_LIMBS[curve]
+        p = np.ascontiguousarray(np.asarray(ps, dtype=np.uint64).reshape(-1, 2 * nq))
+        q = np.ascontiguousarray(np.asarray(qs, dtype=np.uint64).reshape(-1, 4 * nq))
+        assert p.shape[0] == q.shape[0]
+        n = p.shape[0]
+        if n == 0:
+            p, q = np.zeros((1, 2 * nq), dtype=np.uint64), np.zeros((1, 4 * nq), dtype=np.uint64)
+        out = np.zeros((12, nq), dtype=np.uint64)
+        self._check(self.L.zl_pairing_product(self._ctx, curve, _p64(p), _p64(q), n, _p64(out)), "zl_pairing_product")
+        return out
 
     def describe(self) -> str:
         buf = C.create_string_buffer(512)
@@ -562,7 +582,8 @@ class MultiBackend:
 
 # ---- test-only hooks (include/zl_backend_test.h): device Poseidon KAT, raw-limb field / point access ---------------------------------
 TEST_ABI_SYMBOLS = ["zl_test_poseidon_permute_dev", "zl_test_fp28_op", "zl_test_fp28_bn_op", "zl_test_pairing_product", "zl_test_point_op", "zl_test_circuit_tweak", "zl_test_fq_mul_rate", "zl_test_fr28_op", "zl_test_fr29_op",
-                    "zl_test_poseidon_permute_dev28r", "zl_test_fq_mul_clock", "zl_test_acc_clock", "zl_test_acc_clock_read", "zl_test_clock_probe_launch", "zl_test_clock_probe_read"]
+                    "zl_test_poseidon_permute_dev28r", "zl_test_fq_mul_clock", "zl_test_acc_clock", "zl_test_acc_clock_read", "zl_test_clock_probe_launch", "zl_test_clock_probe_read",
+                    "zl_test_miller_dev", "zl_test_final_exp", "zl_test_verify_batch_host"]
 
 
 def _p32(a: np.ndarray):
@@ -614,6 +635,56 @@ def hook_pairing_product(curve: int, ps: np.ndarray, qs: np.ndarray) -> np.ndarr
     if rc:
         raise BackendError(rc, "zl_test_pairing_product")
     return out
+
+
+def hook_miller_dev(be: "Backend", curve: int, ps: np.ndarray, qs: np.ndarray) -> np.ndarray:
+    """the raw device Miller value of every pair (zl_test_miller_dev): ps (n, 2 FQ64) / qs (n, 4 FQ64) -> (n, 12, FQ64) canonical words"""
+    p = np.ascontiguousarray(ps, dtype=np.uint64)
+    q = np.ascontiguousarray(qs, dtype=np.uint64)
+    out = np.zeros((p.shape[0], 12, FQ_LIMBS[curve]), dtype=np.uint64)
+    be._check(be.L.zl_test_miller_dev(be._ctx, curve, p.shape[0], _p64(p), _p64(q), _p64(out)), "zl_test_miller_dev")
+    return out
+
+
+def hook_final_exp(curve: int, f: np.ndarray) -> np.ndarray:
+    """the host final exponentiation of 12 canonical coefficients (zl_test_final_exp)"""
+    a = np.ascontiguousarray(f, dtype=np.uint64)
+    out = np.zeros((12, FQ_LIMBS[curve]), dtype=np.uint64)
+    rc = load_library().zl_test_final_exp(curve, _p64(a), _p64(out))
+    if rc:
+        raise BackendError(rc, "zl_test_final_exp")
+    return out
+
+
+def _proofs_array(proofs):
+    arr = (G16ProofC * max(1, len(proofs)))()
+    for i, pr in enumerate(proofs):
+        arr[i] = _proof_struct(pr)
+    return arr
+
+
+def _pubs_of(public_inputs, count: int, n_public: int) -> np.ndarray:
+    pub = np.ascontiguousarray(np.asarray(public_inputs, dtype=np.uint64).reshape(-1))
+    assert pub.size == count * n_public * 4, "public_inputs: count x n_public x 4 words"
+    return pub if pub.size else np.zeros(4, dtype=np.uint64)
+
+
+def hook_verify_batch_host(curve: int, vk: dict, proofs, public_inputs, n_public: int, seed: Optional[int] = 0):
+    """zl_test_verify_batch_host: the batch verifier's random linear combination on the host.  vk: alpha_g1, beta_g2, gamma_g2, delta_g2 (canonical
+    words) and gamma_abc ((n_public + 1) G1 points); proofs: (a, a_inf, b, b_inf, c, c_inf) tuples.  Returns (ok, per-proof verdicts)."""
+    n = len(proofs)
+    arr = _proofs_array(proofs)
+    pub = _pubs_of(public_inputs, n, n_public)
+    vks = {k: np.ascontiguousarray(vk[k], dtype=np.uint64) for k in ("alpha_g1", "beta_g2", "gamma_g2", "delta_g2", "gamma_abc")}
+    sd = np.array([seed or 0], dtype=np.uint64)
+    ok = C.c_int(0)
+    each = np.zeros(max(1, n), dtype=np.uint8)
+    rc = load_library().zl_test_verify_batch_host(curve, _p64(vks["alpha_g1"]), _p64(vks["beta_g2"]), _p64(vks["gamma_g2"]), _p64(vks["delta_g2"]),
+                                                  _p64(vks["gamma_abc"]), n_public, arr, _p64(pub), n, _p64(sd) if seed is not None else None,
+                                                  C.byref(ok), each.ctypes.data_as(u8p))
+    if rc:
+        raise BackendError(rc, "zl_test_verify_batch_host")
+    return bool(ok.value), each[:n].astype(bool)
 
 
 def hook_point_op(be: Optional["Backend"], group: int, hot: bool, op: int, pq: np.ndarray) -> np.ndarray:
@@ -692,6 +763,11 @@ def poseidon_permute(curve: int, state: np.ndarray) -> np.ndarray:
     if rc:
         raise BackendError(rc, "zl_poseidon_permute")
     return st
+
+
+def pairing_product(backend: "Backend", curve: int, ps: np.ndarray, qs: np.ndarray) -> np.ndarray:
+    """prod_i e(P_i, Q_i) with the Miller loops on backend's GPU (Backend.pairing_product)"""
+    return backend.pairing_product(curve, ps, qs)
 
 
 def pairing(curve: int, p_xy: np.ndarray, q_xy: np.ndarray) -> np.ndarray:
@@ -930,6 +1006,27 @@ class Groth16Keys:
         ok = C.c_int(0)
         self.backend._check(self.L.zl_groth16_verify(self._k, _p64(pub), pub.shape[0], C.byref(pc), C.byref(ok)), "zl_groth16_verify")
         return bool(ok.value)
+
+    def verify_batch(self, proofs, public_inputs, seed: Optional[int] = None, each: bool = False):
+        """Groth16::verify of many proofs in one random linear combination (zl_groth16_verify_batch): device Miller loops and MSM, one host final
+        exponentiation.  public_inputs: (count, n_public, 4) canonical words (or anything that reshapes to it); seed=None draws the combination from
+        the OS (what a verifier must do); an int makes it reproducible (tests).  Returns ok, or (ok, per-proof verdicts) with each=True."""
+        n = len(proofs)
+        pub_arr = np.asarray(public_inputs, dtype=np.uint64)
+        if pub_arr.ndim == 3:
+            n_public = pub_arr.shape[1]
+        elif n:
+            n_public = pub_arr.size // (4 * n)
+        else:
+            n_public = self.circuit.shape[1] - 1
+        arr = _proofs_array(proofs)
+        pub = _pubs_of(pub_arr, n, n_public)
+        sd = np.array([seed or 0], dtype=np.uint64)
+        ok = C.c_int(0)
+        ev = np.zeros(max(1, n), dtype=np.uint8)
+        self.backend._check(self.L.zl_groth16_verify_batch(self.backend._ctx, self._k, _p64(pub), n_public, arr, n, _p64(sd) if seed is not None else None,
+                                                           C.byref(ok), ev.ctypes.data_as(u8p) if each else None), "zl_groth16_verify_batch")
+        return (bool(ok.value), ev[:n].astype(bool)) if each else bool(ok.value)
 
     def close(self):
         if self._k:

@@ -106,7 +106,8 @@ def _compile_stripped(name: str, src: str, defs: list[str], obj: str, verbose: b
 
 def _units():
     units = [("zl_capi", "zl_capi.hip", []), ("zl_ntt", "zl_ntt.hip", ["-DZL_INLINE_MUL"]), ("zl_groth16", "zl_groth16.hip", []), ("zl_host", "zl_host.hip", []), ("zl_testhooks", "zl_testhooks.hip", []), ("zl_multi", "zl_multi.hip", []),
-             ("zl_msm_sort", "zl_msm_sort.hip", [])]  # the curve-independent sort kernels of the MSM: once, not per group
+             ("zl_msm_sort", "zl_msm_sort.hip", []),  # the curve-independent sort kernels of the MSM: once, not per group
+             ("zl_pairing_dev_bls", "zl_pairing_dev.hip", ["-DZL_PAIR_CURVE=1"]), ("zl_pairing_dev_bn", "zl_pairing_dev.hip", ["-DZL_PAIR_CURVE=2"])]  # device Miller loops, once per curve
     for g in GROUPS:
         # Fq2 accumulators: 1 wave/SIMD register budget avoids scratch spills
         extra = ["-DZL_ACC_WAVES=1"] if g.endswith("G2") else []

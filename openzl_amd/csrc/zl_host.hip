@@ -8,7 +8,9 @@
 #include <new>
 #include <atomic>
 #include <thread>
+#include <sys/random.h>
 #include "zl_host.h"
+#include "zl_pairing_dev.h"
 #include "zl_serialize.h"
 
 // zl_groth16.hip: the prover with the assignment in the compiler's two pieces (instance block, witness block; Montgomery limbs)
@@ -980,6 +982,295 @@ int zl_test_pairing_product(zl_curve_t curve, size_t n, const uint64_t* ps_xy, c
     if (curve == ZL_BLS12_381) pairing::BlsEngine::store(out12, pairing::BlsEngine::multi_pairing(ps, qs, &degenerate));
     else pairing::BnEngine::store(out12, pairing::BnEngine::multi_pairing(ps, qs, &degenerate));
     return degenerate ? ZL_ENOTCURVE : ZL_OK;
+}
+}  // extern "C"
+
+// ---- device Miller loops + host final exponentiation (zl_pairing_dev.hip) --------------------------------------------------------------------------
+namespace {
+template <class E> struct PairDev;
+template <> struct PairDev<Bls12_381> {
+    static int product(zl_ctx* c, const uint64_t* p, const uint64_t* q, const uint32_t* s, size_t n, uint32_t* o) { return pairing_dev::miller_product_bls(c, p, q, s, n, o); }
+    static int groups(zl_ctx* c, const uint64_t* p, const uint64_t* q, size_t n, size_t g, uint32_t* o) { return pairing_dev::miller_groups_bls(c, p, q, nullptr, n, g, o); }
+};
+template <> struct PairDev<Bn254> {
+    static int product(zl_ctx* c, const uint64_t* p, const uint64_t* q, const uint32_t* s, size_t n, uint32_t* o) { return pairing_dev::miller_product_bn(c, p, q, s, n, o); }
+    static int groups(zl_ctx* c, const uint64_t* p, const uint64_t* q, size_t n, size_t g, uint32_t* o) { return pairing_dev::miller_groups_bn(c, p, q, nullptr, n, g, o); }
+};
+template <class E> using EngOf = pairing::Engine<typename E::G1::FqP, typename E::PairingP>;
+
+template <class E>
+int pairing_product_t(zl_ctx* ctx, const uint64_t* ps, const uint64_t* qs, size_t n, uint64_t* out12) {
+    using Eng = EngOf<E>;
+    typename Eng::Fq12 f;
+    const int rc = PairDev<E>::product(ctx, ps, qs, nullptr, n, reinterpret_cast<uint32_t*>(f.c));
+    if (rc) return rc;
+    bool degenerate = false;
+    Eng::store(out12, Eng::final_exp(f, &degenerate));
+    return degenerate ? ZL_ENOTCURVE : ZL_OK;
+}
+
+// The verifying key of a batch, canonical affine points (all-zero = infinity)
+struct BatchVk {
+    const uint64_t *alpha_g1, *beta_g2, *gamma_g2, *delta_g2, *gamma_abc;
+    size_t n_abc;
+};
+
+// Groth16::verify of `count` proofs in one random linear combination (include/zl_backend_ext.h zl_groth16_verify_batch).  ctx == NULL: everything on the
+// host (scalar multiplications, Engine::multi_pairing; the test hook); otherwise rho_i A_i is formed inside the device Miller loops, sum rho_i C_i is a device
+// MSM, the Miller loops run on the device and only the final exponentiation(s) on the host.
+template <class E>
+int verify_batch_t(zl_ctx* ctx, const BatchVk& vk, const uint64_t* pubs, size_t n_public, const zl_g16_proof* proofs, size_t count, const uint64_t* seed,
+                   int* ok, uint8_t* ok_each) {
+    using G1 = typename E::G1;
+    using F1 = typename G1::F;
+    using FrP = typename E::FrP;
+    using Fr = Fp<FrP>;
+    using Eng = EngOf<E>;
+    constexpr size_t q1 = 2 * G1::FQ64, q2 = 2 * q1;
+    constexpr int W1 = FieldIO<F1>::WORDS;
+    if (!ok || (count && !proofs) || (count && n_public && !pubs)) return ZL_EINVAL;
+    if (n_public + 1 != vk.n_abc) return ZL_EINVAL;
+    if (count == 0) {
+        *ok = 1;
+        return ZL_OK;
+    }
+    // rho_i: nonzero 128-bit scalars
+    std::vector<uint64_t> rho(2 * count);
+    if (seed) {
+        SplitMix64 rng(*seed);
+        for (size_t i = 0; i < count; i++)
+            do { rho[2 * i] = rng.next(); rho[2 * i + 1] = rng.next(); } while (!rho[2 * i] && !rho[2 * i + 1]);
+    } else {
+        unsigned char* b = reinterpret_cast<unsigned char*>(rho.data());
+        size_t got = 0;
+        while (got < rho.size() * 8) {
+            const ssize_t r = getrandom(b + got, rho.size() * 8 - got, 0);
+            if (r < 0) {
+                if (errno == EINTR) continue;
+                return ZL_EINVAL;
+            }
+            got += (size_t)r;
+        }
+        for (size_t i = 0; i < count; i++)
+            if (!rho[2 * i] && !rho[2 * i + 1]) rho[2 * i] = 1;
+    }
+    auto load = [&](const uint64_t* xy) {
+        const uint32_t* w = reinterpret_cast<const uint32_t*>(xy);
+        uint32_t acc = 0;
+        for (int k = 0; k < 2 * W1; k++) acc |= w[k];
+        if (!acc) return XYZZ<F1>::inf();
+        return XYZZ<F1>::from_affine(Affine<F1>{FieldIO<F1>::load_canon(w), FieldIO<F1>::load_canon(w + W1)});
+    };
+    auto store = [&](XYZZ<F1> p, bool negate, uint64_t* out) {  // canonical affine of (+/-) p, all-zero for infinity
+        for (size_t k = 0; k < q1; k++) out[k] = 0;
+        if (p.is_inf()) return;
+        if (negate) zl::neg_inplace(p);
+        const Affine<F1> a = zl::to_affine(p);
+        uint32_t* w = reinterpret_cast<uint32_t*>(out);
+        FieldIO<F1>::store_canon(w, a.x);
+        FieldIO<F1>::store_canon(w + W1, a.y);
+    };
+    auto words = [](const Fr& canon, uint32_t* k) { memcpy(k, canon.l, 32); };
+    auto to_fr = [](const uint64_t* w) { Fr c; memcpy(c.l, w, 32); return zl::to_mont(c); };
+    // IC of a combination: sum_j e_j gamma_abc[j] (e_0 multiplies the constant ONE)
+    auto ic_of = [&](const std::vector<Fr>& e) {
+        XYZZ<F1> acc = XYZZ<F1>::inf();
+        for (size_t j = 0; j < vk.n_abc; j++) {
+            uint32_t k[8];
+            words(zl::from_mont(e[j]), k);
+            zl::add_full(acc, zl::mul_scalar(load(vk.gamma_abc + j * q1), k));
+        }
+        return acc;
+    };
+    bool any_inf = false;
+    for (size_t i = 0; i < count; i++) any_inf = any_inf || proofs[i].a_inf || proofs[i].b_inf;
+    // e_j = sum_i rho_i x_ij (x_i0 = 1), sum_i rho_i C_i
+    std::vector<Fr> e(vk.n_abc, Fr::zero()), rf(count);
+    for (size_t i = 0; i < count; i++) {
+        const uint64_t rw[4] = {rho[2 * i], rho[2 * i + 1], 0, 0};
+        rf[i] = to_fr(rw);
+        e[0] = zl::add(e[0], rf[i]);
+        for (size_t j = 0; j < n_public; j++) e[j + 1] = zl::add(e[j + 1], zl::mul(rf[i], to_fr(pubs + (i * n_public + j) * 4)));
+    }
+    XYZZ<F1> sum_c = XYZZ<F1>::inf();
+    if (ctx) {
+        std::vector<uint64_t> cs(count * q1), sc(count * 4, 0);
+        for (size_t i = 0; i < count; i++) {
+            if (!proofs[i].c_inf) memcpy(&cs[i * q1], proofs[i].c, q1 * 8);
+            sc[4 * i] = rho[2 * i];
+            sc[4 * i + 1] = rho[2 * i + 1];
+        }
+        uint64_t h = 0;
+        int rc = zl_bases_upload(ctx, E::curve, ZL_G1, cs.data(), count, 0, -1, 0, &h);
+        std::vector<uint64_t> sxy(q1);
+        uint8_t sinf = 0;
+        if (!rc) rc = zl_msm(ctx, h, 0, sc.data(), count, sxy.data(), &sinf);
+        if (h) (void)zl_bases_free(ctx, h);
+        if (rc) return rc;
+        if (!sinf) sum_c = load(sxy.data());
+    } else {
+        for (size_t i = 0; i < count; i++) {
+            uint32_t k[8] = {0};
+            memcpy(k, &rho[2 * i], 16);
+            zl::add_full(sum_c, zl::mul_scalar(load(proofs[i].c), k));
+        }
+    }
+    // the count + 3 pairs: (rho_i A_i, B_i), (-sum rho_i C_i, delta), (-IC, gamma), (-(sum rho_i) alpha, beta)
+    const size_t np = count + 3;
+    std::vector<uint64_t> ps(np * q1, 0), qs(np * q2, 0);
+    std::vector<uint32_t> sc32;
+    for (size_t i = 0; i < count; i++) {
+        memcpy(&qs[i * q2], proofs[i].b, q2 * 8);
+        if (ctx) {
+            memcpy(&ps[i * q1], proofs[i].a, q1 * 8);
+        } else {
+            uint32_t k[8] = {0};
+            memcpy(k, &rho[2 * i], 16);
+            store(zl::mul_scalar(load(proofs[i].a), k), false, &ps[i * q1]);
+        }
+    }
+    store(sum_c, true, &ps[count * q1]);
+    store(ic_of(e), true, &ps[(count + 1) * q1]);
+    {
+        uint32_t k[8];
+        words(zl::from_mont(e[0]), k);
+        store(zl::mul_scalar(load(vk.alpha_g1), k), true, &ps[(count + 2) * q1]);
+    }
+    memcpy(&qs[count * q2], vk.delta_g2, q2 * 8);
+    memcpy(&qs[(count + 1) * q2], vk.gamma_g2, q2 * 8);
+    memcpy(&qs[(count + 2) * q2], vk.beta_g2, q2 * 8);
+    typename Eng::Fq12 gt;
+    if (ctx) {
+        sc32.assign(np * 4, 0);
+        for (size_t i = 0; i < np; i++) {
+            if (i < count) memcpy(&sc32[4 * i], &rho[2 * i], 16);
+            else sc32[4 * i] = 1;
+        }
+        typename Eng::Fq12 f;
+        const int rc = PairDev<E>::product(ctx, ps.data(), qs.data(), sc32.data(), np, reinterpret_cast<uint32_t*>(f.c));
+        if (rc) return rc;
+        gt = Eng::final_exp(f);
+    } else {
+        std::vector<const uint64_t*> pp(np), qq(np);
+        for (size_t i = 0; i < np; i++) { pp[i] = &ps[i * q1]; qq[i] = &qs[i * q2]; }
+        gt = Eng::multi_pairing(pp, qq);
+    }
+    *ok = !any_inf && Eng::eq(gt, Eng::one()) ? 1 : 0;
+    if (!ok_each) return ZL_OK;
+    if (*ok) {
+        memset(ok_each, 1, count);
+        return ZL_OK;
+    }
+    // rejected: one product of four pairings per proof, e(A, B) e(-C, delta) e(-IC_i, gamma) e(-alpha, beta), as zl_groth16_verify
+    std::vector<uint64_t> n_alpha(q1);
+    store(load(vk.alpha_g1), true, n_alpha.data());
+    const size_t chunk = ctx ? pairing_dev::MAX_PAIRS / 4 : 1;
+    std::vector<typename Eng::Fq12> fs(chunk);
+    for (size_t first = 0; first < count; first += chunk) {
+        const size_t m = std::min(chunk, count - first);
+        // pair j of proof i sits at index j * m + i (group i of the device launch)
+        std::vector<uint64_t> pp(4 * m * q1, 0), qq(4 * m * q2, 0);
+        for (size_t i = 0; i < m; i++) {
+            const zl_g16_proof& pr = proofs[first + i];
+            std::vector<Fr> ei(vk.n_abc);
+            ei[0] = Fr::one();
+            for (size_t j = 0; j < n_public; j++) ei[j + 1] = to_fr(pubs + ((first + i) * n_public + j) * 4);
+            memcpy(&pp[i * q1], pr.a, q1 * 8);
+            memcpy(&qq[i * q2], pr.b, q2 * 8);
+            store(load(pr.c), true, &pp[(m + i) * q1]);
+            memcpy(&qq[(m + i) * q2], vk.delta_g2, q2 * 8);
+            store(ic_of(ei), true, &pp[(2 * m + i) * q1]);
+            memcpy(&qq[(2 * m + i) * q2], vk.gamma_g2, q2 * 8);
+            memcpy(&pp[(3 * m + i) * q1], n_alpha.data(), q1 * 8);
+            memcpy(&qq[(3 * m + i) * q2], vk.beta_g2, q2 * 8);
+        }
+        if (ctx) {
+            const int rc = PairDev<E>::groups(ctx, pp.data(), qq.data(), 4 * m, m, reinterpret_cast<uint32_t*>(fs.data()));
+            if (rc) return rc;
+        }
+        // the final exponentiations (and, for the host hook, the Miller loops) of the proofs of this chunk on a few host threads
+        std::atomic<size_t> next{0};
+        auto work = [&]() {
+            for (size_t i; (i = next.fetch_add(1)) < m;) {
+                typename Eng::Fq12 g;
+                if (ctx) {
+                    g = Eng::final_exp(fs[i]);
+                } else {
+                    std::vector<const uint64_t*> a(4), b(4);
+                    for (int j = 0; j < 4; j++) { a[j] = &pp[(j * m + i) * q1]; b[j] = &qq[(j * m + i) * q2]; }
+                    g = Eng::multi_pairing(a, b);
+                }
+                const zl_g16_proof& pr = proofs[first + i];
+                ok_each[first + i] = !pr.a_inf && !pr.b_inf && Eng::eq(g, Eng::one()) ? 1 : 0;
+            }
+        };
+        const size_t nt = std::min<size_t>(m, std::max(1u, std::min(16u, std::thread::hardware_concurrency())));
+        std::vector<std::thread> th;
+        for (size_t t = 1; t < nt; t++) th.emplace_back(work);
+        work();
+        for (auto& t : th) t.join();
+    }
+    return ZL_OK;
+}
+}  // namespace
+
+extern "C" {
+int zl_pairing_product(zl_ctx* ctx, zl_curve_t curve, const uint64_t* ps_xy, const uint64_t* qs_xy, size_t n, uint64_t* out12) {
+    if (!ctx || !out12 || (n && (!ps_xy || !qs_xy))) return ZL_EINVAL;
+    if (curve == ZL_BLS12_381) return pairing_product_t<Bls12_381>(ctx, ps_xy, qs_xy, n, out12);
+    if (curve == ZL_BN254) return pairing_product_t<Bn254>(ctx, ps_xy, qs_xy, n, out12);
+    return ZL_EINVAL;
+}
+int zl_groth16_verify_batch(zl_ctx* ctx, const zl_g16_keys* k, const uint64_t* public_inputs, size_t n_public, const zl_g16_proof* proofs, size_t count,
+                            const uint64_t* seed, int* ok, uint8_t* ok_each) {
+    if (!ctx || !k) return ZL_EINVAL;
+    auto vk_of = [](const auto& v, size_t q1) { return BatchVk{v.alpha_g1.data(), v.beta_g2.data(), v.gamma_g2.data(), v.delta_g2.data(), v.gamma_abc_g1.data(), v.gamma_abc_g1.size() / q1}; };
+    if (k->curve == ZL_BLS12_381) return verify_batch_t<Bls12_381>(ctx, vk_of(k->vk_bls, 12), public_inputs, n_public, proofs, count, seed, ok, ok_each);
+    return verify_batch_t<Bn254>(ctx, vk_of(k->vk_bn, 8), public_inputs, n_public, proofs, count, seed, ok, ok_each);
+}
+// test hooks (include/zl_backend_test.h)
+int zl_test_verify_batch_host(zl_curve_t curve, const uint64_t* alpha_g1, const uint64_t* beta_g2, const uint64_t* gamma_g2, const uint64_t* delta_g2,
+                              const uint64_t* gamma_abc, size_t n_public, const zl_g16_proof* proofs, const uint64_t* public_inputs, size_t count,
+                              const uint64_t* seed, int* ok, uint8_t* ok_each) {
+    if (!alpha_g1 || !beta_g2 || !gamma_g2 || !delta_g2 || !gamma_abc) return ZL_EINVAL;
+    const BatchVk vk{alpha_g1, beta_g2, gamma_g2, delta_g2, gamma_abc, n_public + 1};
+    if (curve == ZL_BLS12_381) return verify_batch_t<Bls12_381>(nullptr, vk, public_inputs, n_public, proofs, count, seed, ok, ok_each);
+    if (curve == ZL_BN254) return verify_batch_t<Bn254>(nullptr, vk, public_inputs, n_public, proofs, count, seed, ok, ok_each);
+    return ZL_EINVAL;
+}
+int zl_test_miller_dev(zl_ctx* ctx, zl_curve_t curve, size_t n, const uint64_t* ps_xy, const uint64_t* qs_xy, uint64_t* out) {
+    if (!ctx || (n && (!ps_xy || !qs_xy || !out)) || (curve != ZL_BLS12_381 && curve != ZL_BN254)) return ZL_EINVAL;
+    const size_t fw = curve == ZL_BLS12_381 ? 6 : 4;  // u64 words per Fq
+    for (size_t first = 0; first < n; first += pairing_dev::MAX_PAIRS) {
+        const size_t m = std::min(n - first, pairing_dev::MAX_PAIRS);
+        uint64_t* o = out + first * 12 * fw;
+        const uint64_t *p = ps_xy + first * 2 * fw, *q = qs_xy + first * 4 * fw;
+        const int rc = curve == ZL_BLS12_381 ? PairDev<Bls12_381>::groups(ctx, p, q, m, m, reinterpret_cast<uint32_t*>(o))
+                                             : PairDev<Bn254>::groups(ctx, p, q, m, m, reinterpret_cast<uint32_t*>(o));
+        if (rc) return rc;
+        for (size_t i = 0; i < m * 12; i++) {  // Montgomery -> canonical
+            if (curve == ZL_BLS12_381) { Fp<BLS12_381_Fq> c; memcpy(c.l, o + i * fw, 48); c = zl::from_mont(c); memcpy(o + i * fw, c.l, 48); }
+            else { Fp<BN254_Fq> c; memcpy(c.l, o + i * fw, 32); c = zl::from_mont(c); memcpy(o + i * fw, c.l, 32); }
+        }
+    }
+    return ZL_OK;
+}
+int zl_test_final_exp(zl_curve_t curve, const uint64_t* in12, uint64_t* out12) {
+    if (!in12 || !out12) return ZL_EINVAL;
+    auto run = [&](auto eng) {
+        using Eng = decltype(eng);
+        typename Eng::Fq12 f;
+        for (int i = 0; i < 12; i++) {
+            memcpy(f.c[i].l, reinterpret_cast<const unsigned char*>(in12) + i * sizeof(f.c[i]), sizeof(f.c[i]));
+            f.c[i] = zl::to_mont(f.c[i]);
+        }
+        bool degenerate = false;
+        Eng::store(out12, Eng::final_exp(f, &degenerate));
+        return degenerate ? ZL_ENOTCURVE : ZL_OK;
+    };
+    if (curve == ZL_BLS12_381) return run(pairing::BlsEngine{});
+    if (curve == ZL_BN254) return run(pairing::BnEngine{});
+    return ZL_EINVAL;
 }
 // Groth16::verify: public_inputs = n x 4 u64 canonical (without the leading ONE); *ok = 1 / 0
 int zl_groth16_verify(const zl_g16_keys* k, const uint64_t* public_inputs, size_t n, const zl_g16_proof* proof, int* ok) {

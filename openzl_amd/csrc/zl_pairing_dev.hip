@@ -1,0 +1,371 @@
+// zl_pairing_dev.hip -- Miller loops of many pairings on the device (the product side of PairingEngine::product_of_pairings, which the plugin's
+// PairingEngineExt helpers and Groth16 verification call: the reference plugin's plugins/arkworks/src/pairing.rs:47-90, groth16.rs:459-466).
+// Compiled once per curve (ZL_PAIR_CURVE = 1 BLS12-381, 2 BN254); the host final exponentiation (zl_pairing.h Engine::final_exp) turns the
+// product into the pairing (zl_host.hip: zl_pairing_product, zl_groth16_verify_batch).
+//
+// Same Fq12 as zl_pairing.h: Fq[w]/(w^12 - M6 w^6 + M0_NEG), 12 Fq coefficients, the same loop schedule (LOOP_BITS / loop_bit, BN_TAIL lines) and the same
+// line placement (put_fq2; TWIST_DIV: BLS12-381 M-type twist).  Differences to the host loop, all annihilated by the final exponentiation (q^12 - 1)/r:
+//   - G2 walks in homogeneous projective coordinates (X : Y : Z) on the twist, no inversion.  The tangent line at R is scaled by 2 Y Z^2 (an Fq2 factor),
+//     the line through R and an affine Q by lambda = xQ Z - X (Fq2):
+//         tangent:  c0 = 2 Y^2 Z - 3 X^3,     cx = 3 X^2 Z,   cy = -2 Y Z^2
+//         chord:    c0 = yQ lambda - theta xQ, cx = theta,     cy = -lambda        (theta = yQ Z - Y)
+//     and the line is c0 + cx xP + cy yP placed like zl_pairing.h's  (y1' - m' x1') + (m' xP) + (-yP)  terms.  Fq2* has order dividing q^6 - 1.
+//   - P may be given in XYZZ coordinates (x = X/ZZ, y = Y/ZZZ: the batch verifier's rho_i A_i): c0 ZZ ZZZ + cx X ZZZ + cy Y ZZ is the line times the Fq factor ZZ ZZZ.
+// The Miller values therefore differ from the host's before the final exponentiation; after it they are equal (tests/test_gpu_pairing_product.py).
+//
+// Kernels:
+//   k_pd_prep   one lane per pair: canonical inputs -> Montgomery, the optional 128-bit scalar multiplication of P (double-and-add in XYZZ), infinity flags.
+//   k_pd_lines  one lane per pair walks R on the twist and writes its NLINES line records (six Fq coefficients each, already multiplied by xP / yP) to HBM,
+//               laid out [step][pair][6][N words] so that a wave writes one contiguous block per step.
+//   k_pd_acc    16-lane groups (12 active lanes, lane k owns coefficient w^k of the accumulator f; operands exchanged through LDS): per step
+//               f <- f^2 prod_{pairs of the group} l_i -- one shared squaring per group and step.  Pair p belongs to group p % ngroups.
+//   k_pd_prod   product of the group accumulators, 16 at a time per group of lanes, until one is left.
+// Plain Fp<Fq> (32-bit limbs, fully reduced): no lazily reduced formulas, so nothing new for zl_bounds.h.  Every loop bound is a compile-time constant or a
+// launch argument: off-curve / non-subgroup inputs give a wrong value (or a zero product, which the host reports as ZL_ENOTCURVE), never a different path.
+#include <string.h>
+#include <vector>
+#include "zl_ctx.h"
+#include "zl_pairing.h"
+#include "zl_pairing_dev.h"
+
+#if ZL_PAIR_CURVE == 1
+#define ZL_PD_FQ BLS12_381_Fq
+#define ZL_PD_PP BLS12_381_Pairing
+#define ZL_PD_SUFFIX(x) x##_bls
+#else
+#define ZL_PD_FQ BN254_Fq
+#define ZL_PD_PP BN254_Pairing
+#define ZL_PD_SUFFIX(x) x##_bn
+#endif
+
+namespace {
+using FqP = ZL_PD_FQ;
+using PP = ZL_PD_PP;
+using F = Fp<FqP>;
+using F2 = Fp2<FqP>;
+constexpr int NW = FqP::N;  // u32 words per Fq
+constexpr int nadd() {
+    int c = 0;
+    for (int i = PP::LOOP_BITS - 2; i >= 0; i--) c += PP::loop_bit(i) ? 1 : 0;
+    return c;
+}
+constexpr int NLINES = PP::LOOP_BITS - 1 + nadd() + (PP::BN_TAIL ? 2 : 0);  // 68 (BLS12-381), 64 + 21 + 2 = 87 (BN254)
+// the three Fq2 terms of a line and where put_fq2 places them (coefficients k and k + 6)
+constexpr int K0 = PP::TWIST_DIV ? 0 : 3, KX = PP::TWIST_DIV ? 2 : 1, KY = PP::TWIST_DIV ? 3 : 0;
+__host__ __device__ constexpr int line_pos(int m) { return (m & 1 ? 6 : 0) + (m < 2 ? K0 : m < 4 ? KX : KY); }
+constexpr int M_ONE = K0 == 0 ? 0 : KX == 0 ? 2 : 4;  // the record slot of coefficient w^0 (where a line equal to 1 puts its 1)
+
+struct Consts {
+    F sh, m6, nm0, m6sq_m0, nm6m0;  // ISHIFT, M6, -M0_NEG, M6^2 - M0_NEG, -M6 M0_NEG (Montgomery)
+    F2 g2, g3;                      // Frobenius constants of the BN tail (zl_pairing.h make_frob_consts)
+};
+
+__device__ __forceinline__ F2 f2s(const F2& a, const F& s) { return F2{zl::mul(a.c0, s), zl::mul(a.c1, s)}; }
+__device__ __forceinline__ F2 conj(const F2& a) { return F2{a.c0, zl::neg(a.c1)}; }
+
+// one line record: c0 zP + cx xP + cy yP placed by put_fq2; `one` replaces it by 1 (a pair with a point at infinity, or padding)
+__device__ __forceinline__ void emit(F* rec, const F2& c0, const F2& cx, const F2& cy, const F& xP, const F& yP, const F& zP, bool one, const Consts& K) {
+    const F2 a = f2s(c0, zP), b = f2s(cx, xP), c = f2s(cy, yP);
+    F v[6] = {zl::sub(a.c0, zl::mul(K.sh, a.c1)), a.c1, zl::sub(b.c0, zl::mul(K.sh, b.c1)), b.c1, zl::sub(c.c0, zl::mul(K.sh, c.c1)), c.c1};
+#pragma unroll
+    for (int m = 0; m < 6; m++) rec[m] = one ? (m == M_ONE ? F::one() : F::zero()) : v[m];
+}
+// R <- 2R, line at the tangent (scaled by 2 Y Z^2)
+__device__ __forceinline__ void dbl_step(F2& X, F2& Y, F2& Z, F2& c0, F2& cx, F2& cy) {
+    const F2 xx = zl::sqr(X), yy = zl::sqr(Y);
+    const F2 w = zl::add(zl::dbl(xx), xx);            // 3 X^2
+    const F2 s = zl::mul(Y, Z);                       // S = Y Z
+    c0 = zl::sub(zl::dbl(zl::mul(yy, Z)), zl::mul(w, X));
+    cx = zl::mul(w, Z);
+    cy = zl::neg(zl::dbl(zl::mul(s, Z)));
+    const F2 b = zl::mul(zl::mul(X, Y), s);           // B = X Y S
+    const F2 b4 = zl::dbl(zl::dbl(b));
+    const F2 h = zl::sub(zl::sqr(w), zl::dbl(b4));    // H = W^2 - 8B
+    const F2 ss = zl::sqr(s);
+    X = zl::dbl(zl::mul(h, s));
+    Y = zl::sub(zl::mul(w, zl::sub(b4, h)), zl::dbl(zl::dbl(zl::dbl(zl::mul(yy, ss)))));
+    Z = zl::dbl(zl::dbl(zl::dbl(zl::mul(s, ss))));
+}
+// R <- R + Q (Q affine), line through R and Q (scaled by lambda = xQ Z - X)
+__device__ __forceinline__ void add_step(F2& X, F2& Y, F2& Z, const F2& xq, const F2& yq, F2& c0, F2& cx, F2& cy) {
+    const F2 th = zl::sub(zl::mul(yq, Z), Y), la = zl::sub(zl::mul(xq, Z), X);
+    c0 = zl::sub(zl::mul(yq, la), zl::mul(th, xq));
+    cx = th;
+    cy = zl::neg(la);
+    const F2 uu = zl::sqr(th), vv = zl::sqr(la), vvv = zl::mul(la, vv), rr = zl::mul(vv, X);
+    const F2 a = zl::sub(zl::sub(zl::mul(uu, Z), vvv), zl::dbl(rr));
+    X = zl::mul(la, a);
+    Y = zl::sub(zl::mul(th, zl::sub(rr, a)), zl::mul(vvv, Y));
+    Z = zl::mul(vvv, Z);
+}
+
+__device__ __forceinline__ F load_canon64(const uint64_t* w) {  // canonical u64 words -> Montgomery
+    F c;
+#pragma unroll
+    for (int i = 0; i < NW / 2; i++) {
+        c.l[2 * i] = (uint32_t)w[i];
+        c.l[2 * i + 1] = (uint32_t)(w[i] >> 32);
+    }
+    return zl::to_mont(c);
+}
+
+// inputs -> Montgomery records: pm[p] = (xP', yP', zP) with zP = 0 for a pair that contributes 1 (a point at infinity, padding), qm[p] = (xQ, yQ)
+__global__ __launch_bounds__(64) void k_pd_prep(const uint64_t* __restrict__ ps, const uint64_t* __restrict__ qs, const uint32_t* __restrict__ sc, size_t n,
+                                                size_t npad, F* __restrict__ pm, F2* __restrict__ qm) {
+    const size_t p = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (p >= npad) return;
+    const size_t pl = p < n ? p : 0;  // padding lanes read pair 0 and are marked as ones
+    F xP = load_canon64(ps + pl * NW), yP = load_canon64(ps + pl * NW + NW / 2), zP = F::one();
+    bool one = p >= n || (xP.is_zero() && yP.is_zero());
+    if (sc) {  // P <- k P for a 128-bit k (XYZZ, the line absorbs the Fq factor zz zzz)
+        XYZZ<F> acc = XYZZ<F>::inf();
+        for (int i = 127; i >= 0; i--) {
+            zl::dbl_inplace(acc);
+            if ((sc[4 * pl + (i >> 5)] >> (i & 31)) & 1) zl::add_mixed(acc, xP, yP, false);
+        }
+        one = one || acc.is_inf();
+        xP = zl::mul(acc.x, acc.zzz);
+        yP = zl::mul(acc.y, acc.zz);
+        zP = zl::mul(acc.zz, acc.zzz);
+    }
+    const uint64_t* q = qs + pl * 2 * NW;
+    const F2 xq{load_canon64(q), load_canon64(q + NW / 2)}, yq{load_canon64(q + NW), load_canon64(q + 3 * NW / 2)};
+    one = one || (xq.is_zero() && yq.is_zero());
+    pm[3 * p] = xP;
+    pm[3 * p + 1] = yP;
+    pm[3 * p + 2] = one ? F::zero() : zP;
+    qm[2 * p] = xq;
+    qm[2 * p + 1] = yq;
+}
+
+__global__ __launch_bounds__(64) void k_pd_lines(const F* __restrict__ pm, const F2* __restrict__ qm, size_t npad, Consts K, F* __restrict__ lines) {
+    const size_t p = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (p >= npad) return;
+    const F xP = pm[3 * p], yP = pm[3 * p + 1], zP = pm[3 * p + 2];
+    const bool one = zP.is_zero();
+    // Q is read again at every addition step instead of being held through the doublings (register budget)
+    F2 X = qm[2 * p], Y = qm[2 * p + 1], Z = F2::one(), c0, cx, cy;
+    F* rec = lines + p * 6;
+    const size_t step = npad * 6;
+    for (int i = PP::LOOP_BITS - 2; i >= 0; i--) {
+        dbl_step(X, Y, Z, c0, cx, cy);
+        emit(rec, c0, cx, cy, xP, yP, zP, one, K);
+        rec += step;
+        if (PP::loop_bit(i)) {
+            add_step(X, Y, Z, qm[2 * p], qm[2 * p + 1], c0, cx, cy);
+            emit(rec, c0, cx, cy, xP, yP, zP, one, K);
+            rec += step;
+        }
+    }
+    if (PP::BN_TAIL) {
+        const F2 x1 = zl::mul(conj(qm[2 * p]), K.g2), y1 = zl::mul(conj(qm[2 * p + 1]), K.g3);
+        const F2 x2 = zl::mul(conj(x1), K.g2), y2 = zl::neg(zl::mul(conj(y1), K.g3));
+        add_step(X, Y, Z, x1, y1, c0, cx, cy);
+        emit(rec, c0, cx, cy, xP, yP, zP, one, K);
+        rec += step;
+        add_step(X, Y, Z, x2, y2, c0, cx, cy);
+        emit(rec, c0, cx, cy, xP, yP, zP, one, K);
+    }
+}
+
+// ---- Fq12 products on a group of 16 lanes (lane k < 12 owns coefficient w^k) ---------------------------------------------------------------
+// t[m] = sum_{i+j=m} a_i b_j, lane k computes t[k] (i <= k) and t[k+12] (i > k): 12 products per lane for a full product, 6 for a line (whose six
+// non-zero coefficients each meet exactly one a_i per lane).  Then w^m = w^(m-12) (M6 w^6 - M0_NEG) folds t[12..22] back:
+//   c_k = t[k] + [k >= 6] M6 t[k+6] + (k <= 5 ? -M0 : M6^2 - M0) t[k+12] + [k <= 4] (-M6 M0) t[k+18]      (t[23] = 0 stands in for absent terms)
+__device__ __forceinline__ F fold(const F* t, int k, const Consts& K) {
+    F c = zl::add(t[k], zl::mul(t[k + 12], k <= 5 ? K.nm0 : K.m6sq_m0));
+    c = zl::add(c, zl::mul(t[k >= 6 ? k + 6 : 23], K.m6));
+    return zl::add(c, zl::mul(t[k <= 4 ? k + 18 : 23], K.nm6m0));
+}
+// fk <- (sum_i a_i w^i)(sum_j b_j w^j) with a, b in LDS; three barriers (the caller's LDS writes must precede the call)
+__device__ __forceinline__ void mul_full(F& fk, const F* a, const F* b, F* t, int k, bool act, const Consts& K) {
+    __syncthreads();
+    if (act) {
+        F lo = F::zero(), hi = F::zero();
+#pragma unroll 1
+        for (int i = 0; i < 12; i++) {
+            const int j = k - i;
+            const F pr = zl::mul(a[i], b[j >= 0 ? j : j + 12]);
+            if (j >= 0) lo = zl::add(lo, pr);
+            else hi = zl::add(hi, pr);
+        }
+        t[k] = lo;
+        t[k + 12] = hi;
+    }
+    __syncthreads();
+    if (act) fk = fold(t, k, K);
+    __syncthreads();
+}
+// fk <- f * line (six coefficients at line_pos(m), read from HBM)
+__device__ __forceinline__ void mul_line(F& fk, F* a, const F* __restrict__ rec, F* t, int k, bool act, const Consts& K) {
+    if (act) a[k] = fk;
+    __syncthreads();
+    if (act) {
+        F lo = F::zero(), hi = F::zero();
+#pragma unroll
+        for (int m = 0; m < 6; m++) {
+            const int j = line_pos(m), i = k - j;
+            const F pr = zl::mul(a[i >= 0 ? i : i + 12], rec[m]);
+            if (i >= 0) lo = zl::add(lo, pr);
+            else hi = zl::add(hi, pr);
+        }
+        t[k] = lo;
+        t[k + 12] = hi;
+    }
+    __syncthreads();
+    if (act) fk = fold(t, k, K);
+    __syncthreads();
+}
+
+__global__ __launch_bounds__(64) void k_pd_acc(const F* __restrict__ lines, size_t npad, uint32_t ngroups, uint32_t G, Consts K, F* __restrict__ acc) {
+    __shared__ F sa[4][12];
+    __shared__ F st[4][24];
+    const int grp = threadIdx.x >> 4, k = threadIdx.x & 15;
+    const uint32_t g = blockIdx.x * 4 + grp;
+    const bool act = k < 12 && g < ngroups;
+    F* a = sa[grp];
+    F* t = st[grp];
+    if (act && k == 11) t[23] = F::zero();
+    F fk = k == 0 ? F::one() : F::zero();
+    const size_t step = npad * 6;
+    const F* rec = lines + (size_t)(act ? g : 0) * 6;
+    for (int i = PP::LOOP_BITS - 2; i >= 0; i--) {
+        if (act) a[k] = fk;
+        mul_full(fk, a, a, t, k, act, K);
+#pragma unroll 1
+        for (uint32_t j = 0; j < G; j++) mul_line(fk, a, rec + (size_t)j * ngroups * 6, t, k, act, K);
+        rec += step;
+        if (PP::loop_bit(i)) {
+#pragma unroll 1
+            for (uint32_t j = 0; j < G; j++) mul_line(fk, a, rec + (size_t)j * ngroups * 6, t, k, act, K);
+            rec += step;
+        }
+    }
+    if (PP::BN_TAIL) {
+#pragma unroll 1
+        for (int e = 0; e < 2; e++) {
+#pragma unroll 1
+            for (uint32_t j = 0; j < G; j++) mul_line(fk, a, rec + (size_t)j * ngroups * 6, t, k, act, K);
+            rec += step;
+        }
+    }
+    if (act) acc[(size_t)g * 12 + k] = fk;
+}
+
+// out[g] = prod of in[g * per .. g * per + per) (entries >= cnt count as 1)
+__global__ __launch_bounds__(64) void k_pd_prod(const F* __restrict__ in, uint32_t cnt, uint32_t per, uint32_t nout, Consts K, F* __restrict__ out) {
+    __shared__ F sa[4][12];
+    __shared__ F sb[4][12];
+    __shared__ F st[4][24];
+    const int grp = threadIdx.x >> 4, k = threadIdx.x & 15;
+    const uint32_t g = blockIdx.x * 4 + grp;
+    const bool act = k < 12 && g < nout;
+    F* a = sa[grp];
+    F* b = sb[grp];
+    F* t = st[grp];
+    if (act && k == 11) t[23] = F::zero();
+    F fk = k == 0 ? F::one() : F::zero();
+#pragma unroll 1
+    for (uint32_t e = 0; e < per; e++) {
+        const size_t idx = (size_t)g * per + e;
+        if (act) {
+            a[k] = fk;
+            b[k] = idx < cnt ? in[idx * 12 + k] : (k == 0 ? F::one() : F::zero());
+        }
+        mul_full(fk, a, b, t, k, act, K);
+    }
+    if (act) out[(size_t)g * 12 + k] = fk;
+}
+
+Consts make_consts() {
+    using Eng = openzl::pairing::Engine<FqP, PP>;
+    Consts K;
+    K.sh = zl::from_u64<FqP>(PP::ISHIFT);
+    K.m6 = zl::from_u64<FqP>(PP::M6);
+    K.nm0 = zl::neg(zl::from_u64<FqP>(PP::M0_NEG));
+    K.m6sq_m0 = zl::from_u64<FqP>((uint64_t)PP::M6 * PP::M6 - PP::M0_NEG);
+    K.nm6m0 = zl::neg(zl::from_u64<FqP>((uint64_t)PP::M6 * PP::M0_NEG));
+    if (PP::BN_TAIL) {
+        const auto fc = Eng::make_frob_consts();
+        K.g2 = fc.g2;
+        K.g3 = fc.g3;
+    } else {
+        K.g2 = K.g3 = F2::one();
+    }
+    return K;
+}
+
+// one launch set: pairs [0, n) in ngroups groups -> `nout_red ? 1 : ngroups` Fq12 values in out (Montgomery words)
+int run(zl_ctx* ctx, const uint64_t* ps, const uint64_t* qs, const uint32_t* sc, size_t n, size_t ngroups, bool reduce, uint32_t* out) {
+    if (!ctx || !out || n == 0 || ngroups == 0 || ngroups > n || n > openzl::pairing_dev::MAX_PAIRS) return ZL_EINVAL;
+    ZL_HIP(ctx, hipSetDevice(ctx->device));
+    static const Consts K = make_consts();
+    const size_t G = (n + ngroups - 1) / ngroups, npad = G * ngroups;
+    const size_t pb = n * NW * 8, qb = 2 * pb, sb = sc ? n * 16 : 0;  // bytes of ps (n x 2 Fq of NW u32), qs (n x 4 Fq), scalars
+    const size_t in_bytes = (pb + qb + sb + 255) & ~(size_t)255;
+    void *d_in = nullptr, *d_lines = nullptr, *d_acc = nullptr, *d_prep = nullptr;
+    int rc = zl_scratch_get(ctx, 30, in_bytes, &d_in);
+    if (!rc) rc = zl_scratch_get(ctx, 33, npad * 7 * sizeof(F), &d_prep);
+    if (!rc) rc = zl_scratch_get(ctx, 31, (size_t)NLINES * npad * 6 * sizeof(F), &d_lines);
+    const size_t nred = (ngroups + 15) / 16;
+    if (!rc) rc = zl_scratch_get(ctx, 32, (ngroups + nred + 1) * 12 * sizeof(F), &d_acc);
+    if (rc) return rc;
+    unsigned char* din = static_cast<unsigned char*>(d_in);
+    ZL_HIP(ctx, hipMemcpyAsync(din, ps, pb, hipMemcpyHostToDevice, ctx->stream));
+    ZL_HIP(ctx, hipMemcpyAsync(din + pb, qs, qb, hipMemcpyHostToDevice, ctx->stream));
+    if (sc) ZL_HIP(ctx, hipMemcpyAsync(din + pb + qb, sc, sb, hipMemcpyHostToDevice, ctx->stream));
+    F* lines = static_cast<F*>(d_lines);
+    F* acc = static_cast<F*>(d_acc);
+    F* pm = static_cast<F*>(d_prep);
+    F2* qm = reinterpret_cast<F2*>(pm + 3 * npad);
+    hipLaunchKernelGGL(k_pd_prep, dim3((unsigned)((npad + 63) / 64)), dim3(64), 0, ctx->stream, reinterpret_cast<const uint64_t*>(din),
+                       reinterpret_cast<const uint64_t*>(din + pb), sc ? reinterpret_cast<const uint32_t*>(din + pb + qb) : nullptr, n, npad, pm, qm);
+    ZL_HIP(ctx, hipGetLastError());
+    hipLaunchKernelGGL(k_pd_lines, dim3((unsigned)((npad + 63) / 64)), dim3(64), 0, ctx->stream, pm, qm, npad, K, lines);
+    ZL_HIP(ctx, hipGetLastError());
+    hipLaunchKernelGGL(k_pd_acc, dim3((unsigned)((ngroups + 3) / 4)), dim3(64), 0, ctx->stream, lines, npad, (uint32_t)ngroups, (uint32_t)G, K, acc);
+    ZL_HIP(ctx, hipGetLastError());
+    const F* res = acc;
+    size_t cnt = ngroups;
+    if (reduce) {
+        F* bufs[2] = {acc + ngroups * 12, acc};  // the levels ping-pong between the space behind the accumulators (nred entries) and their own
+        int side = 0;
+        while (cnt > 1) {
+            const size_t nout = (cnt + 15) / 16;
+            hipLaunchKernelGGL(k_pd_prod, dim3((unsigned)((nout + 3) / 4)), dim3(64), 0, ctx->stream, res, (uint32_t)cnt, 16u, (uint32_t)nout, K, bufs[side]);
+            ZL_HIP(ctx, hipGetLastError());
+            res = bufs[side];
+            side ^= 1;
+            cnt = nout;
+        }
+    }
+    ZL_HIP(ctx, hipMemcpyAsync(out, res, cnt * 12 * sizeof(F), hipMemcpyDeviceToHost, ctx->stream));
+    ZL_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    return ZL_OK;
+}
+}  // namespace
+
+namespace openzl {
+namespace pairing_dev {
+int ZL_PD_SUFFIX(miller_groups)(zl_ctx* ctx, const uint64_t* ps, const uint64_t* qs, const uint32_t* sc, size_t n, size_t ngroups, uint32_t* out) {
+    return run(ctx, ps, qs, sc, n, ngroups, false, out);
+}
+int ZL_PD_SUFFIX(miller_product)(zl_ctx* ctx, const uint64_t* ps, const uint64_t* qs, const uint32_t* sc, size_t n, uint32_t* out) {
+    using Eng = openzl::pairing::Engine<FqP, PP>;
+    if (!ctx || !out || (n && (!ps || !qs))) return ZL_EINVAL;
+    typename Eng::Fq12 f = Eng::one();
+    // groups per launch: about 32 per CU (8 waves of 4 groups): below that a pair gets a group of its own, above it pairs share squarings
+    const size_t target = (size_t)(ctx->cu_count > 0 ? ctx->cu_count : 256) * 32;
+    for (size_t first = 0; first < n; first += MAX_PAIRS) {
+        const size_t m = n - first < MAX_PAIRS ? n - first : MAX_PAIRS;
+        const size_t G = (m + target - 1) / target, ng = (m + G - 1) / G;
+        typename Eng::Fq12 part;
+        const int rc = run(ctx, ps + first * NW, qs + first * 2 * NW, sc ? sc + 4 * first : nullptr, m, ng, true, reinterpret_cast<uint32_t*>(part.c));
+        if (rc) return rc;
+        f = Eng::mul(f, part);
+    }
+    memcpy(out, f.c, sizeof f.c);
+    return ZL_OK;
+}
+}  // namespace pairing_dev
+}  // namespace openzl
