@@ -45,11 +45,7 @@ struct BnG1 {
     static constexpr int ID = 1;
     using FqP = BN254_Fq;
     using FrP = BN254_Fr;
-#ifdef ZL_BN_FIELD32
-    using F = Fp<FqP>;  // rounds 1-3: 8 x 32-bit carry-chain limbs (developer A/B switch)
-#else
     using F = Fp28<BN254_Fq28, BN254_Fq>;  // round 4: 10 x 28-bit lazily reduced limbs like BLS12-381 (zl_field28.h)
-#endif
     using C = BN254_G1;
     static constexpr int SC_BITS = 254;
     static constexpr int FQ64 = 4;
@@ -89,11 +85,7 @@ struct G2Cfg {
 };
 // G2 on the lazily reduced 28-bit fields (Fq2 products as dual scans, zl_field28.h): 14 limbs per component for BLS12-381, 10 for BN254
 using BlsG2 = G2Cfg<BLS12_381_G2, BLS12_381_Fq, BLS12_381_Fr, Fp2L<Fp28<BLS12_381_Fq28, BLS12_381_Fq>>, 255, 6, 2>;
-#ifdef ZL_BN_FIELD32
-using BnG2 = G2Cfg<BN254_G2, BN254_Fq, BN254_Fr, Fp2<BN254_Fq>, 254, 4, 3>;
-#else
 using BnG2 = G2Cfg<BN254_G2, BN254_Fq, BN254_Fr, Fp2L<Fp28<BN254_Fq28, BN254_Fq>>, 254, 4, 3>;  // round 4: like BLS12-381 G2, on 10 limbs
-#endif
 
 // ---- context ----------------------------------------------------------------------------------------------
 struct zl_bases {

@@ -44,8 +44,8 @@
 #include "zl_msm_job.h"
 #include "zl_msm_bases.h"
 // the accumulation and tail kernels of this group are defined in zl_msm_acc.hip / zl_msm_tail.hip
-ZL_MSM_ACCUMULATE_KERNELS(extern, ZL_G)
-ZL_MSM_TAIL_KERNELS(extern, ZL_G)
+ZL_GLIST(ZL_MSM_ACCUMULATE_KERNELS)(extern, ZL_G)
+ZL_GLIST(ZL_MSM_TAIL_KERNELS)(extern, ZL_G)
 
 template <class G>
 static int msm_run_t(zl_ctx* ctx, const zl_bases& bs, size_t first, const void* d_scalars, size_t n, uint64_t* out_partial) {

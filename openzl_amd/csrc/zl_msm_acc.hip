@@ -3,4 +3,4 @@
 #ifndef ZL_G
 #error "compile with -DZL_G=<group config>"
 #endif
-ZL_MSM_ACCUMULATE_KERNELS(, ZL_G)
+ZL_GLIST(ZL_MSM_ACCUMULATE_KERNELS)(, ZL_G)

@@ -1,5 +1,5 @@
 // zl_msm_accumulate.h -- step 3 of the MSM (zl_msm.hip): the bucket accumulation kernels, one lane (or one DPP quad) per chunk of the
-// bucket-sorted entry list.  Instantiated per group in zl_msm_acc.hip; zl_msm.hip only launches them (ZL_MSM_ACCUMULATE_KERNELS(extern, G)).
+// bucket-sorted entry list.  Instantiated per group in zl_msm_acc.hip; zl_msm.hip only launches them (ZL_MSM_ACCUMULATE_KERNELS_G1 / _G2, extern).
 #pragma once
 #include <type_traits>
 #include "zl_ctx.h"
@@ -137,53 +137,54 @@ __global__ void __launch_bounds__(64, ZL_ACC_PAIR_WAVES) k_msm_accumulate_pair(c
                                                         XYZZ<typename G::F>* __restrict__ partials, uint32_t ZL_CHUNK,
                                                         const Affine<typename G::F>* __restrict__ phib_, uint32_t n_real) {
     using B = typename PairBase<typename G::F>::type;
-    if constexpr (!std::is_void<B>::value) {
-        using H = Fp2H<B>;
-        const int half = zl::pair_half(), sub = (int)(threadIdx.x & 3u);
-        const uint32_t t = QUAD ? ZL_OCTET_ITEM() : ZL_PAIR_ITEM();
-        const uint32_t E = offsets[NB];
-        const Affine<typename G::F>* __restrict__ phib = phib_ - n_real;  // GLS: virtual point n_real + i = psi^j(P_i); else n_real = 2^32 - 1 (never selected)
-        const uint64_t start64 = (uint64_t)t * ZL_CHUNK;
-        if (start64 >= E) return;
-        const uint32_t start = (uint32_t)start64;
-        const uint32_t end = (uint32_t)min((uint64_t)E, start64 + ZL_CHUNK);
-        uint32_t b = zl_upper_bound(offsets, NB + 1, start) - 1;
-        uint32_t b_start = offsets[b], b_end = offsets[b + 1];
-        XYZZ<H> acc = XYZZ<H>::inf();
-        for (uint32_t e = start; e < end; e++) {  // (the flat loop of zl_accumulate_chunk)
-            while (e == b_end) {
-                if (b_end > b_start) {
-                    if (b_start >= start) pair_store(&bucket_sums[b], half, acc);
-                    else pair_store(&partials[(size_t)2 * t], half, acc);
-                    acc = XYZZ<H>::inf();
-                }
-                b++;
-                b_start = b_end;
-                b_end = offsets[b + 1];
+    static_assert(!std::is_void<B>::value, "lane-pair kernels: Fq2 groups on 28-bit limbs only");
+    using H = Fp2H<B>;
+    const int half = zl::pair_half(), sub = (int)(threadIdx.x & 3u);
+    const uint32_t t = QUAD ? ZL_OCTET_ITEM() : ZL_PAIR_ITEM();
+    const uint32_t E = offsets[NB];
+    const Affine<typename G::F>* __restrict__ phib = phib_ - n_real;  // GLS: virtual point n_real + i = psi^j(P_i); else n_real = 2^32 - 1 (never selected)
+    const uint64_t start64 = (uint64_t)t * ZL_CHUNK;
+    if (start64 >= E) return;
+    const uint32_t start = (uint32_t)start64;
+    const uint32_t end = (uint32_t)min((uint64_t)E, start64 + ZL_CHUNK);
+    uint32_t b = zl_upper_bound(offsets, NB + 1, start) - 1;
+    uint32_t b_start = offsets[b], b_end = offsets[b + 1];
+    XYZZ<H> acc = XYZZ<H>::inf();
+    for (uint32_t e = start; e < end; e++) {  // (the flat loop of zl_accumulate_chunk)
+        while (e == b_end) {
+            if (b_end > b_start) {
+                if (b_start >= start) pair_store(&bucket_sums[b], half, acc);
+                else pair_store(&partials[(size_t)2 * t], half, acc);
+                acc = XYZZ<H>::inf();
             }
-            const uint32_t ent = entries[e];
-            const uint32_t idx = ent & 0x7fffffffu;
-            const Affine<H> P = pair_load(&(G::GLV && idx >= n_real ? phib : bases_)[idx], half);
-            if (!P.is_inf()) {
-                if constexpr (QUAD) zl::add_mixed_quad(acc, P.x, P.y, (ent >> 31) != 0, sub);
-                else zl::add_mixed(acc, P.x, P.y, (ent >> 31) != 0);
-            }
+            b++;
+            b_start = b_end;
+            b_end = offsets[b + 1];
         }
-        const bool complete = (b_start >= start) && (b_end <= end);
-        if (complete) pair_store(&bucket_sums[b], half, acc);
-        else pair_store(&partials[(size_t)2 * t + (b_start <= start ? 0 : 1)], half, acc);
+        const uint32_t ent = entries[e];
+        const uint32_t idx = ent & 0x7fffffffu;
+        const Affine<H> P = pair_load(&(G::GLV && idx >= n_real ? phib : bases_)[idx], half);
+        if (!P.is_inf()) {
+            if constexpr (QUAD) zl::add_mixed_quad(acc, P.x, P.y, (ent >> 31) != 0, sub);
+            else zl::add_mixed(acc, P.x, P.y, (ent >> 31) != 0);
+        }
     }
+    const bool complete = (b_start >= start) && (b_end <= end);
+    if (complete) pair_store(&bucket_sums[b], half, acc);
+    else pair_store(&partials[(size_t)2 * t + (b_start <= start ? 0 : 1)], half, acc);
 }
-// every instantiation MsmJob<G>::accumulate launches: X = empty defines them (zl_msm_acc.hip), X = extern only declares them
+// every instantiation MsmJob<G>::accumulate launches, one list per kind of group (ZL_GLIST, zl_msm_common.h): X = empty defines them (zl_msm_acc.hip),
+// X = extern only declares them
 #ifdef ZL_MEASURE
 #define ZL_MSM_ACCUMULATE_CLK_KERNEL(X, G) X template __global__ void k_msm_accumulate_clk<G>(const uint32_t*, const uint32_t*, uint32_t, const Affine<typename G::F>*, XYZZ<typename G::F>*, XYZZ<typename G::F>*, uint32_t, const Affine<typename G::F>*, uint32_t, unsigned long long*, uint32_t);
 #else
 #define ZL_MSM_ACCUMULATE_CLK_KERNEL(X, G)
 #endif
-#define ZL_MSM_ACCUMULATE_KERNELS(X, G) \
+#define ZL_MSM_ACCUMULATE_KERNELS_G1(X, G) \
     ZL_MSM_ACCUMULATE_CLK_KERNEL(X, G) \
     X template __global__ void k_msm_accumulate<G>(const uint32_t*, const uint32_t*, uint32_t, const Affine<typename G::F>*, XYZZ<typename G::F>*, XYZZ<typename G::F>*, uint32_t, const Affine<typename G::F>*, uint32_t); \
-    X template __global__ void k_msm_accumulate_quad<G>(const uint32_t*, const uint32_t*, uint32_t, const Affine<typename G::F>*, XYZZ<typename G::F>*, XYZZ<typename G::F>*, uint32_t, const Affine<typename G::F>*, uint32_t); \
+    X template __global__ void k_msm_accumulate_quad<G>(const uint32_t*, const uint32_t*, uint32_t, const Affine<typename G::F>*, XYZZ<typename G::F>*, XYZZ<typename G::F>*, uint32_t, const Affine<typename G::F>*, uint32_t);
+#define ZL_MSM_ACCUMULATE_KERNELS_G2(X, G) \
     X template __global__ void k_msm_accumulate_pair<G, true>(const uint32_t*, const uint32_t*, uint32_t, const Affine<typename G::F>*, XYZZ<typename G::F>*, XYZZ<typename G::F>*, uint32_t, const Affine<typename G::F>*, uint32_t); \
-    X template __global__ void k_msm_accumulate_pair<G, false>(const uint32_t*, const uint32_t*, uint32_t, const Affine<typename G::F>*, XYZZ<typename G::F>*, XYZZ<typename G::F>*, uint32_t, const Affine<typename G::F>*, uint32_t); \
+    X template __global__ void k_msm_accumulate_pair<G, false>(const uint32_t*, const uint32_t*, uint32_t, const Affine<typename G::F>*, XYZZ<typename G::F>*, XYZZ<typename G::F>*, uint32_t, const Affine<typename G::F>*, uint32_t);
 

@@ -7,14 +7,17 @@
 #define ZL_GCAT_(a, b) a##_##b
 #define ZL_GCAT(a, b) ZL_GCAT_(a, b)
 #define ZL_GNAME(f) ZL_GCAT(f, ZL_G)
+// The accumulation and tail kernels cross the units as one instantiation list per kind of group: ZL_GLIST(ZL_MSM_TAIL_KERNELS) is
+// ZL_MSM_TAIL_KERNELS_G1 (the one-lane / four-lane kernels) for BlsG1 and BnG1, ZL_MSM_TAIL_KERNELS_G2 (the lane-pair / octet kernels) for BlsG2 and BnG2
+#define ZL_KIND_BlsG1 G1
+#define ZL_KIND_BnG1 G1
+#define ZL_KIND_BlsG2 G2
+#define ZL_KIND_BnG2 G2
+#define ZL_GLIST(list) ZL_GCAT(list, ZL_GNAME(ZL_KIND))
 
 // Wave issue priority of the sort / tail kernels: in a pipeline they share every SIMD with two waves of the accumulation kernel, which would
 // otherwise win most issue slots (a 1-ms sort kernel then takes 5-9 ms); their own VALU demand is tiny.
-#ifdef ZL_NO_SIDE_PRIO
-#define ZL_SIDE_PRIO() ((void)0)
-#else
 #define ZL_SIDE_PRIO() __builtin_amdgcn_s_setprio(3)
-#endif
 #define ZL_CHUNK_MAX 64    // entries per lane in msm_accumulate (smaller for small inputs: more lanes, shorter chains)
 #define ZL_BIG_SPAN 64     // buckets cut into more chunks than this are merged by a whole block ...
 #define ZL_BIG_SPAN_SMALL 8  // ... 8 for small inputs: a lane folds its partials serially, and 64 dependent additions (1.2 ms for G1, 3 ms

@@ -155,7 +155,7 @@ struct MsmJob {
         bsp = &bs;
         pre = bs.precomp_c > 0;  // table of 2^(c w) P_i present: all windows share one bucket set
         c = pre ? bs.precomp_c : (ctx->msm_c > 0 ? ctx->msm_c : zl_pick_window(n, sc_bits, glv && G::ENDO_K != 2));
-        if (!pre && ctx->msm_c <= 0 && glv && zl_tune("ZL_TUNE_HALF_TABLE", 1)) {
+        if (!pre && ctx->msm_c <= 0 && glv) {
             int h = 0;
             if constexpr (G::ENDO_K == 2) {
                 // (BN254: c = 16 at 2^18 is 11 % faster as a single call and 7 % SLOWER inside a 240 000-constraint proof, where four such MSMs and the witness map share
@@ -506,52 +506,59 @@ struct MsmJob {
     }
     static constexpr bool pair_ok() { return G::COORDS == 2 && !std::is_void<typename PairBase<F>::type>::value; }  // an Fq2 group on 28-bit limbs: the lane-pair kernels exist
     int accumulate(zl_ctx* ctx, hipStream_t st) {
-        if (pair_ok() && zl_tune("ZL_TUNE_G2_OCTET", 1) && nchunks <= (uint64_t)zl_tune("ZL_TUNE_QUAD_ACC_CHUNKS", 24576))  // Fq2 groups: eight lanes per chunk (zl_fq2pair.h)
-            hipLaunchKernelGGL((k_msm_accumulate_pair<G, true>), dim3((nchunks + 7) / 8), dim3(64), 0, st, d_entries, d_offsets, NB, d_bases, d_buckets, d_partials, ZL_CHUNK,
-                               glv ? d_phi : d_bases, glv ? (uint32_t)n_real : 0xFFFFFFFFu);
-        else if (nchunks <= (uint64_t)zl_tune("ZL_TUNE_QUAD_ACC_CHUNKS", 24576))  // four lanes per chunk while that is at most ~1.5 waves per SIMD (round 6: 49 152 -> 24 576; at three waves per SIMD the one-lane kernel is faster: 94 against 131 us at 2^14, profiles/r06_small_knobs2.log)
-            hipLaunchKernelGGL((k_msm_accumulate_quad<G>), dim3((4 * nchunks + ZL_ACC_BLOCK - 1) / ZL_ACC_BLOCK), dim3(ZL_ACC_BLOCK), 0, st, d_entries, d_offsets, NB, d_bases, d_buckets, d_partials, ZL_CHUNK,
-                               glv ? d_phi : d_bases, glv ? (uint32_t)n_real : 0xFFFFFFFFu);
-        else if (pair_ok() && zl_tune("ZL_TUNE_G2_PAIR", 1))  // Fq2 groups: two lanes per chunk, two waves per SIMD (zl_fq2pair.h)
-            hipLaunchKernelGGL((k_msm_accumulate_pair<G, false>), dim3((nchunks + 31) / 32), dim3(64), 0, st, d_entries, d_offsets, NB, d_bases, d_buckets, d_partials, ZL_CHUNK,
-                               glv ? d_phi : d_bases, glv ? (uint32_t)n_real : 0xFFFFFFFFu);
+        static_assert(G::COORDS == 1 || pair_ok(), "every Fq2 group runs on 28-bit limbs: its MSM kernels are the lane-pair ones");
+        // four lanes per chunk (Fq2 groups: eight) while that is at most ~1.5 waves per SIMD (round 6: 49 152 -> 24 576; at three waves per SIMD the one-lane kernel
+        // is faster: 94 against 131 us at 2^14, profiles/r06_small_knobs2.log)
+        const bool quad = nchunks <= (uint64_t)zl_tune("ZL_TUNE_QUAD_ACC_CHUNKS", 24576);
+        if constexpr (pair_ok()) {  // Fq2 groups (zl_fq2pair.h): eight lanes per chunk, else two lanes per chunk at two waves per SIMD
+            if (quad)
+                hipLaunchKernelGGL((k_msm_accumulate_pair<G, true>), dim3((nchunks + 7) / 8), dim3(64), 0, st, d_entries, d_offsets, NB, d_bases, d_buckets, d_partials, ZL_CHUNK,
+                                   glv ? d_phi : d_bases, glv ? (uint32_t)n_real : 0xFFFFFFFFu);
+            else
+                hipLaunchKernelGGL((k_msm_accumulate_pair<G, false>), dim3((nchunks + 31) / 32), dim3(64), 0, st, d_entries, d_offsets, NB, d_bases, d_buckets, d_partials, ZL_CHUNK,
+                                   glv ? d_phi : d_bases, glv ? (uint32_t)n_real : 0xFFFFFFFFu);
+        } else {
+            if (quad)
+                hipLaunchKernelGGL((k_msm_accumulate_quad<G>), dim3((4 * nchunks + ZL_ACC_BLOCK - 1) / ZL_ACC_BLOCK), dim3(ZL_ACC_BLOCK), 0, st, d_entries, d_offsets, NB, d_bases, d_buckets, d_partials, ZL_CHUNK,
+                                   glv ? d_phi : d_bases, glv ? (uint32_t)n_real : 0xFFFFFFFFu);
 #ifdef ZL_MEASURE
-        else if (G::COORDS == 1 && ctx->acc_clk && (size_t)((nchunks + ZL_ACC_BLOCK - 1) / ZL_ACC_BLOCK) * 32 <= ctx->acc_clk_cap) {  // armed by the measurement hook zl_test_acc_clock only
-            ctx->acc_clk_waves = (nchunks + ZL_ACC_BLOCK - 1) / ZL_ACC_BLOCK;
-            hipLaunchKernelGGL((k_msm_accumulate_clk<G>), dim3((nchunks + ZL_ACC_BLOCK - 1) / ZL_ACC_BLOCK), dim3(ZL_ACC_BLOCK), 0, st, d_entries, d_offsets, NB, d_bases, d_buckets, d_partials, ZL_CHUNK,
-                               glv ? d_phi : d_bases, glv ? (uint32_t)n_real : 0xFFFFFFFFu, (unsigned long long*)ctx->acc_clk,
-                               zl_tune("ZL_TUNE_ACC_CLK_IDX_BITS", 31) >= 31 ? 0x7fffffffu : ((1u << zl_tune("ZL_TUNE_ACC_CLK_IDX_BITS", 31)) - 1u));
-        } else
-#else
-        else
+            else if (ctx->acc_clk && (size_t)((nchunks + ZL_ACC_BLOCK - 1) / ZL_ACC_BLOCK) * 32 <= ctx->acc_clk_cap) {  // armed by the measurement hook zl_test_acc_clock only
+                ctx->acc_clk_waves = (nchunks + ZL_ACC_BLOCK - 1) / ZL_ACC_BLOCK;
+                hipLaunchKernelGGL((k_msm_accumulate_clk<G>), dim3((nchunks + ZL_ACC_BLOCK - 1) / ZL_ACC_BLOCK), dim3(ZL_ACC_BLOCK), 0, st, d_entries, d_offsets, NB, d_bases, d_buckets, d_partials, ZL_CHUNK,
+                                   glv ? d_phi : d_bases, glv ? (uint32_t)n_real : 0xFFFFFFFFu, (unsigned long long*)ctx->acc_clk,
+                                   zl_tune("ZL_TUNE_ACC_CLK_IDX_BITS", 31) >= 31 ? 0x7fffffffu : ((1u << zl_tune("ZL_TUNE_ACC_CLK_IDX_BITS", 31)) - 1u));
+            }
 #endif
-        hipLaunchKernelGGL((k_msm_accumulate<G>), dim3((nchunks + ZL_ACC_BLOCK - 1) / ZL_ACC_BLOCK), dim3(ZL_ACC_BLOCK), 0, st, d_entries, d_offsets, NB, d_bases, d_buckets, d_partials, ZL_CHUNK,
-                           glv ? d_phi : d_bases, glv ? (uint32_t)n_real : 0xFFFFFFFFu);
+            else
+                hipLaunchKernelGGL((k_msm_accumulate<G>), dim3((nchunks + ZL_ACC_BLOCK - 1) / ZL_ACC_BLOCK), dim3(ZL_ACC_BLOCK), 0, st, d_entries, d_offsets, NB, d_bases, d_buckets, d_partials, ZL_CHUNK,
+                                   glv ? d_phi : d_bases, glv ? (uint32_t)n_real : 0xFFFFFFFFu);
+        }
         ZL_HIP(ctx, hipGetLastError());
         return ZL_OK;
     }
     int tail(zl_ctx* ctx, hipStream_t st) {
-        // four lanes per group operation (zl_quad.h) in every tail launch that does not fill the machine
+        // four lanes per group operation (zl_quad.h; Fq2 groups: eight, zl_fq2pair.h) in every tail launch that does not fill the machine, one lane (Fq2: a lane pair) in those that do
         const uint32_t quad_max = (uint32_t)zl_tune("ZL_TUNE_QUAD_LANES", 65536);
-        const bool pair_tails = pair_ok() && zl_tune("ZL_TUNE_G2_PAIR_TAILS", 1), octet = pair_ok() && zl_tune("ZL_TUNE_G2_OCTET", 1);  // Fq2 groups: two lanes per item where a launch fills the machine
-        const bool by_cuts = NB > quad_max && nchunks > 1 && zl_tune("ZL_TUNE_MERGE_CUTS", 1);  // one lane (pair) per chunk boundary: every surviving lane folds one bucket
-        if (by_cuts) {
-            hipLaunchKernelGGL((k_msm_fill_empty<G>), dim3((NB + 255) / 256), dim3(256), 0, st, d_offsets, NB, d_buckets);
-            if (pair_tails)
+        const bool by_cuts = NB > quad_max && nchunks > 1;  // one lane (pair) per chunk boundary: every surviving lane folds one bucket
+        if (by_cuts) hipLaunchKernelGGL((k_msm_fill_empty<G>), dim3((NB + 255) / 256), dim3(256), 0, st, d_offsets, NB, d_buckets);
+        if constexpr (pair_ok()) {
+            if (by_cuts)
                 hipLaunchKernelGGL((k_msm_merge_cuts_pair<G>), dim3((nchunks + 31) / 32), dim3(64), 0, st, d_offsets, NB, d_buckets, d_partials, d_big_list, d_big_count, d_giant_list, d_giant_count, ZL_CHUNK, big_span, nchunks);
+            else if (NB > quad_max)
+                hipLaunchKernelGGL((k_msm_merge_pair<G, false>), dim3((NB + 31) / 32), dim3(64), 0, st, d_offsets, NB, d_buckets, d_partials, d_big_list, d_big_count, d_giant_list, d_giant_count, ZL_CHUNK, big_span);
             else
+                hipLaunchKernelGGL((k_msm_merge_pair<G, true>), dim3((NB + 7) / 8), dim3(64), 0, st, d_offsets, NB, d_buckets, d_partials, d_big_list, d_big_count, d_giant_list, d_giant_count, ZL_CHUNK, big_span);
+        } else {
+            if (by_cuts)
                 hipLaunchKernelGGL((k_msm_merge_cuts<G>), dim3((nchunks + 63) / 64), dim3(64), 0, st, d_offsets, NB, d_buckets, d_partials, d_big_list, d_big_count, d_giant_list, d_giant_count, ZL_CHUNK, big_span, nchunks);
-        } else if (pair_tails && NB > quad_max)
-            hipLaunchKernelGGL((k_msm_merge_pair<G, false>), dim3((NB + 31) / 32), dim3(64), 0, st, d_offsets, NB, d_buckets, d_partials, d_big_list, d_big_count, d_giant_list, d_giant_count, ZL_CHUNK, big_span);
-        else if (octet && NB <= quad_max)
-            hipLaunchKernelGGL((k_msm_merge_pair<G, true>), dim3((NB + 7) / 8), dim3(64), 0, st, d_offsets, NB, d_buckets, d_partials, d_big_list, d_big_count, d_giant_list, d_giant_count, ZL_CHUNK, big_span);
-        else if (NB <= quad_max)
-            hipLaunchKernelGGL((k_msm_merge<G, true>), dim3((4 * NB + 63) / 64), dim3(64), 0, st, d_offsets, NB, d_buckets, d_partials, d_big_list, d_big_count, d_giant_list, d_giant_count, ZL_CHUNK, big_span);
-        else
-        hipLaunchKernelGGL((k_msm_merge<G>), dim3((NB + 63) / 64), dim3(64), 0, st, d_offsets, NB, d_buckets, d_partials, d_big_list, d_big_count, d_giant_list, d_giant_count, ZL_CHUNK, big_span);
+            else if (NB > quad_max)  // (a single chunk)
+                hipLaunchKernelGGL((k_msm_merge<G>), dim3((NB + 63) / 64), dim3(64), 0, st, d_offsets, NB, d_buckets, d_partials, d_big_list, d_big_count, d_giant_list, d_giant_count, ZL_CHUNK, big_span);
+            else
+                hipLaunchKernelGGL((k_msm_merge<G, true>), dim3((4 * NB + 63) / 64), dim3(64), 0, st, d_offsets, NB, d_buckets, d_partials, d_big_list, d_big_count, d_giant_list, d_giant_count, ZL_CHUNK, big_span);
+        }
         // a bucket cut into more than big_span (ZL_GIANT_SPAN) chunks needs that many chunks to exist: small jobs skip the launches (three of the ~22 of a small MSM's chain)
         const bool may_big = nchunks > big_span, may_giant = nchunks > (uint32_t)ZL_GIANT_SPAN;
-        if (pair_tails && zl_tune("ZL_TUNE_G2_PAIR_BLOCKS", 1)) {  // Fq2 groups: the block-tree kernels of the heavy buckets on lane pairs
+        if constexpr (pair_ok()) {  // Fq2 groups: the block-tree kernels of the heavy buckets on lane pairs
             if (may_big) hipLaunchKernelGGL((k_msm_merge_big_pair<G>), dim3(std::min<uint32_t>(max_big, 1024)), dim3(2 * TreeLanes<G>::N), TreeLanes<G>::N * sizeof(X), st, d_offsets, d_buckets,
                                d_partials, d_big_list, d_big_count, ZL_CHUNK);
             if (may_giant) hipLaunchKernelGGL((k_msm_merge_giant_pair<G>), dim3(std::min<uint32_t>(max_giant, 16) * ZL_GIANT_PARTS), dim3(2 * TreeLanes<G>::N), TreeLanes<G>::N * sizeof(X), st,
@@ -572,25 +579,31 @@ struct MsmJob {
             const uint32_t fset = spread_t >= 0 ? (uint32_t)(W - 1) : 0xFFFFFFFFu, flog = (uint32_t)std::max(spread_t, 0);
             const uint32_t leaves = SETS * red_blocks;
             X* cur = red_levels == 0 ? d_sets : d_segs;
-            if (pair_tails && leaves > quad_max)
-                hipLaunchKernelGGL((k_msm_reduce_level0_pair<G, false>), dim3((leaves + 31) / 32), dim3(64), 0, st, d_buckets, H, red_g0, red_blocks, leaves, fset, flog, cur);
-            else if (octet && leaves <= quad_max)
-                hipLaunchKernelGGL((k_msm_reduce_level0_pair<G, true>), dim3((leaves + 7) / 8), dim3(64), 0, st, d_buckets, H, red_g0, red_blocks, leaves, fset, flog, cur);
-            else if (leaves <= quad_max)
-                hipLaunchKernelGGL((k_msm_reduce_level0<G, true>), dim3((4 * leaves + 63) / 64), dim3(64), 0, st, d_buckets, H, red_g0, red_blocks, leaves, fset, flog, cur);
-            else
-            hipLaunchKernelGGL((k_msm_reduce_level0<G>), dim3((leaves + 63) / 64), dim3(64), 0, st, d_buckets, H, red_g0, red_blocks, leaves, fset, flog, cur);
+            if constexpr (pair_ok()) {
+                if (leaves > quad_max)
+                    hipLaunchKernelGGL((k_msm_reduce_level0_pair<G, false>), dim3((leaves + 31) / 32), dim3(64), 0, st, d_buckets, H, red_g0, red_blocks, leaves, fset, flog, cur);
+                else
+                    hipLaunchKernelGGL((k_msm_reduce_level0_pair<G, true>), dim3((leaves + 7) / 8), dim3(64), 0, st, d_buckets, H, red_g0, red_blocks, leaves, fset, flog, cur);
+            } else {
+                if (leaves > quad_max)
+                    hipLaunchKernelGGL((k_msm_reduce_level0<G>), dim3((leaves + 63) / 64), dim3(64), 0, st, d_buckets, H, red_g0, red_blocks, leaves, fset, flog, cur);
+                else
+                    hipLaunchKernelGGL((k_msm_reduce_level0<G, true>), dim3((4 * leaves + 63) / 64), dim3(64), 0, st, d_buckets, H, red_g0, red_blocks, leaves, fset, flog, cur);
+            }
             for (uint32_t lv = 1; lv <= red_levels; lv++) {
                 const uint32_t nodes = red_blocks >> lv, lanes = SETS * nodes * (lv + 2);
                 X* nxt = lv == red_levels ? d_sets : ((lv & 1) ? d_stage1 : d_segs);
-                if (pair_tails && lanes > quad_max)
-                    hipLaunchKernelGGL((k_msm_reduce_tree_pair<G, false>), dim3((lanes + 31) / 32), dim3(64), 0, st, cur, nxt, lv, nodes, lanes);
-                else if (octet && lanes <= quad_max)
-                    hipLaunchKernelGGL((k_msm_reduce_tree_pair<G, true>), dim3((lanes + 7) / 8), dim3(64), 0, st, cur, nxt, lv, nodes, lanes);
-                else if (lanes <= quad_max)
-                    hipLaunchKernelGGL((k_msm_reduce_tree<G, true>), dim3((4 * lanes + 63) / 64), dim3(64), 0, st, cur, nxt, lv, nodes, lanes);
-                else
-                hipLaunchKernelGGL((k_msm_reduce_tree<G>), dim3((lanes + 63) / 64), dim3(64), 0, st, cur, nxt, lv, nodes, lanes);
+                if constexpr (pair_ok()) {
+                    if (lanes > quad_max)
+                        hipLaunchKernelGGL((k_msm_reduce_tree_pair<G, false>), dim3((lanes + 31) / 32), dim3(64), 0, st, cur, nxt, lv, nodes, lanes);
+                    else
+                        hipLaunchKernelGGL((k_msm_reduce_tree_pair<G, true>), dim3((lanes + 7) / 8), dim3(64), 0, st, cur, nxt, lv, nodes, lanes);
+                } else {
+                    if (lanes > quad_max)
+                        hipLaunchKernelGGL((k_msm_reduce_tree<G>), dim3((lanes + 63) / 64), dim3(64), 0, st, cur, nxt, lv, nodes, lanes);
+                    else
+                        hipLaunchKernelGGL((k_msm_reduce_tree<G, true>), dim3((4 * lanes + 63) / 64), dim3(64), 0, st, cur, nxt, lv, nodes, lanes);
+                }
                 cur = nxt;
             }
         }

@@ -7,24 +7,14 @@
 #include "zl_fq2pair.h"
 #include "zl_msm_common.h"
 
-// The merge / level-0 / tree kernels of an Fq2 group can compute in the inlining flavour of the field like the accumulation kernel
-// (-DZL_HOT_TAILS): their out-of-line Fq2 product routines take 56 scalar arguments, 24 of which travel on the stack (236 - 1260 B of
-// scratch per lane in round 2's G2 tails).
-#ifdef ZL_HOT_TAILS
-template <class F> using TailF = typename HotField<F>::type;
-#else
-template <class F> using TailF = F;
-#endif
 // one lane per bucket: empty -> infinity; cut into <= ZL_BIG_SPAN chunks -> fold partials; else defer to a block
 template <class G, bool QUAD = false>
-__global__ void __launch_bounds__(64, (QUAD && sizeof(XYZZ<typename G::F>) <= 256) ? 3 : 1) k_msm_merge(const uint32_t* __restrict__ offsets, uint32_t NB, XYZZ<typename G::F>* __restrict__ bucket_sums_,
-                                                   const XYZZ<typename G::F>* __restrict__ partials_, uint32_t* __restrict__ big_list,
+__global__ void __launch_bounds__(64, (QUAD && sizeof(XYZZ<typename G::F>) <= 256) ? 3 : 1) k_msm_merge(const uint32_t* __restrict__ offsets, uint32_t NB, XYZZ<typename G::F>* __restrict__ bucket_sums,
+                                                   const XYZZ<typename G::F>* __restrict__ partials, uint32_t* __restrict__ big_list,
                                                    uint32_t* __restrict__ big_count, uint32_t* __restrict__ giant_list, uint32_t* __restrict__ giant_count,
                                                    uint32_t ZL_CHUNK, uint32_t big_span) {
     ZL_SIDE_PRIO();
-    using F = TailF<typename G::F>;
-    XYZZ<F>* __restrict__ bucket_sums = reinterpret_cast<XYZZ<F>*>(bucket_sums_);
-    const XYZZ<F>* __restrict__ partials = reinterpret_cast<const XYZZ<F>*>(partials_);
+    using F = typename G::F;
     const uint32_t gt = blockIdx.x * blockDim.x + threadIdx.x;
     const uint32_t b = QUAD ? gt >> 2 : gt;  // QUAD: four lanes per bucket (zl_quad.h)
     const int sub = QUAD ? (int)(gt & 3u) : 0;
@@ -65,14 +55,12 @@ __global__ void __launch_bounds__(256) k_msm_fill_empty(const uint32_t* __restri
     bucket_sums[b] = XYZZ<typename G::F>::inf();
 }
 template <class G>
-__global__ void __launch_bounds__(64, sizeof(XYZZ<typename G::F>) <= 256 ? 3 : 1) k_msm_merge_cuts(const uint32_t* __restrict__ offsets, uint32_t NB, XYZZ<typename G::F>* __restrict__ bucket_sums_,
-                                                   const XYZZ<typename G::F>* __restrict__ partials_, uint32_t* __restrict__ big_list,
+__global__ void __launch_bounds__(64, sizeof(XYZZ<typename G::F>) <= 256 ? 3 : 1) k_msm_merge_cuts(const uint32_t* __restrict__ offsets, uint32_t NB, XYZZ<typename G::F>* __restrict__ bucket_sums,
+                                                   const XYZZ<typename G::F>* __restrict__ partials, uint32_t* __restrict__ big_list,
                                                    uint32_t* __restrict__ big_count, uint32_t* __restrict__ giant_list, uint32_t* __restrict__ giant_count,
                                                    uint32_t ZL_CHUNK, uint32_t big_span, uint32_t nchunks) {
     ZL_SIDE_PRIO();
-    using F = TailF<typename G::F>;
-    XYZZ<F>* __restrict__ bucket_sums = reinterpret_cast<XYZZ<F>*>(bucket_sums_);
-    const XYZZ<F>* __restrict__ partials = reinterpret_cast<const XYZZ<F>*>(partials_);
+    using F = typename G::F;
     const uint32_t t = blockIdx.x * blockDim.x + threadIdx.x + 1;  // boundary between chunks t - 1 and t
     if (t >= nchunks) return;
     const uint64_t p64 = (uint64_t)t * ZL_CHUNK;
@@ -176,7 +164,7 @@ __global__ void __launch_bounds__(64) k_msm_merge_giant2(XYZZ<typename G::F>* __
 // sum of the bases whose scalar is 1 (list built by the recoder): strided mixed adds per lane, block tree -> out[block]
 #define ZL_ONES_BLOCKS 128
 
-// Round 6: the kernel also FINISHES the sum (the last block to arrive folds the blocks' partial sums: no k_msm_window_sum launch behind it) and copies the job's two
+// Round 6: the kernel also FINISHES the sum (the last block to arrive folds the blocks' partial sums: no separate window-sum launch behind it) and copies the job's two
 // status words (entries accumulated, non-canonical-scalar flag) behind the result, so that one device-to-host copy fetches everything: two launches fewer on the
 // latency-bound chain of a small MSM.  `done`: a per-job counter word, zero at launch.
 template <class X>
@@ -253,13 +241,11 @@ __global__ void __launch_bounds__(TreeLanes<G>::N) k_msm_ones(const uint32_t* __
 // flat_set: the spread top window (k_msm_recode_wide): its buckets are weighted by their low spread_t bits only; level 0 is weightless
 // for it when spread_t == 0, and the host skips its S_b from bit spread_t on.
 template <class G, bool QUAD = false>
-__global__ void __launch_bounds__(64, TreeLanes<G>::N == 128 ? 1 : 2) k_msm_reduce_level0(const XYZZ<typename G::F>* __restrict__ buckets_, uint32_t H, uint32_t group, uint32_t blocks_per_set,
+__global__ void __launch_bounds__(64, TreeLanes<G>::N == 128 ? 1 : 2) k_msm_reduce_level0(const XYZZ<typename G::F>* __restrict__ buckets, uint32_t H, uint32_t group, uint32_t blocks_per_set,
                                                            uint32_t total_blocks, uint32_t flat_set, uint32_t flat_log,
-                                                           XYZZ<typename G::F>* __restrict__ out_ /* [set][block][2]: T, A */) {
+                                                           XYZZ<typename G::F>* __restrict__ out /* [set][block][2]: T, A */) {
     ZL_SIDE_PRIO();
-    using X = XYZZ<TailF<typename G::F>>;
-    const X* __restrict__ buckets = reinterpret_cast<const X*>(buckets_);
-    X* __restrict__ out = reinterpret_cast<X*>(out_);
+    using X = XYZZ<typename G::F>;
     const uint32_t gt = blockIdx.x * blockDim.x + threadIdx.x;
     const uint32_t t = QUAD ? gt >> 2 : gt;  // QUAD: four lanes per block of buckets (zl_quad.h)
     const int sub = QUAD ? (int)(gt & 3u) : 0;
@@ -289,12 +275,10 @@ __global__ void __launch_bounds__(64, TreeLanes<G>::N == 128 ? 1 : 2) k_msm_redu
 // one tree level: nodes of `level` (1-based) from the nodes of level - 1.  Node layout: [set][node][channel], ch_in = level + 1 channels
 // in (T, A, S_0 .. S_(level-2)), ch_out = level + 2 out.  One lane per (set, node, out channel).
 template <class G, bool QUAD = false>
-__global__ void __launch_bounds__(64) k_msm_reduce_tree(const XYZZ<typename G::F>* __restrict__ in_, XYZZ<typename G::F>* __restrict__ out_, uint32_t level,
+__global__ void __launch_bounds__(64) k_msm_reduce_tree(const XYZZ<typename G::F>* __restrict__ in, XYZZ<typename G::F>* __restrict__ out, uint32_t level,
                                                          uint32_t nodes_out_per_set, uint32_t total_lanes) {
     ZL_SIDE_PRIO();
-    using X = XYZZ<TailF<typename G::F>>;
-    const X* __restrict__ in = reinterpret_cast<const X*>(in_);
-    X* __restrict__ out = reinterpret_cast<X*>(out_);
+    using X = XYZZ<typename G::F>;
     const uint32_t gt = blockIdx.x * blockDim.x + threadIdx.x;
     const uint32_t t = QUAD ? gt >> 2 : gt;  // QUAD: four lanes per (set, node, channel) (zl_quad.h)
     const int sub = QUAD ? (int)(gt & 3u) : 0;
@@ -313,9 +297,10 @@ __global__ void __launch_bounds__(64) k_msm_reduce_tree(const XYZZ<typename G::F
     if (sub == 0) out[t] = acc;
 }
 // ------------------------------------------------------------------------------------------------ Fq2 groups on lane pairs (zl_fq2pair.h)
-// The same three kernels with TWO lanes per item (lane i of a row of 16: the c0 components, lane i ^ 8: the c1 components), for launches that fill the
-// machine: the one-lane forms above hold three Fq2 points across out-of-line product calls -- 512 registers and 540-780 B of scratch per lane, one wave per
-// SIMD -- where a half-point lane stays inside 256 registers with the product scans inlined.  Same buffers, same item numbering.
+// The same three kernels for the Fq2 groups (the one-lane / four-lane forms above are the G1 groups' only) with TWO lanes per item (lane i of a row of 16:
+// the c0 components, lane i ^ 8: the c1 components), for launches that fill the machine: a one-lane Fq2 form held three Fq2 points across out-of-line product
+// calls -- 512 registers and 540-780 B of scratch per lane, one wave per SIMD (rounds 2-5) -- where a half-point lane stays inside 256 registers with the product
+// scans inlined.  Same buffers, same item numbering.
 // QUAD: eight lanes per item (zl_fq2pair.h: four per half) for launches that do NOT fill the machine -- the chain of a small G2 MSM
 template <class G, bool QUAD = false>
 __global__ void __launch_bounds__(64, 2) k_msm_merge_pair(const uint32_t* __restrict__ offsets, uint32_t NB, XYZZ<typename G::F>* __restrict__ bucket_sums,
@@ -323,27 +308,26 @@ __global__ void __launch_bounds__(64, 2) k_msm_merge_pair(const uint32_t* __rest
                                                    uint32_t* __restrict__ big_count, uint32_t* __restrict__ giant_list, uint32_t* __restrict__ giant_count,
                                                    uint32_t ZL_CHUNK, uint32_t big_span) {
     using B = typename PairBase<typename G::F>::type;
-    if constexpr (!std::is_void<B>::value) {
-        ZL_SIDE_PRIO();
-        using X = XYZZ<Fp2H<B>>;
-        const int half = zl::pair_half(), sub = (int)(threadIdx.x & 3u);
-        const uint32_t b = QUAD ? ZL_OCTET_ITEM() : ZL_PAIR_ITEM();
-        if (b >= NB) return;
-        const uint32_t s = offsets[b], e = offsets[b + 1];
-        if (s == e) { pair_store(&bucket_sums[b], half, X::inf()); return; }
-        const uint32_t t0 = s / ZL_CHUNK, t1 = (e - 1) / ZL_CHUNK;
-        if (t0 == t1) return;
-        const bool first = half == 0 && (!QUAD || sub == 0);
-        if (t1 - t0 + 1 > ZL_GIANT_SPAN) { if (first) giant_list[atomicAdd(giant_count, 1u)] = b; return; }
-        if (t1 - t0 + 1 > big_span) { if (first) big_list[atomicAdd(big_count, 1u)] = b; return; }
-        X acc = X::inf();
-        for (uint32_t t = t0; t <= t1; t++) {
-            const X p = pair_load(&partials[(size_t)2 * t + (s <= t * ZL_CHUNK ? 0 : 1)], half);
-            if constexpr (QUAD) zl::add_full_quad(acc, p, sub);
-            else zl::add_full(acc, p);
-        }
-        pair_store(&bucket_sums[b], half, acc);
+    static_assert(!std::is_void<B>::value, "lane-pair kernels: Fq2 groups on 28-bit limbs only");
+    ZL_SIDE_PRIO();
+    using X = XYZZ<Fp2H<B>>;
+    const int half = zl::pair_half(), sub = (int)(threadIdx.x & 3u);
+    const uint32_t b = QUAD ? ZL_OCTET_ITEM() : ZL_PAIR_ITEM();
+    if (b >= NB) return;
+    const uint32_t s = offsets[b], e = offsets[b + 1];
+    if (s == e) { pair_store(&bucket_sums[b], half, X::inf()); return; }
+    const uint32_t t0 = s / ZL_CHUNK, t1 = (e - 1) / ZL_CHUNK;
+    if (t0 == t1) return;
+    const bool first = half == 0 && (!QUAD || sub == 0);
+    if (t1 - t0 + 1 > ZL_GIANT_SPAN) { if (first) giant_list[atomicAdd(giant_count, 1u)] = b; return; }
+    if (t1 - t0 + 1 > big_span) { if (first) big_list[atomicAdd(big_count, 1u)] = b; return; }
+    X acc = X::inf();
+    for (uint32_t t = t0; t <= t1; t++) {
+        const X p = pair_load(&partials[(size_t)2 * t + (s <= t * ZL_CHUNK ? 0 : 1)], half);
+        if constexpr (QUAD) zl::add_full_quad(acc, p, sub);
+        else zl::add_full(acc, p);
     }
+    pair_store(&bucket_sums[b], half, acc);
 }
 template <class G>
 __global__ void __launch_bounds__(64, 2) k_msm_merge_cuts_pair(const uint32_t* __restrict__ offsets, uint32_t NB, XYZZ<typename G::F>* __restrict__ bucket_sums,
@@ -351,28 +335,27 @@ __global__ void __launch_bounds__(64, 2) k_msm_merge_cuts_pair(const uint32_t* _
                                                    uint32_t* __restrict__ big_count, uint32_t* __restrict__ giant_list, uint32_t* __restrict__ giant_count,
                                                    uint32_t ZL_CHUNK, uint32_t big_span, uint32_t nchunks) {
     using B = typename PairBase<typename G::F>::type;
-    if constexpr (!std::is_void<B>::value) {
-        ZL_SIDE_PRIO();
-        using X = XYZZ<Fp2H<B>>;
-        const int half = zl::pair_half();
-        const uint32_t t = ZL_PAIR_ITEM() + 1;  // (k_msm_merge_cuts: one lane PAIR per chunk boundary)
-        if (t >= nchunks) return;
-        const uint64_t p64 = (uint64_t)t * ZL_CHUNK;
-        if (p64 >= offsets[NB]) return;
-        const uint32_t p = (uint32_t)p64;
-        const uint32_t b = zl_bucket_of_entry(offsets, NB, p);
-        const uint32_t s = offsets[b], e = offsets[b + 1];
-        if (s == p || s / ZL_CHUNK != t - 1) return;
-        const uint32_t t0 = t - 1, t1 = (e - 1) / ZL_CHUNK;
-        if (t1 - t0 + 1 > ZL_GIANT_SPAN) { if (half == 0) giant_list[atomicAdd(giant_count, 1u)] = b; return; }
-        if (t1 - t0 + 1 > big_span) { if (half == 0) big_list[atomicAdd(big_count, 1u)] = b; return; }
-        X acc = X::inf();
-        for (uint32_t tt = t0; tt <= t1; tt++) {
-            const X q = pair_load(&partials[(size_t)2 * tt + (s <= tt * ZL_CHUNK ? 0 : 1)], half);
-            zl::add_full(acc, q);
-        }
-        pair_store(&bucket_sums[b], half, acc);
+    static_assert(!std::is_void<B>::value, "lane-pair kernels: Fq2 groups on 28-bit limbs only");
+    ZL_SIDE_PRIO();
+    using X = XYZZ<Fp2H<B>>;
+    const int half = zl::pair_half();
+    const uint32_t t = ZL_PAIR_ITEM() + 1;  // (k_msm_merge_cuts: one lane PAIR per chunk boundary)
+    if (t >= nchunks) return;
+    const uint64_t p64 = (uint64_t)t * ZL_CHUNK;
+    if (p64 >= offsets[NB]) return;
+    const uint32_t p = (uint32_t)p64;
+    const uint32_t b = zl_bucket_of_entry(offsets, NB, p);
+    const uint32_t s = offsets[b], e = offsets[b + 1];
+    if (s == p || s / ZL_CHUNK != t - 1) return;
+    const uint32_t t0 = t - 1, t1 = (e - 1) / ZL_CHUNK;
+    if (t1 - t0 + 1 > ZL_GIANT_SPAN) { if (half == 0) giant_list[atomicAdd(giant_count, 1u)] = b; return; }
+    if (t1 - t0 + 1 > big_span) { if (half == 0) big_list[atomicAdd(big_count, 1u)] = b; return; }
+    X acc = X::inf();
+    for (uint32_t tt = t0; tt <= t1; tt++) {
+        const X q = pair_load(&partials[(size_t)2 * tt + (s <= tt * ZL_CHUNK ? 0 : 1)], half);
+        zl::add_full(acc, q);
     }
+    pair_store(&bucket_sums[b], half, acc);
 }
 #ifndef ZL_L0_PAIR_WAVES
 #define ZL_L0_PAIR_WAVES 2  // (1 = no scratch at one wave per SIMD: the A/B of profiles/r06_l0_pair_waves_ab.log)
@@ -381,55 +364,53 @@ template <class G, bool QUAD = false>
 __global__ void __launch_bounds__(64, ZL_L0_PAIR_WAVES) k_msm_reduce_level0_pair(const XYZZ<typename G::F>* __restrict__ buckets, uint32_t H, uint32_t group, uint32_t blocks_per_set,
                                                            uint32_t total_blocks, uint32_t flat_set, uint32_t flat_log, XYZZ<typename G::F>* __restrict__ out) {
     using B = typename PairBase<typename G::F>::type;
-    if constexpr (!std::is_void<B>::value) {
-        ZL_SIDE_PRIO();
-        using X = XYZZ<Fp2H<B>>;
-        const int half = zl::pair_half(), sub = (int)(threadIdx.x & 3u);
-        const uint32_t t = QUAD ? ZL_OCTET_ITEM() : ZL_PAIR_ITEM();
-        if (t >= total_blocks) return;
-        const uint32_t set = t / blocks_per_set, blk = t % blocks_per_set;
-        const uint32_t i0 = blk * group, i1 = min(H, i0 + group);
-        const size_t base = (size_t)set * H;
-        const bool flat = set == flat_set && flat_log == 0;
-        X run = X::inf(), wsum = X::inf();
-        for (uint32_t i = i1; i > i0; i--) {
-            const X Bk = pair_load(&buckets[base + (i - 1)], half);
-            if constexpr (QUAD) {
-                zl::add_full_quad(run, Bk, sub);
-                if (!flat) zl::add_full_quad(wsum, run, sub);
-            } else {
-                zl::add_full(run, Bk);
-                if (!flat) zl::add_full(wsum, run);
-            }
+    static_assert(!std::is_void<B>::value, "lane-pair kernels: Fq2 groups on 28-bit limbs only");
+    ZL_SIDE_PRIO();
+    using X = XYZZ<Fp2H<B>>;
+    const int half = zl::pair_half(), sub = (int)(threadIdx.x & 3u);
+    const uint32_t t = QUAD ? ZL_OCTET_ITEM() : ZL_PAIR_ITEM();
+    if (t >= total_blocks) return;
+    const uint32_t set = t / blocks_per_set, blk = t % blocks_per_set;
+    const uint32_t i0 = blk * group, i1 = min(H, i0 + group);
+    const size_t base = (size_t)set * H;
+    const bool flat = set == flat_set && flat_log == 0;
+    X run = X::inf(), wsum = X::inf();
+    for (uint32_t i = i1; i > i0; i--) {
+        const X Bk = pair_load(&buckets[base + (i - 1)], half);
+        if constexpr (QUAD) {
+            zl::add_full_quad(run, Bk, sub);
+            if (!flat) zl::add_full_quad(wsum, run, sub);
+        } else {
+            zl::add_full(run, Bk);
+            if (!flat) zl::add_full(wsum, run);
         }
-        pair_store(&out[(size_t)2 * t], half, run);
-        if (flat) pair_store(&out[(size_t)2 * t + 1], half, run);
-        else pair_store(&out[(size_t)2 * t + 1], half, wsum);
     }
+    pair_store(&out[(size_t)2 * t], half, run);
+    if (flat) pair_store(&out[(size_t)2 * t + 1], half, run);
+    else pair_store(&out[(size_t)2 * t + 1], half, wsum);
 }
 template <class G, bool QUAD = false>
 __global__ void __launch_bounds__(64, 2) k_msm_reduce_tree_pair(const XYZZ<typename G::F>* __restrict__ in, XYZZ<typename G::F>* __restrict__ out, uint32_t level,
                                                          uint32_t nodes_out_per_set, uint32_t total_lanes) {
     using B = typename PairBase<typename G::F>::type;
-    if constexpr (!std::is_void<B>::value) {
-        ZL_SIDE_PRIO();
-        using X = XYZZ<Fp2H<B>>;
-        const int half = zl::pair_half(), sub = (int)(threadIdx.x & 3u);
-        const uint32_t t = QUAD ? ZL_OCTET_ITEM() : ZL_PAIR_ITEM();
-        if (t >= total_lanes) return;
-        const uint32_t ch_out = level + 2, ch_in = level + 1;
-        const uint32_t ch = t % ch_out, node = (t / ch_out) % nodes_out_per_set, set = t / (ch_out * nodes_out_per_set);
-        const size_t left = ((size_t)set * nodes_out_per_set * 2 + (size_t)2 * node) * ch_in, right = left + ch_in;
-        if (ch == ch_out - 1) {
-            pair_store(&out[t], half, pair_load(&in[right], half));
-            return;
-        }
-        X acc = pair_load(&in[left + ch], half);
-        const X o = pair_load(&in[right + ch], half);
-        if constexpr (QUAD) zl::add_full_quad(acc, o, sub);
-        else zl::add_full(acc, o);
-        pair_store(&out[t], half, acc);
+    static_assert(!std::is_void<B>::value, "lane-pair kernels: Fq2 groups on 28-bit limbs only");
+    ZL_SIDE_PRIO();
+    using X = XYZZ<Fp2H<B>>;
+    const int half = zl::pair_half(), sub = (int)(threadIdx.x & 3u);
+    const uint32_t t = QUAD ? ZL_OCTET_ITEM() : ZL_PAIR_ITEM();
+    if (t >= total_lanes) return;
+    const uint32_t ch_out = level + 2, ch_in = level + 1;
+    const uint32_t ch = t % ch_out, node = (t / ch_out) % nodes_out_per_set, set = t / (ch_out * nodes_out_per_set);
+    const size_t left = ((size_t)set * nodes_out_per_set * 2 + (size_t)2 * node) * ch_in, right = left + ch_in;
+    if (ch == ch_out - 1) {
+        pair_store(&out[t], half, pair_load(&in[right], half));
+        return;
     }
+    X acc = pair_load(&in[left + ch], half);
+    const X o = pair_load(&in[right + ch], half);
+    if constexpr (QUAD) zl::add_full_quad(acc, o, sub);
+    else zl::add_full(acc, o);
+    pair_store(&out[t], half, acc);
 }
 // The block-tree kernels on lane pairs (round 6): the heavy buckets of a skewed input -- and a Groth16 witness IS skewed: the table-mode G2 MSM of the 958 465-constraint
 // proof spent 0.56 ms in k_msm_merge_big<BlsG2> and 1.3 ms in k_msm_merge_giant<BlsG2> per proof, one-lane kernels at 512 registers + 716 B of scratch
@@ -458,26 +439,25 @@ __global__ void __launch_bounds__(2 * TreeLanes<G>::N) k_msm_merge_big_pair(cons
                                                         const XYZZ<typename G::F>* __restrict__ partials, const uint32_t* __restrict__ big_list,
                                                         const uint32_t* __restrict__ big_count, uint32_t ZL_CHUNK) {
     using B = typename PairBase<typename G::F>::type;
-    if constexpr (!std::is_void<B>::value) {
-        ZL_SIDE_PRIO();
-        using X = XYZZ<Fp2H<B>>;
-        constexpr uint32_t N = TreeLanes<G>::N;
-        extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-        XYZZ<typename G::F>* sh = reinterpret_cast<XYZZ<typename G::F>*>(smem);
-        const int half = zl::pair_half();
-        const uint32_t item = ZL_PAIR_ITEM_IN_BLOCK();
-        for (uint32_t it = blockIdx.x; it < *big_count; it += gridDim.x) {
-            const uint32_t b = big_list[it];
-            const uint32_t s = offsets[b], e = offsets[b + 1];
-            const uint32_t t0 = s / ZL_CHUNK, t1 = (e - 1) / ZL_CHUNK;
-            X acc = X::inf();
-            for (uint32_t t = t0 + item; t <= t1; t += N) {
-                const X p = pair_load(&partials[(size_t)2 * t + (s <= t * ZL_CHUNK ? 0 : 1)], half);
-                zl::add_full(acc, p);
-            }
-            zl_block_tree_pair<G, N>(sh, acc, item, half);
-            if (item == 0) pair_store(&bucket_sums[b], half, acc);
+    static_assert(!std::is_void<B>::value, "lane-pair kernels: Fq2 groups on 28-bit limbs only");
+    ZL_SIDE_PRIO();
+    using X = XYZZ<Fp2H<B>>;
+    constexpr uint32_t N = TreeLanes<G>::N;
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    XYZZ<typename G::F>* sh = reinterpret_cast<XYZZ<typename G::F>*>(smem);
+    const int half = zl::pair_half();
+    const uint32_t item = ZL_PAIR_ITEM_IN_BLOCK();
+    for (uint32_t it = blockIdx.x; it < *big_count; it += gridDim.x) {
+        const uint32_t b = big_list[it];
+        const uint32_t s = offsets[b], e = offsets[b + 1];
+        const uint32_t t0 = s / ZL_CHUNK, t1 = (e - 1) / ZL_CHUNK;
+        X acc = X::inf();
+        for (uint32_t t = t0 + item; t <= t1; t += N) {
+            const X p = pair_load(&partials[(size_t)2 * t + (s <= t * ZL_CHUNK ? 0 : 1)], half);
+            zl::add_full(acc, p);
         }
+        zl_block_tree_pair<G, N>(sh, acc, item, half);
+        if (item == 0) pair_store(&bucket_sums[b], half, acc);
     }
 }
 template <class G>
@@ -485,29 +465,28 @@ __global__ void __launch_bounds__(2 * TreeLanes<G>::N) k_msm_merge_giant_pair(co
                                                           const XYZZ<typename G::F>* __restrict__ partials, const uint32_t* __restrict__ giant_list,
                                                           const uint32_t* __restrict__ giant_count, uint32_t ZL_CHUNK) {
     using B = typename PairBase<typename G::F>::type;
-    if constexpr (!std::is_void<B>::value) {
-        ZL_SIDE_PRIO();
-        using X = XYZZ<Fp2H<B>>;
-        constexpr uint32_t N = TreeLanes<G>::N;
-        extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-        XYZZ<typename G::F>* sh = reinterpret_cast<XYZZ<typename G::F>*>(smem);
-        const int half = zl::pair_half();
-        const uint32_t item = ZL_PAIR_ITEM_IN_BLOCK();
-        const uint32_t part = blockIdx.x % ZL_GIANT_PARTS;
-        for (uint32_t it = blockIdx.x / ZL_GIANT_PARTS; it < *giant_count; it += gridDim.x / ZL_GIANT_PARTS) {
-            const uint32_t b = giant_list[it];
-            const uint32_t s = offsets[b], e = offsets[b + 1];
-            const uint32_t t0 = s / ZL_CHUNK, t1 = (e - 1) / ZL_CHUNK;
-            const uint32_t per = (t1 - t0 + ZL_GIANT_PARTS) / ZL_GIANT_PARTS;
-            const uint32_t lo = t0 + part * per, hi = min(t1 + 1, lo + per);
-            X acc = X::inf();
-            for (uint32_t t = lo + item; t < hi; t += N) {
-                const X p = pair_load(&partials[(size_t)2 * t + (s <= t * ZL_CHUNK ? 0 : 1)], half);
-                zl::add_full(acc, p);
-            }
-            zl_block_tree_pair<G, N>(sh, acc, item, half);
-            if (item == 0) pair_store(&giant_tmp[(size_t)it * ZL_GIANT_PARTS + part], half, acc);
+    static_assert(!std::is_void<B>::value, "lane-pair kernels: Fq2 groups on 28-bit limbs only");
+    ZL_SIDE_PRIO();
+    using X = XYZZ<Fp2H<B>>;
+    constexpr uint32_t N = TreeLanes<G>::N;
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    XYZZ<typename G::F>* sh = reinterpret_cast<XYZZ<typename G::F>*>(smem);
+    const int half = zl::pair_half();
+    const uint32_t item = ZL_PAIR_ITEM_IN_BLOCK();
+    const uint32_t part = blockIdx.x % ZL_GIANT_PARTS;
+    for (uint32_t it = blockIdx.x / ZL_GIANT_PARTS; it < *giant_count; it += gridDim.x / ZL_GIANT_PARTS) {
+        const uint32_t b = giant_list[it];
+        const uint32_t s = offsets[b], e = offsets[b + 1];
+        const uint32_t t0 = s / ZL_CHUNK, t1 = (e - 1) / ZL_CHUNK;
+        const uint32_t per = (t1 - t0 + ZL_GIANT_PARTS) / ZL_GIANT_PARTS;
+        const uint32_t lo = t0 + part * per, hi = min(t1 + 1, lo + per);
+        X acc = X::inf();
+        for (uint32_t t = lo + item; t < hi; t += N) {
+            const X p = pair_load(&partials[(size_t)2 * t + (s <= t * ZL_CHUNK ? 0 : 1)], half);
+            zl::add_full(acc, p);
         }
+        zl_block_tree_pair<G, N>(sh, acc, item, half);
+        if (item == 0) pair_store(&giant_tmp[(size_t)it * ZL_GIANT_PARTS + part], half, acc);
     }
 }
 // stage 2: one block of ZL_GIANT_PARTS pairs per giant bucket (the one-lane kernel folds the 32 sums serially: 32 Fq2 additions of latency)
@@ -515,79 +494,47 @@ template <class G>
 __global__ void __launch_bounds__(2 * ZL_GIANT_PARTS) k_msm_merge_giant2_pair(XYZZ<typename G::F>* __restrict__ bucket_sums, XYZZ<typename G::F>* __restrict__ giant_tmp,
                                                           const uint32_t* __restrict__ giant_list, const uint32_t* __restrict__ giant_count) {
     using B = typename PairBase<typename G::F>::type;
-    if constexpr (!std::is_void<B>::value) {
-        ZL_SIDE_PRIO();
-        using X = XYZZ<Fp2H<B>>;
-        const int half = zl::pair_half();
-        const uint32_t item = ZL_PAIR_ITEM_IN_BLOCK();
-        for (uint32_t it = blockIdx.x; it < *giant_count; it += gridDim.x) {
-            XYZZ<typename G::F>* sh = giant_tmp + (size_t)it * ZL_GIANT_PARTS;  // the tree runs in place over the bucket's 32 part sums (global memory: 16 KB, once per giant bucket)
-            X acc = pair_load(&sh[item], half);
-            __syncthreads();
-            zl_block_tree_pair<G, ZL_GIANT_PARTS>(sh, acc, item, half);
-            if (item == 0) {
-                pair_store(&bucket_sums[giant_list[it]], half, acc);
-            }
-        }
-    }
-}
-// tree-sum of segment results.  Block b belongs to set (b / parts) and sums `count` consecutive elements starting at
-// set * set_stride + (b % parts) * count (clipped to the set): parts = 1 -> one block per set; parts > 1 -> stage 1 of a
-// two-stage sum for sets with many segments.
-template <class G>
-__global__ void __launch_bounds__(TreeLanes<G>::N) k_msm_window_sum(const XYZZ<typename G::F>* __restrict__ seg_out, uint32_t count, uint32_t set_stride,
-                                                         uint32_t parts, XYZZ<typename G::F>* __restrict__ out, const uint32_t* __restrict__ zero_if_zero) {
+    static_assert(!std::is_void<B>::value, "lane-pair kernels: Fq2 groups on 28-bit limbs only");
     ZL_SIDE_PRIO();
-    using F = typename G::F;
-    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    XYZZ<F>* sh = reinterpret_cast<XYZZ<F>*>(smem);
-    if (zero_if_zero && *zero_if_zero == 0) {  // nothing was listed: every part is the point at infinity
-        if (threadIdx.x == 0) out[blockIdx.x] = XYZZ<F>::inf();
-        return;
-    }
-    const uint32_t set = blockIdx.x / parts, part = blockIdx.x % parts;
-    const uint32_t lo = part * count, hi = min(set_stride, lo + count);
-    XYZZ<F> acc = XYZZ<F>::inf();
-    for (uint32_t s = lo + threadIdx.x; s < hi; s += blockDim.x) {
-        const XYZZ<F> p = seg_out[(size_t)set * set_stride + s];
-        zl::add_full(acc, p);
-    }
-    sh[threadIdx.x] = acc;
-    __syncthreads();
-    for (int off = TreeLanes<G>::N / 2; off > 0; off >>= 1) {
-        if ((int)threadIdx.x < off) {
-            XYZZ<F> a = sh[threadIdx.x];
-            const XYZZ<F> o = sh[threadIdx.x + off];
-            zl::add_full(a, o);
-            sh[threadIdx.x] = a;
-        }
+    using X = XYZZ<Fp2H<B>>;
+    const int half = zl::pair_half();
+    const uint32_t item = ZL_PAIR_ITEM_IN_BLOCK();
+    for (uint32_t it = blockIdx.x; it < *giant_count; it += gridDim.x) {
+        XYZZ<typename G::F>* sh = giant_tmp + (size_t)it * ZL_GIANT_PARTS;  // the tree runs in place over the bucket's 32 part sums (global memory: 16 KB, once per giant bucket)
+        X acc = pair_load(&sh[item], half);
         __syncthreads();
+        zl_block_tree_pair<G, ZL_GIANT_PARTS>(sh, acc, item, half);
+        if (item == 0) {
+            pair_store(&bucket_sums[giant_list[it]], half, acc);
+        }
     }
-    if (threadIdx.x == 0) out[blockIdx.x] = sh[0];
 }
 
-// every instantiation MsmJob<G>::tail launches (X as in zl_msm_accumulate.h)
-#define ZL_MSM_TAIL_KERNELS(X, G) \
+// every instantiation MsmJob<G>::tail launches, one list per kind of group (X as in zl_msm_accumulate.h)
+#define ZL_MSM_TAIL_KERNELS_COMMON(X, G) \
+    X template __global__ void k_msm_fill_empty<G>(const uint32_t*, uint32_t, XYZZ<typename G::F>*); \
+    X template __global__ void k_msm_ones<G>(const uint32_t*, const uint32_t*, const Affine<typename G::F>*, XYZZ<typename G::F>*, const Affine<typename G::F>*, uint32_t, XYZZ<typename G::F>*, uint32_t*, const uint32_t*);
+#define ZL_MSM_TAIL_KERNELS_G1(X, G) \
+    ZL_MSM_TAIL_KERNELS_COMMON(X, G) \
     X template __global__ void k_msm_merge<G, false>(const uint32_t*, uint32_t, XYZZ<typename G::F>*, const XYZZ<typename G::F>*, uint32_t*, uint32_t*, uint32_t*, uint32_t*, uint32_t, uint32_t); \
     X template __global__ void k_msm_merge<G, true>(const uint32_t*, uint32_t, XYZZ<typename G::F>*, const XYZZ<typename G::F>*, uint32_t*, uint32_t*, uint32_t*, uint32_t*, uint32_t, uint32_t); \
+    X template __global__ void k_msm_merge_cuts<G>(const uint32_t*, uint32_t, XYZZ<typename G::F>*, const XYZZ<typename G::F>*, uint32_t*, uint32_t*, uint32_t*, uint32_t*, uint32_t, uint32_t, uint32_t); \
     X template __global__ void k_msm_merge_big<G>(const uint32_t*, XYZZ<typename G::F>*, const XYZZ<typename G::F>*, const uint32_t*, const uint32_t*, uint32_t); \
     X template __global__ void k_msm_merge_giant<G>(const uint32_t*, XYZZ<typename G::F>*, const XYZZ<typename G::F>*, const uint32_t*, const uint32_t*, uint32_t); \
     X template __global__ void k_msm_merge_giant2<G>(XYZZ<typename G::F>*, const XYZZ<typename G::F>*, const uint32_t*, const uint32_t*); \
-    X template __global__ void k_msm_ones<G>(const uint32_t*, const uint32_t*, const Affine<typename G::F>*, XYZZ<typename G::F>*, const Affine<typename G::F>*, uint32_t, XYZZ<typename G::F>*, uint32_t*, const uint32_t*); \
     X template __global__ void k_msm_reduce_level0<G, false>(const XYZZ<typename G::F>*, uint32_t, uint32_t, uint32_t, uint32_t, uint32_t, uint32_t, XYZZ<typename G::F>*); \
     X template __global__ void k_msm_reduce_level0<G, true>(const XYZZ<typename G::F>*, uint32_t, uint32_t, uint32_t, uint32_t, uint32_t, uint32_t, XYZZ<typename G::F>*); \
     X template __global__ void k_msm_reduce_tree<G, false>(const XYZZ<typename G::F>*, XYZZ<typename G::F>*, uint32_t, uint32_t, uint32_t); \
-    X template __global__ void k_msm_reduce_tree<G, true>(const XYZZ<typename G::F>*, XYZZ<typename G::F>*, uint32_t, uint32_t, uint32_t); \
-    X template __global__ void k_msm_fill_empty<G>(const uint32_t*, uint32_t, XYZZ<typename G::F>*); \
-    X template __global__ void k_msm_merge_cuts<G>(const uint32_t*, uint32_t, XYZZ<typename G::F>*, const XYZZ<typename G::F>*, uint32_t*, uint32_t*, uint32_t*, uint32_t*, uint32_t, uint32_t, uint32_t); \
+    X template __global__ void k_msm_reduce_tree<G, true>(const XYZZ<typename G::F>*, XYZZ<typename G::F>*, uint32_t, uint32_t, uint32_t);
+#define ZL_MSM_TAIL_KERNELS_G2(X, G) \
+    ZL_MSM_TAIL_KERNELS_COMMON(X, G) \
+    X template __global__ void k_msm_merge_pair<G, false>(const uint32_t*, uint32_t, XYZZ<typename G::F>*, const XYZZ<typename G::F>*, uint32_t*, uint32_t*, uint32_t*, uint32_t*, uint32_t, uint32_t); \
+    X template __global__ void k_msm_merge_pair<G, true>(const uint32_t*, uint32_t, XYZZ<typename G::F>*, const XYZZ<typename G::F>*, uint32_t*, uint32_t*, uint32_t*, uint32_t*, uint32_t, uint32_t); \
     X template __global__ void k_msm_merge_cuts_pair<G>(const uint32_t*, uint32_t, XYZZ<typename G::F>*, const XYZZ<typename G::F>*, uint32_t*, uint32_t*, uint32_t*, uint32_t*, uint32_t, uint32_t, uint32_t); \
     X template __global__ void k_msm_merge_big_pair<G>(const uint32_t*, XYZZ<typename G::F>*, const XYZZ<typename G::F>*, const uint32_t*, const uint32_t*, uint32_t); \
     X template __global__ void k_msm_merge_giant_pair<G>(const uint32_t*, XYZZ<typename G::F>*, const XYZZ<typename G::F>*, const uint32_t*, const uint32_t*, uint32_t); \
     X template __global__ void k_msm_merge_giant2_pair<G>(XYZZ<typename G::F>*, XYZZ<typename G::F>*, const uint32_t*, const uint32_t*); \
-    X template __global__ void k_msm_merge_pair<G, false>(const uint32_t*, uint32_t, XYZZ<typename G::F>*, const XYZZ<typename G::F>*, uint32_t*, uint32_t*, uint32_t*, uint32_t*, uint32_t, uint32_t); \
-    X template __global__ void k_msm_merge_pair<G, true>(const uint32_t*, uint32_t, XYZZ<typename G::F>*, const XYZZ<typename G::F>*, uint32_t*, uint32_t*, uint32_t*, uint32_t*, uint32_t, uint32_t); \
     X template __global__ void k_msm_reduce_level0_pair<G, false>(const XYZZ<typename G::F>*, uint32_t, uint32_t, uint32_t, uint32_t, uint32_t, uint32_t, XYZZ<typename G::F>*); \
     X template __global__ void k_msm_reduce_level0_pair<G, true>(const XYZZ<typename G::F>*, uint32_t, uint32_t, uint32_t, uint32_t, uint32_t, uint32_t, XYZZ<typename G::F>*); \
     X template __global__ void k_msm_reduce_tree_pair<G, false>(const XYZZ<typename G::F>*, XYZZ<typename G::F>*, uint32_t, uint32_t, uint32_t); \
-    X template __global__ void k_msm_reduce_tree_pair<G, true>(const XYZZ<typename G::F>*, XYZZ<typename G::F>*, uint32_t, uint32_t, uint32_t); \
-    X template __global__ void k_msm_window_sum<G>(const XYZZ<typename G::F>*, uint32_t, uint32_t, uint32_t, XYZZ<typename G::F>*, const uint32_t*);
+    X template __global__ void k_msm_reduce_tree_pair<G, true>(const XYZZ<typename G::F>*, XYZZ<typename G::F>*, uint32_t, uint32_t, uint32_t);

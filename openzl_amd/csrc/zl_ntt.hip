@@ -18,16 +18,6 @@
 #include "zl_ctx.h"
 #include "zl_field28r.h"
 
-// first / last two-stage round fused with the global loads / stores (measured, 2^24: no gain over staging through LDS: the fused kernel needs
-// 145-158 VGPRs, one workgroup per CU, 3.0 ms; capped at 128 VGPRs it spills and ties with the unfused form at 2.6 ms)
-#ifndef ZL_NTT_FUSE_LOAD
-#define ZL_NTT_FUSE_LOAD 0
-#endif
-#ifndef ZL_NTT_FUSE_STORE
-#define ZL_NTT_FUSE_STORE 0
-#endif
-#define NTT_THREADS 512
-#define NTT_TILE 2048   // elements per workgroup tile (64 KiB of LDS)
 #define NTT_MAX_S 10
 
 struct NttArgs {
@@ -46,36 +36,11 @@ struct NttArgs {
     uint64_t in_batch, out_batch;  // bytes between the vectors of a batch (blockIdx.y = vector): equal-size transforms of one launch (Groth16's witness map: three at a time)
 };
 
-template <class F>
-__device__ __forceinline__ F lds_load(const uint32_t* sh, uint32_t pos) {
-    F r;
-#pragma unroll
-    for (int k = 0; k < F::N; k++) r.l[k] = sh[k * NTT_TILE + pos];
-    return r;
-}
-template <class F>
-__device__ __forceinline__ void lds_store(uint32_t* sh, uint32_t pos, const F& v) {
-#pragma unroll
-    for (int k = 0; k < F::N; k++) sh[k * NTT_TILE + pos] = v.l[k];
-}
-#ifndef ZL_NTT_ROW_SWIZZLE
-#define ZL_NTT_ROW_SWIZZLE 0  // measured: conflicts 57 % -> 0, time +1 % (the passes are bound by VALU issue, the LDS cycles were hidden): off; -DZL_NTT_ROW_SWIZZLE=1 rebuilds it
-#endif
 __device__ __forceinline__ uint32_t tile_pos(uint32_t row, uint32_t col, uint32_t logC) {
     // swizzle columns so that consecutive rows of one column fall into different LDS banks
     uint32_t C = 1u << logC;
     uint32_t rows_per_wrap_log = logC >= 5 ? 0 : 5 - logC;
     uint32_t cs = (col + (row >> rows_per_wrap_log)) & (C - 1);
-#if ZL_NTT_ROW_SWIZZLE
-    // Round 6 (profiles/r06_ntt_lds_counters.txt: SQ_LDS_BANK_CONFLICT = 57 % of SQ_LDS_IDX_ACTIVE in a 2^8-point pass): with four-column rows (the 2^8 x 4 tiles
-    // of every pass of a 2^24 transform) a row owns the four banks (row mod 8) * 4 .. + 3 of the 32 that ds_read2_b32 / ds_write see, and the column swizzle
-    // above only permutes inside that group.  The rows a half-wave (32 lanes = 8 rows x 4 columns, the conflict domain) touches at once differ in row bits
-    // {0,1,2} (load phase, butterfly distances 64 and 16), {0,1,4} (distance 4), {2,3,4} (distance 1) and {5,6,7} (store phase: bit-reversed rows) -- the
-    // last three put 2, 4 and 8 rows on one bank group.  XOR-ing the low three row bits with b0 = r4 ^ r5, b1 = r3 ^ r6, b2 = r4 ^ r7 makes the bank group a
-    // GF(2)-linear function of the row whose restriction to each of those four bit sets is invertible: eight distinct groups in every phase; and
-    // row -> row ^ f(row >> 3) is a bijection, so the tile stays a permutation of itself.
-    if (logC == 2) row ^= (((row >> 4) ^ (row >> 5)) & 1u) | ((((row >> 3) ^ (row >> 6)) & 1u) << 1) | ((((row >> 4) ^ (row >> 7)) & 1u) << 2);
-#endif
     return (row << logC) | cs;
 }
 template <class F>
@@ -85,205 +50,8 @@ __device__ __forceinline__ F twiddle2(const F* lo, const F* hi, uint32_t L, uint
     return zl::mul(a, b);
 }
 
-template <class FrP, bool LAST>
-__global__ void __launch_bounds__(NTT_THREADS, 4) k_ntt_pass(const Fp<FrP>* __restrict__ in, Fp<FrP>* __restrict__ out, NttArgs a) {
-    using F = Fp<FrP>;
-    in = reinterpret_cast<const Fp<FrP>*>(reinterpret_cast<const unsigned char*>(in) + (size_t)blockIdx.y * a.in_batch);
-    out = reinterpret_cast<Fp<FrP>*>(reinterpret_cast<unsigned char*>(out) + (size_t)blockIdx.y * a.out_batch);
-    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    uint32_t* sh = reinterpret_cast<uint32_t*>(smem);                       // [8][NTT_TILE]
-    const uint32_t tid = threadIdx.x;
-    const uint32_t s = a.s, logC = a.logC, R = 1u << s, C = 1u << logC;
-    F* sh_w = reinterpret_cast<F*>(smem + (size_t)F::N * 4 * NTT_TILE);      // [2^(s-1)] butterfly roots
-    F* sh_row = sh_w + (R >> 1);                                             // [2^s] per-row twiddles (non-last passes)
-    const uint32_t n_log = a.n_log;
-    const F* t_lo = reinterpret_cast<const F*>(a.t_lo);
-    const F* t_hi = reinterpret_cast<const F*>(a.t_hi);
-
-    // ---- tile addressing -------------------------------------------------------------------------------
-    uint64_t in_base, out_base, in_row, in_col, out_row;
-    uint64_t K0 = 0;  // digit-reversed index of the already transformed factors (column 0)
-    {
-        const uint64_t tile = blockIdx.x;
-        if (!LAST) {
-            const uint32_t stride_log = n_log - a.S_prev - s;  // elements between consecutive rows
-            const uint64_t lo_blocks = (1ull << stride_log) >> logC;
-            const uint64_t hi = tile / lo_blocks, lo0 = (tile % lo_blocks) << logC;
-            in_base = (hi << (s + stride_log)) + lo0;
-            out_base = in_base;
-            in_row = 1ull << stride_log;
-            in_col = 1;
-            out_row = in_row;
-            uint64_t rem = hi;
-            uint32_t Sq = a.S_prev;
-            for (int q = (int)a.p - 2; q >= 0; q--) {  // digits k_(p-1) .. k_1, least significant first
-                Sq -= a.sizes[q];
-                K0 += (rem & ((1ull << a.sizes[q]) - 1)) << Sq;
-                rem >>= a.sizes[q];
-            }
-        } else if (a.P == 1) {
-            in_base = out_base = 0;
-            in_row = out_row = 1;
-            in_col = 1;
-        } else {
-            const uint32_t s1 = a.sizes[0];
-            const uint32_t rest_log = a.S_prev - s1;  // bits of (k_2 .. k_(P-1))
-            const uint64_t k1_blocks = (1ull << s1) >> logC;
-            const uint64_t k1_0 = (tile % k1_blocks) << logC, rest = tile / k1_blocks;
-            in_base = ((k1_0 << rest_log) + rest) << s;
-            in_col = 1ull << (rest_log + s);
-            in_row = 1;
-            uint64_t rem = rest, Krest = 0;
-            uint32_t Sq = a.S_prev;
-            for (int q = (int)a.P - 2; q >= 1; q--) {
-                Sq -= a.sizes[q];
-                Krest += (rem & ((1ull << a.sizes[q]) - 1)) << Sq;
-                rem >>= a.sizes[q];
-            }
-            K0 = k1_0 + Krest;
-            out_base = K0;
-            out_row = 1ull << a.S_prev;
-        }
-    }
-    // ---- stage the small tables ----------------------------------------------------------------------------
-    {
-        const F* w_small = reinterpret_cast<const F*>(a.w_small);
-        for (uint32_t i = tid; i < (R >> 1); i += NTT_THREADS) sh_w[i] = w_small[i];
-        if (!LAST && a.p > 1) {
-            const uint32_t shift = n_log - a.S_prev - s;  // N / M_p
-            for (uint32_t r = tid; r < R; r += NTT_THREADS) sh_row[r] = twiddle2(t_lo, t_hi, a.L, ((uint64_t)r * K0) << shift);
-        }
-    }
-    __syncthreads();
-    // ---- element access: load = global read + Montgomery entry / coset scaling / inter-factor twiddle; store = output row k of the tile
-    //      (+ coset / n^-1 scaling and Montgomery exit on the last pass) ----------------------------------------------------------
-    auto load_elem = [&](uint32_t r, uint32_t col) -> F {
-        const uint64_t m = in_base + (uint64_t)r * in_row + (uint64_t)col * in_col;
-        F x = in[m];
-        if (a.p == 1) {
-            if (a.to_mont) x = zl::to_mont(x);
-            if (a.pre_coset) x = zl::mul(x, twiddle2(reinterpret_cast<const F*>(a.g_lo), reinterpret_cast<const F*>(a.g_hi), a.L, m));
-        } else if (!LAST) {
-            x = zl::mul(x, sh_row[r]);
-        } else if (a.last_tw) {
-            x = zl::mul(x, reinterpret_cast<const F*>(a.last_tw)[m]);  // one multiplication: the factor was combined once per key (k_ntt_last_table)
-        } else {
-            x = zl::mul(x, twiddle2(t_lo, t_hi, a.L, (uint64_t)r * (K0 + col)));
-        }
-        return x;
-    };
-    auto store_elem = [&](uint32_t k, uint32_t col, F x) {
-        const uint64_t m = out_base + (uint64_t)k * out_row + col;
-        if (LAST) {
-            if (a.post_coset) {
-                x = zl::mul(x, twiddle2(reinterpret_cast<const F*>(a.g_lo), reinterpret_cast<const F*>(a.g_hi), a.L, m));
-            } else if (a.post_scale) {
-                F ni;
-#pragma unroll
-                for (int w = 0; w < F::N; w++) ni.l[w] = a.ninv[w];
-                x = zl::mul(x, ni);
-            }
-            if (a.from_mont) x = zl::from_mont(x);
-        }
-        out[m] = x;
-    };
-    // two DIF stages on four rows of one column held in registers: stage (distance h) on the pairs (x0, x2), (x1, x3), then stage
-    // (distance h2 = h / 2) on (., .) -- rows i0, i0 + h2, i0 + h, i0 + h + h2 with i0 = (blk << (hl + 2)) | k2
-    auto quad = [&](F& x0, F& x1, F& x2, F& x3, uint32_t k2, uint32_t hl) {
-        const uint32_t h2 = 1u << hl, sh1 = s - 2 - hl;  // stage hl + 1: twiddle index k << (s - 2 - hl); stage hl: k << (s - 1 - hl)
-        const F a0 = zl::add(x0, x2), a1 = zl::add(x1, x3);
-        F a2 = zl::sub(x0, x2);
-        if (k2 != 0) a2 = zl::mul(a2, sh_w[k2 << sh1]);
-        const F a3 = zl::mul(zl::sub(x1, x3), sh_w[(k2 + h2) << sh1]);
-        x0 = zl::add(a0, a1);
-        x2 = zl::add(a2, a3);
-        x1 = zl::sub(a0, a1);
-        x3 = zl::sub(a2, a3);
-        if (k2 != 0) {
-            const F w = sh_w[k2 << (sh1 + 1)];
-            x1 = zl::mul(x1, w);
-            x3 = zl::mul(x3, w);
-        }
-    };
-    // ---- 2^s-point DIF butterflies (all C columns), two stages per round; the first round takes its rows straight from global memory, the
-    //      last one (even s >= 4) writes straight to global memory: three LDS round trips and three barriers per pass at s = 8 instead of
-    //      ten / nine with one stage per round trip.  (Radix-4 by register blocking only: w_4 is an ordinary field multiplication.)
-    const bool fuse_store = ZL_NTT_FUSE_STORE && (s & 1u) == 0 && s >= 4;
-    uint32_t hl = s;
-    if (ZL_NTT_FUSE_LOAD && s >= 2) {
-        hl -= 2;
-        const uint32_t h2 = 1u << hl;  // R / 4
-        for (uint32_t q = tid; q < (R >> 2) * C; q += NTT_THREADS) {
-            uint32_t k2, col;
-            if (LAST && a.P > 1) { k2 = q & (h2 - 1); col = q >> hl; } else { col = q & (C - 1); k2 = q >> logC; }  // consecutive lanes: contiguous memory
-            F x0 = load_elem(k2, col), x1 = load_elem(k2 + h2, col), x2 = load_elem(k2 + 2 * h2, col), x3 = load_elem(k2 + 3 * h2, col);
-            quad(x0, x1, x2, x3, k2, hl);
-            lds_store(sh, tile_pos(k2, col, logC), x0);
-            lds_store(sh, tile_pos(k2 + h2, col, logC), x1);
-            lds_store(sh, tile_pos(k2 + 2 * h2, col, logC), x2);
-            lds_store(sh, tile_pos(k2 + 3 * h2, col, logC), x3);
-        }
-    } else {
-        for (uint32_t idx = tid; idx < R * C; idx += NTT_THREADS) {
-            const uint32_t col = idx & (C - 1), r = idx >> logC;
-            lds_store(sh, tile_pos(r, col, logC), load_elem(r, col));
-        }
-    }
-    __syncthreads();
-    while (hl >= (fuse_store ? 4u : 2u)) {
-        hl -= 2;
-        const uint32_t h2 = 1u << hl, h = h2 << 1;
-        for (uint32_t q = tid; q < (R >> 2) * C; q += NTT_THREADS) {
-            const uint32_t col = q & (C - 1), rr = q >> logC;
-            const uint32_t k2 = rr & (h2 - 1), blk = rr >> hl;
-            const uint32_t i0 = (blk << (hl + 2)) | k2;
-            const uint32_t p0 = tile_pos(i0, col, logC), p1 = tile_pos(i0 + h2, col, logC), p2 = tile_pos(i0 + h, col, logC),
-                           p3 = tile_pos(i0 + h + h2, col, logC);
-            F x0 = lds_load<F>(sh, p0), x1 = lds_load<F>(sh, p1), x2 = lds_load<F>(sh, p2), x3 = lds_load<F>(sh, p3);
-            quad(x0, x1, x2, x3, k2, hl);
-            lds_store(sh, p0, x0);
-            lds_store(sh, p1, x1);
-            lds_store(sh, p2, x2);
-            lds_store(sh, p3, x3);
-        }
-        __syncthreads();
-    }
-    if (fuse_store) {
-        // last round (distances 2 and 1) from LDS, results straight to global memory: row i0 + j of the tile is output index bitrev_s(i0 + j)
-        for (uint32_t q = tid; q < (R >> 2) * C; q += NTT_THREADS) {
-            const uint32_t col = q & (C - 1), rr = q >> logC;
-            const uint32_t i0 = rr << 2;
-            F x0 = lds_load<F>(sh, tile_pos(i0, col, logC)), x1 = lds_load<F>(sh, tile_pos(i0 + 1, col, logC)),
-              x2 = lds_load<F>(sh, tile_pos(i0 + 2, col, logC)), x3 = lds_load<F>(sh, tile_pos(i0 + 3, col, logC));
-            quad(x0, x1, x2, x3, 0u, 0u);
-            store_elem(__brev(i0) >> (32 - s), col, x0);
-            store_elem(__brev(i0 + 1) >> (32 - s), col, x1);
-            store_elem(__brev(i0 + 2) >> (32 - s), col, x2);
-            store_elem(__brev(i0 + 3) >> (32 - s), col, x3);
-        }
-        return;
-    }
-    if (hl == 1) {  // odd s: the last stage (distance 1) on its own
-        for (uint32_t q = tid; q < (R >> 1) * C; q += NTT_THREADS) {
-            const uint32_t col = q & (C - 1), rr = q >> logC;
-            const uint32_t i = rr << 1;
-            const uint32_t pu = tile_pos(i, col, logC), pv = tile_pos(i + 1, col, logC);
-            const F u = lds_load<F>(sh, pu), v = lds_load<F>(sh, pv);
-            lds_store(sh, pu, zl::add(u, v));
-            lds_store(sh, pv, zl::sub(u, v));
-        }
-        __syncthreads();
-    }
-    // ---- store: output row k sits at LDS row bitrev(k) ------------------------------------------------------
-    for (uint32_t idx = tid; idx < R * C; idx += NTT_THREADS) {
-        const uint32_t col = idx & (C - 1), k = idx >> logC;
-        const uint32_t row = s ? (__brev(k) >> (32 - s)) : 0;
-        store_elem(k, col, lds_load<F>(sh, tile_pos(row, col, logC)));
-    }
-}
-
 // ------------------------------------------------------------------------------------------------ the passes on lazily reduced 28-bit limbs
-// Round 4: the same pass with the tile held as 10 x 28-bit lazily reduced elements (zl_field28r.h).  A butterfly addition is ten
+// Round 4: each pass holds its tile as 10 x 28-bit lazily reduced elements (zl_field28r.h).  A butterfly addition is ten
 // v_add_u32 and a carry pass, a subtraction adds a biased multiple 2^j r of the modulus first (no comparison anywhere between two multiplications), a
 // product is a carry-free chain of 210 v_mad_u64_u32 under the Montgomery radix R' = 2^280 -- of the MULTIPLIER only: the data keeps the caller's form
 // (canonical or R = 2^256 Montgomery; mul(x, w R') = x w), so a canonical -> canonical transform needs no conversion multiplications at all, and the
@@ -432,7 +200,7 @@ __global__ void __launch_bounds__(NTT28_THREADS, MINB) k_ntt_pass28(const Fp<FrP
     E* sh_row = sh_w + (a.w_unpacked ? 0u : (R >> 1));                          // [2^s] per-row twiddles (middle passes without a row table)
     const uint32_t n_log = a.n_log;
 
-    // ---- tile addressing (as k_ntt_pass) --------------------------------------------------------------------
+    // ---- tile addressing --------------------------------------------------------------------------------
     uint64_t in_base, out_base, in_row, in_col, out_row;
     uint64_t K0 = 0, tile_hi = 0;
     {
@@ -638,7 +406,12 @@ __global__ void __launch_bounds__(256) k_ntt_unpack_table28(const Fp<FrP>* __res
 #pragma unroll
     for (int k = 0; k < P28::L; k++) out[(size_t)P28::L * i + k] = e.l[k];
 }
-// the combined twiddles of the last pass (k_ntt_last_table) in the lazy multiplier's form
+// The last pass multiplies element (row r, digit-reversed column index K) by w_N^(r K): 2^n distinct factors, so any split into small
+// tables costs a second multiplication per element to combine them (15 instead of 14 multiplications per element at 2^24, and the passes
+// are bound by exactly that count: 0.68 / 0.85 / 1.00 ms for 4 / 5 / 6 multiplications per element).  HBM is the resource with slack
+// (0.43 of 8 TB/s), so the combined factors are tabulated once per (size, direction) in the order the last pass loads its input and
+// streamed beside it: +32 B of reads per element for one multiplication less.  table[m] = scale * w^(r (k1 + Krest)) (canonical, in the lazy multiplier's form) with
+// m = ((k1 << rest_log) + rest) << s | r, exactly the addressing of the last pass (k_ntt_pass28<.., LAST>).
 template <class FrP>
 __global__ void __launch_bounds__(256) k_ntt_last_table28(Fp<FrP>* __restrict__ table, NttArgs a) {
     using P28 = typename Fr28Of<FrP>::type;
@@ -698,29 +471,6 @@ __global__ void __launch_bounds__(256) k_ntt_pow_table(Fp<FrP>* __restrict__ tab
         e >>= 1;
     }
     table[i] = acc;
-}
-
-// The last pass multiplies element (row r, digit-reversed column index K) by w_N^(r K): 2^n distinct factors, so any split into small
-// tables costs a second multiplication per element to combine them (15 instead of 14 multiplications per element at 2^24, and the passes
-// are bound by exactly that count: 0.68 / 0.85 / 1.00 ms for 4 / 5 / 6 multiplications per element).  HBM is the resource with slack
-// (0.43 of 8 TB/s), so the combined factors are tabulated once per (size, direction) in the order the last pass loads its input and
-// streamed beside it: +32 B of reads per element for one multiplication less.  table[m] = scale * w^(r (k1 + Krest)) with
-// m = ((k1 << rest_log) + rest) << s | r, exactly the addressing of k_ntt_pass<LAST>.
-template <class FrP>
-__global__ void __launch_bounds__(256) k_ntt_last_table(Fp<FrP>* __restrict__ table, NttArgs a) {
-    using F = Fp<FrP>;
-    const uint64_t m = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (m >> a.n_log) return;
-    const uint32_t s = a.s, s1 = a.sizes[0], rest_log = a.S_prev - s1;
-    const uint64_t r = m & ((1ull << s) - 1), rest = (m >> s) & ((1ull << rest_log) - 1), k1 = m >> (s + rest_log);
-    uint64_t rem = rest, Krest = 0;
-    uint32_t Sq = a.S_prev;
-    for (int q = (int)a.P - 2; q >= 1; q--) {
-        Sq -= a.sizes[q];
-        Krest += (rem & ((1ull << a.sizes[q]) - 1)) << Sq;
-        rem >>= a.sizes[q];
-    }
-    table[m] = twiddle2(reinterpret_cast<const F*>(a.t_lo), reinterpret_cast<const F*>(a.t_hi), a.L, r * (k1 + Krest));
 }
 
 // ------------------------------------------------------------------------------------------------ host driver
@@ -808,6 +558,8 @@ template <class FrP>
 // count > 1: `count` equal-size transforms with the same flags, vector v at d_data + v * stride_bytes, in ONE launch per pass (grid.y = count)
 static int ntt_run_t(zl_ctx* ctx, int curve, void* d_data, unsigned n, unsigned flags, unsigned count = 1, size_t stride_bytes = 0) {
     using F = Fp<FrP>;
+    using P28 = typename Fr28Of<FrP>::type;  // the passes run on lazily reduced limbs (k_ntt_pass28: round 4, nine 29-bit limbs since round 5)
+    using E28 = Fr28<P28>;
     if (n > (unsigned)FrP::TWO_ADICITY || n > 30) return ZL_EINVAL;
     const bool inverse = flags & ZL_INVERSE, coset = flags & ZL_COSET;
     const bool mont_in = flags & (ZL_MONT | ZL_MONT_IN), mont_out = flags & (ZL_MONT | ZL_MONT_OUT);
@@ -817,19 +569,17 @@ static int ntt_run_t(zl_ctx* ctx, int curve, void* d_data, unsigned n, unsigned 
         if (mont_in != mont_out) return ZL_EINVAL;
         return ZL_OK;
     }
-    // Round 4: the passes run on lazily reduced 28-bit limbs (k_ntt_pass28) unless ZL_NTT_NO_LAZY is set (developer A/B switch; the 32-bit passes stay)
-    static const bool lazy = getenv("ZL_NTT_NO_LAZY") == nullptr;
     const bool roots_global = true;  // round 5: the butterfly roots as limbs from global memory (2^24: 2.16 -> 2.13 ms, profiles/r05_ntt_fr29_ab2.log); the LDS-staged path stays in the kernel for w_unpacked == nullptr
     zl_twiddles* tw;
     int rc;
-    if ((rc = ntt_tables<FrP>(ctx, curve, n, inverse, &tw, lazy))) return rc;
+    if ((rc = ntt_tables<FrP>(ctx, curve, n, inverse, &tw, true))) return rc;
     const NttPlan pl = ntt_plan(n);
     const size_t N = (size_t)1 << n;
     F* data = reinterpret_cast<F*>(d_data);
     F* scratch = nullptr;
     if (pl.P > 1) {
         void* p;
-        if ((rc = zl_scratch_get(ctx, 6, (size_t)count * N * (lazy ? ScratchBytes<typename Fr28Of<FrP>::type>::value : sizeof(F)), &p))) return rc;  // lazy passes: the limbs as they are between passes
+        if ((rc = zl_scratch_get(ctx, 6, (size_t)count * N * ScratchBytes<P28>::value, &p))) return rc;  // the limbs as they are between passes
         scratch = reinterpret_cast<F*>(p);
     }
     const unsigned L = tw->lo_bits;
@@ -838,17 +588,11 @@ static int ntt_run_t(zl_ctx* ctx, int curve, void* d_data, unsigned n, unsigned 
     const F* g_lo = t_hi + ((size_t)1 << (n - L));
     const F* g_hi = g_lo + ((size_t)1 << L);
     const F* small = reinterpret_cast<const F*>(tw->d_small);
-    F ninv = zl::inv(zl::from_u64<FrP>(1ull << n));
-    if (lazy) {  // n^-1 R -> n^-1 R' (canonical), the multiplier form of the lazy passes
-        using P28 = typename Fr28Of<FrP>::type;
-        F rp;
-        for (int k = 0; k < F::N; k++) rp.l[k] = P28::rp(k);
-        ninv = zl::mul(ninv, rp);
-    }
+    F rp;
+    for (int k = 0; k < F::N; k++) rp.l[k] = P28::rp(k);
+    const F ninv = zl::mul(zl::inv(zl::from_u64<FrP>(1ull << n)), rp);  // n^-1 R -> n^-1 R' (canonical), the multiplier form of the lazy passes
     hipStream_t st = ctx->stream;
     // tiles + tables can exceed the 64 KiB default dynamic-LDS limit (gfx950 has 160 KiB per CU); per device, so set per call
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&k_ntt_pass<FrP, true>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&k_ntt_pass<FrP, false>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
     (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&k_ntt_pass28<FrP, true, 2>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
     (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&k_ntt_pass28<FrP, false, 2>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
     (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&k_ntt_pass28<FrP, true, 5>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
@@ -890,24 +634,21 @@ static int ntt_run_t(zl_ctx* ctx, int curve, void* d_data, unsigned n, unsigned 
         a.g_hi = g_hi;
         a.w_small = small + ((size_t)1 << (a.s ? a.s - 1 : 0));
         a.w_unpacked = nullptr;
-        if (lazy && roots_global) {
-            using P28u = typename Fr28Of<FrP>::type;
+        if (roots_global) {
             if (!tw->d_small_limbs) {
                 void* t = nullptr;
-                if (hipMalloc(&t, (size_t)4 * P28u::L << NTT_MAX_S) == hipSuccess) {
+                if (hipMalloc(&t, (size_t)4 * P28::L << NTT_MAX_S) == hipSuccess) {
                     hipLaunchKernelGGL((k_ntt_unpack_table28<FrP>), dim3((1u << NTT_MAX_S) / 256), dim3(256), 0, st, small, (uint32_t*)t, 1u << NTT_MAX_S);
                     tw->d_small_limbs = t;
                 } else {
                     (void)hipGetLastError();
                 }
             }
-            if (tw->d_small_limbs) a.w_unpacked = reinterpret_cast<const uint32_t*>(tw->d_small_limbs) + (size_t)P28u::L * ((size_t)1 << (a.s ? a.s - 1 : 0));
+            if (tw->d_small_limbs) a.w_unpacked = reinterpret_cast<const uint32_t*>(tw->d_small_limbs) + (size_t)P28::L * ((size_t)1 << (a.s ? a.s - 1 : 0));
         }
-        a.to_mont = (p == 1 && !mont_in) ? 1 : 0;
-        if (lazy) a.to_mont = (p == 1 && !mont_in && mont_out) ? 1 : 0;  // the data keeps its form: a conversion only when the caller asks for one
+        a.to_mont = (p == 1 && !mont_in && mont_out) ? 1 : 0;  // the data keeps its form: a conversion only when the caller asks for one
         a.pre_coset = (p == 1 && coset && !inverse) ? 1 : 0;
-        a.from_mont = (last && !mont_out) ? 1 : 0;
-        if (lazy) a.from_mont = (last && mont_in && !mont_out) ? 1 : 0;
+        a.from_mont = (last && mont_in && !mont_out) ? 1 : 0;
         a.post_coset = (last && coset && inverse) ? 1 : 0;
         a.post_scale = (last && inverse && !coset) ? 1 : 0;
         if (a.post_scale && pl.P > 1) {  // n^-1 rides on the last pass's twiddles (ntt_tables)
@@ -917,15 +658,14 @@ static int ntt_run_t(zl_ctx* ctx, int curve, void* d_data, unsigned n, unsigned 
         for (int k = 0; k < 8; k++) a.ninv[k] = ninv.l[k];
         // the combined twiddles of the last pass, tabulated once per (size, direction): forward (plain and coset share it: the coset scaling
         // rides on pass 1) and the scaled inverse; the coset inverse (its 1/n lives in the coset table) combines on the fly
-        if (last && pl.P > 1 && !(inverse && coset) && n <= 26 && !getenv("ZL_NTT_NO_LAST_TABLE")) {
+        if (last && pl.P > 1 && !(inverse && coset) && n <= 26) {
             const size_t want = N * sizeof(F);
             if (!tw->d_last && want <= table_budget) {
                 if ((rc_t = make_room(want))) return rc_t;
                 void* t = nullptr;
                 if (ctx->ntt_last_bytes + want <= table_budget && hipMalloc(&t, want) == hipSuccess) {
                     a.last_tw = nullptr;
-                    if (lazy) hipLaunchKernelGGL((k_ntt_last_table28<FrP>), dim3((uint32_t)((N + 255) / 256)), dim3(256), 0, st, reinterpret_cast<F*>(t), a);
-                    else hipLaunchKernelGGL((k_ntt_last_table<FrP>), dim3((uint32_t)((N + 255) / 256)), dim3(256), 0, st, reinterpret_cast<F*>(t), a);
+                    hipLaunchKernelGGL((k_ntt_last_table28<FrP>), dim3((uint32_t)((N + 255) / 256)), dim3(256), 0, st, reinterpret_cast<F*>(t), a);
                     tw->d_last = t;
                     tw->last_bytes += want;
                     ctx->ntt_last_bytes += want;
@@ -936,7 +676,7 @@ static int ntt_run_t(zl_ctx* ctx, int curve, void* d_data, unsigned n, unsigned 
             if (tw->d_last) tw->last_used = ++ctx->ntt_clock;
             a.last_tw = tw->d_last;
         }
-        if (lazy && !last && p > 1 && p <= 4 && S_prev + a.s <= 20) {  // middle pass: its row twiddles per tile high index, <= 32 MB, kept with the tables
+        if (!last && p > 1 && p <= 4 && S_prev + a.s <= 20) {  // middle pass: its row twiddles per tile high index, <= 32 MB, kept with the tables
             if (!tw->d_row[p - 1]) {
                 //  counted in the same byte budget as the last-pass tables and evicted with them: a sweep over sizes, directions and curves
                 // would otherwise keep up to three 32-MB tables per key for ever
@@ -961,31 +701,24 @@ static int ntt_run_t(zl_ctx* ctx, int curve, void* d_data, unsigned n, unsigned 
         if (pl.P == 1) cols_avail_log = 0;
         else if (!last) cols_avail_log = n - S_prev - a.s;
         else cols_avail_log = pl.sizes[0];
-        uint32_t logC = (lazy ? (uint32_t)NTT28_TILE_LOG : 11u) - a.s;  // NTT_TILE = 2^11, NTT28_TILE = 2^NTT28_TILE_LOG
+        uint32_t logC = (uint32_t)NTT28_TILE_LOG - a.s;
         if (a.s > 10) return ZL_EINVAL;
         if (logC > cols_avail_log) logC = cols_avail_log;
         a.logC = logC;
         const uint64_t tiles = (uint64_t)N >> (a.s + logC);
         const F* src = (p == 1) ? data : scratch;
         F* dst = last ? data : scratch;
-        const size_t scratch_vec = N * (lazy ? ScratchBytes<typename Fr28Of<FrP>::type>::value : sizeof(F));
+        const size_t scratch_vec = N * ScratchBytes<P28>::value;
         a.in_batch = (p == 1) ? stride_bytes : scratch_vec;
         a.out_batch = last ? stride_bytes : scratch_vec;
-        if (lazy) {
-            // tile + butterfly roots (+ the per-row twiddles of a middle pass that has no row table): 45 KB at s = 8 -> three workgroups per CU
-            using E28 = Fr28<typename Fr28Of<FrP>::type>;
-            const size_t lds28 = (size_t)E28::L * 4 * NTT28_TILE + sizeof(E28) * ((a.w_unpacked ? 0 : ((size_t)1 << a.s) / 2) + ((!last && p > 1 && !a.row_tw) ? ((size_t)1 << a.s) : 0));
-            if (ctx->ntt_fit_beside && NTT28_THREADS == 256) {
-                if (last) hipLaunchKernelGGL((k_ntt_pass28<FrP, true, 5>), dim3((uint32_t)tiles, count), dim3(NTT28_THREADS), lds28, st, src, dst, a);
-                else hipLaunchKernelGGL((k_ntt_pass28<FrP, false, 5>), dim3((uint32_t)tiles, count), dim3(NTT28_THREADS), lds28, st, src, dst, a);
-            } else {
-                if (last) hipLaunchKernelGGL((k_ntt_pass28<FrP, true, 2>), dim3((uint32_t)tiles, count), dim3(NTT28_THREADS), lds28, st, src, dst, a);
-                else hipLaunchKernelGGL((k_ntt_pass28<FrP, false, 2>), dim3((uint32_t)tiles, count), dim3(NTT28_THREADS), lds28, st, src, dst, a);
-            }
+        // tile + butterfly roots (+ the per-row twiddles of a middle pass that has no row table): 45 KB at s = 8 -> three workgroups per CU
+        const size_t lds28 = (size_t)E28::L * 4 * NTT28_TILE + sizeof(E28) * ((a.w_unpacked ? 0 : ((size_t)1 << a.s) / 2) + ((!last && p > 1 && !a.row_tw) ? ((size_t)1 << a.s) : 0));
+        if (ctx->ntt_fit_beside && NTT28_THREADS == 256) {
+            if (last) hipLaunchKernelGGL((k_ntt_pass28<FrP, true, 5>), dim3((uint32_t)tiles, count), dim3(NTT28_THREADS), lds28, st, src, dst, a);
+            else hipLaunchKernelGGL((k_ntt_pass28<FrP, false, 5>), dim3((uint32_t)tiles, count), dim3(NTT28_THREADS), lds28, st, src, dst, a);
         } else {
-        const size_t lds = (size_t)F::N * 4 * NTT_TILE + sizeof(F) * (((size_t)1 << a.s) / 2 + ((size_t)1 << a.s));
-        if (last) hipLaunchKernelGGL((k_ntt_pass<FrP, true>), dim3((uint32_t)tiles, count), dim3(NTT_THREADS), lds, st, src, dst, a);
-        else hipLaunchKernelGGL((k_ntt_pass<FrP, false>), dim3((uint32_t)tiles, count), dim3(NTT_THREADS), lds, st, src, dst, a);
+            if (last) hipLaunchKernelGGL((k_ntt_pass28<FrP, true, 2>), dim3((uint32_t)tiles, count), dim3(NTT28_THREADS), lds28, st, src, dst, a);
+            else hipLaunchKernelGGL((k_ntt_pass28<FrP, false, 2>), dim3((uint32_t)tiles, count), dim3(NTT28_THREADS), lds28, st, src, dst, a);
         }
         S_prev += a.s;
     }

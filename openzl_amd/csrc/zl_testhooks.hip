@@ -415,11 +415,7 @@ int zl_test_poseidon_permute_dev28r(zl_ctx* ctx, zl_curve_t curve, uint64_t* sta
 }
 
 int zl_test_fp28_op(zl_ctx* ctx, int op, const uint32_t* in, size_t n, uint32_t* out) { return test_fp28_op_t<F28>(ctx, op, in, n, out); }
-#ifndef ZL_BN_FIELD32
 int zl_test_fp28_bn_op(zl_ctx* ctx, int op, const uint32_t* in, size_t n, uint32_t* out) { return test_fp28_op_t<BnG1::F>(ctx, op, in, n, out); }
-#else
-int zl_test_fp28_bn_op(zl_ctx*, int, const uint32_t*, size_t, uint32_t*) { return ZL_EINVAL; }  // (the A/B build keeps BN254 on the 32-bit field)
-#endif
 
 int zl_test_point_op(zl_ctx* ctx, zl_group_t group, int hot, int op, const uint32_t* in, size_t n, uint32_t* out) {
     if ((!in || !out) && n) return ZL_EINVAL;
