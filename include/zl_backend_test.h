@@ -98,6 +98,13 @@ int zl_test_verify_batch_host(zl_curve_t curve, const uint64_t* alpha_g1, const 
                               const uint64_t* gamma_abc, size_t n_public, const zl_g16_proof* proofs, const uint64_t* public_inputs, size_t count,
                               const uint64_t* seed, int* ok, uint8_t* ok_each);
 
+/* The NTT driver's choices, for the tests that must reach every one of them (openzl_amd/csrc/zl_ntt.hip).
+ *   zl_test_ntt_plan: the pass plan of a 2^log_n-point transform (log_n <= 32): *P passes of sizes[0..P-1] bits, unused sizes 0.  Host only, no ctx.
+ *   zl_test_ntt_fit_beside(ctx, on): sets the ctx's ntt_fit_beside (the passes' 96-register instantiations, otherwise used only by a whole Groth16 proof's
+ *   witness map) and returns the previous value; ZL_EINVAL for a null ctx. */
+int zl_test_ntt_plan(unsigned log_n, unsigned* P, unsigned sizes[4]);
+int zl_test_ntt_fit_beside(zl_ctx* ctx, int on);
+
 #ifdef __cplusplus
 }
 #endif

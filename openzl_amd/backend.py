@@ -181,6 +181,8 @@ def load_library(path: Optional[str] = None):
     L.zl_test_acc_clock_read.argtypes = [vp, C.POINTER(C.c_double)]
     L.zl_test_clock_probe_launch.argtypes = [vp, C.c_uint]
     L.zl_test_clock_probe_read.argtypes = [vp, C.POINTER(C.c_double)]
+    L.zl_test_ntt_plan.argtypes = [C.c_uint, C.POINTER(C.c_uint), C.POINTER(C.c_uint)]
+    L.zl_test_ntt_fit_beside.argtypes = [vp, C.c_int]
     if path is None:
         _lib = L
     return L
@@ -583,7 +585,7 @@ class MultiBackend:
 # ---- test-only hooks (include/zl_backend_test.h): device Poseidon KAT, raw-limb field / point access ---------------------------------
 TEST_ABI_SYMBOLS = ["zl_test_poseidon_permute_dev", "zl_test_fp28_op", "zl_test_fp28_bn_op", "zl_test_pairing_product", "zl_test_point_op", "zl_test_circuit_tweak", "zl_test_fq_mul_rate", "zl_test_fr28_op", "zl_test_fr29_op",
                     "zl_test_poseidon_permute_dev28r", "zl_test_fq_mul_clock", "zl_test_acc_clock", "zl_test_acc_clock_read", "zl_test_clock_probe_launch", "zl_test_clock_probe_read",
-                    "zl_test_miller_dev", "zl_test_final_exp", "zl_test_verify_batch_host"]
+                    "zl_test_miller_dev", "zl_test_final_exp", "zl_test_verify_batch_host", "zl_test_ntt_plan", "zl_test_ntt_fit_beside"]
 
 
 def _p32(a: np.ndarray):
@@ -595,6 +597,25 @@ def groth16_keys_parse(curve: int, data: bytes, check: bool = False) -> int:
     """host-only validation of ProvingContext bytes (zl_groth16_keys_parse): the C error code (0 = acceptable framing)"""
     buf = (C.c_uint8 * max(1, len(data))).from_buffer_copy(data if data else b"\0")
     return int(load_library().zl_groth16_keys_parse(curve, buf, len(data), ZL_CHECK if check else 0))
+
+
+def hook_ntt_plan(log_n: int) -> list[int]:
+    """the pass sizes zl_ntt.hip's driver uses for a 2^log_n-point transform (zl_test_ntt_plan; host only)"""
+    P = C.c_uint(0)
+    sizes = (C.c_uint * 4)()
+    rc = load_library().zl_test_ntt_plan(log_n, C.byref(P), sizes)
+    if rc != 0:
+        raise BackendError(rc, "zl_test_ntt_plan")
+    assert all(sizes[k] == 0 for k in range(P.value, 4))
+    return [int(sizes[k]) for k in range(P.value)]
+
+
+def hook_ntt_fit_beside(be: "Backend", on: bool) -> bool:
+    """set the ctx's ntt_fit_beside (the 96-register instantiations of the NTT passes); returns the previous setting"""
+    old = be.L.zl_test_ntt_fit_beside(be._ctx, int(on))
+    if old < 0:
+        raise BackendError(old, "zl_test_ntt_fit_beside")
+    return bool(old)
 
 
 def hook_poseidon_permute_dev(be: "Backend", curve: int, state: np.ndarray) -> np.ndarray:

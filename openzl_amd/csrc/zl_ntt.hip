@@ -497,6 +497,15 @@ static NttPlan ntt_plan(unsigned n) {
     return pl;
 }
 
+// test hook (include/zl_backend_test.h): the pass plan of a 2^log_n-point transform as the driver below uses it; host only
+extern "C" int zl_test_ntt_plan(unsigned log_n, unsigned* P, unsigned sizes[4]) {
+    if (!P || !sizes || log_n > 32) return ZL_EINVAL;
+    const NttPlan pl = ntt_plan(log_n);
+    *P = pl.P;
+    for (int k = 0; k < 4; k++) sizes[k] = pl.sizes[k];
+    return ZL_OK;
+}
+
 // lazy: the tables of the 28-bit passes (entries w R' mod r as canonical integers) -- a separate set: the distributed transform's cross kernel
 // (k_ntt_cross) keeps the 32-bit field and its Montgomery tables
 template <class FrP>

@@ -602,4 +602,11 @@ int zl_test_acc_clock_read(zl_ctx* ctx, double* out) {
     return ZL_OK;
 }
 
+int zl_test_ntt_fit_beside(zl_ctx* ctx, int on) {
+    if (!ctx) return ZL_EINVAL;
+    const int old = ctx->ntt_fit_beside;
+    ctx->ntt_fit_beside = on ? 1 : 0;
+    return old;
+}
+
 }  // extern "C"
