@@ -5,7 +5,9 @@
  *     [3, 1, 2] over BLS12-381 Fr (/root/reference/openzl-tutorials/src/poseidon.rs:364-405, same numbers in
  *     /root/reference/plugins/arkworks/src/poseidon/permutation_hardcoded_test/width3), and
  *   - drive the lazily reduced 14 x 28-bit field (openzl_amd/csrc/zl_field28.h) and the point formulas built on it with operands AT
- *     their contract bounds, which random MSM inputs never produce.
+ *     their contract bounds, which random MSM inputs never produce, and
+ *   - drive the LANE FORMS of that arithmetic the same way: Fq2 split over a lane pair (openzl_amd/csrc/zl_fq2pair.h, Fp2H) and one XYZZ addition over the
+ *     four lanes of a quad / the eight lanes of an octet (openzl_amd/csrc/zl_quad.h), placed on lanes and in memory exactly as the MSM kernels place them.
  * Nothing in the product path calls them.
  */
 #ifndef ZL_BACKEND_TEST_H
@@ -44,6 +46,27 @@ int zl_test_fp28_bn_op(zl_ctx* ctx, int op, const uint32_t* in, size_t n, uint32
  * op: 0 add_mixed(p, q.x, q.y, +)  1 add_mixed(p, q.x, q.y, -)  2 add_full(p, q)  3 dbl_inplace(p)  4 dbl_affine(p.x, p.y)
  *     5 neg_inplace(p)  6 to_affine(p) (x, y in the first two coordinates) */
 int zl_test_point_op(zl_ctx* ctx, zl_group_t group, int hot, int op, const uint32_t* in, size_t n, uint32_t* out);
+
+/* Fq2 over a LANE PAIR (Fp2H of openzl_amd/csrc/zl_fq2pair.h: c0 in lane i, c1 in lane i ^ 8 of a row of 16), device only: a null ctx is ZL_EINVAL.
+ * curve: ZL_BLS12_381 (L = 14 limbs per component) or ZL_BN254 (L = 10).  in: n records of 4 Fq2 operands (a, b, c, d), each c0 || c1 as 2 x L raw limbs
+ * (NOT reduced: the caller chooses them anywhere inside a contract); out: n x 2 L limbs.  The kernel maps lanes to records with ZL_PAIR_ITEM / pair_half and
+ * moves operands with pair_load / pair_store, on the memory layout of the product (two 64-byte components per element): 32 records per wave.
+ * op: 0 mul(a,b)  1 sqr(a)  2 muladd(a,b,c,d)  3 add(a,b)  4 dbl(a)  5..10 subk<1..6>(a,b)  11 wred(a)  12 canon(a)
+ *     13 is_zero(a)  14 raw_zero(a) (predicates: 0 / 1 in limb 0 of BOTH components, the other limbs 0)  15 x3_of(a,b,c) = a - b - 2c + 6q
+ *     16 Fp2H::one()  17..22 negk<1..6>(a) */
+int zl_test_fp2pair_op(zl_ctx* ctx, zl_curve_t curve, int op, const uint32_t* in, size_t n, uint32_t* out);
+
+/* The point formulas in every form the kernels run them in.  Records, op numbers and meaning as zl_test_point_op; a coordinate is L words (G1) or 2 L words (G2),
+ * L = 14 for ZL_BLS12_381 and 10 for ZL_BN254.
+ *   ZL_TEST_FORM_SCALAR / _SCALAR_HOT  one lane per item, the called / the inlined Fq2 flavour (G1: the same code); host path with a null ctx
+ *   ZL_TEST_FORM_QUAD    G1 only: four lanes per item, ops 0-2 through add_mixed_quad / add_full_quad, 3-6 by every lane on its own; 16 items per wave
+ *   ZL_TEST_FORM_PAIR    G2 only: Fp2H, the per-lane formulas on a lane pair, items by ZL_PAIR_ITEM, pair_load / pair_store; 32 items per wave
+ *   ZL_TEST_FORM_OCTET   G2 only: add_*_quad over Fp2H (ops 0-2; 3-5 per lane pair), items by ZL_OCTET_ITEM; 8 items per wave
+ * The three lane forms run on the device only (null ctx: ZL_EINVAL); a group a form does not exist for is ZL_EINVAL, and so is op 6 on PAIR / OCTET
+ * (Fp2H has no inversion: no kernel leaves the XYZZ form on lane pairs).  QUAD / OCTET: lane 0 of each quad stores the result, and ZL_EHIP is returned
+ * if the four lanes of any quad (each of the two quads of an octet) did not end with identical limbs. */
+typedef enum { ZL_TEST_FORM_SCALAR = 0, ZL_TEST_FORM_SCALAR_HOT = 1, ZL_TEST_FORM_QUAD = 2, ZL_TEST_FORM_PAIR = 3, ZL_TEST_FORM_OCTET = 4 } zl_test_form_t;
+int zl_test_point_form_op(zl_ctx* ctx, zl_curve_t curve, zl_group_t group, int form, int op, const uint32_t* in, size_t n, uint32_t* out);
 
 /* Turns `c` into a different circuit of the SAME shape (the first coefficient of row 0 of A is doubled; the assignment no longer satisfies
  * it).  A proving context compiled for / bound to the original circuit must refuse the tweaked one (its matrices are device-resident and are

@@ -171,6 +171,8 @@ def load_library(path: Optional[str] = None):
     L.zl_test_verify_batch_host.argtypes = [C.c_int, u64p, u64p, u64p, u64p, u64p, C.c_size_t, C.POINTER(G16ProofC), u64p, C.c_size_t, u64p,
                                             C.POINTER(C.c_int), u8p]
     L.zl_test_point_op.argtypes = [vp, C.c_int, C.c_int, C.c_int, u32p, C.c_size_t, u32p]
+    L.zl_test_fp2pair_op.argtypes = [vp, C.c_int, C.c_int, u32p, C.c_size_t, u32p]
+    L.zl_test_point_form_op.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_int, u32p, C.c_size_t, u32p]
     L.zl_test_circuit_tweak.argtypes = [vp]
     L.zl_test_fq_mul_rate.argtypes = [vp, C.c_int, C.c_int, C.POINTER(C.c_double)]
     L.zl_test_fr28_op.argtypes = [vp, C.c_int, C.c_int, C.c_int, u32p, C.c_size_t, u32p]
@@ -585,7 +587,7 @@ class MultiBackend:
 # ---- test-only hooks (include/zl_backend_test.h): device Poseidon KAT, raw-limb field / point access ---------------------------------
 TEST_ABI_SYMBOLS = ["zl_test_poseidon_permute_dev", "zl_test_fp28_op", "zl_test_fp28_bn_op", "zl_test_pairing_product", "zl_test_point_op", "zl_test_circuit_tweak", "zl_test_fq_mul_rate", "zl_test_fr28_op", "zl_test_fr29_op",
                     "zl_test_poseidon_permute_dev28r", "zl_test_fq_mul_clock", "zl_test_acc_clock", "zl_test_acc_clock_read", "zl_test_clock_probe_launch", "zl_test_clock_probe_read",
-                    "zl_test_miller_dev", "zl_test_final_exp", "zl_test_verify_batch_host", "zl_test_ntt_plan", "zl_test_ntt_fit_beside"]
+                    "zl_test_miller_dev", "zl_test_final_exp", "zl_test_verify_batch_host", "zl_test_ntt_plan", "zl_test_ntt_fit_beside", "zl_test_fp2pair_op", "zl_test_point_form_op"]
 
 
 def _p32(a: np.ndarray):
@@ -717,6 +719,35 @@ def hook_point_op(be: Optional["Backend"], group: int, hot: bool, op: int, pq: n
     rc = L.zl_test_point_op(be._ctx if be is not None else None, group, int(hot), op, _p32(a), n, _p32(out))
     if rc:
         raise BackendError(rc, "zl_test_point_op")
+    return out
+
+
+# forms of zl_test_point_form_op (include/zl_backend_test.h)
+FORM_SCALAR, FORM_SCALAR_HOT, FORM_QUAD, FORM_PAIR, FORM_OCTET = 0, 1, 2, 3, 4
+
+
+def hook_fp2pair_op(be: "Backend", curve: int, op: int, operands: np.ndarray) -> np.ndarray:
+    """Fq2 on a lane pair (Fp2H, device only): operands (n, 4, 2 L) uint32 raw limbs, c0 || c1 -> (n, 2 L); L = 14 (BLS12-381) or 10 (BN254)"""
+    a = np.ascontiguousarray(operands, dtype=np.uint32)
+    n, W = a.shape[0], (28 if curve == ZL_BLS12_381 else 20)
+    assert a.shape[1:] == (4, W)
+    out = np.zeros((n, W), dtype=np.uint32)
+    rc = load_library().zl_test_fp2pair_op(be._ctx if be is not None else None, curve, op, _p32(a), n, _p32(out))
+    if rc:
+        raise BackendError(rc, "zl_test_fp2pair_op")
+    return out
+
+
+def hook_point_form_op(be: Optional["Backend"], curve: int, group: int, form: int, op: int, pq: np.ndarray) -> np.ndarray:
+    """pq: (n, 8, W) uint32 raw limbs of two XYZZ points (W = L for G1, 2 L for G2) -> (n, 4, W), through the given form of the point formulas;
+    be = None runs the host code path (scalar forms only)"""
+    a = np.ascontiguousarray(pq, dtype=np.uint32)
+    n, W = a.shape[0], a.shape[2]
+    assert a.shape[1] == 8 and W == (14 if curve == ZL_BLS12_381 else 10) * (1 if group == ZL_G1 else 2)
+    out = np.zeros((n, 4, W), dtype=np.uint32)
+    rc = load_library().zl_test_point_form_op(be._ctx if be is not None else None, curve, group, form, op, _p32(a), n, _p32(out))
+    if rc:
+        raise BackendError(rc, "zl_test_point_form_op")
     return out
 
 

@@ -7,6 +7,7 @@
 #include "zl_ctx.h"
 #include "zl_host.h"
 #include "zl_field28r.h"
+#include "zl_fq2pair.h"
 
 using namespace openzl;
 
@@ -278,15 +279,16 @@ static int test_fr_lazy_op_t(zl_ctx* ctx, zl_curve_t curve, int op, int j, const
 }
 
 template <class F> struct RawIO;
-template <> struct RawIO<F28> {
-    static constexpr int W = 14;
-    ZL_HD static F28 load(const uint32_t* w) { return raw_load(w); }
-    ZL_HD static void store(uint32_t* w, const F28& a) { raw_store(w, a); }
+template <class A, class P> struct RawIO<Fp28<A, P>> {
+    using B = Fp28<A, P>;
+    static constexpr int W = A::L;
+    ZL_HD static B load(const uint32_t* w) { return raw_load<B>(w); }
+    ZL_HD static void store(uint32_t* w, const B& a) { raw_store<B>(w, a); }
 };
-template <bool I> struct RawIO<Fp2LT<F28, I>> {
-    static constexpr int W = 28;
-    ZL_HD static Fp2LT<F28, I> load(const uint32_t* w) { return Fp2LT<F28, I>{raw_load(w), raw_load(w + 14)}; }
-    ZL_HD static void store(uint32_t* w, const Fp2LT<F28, I>& a) { raw_store(w, a.c0); raw_store(w + 14, a.c1); }
+template <class B, bool I> struct RawIO<Fp2LT<B, I>> {
+    static constexpr int W = 2 * B::L;
+    ZL_HD static Fp2LT<B, I> load(const uint32_t* w) { return Fp2LT<B, I>{raw_load<B>(w), raw_load<B>(w + B::L)}; }
+    ZL_HD static void store(uint32_t* w, const Fp2LT<B, I>& a) { raw_store<B>(w, a.c0); raw_store<B>(w + B::L, a.c1); }
 };
 template <class F>
 ZL_HD static void point_op(int op, const uint32_t* in, uint32_t* out) {
@@ -337,6 +339,209 @@ static int run_dev(zl_ctx* ctx, const uint32_t* in, size_t in_words, uint32_t* o
     return ZL_OK;
 }
 
+
+// ------------------------------------------------------------------------------------------------ the lane forms (zl_fq2pair.h, zl_quad.h)
+// Fq2 over a lane pair and one XYZZ addition over a quad / an octet run on the device only; the kernels below place items on lanes exactly as the product
+// kernels do (ZL_PAIR_ITEM / ZL_OCTET_ITEM / pair_half, pair_load / pair_store on the 64-byte-per-component memory layout; quads as k_msm_accumulate_quad).
+// like run_dev, plus one flag word behind the output that a kernel sets (a plain store) when lanes that must agree do not: ZL_EHIP
+template <class Launch>
+static int run_dev_flag(zl_ctx* ctx, const uint32_t* in, size_t in_words, uint32_t* out, size_t out_words, Launch launch) {
+    void* d = nullptr;
+    int rc = zl_scratch_get(ctx, 9, (in_words + out_words) * 4 + 64, &d);
+    if (rc) return rc;
+    uint32_t* d_in = (uint32_t*)d;
+    uint32_t* d_out = d_in + in_words;
+    uint32_t* d_flag = d_out + out_words;
+    hipStream_t st = ctx->stream;
+    uint32_t flag = 0;
+    ZL_HIP(ctx, hipMemcpyAsync(d_in, in, in_words * 4, hipMemcpyHostToDevice, st));
+    ZL_HIP(ctx, hipMemsetAsync(d_out, 0, out_words * 4 + 4, st));
+    launch(d_in, d_out, d_flag, st);
+    ZL_HIP(ctx, hipGetLastError());
+    ZL_HIP(ctx, hipMemcpyAsync(out, d_out, out_words * 4, hipMemcpyDeviceToHost, st));
+    ZL_HIP(ctx, hipMemcpyAsync(&flag, d_flag, 4, hipMemcpyDeviceToHost, st));
+    ZL_HIP(ctx, hipStreamSynchronize(st));
+    return flag ? ZL_EHIP : ZL_OK;
+}
+// raw records (components of L limbs, back to back) <-> the memory layout of Fp2L<B> (two 64-byte components)
+template <class B>
+static void fq2_pad(const uint32_t* in, size_t elems, std::vector<uint32_t>& padded) {
+    padded.assign(elems * 32, 0u);
+    for (size_t e = 0; e < elems; e++)
+        for (int h = 0; h < 2; h++) memcpy(&padded[e * 32 + h * 16], in + (e * 2 + h) * B::L, B::L * 4);
+}
+template <class B>
+static void fq2_unpad(const std::vector<uint32_t>& padded, size_t elems, uint32_t* out) {
+    for (size_t e = 0; e < elems; e++)
+        for (int h = 0; h < 2; h++) memcpy(out + (e * 2 + h) * B::L, &padded[e * 32 + h * 16], B::L * 4);
+}
+static_assert(sizeof(Fp2L<F28>) == 128 && sizeof(Fp2L<BnG1::F>) == 128 && sizeof(XYZZ<Fp2L<F28>>) == 512, "lane-pair memory layout");
+
+template <class B>
+static __global__ void __launch_bounds__(64) k_test_fp2pair(int op, const Fp2L<B>* __restrict__ in, uint32_t n, Fp2L<B>* __restrict__ out) {
+    using H = Fp2H<B>;
+    const uint32_t item = ZL_PAIR_ITEM();
+    if (item >= n) return;  // (both lanes of a pair hold the same item)
+    const int half = zl::pair_half();
+    const H a = pair_load(&in[(size_t)4 * item], half), b = pair_load(&in[(size_t)4 * item + 1], half);
+    const H c = pair_load(&in[(size_t)4 * item + 2], half), d = pair_load(&in[(size_t)4 * item + 3], half);
+    H r = H::zero();
+    switch (op) {
+    case 0: r = zl::mul(a, b); break;
+    case 1: r = zl::sqr(a); break;
+    case 2: r = zl::muladd(a, b, c, d); break;
+    case 3: r = zl::add(a, b); break;
+    case 4: r = zl::dbl(a); break;
+    case 5: r = zl::subk<1>(a, b); break;
+    case 6: r = zl::subk<2>(a, b); break;
+    case 7: r = zl::subk<3>(a, b); break;
+    case 8: r = zl::subk<4>(a, b); break;
+    case 9: r = zl::subk<5>(a, b); break;
+    case 10: r = zl::subk<6>(a, b); break;
+    case 11: r = zl::wred(a); break;
+    case 12: r = zl::canon(a); break;
+    case 13: r.c.l[0] = a.is_zero() ? 1u : 0u; break;
+    case 14: r.c.l[0] = a.raw_zero() ? 1u : 0u; break;
+    case 15: r = zl::x3_of(a, b, c); break;
+    case 16: r = H::one(); break;
+    case 17: r = zl::negk<1>(a); break;
+    case 18: r = zl::negk<2>(a); break;
+    case 19: r = zl::negk<3>(a); break;
+    case 20: r = zl::negk<4>(a); break;
+    case 21: r = zl::negk<5>(a); break;
+    case 22: r = zl::negk<6>(a); break;
+    default: break;
+    }
+    pair_store(&out[item], half, r);
+}
+template <class B>
+static int test_fp2pair_op_t(zl_ctx* ctx, int op, const uint32_t* in, size_t n, uint32_t* out) {
+    std::vector<uint32_t> pin, pout(n * 32);
+    fq2_pad<B>(in, n * 4, pin);
+    const int rc = run_dev(ctx, pin.data(), pin.size(), pout.data(), pout.size(), [&](const uint32_t* d_in, uint32_t* d_out, hipStream_t st) {
+        hipLaunchKernelGGL((k_test_fp2pair<B>), dim3((uint32_t)((n + 31) / 32)), dim3(64), 0, st, op, reinterpret_cast<const Fp2L<B>*>(d_in), (uint32_t)n,
+                           reinterpret_cast<Fp2L<B>*>(d_out));
+    });
+    if (rc) return rc;
+    fq2_unpad<B>(pout, n, out);
+    return ZL_OK;
+}
+
+// the limbs of this lane against those of lane 0 of its quad
+template <class A, class P> __device__ __forceinline__ uint32_t quad_differs(const Fp28<A, P>& v) {
+    uint32_t d = 0;
+#pragma unroll
+    for (int i = 0; i < A::L; i++) d |= v.l[i] ^ zl::quad_bcast_u32<0>(v.l[i]);
+    return d;
+}
+template <class B> __device__ __forceinline__ uint32_t quad_differs(const Fp2H<B>& v) { return quad_differs(v.c); }
+template <class F> __device__ __forceinline__ uint32_t quad_differs(const XYZZ<F>& p) { return quad_differs(p.x) | quad_differs(p.y) | quad_differs(p.zz) | quad_differs(p.zzz); }
+// ops 0-2 on the quad forms, 3-5 per lane (every lane of the quad computes the same doubling / negation, as the kernels do); is_quad = false: the per-lane formulas throughout
+template <bool QUAD, class F>
+__device__ __forceinline__ void lane_point_op(int op, XYZZ<F>& p, const XYZZ<F>& q, int sub) {
+    switch (op) {
+    case 0:
+    case 1:
+        if constexpr (QUAD) zl::add_mixed_quad(p, q.x, q.y, op == 1, sub);
+        else zl::add_mixed(p, q.x, q.y, op == 1);
+        break;
+    case 2:
+        if constexpr (QUAD) zl::add_full_quad(p, q, sub);
+        else zl::add_full(p, q);
+        break;
+    case 3: zl::dbl_inplace(p); break;
+    case 4: p = zl::dbl_affine(p.x, p.y); break;
+    case 5: zl::neg_inplace(p); break;
+    default: break;
+    }
+}
+// G1, four lanes per item (lanes 4t .. 4t+3 of the grid, as k_msm_accumulate_quad); lane 0 of the quad stores
+template <class F>
+static __global__ void __launch_bounds__(64) k_test_point_quad(int op, const uint32_t* __restrict__ in, uint32_t n, uint32_t* __restrict__ out, uint32_t* __restrict__ flag) {
+    const uint32_t gt = blockIdx.x * blockDim.x + threadIdx.x, item = gt >> 2;
+    const int sub = (int)(gt & 3u);
+    if (item >= n) return;  // (uniform in a quad)
+    constexpr int W = RawIO<F>::W;
+    const uint32_t* rec = in + (size_t)item * 8 * W;
+    XYZZ<F> p{RawIO<F>::load(rec), RawIO<F>::load(rec + W), RawIO<F>::load(rec + 2 * W), RawIO<F>::load(rec + 3 * W)};
+    const XYZZ<F> q{RawIO<F>::load(rec + 4 * W), RawIO<F>::load(rec + 5 * W), RawIO<F>::load(rec + 6 * W), RawIO<F>::load(rec + 7 * W)};
+    if (op == 6) {
+        const Affine<F> a = zl::to_affine(p);
+        p.x = a.x; p.y = a.y; p.zz = F::one(); p.zzz = F::one();
+        if (a.is_inf()) { p.zz = F::zero(); p.zzz = F::zero(); }
+    } else {
+        lane_point_op<true>(op, p, q, sub);
+    }
+    if (quad_differs(p)) *flag = 1u;
+    if (sub != 0) return;
+    uint32_t* o = out + (size_t)item * 4 * W;
+    RawIO<F>::store(o, p.x);
+    RawIO<F>::store(o + W, p.y);
+    RawIO<F>::store(o + 2 * W, p.zz);
+    RawIO<F>::store(o + 3 * W, p.zzz);
+}
+// G2 on lane pairs (32 items per wave) or, OCTET, on a quad per half (8 items per wave); lane 0 of each quad stores its half
+template <class B, bool OCTET>
+static __global__ void __launch_bounds__(64) k_test_point_pair(int op, const XYZZ<Fp2L<B>>* __restrict__ in, uint32_t n, XYZZ<Fp2L<B>>* __restrict__ out, uint32_t* __restrict__ flag) {
+    using H = Fp2H<B>;
+    const uint32_t item = OCTET ? ZL_OCTET_ITEM() : ZL_PAIR_ITEM();
+    if (item >= n) return;  // (uniform in a pair / an octet)
+    const int half = zl::pair_half(), sub = (int)(threadIdx.x & 3u);
+    XYZZ<H> p = pair_load(&in[(size_t)2 * item], half);
+    const XYZZ<H> q = pair_load(&in[(size_t)2 * item + 1], half);
+    lane_point_op<OCTET>(op, p, q, sub);
+    if constexpr (OCTET) {
+        if (quad_differs(p)) *flag = 1u;
+        if (sub != 0) return;
+    }
+    pair_store(&out[item], half, p);
+}
+
+// one base field (= one curve): every form of the point formulas over it
+template <class B>
+static int test_point_form_t(zl_ctx* ctx, zl_group_t group, int form, int op, const uint32_t* in, size_t n, uint32_t* out) {
+    constexpr size_t L = B::L;
+    const size_t W = group == ZL_G1 ? L : 2 * L;
+    if (form == ZL_TEST_FORM_SCALAR || form == ZL_TEST_FORM_SCALAR_HOT) {
+        const bool hot = form == ZL_TEST_FORM_SCALAR_HOT;
+        if (!ctx) {
+            for (size_t i = 0; i < n; i++) {
+                if (group == ZL_G1) point_op<B>(op, in + i * 8 * W, out + i * 4 * W);
+                else if (hot) point_op<Fp2LT<B, true>>(op, in + i * 8 * W, out + i * 4 * W);
+                else point_op<Fp2LT<B, false>>(op, in + i * 8 * W, out + i * 4 * W);
+            }
+            return ZL_OK;
+        }
+        ZL_HIP(ctx, hipSetDevice(ctx->device));
+        return run_dev(ctx, in, n * 8 * W, out, n * 4 * W, [&](const uint32_t* d_in, uint32_t* d_out, hipStream_t st) {
+            const dim3 grid((uint32_t)((n + 63) / 64)), block(64);
+            if (group == ZL_G1) hipLaunchKernelGGL((k_test_point<B>), grid, block, 0, st, op, d_in, (uint32_t)n, d_out);
+            else if (hot) hipLaunchKernelGGL((k_test_point<Fp2LT<B, true>>), grid, block, 0, st, op, d_in, (uint32_t)n, d_out);
+            else hipLaunchKernelGGL((k_test_point<Fp2LT<B, false>>), grid, block, 0, st, op, d_in, (uint32_t)n, d_out);
+        });
+    }
+    if (!ctx) return ZL_EINVAL;  // the lane forms exist on the device only
+    ZL_HIP(ctx, hipSetDevice(ctx->device));
+    if (form == ZL_TEST_FORM_QUAD) {
+        if (group != ZL_G1) return ZL_EINVAL;
+        return run_dev_flag(ctx, in, n * 8 * W, out, n * 4 * W, [&](const uint32_t* d_in, uint32_t* d_out, uint32_t* d_flag, hipStream_t st) {
+            hipLaunchKernelGGL((k_test_point_quad<B>), dim3((uint32_t)((n + 15) / 16)), dim3(64), 0, st, op, d_in, (uint32_t)n, d_out, d_flag);
+        });
+    }
+    // pair / octet: G2; Fp2H has no inversion, so no to_affine (no kernel leaves the XYZZ form on lane pairs)
+    if (group != ZL_G2 || op == 6) return ZL_EINVAL;
+    std::vector<uint32_t> pin, pout(n * 4 * 32);
+    fq2_pad<B>(in, n * 8, pin);
+    const int rc = run_dev_flag(ctx, pin.data(), pin.size(), pout.data(), pout.size(), [&](const uint32_t* d_in, uint32_t* d_out, uint32_t* d_flag, hipStream_t st) {
+        const XYZZ<Fp2L<B>>* pi = reinterpret_cast<const XYZZ<Fp2L<B>>*>(d_in);
+        XYZZ<Fp2L<B>>* po = reinterpret_cast<XYZZ<Fp2L<B>>*>(d_out);
+        if (form == ZL_TEST_FORM_PAIR) hipLaunchKernelGGL((k_test_point_pair<B, false>), dim3((uint32_t)((n + 31) / 32)), dim3(64), 0, st, op, pi, (uint32_t)n, po, d_flag);
+        else hipLaunchKernelGGL((k_test_point_pair<B, true>), dim3((uint32_t)((n + 7) / 8)), dim3(64), 0, st, op, pi, (uint32_t)n, po, d_flag);
+    });
+    if (rc) return rc;
+    fq2_unpad<B>(pout, n * 4, out);
+    return ZL_OK;
+}
 
 // ------------------------------------------------------------------------------------------------ live-data multiplier rate
 // The ceiling bench.py's integer-ALU roofline is quoted against, measured on the box of the run: every lane chains x <- x * y with the product scan
@@ -437,6 +642,23 @@ int zl_test_point_op(zl_ctx* ctx, zl_group_t group, int hot, int op, const uint3
         else if (hot) hipLaunchKernelGGL((k_test_point<Fp2LT<F28, true>>), grid, block, 0, st, op, d_in, (uint32_t)n, d_out);
         else hipLaunchKernelGGL((k_test_point<Fp2LT<F28, false>>), grid, block, 0, st, op, d_in, (uint32_t)n, d_out);
     });
+}
+
+int zl_test_fp2pair_op(zl_ctx* ctx, zl_curve_t curve, int op, const uint32_t* in, size_t n, uint32_t* out) {
+    if (!ctx || ((!in || !out) && n)) return ZL_EINVAL;
+    if (op < 0 || op > 22 || n >= (1u << 20) || (curve != ZL_BLS12_381 && curve != ZL_BN254)) return ZL_EINVAL;
+    if (!n) return ZL_OK;
+    ZL_HIP(ctx, hipSetDevice(ctx->device));
+    return curve == ZL_BLS12_381 ? test_fp2pair_op_t<F28>(ctx, op, in, n, out) : test_fp2pair_op_t<BnG1::F>(ctx, op, in, n, out);
+}
+
+int zl_test_point_form_op(zl_ctx* ctx, zl_curve_t curve, zl_group_t group, int form, int op, const uint32_t* in, size_t n, uint32_t* out) {
+    if ((!in || !out) && n) return ZL_EINVAL;
+    if (op < 0 || op > 6 || n >= (1u << 18) || (group != ZL_G1 && group != ZL_G2) || (curve != ZL_BLS12_381 && curve != ZL_BN254)) return ZL_EINVAL;
+    if (form < ZL_TEST_FORM_SCALAR || form > ZL_TEST_FORM_OCTET) return ZL_EINVAL;
+    if (!ctx && form > ZL_TEST_FORM_SCALAR_HOT) return ZL_EINVAL;
+    if (!n) return ZL_OK;
+    return curve == ZL_BLS12_381 ? test_point_form_t<F28>(ctx, group, form, op, in, n, out) : test_point_form_t<BnG1::F>(ctx, group, form, op, in, n, out);
 }
 
 int zl_test_fr28_op(zl_ctx* ctx, zl_curve_t curve, int op, int j, const uint32_t* in, size_t n, uint32_t* out) {

@@ -40,6 +40,14 @@ def test_library_exports_every_declared_test_hook():
         assert getattr(L, sym) is not None
     assert L.zl_test_fp28_op(None, 99, None, 0, None) == -1
     assert L.zl_test_poseidon_permute_dev(None, 1, None) == -1
+    # the lane forms (Fq2 on a lane pair, quad / pair / octet point formulas) exist on the device only: a null ctx is ZL_EINVAL, the scalar forms keep a host path
+    assert L.zl_test_fp2pair_op(None, 1, 0, None, 0, None) == -1
+    for curve in (1, 2):
+        for form, group in ((2, 1), (3, 2), (4, 2)):
+            assert L.zl_test_point_form_op(None, curve, group, form, 2, None, 0, None) == -1
+        assert L.zl_test_point_form_op(None, curve, 1, 0, 2, None, 0, None) == 0
+        assert L.zl_test_point_form_op(None, curve, 2, 1, 2, None, 0, None) == 0
+    assert L.zl_test_point_form_op(None, 1, 1, 5, 2, None, 0, None) == -1
 
 
 def test_strerror_and_argument_checks():
