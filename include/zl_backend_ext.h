@@ -91,7 +91,7 @@ typedef struct zl_g16_shard {
 int zl_groth16_prove_sharded(zl_mctx* m, const zl_g16_pk* pk, const zl_g16_shard* shards, uint64_t r1cs_handle_rank0, const uint64_t* assignment,
                              unsigned flags, const uint64_t* r, const uint64_t* s, zl_g16_proof* out);
 /* the quotient polynomial h of the last successful zl_groth16_prove* call on this ctx (N x 4 u64 canonical), for tests;
- * ZL_EINVAL when there is none (it lives in scratch slot 8 and is invalidated when the next proof starts) */
+ * ZL_EINVAL when there is none (it lives in the Groth16 scratch block of the ctx and is invalidated when the next proof starts) */
 int zl_groth16_last_h(zl_ctx* ctx, uint64_t* out, size_t n);
 
 /* ---- host mirror of the plugin interface (C hooks over the C++ classes of openzl_amd/csrc/zl_host.h) ------------

@@ -398,7 +398,7 @@ int zl_msm(zl_ctx* ctx, uint64_t bases, size_t first, const uint64_t* scalars, s
     ZL_HIP(ctx, hipSetDevice(ctx->device));
     void* d_sc = nullptr;
     if (n) {
-        int rc = zl_scratch_get(ctx, 7, n * 32, &d_sc);
+        int rc = zl_scratch_get(ctx, ZL_SLOT_STAGING, n * 32, &d_sc);
         if (rc) return rc;
         // the window table of a precomputed handle is built for full-size MSMs over it; shards would each pay its merged bucket set
         // (ZL_TUNE_HOST_CHUNK_MIN_LOG: developer / test knob -- the shard pipeline at sizes the oracle can check, with ZL_TUNE_HOST_SHARDS naming the shards)
@@ -450,7 +450,7 @@ int zl_ntt(zl_ctx* ctx, zl_curve_t curve, uint64_t* data, unsigned log_n, unsign
     ZL_HIP(ctx, hipSetDevice(ctx->device));
     const size_t bytes = ((size_t)1 << log_n) * 32;
     void* d;
-    int rc = zl_scratch_get(ctx, 7, bytes, &d);
+    int rc = zl_scratch_get(ctx, ZL_SLOT_STAGING, bytes, &d);
     if (rc) return rc;
     ZL_HIP(ctx, hipMemcpyAsync(d, data, bytes, hipMemcpyHostToDevice, ctx->stream));
     rc = zl_ntt_dev(ctx, curve, d, log_n, flags);

@@ -5,6 +5,7 @@
 #include <stdlib.h>
 #include <atomic>
 #include <functional>
+#include <initializer_list>
 #include <map>
 #include <memory>
 #include <mutex>
@@ -110,6 +111,65 @@ struct zl_scratch {
     void* p = nullptr;
     size_t cap = 0;
 };
+// ---- the map of zl_ctx::scratch: every grow-only device block of a ctx, by owner --------------------------------------------------------
+// A ctx is SINGLE-CALLER and every entry point drains the ctx's streams before it returns, so a block is only ever shared between calls:
+//   * MSM buffer sets 0..3 (ZL_MSM_SET below).  A single call uses set 0; the three-phase pipeline rotates sets 0..2 and sorts every job in
+//     ZL_SLOT_SORT_A / _B (the sorts run in order on one stream); small jobs side by side take sets 0..3, each with its own sort pair.
+//   * ZL_SLOT_PHI_ONE_KEY: the endomorphism image of the bases when the jobs of a call share one key (single call, pipelined batch over one
+//     handle); a heterogeneous or side-by-side batch keeps one image per set (phi).
+//   * ZL_SLOT_TMP_A / _B are set 0's sort pair under another name: the bases entry points (upload staging, download, generation, the
+//     fixed-base and window tables, their batch normalisation) use them as general temporaries, and ZL_SLOT_NTT_VEC (= _B) is the transform's
+//     vector between passes.  None of these calls contains an MSM and each has drained when it returns, so no sort is in flight when they
+//     resize the blocks (a proof's transforms run on ctx->aux2, whose slots are its own).
+//   * ZL_SLOT_STAGING: host scalars / vectors uploaded for one call.  ZL_SLOT_GROTH16: the witness map's vectors (the quotient of the last
+//     proof stays there, zl_ctx::g16_h).  ZL_SLOT_TESTHOOK: inputs and outputs of the test hooks.
+//   * ZL_SLOT_PAIR_*: the device product of pairings.
+enum zl_slot : int {
+    ZL_SLOT_SET0_COUNTS = 0, ZL_SLOT_SET0_ENTRIES = 1, ZL_SLOT_SET0_BUCKETS = 2, ZL_SLOT_SET0_PARTIALS = 3, ZL_SLOT_SET0_TAIL = 4,
+    ZL_SLOT_SORT_A = 5, ZL_SLOT_SORT_B = 6,
+    ZL_SLOT_TMP_A = ZL_SLOT_SORT_A, ZL_SLOT_TMP_B = ZL_SLOT_SORT_B, ZL_SLOT_NTT_VEC = ZL_SLOT_SORT_B,
+    ZL_SLOT_STAGING = 7, ZL_SLOT_GROTH16 = 8, ZL_SLOT_TESTHOOK = 9,
+    ZL_SLOT_SET1_COUNTS = 10, ZL_SLOT_SET1_ENTRIES = 11, ZL_SLOT_SET1_BUCKETS = 12, ZL_SLOT_SET1_PARTIALS = 13,
+    ZL_SLOT_SET2_COUNTS = 14, ZL_SLOT_SET2_ENTRIES = 15, ZL_SLOT_SET2_BUCKETS = 16, ZL_SLOT_SET2_PARTIALS = 17,
+    ZL_SLOT_PHI_ONE_KEY = 18,
+    ZL_SLOT_SET1_TAIL = 19,
+    ZL_SLOT_SET0_PHI = 20, ZL_SLOT_SET1_PHI = 21, ZL_SLOT_SET2_PHI = 22,
+    ZL_SLOT_SET2_TAIL = 23,
+    ZL_SLOT_SET1_SORT_A = 24, ZL_SLOT_SET1_SORT_B = 25, ZL_SLOT_SET2_SORT_A = 26, ZL_SLOT_SET2_SORT_B = 27,
+    ZL_SLOT_SET3_COUNTS = 28, ZL_SLOT_SET3_ENTRIES = 29, ZL_SLOT_SET3_BUCKETS = 30, ZL_SLOT_SET3_PARTIALS = 31, ZL_SLOT_SET3_TAIL = 32,
+    ZL_SLOT_SET3_SORT_A = 33, ZL_SLOT_SET3_SORT_B = 34, ZL_SLOT_SET3_PHI = 35,
+    ZL_SLOT_PAIR_IN = 36, ZL_SLOT_PAIR_LINES = 37, ZL_SLOT_PAIR_ACC = 38, ZL_SLOT_PAIR_PREP = 39,
+    ZL_SLOT_COUNT = 40
+};
+// the slots of MSM buffer set 0..3; sort_a / sort_b are used by a job that owns its sort (side by side), every other job sorts in set 0's pair
+struct zl_msm_set_slots {
+    zl_slot data[4], tail, sort_a, sort_b, phi;  // data: counters | sorted entries | buckets | chunk partials
+};
+constexpr zl_msm_set_slots ZL_MSM_SET[4] = {
+    {{ZL_SLOT_SET0_COUNTS, ZL_SLOT_SET0_ENTRIES, ZL_SLOT_SET0_BUCKETS, ZL_SLOT_SET0_PARTIALS}, ZL_SLOT_SET0_TAIL, ZL_SLOT_SORT_A, ZL_SLOT_SORT_B, ZL_SLOT_SET0_PHI},
+    {{ZL_SLOT_SET1_COUNTS, ZL_SLOT_SET1_ENTRIES, ZL_SLOT_SET1_BUCKETS, ZL_SLOT_SET1_PARTIALS}, ZL_SLOT_SET1_TAIL, ZL_SLOT_SET1_SORT_A, ZL_SLOT_SET1_SORT_B, ZL_SLOT_SET1_PHI},
+    {{ZL_SLOT_SET2_COUNTS, ZL_SLOT_SET2_ENTRIES, ZL_SLOT_SET2_BUCKETS, ZL_SLOT_SET2_PARTIALS}, ZL_SLOT_SET2_TAIL, ZL_SLOT_SET2_SORT_A, ZL_SLOT_SET2_SORT_B, ZL_SLOT_SET2_PHI},
+    {{ZL_SLOT_SET3_COUNTS, ZL_SLOT_SET3_ENTRIES, ZL_SLOT_SET3_BUCKETS, ZL_SLOT_SET3_PARTIALS}, ZL_SLOT_SET3_TAIL, ZL_SLOT_SET3_SORT_A, ZL_SLOT_SET3_SORT_B, ZL_SLOT_SET3_PHI},
+};
+// every slot of the four sets and every slot outside them has one owner (the aliases of set 0's sort pair above are the only sharing)
+constexpr bool zl_slots_disjoint() {
+    int owners[ZL_SLOT_COUNT] = {};
+    for (const zl_msm_set_slots& s : ZL_MSM_SET)
+        for (zl_slot x : {s.data[0], s.data[1], s.data[2], s.data[3], s.tail, s.sort_a, s.sort_b, s.phi}) {
+            if (x < 0 || x >= ZL_SLOT_COUNT) return false;
+            owners[x]++;
+        }
+    for (zl_slot x : {ZL_SLOT_PHI_ONE_KEY, ZL_SLOT_STAGING, ZL_SLOT_GROTH16, ZL_SLOT_TESTHOOK, ZL_SLOT_PAIR_IN, ZL_SLOT_PAIR_LINES, ZL_SLOT_PAIR_ACC, ZL_SLOT_PAIR_PREP}) {
+        if (x < 0 || x >= ZL_SLOT_COUNT) return false;
+        owners[x]++;
+    }
+    for (int n : owners)
+        if (n > 1) return false;
+    return true;
+}
+static_assert(zl_slots_disjoint(), "scratch slots: the four MSM buffer sets, the shared / staging slots and the pairing product must not collide");
+static_assert(ZL_SLOT_TMP_A == ZL_MSM_SET[0].sort_a && ZL_SLOT_TMP_B == ZL_MSM_SET[0].sort_b && ZL_SLOT_NTT_VEC == ZL_MSM_SET[0].sort_b,
+              "the general temporaries and the transform's vector are set 0's sort pair and nothing else (see the map)");
 struct zl_twiddles {
     void* d_lo = nullptr;  // w^i, i < 2^lo_bits
     void* d_hi = nullptr;  // w^(i << lo_bits)
@@ -149,7 +209,7 @@ struct zl_ctx {
     std::map<uint64_t, zl_bases> bases;
     std::map<uint64_t, zl_r1cs_dev> r1cs;
     uint64_t next_handle = 1;
-    zl_scratch scratch[40];  // 0..9: first buffer set + shared; 10..13 / 14..17: second / third MSM buffer set (pipelined batches); 18, 20..22: endomorphism images of the bases (GLV); 4, 19, 23: tail buffers of the three sets
+    zl_scratch scratch[ZL_SLOT_COUNT];  // by zl_slot: the map above
     std::map<uint64_t, zl_twiddles> twiddles;  // key: curve<<16 | log_n<<1 | inverse
     size_t ntt_last_bytes = 0;   // bytes held by the d_last tables of this ctx
     // events of the job pipelines, created once and reused by every call: a hipEventCreate / hipEventDestroy pair costs ~50 us of host time, and a
@@ -172,7 +232,7 @@ struct zl_ctx {
     zl_ctx* aux = nullptr;  // auxiliary stream + scratch set (Groth16: the G2 MSM overlaps the G1 MSMs)
     void* fb_table[4] = {nullptr, nullptr, nullptr, nullptr};  // fixed-base window tables of the generators (per group config, built on first use)
     zl_worker* workers[8] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};  // persistent host threads of this ctx: 0 witness-map issue, 1 G2 MSM (Groth16); 2..5 one per lane stream (side-by-side MSM batches)
-    void* g16_h = nullptr;  // quotient polynomial of the last zl_groth16_prove (inside scratch slot 8; reset when the next proof starts)
+    void* g16_h = nullptr;  // quotient polynomial of the last zl_groth16_prove (inside ZL_SLOT_GROTH16; reset when the next proof starts)
     size_t g16_h_n = 0;
     int ntt_fit_beside = 0;  // this ctx's transforms run beside a kernel that leaves 96 registers per SIMD (a proof's witness map: ctx->aux2): use the capped passes (zl_ntt.hip)
     void* g16_z = nullptr;  // the canonical assignment of the last witness-map-only run (sharded proofs: the other ranks copy their slices from here)
@@ -239,8 +299,8 @@ inline zl_worker& zl_ctx_worker(zl_ctx* ctx, int k) {
     if (!ctx->workers[k]) ctx->workers[k] = new zl_worker();
     return *ctx->workers[k];
 }
-// grow-only device scratch slot
-inline int zl_scratch_get(zl_ctx* ctx, int slot, size_t bytes, void** out) {
+// grow-only device scratch slot (growth synchronises ctx->stream only and frees the old block: callers size a slot before anything that uses it is in flight)
+inline int zl_scratch_get(zl_ctx* ctx, zl_slot slot, size_t bytes, void** out) {
     zl_scratch& s = ctx->scratch[slot];
     if (s.cap < bytes) {
         if (s.p) {

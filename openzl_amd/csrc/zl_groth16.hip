@@ -351,7 +351,7 @@ static int groth16_prove_t(zl_ctx* ctx, const zl_g16_pk* pk, const zl_r1cs_dev* 
     const size_t off_a = take((size_t)N * 32), off_b = take((size_t)N * 32), off_c = take((size_t)N * 32), off_h = take((fold_head + N) * 32) + fold_head * 32;
     void* base;
     int rc;
-    if ((rc = zl_scratch_get(ctx, 8, bytes, &base))) return rc;  // slots 0-7 belong to the MSM / NTT / staging paths
+    if ((rc = zl_scratch_get(ctx, ZL_SLOT_GROTH16, bytes, &base))) return rc;
     unsigned char* d = reinterpret_cast<unsigned char*>(base);
     const unsigned char* dm = reinterpret_cast<const unsigned char*>(cs->d_base);
     const size_t* off_ptr = cs->off_ptr;
@@ -687,7 +687,7 @@ static int groth16_prove_sharded_t(zl_mctx* m, const zl_g16_pk* pk, const zl_g16
             // this rank's scalars: [variables | witnesses | quotient coefficients], canonical, copied from rank 0's device
             void* d = nullptr;
             const size_t nvar = sh.var_count, nwit = sh.wit_count, nh = sh.h_count;
-            int r2 = zl_scratch_get(c, 7, (nvar + nwit + nh + 1) * 32, &d);
+            int r2 = zl_scratch_get(c, ZL_SLOT_STAGING, (nvar + nwit + nh + 1) * 32, &d);
             if (r2) return fail(r2);
             unsigned char* ds = reinterpret_cast<unsigned char*>(d);
             hipError_t e = hipSuccess;

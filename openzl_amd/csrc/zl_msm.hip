@@ -57,7 +57,7 @@ static int msm_run_t(zl_ctx* ctx, const zl_bases& bs, size_t first, const void* 
         const auto tp0 = std::chrono::steady_clock::now();
         MsmJob<G> job;
         int rc;
-        if ((rc = job.plan(ctx, bs, first, d_scalars, n, 18))) return rc;
+        if ((rc = job.plan(ctx, bs, first, d_scalars, n, ZL_SLOT_PHI_ONE_KEY))) return rc;
         if ((rc = job.alloc(ctx, 0))) return rc;
         {   // results land in pinned host memory: the two D2H copies are then plain queue entries behind the last kernel (from pageable
             // memory each cost a staging round trip: ~25 us of idle device in front of either copy)
@@ -155,10 +155,9 @@ static int msm_run_jobs_t(zl_ctx* ctx, const MsmSpec* specs, size_t count, uint6
         for (auto& t : ctx->stream_tail) ZL_HIP(ctx, hipStreamCreateWithPriority(&t, hipStreamNonBlocking, prio_hi));
     }
     std::vector<MsmJob<G>> jobs(count);
-    size_t t5 = 0, t6 = 0;
     uint32_t max_sets = 0;
-    // GLV jobs need phi(P_i) of their bases: a batch over ONE key computes it once (job 0, slot 18; the later jobs borrow the pointer --
-    // their sorts run behind job 0's on the sort stream), a heterogeneous batch once per job in the slot of its buffer set (20 + i % 3: free
+    // GLV jobs need phi(P_i) of their bases: a batch over ONE key computes it once (job 0, ZL_SLOT_PHI_ONE_KEY; the later jobs borrow the pointer --
+    // their sorts run behind job 0's on the sort stream), a heterogeneous batch once per job in the slot of its buffer set (free
     // again when the tail of job i - 3 has finished, like the rest of the set)
     bool one_key = true;
     for (size_t i = 1; i < count; i++) one_key = one_key && specs[i].bs == specs[0].bs && specs[i].first == specs[0].first && specs[i].n == specs[0].n;
@@ -173,12 +172,8 @@ static int msm_run_jobs_t(zl_ctx* ctx, const MsmSpec* specs, size_t count, uint6
     const size_t NS = side ? std::min<size_t>(count, (size_t)std::min(4, std::max(1, zl_tune("ZL_TUNE_SIDE_LANES", 4)))) : 3;
     for (size_t i = 0; i < count; i++) {
         // (side by side every job computes its own phi image: there is no common stream that would order a borrower behind the owner)
-        if ((rc = jobs[i].plan(ctx, *specs[i].bs, specs[i].first, specs[i].d_scalars, specs[i].n, (one_key && !side) ? 18 : MsmJob<G>::phi_slot_of((int)(i % NS))))) return rc;
+        if ((rc = jobs[i].plan(ctx, *specs[i].bs, specs[i].first, specs[i].d_scalars, specs[i].n, (one_key && !side) ? ZL_SLOT_PHI_ONE_KEY : ZL_MSM_SET[i % NS].phi))) return rc;
         if (one_key && !side && i > 0) jobs[i].phi_owner = false;
-        size_t a5, a6;
-        jobs[i].sort_tmp_sizes(a5, a6);
-        t5 = std::max(t5, a5);
-        t6 = std::max(t6, a6);
         max_sets = std::max<uint32_t>(max_sets, jobs[i].SETS * jobs[i].roots_per_set);
     }
     // SMALL side-by-side jobs (the MSMs of a small proof: chains of ~25 kernels of 5-20 us) run on the ordinary default-class lanes.  The runtime multiplexes the
@@ -192,11 +187,8 @@ static int msm_run_jobs_t(zl_ctx* ctx, const MsmSpec* specs, size_t count, uint6
             if (!lanes[k]) ZL_HIP(ctx, hipStreamCreateWithFlags(&lanes[k], hipStreamNonBlocking));
     }
     // all buffers up front (growth synchronises and frees: nothing may be in flight), then bind set i % 3 to job i: the first pass
-    // grows every slot to its largest user, the second binds the final pointers.  Three sets: the tail of job i runs beside the
+    // grows every slot (the shared sort temporaries among them) to its largest user, the second binds the final pointers.  Three sets: the tail of job i runs beside the
     // accumulation of job i+1 and is slow there, so the sort of job i+2 must not have to wait for it.
-    void* dummy;
-    if (!side && t5 && (rc = zl_scratch_get(ctx, 5, t5, &dummy))) return rc;
-    if (!side && t6 && (rc = zl_scratch_get(ctx, 6, t6, &dummy))) return rc;
     for (int pass = 0; pass < 2; pass++) {
         for (size_t i = 0; i < count; i++) {
             if ((rc = jobs[i].alloc(ctx, (int)(i % NS), side))) return rc;
@@ -426,14 +418,14 @@ static int bases_flag_inf_t(zl_ctx* ctx, zl_bases* b) {
     b->n_inf = cnt;
     return ZL_OK;
 }
-// in (XYZZ / Jacobian, n elements) -> out (affine), sharing one inversion among the elements of a lane; prefix scratch in slot `slot`
+// in (XYZZ / Jacobian, n elements) -> out (affine), sharing one inversion among the elements of a lane; prefix products in ZL_SLOT_TMP_B
 template <class G, int FORM>
-static int batch_affine_t(zl_ctx* ctx, const void* d_in, size_t n, Affine<typename G::F>* d_out, int slot, hipStream_t st) {
+static int batch_affine_t(zl_ctx* ctx, const void* d_in, size_t n, Affine<typename G::F>* d_out, hipStream_t st) {
     using F = typename G::F;
     if (!n) return ZL_OK;
     void* d_prefix;
     int rc;
-    if ((rc = zl_scratch_get(ctx, slot, n * sizeof(F), &d_prefix))) return rc;
+    if ((rc = zl_scratch_get(ctx, ZL_SLOT_TMP_B, n * sizeof(F), &d_prefix))) return rc;
     // ~2^18 lanes (>= 1 wave per SIMD) once there is enough work; up to 64 elements share an inversion
     uint32_t per = (uint32_t)std::min<size_t>(64, std::max<size_t>(1, n >> 18));
     per = (uint32_t)std::max(1, zl_tune("ZL_TUNE_BATCH_INV", (int)per));
@@ -451,14 +443,14 @@ static int fb_table_get(zl_ctx* ctx, const Affine<typename G::F>** out) {
         const size_t entries = (size_t)ZL_FB_WINDOWS << ZL_FB_BITS;
         void *d_tab = nullptr, *d_tmp = nullptr;
         ZL_HIP(ctx, hipMalloc(&d_tab, entries * sizeof(Affine<F>)));
-        int rc = zl_scratch_get(ctx, 5, (entries + ZL_FB_WINDOWS) * sizeof(XYZZ<F>), &d_tmp);
+        int rc = zl_scratch_get(ctx, ZL_SLOT_TMP_A, (entries + ZL_FB_WINDOWS) * sizeof(XYZZ<F>), &d_tmp);
         if (rc) { (void)hipFree(d_tab); return rc; }
         XYZZ<F>* d_bw = (XYZZ<F>*)d_tmp;
         XYZZ<F>* d_x = d_bw + ZL_FB_WINDOWS;
         hipStream_t st = ctx->stream;
         hipLaunchKernelGGL((k_fb_bases<G>), dim3((ZL_FB_WINDOWS + 63) / 64), dim3(64), 0, st, d_bw);
         hipLaunchKernelGGL((k_fb_table<G>), dim3((uint32_t)((entries + 63) / 64)), dim3(64), 0, st, d_bw, d_x);
-        rc = batch_affine_t<G, 0>(ctx, d_x, entries, (Affine<F>*)d_tab, 6, st);
+        rc = batch_affine_t<G, 0>(ctx, d_x, entries, (Affine<F>*)d_tab, st);
         hipError_t e = rc ? hipSuccess : hipStreamSynchronize(st);
         if (rc || e != hipSuccess) { (void)hipFree(d_tab); if (!rc) { ctx->last_hip = (int)e; rc = ZL_EHIP; } return rc; }
         slot = d_tab;
@@ -483,13 +475,13 @@ static int bases_precompute_t(zl_ctx* ctx, zl_bases& bs, int c) {
         hipStream_t st = ctx->stream;
         Affine<F>* tab = reinterpret_cast<Affine<F>*>(t);
         void* d_jac = nullptr;
-        int rc = zl_scratch_get(ctx, 5, bs.n * sizeof(Jac<F>), &d_jac);
+        int rc = zl_scratch_get(ctx, ZL_SLOT_TMP_A, bs.n * sizeof(Jac<F>), &d_jac);
         hipError_t e = rc ? hipSuccess : hipMemcpyAsync(tab, bs.d_pts, bs.n * sizeof(Affine<F>), hipMemcpyDeviceToDevice, st);
         for (int w = 1; w < W && !rc && e == hipSuccess; w++) {
             hipLaunchKernelGGL((k_bases_level_dbl<G>), dim3((uint32_t)((bs.n + 63) / 64)), dim3(64), 0, st, tab + (size_t)(w - 1) * bs.n, (uint32_t)bs.n, c,
                                (Jac<F>*)d_jac);
             e = hipGetLastError();
-            if (e == hipSuccess) rc = batch_affine_t<G, 1>(ctx, d_jac, bs.n, tab + (size_t)w * bs.n, 6, st);
+            if (e == hipSuccess) rc = batch_affine_t<G, 1>(ctx, d_jac, bs.n, tab + (size_t)w * bs.n, st);
         }
         if (!rc && e == hipSuccess) e = hipStreamSynchronize(st);
         if (rc || e != hipSuccess) {
@@ -602,7 +594,7 @@ static int bases_upload_t(zl_ctx* ctx, const void* xy, size_t n, size_t stride, 
             for (size_t i = 0; i < n; i++) flags_host[i] = src[i * stride + (size_t)inf_off] ? 1 : 0;
         }
         void* d_in;
-        if ((rc = zl_scratch_get(ctx, 5, n * rec + n + 64, &d_in))) { (void)hipFree(d_pts); return rc; }
+        if ((rc = zl_scratch_get(ctx, ZL_SLOT_TMP_A, n * rec + n + 64, &d_in))) { (void)hipFree(d_pts); return rc; }
         uint8_t* d_flags = reinterpret_cast<uint8_t*>(d_in) + n * rec;
         uint32_t* d_bad = reinterpret_cast<uint32_t*>(reinterpret_cast<unsigned char*>(d_in) + ((n * rec + n + 15) / 16) * 16);
         hipStream_t st = ctx->stream;
@@ -669,9 +661,9 @@ static int bases_generate_t(zl_ctx* ctx, const uint64_t* k, size_t n, zl_bases* 
         void* d_k;
         int rc;
         const Affine<F>* d_tab = nullptr;
-        if ((rc = fb_table_get<G>(ctx, &d_tab))) { (void)hipFree(d_pts); return rc; }  // uses slots 5 / 6 itself: before d_k is bound
+        if ((rc = fb_table_get<G>(ctx, &d_tab))) { (void)hipFree(d_pts); return rc; }  // uses ZL_SLOT_TMP_A / _B itself: before d_k is bound
         void* d_x;
-        if ((rc = zl_scratch_get(ctx, 5, n * 32 + 256 + n * sizeof(XYZZ<F>), &d_k))) { (void)hipFree(d_pts); return rc; }
+        if ((rc = zl_scratch_get(ctx, ZL_SLOT_TMP_A, n * 32 + 256 + n * sizeof(XYZZ<F>), &d_k))) { (void)hipFree(d_pts); return rc; }
         d_x = reinterpret_cast<unsigned char*>(d_k) + ((n * 32 + 255) / 256) * 256;
         hipStream_t st = ctx->stream;
         hipError_t e = hipMemcpyAsync(d_k, k, n * 32, hipMemcpyHostToDevice, st);
@@ -679,7 +671,7 @@ static int bases_generate_t(zl_ctx* ctx, const uint64_t* k, size_t n, zl_bases* 
             hipLaunchKernelGGL((k_bases_generate_fb<G>), dim3((uint32_t)((n + 63) / 64)), dim3(64), 0, st, (const uint32_t*)d_k, (uint32_t)n, d_tab, (XYZZ<F>*)d_x);
             e = hipGetLastError();
         }
-        if (e == hipSuccess) rc = batch_affine_t<G, 0>(ctx, d_x, n, (Affine<F>*)d_pts, 6, st);
+        if (e == hipSuccess) rc = batch_affine_t<G, 0>(ctx, d_x, n, (Affine<F>*)d_pts, st);
         if (e == hipSuccess && !rc) e = hipStreamSynchronize(st);
         if (rc || e != hipSuccess) { if (!rc) { ctx->last_hip = (int)e; rc = ZL_EHIP; } (void)hipStreamSynchronize(st); (void)hipFree(d_pts); return rc; }
     }
@@ -701,7 +693,7 @@ static int bases_download_t(zl_ctx* ctx, const zl_bases& b, size_t first, size_t
     void* d_out;
     int rc;
     const size_t rec = (size_t)2 * FieldIO<F>::WORDS * 4;
-    if ((rc = zl_scratch_get(ctx, 5, count * rec, &d_out))) return rc;
+    if ((rc = zl_scratch_get(ctx, ZL_SLOT_TMP_A, count * rec, &d_out))) return rc;
     hipStream_t st = ctx->stream;
     hipLaunchKernelGGL((k_bases_export<G>), dim3((uint32_t)((count + 127) / 128)), dim3(128), 0, st,
                        reinterpret_cast<const Affine<F>*>(b.d_pts) + first, (uint32_t)count, (uint32_t*)d_out);

@@ -78,6 +78,18 @@ static int zl_pick_window_precomp(size_t n, int sc_bits) {
 // (sort of MSM i+2 | bucket accumulation of MSM i+1 | merge / reduction tail of MSM i): plan() sizes everything, alloc() binds one of
 // three buffer sets, sort() builds the bucket-sorted entry list, accumulate() is the dominant kernel, tail() leaves SETS window sums
 // (+ the sum of the scalar-1 bases) in host memory, finish() does the host Horner.
+// Byte layout of a planned job's two sort temporaries (slot A, slot B).  plan_as fills it and is the only place this arithmetic exists: alloc
+// sizes and binds the slots from it, the sort functions add the offsets to the bound pointers.
+struct MsmSortLayout {
+    size_t a_bytes = 0, b_bytes = 0;  // what the job needs of slot A / slot B (0: nothing -- the global-atomics sort)
+    uint32_t nslices = 0, per_slice = 0;
+    // three-level sort.  A: lo16 | hi8 | part_lo | part_idx | partition counters (P counts, P + 1 offsets, block sums); B: lo2 | idx2 | counters2 (likewise over P2)
+    size_t hi8 = 0, part_lo = 0, part_idx = 0, pcounts = 0, idx2 = 0, counts2 = 0;
+    uint32_t P = 0, pscan_blocks = 0, fsl = 0, P2 = 0, p2scan_blocks = 0;
+    // LDS sort.  A: digits | per-slice bucket counts
+    size_t slice_counts = 0;
+    size_t vs = 0;  // GLV: the half-scalars, behind A's temporaries
+};
 template <class G>
 struct MsmJob {
     using F = typename G::F;
@@ -90,8 +102,10 @@ struct MsmJob {
     bool glv = false;   // the job runs on 2 n_real half-scalars of 127 bits over the points P_i and phi(P_i) (k_glv_split / k_glv_phi)
     bool phi_cached = false;  // d_phi is the handle's own copy (zl_bases::d_endo)
     bool phi_owner = false;  // this job computes the phi image of its bases in its sort phase (else it borrows d_phi from an earlier job of the call)
-    int sc_bits = 0, phi_slot = -1, endo_k = 1;  // endo_k: half-scalars per scalar (2: GLV on G1, 4: GLS on BLS12-381 G2)
-    int slotA = 5, slotB = 6;  // scratch slots of the sort temporaries (shared by the jobs of a pipelined batch; per buffer set when small jobs run side by side)
+    int sc_bits = 0, endo_k = 1;  // endo_k: half-scalars per scalar (2: GLV on G1, 4: GLS on BLS12-381 G2)
+    zl_slot phi_slot = ZL_SLOT_PHI_ONE_KEY;
+    MsmSortLayout lay;
+    unsigned char *d_sort_a = nullptr, *d_sort_b = nullptr;  // the sort temporaries (ZL_SLOT_SORT_A / _B: shared by the jobs of a pipelined batch; the set's own pair when small jobs run side by side)
     size_t n_real = 0;
     uint32_t* d_vs = nullptr;            // the half-scalars (inside the sort temporaries)
     const Affine<F>* d_phi = nullptr;    // phi(P_i), i < n_real
@@ -120,8 +134,8 @@ struct MsmJob {
         hE = reinterpret_cast<uint32_t*>(buf + (size_t)SETS * roots_per_set + 1);
     }
 
-    // phi_slot_: scratch slot for the endomorphism image of the bases when this job computes it (GLV); -1 = never use the endomorphism
-    int plan(zl_ctx* ctx, const zl_bases& bs, size_t first_, const void* d_scalars, size_t n_, int phi_slot_ = -1) {
+    // phi_slot_: scratch slot for the endomorphism image of the bases when this job computes it (GLV)
+    int plan(zl_ctx* ctx, const zl_bases& bs, size_t first_, const void* d_scalars, size_t n_, zl_slot phi_slot_) {
         static const bool no_glv = getenv("ZL_NO_GLV") != nullptr;  // developer A/B switch
         bool try_glv = false;
         // Measured (round 3, profiles/r03_glv_ab.log): halving the bucket sets wins where the merge / reduction tails and the host Horner dominate
@@ -129,7 +143,7 @@ struct MsmJob {
         // (read + write of every point) and the three-level sort of 2 n records cost what the tail saves (2^20: 3.73 = 3.73 ms; 2^24 single
         // call 39.2 -> 39.7 ms, pipelined 36.7 = 36.7), so large inputs keep the plain 255-bit windows.
         static const size_t glv_max = (size_t)1 << zl_tune("ZL_TUNE_GLV_MAX_LOG", 19);
-        if constexpr (G::GLV) try_glv = phi_slot_ >= 0 && bs.precomp_c == 0 && !no_glv && n_ >= 1 && n_ <= glv_max && (uint64_t)n_ * G::ENDO_K < (1ull << 31);
+        if constexpr (G::GLV) try_glv = bs.precomp_c == 0 && !no_glv && n_ >= 1 && n_ <= glv_max && (uint64_t)n_ * G::ENDO_K < (1ull << 31);
         // BN254 G1 (round 6: two-dimensional split, k_glv_split_lattice): its host Horner is cheap (254 doublings at 0.3 us) against the split's extra device work (2 n
         // sort records, one more kernel), so between 2^13 and 2^17 points the plain windows are 3-4 % faster as a single call and 8 % pipelined -- BASELINE config 1's size
         // among them -- while 2^10 (-15 %), 2^17 (-14 %) and 2^19 (-9 %) gain (profiles/r06_small_knobs2.log, r06_bn_glv_ab.log).  BLS12-381 never loses (same logs).
@@ -141,7 +155,7 @@ struct MsmJob {
         if (!rc && glv && c <= 3) rc = plan_as(ctx, bs, first_, d_scalars, n_, false);
         // the global-atomics sort (forced plain c >= 21 beyond 255 sort groups) does not take half-scalars: plan again without them
         if (!rc && glv && !wide && c > 16) rc = plan_as(ctx, bs, first_, d_scalars, n_, false);
-        phi_slot = glv ? phi_slot_ : -1;
+        phi_slot = phi_slot_;
         phi_owner = glv;
         return rc;
     }
@@ -224,6 +238,38 @@ struct MsmJob {
         big_span = nchunks <= (1u << 17) ? (uint32_t)ZL_BIG_SPAN_SMALL : (uint32_t)ZL_BIG_SPAN;
         max_big = (uint32_t)(maxE / ((uint64_t)ZL_CHUNK * big_span)) + 1;
         max_giant = (uint32_t)(maxE / ((uint64_t)ZL_CHUNK * ZL_GIANT_SPAN)) + 1;
+        // the sort temporaries (every part rounded up to 256 bytes)
+        lay = MsmSortLayout{};
+        auto up256 = [](size_t b) { return (b + 255) / 256 * 256; };
+        const uint32_t max_slices = (uint32_t)((n + 4095) / 4096);
+        if (wide) {
+            lay.nslices = std::min<uint32_t>(64, max_slices);
+            lay.P = Gn * W * lay.nslices;  // partition counters, order (group, window, slice)
+            lay.pscan_blocks = (lay.P + SCAN_BLOCK * SCAN_ITEMS - 1) / (SCAN_BLOCK * SCAN_ITEMS);
+            const size_t b_lo = up256((size_t)n * W * 2), b_hi = up256((size_t)n * W), b_idx = up256((size_t)n * W * 4);
+            lay.hi8 = b_lo;
+            lay.part_lo = lay.hi8 + b_hi;
+            lay.part_idx = lay.part_lo + b_lo;
+            lay.pcounts = lay.part_idx + b_idx;
+            lay.a_bytes = lay.pcounts + up256((size_t)(2 * lay.P + lay.pscan_blocks + 8) * 4) + 256;
+            // level 2: 128 sub-groups (256 buckets each) per group, counted in fsl slices
+            lay.fsl = 16;
+            while (lay.fsl * Gn < 2048 && lay.fsl < 128) lay.fsl *= 2;
+            lay.P2 = Gn * 128 * lay.fsl;
+            lay.p2scan_blocks = (lay.P2 + SCAN_BLOCK * SCAN_ITEMS - 1) / (SCAN_BLOCK * SCAN_ITEMS);
+            lay.idx2 = b_lo;
+            lay.counts2 = lay.idx2 + b_idx;
+            lay.b_bytes = lay.counts2 + up256((size_t)(2 * (size_t)lay.P2 + lay.p2scan_blocks + 8) * 4) + 256;
+        } else if (c <= 16) {
+            lay.nslices = std::max<uint32_t>(1, std::min<uint32_t>((256 + W - 1) / W, max_slices));  // ~256+ blocks of 1024 lanes, one per CU (<= 128 KiB LDS each)
+            lay.slice_counts = up256((size_t)n * W * 2);
+            lay.a_bytes = (size_t)n * W * 2 + (size_t)lay.nslices * NB * 4 + 256;  // (the trailing 256 covers the rounding of the digits)
+        }  // plain c >= 21 (more than 255 sort groups): the global-atomics sort needs no temporaries
+        if (lay.nslices) lay.per_slice = (uint32_t)((n + lay.nslices - 1) / lay.nslices);
+        if (glv) {
+            lay.vs = up256(lay.a_bytes);
+            lay.a_bytes = lay.vs + up256((size_t)n * 32);
+        }
         d_bases = pre ? reinterpret_cast<const Affine<F>*>(bs.d_table) : reinterpret_cast<const Affine<F>*>(bs.d_pts) + first;
         d_inf = bs.d_inf ? reinterpret_cast<const uint8_t*>(bs.d_inf) + first : nullptr;
         sc = reinterpret_cast<const uint32_t*>(d_scalars);
@@ -231,26 +277,26 @@ struct MsmJob {
         set_host_buffer(hw_own.data());
         return ZL_OK;
     }
-    // buffer set 0, 1 or 2 (slots 0..3 + 4 / 10..13 + 19 / 14..17 + 23); the sort temporaries (slots 5, 6) are shared: the sorts of consecutive
-    // jobs run in order on the sort stream
-    static int phi_slot_of(int set) { return set == 3 ? 35 : 20 + set; }
+    // buffer set 0..3 (ZL_MSM_SET, zl_ctx.h).  own_sort: the job's sort runs beside the other sets' sorts, in the set's own temporaries; otherwise in
+    // ZL_SLOT_SORT_A / _B, which the jobs of a call share: their sorts run in order on one stream.  Callers bind every job before anything is in
+    // flight (a growing zl_scratch_get frees the old block), and again once every slot has reached its largest user.
     int alloc(zl_ctx* ctx, int set, bool own_sort = false) {
         void* p;
         int rc;
-        const int o = set == 0 ? 0 : (set == 1 ? 10 : (set == 2 ? 14 : 28));
-        if (own_sort) {  // the job's sort runs beside the other sets' sorts: its temporaries are its own, sized here (nothing is in flight yet)
-            static const int A[4] = {5, 24, 26, 33}, B[4] = {6, 25, 27, 34};
-            slotA = A[set];
-            slotB = B[set];
-            size_t a5, a6;
-            sort_tmp_sizes(a5, a6);
-            if (a5 && (rc = zl_scratch_get(ctx, slotA, a5, &p))) return rc;
-            if (a6 && (rc = zl_scratch_get(ctx, slotB, a6, &p))) return rc;
+        const zl_msm_set_slots& slots = ZL_MSM_SET[set];
+        d_sort_a = d_sort_b = nullptr;
+        if (lay.a_bytes) {
+            if ((rc = zl_scratch_get(ctx, own_sort ? slots.sort_a : ZL_SLOT_SORT_A, lay.a_bytes, &p))) return rc;
+            d_sort_a = (unsigned char*)p;
+        }
+        if (lay.b_bytes) {
+            if ((rc = zl_scratch_get(ctx, own_sort ? slots.sort_b : ZL_SLOT_SORT_B, lay.b_bytes, &p))) return rc;
+            d_sort_b = (unsigned char*)p;
         }
         // counters (NB+1) | offsets (NB+2: [NB] = total entries, [NB+1] = non-canonical-scalar flag) | cursor (NB+1) | block sums | big list | counts | giant list | scalar-1 list
         const size_t max_bigsg = (size_t)(maxE / 1024) + 2;  // oversized sub-groups hold > cap >= 1024 entries each
         size_t small_words = (size_t)3 * (NB + 1) + 1 + scan_blocks + 1 + max_big + max_giant + 16 + n + 2 * max_bigsg;
-        if ((rc = zl_scratch_get(ctx, o + 0, small_words * 4, &p))) return rc;
+        if ((rc = zl_scratch_get(ctx, slots.data[0], small_words * 4, &p))) return rc;
         d_counts = (uint32_t*)p;
         d_offsets = d_counts + (NB + 1);
         d_cursor = d_offsets + (NB + 2);
@@ -264,17 +310,17 @@ struct MsmJob {
         d_ones_list = d_giant_list + max_giant;
         d_bigsg_items = d_ones_list + n;
         d_bigsg_head = reinterpret_cast<unsigned long long*>((reinterpret_cast<uintptr_t>(d_big_count + 4) + 7) & ~(uintptr_t)7);  // inside words 4..7
-        if ((rc = zl_scratch_get(ctx, o + 1, maxE * 4, &p))) return rc;
+        if ((rc = zl_scratch_get(ctx, slots.data[1], maxE * 4, &p))) return rc;
         d_entries = (uint32_t*)p;
-        if ((rc = zl_scratch_get(ctx, o + 2, (size_t)NB * sizeof(X), &p))) return rc;
+        if ((rc = zl_scratch_get(ctx, slots.data[2], (size_t)NB * sizeof(X), &p))) return rc;
         d_buckets = (X*)p;
-        if ((rc = zl_scratch_get(ctx, o + 3, (size_t)2 * nchunks * sizeof(X), &p))) return rc;
+        if ((rc = zl_scratch_get(ctx, slots.data[3], (size_t)2 * nchunks * sizeof(X), &p))) return rc;
         d_partials = (X*)p;
         // ping-pong node buffers of the reduction tree: leaves = 2 channels x blocks, level 1 = 3 channels x blocks / 2 (the largest)
         const size_t leaf_elems = (size_t)2 * SETS * red_blocks, lvl1_elems = (size_t)3 * SETS * (red_blocks / 2 + 1);
         const size_t root_elems = (size_t)SETS * roots_per_set;
-        const int tail_slot = set == 0 ? 4 : (set == 1 ? 19 : (set == 2 ? 23 : 32));  // per set: the tails of consecutive jobs may overlap (small jobs)
-        if ((rc = zl_scratch_get(ctx, tail_slot, (leaf_elems + lvl1_elems + root_elems + 2 + ZL_ONES_BLOCKS + (size_t)max_giant * ZL_GIANT_PARTS) * sizeof(X), &p))) return rc;
+        // (per set: the tails of consecutive jobs may overlap)
+        if ((rc = zl_scratch_get(ctx, slots.tail, (leaf_elems + lvl1_elems + root_elems + 2 + ZL_ONES_BLOCKS + (size_t)max_giant * ZL_GIANT_PARTS) * sizeof(X), &p))) return rc;
         d_segs = (X*)p;                    // tree nodes, even levels (level 0 = leaves)
         d_stage1 = d_segs + leaf_elems;    // tree nodes, odd levels
         d_sets = d_stage1 + lvl1_elems;    // the root channels of every set, then the sum of the scalar-1 bases
@@ -314,55 +360,18 @@ struct MsmJob {
         }
         return ZL_OK;
     }
-    // sizes of the sort temporaries (slots 5 and 6), as sort() requests them: a heterogeneous pipeline grows the slots to the
-    // largest job before anything is in flight (a growing zl_scratch_get frees the old block)
-    size_t vs_bytes() const { return glv ? (((size_t)n * 32 + 255) / 256) * 256 : 0; }  // the half-scalars live behind the slot-5 temporaries
-    void sort_tmp_sizes(size_t& s5, size_t& s6) const {
-        sort_tmp_sizes_(s5, s6);
-        if (glv) s5 = ((s5 + 255) / 256) * 256 + vs_bytes();
-    }
-    void sort_tmp_sizes_(size_t& s5, size_t& s6) const {
-        s5 = s6 = 0;
-        if (wide) {
-            uint32_t nslices = 64;
-            const uint32_t max_slices = (uint32_t)((n + 4095) / 4096);
-            if (nslices > max_slices) nslices = max_slices;
-            const uint32_t P = Gn * W * nslices;
-            const uint32_t pscan_blocks = (P + SCAN_BLOCK * SCAN_ITEMS - 1) / (SCAN_BLOCK * SCAN_ITEMS);
-            const size_t b_lo = (((size_t)n * W * 2 + 255) / 256) * 256, b_hi = (((size_t)n * W + 255) / 256) * 256;
-            const size_t b_pidx = (((size_t)n * W * 4 + 255) / 256) * 256;
-            const size_t b_pc = (((size_t)(2 * P + pscan_blocks + 8) * 4 + 255) / 256) * 256;
-            s5 = b_lo + b_hi + b_lo + b_pidx + b_pc + 256;
-            uint32_t fsl = 16;
-            while (fsl * Gn < 2048 && fsl < 128) fsl *= 2;
-            const uint32_t P2 = Gn * 128 * fsl;
-            const uint32_t p2scan_blocks = (P2 + SCAN_BLOCK * SCAN_ITEMS - 1) / (SCAN_BLOCK * SCAN_ITEMS);
-            s6 = b_lo + b_pidx + (((size_t)(2 * (size_t)P2 + p2scan_blocks + 8) * 4 + 255) / 256) * 256 + 256;
-        } else if (c <= 16) {
-            uint32_t nslices = (256 + W - 1) / W;
-            const uint32_t max_slices = (uint32_t)((n + 4095) / 4096);
-            if (nslices > max_slices) nslices = max_slices;
-            if (nslices < 1) nslices = 1;
-            s5 = (size_t)n * W * 2 + (size_t)nslices * NB * 4 + 256;
-        }  // plain c >= 21 (more than 255 sort groups): the global-atomics sort needs no temporaries
-    }
     int sort(zl_ctx* ctx, hipStream_t st) {
-        int rc;
         // the bucket counters are written in full by the LDS path (k_msm_slice_prefix) and by the wide path (k_msm_fine_hist); only the
         // global-atomics sort counts into them
         if (!wide && c > 16) ZL_HIP(ctx, hipMemsetAsync(d_counts, 0, (size_t)(NB + 1) * 4, st));
         hipLaunchKernelGGL(k_msm_zero_words, dim3(1), dim3(64), 0, st, d_big_count, 8u);  // big, ones, giant counts, bad-scalar flag; [4..5]: oversized sub-group queue head (u64); [6]: k_msm_ones' ticket
         const uint32_t nblk = (uint32_t)((n + 255) / 256);
-        // GLV front end: half-scalars behind the slot-5 temporaries, phi image of the bases (once per call for a batch over one key)
+        // GLV front end: half-scalars behind the sort temporaries, phi image of the bases (once per call for a batch over one key)
         const uint32_t* sc_eff = sc;
         const uint8_t* inf_eff = d_inf;
         uint32_t* bad_eff = d_bad_scalar;
         if (glv) {
-            size_t s5tot, s6tot;
-            sort_tmp_sizes(s5tot, s6tot);
-            void* p5;
-            if ((rc = zl_scratch_get(ctx, slotA, s5tot, &p5))) return rc;
-            d_vs = reinterpret_cast<uint32_t*>(reinterpret_cast<unsigned char*>(p5) + (s5tot - vs_bytes()));
+            d_vs = reinterpret_cast<uint32_t*>(d_sort_a + lay.vs);
             if constexpr (G::GLV && G::ENDO_K == 2) {
                 if constexpr (G::GLVP::LATTICE)
                     hipLaunchKernelGGL((k_glv_split_lattice<typename G::GLVP>), dim3((uint32_t)((n_real + 255) / 256)), dim3(256), 0, st, sc, (uint32_t)n_real, d_inf, d_vs, (int)G::SC_BITS, d_bad_scalar);
@@ -383,34 +392,21 @@ struct MsmJob {
         // per call, not once per process: the attribute is per device and a process may own several contexts
         (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&k_msm_hist_lds), hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024);
         (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&k_msm_scatter_range), hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024);
-        if (wide) rc = sort_wide(ctx, st, sc_eff, inf_eff, bad_eff, nblk, glv_i);
-        else if (c <= 16) rc = sort_lds(ctx, st, sc_eff, inf_eff, bad_eff, nblk, glv_i);
-        else rc = sort_atomics(ctx, st, nblk);
-        if (rc) return rc;
+        if (wide) sort_wide(st, sc_eff, inf_eff, bad_eff, nblk, glv_i);
+        else if (c <= 16) sort_lds(st, sc_eff, inf_eff, bad_eff, nblk, glv_i);
+        else sort_atomics(st, nblk);
         ZL_HIP(ctx, hipGetLastError());
         return ZL_OK;
     }
     // ---- three-level counting sort over (window, bucket) ids: the merged set of a table, or W sets of plain wide windows (c = 17 .. 20; GLS quarter-scalars at c = 16)
-    int sort_wide(zl_ctx* ctx, hipStream_t st, const uint32_t* sc_eff, const uint8_t* inf_eff, uint32_t* bad_eff, uint32_t nblk, int glv_i) {
+    void sort_wide(hipStream_t st, const uint32_t* sc_eff, const uint8_t* inf_eff, uint32_t* bad_eff, uint32_t nblk, int glv_i) {
         const zl_bases& bs = *bsp;
-        int rc;
-        uint32_t nslices = 64;
-        const uint32_t max_slices = (uint32_t)((n + 4095) / 4096);
-        if (nslices > max_slices) nslices = max_slices;
-        const uint32_t per_slice = (uint32_t)((n + nslices - 1) / nslices);
-        const uint32_t P = Gn * W * nslices;  // partition counters, order (group, window, slice)
-        const uint32_t pscan_blocks = (P + SCAN_BLOCK * SCAN_ITEMS - 1) / (SCAN_BLOCK * SCAN_ITEMS);
-        const size_t b_lo = (((size_t)n * W * 2 + 255) / 256) * 256, b_hi = (((size_t)n * W + 255) / 256) * 256;
-        const size_t b_plo = b_lo, b_pidx = (((size_t)n * W * 4 + 255) / 256) * 256;
-        const size_t b_pc = (((size_t)(2 * P + pscan_blocks + 8) * 4 + 255) / 256) * 256;
-        void* pd;
-        if ((rc = zl_scratch_get(ctx, slotA, b_lo + b_hi + b_plo + b_pidx + b_pc + 256, &pd))) return rc;
-        unsigned char* q = (unsigned char*)pd;
-        uint16_t* d_lo16 = (uint16_t*)q; q += b_lo;
-        uint8_t* d_hi8 = (uint8_t*)q; q += b_hi;
-        uint16_t* d_part_lo = (uint16_t*)q; q += b_plo;
-        uint32_t* d_part_idx = (uint32_t*)q; q += b_pidx;
-        uint32_t* d_pcounts = (uint32_t*)q;
+        const uint32_t nslices = lay.nslices, per_slice = lay.per_slice, P = lay.P, pscan_blocks = lay.pscan_blocks;
+        uint16_t* d_lo16 = (uint16_t*)d_sort_a;
+        uint8_t* d_hi8 = (uint8_t*)(d_sort_a + lay.hi8);
+        uint16_t* d_part_lo = (uint16_t*)(d_sort_a + lay.part_lo);
+        uint32_t* d_part_idx = (uint32_t*)(d_sort_a + lay.part_idx);
+        uint32_t* d_pcounts = (uint32_t*)(d_sort_a + lay.pcounts);
         uint32_t* d_poff = d_pcounts + P;            // P + 1 entries (total at [P])
         uint32_t* d_pblock = d_poff + P + 1;
         hipLaunchKernelGGL(k_msm_recode_wide, dim3(nblk), dim3(256), 0, st, sc_eff, (uint32_t)n, c, W, pre ? 0u : (H >> 15), spread_t, glv_i, d_lo16, d_hi8, d_ones_list, d_ones_count, inf_eff, sc_bits, bad_eff);
@@ -423,17 +419,10 @@ struct MsmJob {
         const uint32_t gstride = (uint32_t)W * nslices;  // counters per group
         // level 2: 128 sub-groups (256 buckets each) per group; level 3: LDS-staged sort per sub-group
         const uint32_t SG = Gn * 128;
-        uint32_t fsl = 16;
-        while (fsl * Gn < 2048 && fsl < 128) fsl *= 2;
-        const uint32_t P2 = SG * fsl;
-        const uint32_t p2scan_blocks = (P2 + SCAN_BLOCK * SCAN_ITEMS - 1) / (SCAN_BLOCK * SCAN_ITEMS);
-        void* pd2;
-        const size_t b2_lo = b_plo, b2_idx = b_pidx, b2_c = (((size_t)(2 * (size_t)P2 + p2scan_blocks + 8) * 4 + 255) / 256) * 256;
-        if ((rc = zl_scratch_get(ctx, slotB, b2_lo + b2_idx + b2_c + 256, &pd2))) return rc;  // slot 6 is otherwise the NTT's scratch vector
-        unsigned char* q2 = (unsigned char*)pd2;
-        uint16_t* d_lo2 = (uint16_t*)q2; q2 += b2_lo;
-        uint32_t* d_idx2 = (uint32_t*)q2; q2 += b2_idx;
-        uint32_t* d_c2 = (uint32_t*)q2;
+        const uint32_t fsl = lay.fsl, P2 = lay.P2, p2scan_blocks = lay.p2scan_blocks;
+        uint16_t* d_lo2 = (uint16_t*)d_sort_b;
+        uint32_t* d_idx2 = (uint32_t*)(d_sort_b + lay.idx2);
+        uint32_t* d_c2 = (uint32_t*)(d_sort_b + lay.counts2);
         uint32_t* d_off2 = d_c2 + P2;  // P2 + 1
         uint32_t* d_blk2 = d_off2 + P2 + 1;
         hipLaunchKernelGGL(k_msm_sub_hist, dim3(fsl, Gn), dim3(256), 0, st, d_part_lo, d_poff, Gn, gstride, d_poff + P, fsl, d_c2);
@@ -456,21 +445,12 @@ struct MsmJob {
         (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&k_msm_fine_sort_big), hipFuncAttributeMaxDynamicSharedMemorySize, ZL_BT * 4);
         hipLaunchKernelGGL(k_msm_fine_sort_big, dim3(512), dim3(1024), (size_t)ZL_BT * 4, st, d_lo2, d_idx2, d_off2, SG, fsl, d_off2 + P2, d_bigsg_head,
                            d_bigsg_items, d_cursor, d_entries);
-        return ZL_OK;
     }
     // ---- LDS counting sort (c <= 16): recode once (u16 digits), per-(slice, window) LDS histograms, slice prefix, scan, range-owned scatter
-    int sort_lds(zl_ctx* ctx, hipStream_t st, const uint32_t* sc_eff, const uint8_t* inf_eff, uint32_t* bad_eff, uint32_t nblk, int glv_i) {
-        int rc;
-        // LDS counting sort: recode once (u16 digits), per-(slice, window) LDS histograms, slice prefix, scan, range-owned scatter
-        uint32_t nslices = (256 + W - 1) / W;  // ~256+ blocks of 1024 lanes, one per CU (<= 128 KiB LDS each)
-        const uint32_t max_slices = (uint32_t)((n + 4095) / 4096);
-        if (nslices > max_slices) nslices = max_slices;
-        if (nslices < 1) nslices = 1;
-        const uint32_t per_slice = (uint32_t)((n + nslices - 1) / nslices);
-        void* pd;
-        if ((rc = zl_scratch_get(ctx, slotA, (size_t)n * W * 2 + (size_t)nslices * NB * 4 + 256, &pd))) return rc;
-        uint16_t* d_digits = (uint16_t*)pd;
-        uint32_t* d_slice_counts = (uint32_t*)((unsigned char*)pd + (((size_t)n * W * 2 + 255) / 256) * 256);
+    void sort_lds(hipStream_t st, const uint32_t* sc_eff, const uint8_t* inf_eff, uint32_t* bad_eff, uint32_t nblk, int glv_i) {
+        const uint32_t nslices = lay.nslices, per_slice = lay.per_slice;
+        uint16_t* d_digits = (uint16_t*)d_sort_a;
+        uint32_t* d_slice_counts = (uint32_t*)(d_sort_a + lay.slice_counts);
         hipLaunchKernelGGL(k_msm_recode, dim3(nblk), dim3(256), 0, st, sc_eff, (uint32_t)n, c, W, spread_t, glv_i, d_digits, d_ones_list, d_ones_count, inf_eff, sc_bits, bad_eff);
         hipLaunchKernelGGL(k_msm_hist_lds, dim3(nslices, W), dim3(1024), (size_t)H * 4, st, d_digits, (uint32_t)n, H, per_slice, NB, d_slice_counts);
         if (NB <= 14336 && nslices <= 64) {  // (14 336 buckets: 59.6 KB of LDS for the totals beside the 4 KB of the scan)
@@ -491,18 +471,15 @@ struct MsmJob {
         const uint32_t parts = 1;
         hipLaunchKernelGGL(k_msm_scatter_range, dim3(8 * ((W + 7) / 8), ranges, parts), dim3(1024), (size_t)RB * 4, st, d_digits, (uint32_t)n, H, RB, d_offsets, d_entries,
                            (const uint32_t*)d_slice_counts, NB, nslices, per_slice, parts, (uint32_t)W);
-        return ZL_OK;
     }
     // ---- wide windows without a table beyond 255 sort groups (forced plain c >= 21): histogram / scatter with global atomics
-    int sort_atomics(zl_ctx* ctx, hipStream_t st, uint32_t nblk) {
+    void sort_atomics(hipStream_t st, uint32_t nblk) {
         // wide windows without a table: histogram / scatter with global atomics
         hipLaunchKernelGGL((k_msm_digits<0>), dim3(nblk), dim3(256), 0, st, sc, (uint32_t)n, c, W, d_counts, (uint32_t*)nullptr, d_ones_list, d_ones_count, d_inf, (int)G::SC_BITS, d_bad_scalar);
         hipLaunchKernelGGL(k_scan_block_sums, dim3(scan_blocks), dim3(SCAN_BLOCK), 0, st, d_counts, NB, d_block_sums);
         hipLaunchKernelGGL(k_scan_top, dim3(1), dim3(1024), 0, st, d_block_sums, scan_blocks, d_offsets + NB, (const uint32_t*)d_bad_scalar);
         hipLaunchKernelGGL(k_scan_apply, dim3(scan_blocks), dim3(SCAN_BLOCK), 0, st, d_counts, NB, d_block_sums, d_offsets, d_cursor);
         hipLaunchKernelGGL((k_msm_digits<1>), dim3(nblk), dim3(256), 0, st, sc, (uint32_t)n, c, W, d_cursor, d_entries, d_ones_list, d_ones_count, d_inf, (int)G::SC_BITS, d_bad_scalar);
-        (void)ctx;
-        return ZL_OK;
     }
     static constexpr bool pair_ok() { return G::COORDS == 2 && !std::is_void<typename PairBase<F>::type>::value; }  // an Fq2 group on 28-bit limbs: the lane-pair kernels exist
     int accumulate(zl_ctx* ctx, hipStream_t st) {

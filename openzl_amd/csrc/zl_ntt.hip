@@ -588,7 +588,7 @@ static int ntt_run_t(zl_ctx* ctx, int curve, void* d_data, unsigned n, unsigned 
     F* scratch = nullptr;
     if (pl.P > 1) {
         void* p;
-        if ((rc = zl_scratch_get(ctx, 6, (size_t)count * N * ScratchBytes<P28>::value, &p))) return rc;  // the limbs as they are between passes
+        if ((rc = zl_scratch_get(ctx, ZL_SLOT_NTT_VEC, (size_t)count * N * ScratchBytes<P28>::value, &p))) return rc;  // the limbs as they are between passes
         scratch = reinterpret_cast<F*>(p);
     }
     const unsigned L = tw->lo_bits;

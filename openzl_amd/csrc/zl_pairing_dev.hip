@@ -304,11 +304,11 @@ int run(zl_ctx* ctx, const uint64_t* ps, const uint64_t* qs, const uint32_t* sc,
     const size_t pb = n * NW * 8, qb = 2 * pb, sb = sc ? n * 16 : 0;  // bytes of ps (n x 2 Fq of NW u32), qs (n x 4 Fq), scalars
     const size_t in_bytes = (pb + qb + sb + 255) & ~(size_t)255;
     void *d_in = nullptr, *d_lines = nullptr, *d_acc = nullptr, *d_prep = nullptr;
-    int rc = zl_scratch_get(ctx, 30, in_bytes, &d_in);
-    if (!rc) rc = zl_scratch_get(ctx, 33, npad * 7 * sizeof(F), &d_prep);
-    if (!rc) rc = zl_scratch_get(ctx, 31, (size_t)NLINES * npad * 6 * sizeof(F), &d_lines);
+    int rc = zl_scratch_get(ctx, ZL_SLOT_PAIR_IN, in_bytes, &d_in);
+    if (!rc) rc = zl_scratch_get(ctx, ZL_SLOT_PAIR_PREP, npad * 7 * sizeof(F), &d_prep);
+    if (!rc) rc = zl_scratch_get(ctx, ZL_SLOT_PAIR_LINES, (size_t)NLINES * npad * 6 * sizeof(F), &d_lines);
     const size_t nred = (ngroups + 15) / 16;
-    if (!rc) rc = zl_scratch_get(ctx, 32, (ngroups + nred + 1) * 12 * sizeof(F), &d_acc);
+    if (!rc) rc = zl_scratch_get(ctx, ZL_SLOT_PAIR_ACC, (ngroups + nred + 1) * 12 * sizeof(F), &d_acc);
     if (rc) return rc;
     unsigned char* din = static_cast<unsigned char*>(d_in);
     ZL_HIP(ctx, hipMemcpyAsync(din, ps, pb, hipMemcpyHostToDevice, ctx->stream));

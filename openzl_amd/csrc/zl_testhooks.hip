@@ -141,7 +141,7 @@ static int poseidon_dev_t(zl_ctx* ctx, uint64_t* state) {
     }
     void* d = nullptr;
     const size_t kb = keys.size() * 4, sb = 3 * FrP::N * 4;
-    int rc = zl_scratch_get(ctx, 9, kb + sb + 64, &d);
+    int rc = zl_scratch_get(ctx, ZL_SLOT_TESTHOOK, kb + sb + 64, &d);
     if (rc) return rc;
     uint32_t* d_keys = (uint32_t*)d;
     uint32_t* d_state = d_keys + keys.size();
@@ -326,7 +326,7 @@ static __global__ void __launch_bounds__(64) k_test_point(int op, const uint32_t
 template <class Launch>
 static int run_dev(zl_ctx* ctx, const uint32_t* in, size_t in_words, uint32_t* out, size_t out_words, Launch launch) {
     void* d = nullptr;
-    int rc = zl_scratch_get(ctx, 9, (in_words + out_words) * 4 + 64, &d);
+    int rc = zl_scratch_get(ctx, ZL_SLOT_TESTHOOK, (in_words + out_words) * 4 + 64, &d);
     if (rc) return rc;
     uint32_t* d_in = (uint32_t*)d;
     uint32_t* d_out = d_in + in_words;
@@ -347,7 +347,7 @@ static int run_dev(zl_ctx* ctx, const uint32_t* in, size_t in_words, uint32_t* o
 template <class Launch>
 static int run_dev_flag(zl_ctx* ctx, const uint32_t* in, size_t in_words, uint32_t* out, size_t out_words, Launch launch) {
     void* d = nullptr;
-    int rc = zl_scratch_get(ctx, 9, (in_words + out_words) * 4 + 64, &d);
+    int rc = zl_scratch_get(ctx, ZL_SLOT_TESTHOOK, (in_words + out_words) * 4 + 64, &d);
     if (rc) return rc;
     uint32_t* d_in = (uint32_t*)d;
     uint32_t* d_out = d_in + in_words;
@@ -674,7 +674,7 @@ int zl_test_fq_mul_rate(zl_ctx* ctx, int waves_per_simd, int iters, double* g_pr
     ZL_HIP(ctx, hipSetDevice(ctx->device));
     const uint32_t blocks = (uint32_t)ctx->cu_count * 4u * (uint32_t)waves_per_simd;
     void* d = nullptr;
-    int rc = zl_scratch_get(ctx, 9, (size_t)blocks * 64 * 4, &d);
+    int rc = zl_scratch_get(ctx, ZL_SLOT_TESTHOOK, (size_t)blocks * 64 * 4, &d);
     if (rc) return rc;
     hipStream_t st = ctx->stream;
     hipEvent_t e0, e1;
@@ -725,7 +725,7 @@ int zl_test_fq_mul_clock(zl_ctx* ctx, int waves_per_simd, int iters, double* out
     ZL_HIP(ctx, hipSetDevice(ctx->device));
     const uint32_t blocks = (uint32_t)ctx->cu_count * 4u * (uint32_t)waves_per_simd;
     void* d = nullptr;
-    int rc = zl_scratch_get(ctx, 9, (size_t)blocks * 64 * 4 + (size_t)blocks * 32, &d);
+    int rc = zl_scratch_get(ctx, ZL_SLOT_TESTHOOK, (size_t)blocks * 64 * 4 + (size_t)blocks * 32, &d);
     if (rc) return rc;
     unsigned long long* d_clk = (unsigned long long*)((char*)d + (size_t)blocks * 64 * 4);
     hipStream_t st = ctx->stream;
