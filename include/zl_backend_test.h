@@ -128,6 +128,17 @@ int zl_test_verify_batch_host(zl_curve_t curve, const uint64_t* alpha_g1, const 
 int zl_test_ntt_plan(unsigned log_n, unsigned* P, unsigned sizes[4]);
 int zl_test_ntt_fit_beside(zl_ctx* ctx, int on);
 
+/* The scalar split in front of a group's plain MSM (openzl_amd/csrc/zl_msm_endo.h), launched alone: GLV halves on G1, GLS quarters on G2.
+ * scalars: n x 4 u64 words (n < 2^24).  out_records: *endo_k x n records of 8 u32 words -- record j n + i = part j of scalar i: magnitude in the low words,
+ * sign in bit 31 of word 7 -- followed by ONE more word, the kernel's `bad` flags (bit 0: a scalar with bits at or above the group's scalar width; bit 1: a part
+ * at or above 2^*part_bits, which cannot happen); the caller provides 4 n x 8 + 1 words.  *endo_k = parts per scalar (2 / 4), *part_bits = their width (what
+ * the MSM plans its windows over).  ZL_EINVAL for a null ctx, n = 0, or a curve / group without a split.
+ * zl_test_endo_split_inf additionally takes the per-base infinity flags of the MSM (n bytes, 1 = the base is the point at infinity: its scalar gives zero
+ * records; NULL = none). */
+int zl_test_endo_split(zl_ctx* ctx, zl_curve_t curve, zl_group_t group, const uint64_t* scalars, size_t n, uint32_t* out_records, int* endo_k, int* part_bits);
+int zl_test_endo_split_inf(zl_ctx* ctx, zl_curve_t curve, zl_group_t group, const uint64_t* scalars, const uint8_t* inf, size_t n, uint32_t* out_records, int* endo_k,
+                           int* part_bits);
+
 #ifdef __cplusplus
 }
 #endif

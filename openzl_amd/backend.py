@@ -185,6 +185,7 @@ def load_library(path: Optional[str] = None):
     L.zl_test_clock_probe_read.argtypes = [vp, C.POINTER(C.c_double)]
     L.zl_test_ntt_plan.argtypes = [C.c_uint, C.POINTER(C.c_uint), C.POINTER(C.c_uint)]
     L.zl_test_ntt_fit_beside.argtypes = [vp, C.c_int]
+    # (zl_test_endo_split / _inf: hook_endo_split declares them where it calls them)
     if path is None:
         _lib = L
     return L
@@ -587,7 +588,8 @@ class MultiBackend:
 # ---- test-only hooks (include/zl_backend_test.h): device Poseidon KAT, raw-limb field / point access ---------------------------------
 TEST_ABI_SYMBOLS = ["zl_test_poseidon_permute_dev", "zl_test_fp28_op", "zl_test_fp28_bn_op", "zl_test_pairing_product", "zl_test_point_op", "zl_test_circuit_tweak", "zl_test_fq_mul_rate", "zl_test_fr28_op", "zl_test_fr29_op",
                     "zl_test_poseidon_permute_dev28r", "zl_test_fq_mul_clock", "zl_test_acc_clock", "zl_test_acc_clock_read", "zl_test_clock_probe_launch", "zl_test_clock_probe_read",
-                    "zl_test_miller_dev", "zl_test_final_exp", "zl_test_verify_batch_host", "zl_test_ntt_plan", "zl_test_ntt_fit_beside", "zl_test_fp2pair_op", "zl_test_point_form_op"]
+                    "zl_test_miller_dev", "zl_test_final_exp", "zl_test_verify_batch_host", "zl_test_ntt_plan", "zl_test_ntt_fit_beside", "zl_test_fp2pair_op", "zl_test_point_form_op",
+                    "zl_test_endo_split", "zl_test_endo_split_inf"]
 
 
 def _p32(a: np.ndarray):
@@ -618,6 +620,28 @@ def hook_ntt_fit_beside(be: "Backend", on: bool) -> bool:
     if old < 0:
         raise BackendError(old, "zl_test_ntt_fit_beside")
     return bool(old)
+
+
+def hook_endo_split(be: "Backend", curve: int, group: int, scalars: np.ndarray, inf: Optional[np.ndarray] = None):
+    """the scalar split in front of the group's plain MSM, alone (zl_test_endo_split / _inf): scalars (n, 4) uint64, inf (n,) uint8 flags of bases at infinity or
+    None -> (records (endo_k, n, 8) uint32: magnitude in the low words, sign in bit 31 of word 7; the kernel's bad flags; endo_k; bits per part)"""
+    s = np.ascontiguousarray(scalars, dtype=np.uint64)
+    n = s.shape[0]
+    assert s.shape == (n, 4)
+    out = np.zeros(4 * n * 8 + 1, dtype=np.uint32)
+    k, bits = C.c_int(0), C.c_int(0)
+    # declared here, not in load_library: the loader then also takes a build from before the hook (the parent side of tools/ab/bn254_g2_gls_ab.sh)
+    tail = [C.c_size_t, C.POINTER(C.c_uint32), C.POINTER(C.c_int), C.POINTER(C.c_int)]
+    be.L.zl_test_endo_split.argtypes = [C.c_void_p, C.c_int, C.c_int, u64p] + tail
+    be.L.zl_test_endo_split_inf.argtypes = [C.c_void_p, C.c_int, C.c_int, u64p, u8p] + tail
+    if inf is None:
+        rc = be.L.zl_test_endo_split(be._ctx, curve, group, _p64(s), n, _p32(out), C.byref(k), C.byref(bits))
+    else:
+        f = np.ascontiguousarray(inf, dtype=np.uint8)
+        assert f.shape == (n,)
+        rc = be.L.zl_test_endo_split_inf(be._ctx, curve, group, _p64(s), f.ctypes.data_as(u8p), n, _p32(out), C.byref(k), C.byref(bits))
+    be._check(rc, "zl_test_endo_split")
+    return out[: k.value * n * 8].reshape(k.value, n, 8).copy(), int(out[k.value * n * 8]), k.value, bits.value
 
 
 def hook_poseidon_permute_dev(be: "Backend", curve: int, state: np.ndarray) -> np.ndarray:

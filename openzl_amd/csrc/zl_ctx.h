@@ -59,7 +59,7 @@ struct BnG1 {
     ZL_HD static F gen_y() { uint32_t w[FqP::N]; for (int i = 0; i < FqP::N; i++) w[i] = C::gy(i); return FieldIO<F>::load_mont32(w); }
     ZL_HD static F coeff_b() { uint32_t w[FqP::N]; for (int i = 0; i < FqP::N; i++) w[i] = C::b(i); return FieldIO<F>::load_mont32(w); }
 };
-template <class C2, class FqP_, class FrP_, class F_, int SCB, int FQ64_, int ID_>
+template <class C2, class FqP_, class FrP_, class F_, class GLS_, int SCB, int FQ64_, int ID_>
 struct G2Cfg {
     static constexpr int ID = ID_;
     using FqP = FqP_;
@@ -68,11 +68,13 @@ struct G2Cfg {
     static constexpr int SC_BITS = SCB;
     static constexpr int FQ64 = FQ64_;
     static constexpr int COORDS = 2;
-    // BLS12-381 G2 (ID 2): the untwist-Frobenius-twist endomorphism psi acts as [z] = [-|z|], r < |z|^4: a scalar is four base-|z| digits of 64 bits
-    // over P, psi(P), psi^2(P), psi^3(P) with alternating signs (GLS).  BN254 G2 keeps plain 254-bit windows.
-    static constexpr bool GLV = ID_ == 2;
-    static constexpr int ENDO_K = ID_ == 2 ? 4 : 1;
-    using GLVP = BLS12_381_GLS;
+    // GLS: the untwist-Frobenius-twist endomorphism psi acts on G2 as [lambda] with lambda^4 - lambda^2 + 1 = 0 (mod r); a scalar becomes four signed
+    // quarter-scalars of GLVP::QUARTER_BITS bits over P, psi(P), psi^2(P), psi^3(P).  BLS12-381 (ID 2): lambda = z = -|z| and r < |z|^4, the quarters are the
+    // base-|z| digits with alternating signs (k_gls_split).  BN254 (ID 3): lambda = 6 x^2, a four-dimensional lattice split with a sign per quarter
+    // (BN254_GLS, k_gls_split_lattice).  GLVP carries the split parameters and the psi constants of the curve.
+    static constexpr bool GLV = true;
+    static constexpr int ENDO_K = 4;
+    using GLVP = GLS_;
     ZL_HD static F psi_x() { return mk(GLVP::psi_x0, GLVP::psi_x1); }
     ZL_HD static F psi_y() { return mk(GLVP::psi_y0, GLVP::psi_y1); }
     ZL_HD static F mk(uint32_t (*f0)(int), uint32_t (*f1)(int)) {  // two components as arkworks' Montgomery words
@@ -85,8 +87,8 @@ struct G2Cfg {
     ZL_HD static F coeff_b() { return mk(C2::b0, C2::b1); }
 };
 // G2 on the lazily reduced 28-bit fields (Fq2 products as dual scans, zl_field28.h): 14 limbs per component for BLS12-381, 10 for BN254
-using BlsG2 = G2Cfg<BLS12_381_G2, BLS12_381_Fq, BLS12_381_Fr, Fp2L<Fp28<BLS12_381_Fq28, BLS12_381_Fq>>, 255, 6, 2>;
-using BnG2 = G2Cfg<BN254_G2, BN254_Fq, BN254_Fr, Fp2L<Fp28<BN254_Fq28, BN254_Fq>>, 254, 4, 3>;  // round 4: like BLS12-381 G2, on 10 limbs
+using BlsG2 = G2Cfg<BLS12_381_G2, BLS12_381_Fq, BLS12_381_Fr, Fp2L<Fp28<BLS12_381_Fq28, BLS12_381_Fq>>, BLS12_381_GLS, 255, 6, 2>;
+using BnG2 = G2Cfg<BN254_G2, BN254_Fq, BN254_Fr, Fp2L<Fp28<BN254_Fq28, BN254_Fq>>, BN254_GLS, 254, 4, 3>;  // round 4: like BLS12-381 G2, on 10 limbs
 
 // ---- context ----------------------------------------------------------------------------------------------
 struct zl_bases {

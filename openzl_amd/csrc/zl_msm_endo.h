@@ -1,9 +1,18 @@
-// zl_msm_endo.h -- endomorphism front ends of the MSM: GLV on BLS12-381 / BN254 G1 (k = k1 + k2 lambda) and GLS on BLS12-381 G2 (four base-|z|
-// digits over P, psi(P), psi^2(P), psi^3(P)): scalar splits and the images of the bases.  Instantiated where they are launched (zl_msm.hip).
+// zl_msm_endo.h -- endomorphism front ends of the MSM: GLV on BLS12-381 / BN254 G1 (k = k1 + k2 lambda) and GLS on G2 (four quarter-scalars over P, psi(P),
+// psi^2(P), psi^3(P): base-|z| digits on BLS12-381, a four-dimensional lattice split on BN254): scalar splits and the images of the bases.  Instantiated where
+// they are launched (zl_msm.hip, zl_testhooks.hip).
 #pragma once
 #include "zl_ctx.h"
 #include "zl_msm_common.h"
 
+// bits of one part of a split scalar (the sc_bits of a job that runs on split scalars): 127-bit halves on G1, the quarter width of the curve's GLS parameters on G2
+template <class G>
+struct MsmJobPartBits {
+    static constexpr int value = [] {
+        if constexpr (G::ENDO_K == 4) return (int)G::GLVP::QUARTER_BITS;
+        else return 127;
+    }();
+};
 // ------------------------------------------------------------------------------------------------ GLV front end
 // BLS12-381 G1 has the endomorphism phi(x, y) = (beta x, y) = [lambda](x, y) with lambda = z^2 - 1 and r = lambda^2 + lambda + 1.  A plain
 // MSM over n points and 255-bit scalars becomes one over 2n points (P_i and phi(P_i)) and signed 127-bit half-scalars:
@@ -333,6 +342,76 @@ __global__ void __launch_bounds__(256) k_gls_split(const uint32_t* __restrict__ 
         o[0] = make_uint4((uint32_t)d[j], (uint32_t)(d[j] >> 32), 0, 0);
         o[1] = make_uint4(0, 0, 0, (d[j] != 0 && (j & 1)) ? 0x80000000u : 0u);
     }
+}
+// ---- GLS for BN254 G2: psi acts as [lambda], lambda = 6 x^2, a root of Phi_12 (lambda^4 - lambda^2 + 1 = 0 mod r); r is no power of a 64-bit number, so the
+// split is the four-dimensional one of Galbraith-Scott: with the reduced basis b0..b3 of {a: sum a_j lambda^j = 0 mod r} and (1, 0, 0, 0) = sum w_i b_i,
+// c_i = round(w_i k) and (k0, k1, k2, k3) = (k, 0, 0, 0) - sum c_i b_i.  The roundings are taken as (k g_i + 2^255) >> 256 with g_i = round(2^256 |w_i|): at most
+// one off, which moves the result by one basis row and keeps sum k_j lambda^j = k (mod r) exactly.  All products are taken on magnitudes, modulo 2^128 (only the
+// low four words of c_i matter); |k_j| <= 0.8412 * 2^64 (tools/gen_bn254_gls.py proves the bound and runs this arithmetic on edge and random scalars).
+// out: 4n records of 8 words -- record j n + i = |k_j| of scalar i in the low words, its sign in bit 31 of word 7 (per quarter, not alternating as in k_gls_split).
+template <class P>
+__global__ void __launch_bounds__(256) k_gls_split_lattice(const uint32_t* __restrict__ scalars, uint32_t n, const uint8_t* __restrict__ inf, uint32_t* __restrict__ out,
+                                                            int sc_bits, uint32_t* __restrict__ bad) {
+    ZL_SIDE_PRIO();
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const uint4* sp = reinterpret_cast<const uint4*>(scalars + (size_t)i * 8);
+    uint4 lo4 = sp[0], hi4 = sp[1];
+    zl_flag_wide_scalar(hi4.w, sc_bits, bad);
+    if (inf && inf[i]) lo4 = hi4 = make_uint4(0, 0, 0, 0);
+    uint32_t k[8] = {lo4.x, lo4.y, lo4.z, lo4.w, hi4.x, hi4.y, hi4.z, hi4.w};
+    zl_reduce_once_mod_r<P>(k);
+    // c_i mod 2^128 = words 8 .. 11 of k g_i + 2^255
+    uint32_t c[4][4];
+#pragma unroll
+    for (int a = 0; a < 4; a++) {
+        uint32_t g[P::NG], pr[12];
+#pragma unroll
+        for (int w = 0; w < P::NG; w++) g[w] = P::g(a, w);
+        zl_mul_words<8, P::NG, 12>(k, g, pr);
+        uint32_t carry = 0;
+#pragma unroll
+        for (int w = 7; w < 12; w++) {
+            const uint64_t x = (uint64_t)pr[w] + (w == 7 ? 0x80000000u : 0u) + carry;
+            pr[w] = (uint32_t)x;
+            carry = (uint32_t)(x >> 32);
+        }
+#pragma unroll
+        for (int w = 0; w < 4; w++) c[a][w] = pr[8 + w];
+    }
+    // k_j = [j == 0] k -+ c_0 |b_0[j]| -+ c_1 |b_1[j]| -+ c_2 |b_2[j]| -+ c_3 |b_3[j]|   (mod 2^128; the true values are below 2^64 in magnitude)
+    uint32_t over = 0;
+#pragma unroll
+    for (int j = 0; j < 4; j++) {
+        uint32_t kj[4], t[4];
+#pragma unroll
+        for (int w = 0; w < 4; w++) kj[w] = j == 0 ? k[w] : 0u;
+#pragma unroll
+        for (int a = 0; a < 4; a++) {
+            uint32_t b[P::NB];
+#pragma unroll
+            for (int w = 0; w < P::NB; w++) b[w] = P::b(a, j, w);
+            zl_mul_words<4, P::NB, 4>(c[a], b, t);
+            zl_addsub_words<4>(kj, t, ((P::SUB >> (4 * a + j)) & 1u) != 0u);
+        }
+        uint32_t neg = kj[3] >> 31;
+        if (neg) {
+            uint32_t m[4] = {0, 0, 0, 0};
+            zl_addsub_words<4>(m, kj, true);
+#pragma unroll
+            for (int w = 0; w < 4; w++) kj[w] = m[w];
+        }
+#pragma unroll
+        for (int w = 0; w < 4; w++) {
+            if (32 * w >= P::QUARTER_BITS) over |= kj[w];
+            else if (32 * (w + 1) > P::QUARTER_BITS) over |= kj[w] >> (P::QUARTER_BITS - 32 * w);
+        }
+        if ((kj[0] | kj[1] | kj[2] | kj[3]) == 0u) neg = 0;
+        uint4* o = reinterpret_cast<uint4*>(out + ((size_t)j * n + i) * 8);
+        o[0] = make_uint4(kj[0], kj[1], kj[2], kj[3]);
+        o[1] = make_uint4(0, 0, 0, neg << 31);
+    }
+    if (bad && over != 0u) atomicOr(bad, 2u);  // a quarter at or above 2^QUARTER_BITS: cannot happen (see above); reported like a non-canonical scalar
 }
 // phib[(j - 1) n + i] = psi^j(P_i), j = 1..3; psi(x, y) = (conj(x) gx, conj(y) gy); infinity (all-zero) stays itself
 template <class G>

@@ -14,6 +14,16 @@
 #include "zl_msm_accumulate.h"
 #include "zl_msm_reduce.h"
 
+// BN254 G2 (MsmJob::plan): an MSM takes the four-dimensional split below 2^END points, except in the hole [2^LO, 2^HI), where it keeps its plain windows.  Constants of the
+// product, chosen from profiles/bn254_g2_gls_ab.log; only the "open" side of that A/B (tools/ab/bn254_g2_gls_ab.sh) is built with others (0 / 0 / 32: every size up to
+// ZL_TUNE_GLV_MAX_LOG splits).
+#ifndef ZL_GLS_HOLE_LO_LOG
+#define ZL_GLS_HOLE_LO_LOG 11
+#define ZL_GLS_HOLE_HI_LOG 17
+#define ZL_GLS_END_LOG 19
+#endif
+static_assert(ZL_GLS_HOLE_LO_LOG >= 0 && ZL_GLS_HOLE_LO_LOG <= ZL_GLS_HOLE_HI_LOG && ZL_GLS_HOLE_HI_LOG <= ZL_GLS_END_LOG && ZL_GLS_END_LOG <= 32, "split below 2^END outside [2^LO, 2^HI)");
+
 // ------------------------------------------------------------------------------------------------ host driver
 // developer tuning knobs (profiling sweeps only; unset in production): ZL_TUNE_CHUNK, ZL_TUNE_SEG, ZL_TUNE_FS, ZL_TUNE_RANGES (zl_tune, zl_ctx.h)
 static int zl_pick_window(size_t n, int sc_bits, bool wide16 = false /* c = 16 also runs the three-level sort (GLV jobs) */) {
@@ -49,7 +59,8 @@ static int zl_pick_window_half(size_t n_points) {
     return lg >= 11 && lg <= 19 ? best[lg - 11] : 0;
 }
 // ... and the 64-bit quarter-scalars of the G2 split (4 n entries per window): the model's 11 at 2^13 / 2^14 where 12 / 13 are 8-10 % faster, 17 at 2^18 where 14 is 5 % faster
-// (profiles/r06_half_table_ab.log, "G2 window sweep": every c in 8 .. 16 at 2^10 .. 2^18 points)
+// (profiles/r06_half_table_ab.log, "G2 window sweep": every c in 8 .. 16 at 2^10 .. 2^18 points).  Measured on BLS12-381; BN254's quarters are 64 bits too
+// (BN254_GLS::QUARTER_BITS) and run the same kernels on 10 limbs instead of 14, so they take the same table: an assumption, neither swept nor measured on BN254.
 static int zl_pick_window_quarter(size_t n_points) {
     if (n_points < 2) return 0;
     int lg = 63 - __builtin_clzll((unsigned long long)n_points);
@@ -102,7 +113,7 @@ struct MsmJob {
     bool glv = false;   // the job runs on 2 n_real half-scalars of 127 bits over the points P_i and phi(P_i) (k_glv_split / k_glv_phi)
     bool phi_cached = false;  // d_phi is the handle's own copy (zl_bases::d_endo)
     bool phi_owner = false;  // this job computes the phi image of its bases in its sort phase (else it borrows d_phi from an earlier job of the call)
-    int sc_bits = 0, endo_k = 1;  // endo_k: half-scalars per scalar (2: GLV on G1, 4: GLS on BLS12-381 G2)
+    int sc_bits = 0, endo_k = 1;  // endo_k: half-scalars per scalar (2: GLV on G1, 4: GLS on G2)
     zl_slot phi_slot = ZL_SLOT_PHI_ONE_KEY;
     MsmSortLayout lay;
     unsigned char *d_sort_a = nullptr, *d_sort_b = nullptr;  // the sort temporaries (ZL_SLOT_SORT_A / _B: shared by the jobs of a pipelined batch; the set's own pair when small jobs run side by side)
@@ -148,7 +159,21 @@ struct MsmJob {
         // sort records, one more kernel), so between 2^13 and 2^17 points the plain windows are 3-4 % faster as a single call and 8 % pipelined -- BASELINE config 1's size
         // among them -- while 2^10 (-15 %), 2^17 (-14 %) and 2^19 (-9 %) gain (profiles/r06_small_knobs2.log, r06_bn_glv_ab.log).  BLS12-381 never loses (same logs).
         if constexpr (G::GLV && G::ENDO_K == 2) {
-            if (G::GLVP::LATTICE && n_ >= ((size_t)1 << 13) && n_ < ((size_t)1 << 17)) try_glv = false;
+            if constexpr (G::GLVP::LATTICE) {
+                if (n_ >= ((size_t)1 << 13) && n_ < ((size_t)1 << 17)) try_glv = false;
+            }
+        }
+        // BN254 G2 (four-dimensional split, k_gls_split_lattice; interleaved A/B against the commit before it at 2^8 .. 2^20 points, three runs a side, run-to-run spread
+        // 0.2-7 %: profiles/bn254_g2_gls_ab.log).  A single call gains at every size up to 2^18 (2^8: 0.55 -> 0.37 ms, 2^10: 0.59 -> 0.34, 2^14: 0.77 -> 0.62, 2^17: 1.79 -> 1.53,
+        // 2^18: 2.34 -> 2.16), ties at 2^19 and loses 6 % at 2^20 (5.62 -> 5.96).  Pipelined (batches of 8, per MSM) it gains at 2^8 - 2^10 (2^10: 0.185 -> 0.153) and at 2^17 / 2^18
+        // (1.32 -> 1.01, 1.90 -> 1.59), but LOSES at 2^11 (0.196 -> 0.222) and 2^13 (0.245 -> 0.322) and ties at 2^12 and 2^14 - 2^16, where the device chain of 4 n records costs what the
+        // shorter host Horner saves once the Horner is hidden behind the next job; 2^19: -2 %, 2^20: -8 %.  The gate is by size alone, so it keeps the sizes that win both ways:
+        // n < 2^11 and 2^17 <= n < 2^19.  Measured: the powers of two; the bounds between 2^10 and 2^11, 2^16 and 2^17, 2^18 and 2^19 are put at the first measured size that
+        // does not win.  (The single-call gains at 2^11 - 2^16, 6-34 %, are left for a gate that knows whether the job is pipelined.)
+        if constexpr (G::GLV && G::ENDO_K == 4) {
+            if constexpr (G::GLVP::LATTICE) {
+                if (((uint64_t)n_ >= (1ull << ZL_GLS_HOLE_LO_LOG) && (uint64_t)n_ < (1ull << ZL_GLS_HOLE_HI_LOG)) || (uint64_t)n_ >= (1ull << ZL_GLS_END_LOG)) try_glv = false;
+            }
         }
         int rc = plan_as(ctx, bs, first_, d_scalars, n_, try_glv);
         // (c <= 3: the top window of a 127-bit half-scalar can reach magnitude H + carry; not worth a special case)
@@ -164,7 +189,7 @@ struct MsmJob {
         n_real = n_;
         endo_k = glv ? (int)G::ENDO_K : 1;
         n = (size_t)endo_k * n_;
-        sc_bits = !glv ? (int)G::SC_BITS : (G::ENDO_K == 2 ? 127 : 64);
+        sc_bits = !glv ? (int)G::SC_BITS : MsmJobPartBits<G>::value;  // (zl_msm_endo.h)
         first = first_;
         bsp = &bs;
         pre = bs.precomp_c > 0;  // table of 2^(c w) P_i present: all windows share one bucket set
@@ -207,7 +232,18 @@ struct MsmJob {
         // (Half-scalars of an endomorphism split fill only part of their top window's range -- |k_i| <= 0.67 * 2^127 on BLS12-381, 0.43 * 2^127 on BN254 -- so that
         // window's buckets are 1.5-2.3x as dense as the average: counted double.  A 2^14-point G1 MSM, 32 entries per bucket on average and 8-entry chunks, sent a
         // handful of its top window's buckets to k_msm_merge_big: 82 us of a 0.56-ms device chain, profiles/r06_timeline_msm_2_14_glv.txt.)
-        while (ZL_CHUNK < (uint32_t)ZL_CHUNK_MAX && (glv && G::ENDO_K == 2 ? 2u : 1u) * (maxE / std::max<uint64_t>(1, (uint64_t)SETS * H)) > (uint64_t)4 * ZL_CHUNK) ZL_CHUNK <<= 1;
+        // (Quarter-scalars of the G2 splits: BLS12-381's base-|z| digits are uniform below |z| = 0.82 * 2^64, a top window 1.2x as dense as the average: counted once.
+        // BN254's lattice quarters are sums of four roundings and crowd towards 0 far below their proved bound (FILL_PCT): of random scalars the busiest 1/32 of
+        // [0, 2^64) holds PEAK_PCT = 370 % of an even share (tools/gen_bn254_gls.py), so a full top window's low buckets are 3-3.7x as dense as the average: counted
+        // double like the halves, which keeps such a bucket at 3.7 / 2 * 4 = 7.4 chunks, within k_msm_merge's ZL_BIG_SPAN_SMALL.)
+        uint32_t dense = glv && G::ENDO_K == 2 ? 2u : 1u;
+        if constexpr (G::GLV && G::ENDO_K == 4) {
+            if constexpr (G::GLVP::LATTICE) {
+                static_assert(G::GLVP::PEAK_PCT <= 400, "the top window's busiest buckets are more than 4x the average: a factor of 2 no longer keeps them below 8 chunks");
+                if (glv && G::GLVP::PEAK_PCT > 200) dense = 2u;
+            }
+        }
+        while (ZL_CHUNK < (uint32_t)ZL_CHUNK_MAX && dense * (maxE / std::max<uint64_t>(1, (uint64_t)SETS * H)) > (uint64_t)4 * ZL_CHUNK) ZL_CHUNK <<= 1;
         ZL_CHUNK = (uint32_t)std::max(8, zl_tune("ZL_TUNE_CHUNK", (int)ZL_CHUNK));
         nchunks = (uint32_t)((maxE + ZL_CHUNK - 1) / ZL_CHUNK);
         // bucket reduction (k_msm_reduce_level0 + k_msm_reduce_tree): blocks of 8 buckets (4 / 2 for smaller inputs: more lanes, shorter chains)
@@ -380,7 +416,10 @@ struct MsmJob {
                 if (phi_owner)
                     hipLaunchKernelGGL((k_glv_phi<G>), dim3((uint32_t)((n_real + 127) / 128)), dim3(128), 0, st, d_bases, (uint32_t)n_real, const_cast<Affine<F>*>(d_phi));
             } else if constexpr (G::GLV && G::ENDO_K == 4) {
-                hipLaunchKernelGGL((k_gls_split<typename G::GLVP>), dim3((uint32_t)((n_real + 255) / 256)), dim3(256), 0, st, sc, (uint32_t)n_real, d_inf, d_vs, (int)G::SC_BITS, d_bad_scalar);
+                if constexpr (G::GLVP::LATTICE)
+                    hipLaunchKernelGGL((k_gls_split_lattice<typename G::GLVP>), dim3((uint32_t)((n_real + 255) / 256)), dim3(256), 0, st, sc, (uint32_t)n_real, d_inf, d_vs, (int)G::SC_BITS, d_bad_scalar);
+                else
+                    hipLaunchKernelGGL((k_gls_split<typename G::GLVP>), dim3((uint32_t)((n_real + 255) / 256)), dim3(256), 0, st, sc, (uint32_t)n_real, d_inf, d_vs, (int)G::SC_BITS, d_bad_scalar);
                 if (phi_owner)
                     hipLaunchKernelGGL((k_gls_psi<G>), dim3((uint32_t)((n_real + 63) / 64)), dim3(64), 0, st, d_bases, (uint32_t)n_real, const_cast<Affine<F>*>(d_phi));
             }

@@ -8,6 +8,7 @@
 #include "zl_host.h"
 #include "zl_field28r.h"
 #include "zl_fq2pair.h"
+#include "zl_msm_endo.h"
 
 using namespace openzl;
 
@@ -594,6 +595,43 @@ static int test_fp28_op_t(zl_ctx* ctx, int op, const uint32_t* in, size_t n, uin
         hipLaunchKernelGGL((k_test_fp28<F>), dim3((uint32_t)((n + 63) / 64)), dim3(64), 0, st, op, d_in, (uint32_t)n, d_out);
     });
 }
+// The split kernel of a group's plain MSM, alone: what MsmJob::sort launches in front of the recoder (zl_msm_job.h), on the ctx's stream.
+template <class G>
+static int endo_split_run(zl_ctx* ctx, const uint64_t* scalars, const uint8_t* inf, size_t n, uint32_t* out, int* endo_k, int* part_bits) {
+    if constexpr (!G::GLV) {
+        return ZL_EINVAL;
+    } else {
+        using P = typename G::GLVP;
+        *endo_k = (int)G::ENDO_K;
+        *part_bits = MsmJobPartBits<G>::value;
+        const size_t in_words = n * 8, inf_words = (n + 15) / 16 * 4 /* keeps the records 16-byte aligned */, out_words = (size_t)G::ENDO_K * n * 8 + 1;
+        void* d = nullptr;
+        int rc = zl_scratch_get(ctx, ZL_SLOT_TESTHOOK, (in_words + inf_words + out_words) * 4 + 64, &d);
+        if (rc) return rc;
+        uint32_t* d_in = (uint32_t*)d;
+        uint8_t* d_inf = (uint8_t*)(d_in + in_words);
+        uint32_t* d_out = d_in + in_words + inf_words;
+        uint32_t* d_bad = d_out + out_words - 1;
+        hipStream_t st = ctx->stream;
+        ZL_HIP(ctx, hipMemcpyAsync(d_in, scalars, in_words * 4, hipMemcpyHostToDevice, st));
+        if (inf) ZL_HIP(ctx, hipMemcpyAsync(d_inf, inf, n, hipMemcpyHostToDevice, st));
+        ZL_HIP(ctx, hipMemsetAsync(d_out, 0, out_words * 4, st));
+        const dim3 grid((uint32_t)((n + 255) / 256)), block(256);
+        const uint8_t* inf_arg = inf ? d_inf : nullptr;
+        if constexpr (G::ENDO_K == 2) {
+            if constexpr (P::LATTICE) hipLaunchKernelGGL((k_glv_split_lattice<P>), grid, block, 0, st, d_in, (uint32_t)n, inf_arg, d_out, (int)G::SC_BITS, d_bad);
+            else hipLaunchKernelGGL((k_glv_split<P>), grid, block, 0, st, d_in, (uint32_t)n, inf_arg, d_out, (int)G::SC_BITS, d_bad);
+        } else {
+            if constexpr (P::LATTICE) hipLaunchKernelGGL((k_gls_split_lattice<P>), grid, block, 0, st, d_in, (uint32_t)n, inf_arg, d_out, (int)G::SC_BITS, d_bad);
+            else hipLaunchKernelGGL((k_gls_split<P>), grid, block, 0, st, d_in, (uint32_t)n, inf_arg, d_out, (int)G::SC_BITS, d_bad);
+        }
+        ZL_HIP(ctx, hipGetLastError());
+        ZL_HIP(ctx, hipMemcpyAsync(out, d_out, out_words * 4, hipMemcpyDeviceToHost, st));
+        ZL_HIP(ctx, hipStreamSynchronize(st));
+        return ZL_OK;
+    }
+}
+
 extern "C" {
 
 int zl_test_poseidon_permute_dev(zl_ctx* ctx, zl_curve_t curve, uint64_t* state) {
@@ -822,6 +860,21 @@ int zl_test_acc_clock_read(zl_ctx* ctx, double* out) {
     ZL_HIP(ctx, hipMemcpy(r.data(), ctx->acc_clk, r.size() * 8, hipMemcpyDeviceToHost));
     clock_reduce(r, ctx->acc_clk_waves, out);
     return ZL_OK;
+}
+
+int zl_test_endo_split_inf(zl_ctx* ctx, zl_curve_t curve, zl_group_t group, const uint64_t* scalars, const uint8_t* inf, size_t n, uint32_t* out_records, int* endo_k,
+                           int* part_bits) {
+    if (!ctx || !scalars || !out_records || !endo_k || !part_bits || n == 0 || n >= ((size_t)1 << 24)) return ZL_EINVAL;
+    ZL_HIP(ctx, hipSetDevice(ctx->device));
+    if (curve == ZL_BLS12_381 && group == ZL_G1) return endo_split_run<BlsG1>(ctx, scalars, inf, n, out_records, endo_k, part_bits);
+    if (curve == ZL_BN254 && group == ZL_G1) return endo_split_run<BnG1>(ctx, scalars, inf, n, out_records, endo_k, part_bits);
+    if (curve == ZL_BLS12_381 && group == ZL_G2) return endo_split_run<BlsG2>(ctx, scalars, inf, n, out_records, endo_k, part_bits);
+    if (curve == ZL_BN254 && group == ZL_G2) return endo_split_run<BnG2>(ctx, scalars, inf, n, out_records, endo_k, part_bits);
+    return ZL_EINVAL;
+}
+
+int zl_test_endo_split(zl_ctx* ctx, zl_curve_t curve, zl_group_t group, const uint64_t* scalars, size_t n, uint32_t* out_records, int* endo_k, int* part_bits) {
+    return zl_test_endo_split_inf(ctx, curve, group, scalars, nullptr, n, out_records, endo_k, part_bits);
 }
 
 int zl_test_ntt_fit_beside(zl_ctx* ctx, int on) {
