@@ -156,6 +156,23 @@ int zl_groth16_verify_batch(zl_ctx* ctx, const zl_g16_keys* k, const uint64_t* p
 size_t zl_point_bytes(zl_curve_t curve, zl_group_t group);
 int zl_point_to_bytes(zl_curve_t curve, zl_group_t group, const uint64_t* xy, uint8_t inf, uint8_t* out);
 int zl_point_from_bytes(zl_curve_t curve, zl_group_t group, const uint8_t* in, uint64_t* xy, uint8_t* inf);
+/* The same decoding for a batch ON THE DEVICE, one lane per point (openzl_amd/csrc/zl_decode_dev.hip): the square root(s), the sign rule and the
+ * subgroup check (a plain multiplication by r; BN254 G1 has cofactor 1 and needs none).  in: count packed records of zl_point_bytes(curve, group) bytes, at
+ * any byte alignment.  status[i], out_xy + i x (2 or 4 Fq of canonical words) and out_inf[i] are what zl_point_from_bytes returns for record i: all-zero
+ * words and inf = 0 on every status but ZL_OK.  Returns ZL_OK when the batch was processed (bad records are data, not a call failure), ZL_EINVAL for bad
+ * arguments, ZL_EHIP / ZL_ENOMEM as elsewhere.  count == 0 is ZL_OK. */
+int zl_points_from_bytes_batch(zl_ctx* ctx, zl_curve_t curve, zl_group_t group, const uint8_t* in, size_t count, uint64_t* out_xy, uint8_t* out_inf,
+                               int32_t* status);
+/* count proofs of zl_groth16_proof_bytes(curve) bytes each, decoded on the device.  status[i] and proofs[i] are what zl_groth16_proof_from_bytes returns and
+ * leaves for record i: the status of the first failing point of A, B, C; that point and those behind it all-zero, the points in front of it decoded
+ * (a caller looks at the status first, as with the host function). */
+int zl_groth16_proofs_from_bytes_batch(zl_ctx* ctx, zl_curve_t curve, const uint8_t* in, size_t count, zl_g16_proof* proofs, int32_t* status);
+/* zl_groth16_verify_batch over wire proofs: the records are decoded on the device (as above), then the proofs that decoded go through the random linear
+ * combination of zl_groth16_verify_batch with their public inputs.  ok_each[i] (optional) = 1 iff record i decodes AND verifies, i.e. what
+ * zl_groth16_proof_from_bytes followed by zl_groth16_verify gives; *ok = 1 iff every record does; status (optional, count codes) = the decode statuses.
+ * public_inputs, n_public, seed: as zl_groth16_verify_batch (n_public + 1 != the key's gamma_abc length: ZL_EINVAL; count == 0: *ok = 1). */
+int zl_groth16_verify_batch_bytes(zl_ctx* ctx, const zl_g16_keys* k, const uint64_t* public_inputs, size_t n_public, const uint8_t* proofs_bytes,
+                                  size_t count, const uint64_t* seed, int* ok, uint8_t* ok_each, int32_t* status);
 /* Uncompressed form (ark's serialize_uncompressed / serialize_unchecked): x then y, flags on the last byte of y; a finite point
  * carries no flag bits, infinity is written as (0, 1) with bit 6 set.  check = 0 is deserialize_unchecked (coordinates must be canonical
  * integers, nothing else is verified); check != 0 also requires a point of the prime-order subgroup (ZL_ENOTCURVE otherwise). */

@@ -139,6 +139,13 @@ int zl_test_endo_split(zl_ctx* ctx, zl_curve_t curve, zl_group_t group, const ui
 int zl_test_endo_split_inf(zl_ctx* ctx, zl_curve_t curve, zl_group_t group, const uint64_t* scalars, const uint8_t* inf, size_t n, uint32_t* out_records, int* endo_k,
                            int* part_bits);
 
+/* The point decoders behind zl_points_from_bytes_batch (openzl_amd/csrc/zl_decode.h: lane-uniform square roots, sign rule, multiplication by r), compiled
+ * for the HOST: arguments, outputs and statuses as zl_points_from_bytes_batch, no ctx.  The device kernels run the same templates. */
+int zl_test_decode_points_host(zl_curve_t curve, zl_group_t group, const uint8_t* in, size_t count, uint64_t* out_xy, uint8_t* out_inf, int32_t* status);
+/* fq2_sqrt of that header on n arbitrary Fq2 values (in: n x (c0 || c1) canonical u64 words), on the device when a ctx is given and on the host otherwise.
+ * ok[i] = 1 iff value i is a square; out: n roots in the same layout (root^2 == value; either root may come back), all-zero words where ok[i] = 0. */
+int zl_test_fq2_sqrt(zl_ctx* ctx, zl_curve_t curve, const uint64_t* in, size_t n, uint64_t* out, uint8_t* ok);
+
 #ifdef __cplusplus
 }
 #endif

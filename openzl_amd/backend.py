@@ -20,6 +20,7 @@ FQ_LIMBS = {ZL_BLS12_381: 6, ZL_BN254: 4}
 
 u64p = C.POINTER(C.c_uint64)
 u8p = C.POINTER(C.c_uint8)
+i32p = C.POINTER(C.c_int32)
 
 # every symbol include/zl_backend.h declares (tests check the library exports all of them)
 ABI_SYMBOLS = [
@@ -32,6 +33,7 @@ ABI_SYMBOLS = [
     "zl_point_bytes", "zl_point_to_bytes", "zl_point_from_bytes", "zl_groth16_proof_bytes", "zl_groth16_proof_to_bytes", "zl_groth16_proof_from_bytes",
     "zl_point_bytes_uncompressed", "zl_point_to_bytes_uncompressed", "zl_point_from_bytes_uncompressed", "zl_groth16_keys_to_bytes", "zl_groth16_keys_from_bytes", "zl_groth16_keys_parse",
     "zl_groth16_vk_to_bytes", "zl_pairing_product", "zl_groth16_verify_batch",
+    "zl_points_from_bytes_batch", "zl_groth16_proofs_from_bytes_batch", "zl_groth16_verify_batch_bytes",
 ]
 
 
@@ -133,6 +135,9 @@ def load_library(path: Optional[str] = None):
     L.zl_pairing.argtypes = [C.c_int, u64p, u64p, u64p]
     L.zl_pairing_product.argtypes = [vp, C.c_int, u64p, u64p, C.c_size_t, u64p]
     L.zl_groth16_verify_batch.argtypes = [vp, vp, u64p, C.c_size_t, C.POINTER(G16ProofC), C.c_size_t, u64p, C.POINTER(C.c_int), u8p]
+    L.zl_points_from_bytes_batch.argtypes = [vp, C.c_int, C.c_int, vp, C.c_size_t, u64p, u8p, i32p]
+    L.zl_groth16_proofs_from_bytes_batch.argtypes = [vp, C.c_int, vp, C.c_size_t, C.POINTER(G16ProofC), i32p]
+    L.zl_groth16_verify_batch_bytes.argtypes = [vp, vp, u64p, C.c_size_t, vp, C.c_size_t, u64p, C.POINTER(C.c_int), u8p, i32p]
     L.zl_point_bytes.argtypes = [C.c_int, C.c_int]
     L.zl_point_bytes.restype = C.c_size_t
     L.zl_point_to_bytes.argtypes = [C.c_int, C.c_int, u64p, C.c_uint8, u8p]
@@ -185,6 +190,8 @@ def load_library(path: Optional[str] = None):
     L.zl_test_clock_probe_read.argtypes = [vp, C.POINTER(C.c_double)]
     L.zl_test_ntt_plan.argtypes = [C.c_uint, C.POINTER(C.c_uint), C.POINTER(C.c_uint)]
     L.zl_test_ntt_fit_beside.argtypes = [vp, C.c_int]
+    L.zl_test_decode_points_host.argtypes = [C.c_int, C.c_int, vp, C.c_size_t, u64p, u8p, i32p]
+    L.zl_test_fq2_sqrt.argtypes = [vp, C.c_int, u64p, C.c_size_t, u64p, u8p]
     # (zl_test_endo_split / _inf: hook_endo_split declares them where it calls them)
     if path is None:
         _lib = L
@@ -221,6 +228,17 @@ def _pk_struct(curve: int, pk: dict):
         keep.append(arr)
         setattr(pkc, k, arr.ctypes.data_as(u64p))
     return pkc, keep
+
+
+def _bytes_view(data, offset: int, need: int) -> np.ndarray:
+    """contiguous uint8 view of bytes / an array, checked to hold `need` bytes from `offset` on (never empty: ctypes wants an address)"""
+    buf = np.frombuffer(data, dtype=np.uint8) if isinstance(data, (bytes, bytearray, memoryview)) else np.ascontiguousarray(data, dtype=np.uint8).reshape(-1)
+    assert buf.size >= offset + need, "short input"
+    return buf if buf.size else np.zeros(1, dtype=np.uint8)
+
+
+def _addr(buf: np.ndarray, offset: int):
+    return C.c_void_p(buf.ctypes.data + offset)
 
 
 def _proof_tuple(curve: int, proof: "G16ProofC"):
@@ -283,6 +301,28 @@ class Backend:
         out = np.zeros((12, nq), dtype=np.uint64)
         self._check(self.L.zl_pairing_product(self._ctx, curve, _p64(p), _p64(q), n, _p64(out)), "zl_pairing_product")
         return out
+
+    def points_from_bytes(self, curve: int, group: int, data, count: int, offset: int = 0):
+        """zl_points_from_bytes_batch: `count` compressed points decoded on the device (square roots, sign rule, subgroup check), one lane per point.
+        data: bytes or a uint8 array holding the packed records from byte `offset` on (any alignment).  Returns (xy (count, 2 or 4 x FQ64) canonical words,
+        inf (count,) uint8, status (count,) int32): per record what point_from_bytes gives -- a bad record is a status, not an exception."""
+        rec = self.L.zl_point_bytes(curve, group)
+        buf = _bytes_view(data, offset, count * rec)
+        xy = np.zeros((count, 2 * group * FQ_LIMBS[curve]), dtype=np.uint64)
+        inf = np.zeros(count, dtype=np.uint8)
+        st = np.zeros(count, dtype=np.int32)
+        self._check(self.L.zl_points_from_bytes_batch(self._ctx, curve, group, _addr(buf, offset), count, _p64(xy) if count else None, inf.ctypes.data_as(u8p) if count else None,
+                                                      st.ctypes.data_as(i32p) if count else None), "zl_points_from_bytes_batch")
+        return xy, inf, st
+
+    def proofs_from_bytes(self, curve: int, data, count: int):
+        """zl_groth16_proofs_from_bytes_batch: `count` wire proofs decoded on the device -> (proof tuples as proof_from_bytes returns them, status (count,) int32).
+        A record whose status is not 0 did not decode (its tuple holds what the host decoder leaves: the points in front of the failing one)."""
+        buf = _bytes_view(data, 0, count * self.L.zl_groth16_proof_bytes(curve))
+        out = (G16ProofC * max(1, count))()
+        st = np.zeros(max(1, count), dtype=np.int32)
+        self._check(self.L.zl_groth16_proofs_from_bytes_batch(self._ctx, curve, _addr(buf, 0), count, out, st.ctypes.data_as(i32p)), "zl_groth16_proofs_from_bytes_batch")
+        return [_proof_tuple(curve, p) for p in out[:count]], st[:count]
 
     def describe(self) -> str:
         buf = C.create_string_buffer(512)
@@ -589,7 +629,7 @@ class MultiBackend:
 TEST_ABI_SYMBOLS = ["zl_test_poseidon_permute_dev", "zl_test_fp28_op", "zl_test_fp28_bn_op", "zl_test_pairing_product", "zl_test_point_op", "zl_test_circuit_tweak", "zl_test_fq_mul_rate", "zl_test_fr28_op", "zl_test_fr29_op",
                     "zl_test_poseidon_permute_dev28r", "zl_test_fq_mul_clock", "zl_test_acc_clock", "zl_test_acc_clock_read", "zl_test_clock_probe_launch", "zl_test_clock_probe_read",
                     "zl_test_miller_dev", "zl_test_final_exp", "zl_test_verify_batch_host", "zl_test_ntt_plan", "zl_test_ntt_fit_beside", "zl_test_fp2pair_op", "zl_test_point_form_op",
-                    "zl_test_endo_split", "zl_test_endo_split_inf"]
+                    "zl_test_endo_split", "zl_test_endo_split_inf", "zl_test_decode_points_host", "zl_test_fq2_sqrt"]
 
 
 def _p32(a: np.ndarray):
@@ -732,6 +772,32 @@ def hook_verify_batch_host(curve: int, vk: dict, proofs, public_inputs, n_public
     if rc:
         raise BackendError(rc, "zl_test_verify_batch_host")
     return bool(ok.value), each[:n].astype(bool)
+
+
+def hook_decode_points_host(curve: int, group: int, data, count: int):
+    """zl_test_decode_points_host: the device decoders' templates (csrc/zl_decode.h) run on the CPU; arguments and results as Backend.points_from_bytes"""
+    L = load_library()
+    buf = _bytes_view(data, 0, count * L.zl_point_bytes(curve, group))
+    xy = np.zeros((max(1, count), 2 * group * FQ_LIMBS[curve]), dtype=np.uint64)
+    inf = np.zeros(max(1, count), dtype=np.uint8)
+    st = np.zeros(max(1, count), dtype=np.int32)
+    rc = L.zl_test_decode_points_host(curve, group, _addr(buf, 0), count, _p64(xy), inf.ctypes.data_as(u8p), st.ctypes.data_as(i32p))
+    if rc:
+        raise BackendError(rc, "zl_test_decode_points_host")
+    return xy[:count], inf[:count], st[:count]
+
+
+def hook_fq2_sqrt(be: Optional["Backend"], curve: int, values: np.ndarray):
+    """zl_test_fq2_sqrt: values (n, 2 FQ64) canonical words c0 || c1 -> (roots (n, 2 FQ64), all-zero where there is none; ok (n,) bool); be = None: host"""
+    a = np.ascontiguousarray(values, dtype=np.uint64)
+    n = a.shape[0]
+    assert a.shape == (n, 2 * FQ_LIMBS[curve])
+    out = np.zeros_like(a)
+    ok = np.zeros(max(1, n), dtype=np.uint8)
+    rc = load_library().zl_test_fq2_sqrt(be._ctx if be is not None else None, curve, _p64(a) if n else None, n, _p64(out) if n else None, ok.ctypes.data_as(u8p))
+    if rc:
+        raise BackendError(rc, "zl_test_fq2_sqrt")
+    return out, ok[:n].astype(bool)
 
 
 def hook_point_op(be: Optional["Backend"], group: int, hot: bool, op: int, pq: np.ndarray) -> np.ndarray:
@@ -1103,6 +1169,26 @@ class Groth16Keys:
         self.backend._check(self.L.zl_groth16_verify_batch(self.backend._ctx, self._k, _p64(pub), n_public, arr, n, _p64(sd) if seed is not None else None,
                                                            C.byref(ok), ev.ctypes.data_as(u8p) if each else None), "zl_groth16_verify_batch")
         return (bool(ok.value), ev[:n].astype(bool)) if each else bool(ok.value)
+
+    def verify_batch_bytes(self, data, count: int, public_inputs, seed: Optional[int] = None, each: bool = False, n_public: Optional[int] = None):
+        """zl_groth16_verify_batch_bytes: verify_batch over `count` WIRE proofs (packed proof_to_bytes records): decoded on the device, then the random linear
+        combination over the records that decoded.  public_inputs / seed as verify_batch; n_public overrides what the shape of public_inputs implies.
+        Returns ok, or (ok, per-record verdicts, decode statuses (count,) int32) with each=True; a record that does not decode is a rejected proof."""
+        pub_arr = np.asarray(public_inputs, dtype=np.uint64)
+        if n_public is None:
+            n_public = pub_arr.shape[1] if pub_arr.ndim == 3 else (pub_arr.size // (4 * count) if count else self.circuit.shape[1] - 1)
+        buf = _bytes_view(data, 0, count * self.L.zl_groth16_proof_bytes(self.circuit.curve))
+        pub = np.ascontiguousarray(pub_arr.reshape(-1))
+        if not pub.size:
+            pub = np.zeros(4, dtype=np.uint64)
+        sd = np.array([seed or 0], dtype=np.uint64)
+        ok = C.c_int(0)
+        ev = np.zeros(max(1, count), dtype=np.uint8)
+        st = np.zeros(max(1, count), dtype=np.int32)
+        self.backend._check(self.L.zl_groth16_verify_batch_bytes(self.backend._ctx, self._k, _p64(pub), n_public, _addr(buf, 0), count, _p64(sd) if seed is not None else None,
+                                                                 C.byref(ok), ev.ctypes.data_as(u8p) if each else None, st.ctypes.data_as(i32p) if each else None),
+                            "zl_groth16_verify_batch_bytes")
+        return (bool(ok.value), ev[:count].astype(bool), st[:count]) if each else bool(ok.value)
 
     def close(self):
         if self._k:

@@ -126,6 +126,8 @@ struct zl_scratch {
 //   * ZL_SLOT_STAGING: host scalars / vectors uploaded for one call.  ZL_SLOT_GROTH16: the witness map's vectors (the quotient of the last
 //     proof stays there, zl_ctx::g16_h).  ZL_SLOT_TESTHOOK: inputs and outputs of the test hooks.
 //   * ZL_SLOT_PAIR_*: the device product of pairings.
+//   * ZL_SLOT_DECODE_IN / _OUT: the packed records and the decoded points of the device point / proof decoder (zl_decode_dev.hip).  Not the PAIR_* slots:
+//     zl_groth16_verify_batch_bytes runs the decoder and the product of pairings in one call.
 enum zl_slot : int {
     ZL_SLOT_SET0_COUNTS = 0, ZL_SLOT_SET0_ENTRIES = 1, ZL_SLOT_SET0_BUCKETS = 2, ZL_SLOT_SET0_PARTIALS = 3, ZL_SLOT_SET0_TAIL = 4,
     ZL_SLOT_SORT_A = 5, ZL_SLOT_SORT_B = 6,
@@ -141,7 +143,8 @@ enum zl_slot : int {
     ZL_SLOT_SET3_COUNTS = 28, ZL_SLOT_SET3_ENTRIES = 29, ZL_SLOT_SET3_BUCKETS = 30, ZL_SLOT_SET3_PARTIALS = 31, ZL_SLOT_SET3_TAIL = 32,
     ZL_SLOT_SET3_SORT_A = 33, ZL_SLOT_SET3_SORT_B = 34, ZL_SLOT_SET3_PHI = 35,
     ZL_SLOT_PAIR_IN = 36, ZL_SLOT_PAIR_LINES = 37, ZL_SLOT_PAIR_ACC = 38, ZL_SLOT_PAIR_PREP = 39,
-    ZL_SLOT_COUNT = 40
+    ZL_SLOT_DECODE_IN = 40, ZL_SLOT_DECODE_OUT = 41,
+    ZL_SLOT_COUNT = 42
 };
 // the slots of MSM buffer set 0..3; sort_a / sort_b are used by a job that owns its sort (side by side), every other job sorts in set 0's pair
 struct zl_msm_set_slots {
@@ -161,7 +164,8 @@ constexpr bool zl_slots_disjoint() {
             if (x < 0 || x >= ZL_SLOT_COUNT) return false;
             owners[x]++;
         }
-    for (zl_slot x : {ZL_SLOT_PHI_ONE_KEY, ZL_SLOT_STAGING, ZL_SLOT_GROTH16, ZL_SLOT_TESTHOOK, ZL_SLOT_PAIR_IN, ZL_SLOT_PAIR_LINES, ZL_SLOT_PAIR_ACC, ZL_SLOT_PAIR_PREP}) {
+    for (zl_slot x : {ZL_SLOT_PHI_ONE_KEY, ZL_SLOT_STAGING, ZL_SLOT_GROTH16, ZL_SLOT_TESTHOOK, ZL_SLOT_PAIR_IN, ZL_SLOT_PAIR_LINES, ZL_SLOT_PAIR_ACC, ZL_SLOT_PAIR_PREP,
+                      ZL_SLOT_DECODE_IN, ZL_SLOT_DECODE_OUT}) {
         if (x < 0 || x >= ZL_SLOT_COUNT) return false;
         owners[x]++;
     }
@@ -169,7 +173,9 @@ constexpr bool zl_slots_disjoint() {
         if (n > 1) return false;
     return true;
 }
-static_assert(zl_slots_disjoint(), "scratch slots: the four MSM buffer sets, the shared / staging slots and the pairing product must not collide");
+static_assert(zl_slots_disjoint(), "scratch slots: the four MSM buffer sets, the shared / staging slots, the pairing product and the decoder must not collide");
+static_assert(ZL_SLOT_DECODE_IN != ZL_SLOT_PAIR_IN && ZL_SLOT_DECODE_OUT != ZL_SLOT_PAIR_PREP && ZL_SLOT_DECODE_OUT != ZL_SLOT_PAIR_LINES && ZL_SLOT_DECODE_OUT != ZL_SLOT_PAIR_ACC,
+              "the decoder keeps its own slots: the bytes-in verifier decodes and pairs in one call");
 static_assert(ZL_SLOT_TMP_A == ZL_MSM_SET[0].sort_a && ZL_SLOT_TMP_B == ZL_MSM_SET[0].sort_b && ZL_SLOT_NTT_VEC == ZL_MSM_SET[0].sort_b,
               "the general temporaries and the transform's vector are set 0's sort pair and nothing else (see the map)");
 struct zl_twiddles {

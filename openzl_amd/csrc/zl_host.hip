@@ -11,6 +11,7 @@
 #include <sys/random.h>
 #include "zl_host.h"
 #include "zl_pairing_dev.h"
+#include "zl_decode_dev.h"
 #include "zl_serialize.h"
 
 // zl_groth16.hip: the prover with the assignment in the compiler's two pieces (instance block, witness block; Montgomery limbs)
@@ -1227,6 +1228,51 @@ int zl_groth16_verify_batch(zl_ctx* ctx, const zl_g16_keys* k, const uint64_t* p
     auto vk_of = [](const auto& v, size_t q1) { return BatchVk{v.alpha_g1.data(), v.beta_g2.data(), v.gamma_g2.data(), v.delta_g2.data(), v.gamma_abc_g1.data(), v.gamma_abc_g1.size() / q1}; };
     if (k->curve == ZL_BLS12_381) return verify_batch_t<Bls12_381>(ctx, vk_of(k->vk_bls, 12), public_inputs, n_public, proofs, count, seed, ok, ok_each);
     return verify_batch_t<Bn254>(ctx, vk_of(k->vk_bn, 8), public_inputs, n_public, proofs, count, seed, ok, ok_each);
+}
+// ---- wire proofs and points decoded on the device (zl_decode_dev.hip) ---------------------------------------------------------------------------------
+int zl_points_from_bytes_batch(zl_ctx* ctx, zl_curve_t curve, zl_group_t group, const uint8_t* in, size_t count, uint64_t* out_xy, uint8_t* out_inf,
+                               int32_t* status) {
+    if (!ctx || !zl_point_bytes(curve, group)) return ZL_EINVAL;
+    return curve == ZL_BLS12_381 ? decode_dev::points_bls(ctx, group, in, count, out_xy, out_inf, status) : decode_dev::points_bn(ctx, group, in, count, out_xy, out_inf, status);
+}
+int zl_groth16_proofs_from_bytes_batch(zl_ctx* ctx, zl_curve_t curve, const uint8_t* in, size_t count, zl_g16_proof* proofs, int32_t* status) {
+    if (!ctx || !zl_groth16_proof_bytes(curve)) return ZL_EINVAL;
+    return curve == ZL_BLS12_381 ? decode_dev::proofs_bls(ctx, in, count, proofs, status) : decode_dev::proofs_bn(ctx, in, count, proofs, status);
+}
+int zl_groth16_verify_batch_bytes(zl_ctx* ctx, const zl_g16_keys* k, const uint64_t* public_inputs, size_t n_public, const uint8_t* proofs_bytes, size_t count,
+                                  const uint64_t* seed, int* ok, uint8_t* ok_each, int32_t* status) {
+    if (!ctx || !k || !ok || (count && !proofs_bytes) || (count && n_public && !public_inputs)) return ZL_EINVAL;
+    const size_t n_abc = k->curve == ZL_BLS12_381 ? k->vk_bls.gamma_abc_g1.size() / 12 : k->vk_bn.gamma_abc_g1.size() / 8;
+    if (n_public + 1 != n_abc) return ZL_EINVAL;  // before any work, as zl_groth16_verify_batch
+    // decode -> host structs -> the existing combination over the proofs that decoded, with their public inputs
+    std::vector<zl_g16_proof> proofs(count);
+    std::vector<int32_t> st(count);
+    int rc = zl_groth16_proofs_from_bytes_batch(ctx, (zl_curve_t)k->curve, proofs_bytes, count, proofs.data(), st.data());
+    if (rc) return rc;
+    std::vector<size_t> live;
+    for (size_t i = 0; i < count; i++)
+        if (st[i] == ZL_OK) live.push_back(i);
+    if (live.size() != count) {
+        for (size_t j = 0; j < live.size(); j++) proofs[j] = proofs[live[j]];
+    }
+    std::vector<uint64_t> pubs;
+    const uint64_t* pp = public_inputs;
+    if (live.size() != count && n_public) {
+        pubs.resize(live.size() * n_public * 4);
+        for (size_t j = 0; j < live.size(); j++) memcpy(&pubs[j * n_public * 4], public_inputs + live[j] * n_public * 4, n_public * 32);
+        pp = pubs.data();
+    }
+    std::vector<uint8_t> each(ok_each ? live.size() : 0);
+    int vok = 0;
+    rc = zl_groth16_verify_batch(ctx, k, pp, n_public, proofs.data(), live.size(), seed, &vok, ok_each ? each.data() : nullptr);
+    if (rc) return rc;
+    *ok = vok && live.size() == count ? 1 : 0;
+    if (ok_each) {
+        memset(ok_each, 0, count);
+        for (size_t j = 0; j < live.size(); j++) ok_each[live[j]] = each[j];
+    }
+    if (status) memcpy(status, st.data(), count * sizeof(int32_t));
+    return ZL_OK;
 }
 // test hooks (include/zl_backend_test.h)
 int zl_test_verify_batch_host(zl_curve_t curve, const uint64_t* alpha_g1, const uint64_t* beta_g2, const uint64_t* gamma_g2, const uint64_t* delta_g2,

@@ -9,6 +9,7 @@
 #include "zl_field28r.h"
 #include "zl_fq2pair.h"
 #include "zl_msm_endo.h"
+#include "zl_decode_dev.h"
 
 using namespace openzl;
 
@@ -877,6 +878,18 @@ int zl_test_endo_split(zl_ctx* ctx, zl_curve_t curve, zl_group_t group, const ui
     return zl_test_endo_split_inf(ctx, curve, group, scalars, nullptr, n, out_records, endo_k, part_bits);
 }
 
+// the decoders of zl_decode.h: on the host, and their Fq2 square root alone on either side (zl_decode_dev.hip holds the per-curve instances)
+int zl_test_decode_points_host(zl_curve_t curve, zl_group_t group, const uint8_t* in, size_t count, uint64_t* out_xy, uint8_t* out_inf, int32_t* status) {
+    using namespace openzl;
+    if (!zl_point_bytes(curve, group)) return ZL_EINVAL;
+    return curve == ZL_BLS12_381 ? decode_dev::points_host_bls(group, in, count, out_xy, out_inf, status) : decode_dev::points_host_bn(group, in, count, out_xy, out_inf, status);
+}
+int zl_test_fq2_sqrt(zl_ctx* ctx, zl_curve_t curve, const uint64_t* in, size_t n, uint64_t* out, uint8_t* ok) {
+    using namespace openzl;
+    if (curve == ZL_BLS12_381) return decode_dev::fq2_sqrt_bls(ctx, in, n, out, ok);
+    if (curve == ZL_BN254) return decode_dev::fq2_sqrt_bn(ctx, in, n, out, ok);
+    return ZL_EINVAL;
+}
 int zl_test_ntt_fit_beside(zl_ctx* ctx, int on) {
     if (!ctx) return ZL_EINVAL;
     const int old = ctx->ntt_fit_beside;

@@ -1,11 +1,18 @@
 """Throughput of the device product of pairings and of batched Groth16 verification.
 
-  python tools/pairing_bench.py [--quick]
+  python tools/pairing_bench.py [--quick] [--decode | --decode-only]
 
 Times zl_pairing_product at 2^10 / 2^14 / 2^16 pairs (pairs/s), Groth16Keys.verify_batch over 64 / 1 024 / 16 384 proofs of the 235-constraint Poseidon
 circuit (proofs/s, OS-drawn combination as in production), and the host Groth16::verify loop over the first 64 of those proofs, on both curves.  Each
-figure is the median of three timed calls after one warm-up call.  Prints one line per measurement and a JSON summary line."""
+figure is the median of three timed calls after one warm-up call.  Prints one line per measurement and a JSON summary line.
+
+--decode adds the wire-proof leg (--decode-only runs nothing else), at the same three batch sizes on both curves, over proof_to_bytes records of those proofs:
+  (a) zl_groth16_proofs_from_bytes_batch (device decoder)      (b) the host loop of zl_groth16_proof_from_bytes over the same bytes
+  (c) zl_groth16_verify_batch_bytes (device decode + verify)   (d) (b) followed by zl_groth16_verify_batch
+(a) and (c): median of three calls after a warm-up call.  (b) and (d) are timed together (every pass of (d) contains one of (b)): median of three passes,
+one pass at 16 384 proofs (half a minute of single-threaded host work per pass)."""
 import argparse
+import ctypes as C
 import json
 import os
 import statistics
@@ -18,6 +25,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
 from openzl_amd import ZL_BLS12_381, ZL_BN254, ZL_G1, ZL_G2, Backend, Circuit, Groth16Keys  # noqa: E402
+from openzl_amd.backend import G16ProofC, proof_to_bytes  # noqa: E402
 
 NAMES = {ZL_BLS12_381: "bls12_381", ZL_BN254: "bn254"}
 R = {ZL_BLS12_381: 0x73EDA753299D7D483339D80809A1D80553BDA402FFFE5BFEFFFFFFFF00000001,
@@ -41,9 +49,65 @@ def timed(fn, reps=3):
     return statistics.median(ts)
 
 
+def host_decode_loop(L, curve, data: bytes, m: int):
+    """zl_groth16_proof_from_bytes record by record, as a caller without the batch entry point does it"""
+    nbytes = len(data) // m
+    buf = (C.c_uint8 * len(data)).from_buffer_copy(data)
+    base = C.addressof(buf)
+    out = (G16ProofC * m)()
+    u8p = C.POINTER(C.c_uint8)
+    for i in range(m):
+        rc = L.zl_groth16_proof_from_bytes(curve, C.cast(base + i * nbytes, u8p), nbytes, C.byref(out[i]))
+        assert rc == 0
+    return out
+
+
+def decode_leg(be, keys, curve, name, proofs, pub, batch_sizes, res):
+    """every leg at the C ABI (struct arrays and byte buffers made once, outside the timed calls): the Python wrappers' per-proof tuples would be most of (a)"""
+    L = be.L
+    u64p = C.POINTER(C.c_uint64)
+    for m in batch_sizes:
+        data = b"".join(proof_to_bytes(curve, p) for p in proofs[:m])
+        tuples, st = be.proofs_from_bytes(curve, data, m)
+        assert not st.any() and all(np.array_equal(x, y) for p, q in zip(tuples[:64], proofs[:64]) for x, y in zip(p, q))
+        buf = (C.c_uint8 * len(data)).from_buffer_copy(data)
+        pubs = np.ascontiguousarray(np.tile(pub[None], (m, 1, 1)).reshape(-1), dtype=np.uint64)
+        pp, n_public = pubs.ctypes.data_as(u64p), pub.shape[0]
+        out = (G16ProofC * m)()
+        status = (C.c_int32 * m)()
+        ok = C.c_int(0)
+
+        def dev_decode():
+            assert L.zl_groth16_proofs_from_bytes_batch(be._ctx, curve, buf, m, out, status) == 0
+
+        def dev_verify_bytes():
+            assert L.zl_groth16_verify_batch_bytes(be._ctx, keys._k, pp, n_public, buf, m, None, C.byref(ok), None, None) == 0 and ok.value == 1
+
+        ta = timed(dev_decode)
+        assert not any(status)
+        tc = timed(dev_verify_bytes)
+        tb, td = [], []
+        for _ in range(3 if m <= 1024 else 1):
+            t0 = time.perf_counter()
+            hout = host_decode_loop(L, curve, data, m)
+            t1 = time.perf_counter()
+            assert L.zl_groth16_verify_batch(be._ctx, keys._k, pp, n_public, hout, m, None, C.byref(ok), None) == 0 and ok.value == 1
+            t2 = time.perf_counter()
+            tb.append(t1 - t0)
+            td.append(t2 - t0)
+        tb, td = statistics.median(tb), statistics.median(td)
+        for key, t, what in (("a_decode_dev", ta, "(a) proofs_from_bytes_batch"), ("b_decode_host", tb, "(b) host proof_from_bytes loop"),
+                             ("c_verify_bytes", tc, "(c) verify_batch_bytes"), ("d_host_decode_verify", td, "(d) host loop + verify_batch")):
+            res[f"{name}_{key}_{m}_proofs_per_s"] = m / t
+            print(f"{name} {what} count={m}: {t * 1e3:.2f} ms, {m / t:,.0f} proofs/s", flush=True)
+        print(f"{name} count={m}: (a) / (b) = {tb / ta:.1f}x, (c) / (d) = {td / tc:.1f}x", flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--quick", action="store_true", help="smallest sizes only (a smoke run of the tool)")
+    ap.add_argument("--decode", action="store_true", help="add the wire-proof leg: device decoder and bytes-in verifier against the host decode loop")
+    ap.add_argument("--decode-only", action="store_true", help="the wire-proof leg alone")
     args = ap.parse_args()
     be = Backend(0)
     print(be.describe(), flush=True)
@@ -52,6 +116,16 @@ def main():
     batch_sizes = [64] if args.quick else [64, 1024, 16384]
     for curve in (ZL_BLS12_381, ZL_BN254):
         name = NAMES[curve]
+        def make_proofs():
+            circ = Circuit(curve, 1)
+            keys = Groth16Keys(be, circ, seed=0xBE4C)
+            return keys, circ.arrays()["assignment"][1:2], keys.prove_many(list(range(max(batch_sizes))))
+
+        if args.decode_only:
+            keys, pub, proofs = make_proofs()
+            decode_leg(be, keys, curve, name, proofs, pub, batch_sizes, res)
+            keys.close()
+            continue
         nmax = max(pair_sizes)
         h1 = be.bases_generate(curve, scalars(curve, nmax, 1), group=ZL_G1)
         h2 = be.bases_generate(curve, scalars(curve, nmax, 2), group=ZL_G2)
@@ -62,10 +136,7 @@ def main():
             t = timed(lambda: be.pairing_product(curve, P[:n], Q[:n]))
             res[f"{name}_pairing_product_{n}_pairs_per_s"] = n / t
             print(f"{name} pairing_product n={n}: {t * 1e3:.2f} ms, {n / t:,.0f} pairs/s", flush=True)
-        circ = Circuit(curve, 1)
-        keys = Groth16Keys(be, circ, seed=0xBE4C)
-        pub = circ.arrays()["assignment"][1:2]
-        proofs = keys.prove_many(list(range(max(batch_sizes))))
+        keys, pub, proofs = make_proofs()
         for m in batch_sizes:
             pubs = np.tile(pub[None], (m, 1, 1))
             ok = keys.verify_batch(proofs[:m], pubs)
@@ -81,6 +152,8 @@ def main():
         if not args.quick:
             res[f"{name}_speedup_1024"] = res[f"{name}_verify_batch_1024_proofs_per_s"] * th
             print(f"{name} verify_batch(1024) / host verify: {res[f'{name}_speedup_1024']:.1f}x", flush=True)
+        if args.decode:  # after the existing measurements, whose order and surroundings stay as they were
+            decode_leg(be, keys, curve, name, proofs, pub, batch_sizes, res)
         keys.close()
     be.close()
     print(json.dumps({"pairing_bench": {k: round(v, 1) for k, v in res.items()}}), flush=True)
