@@ -32,6 +32,23 @@ int zl_msm_partial_dev(zl_ctx* ctx, uint64_t bases, size_t first, const void* d_
  * pipelined on three streams -- the sort of MSM i+2, the bucket accumulation of MSM i+1 and the merge / reduction tail of MSM i
  * overlap -- so that in steady state an MSM costs little more than its accumulation kernel; results are identical to `count` separate calls. */
 int zl_msm_batch_partial_dev(zl_ctx* ctx, uint64_t bases, size_t first, const void* const* d_scalars, size_t n, size_t count, uint64_t* out_partials);
+/* `count` MSMs over ONE base range in one device pass: vector j = n canonical scalars at d_scalars + j * stride_scalars * 32 bytes
+ * (stride_scalars >= n).  out_xy + j * (2 or 4 Fq of canonical words), out_inf[j] (may be NULL): exactly what zl_msm_dev returns for vector j.
+ * The batch is the parallel dimension (one wave per vector, 6-bit window and slice of 2048 points; openzl_amd/csrc/zl_msm_multi.hip): measured against
+ * zl_msm_batch_partial_dev it is the faster one for many short vectors -- n <= 2^12 with a thousand vectors on every group, G1 from 64 vectors on -- and
+ * the slower one at 2^15 points (profiles/prove_batch_bench.log).  A count whose partial sums exceed the scratch budget runs in chunks
+ * (ZL_TUNE_MSM_MULTI_CHUNK overrides the chunk).  count == 0 or n == 0: ZL_OK, for n == 0 every result is infinity.  A scalar with bits at or
+ * above the scalar field's width: ZL_EINVAL, as from zl_msm_dev. */
+int zl_msm_multi_dev(zl_ctx* ctx, uint64_t bases, size_t first, const void* d_scalars, size_t n, size_t stride_scalars, size_t count, uint64_t* out_xy,
+                     uint8_t* out_inf);
+/* `count` proofs over one key and one resident circuit: assignment j = (n_instance + n_witness) x 4 u64 at assignments + j * that many words (host memory;
+ * flags: 0 or ZL_MONT as zl_groth16_prove_resident), blinding scalars r[j], s[j] at r + 4 j, s + 4 j.  proofs[j] equals what
+ * zl_groth16_prove_resident returns for (assignment j, r[j], s[j]), byte for byte.  Domains up to 2^ZL_TUNE_G16_BATCH_LOG_N with at least
+ * ZL_TUNE_G16_BATCH_MIN proofs keep the whole batch on the device (witness map with a batch dimension, A, B and C as three zl_msm_multi passes over
+ * extended queries cached with the key, no point arithmetic on the host); everything else loops the resident prover.  The first failing proof's
+ * error is returned.  zl_groth16_last_h after a device batch returns ZL_EINVAL. */
+int zl_groth16_prove_batch(zl_ctx* ctx, const zl_g16_pk* pk, uint64_t r1cs_handle, const uint64_t* assignments, unsigned flags, const uint64_t* r,
+                           const uint64_t* s, size_t count, zl_g16_proof* proofs);
 int zl_partials_sum(zl_curve_t curve, zl_group_t group, const uint64_t* partials, size_t count, uint64_t* out_xy, uint8_t* out_inf);
 /* wrap a canonical affine point (all-zero = infinity) as a partial, e.g. to fold an extra term into zl_partials_sum */
 int zl_partial_from_affine(zl_curve_t curve, zl_group_t group, const uint64_t* xy, uint64_t* out_partial);
@@ -200,7 +217,7 @@ int zl_groth16_vk_to_bytes(const zl_g16_keys* k, uint8_t* out, size_t cap, size_
 typedef struct zl_timing {
     float total_ms;      /* first kernel start -> last kernel end of the last zl_msm* / zl_ntt* call */
     float dominant_ms;   /* the dominant kernel: bucket accumulation (MSM) / all butterfly passes (NTT) */
-    uint32_t launches;   /* launches of the dominant kernel in that call */
+    uint32_t launches;   /* launches of the dominant kernel in that call (zl_msm_multi_dev: one accumulation launch per chunk of vectors) */
     uint32_t window_bits;
     uint64_t entries;    /* MSM: (point, window) pairs accumulated */
 } zl_timing;

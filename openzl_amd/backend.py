@@ -33,7 +33,7 @@ ABI_SYMBOLS = [
     "zl_point_bytes", "zl_point_to_bytes", "zl_point_from_bytes", "zl_groth16_proof_bytes", "zl_groth16_proof_to_bytes", "zl_groth16_proof_from_bytes",
     "zl_point_bytes_uncompressed", "zl_point_to_bytes_uncompressed", "zl_point_from_bytes_uncompressed", "zl_groth16_keys_to_bytes", "zl_groth16_keys_from_bytes", "zl_groth16_keys_parse",
     "zl_groth16_vk_to_bytes", "zl_pairing_product", "zl_groth16_verify_batch",
-    "zl_points_from_bytes_batch", "zl_groth16_proofs_from_bytes_batch", "zl_groth16_verify_batch_bytes",
+    "zl_points_from_bytes_batch", "zl_groth16_proofs_from_bytes_batch", "zl_groth16_verify_batch_bytes", "zl_msm_multi_dev", "zl_groth16_prove_batch",
 ]
 
 
@@ -104,6 +104,7 @@ def load_library(path: Optional[str] = None):
     L.zl_partials_sum.argtypes = [C.c_int, C.c_int, u64p, C.c_size_t, u64p, u8p]
     L.zl_partial_from_affine.argtypes = [C.c_int, C.c_int, u64p, u64p]
     L.zl_msm_batch_partial_dev.argtypes = [vp, C.c_uint64, C.c_size_t, C.POINTER(C.c_void_p), C.c_size_t, C.c_size_t, u64p]
+    L.zl_msm_multi_dev.argtypes = [vp, C.c_uint64, C.c_size_t, vp, C.c_size_t, C.c_size_t, C.c_size_t, u64p, u8p]
     L.zl_ntt.argtypes = [vp, C.c_int, u64p, C.c_uint, C.c_uint]
     L.zl_ntt_dev.argtypes = [vp, C.c_int, vp, C.c_uint, C.c_uint]
     L.zl_ntt_cross_dev.argtypes = [vp, C.c_int, vp, C.c_uint, C.c_uint, C.c_uint, C.c_uint]
@@ -116,6 +117,7 @@ def load_library(path: Optional[str] = None):
     L.zl_r1cs_upload.argtypes = [vp, C.c_int, C.POINTER(R1csC), C.POINTER(C.c_uint64)]
     L.zl_r1cs_free.argtypes = [vp, C.c_uint64]
     L.zl_groth16_prove_resident.argtypes = [vp, C.POINTER(G16PkC), C.c_uint64, u64p, C.c_uint, u64p, u64p, C.POINTER(G16ProofC)]
+    L.zl_groth16_prove_batch.argtypes = [vp, C.POINTER(G16PkC), C.c_uint64, u64p, C.c_uint, u64p, u64p, C.c_size_t, C.POINTER(G16ProofC)]
     L.zl_circuit_poseidon_chain.argtypes = [C.c_int, C.c_uint32, u64p, u64p, C.POINTER(vp)]
     L.zl_circuit_free.argtypes = [vp]
     L.zl_circuit_free.restype = None
@@ -410,6 +412,16 @@ class Backend:
         self._check(self.L.zl_msm_batch_partial_dev(self._ctx, handle, first, ptrs, n, count, _p64(out)), "zl_msm_batch_partial_dev")
         return out
 
+    def msm_multi_dev(self, handle: int, d_scalars: int, n: int, count: int, stride: Optional[int] = None, first: int = 0) -> Tuple[np.ndarray, np.ndarray]:
+        """`count` MSMs over bases [first, first + n) in one device pass: vector j = n x 4 u64 canonical scalars at d_scalars + j * stride * 32 bytes
+        (stride in scalars, default n) -> ((count, words) canonical affine results, (count,) infinity flags), each row what msm_dev gives for that vector."""
+        curve, group, _ = self._bases[handle]
+        out = np.zeros((count, 2 * group * FQ_LIMBS[curve]), dtype=np.uint64)
+        inf = np.zeros(max(1, count), dtype=np.uint8)
+        self._check(self.L.zl_msm_multi_dev(self._ctx, handle, first, C.c_void_p(d_scalars), n, n if stride is None else stride, count, _p64(out) if count else None,
+                                            inf.ctypes.data_as(u8p)), "zl_msm_multi_dev")
+        return out, inf[:count]
+
     def partials_sum(self, curve: int, partials: np.ndarray, group: int = ZL_G1) -> Tuple[np.ndarray, int]:
         partials = np.ascontiguousarray(partials.reshape(-1, ZL_PARTIAL_WORDS))
         out, inf = np.zeros(2 * group * FQ_LIMBS[curve], dtype=np.uint64), C.c_uint8(0)
@@ -475,6 +487,21 @@ class Backend:
         self._check(self.L.zl_groth16_prove_resident(self._ctx, C.byref(pkc), r1cs_handle, _p64(z), flags, _p64(np.ascontiguousarray(r)),
                                                      _p64(np.ascontiguousarray(s)), C.byref(proof)), "zl_groth16_prove_resident")
         return _proof_tuple(curve, proof)
+
+    def _prove_batch(self, pkc, curve: int, r1cs_handle: int, assignments: np.ndarray, r: np.ndarray, s: np.ndarray, flags: int):
+        z = np.ascontiguousarray(assignments, dtype=np.uint64)
+        count = z.shape[0]
+        r, s = np.ascontiguousarray(r, dtype=np.uint64).reshape(count, 4), np.ascontiguousarray(s, dtype=np.uint64).reshape(count, 4)
+        out = (G16ProofC * max(1, count))()
+        self._check(self.L.zl_groth16_prove_batch(self._ctx, C.byref(pkc), r1cs_handle, _p64(z) if count else None, flags, _p64(r) if count else None,
+                                                  _p64(s) if count else None, count, out), "zl_groth16_prove_batch")
+        return [_proof_tuple(curve, p) for p in out[:count]]
+
+    def groth16_prove_batch(self, curve: int, pk: dict, r1cs_handle: int, assignments: np.ndarray, r: np.ndarray, s: np.ndarray, flags: int = 0):
+        """zl_groth16_prove_batch: assignments (count, n_variables, 4), r and s (count, 4) -> `count` proofs, proof j what groth16_prove_resident returns for
+        (assignments[j], r[j], s[j]); flags as there."""
+        pkc, keep_pk = _pk_struct(curve, pk)
+        return self._prove_batch(pkc, curve, r1cs_handle, assignments, r, s, flags)
 
     def groth16_last_h(self, n: int) -> np.ndarray:
         out = np.zeros((n, 4), dtype=np.uint64)
@@ -1127,6 +1154,13 @@ class Groth16Keys:
         return (np.array(proof.a[: 2 * nq], dtype=np.uint64), proof.a_inf, np.array(proof.b[: 4 * nq], dtype=np.uint64), proof.b_inf,
                 np.array(proof.c[: 2 * nq], dtype=np.uint64), proof.c_inf), r, s
 
+    def prove_batch(self, assignments: np.ndarray, r: np.ndarray, s: np.ndarray, flags: int = 0, lane: Optional[Backend] = None):
+        """zl_groth16_prove_batch over this key: assignments (count, n_variables, 4) of the keys' circuit, blinding scalars r, s (count, 4) -> `count` proofs.
+        The circuit's matrices are uploaded to the keys' backend on first use (lanes read them there)."""
+        if not getattr(self, "_r1cs", 0):
+            self._r1cs = self.backend.r1cs_upload(self.circuit.curve, self.circuit.arrays())
+        return (lane or self.backend)._prove_batch(self.pk, self.circuit.curve, self._r1cs, assignments, r, s, flags)
+
     def prove_many(self, seeds, circuits=None):
         """zl_groth16_prove_circuits: a stream of proofs over this key on two prover lanes (two host threads inside the library); proofs[i] is what
         prove(seeds[i], circuits[i]) returns.  circuits: None (the keys' own compiler for every proof) or one compiler per seed."""
@@ -1191,6 +1225,9 @@ class Groth16Keys:
         return (bool(ok.value), ev[:count].astype(bool), st[:count]) if each else bool(ok.value)
 
     def close(self):
+        if getattr(self, "_r1cs", 0):
+            self.backend.r1cs_free(self._r1cs)
+            self._r1cs = 0
         if self._k:
             self.L.zl_groth16_keys_free(self._k)
             self._k = C.c_void_p()

@@ -67,8 +67,9 @@ def _units():
         if g == "BlsG1":
             # three waves per SIMD (<= 168 registers): what the accumulation kernel needs anyway (162); without the cap the compiler spreads to 185 = two waves
             extra = extra + ["-DZL_ACC_WAVES=3"]
-        # three units per group: the host side + light kernels, the accumulation kernels, the merge / reduction kernels (zl_msm.hip's header)
-        for part in ("zl_msm", "zl_msm_acc", "zl_msm_tail"):
+        # three units per group: the host side + light kernels, the accumulation kernels, the merge / reduction kernels (zl_msm.hip's header);
+        # a fourth for the multi-vector MSM (zl_msm_multi.hip)
+        for part in ("zl_msm", "zl_msm_acc", "zl_msm_tail", "zl_msm_multi"):
             units.append((f"{part}_{g}", part + ".hip", [f"-DZL_G={g}"] + extra))
     return [u for u in units if os.path.exists(os.path.join(CSRC, u[1]))]
 

@@ -8,6 +8,7 @@
 #include <vector>
 #include "zl_ctx.h"
 #include "zl_pool.h"
+#include "zl_msm_multi_plan.h"
 
 zl_pool& zl_pool_get() {
     static zl_pool pool(std::min(7u, std::max(1u, std::thread::hardware_concurrency()) - 1u));  // + the calling thread
@@ -319,6 +320,17 @@ int zl_msm_dev(zl_ctx* ctx, uint64_t bases, size_t first, const void* d_scalars,
     if (rc) return rc;
     const zl_bases& b = *zl_find_bases(ctx, bases);  // (found by zl_msm_partial_dev above)
     return ZL_DISPATCH(b.curve, b.group, zl_partial_to_affine, partial, out_xy, out_inf);
+}
+// `count` MSMs over one base range in one device pass (zl_msm_multi.hip).  Every check comes before the first launch; the range, pointer and stride
+// checks are zl_mm_check_args (zl_msm_multi_plan.h), repeated by the group's driver.
+int zl_msm_multi_dev(zl_ctx* ctx, uint64_t bases, size_t first, const void* d_scalars, size_t n, size_t stride_scalars, size_t count, uint64_t* out_xy,
+                     uint8_t* out_inf) {
+    if (!ctx) return ZL_EINVAL;
+    const zl_bases* bp = zl_find_bases(ctx, bases);
+    if (!bp) return ZL_EHANDLE;
+    if (zl_mm_check_args(bp->n, first, d_scalars, n, stride_scalars, count, out_xy)) return ZL_EINVAL;
+    ZL_HIP(ctx, hipSetDevice(ctx->device));
+    return ZL_DISPATCH(bp->curve, bp->group, zl_msm_multi_run, ctx, *bp, first, d_scalars, n, stride_scalars, count, out_xy, out_inf);
 }
 // Host scalars (what VariableBaseMSM::multi_scalar_mul is handed: the witness is new for every proof).  One copy followed by one MSM leaves
 // the whole transfer (32 B / point: 12.6 ms for 2^24 from pageable memory) in front of the first kernel.  Large inputs are therefore cut into

@@ -128,6 +128,10 @@ struct zl_scratch {
 //   * ZL_SLOT_PAIR_*: the device product of pairings.
 //   * ZL_SLOT_DECODE_IN / _OUT: the packed records and the decoded points of the device point / proof decoder (zl_decode_dev.hip).  Not the PAIR_* slots:
 //     zl_groth16_verify_batch_bytes runs the decoder and the product of pairings in one call.
+//   * ZL_SLOT_MSM_MULTI: the slice partials and the result staging of one chunk of zl_msm_multi_dev (zl_msm_multi.hip); the chunks of a call follow
+//     each other on ctx->stream.  Its own slot: a caller may hold scalars for it in any other block of the ctx.
+//   * ZL_SLOT_G16_BATCH: one chunk of zl_groth16_prove_batch (zl_groth16.hip): the assignments, the witness map's [3][chunk][N] vectors and the three scalar
+//     matrices its multi-MSMs read; the transforms in between use ZL_SLOT_NTT_VEC, the multi-MSMs ZL_SLOT_MSM_MULTI, one after the other on ctx->stream.
 enum zl_slot : int {
     ZL_SLOT_SET0_COUNTS = 0, ZL_SLOT_SET0_ENTRIES = 1, ZL_SLOT_SET0_BUCKETS = 2, ZL_SLOT_SET0_PARTIALS = 3, ZL_SLOT_SET0_TAIL = 4,
     ZL_SLOT_SORT_A = 5, ZL_SLOT_SORT_B = 6,
@@ -144,7 +148,8 @@ enum zl_slot : int {
     ZL_SLOT_SET3_SORT_A = 33, ZL_SLOT_SET3_SORT_B = 34, ZL_SLOT_SET3_PHI = 35,
     ZL_SLOT_PAIR_IN = 36, ZL_SLOT_PAIR_LINES = 37, ZL_SLOT_PAIR_ACC = 38, ZL_SLOT_PAIR_PREP = 39,
     ZL_SLOT_DECODE_IN = 40, ZL_SLOT_DECODE_OUT = 41,
-    ZL_SLOT_COUNT = 42
+    ZL_SLOT_MSM_MULTI = 42, ZL_SLOT_G16_BATCH = 43,
+    ZL_SLOT_COUNT = 44
 };
 // the slots of MSM buffer set 0..3; sort_a / sort_b are used by a job that owns its sort (side by side), every other job sorts in set 0's pair
 struct zl_msm_set_slots {
@@ -165,7 +170,7 @@ constexpr bool zl_slots_disjoint() {
             owners[x]++;
         }
     for (zl_slot x : {ZL_SLOT_PHI_ONE_KEY, ZL_SLOT_STAGING, ZL_SLOT_GROTH16, ZL_SLOT_TESTHOOK, ZL_SLOT_PAIR_IN, ZL_SLOT_PAIR_LINES, ZL_SLOT_PAIR_ACC, ZL_SLOT_PAIR_PREP,
-                      ZL_SLOT_DECODE_IN, ZL_SLOT_DECODE_OUT}) {
+                      ZL_SLOT_DECODE_IN, ZL_SLOT_DECODE_OUT, ZL_SLOT_MSM_MULTI, ZL_SLOT_G16_BATCH}) {
         if (x < 0 || x >= ZL_SLOT_COUNT) return false;
         owners[x]++;
     }
@@ -339,6 +344,7 @@ inline int zl_scratch_get(zl_ctx* ctx, zl_slot slot, size_t bytes, void** out) {
     int zl_bases_generate_##G(zl_ctx* ctx, const uint64_t* k, size_t n, zl_bases* out);                                     \
     int zl_bases_download_##G(zl_ctx* ctx, const zl_bases& b, size_t first, size_t count, uint64_t* out_xy);                \
     int zl_bases_precompute_##G(zl_ctx* ctx, zl_bases& b, int c);                                                           \
+    int zl_msm_multi_run_##G(zl_ctx* ctx, const zl_bases& b, size_t first, const void* d_scalars, size_t n, size_t stride_scalars, size_t count, uint64_t* out_xy, uint8_t* out_inf); \
     int zl_bases_concat_##G(zl_ctx* ctx, const zl_bases* const* parts, const size_t* first, const size_t* n, size_t count, zl_bases* out);
 ZL_DECL_GROUP(BlsG1)
 ZL_DECL_GROUP(BnG1)

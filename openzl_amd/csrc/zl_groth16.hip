@@ -11,6 +11,7 @@
 // elementwise kernels around zl_ntt_run / zl_msm_run; the window Horner and the final few group operations run on host.
 #include <stdlib.h>
 #include <string.h>
+#include <algorithm>
 #include <array>
 #include <thread>
 #include <vector>
@@ -229,7 +230,22 @@ struct G16KeyCache {
         fold = zl_bases{};
         fold_built = false;
     }
-    ~G16KeyCache() { drop_fold(); }
+    // the three extended queries of zl_groth16_prove_batch (g16_batch_queries below): a | delta1 | alpha1, b2 | delta2 | beta2, l | a | b1 | h | alpha1 | beta1 | delta1
+    zl_bases bq[3];
+    uint64_t bq_handles[5] = {0, 0, 0, 0, 0};
+    size_t bq_nv = 0, bq_nw = 0, bq_nh = 0;
+    bool bq_built = false;
+    static void free_bases(zl_bases& b) {
+        if (b.d_pts) (void)hipFree(b.d_pts);
+        if (b.d_endo) (void)hipFree(b.d_endo);
+        if (b.d_inf) (void)hipFree(b.d_inf);
+        b = zl_bases{};
+    }
+    void drop_batch() {
+        for (zl_bases& b : bq) free_bases(b);
+        bq_built = false;
+    }
+    ~G16KeyCache() { drop_fold(); drop_batch(); }
 };
 template <class G1, class G2>
 static std::vector<uint32_t> g16_key_words(const zl_g16_pk* pk) {
@@ -851,6 +867,310 @@ extern "C" int zl_groth16_prove(zl_ctx* ctx, const zl_g16_pk* pk, const zl_r1cs*
     rc = zl_groth16_prove_resident(ctx, pk, h, assignment, ZL_CANON, r, s, out);
     (void)zl_r1cs_free(ctx, h);
     return rc;
+}
+
+// ---- many proofs over one key in one device pass (zl_groth16_prove_batch) -------------------------------------------------------------------------------------
+// The single small proof is ~16 launches of kernels that occupy a handful of workgroups, three MSMs of a few hundred points and six fixed-base products on host
+// threads.  A batch of witnesses over one key turns every one of those into ONE launch with a batch dimension:
+//   * witness map: a, b, c laid out [3][chunk][N]; the two transform steps are one zl_ntt_run_batch of 3 chunk vectors each, the pointwise step runs over chunk N
+//     elements, the coset inverse is one more batch call;
+//   * the whole proof inside three multi-MSMs (zl_msm_multi.hip) over extended queries cached with the key:
+//       A = <(1, z_1.., r, 1),                      a | delta1 | alpha1>
+//       B = <(1, z_1.., s, 1),                      b2 | delta2 | beta2>
+//       C = <(z_w | s z | r z | h | s | r | r s),   l | a | b1 | h | alpha1 | beta1 | delta1>      (the folded form of C above with its three fixed-base terms inside)
+//     so the host does no point arithmetic and the proofs come back canonical.  Variable 0 enters unscaled as in k_g16_fold_scalars.
+// Batched variants of the matrix-vector products (blockIdx.y = proof): z of proof v at z + v nv, out at out + v N
+template <class FrP>
+__global__ void __launch_bounds__(256) k_r1cs_spmv_batch(const uint32_t* __restrict__ ptr, const uint32_t* __restrict__ col, const Fp<FrP>* __restrict__ val,
+                                                          const Fp<FrP>* __restrict__ z_all, uint32_t nv, uint32_t n_rows, uint32_t tail, uint32_t N,
+                                                          Fp<FrP>* __restrict__ out_all) {
+    using F = Fp<FrP>;
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= N) return;
+    const F* z = z_all + (size_t)blockIdx.y * nv;
+    F acc = F::zero();
+    if (i < n_rows) {
+        for (uint32_t k = ptr[i]; k < ptr[i + 1]; k++) acc = zl::add(acc, zl::mul(val[k], z[col[k]]));
+    } else if (i - n_rows < tail) {
+        acc = z[i - n_rows];
+    }
+    out_all[(size_t)blockIdx.y * N + i] = acc;
+}
+template <class FrP>
+__global__ void __launch_bounds__(256) k_r1cs_spmv8_batch(const uint32_t* __restrict__ ptr, const uint32_t* __restrict__ col, const Fp<FrP>* __restrict__ val,
+                                                           const Fp<FrP>* __restrict__ z_all, uint32_t nv, uint32_t n_rows, uint32_t tail, uint32_t N,
+                                                           Fp<FrP>* __restrict__ out_all) {
+    using F = Fp<FrP>;
+    const uint32_t gt = blockIdx.x * blockDim.x + threadIdx.x;
+    const uint32_t i = gt >> 3, j = gt & 7u;
+    if (i >= N) return;  // (N is a multiple of 32: whole groups leave together)
+    const F* z = z_all + (size_t)blockIdx.y * nv;
+    F acc = F::zero();
+    if (i < n_rows) {
+        const uint32_t e = ptr[i + 1];
+        for (uint32_t k = ptr[i] + j; k < e; k += 8) acc = zl::add(acc, zl::mul(val[k], z[col[k]]));
+    } else if (j == 0 && i - n_rows < tail) {
+        acc = z[i - n_rows];
+    }
+#pragma unroll
+    for (int d = 4; d >= 1; d >>= 1) {
+        F o;
+#pragma unroll
+        for (int w = 0; w < F::N; w++) o.l[w] = (uint32_t)__shfl_xor((int)acc.l[w], d, 8);
+        acc = zl::add(acc, o);
+    }
+    if (j == 0) out_all[(size_t)blockIdx.y * N + i] = acc;
+}
+// The three scalar matrices of a chunk, proof v = blockIdx.y (zc canonical, zm Montgomery, h Montgomery as the coset inverse leaves it; r, s canonical):
+//   sa[v] = (1, z_1.., r, 1)   sb[v] = (1, z_1.., s, 1)   sc[v] = (z_w | s z | r z | h[0 .. N - 1) | s | r | r s)
+template <class FrP>
+__global__ void __launch_bounds__(256) k_g16_batch_scalars(const Fp<FrP>* __restrict__ zc_all, const Fp<FrP>* __restrict__ zm_all, const Fp<FrP>* __restrict__ h_all,
+                                                            const Fp<FrP>* __restrict__ r_all, const Fp<FrP>* __restrict__ s_all, uint32_t ni, uint32_t nv, uint32_t N,
+                                                            Fp<FrP>* __restrict__ sa_all, Fp<FrP>* __restrict__ sb_all, Fp<FrP>* __restrict__ sc_all) {
+    using F = Fp<FrP>;
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x, v = blockIdx.y;
+    const uint32_t nw = nv - ni, na = nv + 2, nc = nw + 2 * nv + (N - 1) + 3;
+    const F r = r_all[v], s = s_all[v];
+    F* sa = sa_all + (size_t)v * na;
+    F* sb = sb_all + (size_t)v * na;
+    F* sc = sc_all + (size_t)v * nc;
+    const F one = zl::from_mont(F::one());
+    if (i < nv) {
+        const F c = zc_all[(size_t)v * nv + i], m = zm_all[(size_t)v * nv + i];
+        sa[i] = i ? c : one;
+        sb[i] = i ? c : one;
+        sc[nw + i] = i ? zl::mul(m, s) : s;        // (z R) s / R = z s, canonical
+        sc[nw + nv + i] = i ? zl::mul(m, r) : r;
+        if (i >= ni) sc[i - ni] = c;
+    }
+    if (i < N - 1) sc[nw + 2 * nv + i] = zl::from_mont(h_all[(size_t)v * N + i]);
+    if (i == 0) {
+        sa[nv] = r; sa[nv + 1] = one;
+        sb[nv] = s; sb[nv + 1] = one;
+        F* t = sc + nw + 2 * nv + (N - 1);
+        t[0] = s; t[1] = r;
+        t[2] = zl::mul(zl::to_mont(r), s);         // (r R) s / R = r s, canonical
+    }
+}
+
+// The three extended queries of a key, cached in its G16KeyCache.  They are built OUTSIDE zl_bases_cache_mutex (uploads, device copies and two synchronisations:
+// a lane that proves over another key must not wait for them) and installed under it; when two lanes build them for one key at once, the second one's are dropped.
+template <class G1, class G2>
+static int g16_batch_queries(zl_ctx* ctx, const zl_g16_pk* pk, const zl_bases* const* bs, size_t nv, size_t nw, size_t nh, std::shared_ptr<G16KeyCache<G1, G2>>* out) {
+    using KC = G16KeyCache<G1, G2>;
+    std::shared_ptr<KC> kc;
+    int rc = g16_key_cache<G1, G2>(ctx, pk, bs, false, nv, nw, nh, &kc);
+    if (rc) return rc;
+    const uint64_t hs[5] = {pk->a_query, pk->b_g1_query, pk->h_query, pk->l_query, pk->b_g2_query};
+    auto fits = [&](const KC& k) { return k.bq_built && k.bq_nv == nv && k.bq_nw == nw && k.bq_nh == nh && !memcmp(k.bq_handles, hs, sizeof hs); };
+    {
+        std::lock_guard<std::mutex> lk(zl_bases_cache_mutex());
+        if (fits(*kc)) { *out = kc; return ZL_OK; }
+    }
+    constexpr size_t W1 = 2 * FieldIO<typename G1::F>::WORDS, W2 = 2 * FieldIO<typename G2::F>::WORDS;
+    std::vector<uint32_t> fx1(3 * W1), fx2(2 * W2);  // delta1 | alpha1 | beta1 and delta2 | beta2, canonical
+    memcpy(&fx1[0], pk->delta_g1, W1 * 4);
+    memcpy(&fx1[W1], pk->alpha_g1, W1 * 4);
+    memcpy(&fx1[2 * W1], pk->beta_g1, W1 * 4);
+    memcpy(&fx2[0], pk->delta_g2, W2 * 4);
+    memcpy(&fx2[W2], pk->beta_g2, W2 * 4);
+    zl_bases t1, t2, q[3];
+    rc = ZL_DISPATCH(pk->curve, ZL_G1, zl_bases_upload, ctx, fx1.data(), 3, 0, -1, 0, &t1);
+    if (!rc) rc = ZL_DISPATCH(pk->curve, ZL_G2, zl_bases_upload, ctx, fx2.data(), 2, 0, -1, 0, &t2);
+    if (!rc) {
+        const zl_bases* parts[3] = {bs[0], &t1, &t1};
+        const size_t first[3] = {0, 0, 1}, n[3] = {nv, 1, 1};
+        rc = ZL_DISPATCH(pk->curve, ZL_G1, zl_bases_concat, ctx, parts, first, n, 3, &q[0]);
+    }
+    if (!rc) {
+        const zl_bases* parts[3] = {bs[4], &t2, &t2};
+        const size_t first[3] = {0, 0, 1}, n[3] = {nv, 1, 1};
+        rc = ZL_DISPATCH(pk->curve, ZL_G2, zl_bases_concat, ctx, parts, first, n, 3, &q[1]);
+    }
+    if (!rc) {
+        const zl_bases* parts[7] = {bs[3], bs[0], bs[1], bs[2], &t1, &t1, &t1};
+        const size_t first[7] = {0, 0, 0, 0, 1, 2, 0}, n[7] = {nw, nv, nv, nh, 1, 1, 1};
+        rc = ZL_DISPATCH(pk->curve, ZL_G1, zl_bases_concat, ctx, parts, first, n, 7, &q[2]);
+    }
+    KC::free_bases(t1);
+    KC::free_bases(t2);
+    if (rc) {
+        for (zl_bases& b : q) KC::free_bases(b);
+        return rc;
+    }
+    for (int i = 0; i < 3; i++) { q[i].curve = (int)pk->curve; q[i].group = i == 1 ? ZL_G2 : ZL_G1; }
+    std::lock_guard<std::mutex> lk(zl_bases_cache_mutex());
+    {   // (a folded proof on another lane may have put a fresh cache object in place meanwhile)
+        std::shared_ptr<KC> now = std::static_pointer_cast<KC>(bs[3]->g16_cache);
+        if (now && now->key_words == kc->key_words) kc = now;
+    }
+    if (fits(*kc)) {
+        for (zl_bases& b : q) KC::free_bases(b);
+    } else if (kc->bq_built && kc.use_count() > 2) {
+        // another lane still proves with the queries of another shape: keep them with their object, hang ours on a fresh one
+        auto fresh = std::make_shared<KC>();
+        fresh->key_words = kc->key_words;
+        fresh->alpha1 = kc->alpha1;
+        fresh->beta1 = kc->beta1;
+        fresh->delta1 = kc->delta1;
+        fresh->delta2 = kc->delta2;
+        kc = fresh;
+        bs[3]->g16_cache = kc;
+    }
+    if (!fits(*kc)) {
+        kc->drop_batch();
+        for (int i = 0; i < 3; i++) kc->bq[i] = q[i];
+        memcpy(kc->bq_handles, hs, sizeof hs);
+        kc->bq_nv = nv;
+        kc->bq_nw = nw;
+        kc->bq_nh = nh;
+        kc->bq_built = true;
+    }
+    *out = kc;
+    return ZL_OK;
+}
+
+// Dispatch bounds, from the interleaved measurement against the zl_groth16_prove_circuits stream (profiles/prove_batch_bench.log; worst pairing of repetitions):
+// domain 2^8 (235 constraints) 1.70x / 6.99x / 8.57x at 64 / 1 024 / 16 384 proofs on BLS12-381, 2.32x / 9.57x / 11.8x on BN254; domain 2^11 (1 873) 1.37x / 2.94x
+// and 1.14x / 4.00x at 64 / 1 024; domain 2^14 (14 977) 0.75 - 0.82x: a loss.  Nothing was measured between 2^11 and 2^14 or below 64 proofs, so the bounds stop there.
+#define ZL_G16_BATCH_LOG_N 11  // largest domain (log2) whose batches stay on the device (ZL_TUNE_G16_BATCH_LOG_N)
+#define ZL_G16_BATCH_MIN 64    // ... from this many proofs on (ZL_TUNE_G16_BATCH_MIN)
+#define ZL_G16_BATCH_BUDGET ((size_t)512 << 20)  // bytes of ZL_SLOT_G16_BATCH a chunk may take
+
+template <class G1, class G2>
+static int groth16_prove_batch_dev_t(zl_ctx* ctx, const zl_g16_pk* pk, const zl_r1cs_dev* cs, const zl_bases* const* bs, unsigned log_n, const uint64_t* assignments,
+                                     unsigned flags, const uint64_t* r, const uint64_t* s, size_t count, zl_g16_proof* proofs) {
+    using FrP = typename G1::FrP;
+    using Fr = Fp<FrP>;
+    const uint32_t nc = cs->n_constraints, ni = cs->n_instance, nw = cs->n_witness, nv = ni + nw, N = 1u << log_n;
+    std::shared_ptr<G16KeyCache<G1, G2>> kc;
+    int rc = g16_batch_queries<G1, G2>(ctx, pk, bs, nv, nw, (size_t)N - 1, &kc);
+    if (rc) return rc;
+    const size_t na = (size_t)nv + 2, ncs = (size_t)nw + 2 * (size_t)nv + (N - 1) + 3;
+    // per proof: z canonical + Montgomery, a | b | c, r, s, the three scalar rows
+    const size_t per = ((size_t)2 * nv + (size_t)3 * N + 2 + 2 * na + ncs) * 32;
+    size_t chunk = std::max<size_t>(1, ZL_G16_BATCH_BUDGET / per);
+    const int forced = zl_tune("ZL_TUNE_G16_BATCH_CHUNK", 0);
+    if (forced > 0) chunk = (size_t)forced;
+    chunk = std::min(std::min(chunk, count), std::min<size_t>(65535 / 3, (size_t)0x7fffffffu / std::max<size_t>(N, ncs)));  // three vectors per proof in one transform call; 32-bit element counts
+    if (chunk < 1) return ZL_EINVAL;
+    void* base;
+    if ((rc = zl_scratch_get(ctx, ZL_SLOT_G16_BATCH, chunk * per + 256, &base))) return rc;
+    Fr* d_zc = reinterpret_cast<Fr*>(base);
+    Fr* d_zm = d_zc + chunk * nv;
+    Fr* d_abc = d_zm + chunk * nv;  // [3][ch][N] for the ch proofs of the chunk in flight
+    Fr* d_r = d_abc + chunk * 3 * N;
+    Fr* d_s = d_r + chunk;
+    Fr* d_sa = d_s + chunk;
+    Fr* d_sb = d_sa + chunk * na;
+    Fr* d_sc = d_sb + chunk * na;
+    const unsigned char* dm = reinterpret_cast<const unsigned char*>(cs->d_base);
+    hipStream_t st = ctx->stream;
+    ctx->g16_h = nullptr;  // no single quotient to hand out after a batch
+    ctx->g16_h_n = 0;
+    const int timing_saved = ctx->timing_on;
+    ctx->timing_on = 0;  // the inner calls must not record into the ctx's events
+    Fr g;
+    for (int i = 0; i < Fr::N; i++) g.l[i] = FrP::generator(i);
+    Fr gN = g;
+    for (unsigned i = 0; i < log_n; i++) gN = zl::sqr(gN);
+    const Fr zinv = zl::inv(zl::sub(gN, Fr::one()));
+    constexpr size_t W1 = FieldIO<typename G1::F>::WORDS, W2 = FieldIO<typename G2::F>::WORDS;  // u64 words of a canonical G1 / G2 point (2 coordinates of WORDS u32)
+    std::vector<uint64_t> xa(chunk * W1), xb(chunk * W2), xc(chunk * W1);
+    std::vector<uint8_t> ia(chunk), ib(chunk), ic(chunk);
+    auto body = [&]() -> int {
+        for (size_t c0 = 0; c0 < count; c0 += chunk) {
+            const uint32_t ch = (uint32_t)std::min(chunk, count - c0);
+            const uint32_t tot_z = ch * nv;
+            Fr* d_in = (flags & ZL_MONT) ? d_zm : d_zc;
+            ZL_HIP(ctx, hipMemcpyAsync(d_in, assignments + c0 * (size_t)nv * 4, (size_t)tot_z * 32, hipMemcpyHostToDevice, st));
+            ZL_HIP(ctx, hipMemcpyAsync(d_r, r + c0 * 4, (size_t)ch * 32, hipMemcpyHostToDevice, st));
+            ZL_HIP(ctx, hipMemcpyAsync(d_s, s + c0 * 4, (size_t)ch * 32, hipMemcpyHostToDevice, st));
+            if (flags & ZL_MONT) {
+                hipLaunchKernelGGL((k_fr_from_mont<FrP>), dim3((tot_z + 255) / 256), dim3(256), 0, st, d_zm, d_zc, tot_z);
+            } else {
+                ZL_HIP(ctx, hipMemcpyAsync(d_zm, d_zc, (size_t)tot_z * 32, hipMemcpyDeviceToDevice, st));
+                hipLaunchKernelGGL((k_fr_to_mont<FrP>), dim3((tot_z + 255) / 256), dim3(256), 0, st, d_zm, tot_z);
+            }
+            for (int m = 0; m < 3; m++) {
+                Fr* out = d_abc + (size_t)m * ch * N;
+                if (cs->nnz[m] >= (size_t)4 * nc && zl_tune("ZL_TUNE_SPMV8", 1))
+                    hipLaunchKernelGGL((k_r1cs_spmv8_batch<FrP>), dim3((uint32_t)(((uint64_t)N * 8 + 255) / 256), ch), dim3(256), 0, st, (const uint32_t*)(dm + cs->off_ptr[m]),
+                                       (const uint32_t*)(dm + cs->off_col[m]), (const Fr*)(dm + cs->off_val[m]), d_zm, nv, nc, m == 0 ? ni : 0u, N, out);
+                else
+                    hipLaunchKernelGGL((k_r1cs_spmv_batch<FrP>), dim3((N + 255) / 256, ch), dim3(256), 0, st, (const uint32_t*)(dm + cs->off_ptr[m]),
+                                       (const uint32_t*)(dm + cs->off_col[m]), (const Fr*)(dm + cs->off_val[m]), d_zm, nv, nc, m == 0 ? ni : 0u, N, out);
+            }
+            ZL_HIP(ctx, hipGetLastError());
+            int e;
+            if ((e = zl_ntt_run_batch(ctx, pk->curve, d_abc, log_n, ZL_MONT | ZL_INVERSE, 3 * ch, (size_t)N * 32))) return e;
+            if ((e = zl_ntt_run_batch(ctx, pk->curve, d_abc, log_n, ZL_MONT | ZL_COSET, 3 * ch, (size_t)N * 32))) return e;
+            const uint32_t tot_n = ch * N;
+            hipLaunchKernelGGL((k_qap_pointwise<FrP>), dim3((tot_n + 255) / 256), dim3(256), 0, st, d_abc, d_abc + (size_t)tot_n, d_abc + 2 * (size_t)tot_n, zinv, tot_n);
+            ZL_HIP(ctx, hipGetLastError());
+            if ((e = zl_ntt_run_batch(ctx, pk->curve, d_abc, log_n, ZL_MONT | ZL_INVERSE | ZL_COSET, ch, (size_t)N * 32))) return e;
+            hipLaunchKernelGGL((k_g16_batch_scalars<FrP>), dim3((std::max(nv, N) + 255) / 256, ch), dim3(256), 0, st, d_zc, d_zm, d_abc, d_r, d_s, ni, nv, N, d_sa, d_sb, d_sc);
+            ZL_HIP(ctx, hipGetLastError());
+            if ((e = ZL_DISPATCH(pk->curve, ZL_G1, zl_msm_multi_run, ctx, kc->bq[0], 0, d_sa, na, na, ch, xa.data(), ia.data()))) return e;
+            if ((e = ZL_DISPATCH(pk->curve, ZL_G2, zl_msm_multi_run, ctx, kc->bq[1], 0, d_sb, na, na, ch, xb.data(), ib.data()))) return e;
+            if ((e = ZL_DISPATCH(pk->curve, ZL_G1, zl_msm_multi_run, ctx, kc->bq[2], 0, d_sc, ncs, ncs, ch, xc.data(), ic.data()))) return e;
+            for (uint32_t j = 0; j < ch; j++) {
+                zl_g16_proof* p = proofs + c0 + j;
+                memset(p, 0, sizeof *p);
+                memcpy(p->a, &xa[j * W1], W1 * 8);
+                memcpy(p->b, &xb[j * W2], W2 * 8);
+                memcpy(p->c, &xc[j * W1], W1 * 8);
+                p->a_inf = ia[j];
+                p->b_inf = ib[j];
+                p->c_inf = ic[j];
+            }
+        }
+        return ZL_OK;
+    };
+    rc = body();
+    if (rc) (void)hipStreamSynchronize(st);  // nothing of the batch may still be running when the caller sees the error
+    ctx->timing_on = timing_saved;
+    return rc;
+}
+
+template <class G1, class G2>
+static int groth16_prove_batch_t(zl_ctx* ctx, const zl_g16_pk* pk, const zl_r1cs_dev* cs, const uint64_t* assignments, unsigned flags, const uint64_t* r,
+                                 const uint64_t* s, size_t count, zl_g16_proof* proofs) {
+    using FrP = typename G1::FrP;
+    // the resident prover's checks, in its order, so that both paths answer a bad key alike
+    const uint32_t nc = cs->n_constraints, ni = cs->n_instance, nw = cs->n_witness;
+    const uint64_t nv64 = (uint64_t)ni + nw;
+    if (ni < 1 || nv64 >= (1ull << 31)) return ZL_EINVAL;
+    const size_t nv = (size_t)nv64;
+    unsigned log_n = 1;
+    while ((1ull << log_n) < (uint64_t)nc + ni) log_n++;
+    if (log_n > (unsigned)FrP::TWO_ADICITY || log_n > 28) return ZL_EINVAL;
+    const uint64_t hs[5] = {pk->a_query, pk->b_g1_query, pk->h_query, pk->l_query, pk->b_g2_query};
+    const zl_bases* bs[5];
+    for (int i = 0; i < 5; i++) {
+        bs[i] = zl_find_bases(ctx, hs[i]);
+        if (!bs[i] || bs[i]->curve != (int)pk->curve || bs[i]->group != (i == 4 ? ZL_G2 : ZL_G1)) return ZL_EHANDLE;
+    }
+    if (bs[0]->n < nv || bs[1]->n < nv || bs[4]->n < nv || bs[2]->n < ((size_t)1 << log_n) - 1 || bs[3]->n < nw) return ZL_EINVAL;
+    if (log_n <= (unsigned)zl_tune("ZL_TUNE_G16_BATCH_LOG_N", ZL_G16_BATCH_LOG_N) && count >= (size_t)std::max(1, zl_tune("ZL_TUNE_G16_BATCH_MIN", ZL_G16_BATCH_MIN)))
+        return groth16_prove_batch_dev_t<G1, G2>(ctx, pk, cs, bs, log_n, assignments, flags, r, s, count, proofs);
+    for (size_t j = 0; j < count; j++) {
+        const int rc = groth16_prove_t<G1, G2>(ctx, pk, cs, assignments + j * nv * 4, flags, r + 4 * j, s + 4 * j, proofs + j);
+        if (rc) return rc;
+    }
+    return ZL_OK;
+}
+extern "C" int zl_groth16_prove_batch(zl_ctx* ctx, const zl_g16_pk* pk, uint64_t r1cs_handle, const uint64_t* assignments, unsigned flags, const uint64_t* r,
+                                      const uint64_t* s, size_t count, zl_g16_proof* proofs) {
+    if (!ctx || !pk || (flags & ~ZL_MONT) || (count && (!assignments || !r || !s || !proofs))) return ZL_EINVAL;
+    if (!pk->alpha_g1 || !pk->beta_g1 || !pk->delta_g1 || !pk->beta_g2 || !pk->delta_g2) return ZL_EINVAL;
+    const zl_r1cs_dev* rd = zl_find_r1cs(ctx, r1cs_handle);
+    if (!rd || rd->curve != (int)pk->curve) return ZL_EHANDLE;
+    if (count == 0) return ZL_OK;
+    ZL_HIP(ctx, hipSetDevice(ctx->device));
+    if (pk->curve == ZL_BLS12_381) return groth16_prove_batch_t<BlsG1, BlsG2>(ctx, pk, rd, assignments, flags, r, s, count, proofs);
+    if (pk->curve == ZL_BN254) return groth16_prove_batch_t<BnG1, BnG2>(ctx, pk, rd, assignments, flags, r, s, count, proofs);
+    return ZL_EINVAL;
 }
 extern "C" int zl_groth16_last_h(zl_ctx* ctx, uint64_t* out, size_t n) {
     if (!ctx || !out || !ctx->g16_h || n > ctx->g16_h_n) return ZL_EINVAL;

@@ -1,0 +1,18 @@
+"""Sanitizer leg of zl_msm_multi_dev, host only: the argument checks and the chunk planner (csrc/zl_msm_multi_plan.h) in a stand-alone program built with
+AddressSanitizer and UndefinedBehaviorSanitizer (tests/c/msm_multi_host.cpp).  No device, no library, nothing loaded into this process."""
+import os
+import subprocess
+
+from openzl_amd import build as zb
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+
+
+def test_msm_multi_host_side_under_sanitizers(tmp_path):
+    exe = tmp_path / "msm_multi_host"
+    cxx = os.path.join(zb._LLVM, "clang++")  # the host compiler beside hipcc: the program holds no device code
+    san = ["-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-fno-omit-frame-pointer"]
+    subprocess.check_call([cxx, "-std=c++17", "-O1", "-g", "-Wall", "-Werror"] + san +
+                          ["-I", os.path.join(ROOT, "openzl_amd", "csrc"), os.path.join(ROOT, "tests", "c", "msm_multi_host.cpp"), "-o", str(exe)])
+    out = subprocess.run([str(exe)], capture_output=True, text=True, timeout=300)
+    assert out.returncode == 0 and "msm_multi_host: OK" in out.stdout, (out.stdout, out.stderr)
