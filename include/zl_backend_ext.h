@@ -153,6 +153,15 @@ int zl_pairing(zl_curve_t curve, const uint64_t* p_xy, const uint64_t* q_xy, uin
  * qs_xy: n G2 points (x.c0||x.c1||y.c0||y.c1); all-zero = infinity, contributes 1.  Miller loops on the device, final exponentiation on the host.
  * ZL_ENOTCURVE when the Miller product is zero (inputs outside the pairing groups), as zl_pairing. */
 int zl_pairing_product(zl_ctx* ctx, zl_curve_t curve, const uint64_t* ps_xy, const uint64_t* qs_xy, size_t n, uint64_t* out12);
+/* `count` INDEPENDENT products of `pairs_each` pairings each, Miller loops AND final exponentiations on the device: what a caller of the plugin's
+ * PairingEngineExt::same / same_ratio (plugins/arkworks/src/pairing.rs:47-90, ratio.rs:102-113) needs when it checks many ratios at once.  Product j runs
+ * over pairs [j * pairs_each, (j + 1) * pairs_each) of ps_xy / qs_xy (layouts of zl_pairing_product); out12 + j * 12 Fq receives exactly what
+ * zl_pairing_product returns for those pairs.  status (optional, count entries): ZL_OK, or ZL_ENOTCURVE for a zero Miller product (inputs outside the
+ * pairing groups; the value is then zero).  A bad product is data, not a failure: the call returns ZL_OK once the batch is processed.  count == 0: ZL_OK,
+ * nothing is written.  pairs_each == 0: every result is one.  pairs_each above 65 536 (the pairs of one device launch set): ZL_EINVAL, before any work.
+ * The products are laid out over launch sets of floor(65 536 / pairs_each) products (fewer when ZL_TUNE_FEXP_CHUNK is set: a test knob). */
+int zl_pairing_products(zl_ctx* ctx, zl_curve_t curve, const uint64_t* ps_xy, const uint64_t* qs_xy, size_t count, size_t pairs_each, uint64_t* out12,
+                        int32_t* status);
 /* Groth16::verify for `count` proofs against one key in one random linear combination:
  *   prod_i e(rho_i A_i, B_i) * e(-sum_i rho_i C_i, delta) * e(-sum_i rho_i IC_i, gamma) * e(-(sum_i rho_i) alpha, beta) == 1,
  * IC_i = gamma_abc[0] + sum_j x_ij gamma_abc[j+1], so the last three pairs are shared by the whole batch (count + 3 Miller loops, one final exponentiation).

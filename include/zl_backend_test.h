@@ -114,6 +114,13 @@ int zl_test_pairing_product(zl_curve_t curve, size_t n, const uint64_t* ps_xy, c
 int zl_test_miller_dev(zl_ctx* ctx, zl_curve_t curve, size_t n, const uint64_t* ps_xy, const uint64_t* qs_xy, uint64_t* out);
 /* The host Engine::final_exp of 12 canonical coefficients (in12 -> out12); ZL_ENOTCURVE for a zero input. */
 int zl_test_final_exp(zl_curve_t curve, const uint64_t* in12, uint64_t* out12);
+/* The device final exponentiation (k_pd_fexp of openzl_amd/csrc/zl_pairing_dev.hip) of `count` values, canonical coefficients in and out as
+ * zl_test_final_exp takes them (count x 12 Fq); singular (optional, count bytes): 1 for a zero input, whose result is zero.  ZL_TUNE_FEXP_CHUNK values per launch. */
+int zl_test_final_exp_dev(zl_ctx* ctx, zl_curve_t curve, size_t count, const uint64_t* in, uint64_t* out, uint8_t* singular);
+/* The inverse in Fq12 by the norm chain of openzl_amd/csrc/zl_fq12_inv.h, run on the host (the kernel takes the same steps, one coefficient per lane): 12
+ * canonical coefficients in and out; *singular = 1 and an all-zero result for a zero input.  zl_test_fq12_zeta: the chain's cube root of unity in Fq, canonical. */
+int zl_test_fq12_inverse(zl_curve_t curve, const uint64_t* in12, uint64_t* out12, uint8_t* singular);
+int zl_test_fq12_zeta(zl_curve_t curve, uint64_t* out);
 /* zl_groth16_verify_batch's random linear combination computed entirely on the host (lock-step Engine::multi_pairing, host scalar multiplications), against
  * a verifying key given as points: alpha_g1 (x||y), beta_g2 / gamma_g2 / delta_g2 (x.c0||x.c1||y.c0||y.c1), gamma_abc (n_public + 1 G1 points).  Same rho
  * derivation, rules and outputs as zl_groth16_verify_batch. */

@@ -34,6 +34,7 @@ ABI_SYMBOLS = [
     "zl_point_bytes_uncompressed", "zl_point_to_bytes_uncompressed", "zl_point_from_bytes_uncompressed", "zl_groth16_keys_to_bytes", "zl_groth16_keys_from_bytes", "zl_groth16_keys_parse",
     "zl_groth16_vk_to_bytes", "zl_pairing_product", "zl_groth16_verify_batch",
     "zl_points_from_bytes_batch", "zl_groth16_proofs_from_bytes_batch", "zl_groth16_verify_batch_bytes", "zl_msm_multi_dev", "zl_groth16_prove_batch",
+    "zl_pairing_products",
 ]
 
 
@@ -136,6 +137,7 @@ def load_library(path: Optional[str] = None):
     L.zl_groth16_verify.argtypes = [vp, u64p, C.c_size_t, C.POINTER(G16ProofC), C.POINTER(C.c_int)]
     L.zl_pairing.argtypes = [C.c_int, u64p, u64p, u64p]
     L.zl_pairing_product.argtypes = [vp, C.c_int, u64p, u64p, C.c_size_t, u64p]
+    L.zl_pairing_products.argtypes = [vp, C.c_int, u64p, u64p, C.c_size_t, C.c_size_t, u64p, i32p]
     L.zl_groth16_verify_batch.argtypes = [vp, vp, u64p, C.c_size_t, C.POINTER(G16ProofC), C.c_size_t, u64p, C.POINTER(C.c_int), u8p]
     L.zl_points_from_bytes_batch.argtypes = [vp, C.c_int, C.c_int, vp, C.c_size_t, u64p, u8p, i32p]
     L.zl_groth16_proofs_from_bytes_batch.argtypes = [vp, C.c_int, vp, C.c_size_t, C.POINTER(G16ProofC), i32p]
@@ -175,6 +177,9 @@ def load_library(path: Optional[str] = None):
     L.zl_test_pairing_product.argtypes = [C.c_int, C.c_size_t, u64p, u64p, u64p]
     L.zl_test_miller_dev.argtypes = [vp, C.c_int, C.c_size_t, u64p, u64p, u64p]
     L.zl_test_final_exp.argtypes = [C.c_int, u64p, u64p]
+    L.zl_test_final_exp_dev.argtypes = [vp, C.c_int, C.c_size_t, u64p, u64p, u8p]
+    L.zl_test_fq12_inverse.argtypes = [C.c_int, u64p, u64p, u8p]
+    L.zl_test_fq12_zeta.argtypes = [C.c_int, u64p]
     L.zl_test_verify_batch_host.argtypes = [C.c_int, u64p, u64p, u64p, u64p, u64p, C.c_size_t, C.POINTER(G16ProofC), u64p, C.c_size_t, u64p,
                                             C.POINTER(C.c_int), u8p]
     L.zl_test_point_op.argtypes = [vp, C.c_int, C.c_int, C.c_int, u32p, C.c_size_t, u32p]
@@ -303,6 +308,23 @@ class Backend:
         out = np.zeros((12, nq), dtype=np.uint64)
         self._check(self.L.zl_pairing_product(self._ctx, curve, _p64(p), _p64(q), n, _p64(out)), "zl_pairing_product")
         return out
+
+    def pairing_products(self, curve: int, ps: np.ndarray, qs: np.ndarray, pairs_each: int, count: Optional[int] = None):
+        """zl_pairing_products: `count` independent products of `pairs_each` pairings, Miller loops and final exponentiations on the device.  ps / qs as
+        pairing_product, product j over pairs [j pairs_each, (j + 1) pairs_each); count defaults to what ps holds.  Returns (values (count, 12, FQ64) canonical
+        words -- row j is pairing_product of product j's pairs --, status (count,) int32: 0 or ZL_ENOTCURVE for a zero Miller product)."""
+        nq = FQ_LIMBS[curve]
+        p = np.ascontiguousarray(np.asarray(ps, dtype=np.uint64).reshape(-1, 2 * nq))
+        q = np.ascontiguousarray(np.asarray(qs, dtype=np.uint64).reshape(-1, 4 * nq))
+        if count is None:
+            count = p.shape[0] // pairs_each if pairs_each else 0
+        assert p.shape[0] == q.shape[0] and p.shape[0] >= count * pairs_each
+        if p.shape[0] == 0:
+            p, q = np.zeros((1, 2 * nq), dtype=np.uint64), np.zeros((1, 4 * nq), dtype=np.uint64)
+        out = np.zeros((max(1, count), 12, nq), dtype=np.uint64)
+        status = np.zeros(max(1, count), dtype=np.int32)
+        self._check(self.L.zl_pairing_products(self._ctx, curve, _p64(p), _p64(q), count, pairs_each, _p64(out), status.ctypes.data_as(i32p)), "zl_pairing_products")
+        return out[:count], status[:count]
 
     def points_from_bytes(self, curve: int, group: int, data, count: int, offset: int = 0):
         """zl_points_from_bytes_batch: `count` compressed points decoded on the device (square roots, sign rule, subgroup check), one lane per point.
@@ -656,7 +678,8 @@ class MultiBackend:
 TEST_ABI_SYMBOLS = ["zl_test_poseidon_permute_dev", "zl_test_fp28_op", "zl_test_fp28_bn_op", "zl_test_pairing_product", "zl_test_point_op", "zl_test_circuit_tweak", "zl_test_fq_mul_rate", "zl_test_fr28_op", "zl_test_fr29_op",
                     "zl_test_poseidon_permute_dev28r", "zl_test_fq_mul_clock", "zl_test_acc_clock", "zl_test_acc_clock_read", "zl_test_clock_probe_launch", "zl_test_clock_probe_read",
                     "zl_test_miller_dev", "zl_test_final_exp", "zl_test_verify_batch_host", "zl_test_ntt_plan", "zl_test_ntt_fit_beside", "zl_test_fp2pair_op", "zl_test_point_form_op",
-                    "zl_test_endo_split", "zl_test_endo_split_inf", "zl_test_decode_points_host", "zl_test_fq2_sqrt"]
+                    "zl_test_endo_split", "zl_test_endo_split_inf", "zl_test_decode_points_host", "zl_test_fq2_sqrt",
+                    "zl_test_final_exp_dev", "zl_test_fq12_inverse", "zl_test_fq12_zeta"]
 
 
 def _p32(a: np.ndarray):
@@ -767,6 +790,37 @@ def hook_final_exp(curve: int, f: np.ndarray) -> np.ndarray:
     rc = load_library().zl_test_final_exp(curve, _p64(a), _p64(out))
     if rc:
         raise BackendError(rc, "zl_test_final_exp")
+    return out
+
+
+def hook_final_exp_dev(be: "Backend", curve: int, f: np.ndarray):
+    """the device final exponentiation (zl_test_final_exp_dev) of (count, 12, FQ64) canonical values -> (values of the same shape, singular (count,) uint8)"""
+    a = np.ascontiguousarray(np.asarray(f, dtype=np.uint64).reshape(-1, 12, FQ_LIMBS[curve]))
+    out = np.zeros_like(a)
+    sing = np.zeros(max(1, a.shape[0]), dtype=np.uint8)
+    be._check(be.L.zl_test_final_exp_dev(be._ctx, curve, a.shape[0], _p64(a if a.size else np.zeros(1, dtype=np.uint64)),
+                                         _p64(out if out.size else np.zeros(1, dtype=np.uint64)), sing.ctypes.data_as(u8p)), "zl_test_final_exp_dev")
+    return out, sing[:a.shape[0]]
+
+
+def hook_fq12_inverse(curve: int, f: np.ndarray):
+    """the inverse in Fq12 by the norm chain the device final exponentiation uses, on the host (zl_test_fq12_inverse): 12 canonical coefficients ->
+    (12 canonical coefficients, singular)"""
+    a = np.ascontiguousarray(np.asarray(f, dtype=np.uint64).reshape(12, FQ_LIMBS[curve]))
+    out = np.zeros_like(a)
+    sing = np.zeros(1, dtype=np.uint8)
+    rc = load_library().zl_test_fq12_inverse(curve, _p64(a), _p64(out), sing.ctypes.data_as(u8p))
+    if rc:
+        raise BackendError(rc, "zl_test_fq12_inverse")
+    return out, bool(sing[0])
+
+
+def hook_fq12_zeta(curve: int) -> np.ndarray:
+    """the cube root of unity in Fq of the inverse chain (zl_test_fq12_zeta), canonical words"""
+    out = np.zeros(FQ_LIMBS[curve], dtype=np.uint64)
+    rc = load_library().zl_test_fq12_zeta(curve, _p64(out))
+    if rc:
+        raise BackendError(rc, "zl_test_fq12_zeta")
     return out
 
 

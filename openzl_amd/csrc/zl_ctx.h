@@ -125,7 +125,8 @@ struct zl_scratch {
 //     resize the blocks (a proof's transforms run on ctx->aux2, whose slots are its own).
 //   * ZL_SLOT_STAGING: host scalars / vectors uploaded for one call.  ZL_SLOT_GROTH16: the witness map's vectors (the quotient of the last
 //     proof stays there, zl_ctx::g16_h).  ZL_SLOT_TESTHOOK: inputs and outputs of the test hooks.
-//   * ZL_SLOT_PAIR_*: the device product of pairings.
+//   * ZL_SLOT_PAIR_*: the device product of pairings.  ZL_SLOT_PAIR_FEXP: the device final exponentiations (zl_pairing_dev.hip fexp): exponent words, values,
+//     flags and the window powers of one launch.  Its own slot: it reads the Miller values of a groups launch out of ZL_SLOT_PAIR_ACC on the same stream.
 //   * ZL_SLOT_DECODE_IN / _OUT: the packed records and the decoded points of the device point / proof decoder (zl_decode_dev.hip).  Not the PAIR_* slots:
 //     zl_groth16_verify_batch_bytes runs the decoder and the product of pairings in one call.
 //   * ZL_SLOT_MSM_MULTI: the slice partials and the result staging of one chunk of zl_msm_multi_dev (zl_msm_multi.hip); the chunks of a call follow
@@ -149,7 +150,8 @@ enum zl_slot : int {
     ZL_SLOT_PAIR_IN = 36, ZL_SLOT_PAIR_LINES = 37, ZL_SLOT_PAIR_ACC = 38, ZL_SLOT_PAIR_PREP = 39,
     ZL_SLOT_DECODE_IN = 40, ZL_SLOT_DECODE_OUT = 41,
     ZL_SLOT_MSM_MULTI = 42, ZL_SLOT_G16_BATCH = 43,
-    ZL_SLOT_COUNT = 44
+    ZL_SLOT_PAIR_FEXP = 44,
+    ZL_SLOT_COUNT = 45
 };
 // the slots of MSM buffer set 0..3; sort_a / sort_b are used by a job that owns its sort (side by side), every other job sorts in set 0's pair
 struct zl_msm_set_slots {
@@ -170,7 +172,7 @@ constexpr bool zl_slots_disjoint() {
             owners[x]++;
         }
     for (zl_slot x : {ZL_SLOT_PHI_ONE_KEY, ZL_SLOT_STAGING, ZL_SLOT_GROTH16, ZL_SLOT_TESTHOOK, ZL_SLOT_PAIR_IN, ZL_SLOT_PAIR_LINES, ZL_SLOT_PAIR_ACC, ZL_SLOT_PAIR_PREP,
-                      ZL_SLOT_DECODE_IN, ZL_SLOT_DECODE_OUT, ZL_SLOT_MSM_MULTI, ZL_SLOT_G16_BATCH}) {
+                      ZL_SLOT_DECODE_IN, ZL_SLOT_DECODE_OUT, ZL_SLOT_MSM_MULTI, ZL_SLOT_G16_BATCH, ZL_SLOT_PAIR_FEXP}) {
         if (x < 0 || x >= ZL_SLOT_COUNT) return false;
         owners[x]++;
     }
@@ -181,6 +183,9 @@ constexpr bool zl_slots_disjoint() {
 static_assert(zl_slots_disjoint(), "scratch slots: the four MSM buffer sets, the shared / staging slots, the pairing product and the decoder must not collide");
 static_assert(ZL_SLOT_DECODE_IN != ZL_SLOT_PAIR_IN && ZL_SLOT_DECODE_OUT != ZL_SLOT_PAIR_PREP && ZL_SLOT_DECODE_OUT != ZL_SLOT_PAIR_LINES && ZL_SLOT_DECODE_OUT != ZL_SLOT_PAIR_ACC,
               "the decoder keeps its own slots: the bytes-in verifier decodes and pairs in one call");
+static_assert(ZL_SLOT_PAIR_FEXP != ZL_SLOT_PAIR_ACC && ZL_SLOT_PAIR_FEXP != ZL_SLOT_PAIR_IN && ZL_SLOT_PAIR_FEXP != ZL_SLOT_PAIR_PREP && ZL_SLOT_PAIR_FEXP != ZL_SLOT_PAIR_LINES &&
+                  ZL_SLOT_PAIR_FEXP != ZL_SLOT_DECODE_IN && ZL_SLOT_PAIR_FEXP != ZL_SLOT_DECODE_OUT,
+              "the final exponentiations read a groups launch's accumulators in place and run inside the bytes-in verifier: their own slot");
 static_assert(ZL_SLOT_TMP_A == ZL_MSM_SET[0].sort_a && ZL_SLOT_TMP_B == ZL_MSM_SET[0].sort_b && ZL_SLOT_NTT_VEC == ZL_MSM_SET[0].sort_b,
               "the general temporaries and the transform's vector are set 0's sort pair and nothing else (see the map)");
 struct zl_twiddles {

@@ -11,6 +11,7 @@
 #include <sys/random.h>
 #include "zl_host.h"
 #include "zl_pairing_dev.h"
+#include "zl_fq12_inv.h"
 #include "zl_decode_dev.h"
 #include "zl_serialize.h"
 
@@ -992,10 +993,14 @@ template <class E> struct PairDev;
 template <> struct PairDev<Bls12_381> {
     static int product(zl_ctx* c, const uint64_t* p, const uint64_t* q, const uint32_t* s, size_t n, uint32_t* o) { return pairing_dev::miller_product_bls(c, p, q, s, n, o); }
     static int groups(zl_ctx* c, const uint64_t* p, const uint64_t* q, size_t n, size_t g, uint32_t* o) { return pairing_dev::miller_groups_bls(c, p, q, nullptr, n, g, o); }
+    static int groups_fexp(zl_ctx* c, const uint64_t* p, const uint64_t* q, size_t n, size_t g, uint32_t* o, uint8_t* s) { return pairing_dev::pairing_groups_bls(c, p, q, nullptr, n, g, o, s); }
+    static int fexp(zl_ctx* c, const uint32_t* in, size_t n, uint32_t* o, uint8_t* s) { return pairing_dev::final_exp_bls(c, in, n, o, s); }
 };
 template <> struct PairDev<Bn254> {
     static int product(zl_ctx* c, const uint64_t* p, const uint64_t* q, const uint32_t* s, size_t n, uint32_t* o) { return pairing_dev::miller_product_bn(c, p, q, s, n, o); }
     static int groups(zl_ctx* c, const uint64_t* p, const uint64_t* q, size_t n, size_t g, uint32_t* o) { return pairing_dev::miller_groups_bn(c, p, q, nullptr, n, g, o); }
+    static int groups_fexp(zl_ctx* c, const uint64_t* p, const uint64_t* q, size_t n, size_t g, uint32_t* o, uint8_t* s) { return pairing_dev::pairing_groups_bn(c, p, q, nullptr, n, g, o, s); }
+    static int fexp(zl_ctx* c, const uint32_t* in, size_t n, uint32_t* o, uint8_t* s) { return pairing_dev::final_exp_bn(c, in, n, o, s); }
 };
 template <class E> using EngOf = pairing::Engine<typename E::G1::FqP, typename E::PairingP>;
 
@@ -1008,6 +1013,49 @@ int pairing_product_t(zl_ctx* ctx, const uint64_t* ps, const uint64_t* qs, size_
     bool degenerate = false;
     Eng::store(out12, Eng::final_exp(f, &degenerate));
     return degenerate ? ZL_ENOTCURVE : ZL_OK;
+}
+
+// T: the smallest reject-path chunk of verify_batch_t whose final exponentiations run on the device (ZL_TUNE_FEXP_DEV_MIN).  Measured: the smallest power of two
+// from which the device path beat the host threads in every repetition, on both curves (profiles/final_exp_bench.log, the table in DESIGN.md §4.6)
+constexpr int FEXP_DEV_MIN = 128;
+
+// zl_pairing_products: `count` independent products of `each` pairs, Miller loops and final exponentiations on the device
+template <class E>
+int pairing_products_t(zl_ctx* ctx, const uint64_t* ps, const uint64_t* qs, size_t count, size_t each, uint64_t* out12, int32_t* status) {
+    using Eng = EngOf<E>;
+    constexpr size_t q1 = 2 * E::G1::FQ64, q2 = 2 * q1, ow = 6 * q1;  // u64 words of a G1 point, a G2 point, an Fq12 value
+    if (each == 0) {
+        for (size_t j = 0; j < count; j++) {
+            Eng::store(out12 + j * ow, Eng::one());
+            if (status) status[j] = ZL_OK;
+        }
+        return ZL_OK;
+    }
+    // products per launch set: what MAX_PAIRS holds (the final exponentiations of a set run ZL_TUNE_FEXP_CHUNK values per launch inside groups_fexp).  Only a
+    // ZL_TUNE_FEXP_CHUNK that is SET also lowers the products per set, so that tests reach several sets at small counts.
+    const int tune = zl_tune("ZL_TUNE_FEXP_CHUNK", 0);
+    const size_t per = tune >= 1 ? std::min(pairing_dev::MAX_PAIRS / each, (size_t)tune) : pairing_dev::MAX_PAIRS / each;
+    std::vector<typename Eng::Fq12> fs(std::min(per, count));
+    std::vector<uint8_t> sing(fs.size());
+    std::vector<uint64_t> pp, qq;
+    for (size_t first = 0; first < count; first += per) {
+        const size_t m = std::min(per, count - first);
+        // pair i of product j sits at index i * m + j: group j of the launch (pair p belongs to group p % m)
+        pp.resize(m * each * q1);
+        qq.resize(m * each * q2);
+        for (size_t j = 0; j < m; j++)
+            for (size_t i = 0; i < each; i++) {
+                memcpy(&pp[(i * m + j) * q1], ps + ((first + j) * each + i) * q1, q1 * 8);
+                memcpy(&qq[(i * m + j) * q2], qs + ((first + j) * each + i) * q2, q2 * 8);
+            }
+        const int rc = PairDev<E>::groups_fexp(ctx, pp.data(), qq.data(), m * each, m, reinterpret_cast<uint32_t*>(fs.data()), sing.data());
+        if (rc) return rc;
+        for (size_t j = 0; j < m; j++) {
+            Eng::store(out12 + (first + j) * ow, fs[j]);
+            if (status) status[first + j] = sing[j] ? ZL_ENOTCURVE : ZL_OK;
+        }
+    }
+    return ZL_OK;
 }
 
 // The verifying key of a batch, canonical affine points (all-zero = infinity)
@@ -1185,6 +1233,18 @@ int verify_batch_t(zl_ctx* ctx, const BatchVk& vk, const uint64_t* pubs, size_t 
             memcpy(&pp[(3 * m + i) * q1], n_alpha.data(), q1 * 8);
             memcpy(&qq[(3 * m + i) * q2], vk.beta_g2, q2 * 8);
         }
+        // a chunk of at least ZL_TUNE_FEXP_DEV_MIN proofs takes its final exponentiations on the device too: the Miller values never come to the host
+        const int dev_min = zl_tune("ZL_TUNE_FEXP_DEV_MIN", FEXP_DEV_MIN);
+        if (ctx && m >= (size_t)(dev_min < 1 ? 1 : dev_min)) {
+            // no singular flags: a zero Miller product (points outside the pairing groups) comes out as 0, which is not one -- rejected, as the host path does
+            const int rc = PairDev<E>::groups_fexp(ctx, pp.data(), qq.data(), 4 * m, m, reinterpret_cast<uint32_t*>(fs.data()), nullptr);
+            if (rc) return rc;
+            for (size_t i = 0; i < m; i++) {
+                const zl_g16_proof& pr = proofs[first + i];
+                ok_each[first + i] = !pr.a_inf && !pr.b_inf && Eng::eq(fs[i], Eng::one()) ? 1 : 0;
+            }
+            continue;
+        }
         if (ctx) {
             const int rc = PairDev<E>::groups(ctx, pp.data(), qq.data(), 4 * m, m, reinterpret_cast<uint32_t*>(fs.data()));
             if (rc) return rc;
@@ -1221,6 +1281,14 @@ int zl_pairing_product(zl_ctx* ctx, zl_curve_t curve, const uint64_t* ps_xy, con
     if (curve == ZL_BLS12_381) return pairing_product_t<Bls12_381>(ctx, ps_xy, qs_xy, n, out12);
     if (curve == ZL_BN254) return pairing_product_t<Bn254>(ctx, ps_xy, qs_xy, n, out12);
     return ZL_EINVAL;
+}
+int zl_pairing_products(zl_ctx* ctx, zl_curve_t curve, const uint64_t* ps_xy, const uint64_t* qs_xy, size_t count, size_t pairs_each, uint64_t* out12,
+                        int32_t* status) {
+    if (!ctx || (curve != ZL_BLS12_381 && curve != ZL_BN254) || pairs_each > pairing_dev::MAX_PAIRS) return ZL_EINVAL;
+    if (count == 0) return ZL_OK;
+    if (!out12 || (pairs_each && (!ps_xy || !qs_xy))) return ZL_EINVAL;
+    if (curve == ZL_BLS12_381) return pairing_products_t<Bls12_381>(ctx, ps_xy, qs_xy, count, pairs_each, out12, status);
+    return pairing_products_t<Bn254>(ctx, ps_xy, qs_xy, count, pairs_each, out12, status);
 }
 int zl_groth16_verify_batch(zl_ctx* ctx, const zl_g16_keys* k, const uint64_t* public_inputs, size_t n_public, const zl_g16_proof* proofs, size_t count,
                             const uint64_t* seed, int* ok, uint8_t* ok_each) {
@@ -1317,6 +1385,45 @@ int zl_test_final_exp(zl_curve_t curve, const uint64_t* in12, uint64_t* out12) {
     if (curve == ZL_BLS12_381) return run(pairing::BlsEngine{});
     if (curve == ZL_BN254) return run(pairing::BnEngine{});
     return ZL_EINVAL;
+}
+int zl_test_final_exp_dev(zl_ctx* ctx, zl_curve_t curve, size_t count, const uint64_t* in, uint64_t* out, uint8_t* singular) {
+    if (!ctx || (count && (!in || !out)) || (curve != ZL_BLS12_381 && curve != ZL_BN254)) return ZL_EINVAL;
+    auto run = [&](auto e) {
+        using E = decltype(e);
+        using F = Fp<typename E::G1::FqP>;
+        std::vector<F> v(count * 12);
+        memcpy(static_cast<void*>(v.data()), in, v.size() * sizeof(F));
+        for (auto& c : v) c = zl::to_mont(c);
+        const int rc = PairDev<E>::fexp(ctx, reinterpret_cast<const uint32_t*>(v.data()), count, reinterpret_cast<uint32_t*>(v.data()), singular);
+        if (rc) return rc;
+        for (auto& c : v) c = zl::from_mont(c);
+        memcpy(out, v.data(), v.size() * sizeof(F));
+        return (int)ZL_OK;
+    };
+    return curve == ZL_BLS12_381 ? run(Bls12_381{}) : run(Bn254{});
+}
+int zl_test_fq12_inverse(zl_curve_t curve, const uint64_t* in12, uint64_t* out12, uint8_t* singular) {
+    if (!in12 || !out12 || !singular || (curve != ZL_BLS12_381 && curve != ZL_BN254)) return ZL_EINVAL;
+    auto run = [&](auto fq, auto pp) {
+        using FqP = decltype(fq);
+        using PP = decltype(pp);
+        fq12inv::El<FqP> f;
+        memcpy(static_cast<void*>(f.c), in12, sizeof f.c);
+        for (auto& c : f.c) c = zl::to_mont(c);
+        bool sing = false;
+        fq12inv::El<FqP> g = fq12inv::inverse<FqP, PP>(f, &sing);
+        for (auto& c : g.c) c = zl::from_mont(c);
+        memcpy(out12, g.c, sizeof g.c);
+        *singular = sing ? 1 : 0;
+        return (int)ZL_OK;
+    };
+    return curve == ZL_BLS12_381 ? run(BLS12_381_Fq{}, BLS12_381_Pairing{}) : run(BN254_Fq{}, BN254_Pairing{});
+}
+int zl_test_fq12_zeta(zl_curve_t curve, uint64_t* out) {
+    if (!out || (curve != ZL_BLS12_381 && curve != ZL_BN254)) return ZL_EINVAL;
+    if (curve == ZL_BLS12_381) { const auto z = zl::from_mont(fq12inv::zeta<BLS12_381_Fq>()); memcpy(out, z.l, sizeof z.l); }
+    else { const auto z = zl::from_mont(fq12inv::zeta<BN254_Fq>()); memcpy(out, z.l, sizeof z.l); }
+    return ZL_OK;
 }
 // Groth16::verify: public_inputs = n x 4 u64 canonical (without the leading ONE); *ok = 1 / 0
 int zl_groth16_verify(const zl_g16_keys* k, const uint64_t* public_inputs, size_t n, const zl_g16_proof* proof, int* ok) {

@@ -15,6 +15,15 @@ int miller_product_bls(zl_ctx* ctx, const uint64_t* ps, const uint64_t* qs, cons
 int miller_groups_bls(zl_ctx* ctx, const uint64_t* ps, const uint64_t* qs, const uint32_t* sc, size_t n, size_t ngroups, uint32_t* out);
 int miller_product_bn(zl_ctx* ctx, const uint64_t* ps, const uint64_t* qs, const uint32_t* sc, size_t n, uint32_t* out);
 int miller_groups_bn(zl_ctx* ctx, const uint64_t* ps, const uint64_t* qs, const uint32_t* sc, size_t n, size_t ngroups, uint32_t* out);
+// final_exp_*: out[i] = in[i]^((q^12 - 1)/r) on the device (k_pd_fexp), Montgomery Fq12 values in host buffers (12 x N words each); singular (optional, count
+// bytes): 1 for a zero input, whose result is zero -- what Engine::final_exp leaves and reports for it.  The unique GT value of the host, bit for bit.
+// pairing_groups_*: miller_groups_* followed by the final exponentiation of every group, the Miller values staying on the device in between.
+// Both run ZL_TUNE_FEXP_CHUNK values per launch (default FEXP_CHUNK).
+int final_exp_bls(zl_ctx* ctx, const uint32_t* in, size_t count, uint32_t* out, uint8_t* singular);
+int final_exp_bn(zl_ctx* ctx, const uint32_t* in, size_t count, uint32_t* out, uint8_t* singular);
+int pairing_groups_bls(zl_ctx* ctx, const uint64_t* ps, const uint64_t* qs, const uint32_t* sc, size_t n, size_t ngroups, uint32_t* out, uint8_t* singular);
+int pairing_groups_bn(zl_ctx* ctx, const uint64_t* ps, const uint64_t* qs, const uint32_t* sc, size_t n, size_t ngroups, uint32_t* out, uint8_t* singular);
+constexpr size_t FEXP_CHUNK = (size_t)1 << 14;  // values per k_pd_fexp launch: their window powers take 15 x 12 Fq each, 141 MB of HBM for 2^14 BLS12-381 values
 constexpr size_t MAX_PAIRS = (size_t)1 << 16;  // pairs per launch set: line stream of 2^16 BLS12-381 pairs = 1.3 GB of HBM
 }  // namespace pairing_dev
 }  // namespace openzl

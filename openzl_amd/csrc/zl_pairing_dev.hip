@@ -20,11 +20,16 @@
 //   k_pd_acc    16-lane groups (12 active lanes, lane k owns coefficient w^k of the accumulator f; operands exchanged through LDS): per step
 //               f <- f^2 prod_{pairs of the group} l_i -- one shared squaring per group and step.  Pair p belongs to group p % ngroups.
 //   k_pd_prod   product of the group accumulators, 16 at a time per group of lanes, until one is left.
+//   k_pd_fexp   the final exponentiation (q^12 - 1)/r of one Fq12 value per 16-lane group, Engine::final_exp's schedule: g = conj6(f) / f with the inverse by the
+//               norm chain of zl_fq12_inv.h, then g^((q^6 + 1)/r) in 4-bit fixed windows over PP::final_exp().  The 15 window powers of a group live in HBM
+//               (ZL_SLOT_PAIR_FEXP); squarings use the symmetry of Engine::sqr (7 products per lane instead of 12).
 // Plain Fp<Fq> (32-bit limbs, fully reduced): no lazily reduced formulas, so nothing new for zl_bounds.h.  Every loop bound is a compile-time constant or a
 // launch argument: off-curve / non-subgroup inputs give a wrong value (or a zero product, which the host reports as ZL_ENOTCURVE), never a different path.
 #include <string.h>
+#include <algorithm>
 #include <vector>
 #include "zl_ctx.h"
+#include "zl_fq12_inv.h"
 #include "zl_pairing.h"
 #include "zl_pairing_dev.h"
 
@@ -277,6 +282,138 @@ __global__ __launch_bounds__(64) void k_pd_prod(const F* __restrict__ in, uint32
     if (act) out[(size_t)g * 12 + k] = fk;
 }
 
+// fk <- f^2 with f's coefficients in the lanes' fk: t[m] = sum_{i<=j, i+j=m} (i < j ? 2 : 1) a_i a_j.  Lane k has k/2 + 1 such pairs for t[k] and 6 - ceil(k/2) for
+// t[k+12]: seven steps for an even k, six for an odd one (whose seventh step is empty), where mul_full takes twelve.
+__device__ __forceinline__ void sqr_full(F& fk, F* a, F* t, int k, bool act, const Consts& K) {
+    if (act) a[k] = fk;
+    __syncthreads();
+    if (act) {
+        F lo = F::zero(), hi = F::zero();
+        const int h = k >> 1;
+#pragma unroll 1
+        for (int s = 0; s < 7; s++) {
+            const bool low = s <= h;
+            const int i = low ? s : k + s - h, j = (low ? k : k + 12) - i;
+            if (i <= j) {
+                F pr = zl::mul(a[i], a[j]);
+                if (i != j) pr = zl::dbl(pr);
+                if (low) lo = zl::add(lo, pr);
+                else hi = zl::add(hi, pr);
+            }
+        }
+        t[k] = lo;
+        t[k + 12] = hi;
+    }
+    __syncthreads();
+    if (act) fk = fold(t, k, K);
+    __syncthreads();
+}
+
+constexpr int FEXP_TAB = 15;  // window powers g^1 .. g^15 of a value (g^0 = 1 is never multiplied in)
+// out[g] = in[g]^((q^12 - 1)/r), Montgomery in and out (out may be in); singular[g] = (in[g] == 0), whose result is 0.  ew: the words of PP::final_exp().
+// The exponent is the same for every group, so the branches on its nibbles are uniform over the launch; nothing depends on the values.
+__global__ __launch_bounds__(64) void k_pd_fexp(const F* in, uint32_t count, Consts K, const uint32_t* __restrict__ ew, F* tab, F* out, uint8_t* __restrict__ singular) {
+    __shared__ F sa[4][12];
+    __shared__ F sb[4][12];
+    __shared__ F st[4][24];
+    const int grp = threadIdx.x >> 4, k = threadIdx.x & 15;
+    const uint32_t g = blockIdx.x * 4 + grp;
+    const bool act = k < 12 && g < count;
+    F* a = sa[grp];
+    F* b = sb[grp];
+    F* t = st[grp];
+    if (act && k == 11) t[23] = F::zero();
+    F* T = tab + (size_t)(act ? g : 0) * FEXP_TAB * 12 + (act ? k : 0);  // this lane's coefficient of g^e at T[(e - 1) * 12]
+    const F fk = act ? in[(size_t)g * 12 + k] : F::zero();
+    const F ck = (k & 1) ? zl::neg(fk) : fk;  // conj6(f)
+    // f^-1 (zl_fq12_inv.h): n6 = f conj6(f)
+    F n6 = F::zero(), cof = F::zero(), x = F::zero();
+    if (act) {
+        a[k] = fk;
+        b[k] = ck;
+    }
+    mul_full(n6, a, b, t, k, act, K);
+    // cof = sigma(n6) sigma^2(n6)
+    if (act) {
+        a[k] = zl::mul(n6, openzl::fq12inv::sigma_factor<FqP>(k, 1));
+        b[k] = zl::mul(n6, openzl::fq12inv::sigma_factor<FqP>(k, 2));
+    }
+    mul_full(cof, a, b, t, k, act, K);
+    // n2 = n6 cof = a0 + a1 w^6
+    if (act) {
+        a[k] = n6;
+        b[k] = cof;
+    }
+    mul_full(x, a, b, t, k, act, K);
+    // n2^-1 = b0 + b1 w^6 on lane 0 of the group (one Fermat inversion in Fq), left in b
+    if (act) {
+        a[k] = x;
+        if (k != 0 && k != 6) b[k] = F::zero();
+    }
+    __syncthreads();
+    if (act && k == 0) {
+        F b0, b1;
+        const bool z = openzl::fq12inv::quad_inverse<FqP, PP>(a[0], a[6], b0, b1);
+        b[0] = b0;
+        b[6] = b1;
+        singular[g] = z ? 1 : 0;
+    }
+    __syncthreads();
+    // g = conj6(f) f^-1 = conj6(f)^2 cof n2^-1
+    if (act) a[k] = cof;
+    mul_full(x, a, b, t, k, act, K);
+    if (act) {
+        a[k] = x;
+        b[k] = ck;
+    }
+    mul_full(x, a, b, t, k, act, K);
+    if (act) {
+        a[k] = x;
+        b[k] = ck;
+    }
+    mul_full(x, a, b, t, k, act, K);
+    // the window powers: g^e = g^(e-1) g for an odd e, (g^(e/2))^2 for an even one (each lane reads back only what it wrote itself)
+    const F gk = x;
+    if (act) T[0] = x;
+#pragma unroll 1
+    for (int e = 2; e <= FEXP_TAB; e++) {
+        if (e & 1) {
+            if (act) {
+                a[k] = x;
+                b[k] = gk;
+            }
+            mul_full(x, a, b, t, k, act, K);
+        } else {
+            if (act) x = T[(size_t)((e >> 1) - 1) * 12];
+            sqr_full(x, a, t, k, act, K);
+        }
+        if (act) T[(size_t)(e - 1) * 12] = x;
+    }
+    F acc = k == 0 ? F::one() : F::zero();
+    bool started = false;
+#pragma unroll 1
+    for (int i = PP::FINAL_EXP_WORDS * 8 - 1; i >= 0; i--) {
+        const uint32_t nib = (ew[i >> 3] >> (4 * (i & 7))) & 15u;
+        if (started) {
+#pragma unroll 1
+            for (int s = 0; s < 4; s++) sqr_full(acc, a, t, k, act, K);
+        }
+        if (nib) {
+            if (started) {
+                if (act) {
+                    a[k] = acc;
+                    b[k] = T[(size_t)(nib - 1) * 12];
+                }
+                mul_full(acc, a, b, t, k, act, K);
+            } else {
+                if (act) acc = T[(size_t)(nib - 1) * 12];
+                started = true;
+            }
+        }
+    }
+    if (act) out[(size_t)g * 12 + k] = acc;
+}
+
 Consts make_consts() {
     using Eng = openzl::pairing::Engine<FqP, PP>;
     Consts K;
@@ -295,9 +432,10 @@ Consts make_consts() {
     return K;
 }
 
-// one launch set: pairs [0, n) in ngroups groups -> `nout_red ? 1 : ngroups` Fq12 values in out (Montgomery words)
-int run(zl_ctx* ctx, const uint64_t* ps, const uint64_t* qs, const uint32_t* sc, size_t n, size_t ngroups, bool reduce, uint32_t* out) {
-    if (!ctx || !out || n == 0 || ngroups == 0 || ngroups > n || n > openzl::pairing_dev::MAX_PAIRS) return ZL_EINVAL;
+// one launch set: pairs [0, n) in ngroups groups -> `reduce ? 1 : ngroups` Fq12 values in out (Montgomery words).  With d_res the values stay on the device:
+// *d_res points at them (inside ZL_SLOT_PAIR_ACC), nothing is copied and the stream is not drained -- the caller goes on with them on ctx->stream.
+int run(zl_ctx* ctx, const uint64_t* ps, const uint64_t* qs, const uint32_t* sc, size_t n, size_t ngroups, bool reduce, uint32_t* out, const F** d_res = nullptr) {
+    if (!ctx || (!out && !d_res) || n == 0 || ngroups == 0 || ngroups > n || n > openzl::pairing_dev::MAX_PAIRS) return ZL_EINVAL;
     ZL_HIP(ctx, hipSetDevice(ctx->device));
     static const Consts K = make_consts();
     const size_t G = (n + ngroups - 1) / ngroups, npad = G * ngroups;
@@ -339,7 +477,46 @@ int run(zl_ctx* ctx, const uint64_t* ps, const uint64_t* qs, const uint32_t* sc,
             cnt = nout;
         }
     }
+    if (d_res) {
+        *d_res = res;
+        return ZL_OK;
+    }
     ZL_HIP(ctx, hipMemcpyAsync(out, res, cnt * 12 * sizeof(F), hipMemcpyDeviceToHost, ctx->stream));
+    ZL_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    return ZL_OK;
+}
+
+// count final exponentiations, ZL_TUNE_FEXP_CHUNK values per launch: d_in (device, Montgomery; a groups launch of run()) or, when it is null, h_in (host)
+// -> out (host, Montgomery), singular (host, optional).  ZL_SLOT_PAIR_FEXP: exponent words | count values | count flags | the window powers of one launch.
+int fexp(zl_ctx* ctx, const F* d_in, const uint32_t* h_in, size_t count, uint32_t* out, uint8_t* singular) {
+    if (!ctx || !out || (!d_in && !h_in)) return ZL_EINVAL;
+    if (count == 0) return ZL_OK;
+    ZL_HIP(ctx, hipSetDevice(ctx->device));
+    static const Consts K = make_consts();
+    const int tune = zl_tune("ZL_TUNE_FEXP_CHUNK", (int)openzl::pairing_dev::FEXP_CHUNK);
+    const size_t chunk = std::min(count, (size_t)(tune < 1 ? 1 : tune));
+    auto pad = [](size_t b) { return (b + 255) & ~(size_t)255; };
+    const size_t ew_bytes = pad(PP::FINAL_EXP_WORDS * 4), val_bytes = pad(count * 12 * sizeof(F)), sing_bytes = pad(count);
+    void* d = nullptr;
+    const int rc = zl_scratch_get(ctx, ZL_SLOT_PAIR_FEXP, ew_bytes + val_bytes + sing_bytes + chunk * FEXP_TAB * 12 * sizeof(F), &d);
+    if (rc) return rc;
+    unsigned char* base = static_cast<unsigned char*>(d);
+    uint32_t* ew = reinterpret_cast<uint32_t*>(base);
+    F* vals = reinterpret_cast<F*>(base + ew_bytes);
+    uint8_t* sing = base + ew_bytes + val_bytes;
+    F* tab = reinterpret_cast<F*>(base + ew_bytes + val_bytes + sing_bytes);
+    ZL_HIP(ctx, hipMemcpyAsync(ew, PP::final_exp(), PP::FINAL_EXP_WORDS * 4, hipMemcpyHostToDevice, ctx->stream));
+    if (!d_in) {
+        ZL_HIP(ctx, hipMemcpyAsync(vals, h_in, count * 12 * sizeof(F), hipMemcpyHostToDevice, ctx->stream));
+        d_in = vals;  // in place: a lane reads its coefficient before anything is written
+    }
+    for (size_t first = 0; first < count; first += chunk) {
+        const size_t m = std::min(chunk, count - first);
+        hipLaunchKernelGGL(k_pd_fexp, dim3((unsigned)((m + 3) / 4)), dim3(64), 0, ctx->stream, d_in + first * 12, (uint32_t)m, K, ew, tab, vals + first * 12, sing + first);
+        ZL_HIP(ctx, hipGetLastError());
+    }
+    ZL_HIP(ctx, hipMemcpyAsync(out, vals, count * 12 * sizeof(F), hipMemcpyDeviceToHost, ctx->stream));
+    if (singular) ZL_HIP(ctx, hipMemcpyAsync(singular, sing, count, hipMemcpyDeviceToHost, ctx->stream));
     ZL_HIP(ctx, hipStreamSynchronize(ctx->stream));
     return ZL_OK;
 }
@@ -366,6 +543,15 @@ int ZL_PD_SUFFIX(miller_product)(zl_ctx* ctx, const uint64_t* ps, const uint64_t
     }
     memcpy(out, f.c, sizeof f.c);
     return ZL_OK;
+}
+int ZL_PD_SUFFIX(final_exp)(zl_ctx* ctx, const uint32_t* in, size_t count, uint32_t* out, uint8_t* singular) {
+    if (count && !in) return ZL_EINVAL;
+    return fexp(ctx, nullptr, in, count, out, singular);
+}
+int ZL_PD_SUFFIX(pairing_groups)(zl_ctx* ctx, const uint64_t* ps, const uint64_t* qs, const uint32_t* sc, size_t n, size_t ngroups, uint32_t* out, uint8_t* singular) {
+    const F* d_f = nullptr;
+    const int rc = run(ctx, ps, qs, sc, n, ngroups, false, nullptr, &d_f);
+    return rc ? rc : fexp(ctx, d_f, nullptr, ngroups, out, singular);
 }
 }  // namespace pairing_dev
 }  // namespace openzl
