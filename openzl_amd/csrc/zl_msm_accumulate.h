@@ -30,13 +30,15 @@ __device__ __forceinline__ void zl_accumulate_chunk(uint32_t t, int sub, uint32_
                                                     const Affine<typename HotField<typename G::F>::type>* __restrict__ bases,
                                                     XYZZ<typename HotField<typename G::F>::type>* __restrict__ bucket_sums,
                                                     XYZZ<typename HotField<typename G::F>::type>* __restrict__ partials, uint32_t ZL_CHUNK,
-                                                    const Affine<typename HotField<typename G::F>::type>* __restrict__ phib, uint32_t n_real, uint32_t idx_mask = 0x7fffffffu) {
+                                                    const Affine<typename HotField<typename G::F>::type>* __restrict__ phib, uint32_t n_real, uint32_t* __restrict__ chunk_head,
+                                                    uint32_t idx_mask = 0x7fffffffu) {
     using F = typename HotField<typename G::F>::type;  // same layout as G::F; Fq2 on 28-bit limbs: the inlining flavour (zl_curve.h)
     const uint64_t start64 = (uint64_t)t * ZL_CHUNK;
     if (start64 >= E) return;
     const uint32_t start = (uint32_t)start64;
     const uint32_t end = (uint32_t)min((uint64_t)E, start64 + ZL_CHUNK);
     uint32_t b = zl_upper_bound(offsets, NB + 1, start) - 1;  // bucket holding entry `start`
+    if (!QUAD || sub == 0) chunk_head[t] = b;  // k_msm_merge_cuts (zl_msm_reduce.h) folds the bucket cut at `start` without searching for it again
     uint32_t b_start = offsets[b], b_end = offsets[b + 1];
     XYZZ<F> acc = XYZZ<F>::inf();
     // ONE flat loop of exactly (end - start) mixed additions per lane: a per-segment inner loop would make the
@@ -73,13 +75,13 @@ __global__ void __launch_bounds__(ZL_ACC_BLOCK, ZL_ACC_WAVES * 64 / ZL_ACC_BLOCK
                                                         const Affine<typename G::F>* __restrict__ bases_,
                                                         XYZZ<typename G::F>* __restrict__ bucket_sums_,
                                                         XYZZ<typename G::F>* __restrict__ partials_, uint32_t ZL_CHUNK,
-                                                        const Affine<typename G::F>* __restrict__ phib_, uint32_t n_real) {
+                                                        const Affine<typename G::F>* __restrict__ phib_, uint32_t n_real, uint32_t* __restrict__ chunk_head) {
     using F = typename HotField<typename G::F>::type;
     static_assert(sizeof(F) == sizeof(typename G::F), "hot flavour must share the layout");
     // GLV: virtual point n_real + i = phi(P_i); else n_real = 2^32 - 1 (never selected)
     zl_accumulate_chunk<G>(blockIdx.x * blockDim.x + threadIdx.x, 0, offsets[NB], entries, offsets, NB, reinterpret_cast<const Affine<F>*>(bases_),
                            reinterpret_cast<XYZZ<F>*>(bucket_sums_), reinterpret_cast<XYZZ<F>*>(partials_), ZL_CHUNK,
-                           reinterpret_cast<const Affine<F>*>(phib_) - n_real, n_real);
+                           reinterpret_cast<const Affine<F>*>(phib_) - n_real, n_real, chunk_head);
 }
 #ifdef ZL_MEASURE
 // MEASUREMENT BUILDS ONLY (-DZL_MEASURE: ZL_EXTRA_FLAGS=-DZL_MEASURE ZL_BUILD_TAG=measure python -m openzl_amd.build; zl_test_acc_clock, include/zl_backend_test.h): the same kernel with four scalar clock reads per WAVE -- s_memtime (shader cycles) and
@@ -93,13 +95,13 @@ __global__ void __launch_bounds__(ZL_ACC_BLOCK, ZL_ACC_WAVES * 64 / ZL_ACC_BLOCK
                                                         const Affine<typename G::F>* __restrict__ bases_,
                                                         XYZZ<typename G::F>* __restrict__ bucket_sums_,
                                                         XYZZ<typename G::F>* __restrict__ partials_, uint32_t ZL_CHUNK,
-                                                        const Affine<typename G::F>* __restrict__ phib_, uint32_t n_real, unsigned long long* __restrict__ clk, uint32_t idx_mask) {
+                                                        const Affine<typename G::F>* __restrict__ phib_, uint32_t n_real, uint32_t* __restrict__ chunk_head, unsigned long long* __restrict__ clk, uint32_t idx_mask) {
     if constexpr (G::COORDS == 1) {
         using F = typename HotField<typename G::F>::type;
         const unsigned long long c0 = __builtin_readcyclecounter(), w0 = __builtin_amdgcn_s_memrealtime();
         zl_accumulate_chunk<G>(blockIdx.x * blockDim.x + threadIdx.x, 0, offsets[NB], entries, offsets, NB, reinterpret_cast<const Affine<F>*>(bases_),
                                reinterpret_cast<XYZZ<F>*>(bucket_sums_), reinterpret_cast<XYZZ<F>*>(partials_), ZL_CHUNK,
-                               reinterpret_cast<const Affine<F>*>(phib_) - n_real, n_real, idx_mask);
+                               reinterpret_cast<const Affine<F>*>(phib_) - n_real, n_real, chunk_head, idx_mask);
         const unsigned long long c1 = __builtin_readcyclecounter(), w1 = __builtin_amdgcn_s_memrealtime();
         if (threadIdx.x == 0) {
             unsigned long long* o = clk + (size_t)4 * blockIdx.x;
@@ -115,12 +117,12 @@ __global__ void __launch_bounds__(ZL_ACC_BLOCK, ZL_ACC_WAVES * 64 / ZL_ACC_BLOCK
                                                         const Affine<typename G::F>* __restrict__ bases_,
                                                         XYZZ<typename G::F>* __restrict__ bucket_sums_,
                                                         XYZZ<typename G::F>* __restrict__ partials_, uint32_t ZL_CHUNK,
-                                                        const Affine<typename G::F>* __restrict__ phib_, uint32_t n_real) {
+                                                        const Affine<typename G::F>* __restrict__ phib_, uint32_t n_real, uint32_t* __restrict__ chunk_head) {
     using F = typename HotField<typename G::F>::type;
     const uint32_t gt = blockIdx.x * blockDim.x + threadIdx.x;
     zl_accumulate_chunk<G, true>(gt >> 2, (int)(gt & 3u), offsets[NB], entries, offsets, NB, reinterpret_cast<const Affine<F>*>(bases_),
                                  reinterpret_cast<XYZZ<F>*>(bucket_sums_), reinterpret_cast<XYZZ<F>*>(partials_), ZL_CHUNK,
-                                 reinterpret_cast<const Affine<F>*>(phib_) - n_real, n_real);
+                                 reinterpret_cast<const Affine<F>*>(phib_) - n_real, n_real, chunk_head);
 }
 // Fq2 groups, TWO lanes per chunk (zl_fq2pair.h): lane i of a row of 16 holds the c0 components of the chunk's running sum and of the base it adds,
 // lane i ^ 8 the c1 components; a wave walks 32 chunks.  Registers per lane halve (416 -> two waves per SIMD), the instruction stream of one mixed
@@ -176,14 +178,14 @@ __global__ void __launch_bounds__(64, ZL_ACC_PAIR_WAVES) k_msm_accumulate_pair(c
 // every instantiation MsmJob<G>::accumulate launches, one list per kind of group (ZL_GLIST, zl_msm_common.h): X = empty defines them (zl_msm_acc.hip),
 // X = extern only declares them
 #ifdef ZL_MEASURE
-#define ZL_MSM_ACCUMULATE_CLK_KERNEL(X, G) X template __global__ void k_msm_accumulate_clk<G>(const uint32_t*, const uint32_t*, uint32_t, const Affine<typename G::F>*, XYZZ<typename G::F>*, XYZZ<typename G::F>*, uint32_t, const Affine<typename G::F>*, uint32_t, unsigned long long*, uint32_t);
+#define ZL_MSM_ACCUMULATE_CLK_KERNEL(X, G) X template __global__ void k_msm_accumulate_clk<G>(const uint32_t*, const uint32_t*, uint32_t, const Affine<typename G::F>*, XYZZ<typename G::F>*, XYZZ<typename G::F>*, uint32_t, const Affine<typename G::F>*, uint32_t, uint32_t*, unsigned long long*, uint32_t);
 #else
 #define ZL_MSM_ACCUMULATE_CLK_KERNEL(X, G)
 #endif
 #define ZL_MSM_ACCUMULATE_KERNELS_G1(X, G) \
     ZL_MSM_ACCUMULATE_CLK_KERNEL(X, G) \
-    X template __global__ void k_msm_accumulate<G>(const uint32_t*, const uint32_t*, uint32_t, const Affine<typename G::F>*, XYZZ<typename G::F>*, XYZZ<typename G::F>*, uint32_t, const Affine<typename G::F>*, uint32_t); \
-    X template __global__ void k_msm_accumulate_quad<G>(const uint32_t*, const uint32_t*, uint32_t, const Affine<typename G::F>*, XYZZ<typename G::F>*, XYZZ<typename G::F>*, uint32_t, const Affine<typename G::F>*, uint32_t);
+    X template __global__ void k_msm_accumulate<G>(const uint32_t*, const uint32_t*, uint32_t, const Affine<typename G::F>*, XYZZ<typename G::F>*, XYZZ<typename G::F>*, uint32_t, const Affine<typename G::F>*, uint32_t, uint32_t*); \
+    X template __global__ void k_msm_accumulate_quad<G>(const uint32_t*, const uint32_t*, uint32_t, const Affine<typename G::F>*, XYZZ<typename G::F>*, XYZZ<typename G::F>*, uint32_t, const Affine<typename G::F>*, uint32_t, uint32_t*);
 #define ZL_MSM_ACCUMULATE_KERNELS_G2(X, G) \
     X template __global__ void k_msm_accumulate_pair<G, true>(const uint32_t*, const uint32_t*, uint32_t, const Affine<typename G::F>*, XYZZ<typename G::F>*, XYZZ<typename G::F>*, uint32_t, const Affine<typename G::F>*, uint32_t); \
     X template __global__ void k_msm_accumulate_pair<G, false>(const uint32_t*, const uint32_t*, uint32_t, const Affine<typename G::F>*, XYZZ<typename G::F>*, XYZZ<typename G::F>*, uint32_t, const Affine<typename G::F>*, uint32_t);

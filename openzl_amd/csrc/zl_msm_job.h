@@ -129,7 +129,7 @@ struct MsmJob {
     // buffers
     uint32_t *d_counts = nullptr, *d_offsets = nullptr, *d_cursor = nullptr, *d_entries = nullptr, *d_block_sums = nullptr, *d_big_list = nullptr,
              *d_big_count = nullptr, *d_ones_count = nullptr, *d_giant_count = nullptr, *d_giant_list = nullptr, *d_ones_list = nullptr,
-             *d_bigsg_items = nullptr, *d_bad_scalar = nullptr;
+             *d_bigsg_items = nullptr, *d_bad_scalar = nullptr, *d_chunk_head = nullptr;
     unsigned long long* d_bigsg_head = nullptr;
     X *d_buckets = nullptr, *d_partials = nullptr, *d_segs = nullptr, *d_stage1 = nullptr, *d_sets = nullptr, *d_ones_parts = nullptr, *d_giant_tmp = nullptr;
     const Affine<F>* d_bases = nullptr;
@@ -329,9 +329,10 @@ struct MsmJob {
             if ((rc = zl_scratch_get(ctx, own_sort ? slots.sort_b : ZL_SLOT_SORT_B, lay.b_bytes, &p))) return rc;
             d_sort_b = (unsigned char*)p;
         }
-        // counters (NB+1) | offsets (NB+2: [NB] = total entries, [NB+1] = non-canonical-scalar flag) | cursor (NB+1) | block sums | big list | counts | giant list | scalar-1 list
+        // counters (NB+1) | offsets (NB+2: [NB] = total entries, [NB+1] = non-canonical-scalar flag) | cursor (NB+1) | block sums | big list | counts | giant list | scalar-1 list |
+        // oversized sub-groups | chunk heads (G1: the bucket every chunk starts in, left by the accumulation for k_msm_merge_cuts; per set like the offsets it indexes)
         const size_t max_bigsg = (size_t)(maxE / 1024) + 2;  // oversized sub-groups hold > cap >= 1024 entries each
-        size_t small_words = (size_t)3 * (NB + 1) + 1 + scan_blocks + 1 + max_big + max_giant + 16 + n + 2 * max_bigsg;
+        size_t small_words = (size_t)3 * (NB + 1) + 1 + scan_blocks + 1 + max_big + max_giant + 16 + n + 2 * max_bigsg + nchunks;
         if ((rc = zl_scratch_get(ctx, slots.data[0], small_words * 4, &p))) return rc;
         d_counts = (uint32_t*)p;
         d_offsets = d_counts + (NB + 1);
@@ -345,6 +346,7 @@ struct MsmJob {
         d_giant_list = d_big_count + 16;
         d_ones_list = d_giant_list + max_giant;
         d_bigsg_items = d_ones_list + n;
+        d_chunk_head = d_bigsg_items + 2 * max_bigsg;
         d_bigsg_head = reinterpret_cast<unsigned long long*>((reinterpret_cast<uintptr_t>(d_big_count + 4) + 7) & ~(uintptr_t)7);  // inside words 4..7
         if ((rc = zl_scratch_get(ctx, slots.data[1], maxE * 4, &p))) return rc;
         d_entries = (uint32_t*)p;
@@ -431,14 +433,14 @@ struct MsmJob {
         // per call, not once per process: the attribute is per device and a process may own several contexts
         (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&k_msm_hist_lds), hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024);
         (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&k_msm_scatter_range), hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024);
-        if (wide) sort_wide(st, sc_eff, inf_eff, bad_eff, nblk, glv_i);
+        if (wide) sort_wide(st, sc_eff, inf_eff, bad_eff, glv_i);
         else if (c <= 16) sort_lds(st, sc_eff, inf_eff, bad_eff, nblk, glv_i);
         else sort_atomics(st, nblk);
         ZL_HIP(ctx, hipGetLastError());
         return ZL_OK;
     }
     // ---- three-level counting sort over (window, bucket) ids: the merged set of a table, or W sets of plain wide windows (c = 17 .. 20; GLS quarter-scalars at c = 16)
-    void sort_wide(hipStream_t st, const uint32_t* sc_eff, const uint8_t* inf_eff, uint32_t* bad_eff, uint32_t nblk, int glv_i) {
+    void sort_wide(hipStream_t st, const uint32_t* sc_eff, const uint8_t* inf_eff, uint32_t* bad_eff, int glv_i) {
         const zl_bases& bs = *bsp;
         const uint32_t nslices = lay.nslices, per_slice = lay.per_slice, P = lay.P, pscan_blocks = lay.pscan_blocks;
         uint16_t* d_lo16 = (uint16_t*)d_sort_a;
@@ -448,8 +450,12 @@ struct MsmJob {
         uint32_t* d_pcounts = (uint32_t*)(d_sort_a + lay.pcounts);
         uint32_t* d_poff = d_pcounts + P;            // P + 1 entries (total at [P])
         uint32_t* d_pblock = d_poff + P + 1;
-        hipLaunchKernelGGL(k_msm_recode_wide, dim3(nblk), dim3(256), 0, st, sc_eff, (uint32_t)n, c, W, pre ? 0u : (H >> 15), spread_t, glv_i, d_lo16, d_hi8, d_ones_list, d_ones_count, inf_eff, sc_bits, bad_eff);
-        hipLaunchKernelGGL(k_msm_part_hist, dim3(nslices, W), dim3(256), 0, st, d_hi8, (uint32_t)n, (uint32_t)W, Gn, per_slice, nslices, d_pcounts);
+        // the recoder counts the first partition's histogram as it goes (into zeroed counters): blocks of up to 8192 scalars inside one slice, so that a block sends
+        // one atomic per (window, group) it met -- 2048 blocks at 2^24 -- and still one block per 256 scalars below 2^19, where the launch is latency
+        const uint32_t span = 256u * std::min<uint32_t>(32u, std::max<uint32_t>(1u, (uint32_t)(n >> 19)));
+        (void)hipMemsetAsync(d_pcounts, 0, (size_t)P * 4, st);
+        hipLaunchKernelGGL(k_msm_recode_wide, dim3((per_slice + span - 1) / span, nslices), dim3(256), zl_recode_wide_lds(Gn, (uint32_t)W, pre ? 0u : (H >> 15)), st, sc_eff, (uint32_t)n, c, W, pre ? 0u : (H >> 15), spread_t, glv_i,
+                           d_lo16, d_hi8, d_ones_list, d_ones_count, inf_eff, sc_bits, bad_eff, Gn, per_slice, span, nslices, d_pcounts);
         hipLaunchKernelGGL(k_scan_block_sums, dim3(pscan_blocks), dim3(SCAN_BLOCK), 0, st, d_pcounts, P, d_pblock);
         hipLaunchKernelGGL(k_scan_top, dim3(1), dim3(1024), 0, st, d_pblock, pscan_blocks, d_poff + P, (const uint32_t*)nullptr);
         hipLaunchKernelGGL(k_scan_apply, dim3(pscan_blocks), dim3(SCAN_BLOCK), 0, st, d_pcounts, P, d_pblock, d_poff, d_pcounts);
@@ -536,18 +542,18 @@ struct MsmJob {
         } else {
             if (quad)
                 hipLaunchKernelGGL((k_msm_accumulate_quad<G>), dim3((4 * nchunks + ZL_ACC_BLOCK - 1) / ZL_ACC_BLOCK), dim3(ZL_ACC_BLOCK), 0, st, d_entries, d_offsets, NB, d_bases, d_buckets, d_partials, ZL_CHUNK,
-                                   glv ? d_phi : d_bases, glv ? (uint32_t)n_real : 0xFFFFFFFFu);
+                                   glv ? d_phi : d_bases, glv ? (uint32_t)n_real : 0xFFFFFFFFu, d_chunk_head);
 #ifdef ZL_MEASURE
             else if (ctx->acc_clk && (size_t)((nchunks + ZL_ACC_BLOCK - 1) / ZL_ACC_BLOCK) * 32 <= ctx->acc_clk_cap) {  // armed by the measurement hook zl_test_acc_clock only
                 ctx->acc_clk_waves = (nchunks + ZL_ACC_BLOCK - 1) / ZL_ACC_BLOCK;
                 hipLaunchKernelGGL((k_msm_accumulate_clk<G>), dim3((nchunks + ZL_ACC_BLOCK - 1) / ZL_ACC_BLOCK), dim3(ZL_ACC_BLOCK), 0, st, d_entries, d_offsets, NB, d_bases, d_buckets, d_partials, ZL_CHUNK,
-                                   glv ? d_phi : d_bases, glv ? (uint32_t)n_real : 0xFFFFFFFFu, (unsigned long long*)ctx->acc_clk,
+                                   glv ? d_phi : d_bases, glv ? (uint32_t)n_real : 0xFFFFFFFFu, d_chunk_head, (unsigned long long*)ctx->acc_clk,
                                    zl_tune("ZL_TUNE_ACC_CLK_IDX_BITS", 31) >= 31 ? 0x7fffffffu : ((1u << zl_tune("ZL_TUNE_ACC_CLK_IDX_BITS", 31)) - 1u));
             }
 #endif
             else
                 hipLaunchKernelGGL((k_msm_accumulate<G>), dim3((nchunks + ZL_ACC_BLOCK - 1) / ZL_ACC_BLOCK), dim3(ZL_ACC_BLOCK), 0, st, d_entries, d_offsets, NB, d_bases, d_buckets, d_partials, ZL_CHUNK,
-                                   glv ? d_phi : d_bases, glv ? (uint32_t)n_real : 0xFFFFFFFFu);
+                                   glv ? d_phi : d_bases, glv ? (uint32_t)n_real : 0xFFFFFFFFu, d_chunk_head);
         }
         ZL_HIP(ctx, hipGetLastError());
         return ZL_OK;
@@ -566,7 +572,7 @@ struct MsmJob {
                 hipLaunchKernelGGL((k_msm_merge_pair<G, true>), dim3((NB + 7) / 8), dim3(64), 0, st, d_offsets, NB, d_buckets, d_partials, d_big_list, d_big_count, d_giant_list, d_giant_count, ZL_CHUNK, big_span);
         } else {
             if (by_cuts)
-                hipLaunchKernelGGL((k_msm_merge_cuts<G>), dim3((nchunks + 63) / 64), dim3(64), 0, st, d_offsets, NB, d_buckets, d_partials, d_big_list, d_big_count, d_giant_list, d_giant_count, ZL_CHUNK, big_span, nchunks);
+                hipLaunchKernelGGL((k_msm_merge_cuts<G>), dim3((nchunks + 63) / 64), dim3(64), 0, st, d_offsets, d_chunk_head, NB, d_buckets, d_partials, d_big_list, d_big_count, d_giant_list, d_giant_count, ZL_CHUNK, big_span, nchunks);
             else if (NB > quad_max)  // (a single chunk)
                 hipLaunchKernelGGL((k_msm_merge<G>), dim3((NB + 63) / 64), dim3(64), 0, st, d_offsets, NB, d_buckets, d_partials, d_big_list, d_big_count, d_giant_list, d_giant_count, ZL_CHUNK, big_span);
             else
@@ -615,8 +621,11 @@ struct MsmJob {
                     else
                         hipLaunchKernelGGL((k_msm_reduce_tree_pair<G, true>), dim3((lanes + 7) / 8), dim3(64), 0, st, cur, nxt, lv, nodes, lanes);
                 } else {
-                    if (lanes > quad_max)
-                        hipLaunchKernelGGL((k_msm_reduce_tree<G>), dim3((lanes + 63) / 64), dim3(64), 0, st, cur, nxt, lv, nodes, lanes);
+                    if (lanes > quad_max) {  // adding blocks, then the blocks that copy the top channels
+                        uint32_t add_blocks, copy_blocks;
+                        zl_tree_blocks<G>(lv, SETS * nodes, add_blocks, copy_blocks);
+                        hipLaunchKernelGGL((k_msm_reduce_tree<G>), dim3(add_blocks + copy_blocks), dim3(64), 0, st, cur, nxt, lv, nodes, lanes);
+                    }
                     else
                         hipLaunchKernelGGL((k_msm_reduce_tree<G, true>), dim3((4 * lanes + 63) / 64), dim3(64), 0, st, cur, nxt, lv, nodes, lanes);
                 }

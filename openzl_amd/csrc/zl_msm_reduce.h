@@ -54,8 +54,11 @@ __global__ void __launch_bounds__(256) k_msm_fill_empty(const uint32_t* __restri
     if (b >= NB || offsets[b] != offsets[b + 1]) return;
     bucket_sums[b] = XYZZ<typename G::F>::inf();
 }
+// (two waves per SIMD: one full addition holds both operands and four products; capped at the 168 registers of three waves it kept 156-184 B of them in private memory,
+// with or without the search: 0.46 ms against 0.40 ms at 210 registers, and a slower pipelined step -- profiles/tail_work_ab.log)
 template <class G>
-__global__ void __launch_bounds__(64, sizeof(XYZZ<typename G::F>) <= 256 ? 3 : 1) k_msm_merge_cuts(const uint32_t* __restrict__ offsets, uint32_t NB, XYZZ<typename G::F>* __restrict__ bucket_sums,
+__global__ void __launch_bounds__(64, sizeof(XYZZ<typename G::F>) <= 256 ? 2 : 1) k_msm_merge_cuts(const uint32_t* __restrict__ offsets, const uint32_t* __restrict__ chunk_head, uint32_t NB,
+                                                   XYZZ<typename G::F>* __restrict__ bucket_sums,
                                                    const XYZZ<typename G::F>* __restrict__ partials, uint32_t* __restrict__ big_list,
                                                    uint32_t* __restrict__ big_count, uint32_t* __restrict__ giant_list, uint32_t* __restrict__ giant_count,
                                                    uint32_t ZL_CHUNK, uint32_t big_span, uint32_t nchunks) {
@@ -66,15 +69,18 @@ __global__ void __launch_bounds__(64, sizeof(XYZZ<typename G::F>) <= 256 ? 3 : 1
     const uint64_t p64 = (uint64_t)t * ZL_CHUNK;
     if (p64 >= offsets[NB]) return;
     const uint32_t p = (uint32_t)p64;
-    const uint32_t b = zl_bucket_of_entry(offsets, NB, p);
+    // the bucket that holds entry p: what zl_bucket_of_entry finds, found by the accumulation lane of chunk t (chunk_head, zl_accumulate_chunk)
+    const uint32_t b = chunk_head[t];
     const uint32_t s = offsets[b], e = offsets[b + 1];
     if (s == p || s / ZL_CHUNK != t - 1) return;  // not cut here, or an earlier boundary of the same bucket owns it
     const uint32_t t0 = t - 1, t1 = (e - 1) / ZL_CHUNK;
     if (t1 - t0 + 1 > ZL_GIANT_SPAN) { giant_list[atomicAdd(giant_count, 1u)] = b; return; }
     if (t1 - t0 + 1 > big_span) { big_list[atomicAdd(big_count, 1u)] = b; return; }
-    XYZZ<F> acc = XYZZ<F>::inf();
-    for (uint32_t tt = t0; tt <= t1; tt++) {
-        const XYZZ<F> q = partials[(size_t)2 * tt + (s <= tt * ZL_CHUNK ? 0 : 1)];
+    // The fold starts from the bucket's piece in chunk t0 (its head partial when s is t0's first entry, else its tail partial) instead of from infinity -- the same
+    // bits, add_full(inf, q) copies q -- and every later chunk holds the bucket in its head partial.  The usual bucket is cut once: two loads, one addition.
+    XYZZ<F> acc = partials[(size_t)2 * t0 + (s == t0 * ZL_CHUNK ? 0 : 1)];
+    for (uint32_t tt = t; tt <= t1; tt++) {
+        const XYZZ<F> q = partials[(size_t)2 * tt];
         zl::add_full(acc, q);
     }
     bucket_sums[b] = acc;
@@ -273,28 +279,61 @@ __global__ void __launch_bounds__(64, TreeLanes<G>::N == 128 ? 1 : 2) k_msm_redu
     else out[(size_t)2 * t + 1] = wsum;
 }
 // one tree level: nodes of `level` (1-based) from the nodes of level - 1.  Node layout: [set][node][channel], ch_in = level + 1 channels
-// in (T, A, S_0 .. S_(level-2)), ch_out = level + 2 out.  One lane per (set, node, out channel).
+// in (T, A, S_0 .. S_(level-2)), ch_out = level + 2 out.
+// QUAD (launches that do not fill the machine): four lanes per (set, node, out channel); the top channel's lanes copy.
+// One lane (launches that do): the waves of the first blocks only ADD, one lane per (set, node, ch < ch_out - 1), densely numbered -- with one lane per OUT channel
+// every (level + 2)-th lane of every wave idled through a whole addition to copy one point (a third, a quarter, a fifth of the three largest levels) -- and the
+// new top channels, out[node][ch_out - 1] = in[right child][0], are moved by the blocks behind them, one lane per 16 bytes (zl_tree_blocks: the grid).
+template <class G>
+struct TreeCopy { static constexpr uint32_t VECS = sizeof(XYZZ<typename G::F>) / 16; };
+template <class G>
+inline void zl_tree_blocks(uint32_t level, uint32_t total_nodes, uint32_t& add_blocks, uint32_t& copy_blocks) {
+    add_blocks = (uint32_t)(((uint64_t)total_nodes * (level + 1) + 63) / 64);
+    copy_blocks = (uint32_t)(((uint64_t)total_nodes * TreeCopy<G>::VECS + 63) / 64);
+}
 template <class G, bool QUAD = false>
 __global__ void __launch_bounds__(64) k_msm_reduce_tree(const XYZZ<typename G::F>* __restrict__ in, XYZZ<typename G::F>* __restrict__ out, uint32_t level,
                                                          uint32_t nodes_out_per_set, uint32_t total_lanes) {
     ZL_SIDE_PRIO();
     using X = XYZZ<typename G::F>;
-    const uint32_t gt = blockIdx.x * blockDim.x + threadIdx.x;
-    const uint32_t t = QUAD ? gt >> 2 : gt;  // QUAD: four lanes per (set, node, channel) (zl_quad.h)
-    const int sub = QUAD ? (int)(gt & 3u) : 0;
-    if (t >= total_lanes) return;
     const uint32_t ch_out = level + 2, ch_in = level + 1;
-    const uint32_t ch = t % ch_out, node = (t / ch_out) % nodes_out_per_set, set = t / (ch_out * nodes_out_per_set);
-    const size_t left = ((size_t)set * nodes_out_per_set * 2 + (size_t)2 * node) * ch_in, right = left + ch_in;
-    if (ch == ch_out - 1) {  // the new top channel: blocks of the right child have this bit set
-        if (sub == 0) out[t] = in[right];
-        return;
+    if constexpr (!QUAD) {
+        static_assert(sizeof(X) % 16 == 0 && alignof(X) <= 16, "the top channel is copied in 16-byte vectors");
+        const uint32_t total_nodes = total_lanes / ch_out;  // sets x nodes: node g of the level has the children 2 g, 2 g + 1 whatever its set
+        const uint32_t add_lanes = total_nodes * ch_in, add_blocks = (add_lanes + 63) / 64;
+        if (blockIdx.x >= add_blocks) {
+            const uint32_t j = (blockIdx.x - add_blocks) * 64 + threadIdx.x;
+            const uint32_t g = j / TreeCopy<G>::VECS, v = j % TreeCopy<G>::VECS;
+            if (g >= total_nodes) return;
+            const uint4* src = reinterpret_cast<const uint4*>(in + ((size_t)2 * g + 1) * ch_in);  // channel T of the right child: its blocks have this bit set
+            uint4* dst = reinterpret_cast<uint4*>(out + (size_t)g * ch_out + ch_in);
+            dst[v] = src[v];
+            return;
+        }
+        const uint32_t t = blockIdx.x * 64 + threadIdx.x;
+        if (t >= add_lanes) return;
+        const uint32_t g = t / ch_in, ch = t % ch_in;
+        const size_t left = (size_t)2 * g * ch_in, right = left + ch_in;
+        X acc = in[left + ch];
+        const X o = in[right + ch];
+        zl::add_full(acc, o);
+        out[(size_t)g * ch_out + ch] = acc;
+    } else {
+        const uint32_t gt = blockIdx.x * blockDim.x + threadIdx.x;
+        const uint32_t t = gt >> 2;  // four lanes per (set, node, channel) (zl_quad.h)
+        const int sub = (int)(gt & 3u);
+        if (t >= total_lanes) return;
+        const uint32_t ch = t % ch_out, node = (t / ch_out) % nodes_out_per_set, set = t / (ch_out * nodes_out_per_set);
+        const size_t left = ((size_t)set * nodes_out_per_set * 2 + (size_t)2 * node) * ch_in, right = left + ch_in;
+        if (ch == ch_out - 1) {  // the new top channel: blocks of the right child have this bit set
+            if (sub == 0) out[t] = in[right];
+            return;
+        }
+        X acc = in[left + ch];
+        const X o = in[right + ch];
+        zl::add_full_quad(acc, o, sub);
+        if (sub == 0) out[t] = acc;
     }
-    X acc = in[left + ch];
-    const X o = in[right + ch];
-    if constexpr (QUAD) zl::add_full_quad(acc, o, sub);
-    else zl::add_full(acc, o);
-    if (sub == 0) out[t] = acc;
 }
 // ------------------------------------------------------------------------------------------------ Fq2 groups on lane pairs (zl_fq2pair.h)
 // The same three kernels for the Fq2 groups (the one-lane / four-lane forms above are the G1 groups' only) with TWO lanes per item (lane i of a row of 16:
@@ -518,7 +557,7 @@ __global__ void __launch_bounds__(2 * ZL_GIANT_PARTS) k_msm_merge_giant2_pair(XY
     ZL_MSM_TAIL_KERNELS_COMMON(X, G) \
     X template __global__ void k_msm_merge<G, false>(const uint32_t*, uint32_t, XYZZ<typename G::F>*, const XYZZ<typename G::F>*, uint32_t*, uint32_t*, uint32_t*, uint32_t*, uint32_t, uint32_t); \
     X template __global__ void k_msm_merge<G, true>(const uint32_t*, uint32_t, XYZZ<typename G::F>*, const XYZZ<typename G::F>*, uint32_t*, uint32_t*, uint32_t*, uint32_t*, uint32_t, uint32_t); \
-    X template __global__ void k_msm_merge_cuts<G>(const uint32_t*, uint32_t, XYZZ<typename G::F>*, const XYZZ<typename G::F>*, uint32_t*, uint32_t*, uint32_t*, uint32_t*, uint32_t, uint32_t, uint32_t); \
+    X template __global__ void k_msm_merge_cuts<G>(const uint32_t*, const uint32_t*, uint32_t, XYZZ<typename G::F>*, const XYZZ<typename G::F>*, uint32_t*, uint32_t*, uint32_t*, uint32_t*, uint32_t, uint32_t, uint32_t); \
     X template __global__ void k_msm_merge_big<G>(const uint32_t*, XYZZ<typename G::F>*, const XYZZ<typename G::F>*, const uint32_t*, const uint32_t*, uint32_t); \
     X template __global__ void k_msm_merge_giant<G>(const uint32_t*, XYZZ<typename G::F>*, const XYZZ<typename G::F>*, const uint32_t*, const uint32_t*, uint32_t); \
     X template __global__ void k_msm_merge_giant2<G>(XYZZ<typename G::F>*, const XYZZ<typename G::F>*, const uint32_t*, const uint32_t*); \

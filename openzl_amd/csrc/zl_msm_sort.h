@@ -28,9 +28,10 @@ __global__ void __launch_bounds__(1024) k_msm_scatter_range(const uint16_t* __re
 __global__ void __launch_bounds__(256) k_msm_recode_wide(const uint32_t* __restrict__ scalars, uint32_t n, int c, int W, uint32_t gw, int spread_t, int glv,
                                                                   uint16_t* __restrict__ lo16, uint8_t* __restrict__ hi8,
                                                                   uint32_t* __restrict__ ones_list, uint32_t* __restrict__ ones_count, const uint8_t* __restrict__ inf,
-                                                                  int sc_bits, uint32_t* __restrict__ bad);
-__global__ void __launch_bounds__(256) k_msm_part_hist(const uint8_t* __restrict__ hi8, uint32_t n, uint32_t W, uint32_t G, uint32_t per_slice,
-                                                                uint32_t nslices, uint32_t* __restrict__ counts);
+                                                                  int sc_bits, uint32_t* __restrict__ bad, uint32_t G, uint32_t per_slice, uint32_t span, uint32_t nslices,
+                                                                  uint32_t* __restrict__ counts);
+// its dynamic LDS: one counter per group (plain windows, gw > 0) or per (group, window) (a merged set)
+inline size_t zl_recode_wide_lds(uint32_t G, uint32_t W, uint32_t gw) { return (size_t)(gw ? G : G * W) * 4; }
 __global__ void __launch_bounds__(256) k_msm_sub_hist(const uint16_t* __restrict__ part_lo, const uint32_t* __restrict__ part_off, uint32_t G,
                                                                uint32_t stride, const uint32_t* __restrict__ total, uint32_t fslices,
                                                                uint32_t* __restrict__ counts);

@@ -245,71 +245,74 @@ __global__ void __launch_bounds__(1024) k_msm_scatter_range(const uint16_t* __re
 // spread_t >= 0 (plain wide windows only): the top window holds just spread_t + 1 bits, so its 2^spread_t magnitudes would crowd n entries
 // into 2^spread_t buckets (one sort group) while its bucket set has 2^(c-1).  It is spread over the whole set instead: bucket =
 // (low bits of the point index) << spread_t | (magnitude - 1); the reduction weights those buckets by their low spread_t bits only.
+// The kernel also counts the first partition's histogram (a pass of its own, k_msm_part_hist, re-read every hi8 byte one kernel later only to count 16 groups per
+// (window, slice)): block (x, slice) walks `span` consecutive scalars of ONE slice -- so no block straddles a slice edge, whatever per_slice is -- counts its group ids
+// in LDS beside the stores and adds its non-zero counts to counts[(g * W + w) * nslices + slice] (zero at launch: MsmJob::sort_wide) -- one global atomic per block and
+// (window, group), with blocks of several thousand scalars at large n.  Plain windows (gw > 0): group g belongs to window g / gw, one LDS cell per group; a merged set
+// (gw = 0): every window meets every group, one cell per (group, window).  The next scalar is loaded before the current one is recoded.
+// (Four copies of every cell, picked by the lane -- the 64 digits of a wave-level store fall into the 16 groups of one window -- measured the same: 0.34 = 0.35 ms.)
 __global__ void __launch_bounds__(256) k_msm_recode_wide(const uint32_t* __restrict__ scalars, uint32_t n, int c, int W, uint32_t gw, int spread_t, int glv,
                                                                   uint16_t* __restrict__ lo16, uint8_t* __restrict__ hi8,
                                                                   uint32_t* __restrict__ ones_list, uint32_t* __restrict__ ones_count, const uint8_t* __restrict__ inf,
-                                                                  int sc_bits, uint32_t* __restrict__ bad) {
+                                                                  int sc_bits, uint32_t* __restrict__ bad, uint32_t G, uint32_t per_slice, uint32_t span, uint32_t nslices,
+                                                                  uint32_t* __restrict__ counts) {
     ZL_SIDE_PRIO();
-    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-    const bool live = i < n;
-    const uint4* sp = reinterpret_cast<const uint4*>(scalars + (size_t)(live ? i : 0) * 8);
-    uint4 lo = sp[0], hi = sp[1];
-    if (live) zl_flag_wide_scalar(hi.w, sc_bits, bad);
-    if (!live || (inf && inf[i])) lo = hi = make_uint4(0, 0, 0, 0);  // a base at infinity contributes nothing
-    uint32_t s[8] = {lo.x, lo.y, lo.z, lo.w, hi.x, hi.y, hi.z, hi.w};
-    if (zl_take_one(s, i, ones_list, ones_count)) s[0] = 0;
-    if (!live) return;
-    const uint32_t sg = zl_take_sign(s[7], glv);
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    uint32_t* hist = reinterpret_cast<uint32_t*>(smem);  // one word per cell; the launch sizes it: zl_recode_wide_lds
+    const uint32_t slice = blockIdx.y, cells = gw ? G : G * (uint32_t)W;
+    for (uint32_t k = threadIdx.x; k < cells; k += blockDim.x) hist[k] = 0;
+    __syncthreads();
+    const uint32_t s_hi = min(n, (slice + 1) * per_slice);  // (slice * per_slice < n + per_slice, n < 2^31: no overflow)
+    const uint32_t b0 = min(s_hi, slice * per_slice + blockIdx.x * span), b1 = min(s_hi, b0 + span);
     const uint32_t H = 1u << (c - 1);
-    uint32_t carry = 0;
-    for (int w = 0; w < W; w++) {
-        const int pos = w * c;
-        const int word = pos >> 5, sh = pos & 31;
-        uint64_t v = 0;
-#pragma unroll
-        for (int k = 0; k < 8; k++) {
-            if (k == word) v |= s[k];
-            if (k == word + 1) v |= (uint64_t)s[k] << 32;
-        }
-        uint32_t d = ((uint32_t)(v >> sh) & ((1u << c) - 1)) + carry;
-        uint32_t neg = 0;
-        carry = 0;
-        if (d > H) { d = 2 * H - d; neg = 1; carry = 1; }
-        uint32_t b = d - 1;  // bucket (d != 0)
-        if (spread_t >= 0 && w == W - 1) b |= (i & ((1u << (c - 1 - spread_t)) - 1u)) << spread_t;
-        lo16[(size_t)w * n + i] = (uint16_t)((b & 0x7FFFu) | ((neg ^ sg) << 15));
-        hi8[(size_t)w * n + i] = d == 0 ? (uint8_t)0xFF : (uint8_t)((uint32_t)w * gw + (b >> 15));  // gw = groups per window (0: merged set)
+    uint4 nlo = make_uint4(0, 0, 0, 0), nhi = nlo;
+    if (b0 + threadIdx.x < b1) {
+        const uint4* sp = reinterpret_cast<const uint4*>(scalars + (size_t)(b0 + threadIdx.x) * 8);
+        nlo = sp[0]; nhi = sp[1];
     }
-}
-// block (slice, w): histogram of the group ids of window w over a slice of scalars -> counts[(g*W + w)*nslices + slice]
-__global__ void __launch_bounds__(256) k_msm_part_hist(const uint8_t* __restrict__ hi8, uint32_t n, uint32_t W, uint32_t G, uint32_t per_slice,
-                                                                uint32_t nslices, uint32_t* __restrict__ counts) {
-    ZL_SIDE_PRIO();
-    __shared__ uint32_t hist[256];
-    const uint32_t slice = blockIdx.x, w = blockIdx.y;
-    hist[threadIdx.x] = 0;
-    __syncthreads();
-    const uint32_t lo = slice * per_slice, hi = min(n, lo + per_slice);
-    const uint8_t* hw = hi8 + (size_t)w * n;
-    // 16 group ids per 16-B load over the aligned body (row base w*n and lo are multiples of 16 for the usual power-of-two n)
-    const bool al = ((((size_t)w * n) | lo) & 15) == 0;
-    const uint32_t body1 = al ? lo + ((hi - lo) & ~15u) : lo;
-    const uint4* hv = reinterpret_cast<const uint4*>(hw);
-    for (uint32_t i16 = lo / 16 + threadIdx.x; i16 < body1 / 16; i16 += blockDim.x) {
-        const uint4 v = hv[i16];
-        const uint32_t words[4] = {v.x, v.y, v.z, v.w};
-#pragma unroll
-        for (int k = 0; k < 16; k++) {
-            const uint32_t g = (words[k >> 2] >> ((k & 3) * 8)) & 0xFFu;
-            if (g != 0xFFu) atomicAdd(&hist[g], 1u);
+    for (uint32_t base = b0; base < b1; base += blockDim.x) {  // (uniform bounds: the ballot of zl_take_one sees whole waves)
+        const uint32_t i = base + threadIdx.x;
+        const bool live = i < b1;
+        uint4 lo = nlo, hi = nhi;
+        if (i + blockDim.x < b1) {
+            const uint4* sp = reinterpret_cast<const uint4*>(scalars + (size_t)(i + blockDim.x) * 8);
+            nlo = sp[0]; nhi = sp[1];
         }
-    }
-    for (uint32_t i = body1 + threadIdx.x; i < hi; i += blockDim.x) {
-        const uint32_t g = hw[i];
-        if (g != 0xFFu) atomicAdd(&hist[g], 1u);
+        if (live) zl_flag_wide_scalar(hi.w, sc_bits, bad);
+        if (!live || (inf && inf[i])) lo = hi = make_uint4(0, 0, 0, 0);  // a base at infinity contributes nothing
+        uint32_t s[8] = {lo.x, lo.y, lo.z, lo.w, hi.x, hi.y, hi.z, hi.w};
+        if (zl_take_one(s, i, ones_list, ones_count)) s[0] = 0;
+        if (!live) continue;
+        const uint32_t sg = zl_take_sign(s[7], glv);
+        uint32_t carry = 0;
+        for (int w = 0; w < W; w++) {
+            const int pos = w * c;
+            const int word = pos >> 5, sh = pos & 31;
+            uint64_t v = 0;
+#pragma unroll
+            for (int k = 0; k < 8; k++) {
+                if (k == word) v |= s[k];
+                if (k == word + 1) v |= (uint64_t)s[k] << 32;
+            }
+            uint32_t d = ((uint32_t)(v >> sh) & ((1u << c) - 1)) + carry;
+            uint32_t neg = 0;
+            carry = 0;
+            if (d > H) { d = 2 * H - d; neg = 1; carry = 1; }
+            uint32_t b = d - 1;  // bucket (d != 0)
+            if (spread_t >= 0 && w == W - 1) b |= (i & ((1u << (c - 1 - spread_t)) - 1u)) << spread_t;
+            const uint32_t g = (uint32_t)w * gw + (b >> 15);  // gw = groups per window (0: merged set)
+            lo16[(size_t)w * n + i] = (uint16_t)((b & 0x7FFFu) | ((neg ^ sg) << 15));
+            hi8[(size_t)w * n + i] = d == 0 ? (uint8_t)0xFF : (uint8_t)g;
+            // (d <= H and the spread bits stay below H, so b < H and g < G, in window g / gw, for every input: the test only states the bound of the LDS index)
+            if (d != 0 && g < G) atomicAdd(&hist[gw ? g : g * (uint32_t)W + (uint32_t)w], 1u);
+        }
     }
     __syncthreads();
-    if (threadIdx.x < G) counts[((size_t)threadIdx.x * W + w) * nslices + slice] = hist[threadIdx.x];
+    for (uint32_t k = threadIdx.x; k < cells; k += blockDim.x) {
+        const uint32_t v = hist[k];
+        const uint32_t cell = gw ? k * (uint32_t)W + k / gw : k;  // (g, w) -> g * W + w
+        if (v) atomicAdd(&counts[(size_t)cell * nslices + slice], v);
+    }
 }
 // group range [s, e) from the scanned partition counters
 __device__ __forceinline__ void zl_group_range(const uint32_t* __restrict__ part_off, uint32_t g, uint32_t G, uint32_t stride, uint32_t E, uint32_t& s,
