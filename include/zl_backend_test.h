@@ -112,6 +112,11 @@ int zl_test_pairing_product(zl_curve_t curve, size_t n, const uint64_t* ps_xy, c
 /* The device Miller loops of zl_pairing_product, one value per pair: out = n x 12 canonical Fq coefficients (BLS12-381: 12 x 6 u64, BN254: 12 x 4 u64).
  * These are Miller values times subfield factors (openzl_amd/csrc/zl_pairing_dev.hip): only their final exponentiation is defined. */
 int zl_test_miller_dev(zl_ctx* ctx, zl_curve_t curve, size_t n, const uint64_t* ps_xy, const uint64_t* qs_xy, uint64_t* out);
+/* prod_i e(k_i P_i, Q_i) through the production driver of zl_pairing_product and zl_groth16_verify_batch (device Miller loops with the 128-bit scalars k_i
+ * applied inside them, honouring ZL_TUNE_PAIR_GROUPS / ZL_TUNE_PAIR_SET) and the host Engine::final_exp.  scalars128: n x 2 u64 little-endian, NULL = none.
+ * ZL_ENOTCURVE for a zero Miller product. */
+int zl_test_pairing_product_scaled(zl_ctx* ctx, zl_curve_t curve, size_t n, const uint64_t* ps_xy, const uint64_t* qs_xy, const uint64_t* scalars128,
+                                   uint64_t* out12);
 /* The host Engine::final_exp of 12 canonical coefficients (in12 -> out12); ZL_ENOTCURVE for a zero input. */
 int zl_test_final_exp(zl_curve_t curve, const uint64_t* in12, uint64_t* out12);
 /* The device final exponentiation (k_pd_fexp of openzl_amd/csrc/zl_pairing_dev.hip) of `count` values, canonical coefficients in and out as

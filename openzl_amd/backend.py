@@ -176,6 +176,7 @@ def load_library(path: Optional[str] = None):
     L.zl_test_fp28_bn_op.argtypes = [vp, C.c_int, u32p, C.c_size_t, u32p]
     L.zl_test_pairing_product.argtypes = [C.c_int, C.c_size_t, u64p, u64p, u64p]
     L.zl_test_miller_dev.argtypes = [vp, C.c_int, C.c_size_t, u64p, u64p, u64p]
+    L.zl_test_pairing_product_scaled.argtypes = [vp, C.c_int, C.c_size_t, u64p, u64p, u64p, u64p]
     L.zl_test_final_exp.argtypes = [C.c_int, u64p, u64p]
     L.zl_test_final_exp_dev.argtypes = [vp, C.c_int, C.c_size_t, u64p, u64p, u8p]
     L.zl_test_fq12_inverse.argtypes = [C.c_int, u64p, u64p, u8p]
@@ -679,7 +680,7 @@ TEST_ABI_SYMBOLS = ["zl_test_poseidon_permute_dev", "zl_test_fp28_op", "zl_test_
                     "zl_test_poseidon_permute_dev28r", "zl_test_fq_mul_clock", "zl_test_acc_clock", "zl_test_acc_clock_read", "zl_test_clock_probe_launch", "zl_test_clock_probe_read",
                     "zl_test_miller_dev", "zl_test_final_exp", "zl_test_verify_batch_host", "zl_test_ntt_plan", "zl_test_ntt_fit_beside", "zl_test_fp2pair_op", "zl_test_point_form_op",
                     "zl_test_endo_split", "zl_test_endo_split_inf", "zl_test_decode_points_host", "zl_test_fq2_sqrt",
-                    "zl_test_final_exp_dev", "zl_test_fq12_inverse", "zl_test_fq12_zeta"]
+                    "zl_test_final_exp_dev", "zl_test_fq12_inverse", "zl_test_fq12_zeta", "zl_test_pairing_product_scaled"]
 
 
 def _p32(a: np.ndarray):
@@ -780,6 +781,26 @@ def hook_miller_dev(be: "Backend", curve: int, ps: np.ndarray, qs: np.ndarray) -
     q = np.ascontiguousarray(qs, dtype=np.uint64)
     out = np.zeros((p.shape[0], 12, FQ_LIMBS[curve]), dtype=np.uint64)
     be._check(be.L.zl_test_miller_dev(be._ctx, curve, p.shape[0], _p64(p), _p64(q), _p64(out)), "zl_test_miller_dev")
+    return out
+
+
+def hook_pairing_product_scaled(be: "Backend", curve: int, ps: np.ndarray, qs: np.ndarray, scalars128: Optional[np.ndarray]) -> np.ndarray:
+    """prod_i e(k_i P_i, Q_i) through the production Miller-product driver with its scalars (zl_test_pairing_product_scaled): ps (n, 2 FQ64) / qs (n, 4 FQ64)
+    canonical words, scalars128 (n, 2) u64 little-endian or None -> 12 x FQ64 canonical words"""
+    nq = FQ_LIMBS[curve]
+    p = np.ascontiguousarray(np.asarray(ps, dtype=np.uint64).reshape(-1, 2 * nq))
+    q = np.ascontiguousarray(np.asarray(qs, dtype=np.uint64).reshape(-1, 4 * nq))
+    n = p.shape[0]
+    assert q.shape[0] == n
+    k = None
+    if scalars128 is not None:
+        k = np.ascontiguousarray(scalars128, dtype=np.uint64)
+        assert k.shape == (n, 2)
+    if n == 0:
+        p, q = np.zeros((1, 2 * nq), dtype=np.uint64), np.zeros((1, 4 * nq), dtype=np.uint64)
+    out = np.zeros((12, nq), dtype=np.uint64)
+    be._check(be.L.zl_test_pairing_product_scaled(be._ctx, curve, n, _p64(p), _p64(q), _p64(k) if k is not None and n else None, _p64(out)),
+              "zl_test_pairing_product_scaled")
     return out
 
 

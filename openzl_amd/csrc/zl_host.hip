@@ -1213,7 +1213,9 @@ int verify_batch_t(zl_ctx* ctx, const BatchVk& vk, const uint64_t* pubs, size_t 
     // rejected: one product of four pairings per proof, e(A, B) e(-C, delta) e(-IC_i, gamma) e(-alpha, beta), as zl_groth16_verify
     std::vector<uint64_t> n_alpha(q1);
     store(load(vk.alpha_g1), true, n_alpha.data());
-    const size_t chunk = ctx ? pairing_dev::MAX_PAIRS / 4 : 1;
+    // proofs per launch set: what MAX_PAIRS holds; only a ZL_TUNE_PAIR_SET that is SET lowers it (to a quarter of its pairs), the tests' way to several sets
+    const size_t set_pairs = getenv("ZL_TUNE_PAIR_SET") ? pairing_dev::pair_set(zl_tune("ZL_TUNE_PAIR_SET", 0)) : pairing_dev::MAX_PAIRS;
+    const size_t chunk = ctx ? std::max<size_t>(1, set_pairs / 4) : 1;
     std::vector<typename Eng::Fq12> fs(chunk);
     for (size_t first = 0; first < count; first += chunk) {
         const size_t m = std::min(chunk, count - first);
@@ -1368,6 +1370,20 @@ int zl_test_miller_dev(zl_ctx* ctx, zl_curve_t curve, size_t n, const uint64_t* 
         }
     }
     return ZL_OK;
+}
+int zl_test_pairing_product_scaled(zl_ctx* ctx, zl_curve_t curve, size_t n, const uint64_t* ps_xy, const uint64_t* qs_xy, const uint64_t* scalars128, uint64_t* out12) {
+    if (!ctx || !out12 || (n && (!ps_xy || !qs_xy)) || (curve != ZL_BLS12_381 && curve != ZL_BN254)) return ZL_EINVAL;
+    auto run = [&](auto e) {
+        using E = decltype(e);
+        using Eng = EngOf<E>;
+        typename Eng::Fq12 f;
+        const int rc = PairDev<E>::product(ctx, ps_xy, qs_xy, reinterpret_cast<const uint32_t*>(scalars128), n, reinterpret_cast<uint32_t*>(f.c));
+        if (rc) return rc;
+        bool degenerate = false;
+        Eng::store(out12, Eng::final_exp(f, &degenerate));
+        return degenerate ? (int)ZL_ENOTCURVE : (int)ZL_OK;
+    };
+    return curve == ZL_BLS12_381 ? run(Bls12_381{}) : run(Bn254{});
 }
 int zl_test_final_exp(zl_curve_t curve, const uint64_t* in12, uint64_t* out12) {
     if (!in12 || !out12) return ZL_EINVAL;

@@ -531,10 +531,14 @@ int ZL_PD_SUFFIX(miller_product)(zl_ctx* ctx, const uint64_t* ps, const uint64_t
     using Eng = openzl::pairing::Engine<FqP, PP>;
     if (!ctx || !out || (n && (!ps || !qs))) return ZL_EINVAL;
     typename Eng::Fq12 f = Eng::one();
-    // groups per launch: about 32 per CU (8 waves of 4 groups): below that a pair gets a group of its own, above it pairs share squarings
-    const size_t target = (size_t)(ctx->cu_count > 0 ? ctx->cu_count : 256) * 32;
-    for (size_t first = 0; first < n; first += MAX_PAIRS) {
-        const size_t m = n - first < MAX_PAIRS ? n - first : MAX_PAIRS;
+    // groups per launch: about 32 per CU (8 waves of 4 groups): below that a pair gets a group of its own, above it pairs share squarings.
+    // ZL_TUNE_PAIR_GROUPS (>= 1) and ZL_TUNE_PAIR_SET (clamped to [1, MAX_PAIRS]) lower the two numbers so that tests reach shared groups, padding
+    // lanes and several launch sets at tens of pairs; run() still checks against MAX_PAIRS and the scratch sizing is unchanged.
+    const int tune_groups = zl_tune("ZL_TUNE_PAIR_GROUPS", 0);
+    const size_t target = tune_groups >= 1 ? (size_t)tune_groups : (size_t)(ctx->cu_count > 0 ? ctx->cu_count : 256) * 32;
+    const size_t set = pair_set(zl_tune("ZL_TUNE_PAIR_SET", (int)MAX_PAIRS));
+    for (size_t first = 0; first < n; first += set) {
+        const size_t m = n - first < set ? n - first : set;
         const size_t G = (m + target - 1) / target, ng = (m + G - 1) / G;
         typename Eng::Fq12 part;
         const int rc = run(ctx, ps + first * NW, qs + first * 2 * NW, sc ? sc + 4 * first : nullptr, m, ng, true, reinterpret_cast<uint32_t*>(part.c));
