@@ -128,6 +128,42 @@ int zl_circuit_export(const zl_circuit* c, zl_r1cs* view, const uint64_t** assig
 int zl_circuit_is_satisfied(const zl_circuit* c); /* 1 / 0 */
 /* native Poseidon permutation, width 3 (tutorial schedule): state = 3 x 4 u64 canonical, in place */
 int zl_poseidon_permute(zl_curve_t curve, uint64_t* state);
+/* ---- batched Poseidon (openzl_amd/csrc/zl_poseidon_dev.hip): the same width-3 permutation (8 full + 55 partial rounds, x^5, tutorial schedule) for many
+ * states at once, one device lane per permutation.  H(x, y) = element 0 of permute([3, x, y]) -- 3 is the arity-2 domain tag of the circuit's hash
+ * (openzl-crypto/src/poseidon/hash.rs:93-135) -- so H is the hash zl_circuit_poseidon_chain proves.  Every field element is 4 u64 canonical (< r).
+ * Common rules: count == 0 is ZL_OK and nothing is written; an input element >= r is ZL_EINVAL (the kernels raise a flag word; the outputs are then
+ * unspecified); null pointers, an unknown curve, a depth outside 1..40 or n > 2^depth are ZL_EINVAL.  On the entry points that take HOST pointers ctx may
+ * be NULL: the call then runs the host mirror's permutation over the library's host thread pool and opens no device; with a ctx, batches below
+ * ZL_TUNE_POSEIDON_DEV_MIN items take that host path too.  Host batches are staged through one scratch slot of the ctx under a byte budget, in chunks of at
+ * most ZL_TUNE_POSEIDON_CHUNK permutations (also the permutations of one launch).  Every call has FINISHED when it returns: it reads the flag word back on
+ * the ctx's stream (zl_ctx_set_stream is honoured) and waits for it. */
+int zl_poseidon_permute_batch(zl_ctx* ctx, zl_curve_t curve, uint64_t* states, size_t count); /* count x 3 elements, in place: state i as zl_poseidon_permute */
+int zl_poseidon_hash2_batch(zl_ctx* ctx, zl_curve_t curve, const uint64_t* xy, size_t count, uint64_t* out); /* out[i] = H(xy[2i], xy[2i+1]) */
+/* the same on DEVICE pointers (count x 2 elements in, count elements out; they may not overlap): never the host path, ctx == NULL is ZL_EINVAL */
+int zl_poseidon_hash2_batch_dev(zl_ctx* ctx, zl_curve_t curve, const void* d_xy, size_t count, void* d_out);
+/* out[i] = h_k with h_1 = H(x0[i], x1[i]), h_{j+1} = H(h_j, x1[i]): the public input of zl_circuit_poseidon_chain(curve, k, x0[i], x1[i]); the k dependent
+ * hashes of a chain run inside one kernel.  k == 0: ZL_EINVAL, as zl_circuit_poseidon_chain. */
+int zl_poseidon_chain_batch(zl_ctx* ctx, zl_curve_t curve, const uint64_t* x0, const uint64_t* x1, uint32_t k, size_t count, uint64_t* out);
+/* Merkle tree over n leaf digests with `depth` hash levels (openzl-crypto/src/merkle_tree, one H for join_leaves and join): level 0 = the n leaves, level k
+ * has ceil(n / 2^k) nodes, node(k, j) = H(node(k-1, 2j), node(k-1, 2j+1)) where an absent right child reads as the zero digest.  A node whose subtree holds no
+ * leaf is absent -- zero when read as a sibling, NOT H(0, 0): the reference's Default::default() rule (merkle_tree/node.rs:55-73, path.rs:405-454).  The root
+ * is the one node of level `depth` (n == 0: the zero digest).  Nodes are stored level after level from level 0: zl_poseidon_merkle_nodes(n, depth) elements
+ * (0 for a depth outside 1..40 or n > 2^depth).  Levels of at most ZL_TUNE_POSEIDON_TAIL nodes are finished by ONE workgroup in one launch (0: a launch per level). */
+size_t zl_poseidon_merkle_nodes(size_t n, unsigned depth);
+int zl_poseidon_merkle_build_dev(zl_ctx* ctx, zl_curve_t curve, const void* d_leaves, size_t n, unsigned depth, void* d_nodes, uint64_t* root_out);
+/* the same from host leaves into a host node array / to the root alone (device scratch of the call is freed before it returns) */
+int zl_poseidon_merkle_build(zl_ctx* ctx, zl_curve_t curve, const uint64_t* leaves, size_t n, unsigned depth, uint64_t* nodes, uint64_t* root);
+int zl_poseidon_merkle_root(zl_ctx* ctx, zl_curve_t curve, const uint64_t* leaves, size_t n, unsigned depth, uint64_t* root);
+/* paths[i] = the `depth` sibling digests of leaf indices[i] from the bottom up: entry 0 is the reference's Path::sibling_digest, the rest its inner_path
+ * (path.rs:628-636); absent siblings are zero.  An index >= n is ZL_EINVAL before any work.  indices and paths are host memory; _dev gathers from a node
+ * array in device memory, the other form from one in host memory (a plain gather: no ctx). */
+int zl_poseidon_merkle_paths_dev(zl_ctx* ctx, zl_curve_t curve, const void* d_nodes, size_t n, unsigned depth, const uint64_t* indices, size_t count,
+                                 uint64_t* paths);
+int zl_poseidon_merkle_paths(const uint64_t* nodes, size_t n, unsigned depth, const uint64_t* indices, size_t count, uint64_t* paths);
+/* roots[i] = the fold of paths[i] (depth elements) over leaves[i]: at level k the running digest joins on the right when bit k of indices[i] is set, on the
+ * left otherwise (Parity::join); one lane per path, `depth` dependent hashes each.  An index >= 2^depth is ZL_EINVAL.  Host pointers. */
+int zl_poseidon_merkle_roots_from_paths(zl_ctx* ctx, zl_curve_t curve, const uint64_t* leaves, const uint64_t* indices, const uint64_t* paths, unsigned depth,
+                                        size_t count, uint64_t* roots);
 /* Groth16::compile with rng = SplitMix64(seed): trapdoor setup, proving key generated on the device */
 int zl_groth16_compile(zl_ctx* ctx, const zl_circuit* c, uint64_t seed, zl_g16_keys** out);
 int zl_groth16_keys_trapdoor(const zl_g16_keys* k, uint64_t* out20); /* alpha, beta, gamma, delta, tau (canonical) */

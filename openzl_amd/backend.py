@@ -35,6 +35,9 @@ ABI_SYMBOLS = [
     "zl_groth16_vk_to_bytes", "zl_pairing_product", "zl_groth16_verify_batch",
     "zl_points_from_bytes_batch", "zl_groth16_proofs_from_bytes_batch", "zl_groth16_verify_batch_bytes", "zl_msm_multi_dev", "zl_groth16_prove_batch",
     "zl_pairing_products",
+    "zl_poseidon_permute_batch", "zl_poseidon_hash2_batch", "zl_poseidon_hash2_batch_dev", "zl_poseidon_chain_batch", "zl_poseidon_merkle_nodes",
+    "zl_poseidon_merkle_build_dev", "zl_poseidon_merkle_build", "zl_poseidon_merkle_root", "zl_poseidon_merkle_paths_dev", "zl_poseidon_merkle_paths",
+    "zl_poseidon_merkle_roots_from_paths",
 ]
 
 
@@ -126,6 +129,18 @@ def load_library(path: Optional[str] = None):
     L.zl_circuit_poseidon_chain_witness.argtypes = L.zl_circuit_poseidon_chain.argtypes
     L.zl_circuit_is_satisfied.argtypes = [vp]
     L.zl_poseidon_permute.argtypes = [C.c_int, u64p]
+    L.zl_poseidon_permute_batch.argtypes = [vp, C.c_int, u64p, C.c_size_t]
+    L.zl_poseidon_hash2_batch.argtypes = [vp, C.c_int, u64p, C.c_size_t, u64p]
+    L.zl_poseidon_hash2_batch_dev.argtypes = [vp, C.c_int, vp, C.c_size_t, vp]
+    L.zl_poseidon_chain_batch.argtypes = [vp, C.c_int, u64p, u64p, C.c_uint32, C.c_size_t, u64p]
+    L.zl_poseidon_merkle_nodes.argtypes = [C.c_size_t, C.c_uint]
+    L.zl_poseidon_merkle_nodes.restype = C.c_size_t
+    L.zl_poseidon_merkle_build_dev.argtypes = [vp, C.c_int, vp, C.c_size_t, C.c_uint, vp, u64p]
+    L.zl_poseidon_merkle_build.argtypes = [vp, C.c_int, u64p, C.c_size_t, C.c_uint, u64p, u64p]
+    L.zl_poseidon_merkle_root.argtypes = [vp, C.c_int, u64p, C.c_size_t, C.c_uint, u64p]
+    L.zl_poseidon_merkle_paths_dev.argtypes = [vp, C.c_int, vp, C.c_size_t, C.c_uint, u64p, C.c_size_t, u64p]
+    L.zl_poseidon_merkle_paths.argtypes = [u64p, C.c_size_t, C.c_uint, u64p, C.c_size_t, u64p]
+    L.zl_poseidon_merkle_roots_from_paths.argtypes = [vp, C.c_int, u64p, u64p, u64p, C.c_uint, C.c_size_t, u64p]
     L.zl_groth16_compile.argtypes = [vp, vp, C.c_uint64, C.POINTER(vp)]
     L.zl_groth16_keys_free.argtypes = [vp]
     L.zl_groth16_keys_free.restype = None
@@ -478,6 +493,47 @@ class Backend:
     def ntt_cross_dev(self, curve: int, d_data: int, log_n: int, log_g: int, rank: int, flags: int):
         """Cross-rank step of the distributed transform (include/zl_backend.h: zl_ntt_cross_dev)."""
         self._check(self.L.zl_ntt_cross_dev(self._ctx, curve, C.c_void_p(d_data), log_n, log_g, rank, flags), "zl_ntt_cross_dev")
+
+    # ---- batched Poseidon (include/zl_backend_ext.h; the module-level poseidon_*_host functions are the same calls with ctx == NULL) ----------
+    def poseidon_permute_batch(self, curve: int, states: np.ndarray) -> np.ndarray:
+        """(count, 3, 4) canonical states -> the permuted copy (zl_poseidon_permute_batch)"""
+        return _poseidon_permute_batch(self.L, self._ctx, curve, states)
+
+    def poseidon_hash2(self, curve: int, xy: np.ndarray) -> np.ndarray:
+        """(count, 2, 4) canonical pairs -> (count, 4) digests H(x, y)"""
+        return _poseidon_hash2(self.L, self._ctx, curve, xy)
+
+    def poseidon_hash2_dev(self, curve: int, d_xy: int, count: int, d_out: int):
+        """zl_poseidon_hash2_batch_dev: count pairs at device address d_xy -> count digests at d_out; finished on return"""
+        self._check(self.L.zl_poseidon_hash2_batch_dev(self._ctx, curve, C.c_void_p(d_xy), count, C.c_void_p(d_out)), "zl_poseidon_hash2_batch_dev")
+
+    def poseidon_chain(self, curve: int, x0: np.ndarray, x1: np.ndarray, k: int) -> np.ndarray:
+        """out[i] = h_k of the chain over (x0[i], x1[i]): the public input of Circuit(curve, k, x0[i], x1[i])"""
+        return _poseidon_chain(self.L, self._ctx, curve, x0, x1, k)
+
+    def poseidon_merkle_root(self, curve: int, leaves: np.ndarray, depth: int) -> np.ndarray:
+        return _poseidon_merkle_root(self.L, self._ctx, curve, leaves, depth)
+
+    def poseidon_merkle_build(self, curve: int, leaves: np.ndarray, depth: int):
+        """host leaves -> (nodes (zl_poseidon_merkle_nodes, 4), root (4,))"""
+        return _poseidon_merkle_build(self.L, self._ctx, curve, leaves, depth)
+
+    def poseidon_merkle_build_dev(self, curve: int, d_leaves: int, n: int, depth: int, d_nodes: int) -> np.ndarray:
+        """zl_poseidon_merkle_build_dev: every level into the device node array at d_nodes (poseidon_merkle_nodes(n, depth) elements); returns the root"""
+        root = np.zeros(4, dtype=np.uint64)
+        self._check(self.L.zl_poseidon_merkle_build_dev(self._ctx, curve, C.c_void_p(d_leaves), n, depth, C.c_void_p(d_nodes), _p64(root)), "zl_poseidon_merkle_build_dev")
+        return root
+
+    def poseidon_merkle_paths(self, curve: int, d_nodes: int, n: int, depth: int, indices) -> np.ndarray:
+        """(count, depth, 4) sibling digests of the leaves `indices`, bottom up, gathered from the device node array"""
+        idx = np.ascontiguousarray(indices, dtype=np.uint64).reshape(-1)
+        paths = np.zeros((max(1, idx.size), depth, 4), dtype=np.uint64)
+        self._check(self.L.zl_poseidon_merkle_paths_dev(self._ctx, curve, C.c_void_p(d_nodes), n, depth, _p64(idx) if idx.size else None, idx.size, _p64(paths)),
+                    "zl_poseidon_merkle_paths_dev")
+        return paths[: idx.size]
+
+    def poseidon_merkle_roots_from_paths(self, curve: int, leaves: np.ndarray, indices, paths: np.ndarray, depth: int) -> np.ndarray:
+        return _poseidon_roots_from_paths(self.L, self._ctx, curve, leaves, indices, paths, depth)
 
     # ---- Groth16 ----------------------------------------------------------------------------------------------
     def groth16_prove(self, curve: int, pk: dict, r1cs: dict, assignment: np.ndarray, r: np.ndarray, s: np.ndarray):
@@ -1007,6 +1063,107 @@ def poseidon_permute(curve: int, state: np.ndarray) -> np.ndarray:
     if rc:
         raise BackendError(rc, "zl_poseidon_permute")
     return st
+
+
+# ---- batched Poseidon: one implementation per call for Backend (its ctx) and for the host forms below (ctx == NULL: host thread pool, no device) ----
+def _pos_check(L, rc: int, what: str):
+    if rc != 0:
+        raise BackendError(rc, what, L.zl_strerror(rc).decode())
+
+
+def _elems(a, per: int) -> np.ndarray:
+    """contiguous (count, per, 4) uint64 copy-or-view of canonical field elements"""
+    return np.ascontiguousarray(np.asarray(a, dtype=np.uint64).reshape(-1, per, 4))
+
+
+def _ptr_or_none(a: np.ndarray):
+    return _p64(a) if a.size else None
+
+
+def _poseidon_permute_batch(L, ctx, curve: int, states) -> np.ndarray:
+    st = _elems(states, 3).copy()
+    _pos_check(L, L.zl_poseidon_permute_batch(ctx, curve, _ptr_or_none(st), st.shape[0]), "zl_poseidon_permute_batch")
+    return st
+
+
+def _poseidon_hash2(L, ctx, curve: int, xy) -> np.ndarray:
+    v = _elems(xy, 2)
+    out = np.zeros((v.shape[0], 4), dtype=np.uint64)
+    _pos_check(L, L.zl_poseidon_hash2_batch(ctx, curve, _ptr_or_none(v), v.shape[0], _ptr_or_none(out)), "zl_poseidon_hash2_batch")
+    return out
+
+
+def _poseidon_chain(L, ctx, curve: int, x0, x1, k: int) -> np.ndarray:
+    a, b = _elems(x0, 1), _elems(x1, 1)
+    assert a.shape == b.shape
+    out = np.zeros((a.shape[0], 4), dtype=np.uint64)
+    _pos_check(L, L.zl_poseidon_chain_batch(ctx, curve, _ptr_or_none(a), _ptr_or_none(b), k, a.shape[0], _ptr_or_none(out)), "zl_poseidon_chain_batch")
+    return out
+
+
+def _poseidon_merkle_root(L, ctx, curve: int, leaves, depth: int) -> np.ndarray:
+    lv = _elems(leaves, 1)
+    root = np.zeros(4, dtype=np.uint64)
+    _pos_check(L, L.zl_poseidon_merkle_root(ctx, curve, _ptr_or_none(lv), lv.shape[0], depth, _p64(root)), "zl_poseidon_merkle_root")
+    return root
+
+
+def _poseidon_merkle_build(L, ctx, curve: int, leaves, depth: int):
+    lv = _elems(leaves, 1)
+    nodes = np.zeros((L.zl_poseidon_merkle_nodes(lv.shape[0], depth), 4), dtype=np.uint64)
+    root = np.zeros(4, dtype=np.uint64)
+    _pos_check(L, L.zl_poseidon_merkle_build(ctx, curve, _ptr_or_none(lv), lv.shape[0], depth, _ptr_or_none(nodes), _p64(root)), "zl_poseidon_merkle_build")
+    return nodes, root
+
+
+def _poseidon_roots_from_paths(L, ctx, curve: int, leaves, indices, paths, depth: int) -> np.ndarray:
+    lv = _elems(leaves, 1)
+    idx = np.ascontiguousarray(indices, dtype=np.uint64).reshape(-1)
+    pa = np.ascontiguousarray(np.asarray(paths, dtype=np.uint64).reshape(-1, depth, 4))
+    assert lv.shape[0] == idx.size == pa.shape[0]
+    roots = np.zeros((idx.size, 4), dtype=np.uint64)
+    _pos_check(L, L.zl_poseidon_merkle_roots_from_paths(ctx, curve, _ptr_or_none(lv), _ptr_or_none(idx), _ptr_or_none(pa), depth, idx.size, _ptr_or_none(roots)),
+               "zl_poseidon_merkle_roots_from_paths")
+    return roots
+
+
+def poseidon_merkle_nodes(n: int, depth: int) -> int:
+    """elements of the node array of a tree over n leaves with `depth` hash levels (0 for an invalid shape)"""
+    return int(load_library().zl_poseidon_merkle_nodes(n, depth))
+
+
+def poseidon_permute_batch_host(curve: int, states) -> np.ndarray:
+    return _poseidon_permute_batch(load_library(), None, curve, states)
+
+
+def poseidon_hash2_host(curve: int, xy) -> np.ndarray:
+    return _poseidon_hash2(load_library(), None, curve, xy)
+
+
+def poseidon_chain_host(curve: int, x0, x1, k: int) -> np.ndarray:
+    return _poseidon_chain(load_library(), None, curve, x0, x1, k)
+
+
+def poseidon_merkle_root_host(curve: int, leaves, depth: int) -> np.ndarray:
+    return _poseidon_merkle_root(load_library(), None, curve, leaves, depth)
+
+
+def poseidon_merkle_build_host(curve: int, leaves, depth: int):
+    return _poseidon_merkle_build(load_library(), None, curve, leaves, depth)
+
+
+def poseidon_merkle_paths_host(nodes: np.ndarray, n: int, depth: int, indices) -> np.ndarray:
+    """zl_poseidon_merkle_paths: the gather of Backend.poseidon_merkle_paths over a node array in host memory"""
+    L = load_library()
+    nd = _elems(nodes, 1)
+    idx = np.ascontiguousarray(indices, dtype=np.uint64).reshape(-1)
+    paths = np.zeros((max(1, idx.size), depth, 4), dtype=np.uint64)
+    _pos_check(L, L.zl_poseidon_merkle_paths(_ptr_or_none(nd), n, depth, _ptr_or_none(idx), idx.size, _p64(paths)), "zl_poseidon_merkle_paths")
+    return paths[: idx.size]
+
+
+def poseidon_roots_from_paths_host(curve: int, leaves, indices, paths, depth: int) -> np.ndarray:
+    return _poseidon_roots_from_paths(load_library(), None, curve, leaves, indices, paths, depth)
 
 
 def pairing_product(backend: "Backend", curve: int, ps: np.ndarray, qs: np.ndarray) -> np.ndarray:

@@ -133,6 +133,8 @@ struct zl_scratch {
 //     each other on ctx->stream.  Its own slot: a caller may hold scalars for it in any other block of the ctx.
 //   * ZL_SLOT_G16_BATCH: one chunk of zl_groth16_prove_batch (zl_groth16.hip): the assignments, the witness map's [3][chunk][N] vectors and the three scalar
 //     matrices its multi-MSMs read; the transforms in between use ZL_SLOT_NTT_VEC, the multi-MSMs ZL_SLOT_MSM_MULTI, one after the other on ctx->stream.
+//   * ZL_SLOT_POSEIDON: the flag word and one staged chunk (inputs, outputs) of the batched Poseidon entry points (zl_poseidon_dev.hip), under a byte budget;
+//     the chunks of a call follow each other on ctx->stream.  Its own slot: a caller may hold device operands for the _dev forms in any other block.
 enum zl_slot : int {
     ZL_SLOT_SET0_COUNTS = 0, ZL_SLOT_SET0_ENTRIES = 1, ZL_SLOT_SET0_BUCKETS = 2, ZL_SLOT_SET0_PARTIALS = 3, ZL_SLOT_SET0_TAIL = 4,
     ZL_SLOT_SORT_A = 5, ZL_SLOT_SORT_B = 6,
@@ -151,7 +153,8 @@ enum zl_slot : int {
     ZL_SLOT_DECODE_IN = 40, ZL_SLOT_DECODE_OUT = 41,
     ZL_SLOT_MSM_MULTI = 42, ZL_SLOT_G16_BATCH = 43,
     ZL_SLOT_PAIR_FEXP = 44,
-    ZL_SLOT_COUNT = 45
+    ZL_SLOT_POSEIDON = 45,
+    ZL_SLOT_COUNT = 46
 };
 // the slots of MSM buffer set 0..3; sort_a / sort_b are used by a job that owns its sort (side by side), every other job sorts in set 0's pair
 struct zl_msm_set_slots {
@@ -172,7 +175,7 @@ constexpr bool zl_slots_disjoint() {
             owners[x]++;
         }
     for (zl_slot x : {ZL_SLOT_PHI_ONE_KEY, ZL_SLOT_STAGING, ZL_SLOT_GROTH16, ZL_SLOT_TESTHOOK, ZL_SLOT_PAIR_IN, ZL_SLOT_PAIR_LINES, ZL_SLOT_PAIR_ACC, ZL_SLOT_PAIR_PREP,
-                      ZL_SLOT_DECODE_IN, ZL_SLOT_DECODE_OUT, ZL_SLOT_MSM_MULTI, ZL_SLOT_G16_BATCH, ZL_SLOT_PAIR_FEXP}) {
+                      ZL_SLOT_DECODE_IN, ZL_SLOT_DECODE_OUT, ZL_SLOT_MSM_MULTI, ZL_SLOT_G16_BATCH, ZL_SLOT_PAIR_FEXP, ZL_SLOT_POSEIDON}) {
         if (x < 0 || x >= ZL_SLOT_COUNT) return false;
         owners[x]++;
     }
@@ -253,6 +256,7 @@ struct zl_ctx {
     void* g16_h = nullptr;  // quotient polynomial of the last zl_groth16_prove (inside ZL_SLOT_GROTH16; reset when the next proof starts)
     size_t g16_h_n = 0;
     int ntt_fit_beside = 0;  // this ctx's transforms run beside a kernel that leaves 96 registers per SIMD (a proof's witness map: ctx->aux2): use the capped passes (zl_ntt.hip)
+    void* poseidon_tab[2] = {nullptr, nullptr};  // Poseidon round keys, MDS entries and the domain tag in Montgomery form, per curve (zl_poseidon_dev.hip): built once by the ROOT ctx, read by its forks, freed at destroy
     void* g16_z = nullptr;  // the canonical assignment of the last witness-map-only run (sharded proofs: the other ranks copy their slices from here)
     // MEASUREMENT ONLY (zl_test_acc_clock): when non-null, large G1 accumulations run as k_msm_accumulate_clk and leave four clock reads per wave here
     void* acc_clk = nullptr;

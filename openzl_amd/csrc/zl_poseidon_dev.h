@@ -1,0 +1,36 @@
+// zl_poseidon_dev.h -- internal layout and limits of the batched Poseidon unit (zl_poseidon_dev.hip): the device constant table, the knob defaults and the
+// Merkle node-array geometry shared by the host path, the device path and the gather.
+#pragma once
+#include <stddef.h>
+#include <stdint.h>
+
+namespace openzl {
+namespace poseidon_dev {
+constexpr int WIDTH = 3, FULL_ROUNDS = 8, PARTIAL_ROUNDS = 55, ROUNDS = FULL_ROUNDS + PARTIAL_ROUNDS;
+// the device table of one curve: entries of TAB_WORDS u32 slots holding the nine 29-bit limbs of x R' mod r (R' = 2^261: the device multiplier's own Montgomery form)
+constexpr int TAB_KEYS = 0;                     // 189 round keys, [3 * round + lane]
+constexpr int TAB_MDS = WIDTH * ROUNDS;         // 9 MDS entries, [3 * row + column]
+constexpr int TAB_TAG = TAB_MDS + WIDTH * WIDTH;  // the arity-2 domain tag 3
+constexpr int TAB_ENTRIES = TAB_TAG + 1;
+constexpr int TAB_WORDS = 10;
+constexpr size_t TAB_BYTES = (size_t)TAB_ENTRIES * TAB_WORDS * 4;
+
+constexpr unsigned MAX_DEPTH = 40;
+constexpr int TAIL_MAX = 1024;       // nodes the one-workgroup tail kernel can take over: (T + T / 2) x 32 B of LDS = 48 KB
+constexpr int TAIL_BLOCK = 256;
+// knob defaults: ZL_TUNE_POSEIDON_CHUNK / _TAIL / _DEV_MIN (README).  TAIL and DEV_MIN rest on MEASUREMENTS (profiles/poseidon_bench.log): DEV_MIN is
+// the smallest power of two from which the device won every repetition against the host path on both curves; for TAIL every value up to 256 lies inside the
+// run-to-run spread on a 2^20-leaf build (a level is ~0.45 ms of dependent arithmetic, not launch overhead) and 256 is the largest one round of the workgroup covers.
+constexpr int DEFAULT_CHUNK = 1 << 20, DEFAULT_TAIL = 256, DEFAULT_DEV_MIN = 64;
+constexpr size_t STAGE_BUDGET = (size_t)256 << 20;  // bytes of ZL_SLOT_POSEIDON one staged chunk may take
+constexpr size_t FLAG_BYTES = 256;                  // the flag word's corner of the slot
+
+constexpr bool geometry_ok(size_t n, unsigned depth) { return depth >= 1 && depth <= MAX_DEPTH && ((n >> depth) == 0 || n == ((size_t)1 << depth)); }
+constexpr size_t level_size(size_t n, unsigned k) { return k >= 64 ? (n ? 1 : 0) : (n >> k) + ((n & (((size_t)1 << k) - 1)) ? 1 : 0); }  // ceil(n / 2^k)
+constexpr size_t level_offset(size_t n, unsigned k) {  // elements in front of level k
+    size_t off = 0;
+    for (unsigned l = 0; l < k; l++) off += level_size(n, l);
+    return off;
+}
+}  // namespace poseidon_dev
+}  // namespace openzl

@@ -1,0 +1,766 @@
+// zl_poseidon_dev.hip -- batched Poseidon on the device (include/zl_backend_ext.h): many width-3 permutations, arity-2 hashes, hash chains
+// and Merkle trees per call, one lane per permutation, with a host path (the host mirror's permute_native over the library's thread pool) behind the same
+// entry points.  One unit for both scalar fields; built with the multiplier inlined (ZL_INLINE_MUL_DEVICE).
+//
+// Kernels (all templates over the scalar-field parameters FrP):
+//   k_pos_permute / k_pos_hash2 / k_pos_chain / k_pos_fold / k_pos_level   one lane per permutation (chain and fold: per chain / path, the dependent hashes in a
+//                    loop inside the lane).  Thin wrappers around ONE __device__ permutation, permute_dev: the three state elements stay in registers for
+//                    all 63 rounds; round keys, MDS entries and the domain tag come from a 199-entry device table (zl_poseidon_dev.h) at wave-uniform
+//                    addresses -- the compiler reads them with uniform loads -- already in the multiplier's Montgomery form (x R', R' = 2^261).
+//   k_pos_tail       one workgroup finishes ALL remaining levels of a Merkle tree once a level has at most T nodes: the level lives in LDS (two buffers,
+//                    canonical words), __syncthreads() between levels, every level is also written to the node array at the offsets the wide path uses.
+//   k_pos_gather     sibling digests of `count` leaves out of a device node array.
+// Arithmetic: the lazily reduced 9 x 29-bit Fr of zl_field28r.h (the NTT's multiplier), 1.29 - 1.46 x the carry-chain Fp<FrP> here and ahead of the 10 x 28 form at
+// every size measured (profiles/poseidon_field_ab.log); the bound argument stands beside the type below.  The host path stays on Fp<FrP>.
+// A lane at or above the item count returns before it reads or writes anything.  An input element >= r sets the flag word (atomicOr) and the lane goes on with
+// the value as it is: the conversion product takes any 256-bit operand within its bound, the result is then meaningless and the call returns ZL_EINVAL.
+#include <string.h>
+#include <atomic>
+#include <functional>
+#include <memory>
+#include <mutex>
+#include <new>
+#include <type_traits>
+#include <vector>
+#include "zl_ctx.h"
+#include "zl_host.h"
+#include "zl_poseidon_dev.h"
+#include "zl_field28r.h"
+
+using namespace openzl;
+namespace pd = openzl::poseidon_dev;
+
+namespace {
+// ---------------------------------------------------------------------------------------------------------------- element I/O of the host path (Fp<FrP>)
+// canonical u64 words -> Montgomery; false when the value is not below r
+template <class FrP>
+ZL_HD bool load_canon(const uint64_t* w, Fp<FrP>& out) {
+    static_assert(FrP::N == 8, "scalar fields are 8 x 32 bits");
+    Fp<FrP> c;
+#pragma unroll
+    for (int i = 0; i < 4; i++) {
+        c.l[2 * i] = (uint32_t)w[i];
+        c.l[2 * i + 1] = (uint32_t)(w[i] >> 32);
+    }
+    uint64_t br = 0;
+#pragma unroll
+    for (int i = 0; i < 8; i++) br = (((uint64_t)c.l[i] - FrP::mod(i) - br) >> 32) & 1;
+    out = zl::to_mont(c);
+    return br != 0;
+}
+template <class FrP>
+ZL_HD void store_canon(uint64_t* w, const Fp<FrP>& m) {
+    const Fp<FrP> c = zl::from_mont(m);
+#pragma unroll
+    for (int i = 0; i < 4; i++) w[i] = (uint64_t)c.l[2 * i] | ((uint64_t)c.l[2 * i + 1] << 32);
+}
+
+
+// ---------------------------------------------------------------------------------------------------------------- the device field: 9 x 29-bit lazy Fr
+// zl_field28r.h's 9 x 29 instance (R' = 2^261), chosen by an interleaved A/B against the carry-chain Fp<FrP> and the 10 x 28 instance (profiles/poseidon_field_ab.log).
+// Everything is kept as x R' in the multiplier's own Montgomery form and is only BOUNDED, never compared with r, until the final canon.  Bounds in units of r
+// (the argument above k_test_poseidon28r, restated for these kernels):
+//   * a product is < 2r; a loaded element is mul(c, R'^2) with c < 2^256 < 5.3 r (BN254; 2.3 r on BLS12-381) and R'^2 mod r < r: < 2r, canonical or not;
+//   * a table entry (round key, MDS entry, tag) is < 2r; an MDS row is a sum of three products: < 6r;
+//   * a state element entering a round is < 6r (from the MDS product, or the digest of the previous hash of a chain / fold / tree level) or < 2r (loaded);
+//     plus its round key: < 8r.  S-box: x^2 = mul(x, x) needs 8 * 8 = 64, x^4 = mul(x^2, x^2) 2 * 2, x^5 = mul(x^4, x) 2 * 8; the MDS product multiplies an
+//     entry < 2r by an element < 8r (the lanes a partial round leaves without S-box): 16.  The largest requirement, 64, is within MUL_BOUND of both fields
+//     (70 and 169: the static_assert below);
+//   * sums stay below 8r < 2^259: far inside the 261 bits of nine limbs and wred's limit of 128 r; the output is canon(mul(x, 1)): a product < 2r.
+template <class FrP> struct LazyP;
+template <> struct LazyP<BLS12_381_Fr> { using P = BLS12_381_Fr29; };
+template <> struct LazyP<BN254_Fr> { using P = BN254_Fr29; };
+template <class FrP> using El = Fr28<typename LazyP<FrP>::P>;
+static_assert(BLS12_381_Fr29::MUL_BOUND >= 64 && BN254_Fr29::MUL_BOUND >= 64, "x^2 of a state element < 8r needs B(a) B(b) = 64");
+constexpr int TABW = pd::TAB_WORDS;  // u32 words per table entry (nine limbs used)
+static_assert(El<BLS12_381_Fr>::L <= TABW && El<BN254_Fr>::L <= TABW, "a table entry holds every limb");
+template <class FrP>
+ZL_HD El<FrP> ezero() { El<FrP> r; for (int i = 0; i < El<FrP>::L; i++) r.l[i] = 0; return r; }
+template <class FrP>
+ZL_HD El<FrP> to_lazy(const uint32_t* c) {  // 8 x 32-bit words of a value < 2^256 -> x R' (< 2r)
+    using P = typename LazyP<FrP>::P;
+    uint32_t rp[8];
+    for (int k = 0; k < 8; k++) rp[k] = P::rp2(k);
+    return zl::mul(zl::unpack28r<P>(c), zl::unpack28r<P>(rp));
+}
+template <class FrP>
+__device__ __forceinline__ bool dload(const uint64_t* w, El<FrP>& out) {
+    uint32_t c[8];
+#pragma unroll
+    for (int i = 0; i < 4; i++) { c[2 * i] = (uint32_t)w[i]; c[2 * i + 1] = (uint32_t)(w[i] >> 32); }
+    uint64_t br = 0;
+#pragma unroll
+    for (int i = 0; i < 8; i++) br = (((uint64_t)c[i] - FrP::mod(i) - br) >> 32) & 1;
+    out = to_lazy<FrP>(c);
+    return br != 0;
+}
+template <class FrP>
+__device__ __forceinline__ void dstore(uint64_t* w, const El<FrP>& m) {
+    using P = typename LazyP<FrP>::P;
+    uint32_t o[8] = {1, 0, 0, 0, 0, 0, 0, 0};
+    const El<FrP> c = zl::canon(zl::mul(m, zl::unpack28r<P>(o)));
+    uint32_t v[8];
+    zl::pack28r<P>(v, c);
+#pragma unroll
+    for (int i = 0; i < 4; i++) w[i] = (uint64_t)v[2 * i] | ((uint64_t)v[2 * i + 1] << 32);
+}
+// ---------------------------------------------------------------------------------------------------------------- the device permutation
+template <class FrP>
+__device__ __forceinline__ El<FrP> tab_ld(const uint32_t* __restrict__ tab, int entry) {
+    El<FrP> r;
+#pragma unroll
+    for (int k = 0; k < El<FrP>::L; k++) r.l[k] = tab[entry * TABW + k];
+    return r;
+}
+template <class FrP>
+__device__ __forceinline__ void sbox(El<FrP>& x) {
+    const El<FrP> x2 = zl::mul(x, x), x4 = zl::mul(x2, x2);
+    x = zl::mul(x4, x);
+}
+// 63 rounds of add-round-key / x^5 / MDS: 8 * (9 + 9) + 55 * (3 + 9) = 804 multiplications.  One rolled loop (18 inlined multiplier bodies), the full / partial
+// choice is a wave-uniform branch.
+template <class FrP>
+__device__ __forceinline__ void permute_dev(const uint32_t* __restrict__ tab, El<FrP>& s0, El<FrP>& s1, El<FrP>& s2) {
+    constexpr int half = pd::FULL_ROUNDS / 2;
+#pragma unroll 1
+    for (int rnd = 0; rnd < pd::ROUNDS; rnd++) {
+        s0 = zl::add(s0, tab_ld<FrP>(tab, pd::TAB_KEYS + 3 * rnd));
+        s1 = zl::add(s1, tab_ld<FrP>(tab, pd::TAB_KEYS + 3 * rnd + 1));
+        s2 = zl::add(s2, tab_ld<FrP>(tab, pd::TAB_KEYS + 3 * rnd + 2));
+        sbox<FrP>(s0);
+        if (rnd < half || rnd >= half + pd::PARTIAL_ROUNDS) {
+            sbox<FrP>(s1);
+            sbox<FrP>(s2);
+        }
+        El<FrP> nx[3];
+#pragma unroll
+        for (int i = 0; i < 3; i++) {
+            El<FrP> acc = zl::mul(tab_ld<FrP>(tab, pd::TAB_MDS + 3 * i), s0);
+            acc = zl::add(acc, zl::mul(tab_ld<FrP>(tab, pd::TAB_MDS + 3 * i + 1), s1));
+            nx[i] = zl::add(acc, zl::mul(tab_ld<FrP>(tab, pd::TAB_MDS + 3 * i + 2), s2));
+        }
+        s0 = nx[0];
+        s1 = nx[1];
+        s2 = nx[2];
+    }
+}
+// H(x, y) on Montgomery operands
+template <class FrP>
+__device__ __forceinline__ El<FrP> hash2_dev(const uint32_t* __restrict__ tab, const El<FrP>& x, const El<FrP>& y) {
+    El<FrP> s0 = tab_ld<FrP>(tab, pd::TAB_TAG), s1 = x, s2 = y;
+    permute_dev<FrP>(tab, s0, s1, s2);
+    return s0;
+}
+
+// ---------------------------------------------------------------------------------------------------------------- kernels
+constexpr int BLOCK = 64;
+
+template <class FrP>
+__global__ __launch_bounds__(BLOCK) void k_pos_permute(const uint32_t* __restrict__ tab, uint64_t* __restrict__ states, size_t n, uint32_t* __restrict__ flag) {
+    const size_t p = (size_t)blockIdx.x * BLOCK + threadIdx.x;
+    if (p >= n) return;
+    uint64_t* st = states + p * 12;
+    El<FrP> s0, s1, s2;
+    bool ok = dload<FrP>(st, s0);
+    ok &= dload<FrP>(st + 4, s1);
+    ok &= dload<FrP>(st + 8, s2);
+    if (!ok) atomicOr(flag, 1u);
+    permute_dev<FrP>(tab, s0, s1, s2);
+    dstore<FrP>(st, s0);
+    dstore<FrP>(st + 4, s1);
+    dstore<FrP>(st + 8, s2);
+}
+template <class FrP>
+__global__ __launch_bounds__(BLOCK) void k_pos_hash2(const uint32_t* __restrict__ tab, const uint64_t* __restrict__ xy, size_t n, uint64_t* __restrict__ out,
+                                                     uint32_t* __restrict__ flag) {
+    const size_t p = (size_t)blockIdx.x * BLOCK + threadIdx.x;
+    if (p >= n) return;
+    El<FrP> x, y;
+    bool ok = dload<FrP>(xy + p * 8, x);
+    ok &= dload<FrP>(xy + p * 8 + 4, y);
+    if (!ok) atomicOr(flag, 1u);
+    dstore<FrP>(out + p * 4, hash2_dev<FrP>(tab, x, y));
+}
+template <class FrP>
+__global__ __launch_bounds__(BLOCK) void k_pos_chain(const uint32_t* __restrict__ tab, const uint64_t* __restrict__ x0, const uint64_t* __restrict__ x1, uint32_t k,
+                                                     size_t n, uint64_t* __restrict__ out, uint32_t* __restrict__ flag) {
+    const size_t p = (size_t)blockIdx.x * BLOCK + threadIdx.x;
+    if (p >= n) return;
+    El<FrP> h, b;
+    bool ok = dload<FrP>(x0 + p * 4, h);
+    ok &= dload<FrP>(x1 + p * 4, b);
+    if (!ok) atomicOr(flag, 1u);
+#pragma unroll 1
+    for (uint32_t j = 0; j < k; j++) h = hash2_dev<FrP>(tab, h, b);
+    dstore<FrP>(out + p * 4, h);
+}
+// one lane per path: `depth` dependent hashes, the running digest on the right when the index bit of the level is set
+template <class FrP>
+__global__ __launch_bounds__(BLOCK) void k_pos_fold(const uint32_t* __restrict__ tab, const uint64_t* __restrict__ leaves, const uint64_t* __restrict__ indices,
+                                                    const uint64_t* __restrict__ paths, unsigned depth, size_t n, uint64_t* __restrict__ roots,
+                                                    uint32_t* __restrict__ flag) {
+    const size_t p = (size_t)blockIdx.x * BLOCK + threadIdx.x;
+    if (p >= n) return;
+    El<FrP> cur;
+    bool ok = dload<FrP>(leaves + p * 4, cur);
+    const uint64_t idx = indices[p];
+    const uint64_t* path = paths + p * (size_t)depth * 4;
+#pragma unroll 1
+    for (unsigned k = 0; k < depth; k++) {
+        El<FrP> sib;
+        ok &= dload<FrP>(path + (size_t)k * 4, sib);
+        const bool right = (idx >> k) & 1;
+        El<FrP> x, y;
+#pragma unroll
+        for (int w = 0; w < El<FrP>::L; w++) {
+            x.l[w] = right ? sib.l[w] : cur.l[w];
+            y.l[w] = right ? cur.l[w] : sib.l[w];
+        }
+        cur = hash2_dev<FrP>(tab, x, y);
+    }
+    if (!ok) atomicOr(flag, 1u);
+    dstore<FrP>(roots + p * 4, cur);
+}
+// one Merkle level, wide: parent j of [first, first + n) = H(child 2j, child 2j + 1 or zero)
+template <class FrP>
+__global__ __launch_bounds__(BLOCK) void k_pos_level(const uint32_t* __restrict__ tab, const uint64_t* __restrict__ child, size_t n_child, uint64_t* __restrict__ parent,
+                                                     size_t first, size_t n, uint32_t* __restrict__ flag) {
+    const size_t p = (size_t)blockIdx.x * BLOCK + threadIdx.x;
+    if (p >= n) return;
+    const size_t j = first + p;
+    El<FrP> x, y = ezero<FrP>();
+    bool ok = dload<FrP>(child + 2 * j * 4, x);
+    if (2 * j + 1 < n_child) ok &= dload<FrP>(child + (2 * j + 1) * 4, y);
+    if (!ok) atomicOr(flag, 1u);
+    dstore<FrP>(parent + j * 4, hash2_dev<FrP>(tab, x, y));
+}
+// one workgroup, every level above `level` (m <= TAIL_MAX nodes at `level`, which starts the node range this kernel owns): LDS buffer A holds m nodes, B the
+// ceil(m / 2) parents; the buffers swap per level.  Level l + 1 goes to level + off, off = the nodes of the levels in front of it, as in the wide path.
+template <class FrP>
+__global__ __launch_bounds__(pd::TAIL_BLOCK) void k_pos_tail(const uint32_t* __restrict__ tab, uint64_t* __restrict__ level, unsigned m, unsigned levels,
+                                                             uint32_t* __restrict__ flag) {
+    extern __shared__ uint64_t lds[];
+    uint64_t* cur = lds;
+    uint64_t* nxt = lds + (size_t)m * 4;
+    for (unsigned i = threadIdx.x; i < m * 4; i += pd::TAIL_BLOCK) cur[i] = level[i];
+    size_t off = m;
+    unsigned cm = m;
+    for (unsigned l = 0; l < levels; l++) {
+        const unsigned pm = (cm + 1) / 2;
+        __syncthreads();
+        for (unsigned j = threadIdx.x; j < pm; j += pd::TAIL_BLOCK) {
+            El<FrP> x, y = ezero<FrP>();
+            bool ok = dload<FrP>(cur + 2 * j * 4, x);
+            if (2 * j + 1 < cm) ok &= dload<FrP>(cur + (2 * j + 1) * 4, y);
+            if (!ok) atomicOr(flag, 1u);
+            uint64_t w[4];
+            dstore<FrP>(w, hash2_dev<FrP>(tab, x, y));
+#pragma unroll
+            for (int i = 0; i < 4; i++) {
+                nxt[j * 4 + i] = w[i];
+                level[(off + j) * 4 + i] = w[i];
+            }
+        }
+        off += pm;
+        cm = pm;
+        uint64_t* t = cur;
+        cur = nxt;
+        nxt = t;
+    }
+}
+struct LevelTable {
+    uint64_t off[pd::MAX_DEPTH], size[pd::MAX_DEPTH];  // of levels 0 .. depth - 1: where a leaf's siblings live
+};
+// thread t = path t / depth, level t % depth: the sibling of (index >> level), zero where the tree has no such node
+__global__ __launch_bounds__(BLOCK) void k_pos_gather(const uint64_t* __restrict__ nodes, LevelTable lt, unsigned depth, const uint64_t* __restrict__ indices, size_t total,
+                                                      uint64_t* __restrict__ paths) {
+    const size_t t = (size_t)blockIdx.x * BLOCK + threadIdx.x;
+    if (t >= total) return;
+    const size_t p = t / depth;
+    const unsigned k = (unsigned)(t % depth);
+    const uint64_t sib = (indices[p] >> k) ^ 1;
+    const bool present = sib < lt.size[k];
+#pragma unroll
+    for (int i = 0; i < 4; i++) paths[t * 4 + i] = present ? nodes[(lt.off[k] + sib) * 4 + i] : 0;
+}
+
+// ---------------------------------------------------------------------------------------------------------------- host path
+template <class FrP>
+const poseidon::Constants<FrP>& consts() {
+    static const poseidon::Constants<FrP> c;
+    return c;
+}
+template <class FrP>
+bool host_hash2(const uint64_t* x, const uint64_t* y, uint64_t* out) {  // y == nullptr: the zero digest
+    Fp<FrP> st[3] = {zl::from_u64<FrP>(3), Fp<FrP>::zero(), Fp<FrP>::zero()};
+    bool ok = load_canon<FrP>(x, st[1]);
+    if (y) ok &= load_canon<FrP>(y, st[2]);
+    poseidon::permute_native(consts<FrP>(), st);
+    store_canon<FrP>(out, st[0]);
+    return ok;
+}
+// f(0) .. f(n - 1) over the host pool in blocks; false when any f returned false
+template <class Fn>
+bool host_for(size_t n, const Fn& f) {
+    constexpr size_t B = 32;
+    std::atomic<int> bad{0};
+    const std::function<void(size_t)> g = [&](size_t b) {
+        const size_t end = (b + 1) * B < n ? (b + 1) * B : n;
+        bool ok = true;
+        for (size_t i = b * B; i < end; i++) ok &= f(i);
+        if (!ok) bad.store(1);
+    };
+    zl_pool_get().parallel_for((n + B - 1) / B, g);
+    return bad.load() == 0;
+}
+template <class FrP>
+int host_permute(uint64_t* states, size_t count) {
+    consts<FrP>();  // (built before the pool's threads ask for it)
+    return host_for(count, [&](size_t i) {
+        Fp<FrP> st[3];
+        bool ok = true;
+        for (int e = 0; e < 3; e++) ok &= load_canon<FrP>(states + i * 12 + 4 * e, st[e]);
+        poseidon::permute_native(consts<FrP>(), st);
+        for (int e = 0; e < 3; e++) store_canon<FrP>(states + i * 12 + 4 * e, st[e]);
+        return ok;
+    }) ? ZL_OK : ZL_EINVAL;
+}
+template <class FrP>
+int host_hash2_batch(const uint64_t* xy, size_t count, uint64_t* out) {
+    consts<FrP>();
+    return host_for(count, [&](size_t i) { return host_hash2<FrP>(xy + i * 8, xy + i * 8 + 4, out + i * 4); }) ? ZL_OK : ZL_EINVAL;
+}
+template <class FrP>
+int host_chain(const uint64_t* x0, const uint64_t* x1, uint32_t k, size_t count, uint64_t* out) {
+    consts<FrP>();
+    return host_for(count, [&](size_t i) {
+        Fp<FrP> h, b;
+        bool ok = load_canon<FrP>(x0 + i * 4, h);
+        ok &= load_canon<FrP>(x1 + i * 4, b);
+        for (uint32_t j = 0; j < k; j++) {
+            Fp<FrP> st[3] = {zl::from_u64<FrP>(3), h, b};
+            poseidon::permute_native(consts<FrP>(), st);
+            h = st[0];
+        }
+        store_canon<FrP>(out + i * 4, h);
+        return ok;
+    }) ? ZL_OK : ZL_EINVAL;
+}
+// every level into `nodes` (level 0 = the leaves)
+template <class FrP>
+int host_merkle(const uint64_t* leaves, size_t n, unsigned depth, uint64_t* nodes) {
+    consts<FrP>();
+    if (n && nodes != leaves) memcpy(nodes, leaves, n * 32);
+    bool ok = true;
+    size_t off = 0, cm = n;
+    for (unsigned k = 1; k <= depth && cm; k++) {
+        const size_t pm = (cm + 1) / 2;
+        const uint64_t* child = nodes + off * 4;
+        uint64_t* parent = nodes + (off + cm) * 4;
+        ok &= host_for(pm, [&](size_t j) { return host_hash2<FrP>(child + 2 * j * 4, 2 * j + 1 < cm ? child + (2 * j + 1) * 4 : nullptr, parent + j * 4); });
+        off += cm;
+        cm = pm;
+    }
+    return ok ? ZL_OK : ZL_EINVAL;
+}
+template <class FrP>
+int host_fold(const uint64_t* leaves, const uint64_t* indices, const uint64_t* paths, unsigned depth, size_t count, uint64_t* roots) {
+    consts<FrP>();
+    return host_for(count, [&](size_t i) {
+        uint64_t cur[4];
+        memcpy(cur, leaves + i * 4, 32);
+        bool ok = true;
+        for (unsigned k = 0; k < depth; k++) {
+            const uint64_t* sib = paths + (i * depth + k) * 4;
+            uint64_t nx[4];
+            ok &= ((indices[i] >> k) & 1) ? host_hash2<FrP>(sib, cur, nx) : host_hash2<FrP>(cur, sib, nx);
+            memcpy(cur, nx, 32);
+        }
+        memcpy(roots + i * 4, cur, 32);
+        return ok;
+    }) ? ZL_OK : ZL_EINVAL;
+}
+
+// ---------------------------------------------------------------------------------------------------------------- device path: table, staging, launches
+bool valid_curve(zl_curve_t c) { return c == ZL_BLS12_381 || c == ZL_BN254; }
+size_t tune_chunk() {
+    const int c = zl_tune("ZL_TUNE_POSEIDON_CHUNK", pd::DEFAULT_CHUNK);
+    return c < 1 ? 1 : c > (1 << 24) ? (size_t)1 << 24 : (size_t)c;  // (a launch of 2^24 / 64 blocks at the most)
+}
+unsigned tune_tail() {
+    const int t = zl_tune("ZL_TUNE_POSEIDON_TAIL", pd::DEFAULT_TAIL);
+    return t < 0 ? 0u : t > pd::TAIL_MAX ? (unsigned)pd::TAIL_MAX : (unsigned)t;
+}
+bool on_host(const zl_ctx* ctx, size_t count) {
+    if (!ctx) return true;
+    const int m = zl_tune("ZL_TUNE_POSEIDON_DEV_MIN", pd::DEFAULT_DEV_MIN);
+    return m > 0 && count < (size_t)m;
+}
+// staged items per chunk: the launch chunk, cut to the slot's byte budget
+size_t stage_items(size_t bytes_per_item) {
+    const size_t by_budget = pd::STAGE_BUDGET / bytes_per_item ? pd::STAGE_BUDGET / bytes_per_item : 1;
+    const size_t c = tune_chunk();
+    return c < by_budget ? c : by_budget;
+}
+constexpr size_t up256(size_t v) { return (v + 255) & ~(size_t)255; }
+unsigned blocks_of(size_t n) { return (unsigned)((n + BLOCK - 1) / BLOCK); }
+
+std::mutex& tab_mutex() {
+    static std::mutex m;
+    return m;
+}
+// The constant table of the curve: built once by the first call on the ROOT ctx or any of its forks, owned by the root (zl_ctx_destroy frees it); the copy is
+// synchronous, so the table is complete before the lock is released and any lane launches against it.
+template <class FrP>
+int get_table(zl_ctx* ctx, const uint32_t** out) {
+    zl_ctx* owner = ctx->parent ? ctx->parent : ctx;
+    std::lock_guard<std::mutex> lk(tab_mutex());
+    void*& slot = owner->poseidon_tab[std::is_same<FrP, BLS12_381_Fr>::value ? 0 : 1];
+    if (!slot) {
+        const poseidon::Constants<FrP>& c = consts<FrP>();
+        std::vector<uint32_t> w((size_t)pd::TAB_ENTRIES * TABW, 0u);
+        auto put = [&](int e, const Fp<FrP>& m) {
+            const Fp<FrP> cw = zl::from_mont(m);
+            const El<FrP> v = to_lazy<FrP>(cw.l);
+            for (int k = 0; k < El<FrP>::L; k++) w[(size_t)e * TABW + k] = v.l[k];
+        };
+        for (int i = 0; i < pd::WIDTH * pd::ROUNDS; i++) put(pd::TAB_KEYS + i, c.round_keys[(size_t)i]);
+        for (int i = 0; i < 3; i++)
+            for (int j = 0; j < 3; j++) put(pd::TAB_MDS + 3 * i + j, c.mds[i][j]);
+        put(pd::TAB_TAG, zl::from_u64<FrP>(3));
+        void* d = nullptr;
+        ZL_HIP(ctx, hipMalloc(&d, pd::TAB_BYTES));
+        const hipError_t e = hipMemcpy(d, w.data(), pd::TAB_BYTES, hipMemcpyHostToDevice);
+        if (e != hipSuccess) {
+            (void)hipFree(d);
+            ctx->last_hip = (int)e;
+            return ZL_EHIP;
+        }
+        slot = d;
+    }
+    *out = static_cast<const uint32_t*>(slot);
+    return ZL_OK;
+}
+// the flag word (cleared) and `bytes` of staging behind it
+struct Stage {
+    uint32_t* flag = nullptr;
+    unsigned char* data = nullptr;
+};
+int stage_get(zl_ctx* ctx, size_t bytes, Stage* s) {
+    void* d = nullptr;
+    const int rc = zl_scratch_get(ctx, ZL_SLOT_POSEIDON, pd::FLAG_BYTES + bytes, &d);
+    if (rc) return rc;
+    s->flag = static_cast<uint32_t*>(d);
+    s->data = static_cast<unsigned char*>(d) + pd::FLAG_BYTES;
+    ZL_HIP(ctx, hipMemsetAsync(s->flag, 0, 4, ctx->stream));
+    return ZL_OK;
+}
+// wait for the call's work and read the flag: every entry point has finished when it returns
+int finish(zl_ctx* ctx, const uint32_t* d_flag) {
+    uint32_t bad = 0;
+    ZL_HIP(ctx, hipMemcpyAsync(&bad, d_flag, 4, hipMemcpyDeviceToHost, ctx->stream));
+    ZL_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    return bad ? ZL_EINVAL : ZL_OK;
+}
+#define ZL_POS_LAUNCH(ctx, kernel, grid, block, lds, ...)                          \
+    do {                                                                           \
+        hipLaunchKernelGGL(kernel, dim3(grid), dim3(block), lds, (ctx)->stream, __VA_ARGS__); \
+        ZL_HIP(ctx, hipGetLastError());                                            \
+    } while (0)
+
+template <class FrP>
+int dev_permute(zl_ctx* ctx, uint64_t* states, size_t count) {
+    const uint32_t* tab;
+    int rc = get_table<FrP>(ctx, &tab);
+    if (rc) return rc;
+    const size_t chunk = stage_items(96);
+    Stage s;
+    if ((rc = stage_get(ctx, (count < chunk ? count : chunk) * 96, &s))) return rc;
+    uint64_t* d = reinterpret_cast<uint64_t*>(s.data);
+    for (size_t first = 0; first < count; first += chunk) {
+        const size_t m = count - first < chunk ? count - first : chunk;
+        ZL_HIP(ctx, hipMemcpyAsync(d, states + first * 12, m * 96, hipMemcpyHostToDevice, ctx->stream));
+        ZL_POS_LAUNCH(ctx, (k_pos_permute<FrP>), blocks_of(m), BLOCK, 0, tab, d, m, s.flag);
+        ZL_HIP(ctx, hipMemcpyAsync(states + first * 12, d, m * 96, hipMemcpyDeviceToHost, ctx->stream));
+    }
+    return finish(ctx, s.flag);
+}
+// device operands, launches of at most one chunk
+template <class FrP>
+int launch_hash2(zl_ctx* ctx, const uint32_t* tab, const uint64_t* d_xy, size_t count, uint64_t* d_out, uint32_t* flag) {
+    const size_t chunk = tune_chunk();
+    for (size_t first = 0; first < count; first += chunk) {
+        const size_t m = count - first < chunk ? count - first : chunk;
+        ZL_POS_LAUNCH(ctx, (k_pos_hash2<FrP>), blocks_of(m), BLOCK, 0, tab, d_xy + first * 8, m, d_out + first * 4, flag);
+    }
+    return ZL_OK;
+}
+template <class FrP>
+int dev_hash2_dev(zl_ctx* ctx, const void* d_xy, size_t count, void* d_out) {
+    const uint32_t* tab;
+    int rc = get_table<FrP>(ctx, &tab);
+    if (rc) return rc;
+    Stage s;
+    if ((rc = stage_get(ctx, 0, &s))) return rc;
+    if ((rc = launch_hash2<FrP>(ctx, tab, static_cast<const uint64_t*>(d_xy), count, static_cast<uint64_t*>(d_out), s.flag))) return rc;
+    return finish(ctx, s.flag);
+}
+template <class FrP>
+int dev_hash2(zl_ctx* ctx, const uint64_t* xy, size_t count, uint64_t* out) {
+    const uint32_t* tab;
+    int rc = get_table<FrP>(ctx, &tab);
+    if (rc) return rc;
+    const size_t chunk = stage_items(96), m0 = count < chunk ? count : chunk;
+    Stage s;
+    if ((rc = stage_get(ctx, up256(m0 * 64) + m0 * 32, &s))) return rc;
+    uint64_t* d_in = reinterpret_cast<uint64_t*>(s.data);
+    uint64_t* d_out = reinterpret_cast<uint64_t*>(s.data + up256(m0 * 64));
+    for (size_t first = 0; first < count; first += chunk) {
+        const size_t m = count - first < chunk ? count - first : chunk;
+        ZL_HIP(ctx, hipMemcpyAsync(d_in, xy + first * 8, m * 64, hipMemcpyHostToDevice, ctx->stream));
+        ZL_POS_LAUNCH(ctx, (k_pos_hash2<FrP>), blocks_of(m), BLOCK, 0, tab, d_in, m, d_out, s.flag);
+        ZL_HIP(ctx, hipMemcpyAsync(out + first * 4, d_out, m * 32, hipMemcpyDeviceToHost, ctx->stream));
+    }
+    return finish(ctx, s.flag);
+}
+template <class FrP>
+int dev_chain(zl_ctx* ctx, const uint64_t* x0, const uint64_t* x1, uint32_t k, size_t count, uint64_t* out) {
+    const uint32_t* tab;
+    int rc = get_table<FrP>(ctx, &tab);
+    if (rc) return rc;
+    const size_t chunk = stage_items(96), m0 = count < chunk ? count : chunk, seg = up256(m0 * 32);
+    Stage s;
+    if ((rc = stage_get(ctx, 3 * seg, &s))) return rc;
+    uint64_t* d0 = reinterpret_cast<uint64_t*>(s.data);
+    uint64_t* d1 = reinterpret_cast<uint64_t*>(s.data + seg);
+    uint64_t* d_out = reinterpret_cast<uint64_t*>(s.data + 2 * seg);
+    for (size_t first = 0; first < count; first += chunk) {
+        const size_t m = count - first < chunk ? count - first : chunk;
+        ZL_HIP(ctx, hipMemcpyAsync(d0, x0 + first * 4, m * 32, hipMemcpyHostToDevice, ctx->stream));
+        ZL_HIP(ctx, hipMemcpyAsync(d1, x1 + first * 4, m * 32, hipMemcpyHostToDevice, ctx->stream));
+        ZL_POS_LAUNCH(ctx, (k_pos_chain<FrP>), blocks_of(m), BLOCK, 0, tab, d0, d1, k, m, d_out, s.flag);
+        ZL_HIP(ctx, hipMemcpyAsync(out + first * 4, d_out, m * 32, hipMemcpyDeviceToHost, ctx->stream));
+    }
+    return finish(ctx, s.flag);
+}
+template <class FrP>
+int dev_fold(zl_ctx* ctx, const uint64_t* leaves, const uint64_t* indices, const uint64_t* paths, unsigned depth, size_t count, uint64_t* roots) {
+    const uint32_t* tab;
+    int rc = get_table<FrP>(ctx, &tab);
+    if (rc) return rc;
+    const size_t per = 32 + 8 + (size_t)depth * 32 + 32;
+    const size_t chunk = stage_items(per), m0 = count < chunk ? count : chunk;
+    const size_t o_idx = up256(m0 * 32), o_path = o_idx + up256(m0 * 8), o_root = o_path + up256(m0 * depth * 32);
+    Stage s;
+    if ((rc = stage_get(ctx, o_root + m0 * 32, &s))) return rc;
+    uint64_t* d_leaf = reinterpret_cast<uint64_t*>(s.data);
+    uint64_t* d_idx = reinterpret_cast<uint64_t*>(s.data + o_idx);
+    uint64_t* d_path = reinterpret_cast<uint64_t*>(s.data + o_path);
+    uint64_t* d_root = reinterpret_cast<uint64_t*>(s.data + o_root);
+    for (size_t first = 0; first < count; first += chunk) {
+        const size_t m = count - first < chunk ? count - first : chunk;
+        ZL_HIP(ctx, hipMemcpyAsync(d_leaf, leaves + first * 4, m * 32, hipMemcpyHostToDevice, ctx->stream));
+        ZL_HIP(ctx, hipMemcpyAsync(d_idx, indices + first, m * 8, hipMemcpyHostToDevice, ctx->stream));
+        ZL_HIP(ctx, hipMemcpyAsync(d_path, paths + first * depth * 4, m * depth * 32, hipMemcpyHostToDevice, ctx->stream));
+        ZL_POS_LAUNCH(ctx, (k_pos_fold<FrP>), blocks_of(m), BLOCK, 0, tab, d_leaf, d_idx, d_path, depth, m, d_root, s.flag);
+        ZL_HIP(ctx, hipMemcpyAsync(roots + first * 4, d_root, m * 32, hipMemcpyDeviceToHost, ctx->stream));
+    }
+    return finish(ctx, s.flag);
+}
+// every level of the tree in device memory (n >= 1): wide launches per level while a level has more than T nodes, then the one-workgroup tail
+template <class FrP>
+int launch_merkle(zl_ctx* ctx, const uint32_t* tab, const uint64_t* d_leaves, size_t n, unsigned depth, uint64_t* d_nodes, uint32_t* flag) {
+    if (d_leaves != d_nodes) ZL_HIP(ctx, hipMemcpyAsync(d_nodes, d_leaves, n * 32, hipMemcpyDeviceToDevice, ctx->stream));
+    const unsigned T = tune_tail();
+    const size_t chunk = tune_chunk();
+    size_t off = 0, cm = n;
+    for (unsigned k = 1; k <= depth; k++) {
+        uint64_t* child = d_nodes + off * 4;
+        if (T && cm <= T) {
+            const size_t lds = (cm + (cm + 1) / 2) * 32;
+            ZL_POS_LAUNCH(ctx, (k_pos_tail<FrP>), 1, pd::TAIL_BLOCK, lds, tab, child, (unsigned)cm, depth - (k - 1), flag);
+            break;
+        }
+        const size_t pm = (cm + 1) / 2;
+        uint64_t* parent = child + cm * 4;
+        for (size_t first = 0; first < pm; first += chunk) {
+            const size_t m = pm - first < chunk ? pm - first : chunk;
+            ZL_POS_LAUNCH(ctx, (k_pos_level<FrP>), blocks_of(m), BLOCK, 0, tab, child, cm, parent, first, m, flag);
+        }
+        off += cm;
+        cm = pm;
+    }
+    return ZL_OK;
+}
+template <class FrP>
+int dev_merkle_build_dev(zl_ctx* ctx, const void* d_leaves, size_t n, unsigned depth, void* d_nodes, uint64_t* root_out) {
+    const uint32_t* tab;
+    int rc = get_table<FrP>(ctx, &tab);
+    if (rc) return rc;
+    Stage s;
+    if ((rc = stage_get(ctx, 0, &s))) return rc;
+    uint64_t* nodes = static_cast<uint64_t*>(d_nodes);
+    if ((rc = launch_merkle<FrP>(ctx, tab, static_cast<const uint64_t*>(d_leaves), n, depth, nodes, s.flag))) return rc;
+    ZL_HIP(ctx, hipMemcpyAsync(root_out, nodes + (pd::level_offset(n, depth + 1) - 1) * 4, 32, hipMemcpyDeviceToHost, ctx->stream));
+    return finish(ctx, s.flag);
+}
+struct DevFree {
+    void operator()(void* p) const { (void)hipFree(p); }
+};
+// host leaves -> (optionally) the host node array and the root, through a node array of the call's own in device memory
+template <class FrP>
+int dev_merkle_host(zl_ctx* ctx, const uint64_t* leaves, size_t n, unsigned depth, uint64_t* nodes_out, uint64_t* root) {
+    const size_t total = pd::level_offset(n, depth + 1);
+    void* d = nullptr;
+    ZL_HIP(ctx, hipMalloc(&d, total * 32));
+    const std::unique_ptr<void, DevFree> hold(d);
+    ZL_HIP(ctx, hipMemcpyAsync(d, leaves, n * 32, hipMemcpyHostToDevice, ctx->stream));
+    int rc = dev_merkle_build_dev<FrP>(ctx, d, n, depth, d, root);
+    if (rc == ZL_OK && nodes_out) {
+        const hipError_t e = hipMemcpyAsync(nodes_out, d, total * 32, hipMemcpyDeviceToHost, ctx->stream);
+        if (e != hipSuccess) { ctx->last_hip = (int)e; rc = ZL_EHIP; }
+    }
+    const hipError_t e = hipStreamSynchronize(ctx->stream);  // (also on the error paths: the block is freed behind this)
+    if (e != hipSuccess && rc == ZL_OK) { ctx->last_hip = (int)e; rc = ZL_EHIP; }
+    return rc;
+}
+LevelTable level_table(size_t n, unsigned depth) {
+    LevelTable lt{};
+    size_t off = 0;
+    for (unsigned k = 0; k < depth; k++) {
+        lt.off[k] = off;
+        lt.size[k] = pd::level_size(n, k);
+        off += lt.size[k];
+    }
+    return lt;
+}
+int dev_paths(zl_ctx* ctx, const void* d_nodes, size_t n, unsigned depth, const uint64_t* indices, size_t count, uint64_t* paths) {
+    const size_t chunk = stage_items(8 + (size_t)depth * 32), m0 = count < chunk ? count : chunk, o_path = up256(m0 * 8);
+    Stage s;
+    const int rc = stage_get(ctx, o_path + m0 * depth * 32, &s);
+    if (rc) return rc;
+    uint64_t* d_idx = reinterpret_cast<uint64_t*>(s.data);
+    uint64_t* d_path = reinterpret_cast<uint64_t*>(s.data + o_path);
+    const LevelTable lt = level_table(n, depth);
+    for (size_t first = 0; first < count; first += chunk) {
+        const size_t m = count - first < chunk ? count - first : chunk;
+        ZL_HIP(ctx, hipMemcpyAsync(d_idx, indices + first, m * 8, hipMemcpyHostToDevice, ctx->stream));
+        ZL_POS_LAUNCH(ctx, k_pos_gather, blocks_of(m * depth), BLOCK, 0, static_cast<const uint64_t*>(d_nodes), lt, depth, d_idx, m * depth, d_path);
+        ZL_HIP(ctx, hipMemcpyAsync(paths + first * depth * 4, d_path, m * depth * 32, hipMemcpyDeviceToHost, ctx->stream));
+    }
+    ZL_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    return ZL_OK;
+}
+}  // namespace
+
+#define ZL_POS_CURVE(curve, fn, ...) ((curve) == ZL_BLS12_381 ? fn<BLS12_381_Fr>(__VA_ARGS__) : fn<BN254_Fr>(__VA_ARGS__))
+
+extern "C" {
+
+int zl_poseidon_permute_batch(zl_ctx* ctx, zl_curve_t curve, uint64_t* states, size_t count) {
+    if (!valid_curve(curve) || (count && !states)) return ZL_EINVAL;
+    if (count == 0) return ZL_OK;
+    if (on_host(ctx, count)) return ZL_POS_CURVE(curve, host_permute, states, count);
+    ZL_HIP(ctx, hipSetDevice(ctx->device));
+    return ZL_POS_CURVE(curve, dev_permute, ctx, states, count);
+}
+int zl_poseidon_hash2_batch(zl_ctx* ctx, zl_curve_t curve, const uint64_t* xy, size_t count, uint64_t* out) {
+    if (!valid_curve(curve) || (count && (!xy || !out))) return ZL_EINVAL;
+    if (count == 0) return ZL_OK;
+    if (on_host(ctx, count)) return ZL_POS_CURVE(curve, host_hash2_batch, xy, count, out);
+    ZL_HIP(ctx, hipSetDevice(ctx->device));
+    return ZL_POS_CURVE(curve, dev_hash2, ctx, xy, count, out);
+}
+int zl_poseidon_hash2_batch_dev(zl_ctx* ctx, zl_curve_t curve, const void* d_xy, size_t count, void* d_out) {
+    if (!ctx || !valid_curve(curve) || (count && (!d_xy || !d_out))) return ZL_EINVAL;
+    if (count == 0) return ZL_OK;
+    ZL_HIP(ctx, hipSetDevice(ctx->device));
+    return ZL_POS_CURVE(curve, dev_hash2_dev, ctx, d_xy, count, d_out);
+}
+int zl_poseidon_chain_batch(zl_ctx* ctx, zl_curve_t curve, const uint64_t* x0, const uint64_t* x1, uint32_t k, size_t count, uint64_t* out) {
+    if (!valid_curve(curve) || k == 0 || (count && (!x0 || !x1 || !out))) return ZL_EINVAL;
+    if (count == 0) return ZL_OK;
+    if (on_host(ctx, count)) return ZL_POS_CURVE(curve, host_chain, x0, x1, k, count, out);
+    ZL_HIP(ctx, hipSetDevice(ctx->device));
+    return ZL_POS_CURVE(curve, dev_chain, ctx, x0, x1, k, count, out);
+}
+size_t zl_poseidon_merkle_nodes(size_t n, unsigned depth) {
+    return pd::geometry_ok(n, depth) ? pd::level_offset(n, depth + 1) : 0;
+}
+int zl_poseidon_merkle_build_dev(zl_ctx* ctx, zl_curve_t curve, const void* d_leaves, size_t n, unsigned depth, void* d_nodes, uint64_t* root_out) {
+    if (!ctx || !valid_curve(curve) || !pd::geometry_ok(n, depth) || !root_out || (n && (!d_leaves || !d_nodes))) return ZL_EINVAL;
+    if (n == 0) {
+        memset(root_out, 0, 32);
+        return ZL_OK;
+    }
+    ZL_HIP(ctx, hipSetDevice(ctx->device));
+    return ZL_POS_CURVE(curve, dev_merkle_build_dev, ctx, d_leaves, n, depth, d_nodes, root_out);
+}
+int zl_poseidon_merkle_build(zl_ctx* ctx, zl_curve_t curve, const uint64_t* leaves, size_t n, unsigned depth, uint64_t* nodes, uint64_t* root) {
+    if (!valid_curve(curve) || !pd::geometry_ok(n, depth) || !root || (n && (!leaves || !nodes))) return ZL_EINVAL;
+    if (n == 0) {
+        memset(root, 0, 32);
+        return ZL_OK;
+    }
+    if (on_host(ctx, n)) {
+        const int rc = ZL_POS_CURVE(curve, host_merkle, leaves, n, depth, nodes);
+        memcpy(root, nodes + (pd::level_offset(n, depth + 1) - 1) * 4, 32);
+        return rc;
+    }
+    ZL_HIP(ctx, hipSetDevice(ctx->device));
+    return ZL_POS_CURVE(curve, dev_merkle_host, ctx, leaves, n, depth, nodes, root);
+}
+int zl_poseidon_merkle_root(zl_ctx* ctx, zl_curve_t curve, const uint64_t* leaves, size_t n, unsigned depth, uint64_t* root) {
+    if (!valid_curve(curve) || !pd::geometry_ok(n, depth) || !root || (n && !leaves)) return ZL_EINVAL;
+    if (n == 0) {
+        memset(root, 0, 32);
+        return ZL_OK;
+    }
+    if (on_host(ctx, n)) {
+        const size_t total = pd::level_offset(n, depth + 1);
+        const std::unique_ptr<uint64_t[]> nodes(new (std::nothrow) uint64_t[total * 4]);
+        if (!nodes) return ZL_ENOMEM;
+        const int rc = ZL_POS_CURVE(curve, host_merkle, leaves, n, depth, nodes.get());
+        memcpy(root, nodes.get() + (total - 1) * 4, 32);
+        return rc;
+    }
+    ZL_HIP(ctx, hipSetDevice(ctx->device));
+    return ZL_POS_CURVE(curve, dev_merkle_host, ctx, leaves, n, depth, nullptr, root);
+}
+static int paths_args_ok(size_t n, unsigned depth, const uint64_t* indices, size_t count, const uint64_t* paths) {
+    if (!pd::geometry_ok(n, depth) || (count && (!indices || !paths))) return 0;
+    for (size_t i = 0; i < count; i++)
+        if (indices[i] >= n) return 0;
+    return 1;
+}
+int zl_poseidon_merkle_paths_dev(zl_ctx* ctx, zl_curve_t curve, const void* d_nodes, size_t n, unsigned depth, const uint64_t* indices, size_t count,
+                                 uint64_t* paths) {
+    if (!ctx || !valid_curve(curve) || !paths_args_ok(n, depth, indices, count, paths) || (count && !d_nodes)) return ZL_EINVAL;
+    if (count == 0) return ZL_OK;
+    ZL_HIP(ctx, hipSetDevice(ctx->device));
+    return dev_paths(ctx, d_nodes, n, depth, indices, count, paths);
+}
+int zl_poseidon_merkle_paths(const uint64_t* nodes, size_t n, unsigned depth, const uint64_t* indices, size_t count, uint64_t* paths) {
+    if (!paths_args_ok(n, depth, indices, count, paths) || (count && !nodes)) return ZL_EINVAL;
+    const LevelTable lt = level_table(n, depth);
+    for (size_t i = 0; i < count; i++)
+        for (unsigned k = 0; k < depth; k++) {
+            const uint64_t sib = (indices[i] >> k) ^ 1;
+            uint64_t* dst = paths + (i * depth + k) * 4;
+            if (sib < lt.size[k]) memcpy(dst, nodes + (lt.off[k] + sib) * 4, 32);
+            else memset(dst, 0, 32);
+        }
+    return ZL_OK;
+}
+int zl_poseidon_merkle_roots_from_paths(zl_ctx* ctx, zl_curve_t curve, const uint64_t* leaves, const uint64_t* indices, const uint64_t* paths, unsigned depth,
+                                        size_t count, uint64_t* roots) {
+    if (!valid_curve(curve) || depth < 1 || depth > pd::MAX_DEPTH || (count && (!leaves || !indices || !paths || !roots))) return ZL_EINVAL;
+    for (size_t i = 0; i < count; i++)
+        if (indices[i] >> depth) return ZL_EINVAL;
+    if (count == 0) return ZL_OK;
+    if (on_host(ctx, count)) return ZL_POS_CURVE(curve, host_fold, leaves, indices, paths, depth, count, roots);
+    ZL_HIP(ctx, hipSetDevice(ctx->device));
+    return ZL_POS_CURVE(curve, dev_fold, ctx, leaves, indices, paths, depth, count, roots);
+}
+
+}  // extern "C"
