@@ -49,6 +49,22 @@ int zl_msm_multi_dev(zl_ctx* ctx, uint64_t bases, size_t first, const void* d_sc
  * error is returned.  zl_groth16_last_h after a device batch returns ZL_EINVAL. */
 int zl_groth16_prove_batch(zl_ctx* ctx, const zl_g16_pk* pk, uint64_t r1cs_handle, const uint64_t* assignments, unsigned flags, const uint64_t* r,
                            const uint64_t* s, size_t count, zl_g16_proof* proofs);
+/* The same with the assignments in DEVICE memory (count x (n_instance + n_witness) elements, densely): on the device path every chunk is one device-to-device
+ * copy into the batch's block; where the dispatch bounds send the batch to the loop over the resident prover -- it reads its assignment from host memory -- the
+ * assignments come back through host staging of at most 64 MiB at a time.  r, s and proofs are host memory.  Same proofs, same error codes. */
+int zl_groth16_prove_batch_dev(zl_ctx* ctx, const zl_g16_pk* pk, uint64_t r1cs_handle, const void* d_assignments, unsigned flags, const uint64_t* r,
+                               const uint64_t* s, size_t count, zl_g16_proof* proofs);
+/* Poseidon-chain inputs in, proofs out: proofs[j] = what zl_groth16_prove_resident returns for the assignment of zl_circuit_poseidon_chain(curve, k, x0[j], x1[j])
+ * (zl_poseidon_chain_assignments below) with r[j], s[j], byte for byte; x0, x1, r, s: count x 4 u64 in host memory; public_out (may be NULL) receives h_k per
+ * proof, the public input.  On the device path of zl_groth16_prove_batch the trace kernel of zl_poseidon_dev.hip writes every chunk's assignments straight into
+ * the chunk's block of the batch (inputs staged in chunks of at most ZL_TUNE_POSEIDON_CHUNK chains): no assignment crosses the bus or exists in host memory.
+ * Off it, assignments are produced zl_poseidon_chain_assignments-wise, at most 64 MiB at a time, for the loop over the resident prover.  The resident circuit
+ * must have the SHAPE of a k-link chain (n_instance == 2, n_witness == 2 + 234 k, n_constraints == 234 k + 1), else ZL_EINVAL; what its matrices hold cannot be
+ * checked -- as with a witness-only compiler, a different circuit of that shape yields proofs that do not verify.  k == 0, an input >= r, or -- off the
+ * device path only -- a k above zl_poseidon_chain_assignments' 35 848: ZL_EINVAL; the
+ * other error codes and their order are those of zl_groth16_prove_batch. */
+int zl_groth16_prove_poseidon_chains(zl_ctx* ctx, const zl_g16_pk* pk, uint64_t r1cs_handle, uint32_t k, const uint64_t* x0, const uint64_t* x1, const uint64_t* r,
+                                     const uint64_t* s, size_t count, zl_g16_proof* proofs, uint64_t* public_out);
 int zl_partials_sum(zl_curve_t curve, zl_group_t group, const uint64_t* partials, size_t count, uint64_t* out_xy, uint8_t* out_inf);
 /* wrap a canonical affine point (all-zero = infinity) as a partial, e.g. to fold an extra term into zl_partials_sum */
 int zl_partial_from_affine(zl_curve_t curve, zl_group_t group, const uint64_t* xy, uint64_t* out_partial);
@@ -144,6 +160,18 @@ int zl_poseidon_hash2_batch_dev(zl_ctx* ctx, zl_curve_t curve, const void* d_xy,
 /* out[i] = h_k with h_1 = H(x0[i], x1[i]), h_{j+1} = H(h_j, x1[i]): the public input of zl_circuit_poseidon_chain(curve, k, x0[i], x1[i]); the k dependent
  * hashes of a chain run inside one kernel.  k == 0: ZL_EINVAL, as zl_circuit_poseidon_chain. */
 int zl_poseidon_chain_batch(zl_ctx* ctx, zl_curve_t curve, const uint64_t* x0, const uint64_t* x1, uint32_t k, size_t count, uint64_t* out);
+/* The complete ASSIGNMENT of zl_circuit_poseidon_chain(curve, k, x0[i], x1[i]) per chain, the witness a prover of the chain needs, computed where the chain is:
+ *   [0] = 1   [1] = h_k   [2] = x0   [3] = x1   then for link j = 1..k, in round order, x^2, x^4, x^5 of every S-box except lane 0 of round 0 (its input is
+ *   the domain tag plus a round key: a constant the circuit folds) -- 78 S-boxes, 234 elements per link.
+ * zl_poseidon_chain_assignment_elems(k) = 4 + 234 k elements per chain (0 for k == 0 or a count that does not fit 31 bits); word for word what the host
+ * compilers (full and witness-only) export.  The host-pointer form writes count dense rows and follows the common rules above (ctx == NULL or a count below
+ * ZL_TUNE_POSEIDON_DEV_MIN: the host mirror over the host pool); it stages whole rows, so a row with its inputs must fit the 256 MiB staging budget: k above
+ * 35 848 is ZL_EINVAL there, on either path.  The _dev form takes device pointers (never the host path; ctx == NULL is ZL_EINVAL) and any k the element
+ * count allows: row i starts at d_out + i * stride_elems elements, stride_elems >= the row length, elements behind the row are not written; d_out must be
+ * 16-byte aligned and the rows must not overlap d_x0 or d_x1 (the inputs are read again after a row's records are stored). */
+size_t zl_poseidon_chain_assignment_elems(uint32_t k);
+int zl_poseidon_chain_assignments_dev(zl_ctx* ctx, zl_curve_t curve, const void* d_x0, const void* d_x1, uint32_t k, size_t count, void* d_out, size_t stride_elems);
+int zl_poseidon_chain_assignments(zl_ctx* ctx, zl_curve_t curve, const uint64_t* x0, const uint64_t* x1, uint32_t k, size_t count, uint64_t* out);
 /* Merkle tree over n leaf digests with `depth` hash levels (openzl-crypto/src/merkle_tree, one H for join_leaves and join): level 0 = the n leaves, level k
  * has ceil(n / 2^k) nodes, node(k, j) = H(node(k-1, 2j), node(k-1, 2j+1)) where an absent right child reads as the zero digest.  A node whose subtree holds no
  * leaf is absent -- zero when read as a sibling, NOT H(0, 0): the reference's Default::default() rule (merkle_tree/node.rs:55-73, path.rs:405-454).  The root

@@ -38,6 +38,8 @@ ABI_SYMBOLS = [
     "zl_poseidon_permute_batch", "zl_poseidon_hash2_batch", "zl_poseidon_hash2_batch_dev", "zl_poseidon_chain_batch", "zl_poseidon_merkle_nodes",
     "zl_poseidon_merkle_build_dev", "zl_poseidon_merkle_build", "zl_poseidon_merkle_root", "zl_poseidon_merkle_paths_dev", "zl_poseidon_merkle_paths",
     "zl_poseidon_merkle_roots_from_paths",
+    "zl_poseidon_chain_assignment_elems", "zl_poseidon_chain_assignments_dev", "zl_poseidon_chain_assignments", "zl_groth16_prove_batch_dev",
+    "zl_groth16_prove_poseidon_chains",
 ]
 
 
@@ -122,6 +124,8 @@ def load_library(path: Optional[str] = None):
     L.zl_r1cs_free.argtypes = [vp, C.c_uint64]
     L.zl_groth16_prove_resident.argtypes = [vp, C.POINTER(G16PkC), C.c_uint64, u64p, C.c_uint, u64p, u64p, C.POINTER(G16ProofC)]
     L.zl_groth16_prove_batch.argtypes = [vp, C.POINTER(G16PkC), C.c_uint64, u64p, C.c_uint, u64p, u64p, C.c_size_t, C.POINTER(G16ProofC)]
+    L.zl_groth16_prove_batch_dev.argtypes = [vp, C.POINTER(G16PkC), C.c_uint64, vp, C.c_uint, u64p, u64p, C.c_size_t, C.POINTER(G16ProofC)]
+    L.zl_groth16_prove_poseidon_chains.argtypes = [vp, C.POINTER(G16PkC), C.c_uint64, C.c_uint32, u64p, u64p, u64p, u64p, C.c_size_t, C.POINTER(G16ProofC), u64p]
     L.zl_circuit_poseidon_chain.argtypes = [C.c_int, C.c_uint32, u64p, u64p, C.POINTER(vp)]
     L.zl_circuit_free.argtypes = [vp]
     L.zl_circuit_free.restype = None
@@ -133,6 +137,10 @@ def load_library(path: Optional[str] = None):
     L.zl_poseidon_hash2_batch.argtypes = [vp, C.c_int, u64p, C.c_size_t, u64p]
     L.zl_poseidon_hash2_batch_dev.argtypes = [vp, C.c_int, vp, C.c_size_t, vp]
     L.zl_poseidon_chain_batch.argtypes = [vp, C.c_int, u64p, u64p, C.c_uint32, C.c_size_t, u64p]
+    L.zl_poseidon_chain_assignment_elems.argtypes = [C.c_uint32]
+    L.zl_poseidon_chain_assignment_elems.restype = C.c_size_t
+    L.zl_poseidon_chain_assignments_dev.argtypes = [vp, C.c_int, vp, vp, C.c_uint32, C.c_size_t, vp, C.c_size_t]
+    L.zl_poseidon_chain_assignments.argtypes = [vp, C.c_int, u64p, u64p, C.c_uint32, C.c_size_t, u64p]
     L.zl_poseidon_merkle_nodes.argtypes = [C.c_size_t, C.c_uint]
     L.zl_poseidon_merkle_nodes.restype = C.c_size_t
     L.zl_poseidon_merkle_build_dev.argtypes = [vp, C.c_int, vp, C.c_size_t, C.c_uint, vp, u64p]
@@ -511,6 +519,17 @@ class Backend:
         """out[i] = h_k of the chain over (x0[i], x1[i]): the public input of Circuit(curve, k, x0[i], x1[i])"""
         return _poseidon_chain(self.L, self._ctx, curve, x0, x1, k)
 
+    def poseidon_chain_assignments(self, curve: int, x0: np.ndarray, x1: np.ndarray, k: int) -> np.ndarray:
+        """zl_poseidon_chain_assignments: (count, 4 + 234 k, 4) canonical words, row i the complete assignment of Circuit(curve, k, x0[i], x1[i])"""
+        return _poseidon_chain_assignments(self.L, self._ctx, curve, x0, x1, k)
+
+    def poseidon_chain_assignments_dev(self, curve: int, d_x0: int, d_x1: int, k: int, count: int, d_out: int, stride_elems: Optional[int] = None):
+        """zl_poseidon_chain_assignments_dev: count chains from the device addresses d_x0 / d_x1 -> row i at d_out + i * stride_elems elements (default: the
+        row length, poseidon_chain_assignment_elems(k)); finished on return"""
+        stride = self.L.zl_poseidon_chain_assignment_elems(k) if stride_elems is None else stride_elems
+        self._check(self.L.zl_poseidon_chain_assignments_dev(self._ctx, curve, C.c_void_p(d_x0), C.c_void_p(d_x1), k, count, C.c_void_p(d_out), stride),
+                    "zl_poseidon_chain_assignments_dev")
+
     def poseidon_merkle_root(self, curve: int, leaves: np.ndarray, depth: int) -> np.ndarray:
         return _poseidon_merkle_root(self.L, self._ctx, curve, leaves, depth)
 
@@ -581,6 +600,35 @@ class Backend:
         (assignments[j], r[j], s[j]); flags as there."""
         pkc, keep_pk = _pk_struct(curve, pk)
         return self._prove_batch(pkc, curve, r1cs_handle, assignments, r, s, flags)
+
+    def _prove_batch_dev(self, pkc, curve: int, r1cs_handle: int, d_assignments: int, count: int, r: np.ndarray, s: np.ndarray, flags: int):
+        r, s = np.ascontiguousarray(r, dtype=np.uint64).reshape(count, 4), np.ascontiguousarray(s, dtype=np.uint64).reshape(count, 4)
+        out = (G16ProofC * max(1, count))()
+        self._check(self.L.zl_groth16_prove_batch_dev(self._ctx, C.byref(pkc), r1cs_handle, C.c_void_p(d_assignments) if count else None, flags,
+                                                      _p64(r) if count else None, _p64(s) if count else None, count, out), "zl_groth16_prove_batch_dev")
+        return [_proof_tuple(curve, p) for p in out[:count]]
+
+    def groth16_prove_batch_dev(self, curve: int, pk: dict, r1cs_handle: int, d_assignments: int, count: int, r: np.ndarray, s: np.ndarray, flags: int = 0):
+        """zl_groth16_prove_batch_dev: groth16_prove_batch over `count` dense assignments at the device address d_assignments"""
+        pkc, keep_pk = _pk_struct(curve, pk)
+        return self._prove_batch_dev(pkc, curve, r1cs_handle, d_assignments, count, r, s, flags)
+
+    def _prove_chains(self, pkc, curve: int, r1cs_handle: int, k: int, x0, x1, r: np.ndarray, s: np.ndarray):
+        a, b = _elems(x0, 1), _elems(x1, 1)
+        count = a.shape[0]
+        assert b.shape == a.shape
+        r, s = np.ascontiguousarray(r, dtype=np.uint64).reshape(count, 4), np.ascontiguousarray(s, dtype=np.uint64).reshape(count, 4)
+        out = (G16ProofC * max(1, count))()
+        pub = np.zeros((count, 4), dtype=np.uint64)
+        self._check(self.L.zl_groth16_prove_poseidon_chains(self._ctx, C.byref(pkc), r1cs_handle, k, _ptr_or_none(a), _ptr_or_none(b), _ptr_or_none(r), _ptr_or_none(s),
+                                                            count, out, _ptr_or_none(pub)), "zl_groth16_prove_poseidon_chains")
+        return [_proof_tuple(curve, p) for p in out[:count]], pub
+
+    def groth16_prove_poseidon_chains(self, curve: int, pk: dict, r1cs_handle: int, k: int, x0, x1, r: np.ndarray, s: np.ndarray):
+        """zl_groth16_prove_poseidon_chains: chain inputs x0, x1 (count, 4) and blinding scalars -> (`count` proofs, the public inputs h_k (count, 4)); the
+        assignments are made on the device and never leave it"""
+        pkc, keep_pk = _pk_struct(curve, pk)
+        return self._prove_chains(pkc, curve, r1cs_handle, k, x0, x1, r, s)
 
     def groth16_last_h(self, n: int) -> np.ndarray:
         out = np.zeros((n, 4), dtype=np.uint64)
@@ -1101,6 +1149,14 @@ def _poseidon_chain(L, ctx, curve: int, x0, x1, k: int) -> np.ndarray:
     return out
 
 
+def _poseidon_chain_assignments(L, ctx, curve: int, x0, x1, k: int) -> np.ndarray:
+    a, b = _elems(x0, 1), _elems(x1, 1)
+    assert a.shape == b.shape
+    out = np.zeros((a.shape[0], L.zl_poseidon_chain_assignment_elems(k), 4), dtype=np.uint64)
+    _pos_check(L, L.zl_poseidon_chain_assignments(ctx, curve, _ptr_or_none(a), _ptr_or_none(b), k, a.shape[0], _ptr_or_none(out)), "zl_poseidon_chain_assignments")
+    return out
+
+
 def _poseidon_merkle_root(L, ctx, curve: int, leaves, depth: int) -> np.ndarray:
     lv = _elems(leaves, 1)
     root = np.zeros(4, dtype=np.uint64)
@@ -1142,6 +1198,15 @@ def poseidon_hash2_host(curve: int, xy) -> np.ndarray:
 
 def poseidon_chain_host(curve: int, x0, x1, k: int) -> np.ndarray:
     return _poseidon_chain(load_library(), None, curve, x0, x1, k)
+
+
+def poseidon_chain_assignment_elems(k: int) -> int:
+    """elements of one chain's assignment: 4 + 234 k (0 for k == 0 or a variable count that does not fit 31 bits)"""
+    return int(load_library().zl_poseidon_chain_assignment_elems(k))
+
+
+def poseidon_chain_assignments_host(curve: int, x0, x1, k: int) -> np.ndarray:
+    return _poseidon_chain_assignments(load_library(), None, curve, x0, x1, k)
 
 
 def poseidon_merkle_root_host(curve: int, leaves, depth: int) -> np.ndarray:
@@ -1392,6 +1457,28 @@ class Groth16Keys:
         if not getattr(self, "_r1cs", 0):
             self._r1cs = self.backend.r1cs_upload(self.circuit.curve, self.circuit.arrays())
         return (lane or self.backend)._prove_batch(self.pk, self.circuit.curve, self._r1cs, assignments, r, s, flags)
+
+    def prove_batch_dev(self, d_assignments: int, count: int, r: np.ndarray, s: np.ndarray, flags: int = 0, lane: Optional[Backend] = None):
+        """prove_batch over `count` dense assignments at the device address d_assignments (zl_groth16_prove_batch_dev)"""
+        if not getattr(self, "_r1cs", 0):
+            self._r1cs = self.backend.r1cs_upload(self.circuit.curve, self.circuit.arrays())
+        return (lane or self.backend)._prove_batch_dev(self.pk, self.circuit.curve, self._r1cs, d_assignments, count, r, s, flags)
+
+    def chain_links(self) -> int:
+        """k when the keys' circuit has the shape of a k-link Poseidon chain, else 0"""
+        n_c, n_i, n_w = self.circuit.shape
+        k = (n_w - 2) // 234
+        return k if k >= 1 and (n_c, n_i, n_w) == (234 * k + 1, 2, 2 + 234 * k) else 0
+
+    def prove_chains(self, x0, x1, r: np.ndarray, s: np.ndarray, lane: Optional[Backend] = None):
+        """zl_groth16_prove_poseidon_chains over this key: chain inputs x0, x1 and blinding scalars r, s (count, 4) -> (proofs, public inputs (count, 4));
+        proof j is prove_batch's for the assignment of Circuit(curve, k, x0[j], x1[j]).  Keys of a circuit that is no Poseidon chain are refused."""
+        k = self.chain_links()
+        if not k:
+            raise ValueError("prove_chains: the keys' circuit is not a Poseidon chain")
+        if not getattr(self, "_r1cs", 0):
+            self._r1cs = self.backend.r1cs_upload(self.circuit.curve, self.circuit.arrays())
+        return (lane or self.backend)._prove_chains(self.pk, self.circuit.curve, self._r1cs, k, x0, x1, r, s)
 
     def prove_many(self, seeds, circuits=None):
         """zl_groth16_prove_circuits: a stream of proofs over this key on two prover lanes (two host threads inside the library); proofs[i] is what

@@ -18,7 +18,9 @@
 #include <chrono>
 #include <stdio.h>
 #include <stdlib.h>
+#include <functional>
 #include "zl_ctx.h"
+#include "zl_poseidon_dev.h"
 
 template <class FrP>
 __global__ void __launch_bounds__(256) k_fr_to_mont(Fp<FrP>* __restrict__ v, uint32_t n) {
@@ -1037,8 +1039,19 @@ static int g16_batch_queries(zl_ctx* ctx, const zl_g16_pk* pk, const zl_bases* c
 #define ZL_G16_BATCH_MIN 64    // ... from this many proofs on (ZL_TUNE_G16_BATCH_MIN)
 #define ZL_G16_BATCH_BUDGET ((size_t)512 << 20)  // bytes of ZL_SLOT_G16_BATCH a chunk may take
 
+// Where the assignments of a batch come from: host memory (zl_groth16_prove_batch: one upload per chunk), device memory (zl_groth16_prove_batch_dev: one
+// device-to-device copy per chunk), or a producer (zl_groth16_prove_poseidon_chains) that writes the `ch` canonical rows of the chunk from proof c0 on in place
+// (fill_dev: into the chunk's block of ZL_SLOT_G16_BATCH, on ctx->stream, finished on return) -- and, for the loop over the resident prover, into host rows.
+struct G16BatchSource {
+    const uint64_t* host = nullptr;
+    const uint64_t* dev = nullptr;
+    std::function<int(size_t c0, size_t ch, void* d_rows)> fill_dev;
+    std::function<int(size_t c0, size_t ch, uint64_t* rows)> fill_host;
+};
+#define ZL_G16_BATCH_HOST_STAGE ((size_t)64 << 20)  // bytes of host staging the resident loop takes for assignments that are not in host memory
+
 template <class G1, class G2>
-static int groth16_prove_batch_dev_t(zl_ctx* ctx, const zl_g16_pk* pk, const zl_r1cs_dev* cs, const zl_bases* const* bs, unsigned log_n, const uint64_t* assignments,
+static int groth16_prove_batch_dev_t(zl_ctx* ctx, const zl_g16_pk* pk, const zl_r1cs_dev* cs, const zl_bases* const* bs, unsigned log_n, const G16BatchSource& src,
                                      unsigned flags, const uint64_t* r, const uint64_t* s, size_t count, zl_g16_proof* proofs) {
     using FrP = typename G1::FrP;
     using Fr = Fp<FrP>;
@@ -1083,7 +1096,13 @@ static int groth16_prove_batch_dev_t(zl_ctx* ctx, const zl_g16_pk* pk, const zl_
             const uint32_t ch = (uint32_t)std::min(chunk, count - c0);
             const uint32_t tot_z = ch * nv;
             Fr* d_in = (flags & ZL_MONT) ? d_zm : d_zc;
-            ZL_HIP(ctx, hipMemcpyAsync(d_in, assignments + c0 * (size_t)nv * 4, (size_t)tot_z * 32, hipMemcpyHostToDevice, st));
+            if (src.fill_dev) {
+                const int e = src.fill_dev(c0, ch, d_in);
+                if (e) return e;
+            } else {
+                const uint64_t* from = (src.dev ? src.dev : src.host) + c0 * (size_t)nv * 4;
+                ZL_HIP(ctx, hipMemcpyAsync(d_in, from, (size_t)tot_z * 32, src.dev ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, st));
+            }
             ZL_HIP(ctx, hipMemcpyAsync(d_r, r + c0 * 4, (size_t)ch * 32, hipMemcpyHostToDevice, st));
             ZL_HIP(ctx, hipMemcpyAsync(d_s, s + c0 * 4, (size_t)ch * 32, hipMemcpyHostToDevice, st));
             if (flags & ZL_MONT) {
@@ -1134,7 +1153,7 @@ static int groth16_prove_batch_dev_t(zl_ctx* ctx, const zl_g16_pk* pk, const zl_
 }
 
 template <class G1, class G2>
-static int groth16_prove_batch_t(zl_ctx* ctx, const zl_g16_pk* pk, const zl_r1cs_dev* cs, const uint64_t* assignments, unsigned flags, const uint64_t* r,
+static int groth16_prove_batch_t(zl_ctx* ctx, const zl_g16_pk* pk, const zl_r1cs_dev* cs, const G16BatchSource& src, unsigned flags, const uint64_t* r,
                                  const uint64_t* s, size_t count, zl_g16_proof* proofs) {
     using FrP = typename G1::FrP;
     // the resident prover's checks, in its order, so that both paths answer a bad key alike
@@ -1153,12 +1172,37 @@ static int groth16_prove_batch_t(zl_ctx* ctx, const zl_g16_pk* pk, const zl_r1cs
     }
     if (bs[0]->n < nv || bs[1]->n < nv || bs[4]->n < nv || bs[2]->n < ((size_t)1 << log_n) - 1 || bs[3]->n < nw) return ZL_EINVAL;
     if (log_n <= (unsigned)zl_tune("ZL_TUNE_G16_BATCH_LOG_N", ZL_G16_BATCH_LOG_N) && count >= (size_t)std::max(1, zl_tune("ZL_TUNE_G16_BATCH_MIN", ZL_G16_BATCH_MIN)))
-        return groth16_prove_batch_dev_t<G1, G2>(ctx, pk, cs, bs, log_n, assignments, flags, r, s, count, proofs);
-    for (size_t j = 0; j < count; j++) {
-        const int rc = groth16_prove_t<G1, G2>(ctx, pk, cs, assignments + j * nv * 4, flags, r + 4 * j, s + 4 * j, proofs + j);
-        if (rc) return rc;
+        return groth16_prove_batch_dev_t<G1, G2>(ctx, pk, cs, bs, log_n, src, flags, r, s, count, proofs);
+    // The resident prover takes its assignment from host memory: assignments that live on the device, or that a producer makes, come through host staging
+    // of at most ZL_G16_BATCH_HOST_STAGE bytes at a time.
+    const size_t block = src.host ? count : std::min(count, std::max<size_t>(1, ZL_G16_BATCH_HOST_STAGE / (nv * 32)));
+    std::vector<uint64_t> staged(src.host ? 0 : block * nv * 4);
+    for (size_t c0 = 0; c0 < count; c0 += block) {
+        const size_t ch = std::min(block, count - c0);
+        const uint64_t* rows = src.host;
+        if (!src.host) {
+            if (src.dev) {
+                ZL_HIP(ctx, hipMemcpyAsync(staged.data(), src.dev + c0 * nv * 4, ch * nv * 32, hipMemcpyDeviceToHost, ctx->stream));
+                ZL_HIP(ctx, hipStreamSynchronize(ctx->stream));
+            } else {
+                const int rc = src.fill_host(c0, ch, staged.data());
+                if (rc) return rc;
+            }
+            rows = staged.data();
+        }
+        for (size_t j = c0; j < c0 + ch; j++) {
+            const int rc = groth16_prove_t<G1, G2>(ctx, pk, cs, rows + (src.host ? j : j - c0) * nv * 4, flags, r + 4 * j, s + 4 * j, proofs + j);
+            if (rc) return rc;
+        }
     }
     return ZL_OK;
+}
+static int groth16_prove_batch_any(zl_ctx* ctx, const zl_g16_pk* pk, const zl_r1cs_dev* rd, const G16BatchSource& src, unsigned flags, const uint64_t* r, const uint64_t* s,
+                                   size_t count, zl_g16_proof* proofs) {
+    ZL_HIP(ctx, hipSetDevice(ctx->device));
+    if (pk->curve == ZL_BLS12_381) return groth16_prove_batch_t<BlsG1, BlsG2>(ctx, pk, rd, src, flags, r, s, count, proofs);
+    if (pk->curve == ZL_BN254) return groth16_prove_batch_t<BnG1, BnG2>(ctx, pk, rd, src, flags, r, s, count, proofs);
+    return ZL_EINVAL;
 }
 extern "C" int zl_groth16_prove_batch(zl_ctx* ctx, const zl_g16_pk* pk, uint64_t r1cs_handle, const uint64_t* assignments, unsigned flags, const uint64_t* r,
                                       const uint64_t* s, size_t count, zl_g16_proof* proofs) {
@@ -1167,10 +1211,44 @@ extern "C" int zl_groth16_prove_batch(zl_ctx* ctx, const zl_g16_pk* pk, uint64_t
     const zl_r1cs_dev* rd = zl_find_r1cs(ctx, r1cs_handle);
     if (!rd || rd->curve != (int)pk->curve) return ZL_EHANDLE;
     if (count == 0) return ZL_OK;
-    ZL_HIP(ctx, hipSetDevice(ctx->device));
-    if (pk->curve == ZL_BLS12_381) return groth16_prove_batch_t<BlsG1, BlsG2>(ctx, pk, rd, assignments, flags, r, s, count, proofs);
-    if (pk->curve == ZL_BN254) return groth16_prove_batch_t<BnG1, BnG2>(ctx, pk, rd, assignments, flags, r, s, count, proofs);
-    return ZL_EINVAL;
+    G16BatchSource src;
+    src.host = assignments;
+    return groth16_prove_batch_any(ctx, pk, rd, src, flags, r, s, count, proofs);
+}
+extern "C" int zl_groth16_prove_batch_dev(zl_ctx* ctx, const zl_g16_pk* pk, uint64_t r1cs_handle, const void* d_assignments, unsigned flags, const uint64_t* r,
+                                          const uint64_t* s, size_t count, zl_g16_proof* proofs) {
+    if (!ctx || !pk || (flags & ~ZL_MONT) || (count && (!d_assignments || !r || !s || !proofs))) return ZL_EINVAL;
+    if (!pk->alpha_g1 || !pk->beta_g1 || !pk->delta_g1 || !pk->beta_g2 || !pk->delta_g2) return ZL_EINVAL;
+    const zl_r1cs_dev* rd = zl_find_r1cs(ctx, r1cs_handle);
+    if (!rd || rd->curve != (int)pk->curve) return ZL_EHANDLE;
+    if (count == 0) return ZL_OK;
+    G16BatchSource src;
+    src.dev = static_cast<const uint64_t*>(d_assignments);
+    return groth16_prove_batch_any(ctx, pk, rd, src, flags, r, s, count, proofs);
+}
+extern "C" int zl_groth16_prove_poseidon_chains(zl_ctx* ctx, const zl_g16_pk* pk, uint64_t r1cs_handle, uint32_t k, const uint64_t* x0, const uint64_t* x1, const uint64_t* r,
+                                                const uint64_t* s, size_t count, zl_g16_proof* proofs, uint64_t* public_out) {
+    const size_t nv = zl_poseidon_chain_assignment_elems(k);
+    if (!ctx || !pk || nv == 0 || (count && (!x0 || !x1 || !r || !s || !proofs))) return ZL_EINVAL;
+    if (!pk->alpha_g1 || !pk->beta_g1 || !pk->delta_g1 || !pk->beta_g2 || !pk->delta_g2) return ZL_EINVAL;
+    const zl_r1cs_dev* rd = zl_find_r1cs(ctx, r1cs_handle);
+    if (!rd || rd->curve != (int)pk->curve) return ZL_EHANDLE;
+    if (pk->curve != ZL_BLS12_381 && pk->curve != ZL_BN254) return ZL_EINVAL;
+    // the shape of a k-link chain; what the matrices say cannot be checked, as with a witness-only compiler
+    if (rd->n_instance != 2 || rd->n_witness != nv - 2 || rd->n_constraints != nv - 3) return ZL_EINVAL;
+    if (count == 0) return ZL_OK;
+    const zl_curve_t curve = pk->curve;
+    G16BatchSource src;
+    src.fill_dev = [=](size_t c0, size_t ch, void* d_rows) {
+        return zl_poseidon_trace_rows(ctx, (int)curve, x0 + c0 * 4, x1 + c0 * 4, k, ch, d_rows, nv, public_out ? public_out + c0 * 4 : nullptr);
+    };
+    src.fill_host = [=](size_t c0, size_t ch, uint64_t* rows) {
+        const int rc = zl_poseidon_chain_assignments(ctx, curve, x0 + c0 * 4, x1 + c0 * 4, k, ch, rows);
+        if (rc == ZL_OK && public_out)
+            for (size_t j = 0; j < ch; j++) memcpy(public_out + (c0 + j) * 4, rows + j * nv * 4 + 4, 32);
+        return rc;
+    };
+    return groth16_prove_batch_any(ctx, pk, rd, src, 0, r, s, count, proofs);
 }
 extern "C" int zl_groth16_last_h(zl_ctx* ctx, uint64_t* out, size_t n) {
     if (!ctx || !out || !ctx->g16_h || n > ctx->g16_h_n) return ZL_EINVAL;

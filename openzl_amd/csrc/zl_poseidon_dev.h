@@ -25,6 +25,10 @@ constexpr int DEFAULT_CHUNK = 1 << 20, DEFAULT_TAIL = 256, DEFAULT_DEV_MIN = 64;
 constexpr size_t STAGE_BUDGET = (size_t)256 << 20;  // bytes of ZL_SLOT_POSEIDON one staged chunk may take
 constexpr size_t FLAG_BYTES = 256;                  // the flag word's corner of the slot
 
+// the chain circuit's assignment (zl_poseidon_chain_assignments): 1, h_k, x0, x1, then per link x^2, x^4, x^5 of its 79 S-boxes less the constant one
+constexpr int TRACE_PER_LINK = 3 * (FULL_ROUNDS * WIDTH + PARTIAL_ROUNDS - 1);
+static_assert(TRACE_PER_LINK == 234, "78 recorded S-boxes per link");
+
 constexpr bool geometry_ok(size_t n, unsigned depth) { return depth >= 1 && depth <= MAX_DEPTH && ((n >> depth) == 0 || n == ((size_t)1 << depth)); }
 constexpr size_t level_size(size_t n, unsigned k) { return k >= 64 ? (n ? 1 : 0) : (n >> k) + ((n & (((size_t)1 << k) - 1)) ? 1 : 0); }  // ceil(n / 2^k)
 constexpr size_t level_offset(size_t n, unsigned k) {  // elements in front of level k
@@ -34,3 +38,9 @@ constexpr size_t level_offset(size_t n, unsigned k) {  // elements in front of l
 }
 }  // namespace poseidon_dev
 }  // namespace openzl
+
+// The fused prover's producer (zl_groth16.hip): the assignments of `count` chains from HOST inputs straight into rows in DEVICE memory (row i at d_rows + i *
+// stride_elems elements, 16-byte aligned), h_k of every chain to public_out (host, may be null).  Inputs are staged through ZL_SLOT_POSEIDON, launches are of at
+// most ZL_TUNE_POSEIDON_CHUNK chains; finished on return, ZL_EINVAL for an input >= r.  ctx's device is current; curve and k are the caller's to check.
+struct zl_ctx;
+int zl_poseidon_trace_rows(zl_ctx* ctx, int curve, const uint64_t* x0, const uint64_t* x1, uint32_t k, size_t count, void* d_rows, size_t stride_elems, uint64_t* public_out);

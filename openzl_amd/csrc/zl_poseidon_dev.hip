@@ -7,6 +7,8 @@
 //                    loop inside the lane).  Thin wrappers around ONE __device__ permutation, permute_dev: the three state elements stay in registers for
 //                    all 63 rounds; round keys, MDS entries and the domain tag come from a 199-entry device table (zl_poseidon_dev.h) at wave-uniform
 //                    addresses -- the compiler reads them with uniform loads -- already in the multiplier's Montgomery form (x R', R' = 2^261).
+//   k_pos_chain_trace  k_pos_chain that also WRITES what the lane computes on the way: the complete assignment of zl_circuit_poseidon_chain(curve, k, x0, x1)
+//                    -- 1, h_k, x0, x1, then x^2, x^4, x^5 of every S-box the circuit allocates -- as one row of canonical words per chain.
 //   k_pos_tail       one workgroup finishes ALL remaining levels of a Merkle tree once a level has at most T nodes: the level lives in LDS (two buffers,
 //                    canonical words), __syncthreads() between levels, every level is also written to the node array at the offsets the wide path uses.
 //   k_pos_gather     sibling digests of `count` leaves out of a device node array.
@@ -66,7 +68,9 @@ ZL_HD void store_canon(uint64_t* w, const Fp<FrP>& m) {
 //     plus its round key: < 8r.  S-box: x^2 = mul(x, x) needs 8 * 8 = 64, x^4 = mul(x^2, x^2) 2 * 2, x^5 = mul(x^4, x) 2 * 8; the MDS product multiplies an
 //     entry < 2r by an element < 8r (the lanes a partial round leaves without S-box): 16.  The largest requirement, 64, is within MUL_BOUND of both fields
 //     (70 and 169: the static_assert below);
-//   * sums stay below 8r < 2^259: far inside the 261 bits of nine limbs and wred's limit of 128 r; the output is canon(mul(x, 1)): a product < 2r.
+//   * sums stay below 8r < 2^259: far inside the 261 bits of nine limbs and wred's limit of 128 r; the output is canon(mul(x, 1)): a product < 2r;
+//   * the values k_pos_chain_trace records -- x^2, x^4, x^5 of an S-box -- are products themselves (< 2r), so dstore's mul(x, 1) takes them at 2 * 1 and
+//     its canon sees a product again; recording reads the S-box's intermediates and changes none of them, so every bound above holds unchanged.
 template <class FrP> struct LazyP;
 template <> struct LazyP<BLS12_381_Fr> { using P = BLS12_381_Fr29; };
 template <> struct LazyP<BN254_Fr> { using P = BN254_Fr29; };
@@ -104,7 +108,34 @@ __device__ __forceinline__ void dstore(uint64_t* w, const El<FrP>& m) {
 #pragma unroll
     for (int i = 0; i < 4; i++) w[i] = (uint64_t)v[2 * i] | ((uint64_t)v[2 * i + 1] << 32);
 }
+// the same into a 16-byte aligned destination: two 16-byte stores instead of four 8-byte ones (the rows of k_pos_chain_trace)
+template <class FrP>
+__device__ __forceinline__ void dstore16(uint64_t* w, const El<FrP>& m) {
+    using P = typename LazyP<FrP>::P;
+    uint32_t o[8] = {1, 0, 0, 0, 0, 0, 0, 0};
+    const El<FrP> c = zl::canon(zl::mul(m, zl::unpack28r<P>(o)));
+    uint32_t v[8];
+    zl::pack28r<P>(v, c);
+    ulonglong2* q = reinterpret_cast<ulonglong2*>(w);
+    q[0] = make_ulonglong2((uint64_t)v[0] | ((uint64_t)v[1] << 32), (uint64_t)v[2] | ((uint64_t)v[3] << 32));
+    q[1] = make_ulonglong2((uint64_t)v[4] | ((uint64_t)v[5] << 32), (uint64_t)v[6] | ((uint64_t)v[7] << 32));
+}
 // ---------------------------------------------------------------------------------------------------------------- the device permutation
+// What an S-box hands to its recorder: nothing (every kernel but the trace), or x^2, x^4, x^5 appended to the lane's assignment row.
+struct NoRec {
+    template <class E>
+    __device__ __forceinline__ void operator()(const E&, const E&, const E&) {}
+};
+template <class FrP>
+struct RowRec {
+    uint64_t* w;  // the next record of the lane's row
+    __device__ __forceinline__ void operator()(const El<FrP>& x2, const El<FrP>& x4, const El<FrP>& x5) {
+        dstore16<FrP>(w, x2);
+        dstore16<FrP>(w + 4, x4);
+        dstore16<FrP>(w + 8, x5);
+        w += 12;
+    }
+};
 template <class FrP>
 __device__ __forceinline__ El<FrP> tab_ld(const uint32_t* __restrict__ tab, int entry) {
     El<FrP> r;
@@ -112,25 +143,27 @@ __device__ __forceinline__ El<FrP> tab_ld(const uint32_t* __restrict__ tab, int 
     for (int k = 0; k < El<FrP>::L; k++) r.l[k] = tab[entry * TABW + k];
     return r;
 }
-template <class FrP>
-__device__ __forceinline__ void sbox(El<FrP>& x) {
+template <class FrP, class Rec>
+__device__ __forceinline__ void sbox(El<FrP>& x, Rec& rec, bool recorded) {
     const El<FrP> x2 = zl::mul(x, x), x4 = zl::mul(x2, x2);
     x = zl::mul(x4, x);
+    if (recorded) rec(x2, x4, x);
 }
 // 63 rounds of add-round-key / x^5 / MDS: 8 * (9 + 9) + 55 * (3 + 9) = 804 multiplications.  One rolled loop (18 inlined multiplier bodies), the full / partial
-// choice is a wave-uniform branch.
-template <class FrP>
-__device__ __forceinline__ void permute_dev(const uint32_t* __restrict__ tab, El<FrP>& s0, El<FrP>& s1, El<FrP>& s2) {
+// choice is a wave-uniform branch.  `rec` sees the S-boxes in the order the in-circuit hash allocates them, without lane 0 of round 0: its input is the domain
+// tag plus a round key, a constant, and the circuit folds it (poseidon::hash in zl_host.h; permute_native_record is the host's form of this).
+template <class FrP, class Rec>
+__device__ __forceinline__ void permute_dev(const uint32_t* __restrict__ tab, El<FrP>& s0, El<FrP>& s1, El<FrP>& s2, Rec& rec) {
     constexpr int half = pd::FULL_ROUNDS / 2;
 #pragma unroll 1
     for (int rnd = 0; rnd < pd::ROUNDS; rnd++) {
         s0 = zl::add(s0, tab_ld<FrP>(tab, pd::TAB_KEYS + 3 * rnd));
         s1 = zl::add(s1, tab_ld<FrP>(tab, pd::TAB_KEYS + 3 * rnd + 1));
         s2 = zl::add(s2, tab_ld<FrP>(tab, pd::TAB_KEYS + 3 * rnd + 2));
-        sbox<FrP>(s0);
+        sbox<FrP>(s0, rec, rnd != 0);
         if (rnd < half || rnd >= half + pd::PARTIAL_ROUNDS) {
-            sbox<FrP>(s1);
-            sbox<FrP>(s2);
+            sbox<FrP>(s1, rec, true);
+            sbox<FrP>(s2, rec, true);
         }
         El<FrP> nx[3];
 #pragma unroll
@@ -148,7 +181,8 @@ __device__ __forceinline__ void permute_dev(const uint32_t* __restrict__ tab, El
 template <class FrP>
 __device__ __forceinline__ El<FrP> hash2_dev(const uint32_t* __restrict__ tab, const El<FrP>& x, const El<FrP>& y) {
     El<FrP> s0 = tab_ld<FrP>(tab, pd::TAB_TAG), s1 = x, s2 = y;
-    permute_dev<FrP>(tab, s0, s1, s2);
+    NoRec none;
+    permute_dev<FrP>(tab, s0, s1, s2, none);
     return s0;
 }
 
@@ -165,7 +199,8 @@ __global__ __launch_bounds__(BLOCK) void k_pos_permute(const uint32_t* __restric
     ok &= dload<FrP>(st + 4, s1);
     ok &= dload<FrP>(st + 8, s2);
     if (!ok) atomicOr(flag, 1u);
-    permute_dev<FrP>(tab, s0, s1, s2);
+    NoRec none;
+    permute_dev<FrP>(tab, s0, s1, s2, none);
     dstore<FrP>(st, s0);
     dstore<FrP>(st + 4, s1);
     dstore<FrP>(st + 8, s2);
@@ -193,6 +228,39 @@ __global__ __launch_bounds__(BLOCK) void k_pos_chain(const uint32_t* __restrict_
 #pragma unroll 1
     for (uint32_t j = 0; j < k; j++) h = hash2_dev<FrP>(tab, h, b);
     dstore<FrP>(out + p * 4, h);
+}
+// k_pos_chain with the witness written out: row p = out + p * stride elements (16-byte aligned) receives [0] = 1, [1] = h_k, [2] = x0, [3] = x1 and, from [4] on,
+// the 234 records of each link in turn; elements from 4 + 234 k to the stride are not touched.  pub (may be null) receives h_k once more, densely.  Every lane
+// stores 32 bytes at a time at a stride of one row.  Measured against rows staged through LDS (a wave then writes runs of 288 bytes): 12 - 15 % ahead from 2^10
+// to 2^16 chains, where a launch takes the 0.56 ms of ONE chain whatever its width, 13 % behind at 2^18 (profiles/chain_trace_layout_ab.log);
+// the batched prover's chunks stay below 2^13 chains.
+template <class FrP>
+__global__ __launch_bounds__(BLOCK) void k_pos_chain_trace(const uint32_t* __restrict__ tab, const uint64_t* __restrict__ x0, const uint64_t* __restrict__ x1, uint32_t k,
+                                                           size_t n, uint64_t* __restrict__ out, size_t stride, uint64_t* __restrict__ pub, uint32_t* __restrict__ flag) {
+    const size_t p = (size_t)blockIdx.x * BLOCK + threadIdx.x;
+    if (p >= n) return;
+    El<FrP> h, b;
+    bool ok = dload<FrP>(x0 + p * 4, h);
+    ok &= dload<FrP>(x1 + p * 4, b);
+    if (!ok) atomicOr(flag, 1u);
+    uint64_t* row = out + p * stride * 4;
+    RowRec<FrP> rec{row + 16};
+#pragma unroll 1
+    for (uint32_t j = 0; j < k; j++) {
+        El<FrP> s0 = tab_ld<FrP>(tab, pd::TAB_TAG), s2 = b;
+        permute_dev<FrP>(tab, s0, h, s2, rec);
+        h = s0;
+    }
+    ulonglong2* q = reinterpret_cast<ulonglong2*>(row);
+    q[0] = make_ulonglong2(1, 0);
+    q[1] = make_ulonglong2(0, 0);
+    dstore16<FrP>(row + 4, h);
+#pragma unroll
+    for (int i = 0; i < 4; i++) {
+        row[8 + i] = x0[p * 4 + i];
+        row[12 + i] = x1[p * 4 + i];
+    }
+    if (pub) dstore<FrP>(pub + p * 4, h);
 }
 // one lane per path: `depth` dependent hashes, the running digest on the right when the index bit of the level is set
 template <class FrP>
@@ -343,6 +411,33 @@ int host_chain(const uint64_t* x0, const uint64_t* x1, uint32_t k, size_t count,
             h = st[0];
         }
         store_canon<FrP>(out + i * 4, h);
+        return ok;
+    }) ? ZL_OK : ZL_EINVAL;
+}
+// row i = the assignment of chain i (nv = 4 + 234 k elements): what poseidon_chain_witness allocates, through permute_native_record
+template <class FrP>
+int host_assignments(const uint64_t* x0, const uint64_t* x1, uint32_t k, size_t count, uint64_t* out, size_t nv) {
+    consts<FrP>();
+    return host_for(count, [&](size_t i) {
+        Fp<FrP> h, b;
+        bool ok = load_canon<FrP>(x0 + i * 4, h);
+        ok &= load_canon<FrP>(x1 + i * 4, b);
+        uint64_t* row = out + i * nv * 4;
+        std::vector<Fp<FrP>> rec;  // one link at a time: 234 elements, whatever k is
+        rec.reserve(pd::TRACE_PER_LINK);
+        for (uint32_t j = 0; j < k; j++) {
+            Fp<FrP> st[3] = {zl::from_u64<FrP>(3), h, b};
+            rec.clear();
+            poseidon::permute_native_record(consts<FrP>(), st, rec);
+            h = st[0];
+            uint64_t* link = row + 16 + (size_t)j * pd::TRACE_PER_LINK * 4;
+            for (size_t t = 0; t < rec.size(); t++) store_canon<FrP>(link + 4 * t, rec[t]);
+        }
+        row[0] = 1;
+        row[1] = row[2] = row[3] = 0;
+        store_canon<FrP>(row + 4, h);
+        memcpy(row + 8, x0 + i * 4, 32);
+        memcpy(row + 12, x1 + i * 4, 32);
         return ok;
     }) ? ZL_OK : ZL_EINVAL;
 }
@@ -543,6 +638,71 @@ int dev_chain(zl_ctx* ctx, const uint64_t* x0, const uint64_t* x1, uint32_t k, s
     }
     return finish(ctx, s.flag);
 }
+// device operands, launches of at most one chunk: row i at d_out + i * stride elements, h_k of chain i also at d_pub + i when d_pub is not null
+template <class FrP>
+int launch_trace(zl_ctx* ctx, const uint32_t* tab, const uint64_t* d_x0, const uint64_t* d_x1, uint32_t k, size_t count, uint64_t* d_out, size_t stride, uint64_t* d_pub,
+                 uint32_t* flag) {
+    const size_t chunk = tune_chunk();
+    for (size_t first = 0; first < count; first += chunk) {
+        const size_t m = count - first < chunk ? count - first : chunk;
+        uint64_t* pub = d_pub ? d_pub + first * 4 : nullptr;
+        ZL_POS_LAUNCH(ctx, (k_pos_chain_trace<FrP>), blocks_of(m), BLOCK, 0, tab, d_x0 + first * 4, d_x1 + first * 4, k, m, d_out + first * stride * 4, stride, pub, flag);
+    }
+    return ZL_OK;
+}
+template <class FrP>
+int dev_assignments_dev(zl_ctx* ctx, const void* d_x0, const void* d_x1, uint32_t k, size_t count, void* d_out, size_t stride) {
+    const uint32_t* tab;
+    int rc = get_table<FrP>(ctx, &tab);
+    if (rc) return rc;
+    Stage s;
+    if ((rc = stage_get(ctx, 0, &s))) return rc;
+    if ((rc = launch_trace<FrP>(ctx, tab, static_cast<const uint64_t*>(d_x0), static_cast<const uint64_t*>(d_x1), k, count, static_cast<uint64_t*>(d_out), stride, nullptr,
+                                s.flag)))
+        return rc;
+    return finish(ctx, s.flag);
+}
+// host inputs, rows in DEVICE memory (the fused prover's chunk: zl_poseidon_dev.h), h_k of every chain to host_pub when it is not null
+template <class FrP>
+int dev_trace_rows(zl_ctx* ctx, const uint64_t* x0, const uint64_t* x1, uint32_t k, size_t count, uint64_t* d_rows, size_t stride, uint64_t* host_pub) {
+    const uint32_t* tab;
+    int rc = get_table<FrP>(ctx, &tab);
+    if (rc) return rc;
+    const size_t chunk = stage_items(96), m0 = count < chunk ? count : chunk, seg = up256(m0 * 32);
+    Stage s;
+    if ((rc = stage_get(ctx, 3 * seg, &s))) return rc;
+    uint64_t* d0 = reinterpret_cast<uint64_t*>(s.data);
+    uint64_t* d1 = reinterpret_cast<uint64_t*>(s.data + seg);
+    uint64_t* d_pub = host_pub ? reinterpret_cast<uint64_t*>(s.data + 2 * seg) : nullptr;
+    for (size_t first = 0; first < count; first += chunk) {
+        const size_t m = count - first < chunk ? count - first : chunk;
+        ZL_HIP(ctx, hipMemcpyAsync(d0, x0 + first * 4, m * 32, hipMemcpyHostToDevice, ctx->stream));
+        ZL_HIP(ctx, hipMemcpyAsync(d1, x1 + first * 4, m * 32, hipMemcpyHostToDevice, ctx->stream));
+        if ((rc = launch_trace<FrP>(ctx, tab, d0, d1, k, m, d_rows + first * stride * 4, stride, d_pub, s.flag))) return rc;
+        if (host_pub) ZL_HIP(ctx, hipMemcpyAsync(host_pub + first * 4, d_pub, m * 32, hipMemcpyDeviceToHost, ctx->stream));
+    }
+    return finish(ctx, s.flag);
+}
+template <class FrP>
+int dev_assignments(zl_ctx* ctx, const uint64_t* x0, const uint64_t* x1, uint32_t k, size_t count, uint64_t* out, size_t nv) {
+    const uint32_t* tab;
+    int rc = get_table<FrP>(ctx, &tab);
+    if (rc) return rc;
+    const size_t chunk = stage_items(64 + nv * 32), m0 = count < chunk ? count : chunk, seg = up256(m0 * 32);
+    Stage s;
+    if ((rc = stage_get(ctx, 2 * seg + m0 * nv * 32, &s))) return rc;
+    uint64_t* d0 = reinterpret_cast<uint64_t*>(s.data);
+    uint64_t* d1 = reinterpret_cast<uint64_t*>(s.data + seg);
+    uint64_t* d_out = reinterpret_cast<uint64_t*>(s.data + 2 * seg);
+    for (size_t first = 0; first < count; first += chunk) {
+        const size_t m = count - first < chunk ? count - first : chunk;
+        ZL_HIP(ctx, hipMemcpyAsync(d0, x0 + first * 4, m * 32, hipMemcpyHostToDevice, ctx->stream));
+        ZL_HIP(ctx, hipMemcpyAsync(d1, x1 + first * 4, m * 32, hipMemcpyHostToDevice, ctx->stream));
+        if ((rc = launch_trace<FrP>(ctx, tab, d0, d1, k, m, d_out, nv, nullptr, s.flag))) return rc;
+        ZL_HIP(ctx, hipMemcpyAsync(out + first * nv * 4, d_out, m * nv * 32, hipMemcpyDeviceToHost, ctx->stream));
+    }
+    return finish(ctx, s.flag);
+}
 template <class FrP>
 int dev_fold(zl_ctx* ctx, const uint64_t* leaves, const uint64_t* indices, const uint64_t* paths, unsigned depth, size_t count, uint64_t* roots) {
     const uint32_t* tab;
@@ -655,6 +815,10 @@ int dev_paths(zl_ctx* ctx, const void* d_nodes, size_t n, unsigned depth, const 
 
 #define ZL_POS_CURVE(curve, fn, ...) ((curve) == ZL_BLS12_381 ? fn<BLS12_381_Fr>(__VA_ARGS__) : fn<BN254_Fr>(__VA_ARGS__))
 
+int zl_poseidon_trace_rows(zl_ctx* ctx, int curve, const uint64_t* x0, const uint64_t* x1, uint32_t k, size_t count, void* d_rows, size_t stride_elems, uint64_t* public_out) {
+    return ZL_POS_CURVE(curve, dev_trace_rows, ctx, x0, x1, k, count, static_cast<uint64_t*>(d_rows), stride_elems, public_out);
+}
+
 extern "C" {
 
 int zl_poseidon_permute_batch(zl_ctx* ctx, zl_curve_t curve, uint64_t* states, size_t count) {
@@ -683,6 +847,26 @@ int zl_poseidon_chain_batch(zl_ctx* ctx, zl_curve_t curve, const uint64_t* x0, c
     if (on_host(ctx, count)) return ZL_POS_CURVE(curve, host_chain, x0, x1, k, count, out);
     ZL_HIP(ctx, hipSetDevice(ctx->device));
     return ZL_POS_CURVE(curve, dev_chain, ctx, x0, x1, k, count, out);
+}
+size_t zl_poseidon_chain_assignment_elems(uint32_t k) {
+    const uint64_t nv = 4 + (uint64_t)pd::TRACE_PER_LINK * k;
+    return k == 0 || nv >= (1ull << 31) ? 0 : (size_t)nv;
+}
+int zl_poseidon_chain_assignments_dev(zl_ctx* ctx, zl_curve_t curve, const void* d_x0, const void* d_x1, uint32_t k, size_t count, void* d_out, size_t stride_elems) {
+    const size_t nv = zl_poseidon_chain_assignment_elems(k);
+    if (!ctx || !valid_curve(curve) || nv == 0 || stride_elems < nv || (count && (!d_x0 || !d_x1 || !d_out)) || ((uintptr_t)d_out & 15)) return ZL_EINVAL;
+    if (count == 0) return ZL_OK;
+    ZL_HIP(ctx, hipSetDevice(ctx->device));
+    return ZL_POS_CURVE(curve, dev_assignments_dev, ctx, d_x0, d_x1, k, count, d_out, stride_elems);
+}
+int zl_poseidon_chain_assignments(zl_ctx* ctx, zl_curve_t curve, const uint64_t* x0, const uint64_t* x1, uint32_t k, size_t count, uint64_t* out) {
+    const size_t nv = zl_poseidon_chain_assignment_elems(k);
+    // (a staged chunk holds whole rows: one row with its inputs must fit the slot's byte budget, k <= 35 848)
+    if (!valid_curve(curve) || nv == 0 || 64 + nv * 32 > pd::STAGE_BUDGET || (count && (!x0 || !x1 || !out))) return ZL_EINVAL;
+    if (count == 0) return ZL_OK;
+    if (on_host(ctx, count)) return ZL_POS_CURVE(curve, host_assignments, x0, x1, k, count, out, nv);
+    ZL_HIP(ctx, hipSetDevice(ctx->device));
+    return ZL_POS_CURVE(curve, dev_assignments, ctx, x0, x1, k, count, out, nv);
 }
 size_t zl_poseidon_merkle_nodes(size_t n, unsigned depth) {
     return pd::geometry_ok(n, depth) ? pd::level_offset(n, depth + 1) : 0;
