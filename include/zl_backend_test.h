@@ -151,6 +151,30 @@ int zl_test_endo_split(zl_ctx* ctx, zl_curve_t curve, zl_group_t group, const ui
 int zl_test_endo_split_inf(zl_ctx* ctx, zl_curve_t curve, zl_group_t group, const uint64_t* scalars, const uint8_t* inf, size_t n, uint32_t* out_records, int* endo_k,
                            int* part_bits);
 
+/* The MSM planner's choices, for the tests that must reach every launch form at small sizes (openzl_amd/csrc/zl_msm_job.h, zl_msm.hip).
+ * zl_test_msm_plan runs MsmJob::plan alone for a single MSM over points [first, first + n) of the handle -- under the ctx's forced window
+ * (zl_ctx_set_msm_window) and the ZL_TUNE_* environment of the moment, exactly as the next zl_msm call would -- and reports the plan: no launch, no device
+ * allocation.  The predicates are the members the launch code itself asks (acc_quad, by_cuts, ...), not a copy of their arithmetic.
+ *   c, W, SETS, NB: window bits, windows, bucket sets, buckets of all sets; sc_bits: width of what is recoded (the scalar, or a part of its split)
+ *   glv, endo_k: the job runs on endo_k parts per scalar (1: plain scalars);  wide: three-level sort;  pre: table of a precomputed handle
+ *   chunk, nchunks, big_span: entries per accumulation chunk, chunks, and the cut count above which a bucket leaves the serial fold for the big list
+ *   red_g0, red_levels, spread_t: level-0 block length of the bucket reduction, tree levels, and the bits of a spread top window (-1: not spread)
+ *   nslices, per_slice, fsl, Gn: sort slices, scalars per slice, level-2 slices (wide sort), sort groups
+ *   sort_lds: the LDS counting sort (else wide, or global atomics when !wide);  lds_prefix_small, lds_ranges: its one-block prefix and its scatter ranges (0 otherwise)
+ *   fine_cap, fine_threads: staged entries and threads per block of the wide sort's last level (0 unless wide)
+ *   acc_quad: four (G2: eight) lanes per chunk in the accumulation, else one lane (G2: a lane pair)
+ *   tail_quad_max: tail launches of at most this many lanes run four (eight) lanes per operation;  by_cuts: merge by chunk boundaries, else per bucket
+ *   may_big, may_giant: the big / giant bucket kernels are launched
+ * ZL_EINVAL for a null ctx or out, ZL_EHANDLE for an unknown handle, otherwise the planner's own code.
+ * zl_test_msm_batch_form: how zl_msm_batch_partial_dev / the job driver runs `count` >= 2 jobs, the biggest of `biggest` points: *side = side-by-side lanes (else the
+ * three-stream pipeline over three buffer sets), *lanes = buffer sets in rotation, *phased = phase-major issue.  Host only. */
+typedef struct zl_test_msm_plan_s {
+    int32_t c, W, SETS, NB, sc_bits, glv, endo_k, wide, pre, chunk, nchunks, big_span, red_g0, red_levels, spread_t, nslices, per_slice, fsl, Gn;
+    int32_t sort_lds, lds_prefix_small, lds_ranges, fine_cap, fine_threads, acc_quad, tail_quad_max, by_cuts, may_big, may_giant;
+} zl_test_msm_plan_t;
+int zl_test_msm_plan(zl_ctx* ctx, uint64_t bases, size_t first, size_t n, zl_test_msm_plan_t* out);
+int zl_test_msm_batch_form(size_t count, uint64_t biggest, int* side, int* lanes, int* phased);
+
 /* The point decoders behind zl_points_from_bytes_batch (openzl_amd/csrc/zl_decode.h: lane-uniform square roots, sign rule, multiplication by r), compiled
  * for the HOST: arguments, outputs and statuses as zl_points_from_bytes_batch, no ctx.  The device kernels run the same templates. */
 int zl_test_decode_points_host(zl_curve_t curve, zl_group_t group, const uint8_t* in, size_t count, uint64_t* out_xy, uint8_t* out_inf, int32_t* status);

@@ -784,7 +784,8 @@ TEST_ABI_SYMBOLS = ["zl_test_poseidon_permute_dev", "zl_test_fp28_op", "zl_test_
                     "zl_test_poseidon_permute_dev28r", "zl_test_fq_mul_clock", "zl_test_acc_clock", "zl_test_acc_clock_read", "zl_test_clock_probe_launch", "zl_test_clock_probe_read",
                     "zl_test_miller_dev", "zl_test_final_exp", "zl_test_verify_batch_host", "zl_test_ntt_plan", "zl_test_ntt_fit_beside", "zl_test_fp2pair_op", "zl_test_point_form_op",
                     "zl_test_endo_split", "zl_test_endo_split_inf", "zl_test_decode_points_host", "zl_test_fq2_sqrt",
-                    "zl_test_final_exp_dev", "zl_test_fq12_inverse", "zl_test_fq12_zeta", "zl_test_pairing_product_scaled"]
+                    "zl_test_final_exp_dev", "zl_test_fq12_inverse", "zl_test_fq12_zeta", "zl_test_pairing_product_scaled",
+                    "zl_test_msm_plan", "zl_test_msm_batch_form"]
 
 
 def _p32(a: np.ndarray):
@@ -837,6 +838,36 @@ def hook_endo_split(be: "Backend", curve: int, group: int, scalars: np.ndarray, 
         rc = be.L.zl_test_endo_split_inf(be._ctx, curve, group, _p64(s), f.ctypes.data_as(u8p), n, _p32(out), C.byref(k), C.byref(bits))
     be._check(rc, "zl_test_endo_split")
     return out[: k.value * n * 8].reshape(k.value, n, 8).copy(), int(out[k.value * n * 8]), k.value, bits.value
+
+
+class MsmPlanC(C.Structure):
+    """zl_test_msm_plan_t (include/zl_backend_test.h)"""
+    _fields_ = [(f, C.c_int32) for f in ("c W SETS NB sc_bits glv endo_k wide pre chunk nchunks big_span red_g0 red_levels spread_t nslices per_slice fsl Gn "
+                                         "sort_lds lds_prefix_small lds_ranges fine_cap fine_threads acc_quad tail_quad_max by_cuts may_big may_giant").split()]
+
+    def __repr__(self):
+        return "MsmPlan(" + ", ".join(f"{f}={getattr(self, f)}" for f, _ in self._fields_) + ")"
+
+
+def hook_msm_plan(be: "Backend", handle: int, n: int, first: int = 0) -> MsmPlanC:
+    """the plan of the next single MSM over points [first, first + n) of the handle, under the ctx's forced window and the ZL_TUNE_* environment of the moment
+    (zl_test_msm_plan: MsmJob::plan alone, nothing launched or allocated), with the launch forms the driver derives from it"""
+    p = MsmPlanC()
+    be.L.zl_test_msm_plan.argtypes = [C.c_void_p, C.c_uint64, C.c_size_t, C.c_size_t, C.POINTER(MsmPlanC)]
+    be._check(be.L.zl_test_msm_plan(be._ctx, handle, first, n, C.byref(p)), "zl_test_msm_plan")
+    return p
+
+
+def hook_msm_batch_form(count: int, biggest: int) -> dict:
+    """how the job driver runs a batch of `count` MSMs, the biggest of `biggest` points (zl_test_msm_batch_form; host only): side (side-by-side lanes, else the
+    three-stream pipeline), lanes (buffer sets in rotation), phased (phase-major issue)"""
+    L = load_library()
+    L.zl_test_msm_batch_form.argtypes = [C.c_size_t, C.c_uint64, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]
+    s, l, p = C.c_int(0), C.c_int(0), C.c_int(0)
+    rc = L.zl_test_msm_batch_form(count, biggest, C.byref(s), C.byref(l), C.byref(p))
+    if rc != 0:
+        raise BackendError(rc, "zl_test_msm_batch_form")
+    return {"side": bool(s.value), "lanes": l.value, "phased": bool(p.value)}
 
 
 def hook_poseidon_permute_dev(be: "Backend", curve: int, state: np.ndarray) -> np.ndarray:

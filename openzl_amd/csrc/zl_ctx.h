@@ -3,6 +3,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stdlib.h>
+#include <algorithm>
 #include <atomic>
 #include <functional>
 #include <initializer_list>
@@ -304,6 +305,21 @@ inline int zl_tune(const char* name, int dflt) {
     const char* v = getenv(name);
     return v ? atoi(v) : dflt;
 }
+// How msm_run_jobs_t (zl_msm.hip) runs a batch of `count` >= 2 jobs, the biggest of `biggest` points: `side` = every job on the lane of its buffer set, the jobs
+// side by side (else the three-stream pipeline: sort | accumulate | tail over three rotating buffer sets); `lanes` = buffer sets in rotation; `phased` =
+// phase-major issue (all sorts, then the accumulations and tails).  The measurements behind the thresholds are with the driver.
+struct zl_msm_batch_form {
+    bool side;
+    size_t lanes;
+    bool phased;
+};
+inline zl_msm_batch_form zl_msm_batch_form_of(size_t count, uint64_t biggest) {
+    zl_msm_batch_form f;
+    f.side = biggest <= ((uint64_t)1 << zl_tune("ZL_TUNE_SIDE_BY_SIDE_LOG", 20));
+    f.lanes = f.side ? std::min<size_t>(count, (size_t)std::min(4, std::max(1, zl_tune("ZL_TUNE_SIDE_LANES", 4)))) : 3;
+    f.phased = f.side && count <= f.lanes && biggest >= ((uint64_t)1 << zl_tune("ZL_TUNE_PHASED_MIN_LOG", 17));
+    return f;
+}
 // the first `count` events of the ctx's pool of one kind (grown on demand; owned by the ctx: zl_ctx_destroy).  The pointer is valid until the next call for
 // the SAME kind that has to grow the pool: callers take it once per pipeline call, under ctx->pipeline_busy
 inline int zl_ctx_events(zl_ctx* ctx, int timing, size_t count, hipEvent_t** out) {
@@ -341,6 +357,7 @@ inline int zl_scratch_get(zl_ctx* ctx, zl_slot slot, size_t bytes, void** out) {
     return ZL_OK;
 }
 
+struct zl_test_msm_plan_s;  // (include/zl_backend_test.h)
 // entry points implemented per translation unit; the MSM file is compiled once per group (suffix = group config)
 #define ZL_DECL_GROUP(G)                                                                                                   \
     int zl_msm_run_##G(zl_ctx* ctx, const zl_bases& b, size_t first, const void* d_scalars, size_t n, uint64_t* out_partial); \
@@ -353,6 +370,7 @@ inline int zl_scratch_get(zl_ctx* ctx, zl_slot slot, size_t bytes, void** out) {
     int zl_bases_generate_##G(zl_ctx* ctx, const uint64_t* k, size_t n, zl_bases* out);                                     \
     int zl_bases_download_##G(zl_ctx* ctx, const zl_bases& b, size_t first, size_t count, uint64_t* out_xy);                \
     int zl_bases_precompute_##G(zl_ctx* ctx, zl_bases& b, int c);                                                           \
+    int zl_msm_plan_report_##G(zl_ctx* ctx, const zl_bases& b, size_t first, size_t n, struct zl_test_msm_plan_s* out);       \
     int zl_msm_multi_run_##G(zl_ctx* ctx, const zl_bases& b, size_t first, const void* d_scalars, size_t n, size_t stride_scalars, size_t count, uint64_t* out_xy, uint8_t* out_inf); \
     int zl_bases_concat_##G(zl_ctx* ctx, const zl_bases* const* parts, const size_t* first, const size_t* n, size_t count, zl_bases* out);
 ZL_DECL_GROUP(BlsG1)

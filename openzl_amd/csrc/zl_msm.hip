@@ -34,6 +34,7 @@
 #include <mutex>
 #include <thread>
 #include <vector>
+#include "../../include/zl_backend_test.h"
 #include "zl_ctx.h"
 #include "zl_pool.h"
 #include "zl_quad.h"
@@ -168,8 +169,9 @@ static int msm_run_jobs_t(zl_ctx* ctx, const MsmSpec* specs, size_t count, uint6
     for (size_t i = 0; i < count; i++) biggest = std::max<uint64_t>(biggest, (uint64_t)specs[i].n);
     // measured (round 3, batches of 6): 2^16 0.69 -> 0.50 ms per MSM, 2^20 3.31 -> 3.10; equal at 2^18 - 2^19; from 2^21 on the three-phase pipeline
     // wins (2^24: 36.3 against 37.3 ms)
-    const bool side = biggest <= ((uint64_t)1 << zl_tune("ZL_TUNE_SIDE_BY_SIDE_LOG", 20));
-    const size_t NS = side ? std::min<size_t>(count, (size_t)std::min(4, std::max(1, zl_tune("ZL_TUNE_SIDE_LANES", 4)))) : 3;
+    const zl_msm_batch_form form = zl_msm_batch_form_of(count, biggest);  // (zl_ctx.h: the one place that reads the three knobs of this choice)
+    const bool side = form.side;
+    const size_t NS = form.lanes;
     for (size_t i = 0; i < count; i++) {
         // (side by side every job computes its own phi image: there is no common stream that would order a borrower behind the owner)
         if ((rc = jobs[i].plan(ctx, *specs[i].bs, specs[i].first, specs[i].d_scalars, specs[i].n, (one_key && !side) ? ZL_SLOT_PHI_ONE_KEY : ZL_MSM_SET[i % NS].phi))) return rc;
@@ -293,7 +295,7 @@ static int msm_run_jobs_t(zl_ctx* ctx, const MsmSpec* specs, size_t count, uint6
     // removed: the G2 accumulation held back until those sorts had finished (the sort kernels need 104 - 160 registers per SIMD and stall beside the
     // 416-register G2 wave): the a accumulation then starts 3 ms earlier, the G2 accumulation 3 ms later, and the proof takes the same 18.1 ms --
     // the proof is bound by the sum of its group additions, whatever their order.
-    const bool phased = side && count <= NS && biggest >= ((uint64_t)1 << zl_tune("ZL_TUNE_PHASED_MIN_LOG", 17));
+    const bool phased = form.phased;
     // issued[i]: 0 not yet, 1 issued, < 0 failed (-code).  (Round 3 also built one persistent issuing thread per lane: all four jobs of a small proof then reach the
     // device within 0.15 ms, but finish together and later than the staggered jobs of a single issuing thread -- median 1.40 against 1.16 ms per proof; removed in round 6.)
     std::unique_ptr<std::atomic<int>[]> issued(new std::atomic<int>[count]);
@@ -496,6 +498,28 @@ static int bases_precompute_t(zl_ctx* ctx, zl_bases& bs, int c) {
     return ZL_OK;
 }
 int ZL_GNAME(zl_bases_precompute)(zl_ctx* ctx, zl_bases& b, int c) { return bases_precompute_t<ZL_G>(ctx, b, c); }
+
+// TEST HOOK (zl_test_msm_plan, zl_testhooks.hip): the plan a single call over this range would run on, and the launch forms it implies.  Plans only: no
+// launch, no device allocation.
+template <class G>
+static int msm_plan_report_t(zl_ctx* ctx, const zl_bases& bs, size_t first, size_t n, zl_test_msm_plan_t* o) {
+    MsmJob<G> job;
+    int rc;
+    if ((rc = job.plan(ctx, bs, first, nullptr, n, ZL_SLOT_PHI_ONE_KEY))) return rc;
+    *o = zl_test_msm_plan_t{};
+    o->c = job.c; o->W = job.W; o->SETS = (int32_t)job.SETS; o->NB = (int32_t)job.NB; o->sc_bits = job.sc_bits;
+    o->glv = job.glv; o->endo_k = job.endo_k; o->wide = job.wide; o->pre = job.pre;
+    o->chunk = (int32_t)job.ZL_CHUNK; o->nchunks = (int32_t)job.nchunks; o->big_span = (int32_t)job.big_span;
+    o->red_g0 = (int32_t)job.red_g0; o->red_levels = (int32_t)job.red_levels; o->spread_t = job.spread_t;
+    o->nslices = (int32_t)job.lay.nslices; o->per_slice = (int32_t)job.lay.per_slice; o->fsl = (int32_t)job.lay.fsl; o->Gn = (int32_t)job.Gn;
+    o->sort_lds = job.sort_is_lds();
+    if (job.sort_is_lds()) { o->lds_prefix_small = job.lds_prefix_small(); o->lds_ranges = (int32_t)job.lds_ranges(); }
+    if (job.wide) { o->fine_cap = (int32_t)job.fine_cap(); o->fine_threads = (int32_t)job.fine_threads(); }
+    o->acc_quad = job.acc_quad(); o->tail_quad_max = (int32_t)std::min<uint32_t>(job.tail_quad_max(), 0x7fffffffu); o->by_cuts = job.by_cuts();
+    o->may_big = job.may_big(); o->may_giant = job.may_giant();
+    return ZL_OK;
+}
+int ZL_GNAME(zl_msm_plan_report)(zl_ctx* ctx, const zl_bases& b, size_t first, size_t n, zl_test_msm_plan_t* out) { return msm_plan_report_t<ZL_G>(ctx, b, first, n, out); }
 
 int ZL_GNAME(zl_msm_run_batch)(zl_ctx* ctx, const zl_bases& b, size_t first, const void* const* d_scalars, size_t n, size_t count, uint64_t* out_partials) {
     std::vector<MsmSpec> specs(count);

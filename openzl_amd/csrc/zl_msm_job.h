@@ -313,6 +313,34 @@ struct MsmJob {
         set_host_buffer(hw_own.data());
         return ZL_OK;
     }
+    // ---- the launch forms that follow from the plan: sort(), accumulate() and tail() below ask these members, and so does the plan report of the tests
+    // (zl_msm_plan_report, zl_msm.hip), so that a test asserts the branch the launch code takes and not a copy of its arithmetic
+    bool sort_is_lds() const { return !wide && c <= 16; }  // else the three-level sort (wide) or, beyond 255 sort groups, global atomics
+    bool lds_prefix_small() const { return NB <= 14336 && lay.nslices <= 64; }  // (14 336 buckets: 59.6 KB of LDS for the totals beside the 4 KB of the scan)
+    // LDS sort, scatter: one block per (bucket range, window); ranges sized so that W * ranges ~ 256..512 blocks
+    uint32_t lds_ranges() const {
+        uint32_t ranges = 1;
+        while (ranges * W < 256 && (H / (ranges * 2)) >= 64) ranges *= 2;
+        return (uint32_t)std::max(1, zl_tune("ZL_TUNE_RANGES", (int)ranges));
+    }
+    // wide sort, level 3: staged entries per block: at most 144 KiB + 1 KiB of cursors (1 block per CU); sub-groups average n*W/SG entries, so many small
+    // sub-groups (plain wide windows) get a smaller stage and two blocks per CU.  A sub-group above the cap goes to k_msm_fine_sort_big's queue.
+    uint32_t fine_cap() const {
+        const uint32_t SG = Gn * 128;
+        const uint32_t cap = (uint32_t)std::min<uint64_t>(36 * 1024, std::max<uint64_t>(4096, (maxE / SG) * 22 / 10));
+        return (uint32_t)std::max(1024, zl_tune("ZL_TUNE_FS_CAP", (int)cap));
+    }
+    uint32_t fine_threads() const { return (uint32_t)zl_tune("ZL_TUNE_FS", 1024); }
+    // four lanes per chunk (Fq2 groups: eight) while that is at most ~1.5 waves per SIMD (round 6: 49 152 -> 24 576; at three waves per SIMD the one-lane kernel
+    // is faster: 94 against 131 us at 2^14, profiles/r06_small_knobs2.log)
+    bool acc_quad() const { return nchunks <= (uint64_t)zl_tune("ZL_TUNE_QUAD_ACC_CHUNKS", 24576); }
+    // four lanes per group operation (zl_quad.h; Fq2 groups: eight, zl_fq2pair.h) in every tail launch of at most this many lanes, one lane (Fq2: a lane pair) beyond
+    uint32_t tail_quad_max() const { return (uint32_t)zl_tune("ZL_TUNE_QUAD_LANES", 65536); }
+    bool by_cuts() const { return NB > tail_quad_max() && nchunks > 1; }  // one lane (pair) per chunk boundary: every surviving lane folds one bucket
+    // a bucket cut into more than big_span (ZL_GIANT_SPAN) chunks needs that many chunks to exist: small jobs skip the launches (three of the ~22 of a small MSM's chain)
+    bool may_big() const { return nchunks > big_span; }
+    bool may_giant() const { return nchunks > (uint32_t)ZL_GIANT_SPAN; }
+
     // buffer set 0..3 (ZL_MSM_SET, zl_ctx.h).  own_sort: the job's sort runs beside the other sets' sorts, in the set's own temporaries; otherwise in
     // ZL_SLOT_SORT_A / _B, which the jobs of a call share: their sorts run in order on one stream.  Callers bind every job before anything is in
     // flight (a growing zl_scratch_get frees the old block), and again once every slot has reached its largest user.
@@ -434,7 +462,7 @@ struct MsmJob {
         (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&k_msm_hist_lds), hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024);
         (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&k_msm_scatter_range), hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024);
         if (wide) sort_wide(st, sc_eff, inf_eff, bad_eff, glv_i);
-        else if (c <= 16) sort_lds(st, sc_eff, inf_eff, bad_eff, nblk, glv_i);
+        else if (sort_is_lds()) sort_lds(st, sc_eff, inf_eff, bad_eff, nblk, glv_i);
         else sort_atomics(st, nblk);
         ZL_HIP(ctx, hipGetLastError());
         return ZL_OK;
@@ -480,12 +508,9 @@ struct MsmJob {
         hipLaunchKernelGGL(k_scan_block_sums, dim3(scan_blocks), dim3(SCAN_BLOCK), 0, st, d_counts, NB, d_block_sums);
         hipLaunchKernelGGL(k_scan_top, dim3(1), dim3(1024), 0, st, d_block_sums, scan_blocks, d_offsets + NB, (const uint32_t*)d_bad_scalar);
         hipLaunchKernelGGL(k_scan_apply, dim3(scan_blocks), dim3(SCAN_BLOCK), 0, st, d_counts, NB, d_block_sums, d_offsets, d_cursor);
-        // staged entries per block: at most 144 KiB + 1 KiB of cursors (1 block per CU); sub-groups average n*W/SG entries, so many small
-        // sub-groups (plain wide windows) get a smaller stage and two blocks per CU
-        uint32_t cap = (uint32_t)std::min<uint64_t>(36 * 1024, std::max<uint64_t>(4096, (maxE / SG) * 22 / 10));
-        cap = (uint32_t)std::max(1024, zl_tune("ZL_TUNE_FS_CAP", (int)cap));
+        const uint32_t cap = fine_cap();
         (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&k_msm_fine_sort), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        hipLaunchKernelGGL(k_msm_fine_sort, dim3(SG), dim3(zl_tune("ZL_TUNE_FS", 1024)), (size_t)(256 + cap) * 4, st, d_lo2, d_idx2, d_off2, SG, fsl, d_off2 + P2, d_offsets, cap,
+        hipLaunchKernelGGL(k_msm_fine_sort, dim3(SG), dim3(fine_threads()), (size_t)(256 + cap) * 4, st, d_lo2, d_idx2, d_off2, SG, fsl, d_off2 + P2, d_offsets, cap,
                            d_entries, d_bigsg_head, d_bigsg_items);
         (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&k_msm_fine_sort_big), hipFuncAttributeMaxDynamicSharedMemorySize, ZL_BT * 4);
         hipLaunchKernelGGL(k_msm_fine_sort_big, dim3(512), dim3(1024), (size_t)ZL_BT * 4, st, d_lo2, d_idx2, d_off2, SG, fsl, d_off2 + P2, d_bigsg_head,
@@ -498,7 +523,7 @@ struct MsmJob {
         uint32_t* d_slice_counts = (uint32_t*)(d_sort_a + lay.slice_counts);
         hipLaunchKernelGGL(k_msm_recode, dim3(nblk), dim3(256), 0, st, sc_eff, (uint32_t)n, c, W, spread_t, glv_i, d_digits, d_ones_list, d_ones_count, inf_eff, sc_bits, bad_eff);
         hipLaunchKernelGGL(k_msm_hist_lds, dim3(nslices, W), dim3(1024), (size_t)H * 4, st, d_digits, (uint32_t)n, H, per_slice, NB, d_slice_counts);
-        if (NB <= 14336 && nslices <= 64) {  // (14 336 buckets: 59.6 KB of LDS for the totals beside the 4 KB of the scan)
+        if (lds_prefix_small()) {
             hipLaunchKernelGGL(k_msm_prefix_small, dim3(1), dim3(1024), ((size_t)NB + NB / 16 + 16) * 4, st, d_slice_counts, NB, nslices, d_offsets, d_cursor, (const uint32_t*)d_bad_scalar);
         } else {
         hipLaunchKernelGGL(k_msm_slice_prefix, dim3((NB + 255) / 256), dim3(256), 0, st, d_slice_counts, NB, nslices, d_counts);
@@ -506,10 +531,7 @@ struct MsmJob {
         hipLaunchKernelGGL(k_scan_top, dim3(1), dim3(1024), 0, st, d_block_sums, scan_blocks, d_offsets + NB, (const uint32_t*)d_bad_scalar);
         hipLaunchKernelGGL(k_scan_apply, dim3(scan_blocks), dim3(SCAN_BLOCK), 0, st, d_counts, NB, d_block_sums, d_offsets, d_cursor);
         }
-        // scatter: one block per (bucket range, window); ranges sized so that W * ranges ~ 256..512 blocks
-        uint32_t ranges = 1;
-        while (ranges * W < 256 && (H / (ranges * 2)) >= 64) ranges *= 2;
-        ranges = (uint32_t)std::max(1, zl_tune("ZL_TUNE_RANGES", (int)ranges));
+        const uint32_t ranges = lds_ranges();
         const uint32_t RB = (H + ranges - 1) / ranges;
         // (the digit row of a window can be walked by `parts` blocks, slice-aligned: measured 1 = 2 = 4 = 8 at 2^18 .. 2^21 -- the kernel is bound by
         // its 4-byte scattered stores, 16.8 M of them in 0.19 ms at 2^20, not by the length of the row, the load latency or the LDS atomics)
@@ -529,9 +551,7 @@ struct MsmJob {
     static constexpr bool pair_ok() { return G::COORDS == 2 && !std::is_void<typename PairBase<F>::type>::value; }  // an Fq2 group on 28-bit limbs: the lane-pair kernels exist
     int accumulate(zl_ctx* ctx, hipStream_t st) {
         static_assert(G::COORDS == 1 || pair_ok(), "every Fq2 group runs on 28-bit limbs: its MSM kernels are the lane-pair ones");
-        // four lanes per chunk (Fq2 groups: eight) while that is at most ~1.5 waves per SIMD (round 6: 49 152 -> 24 576; at three waves per SIMD the one-lane kernel
-        // is faster: 94 against 131 us at 2^14, profiles/r06_small_knobs2.log)
-        const bool quad = nchunks <= (uint64_t)zl_tune("ZL_TUNE_QUAD_ACC_CHUNKS", 24576);
+        const bool quad = acc_quad();
         if constexpr (pair_ok()) {  // Fq2 groups (zl_fq2pair.h): eight lanes per chunk, else two lanes per chunk at two waves per SIMD
             if (quad)
                 hipLaunchKernelGGL((k_msm_accumulate_pair<G, true>), dim3((nchunks + 7) / 8), dim3(64), 0, st, d_entries, d_offsets, NB, d_bases, d_buckets, d_partials, ZL_CHUNK,
@@ -559,9 +579,9 @@ struct MsmJob {
         return ZL_OK;
     }
     int tail(zl_ctx* ctx, hipStream_t st) {
-        // four lanes per group operation (zl_quad.h; Fq2 groups: eight, zl_fq2pair.h) in every tail launch that does not fill the machine, one lane (Fq2: a lane pair) in those that do
-        const uint32_t quad_max = (uint32_t)zl_tune("ZL_TUNE_QUAD_LANES", 65536);
-        const bool by_cuts = NB > quad_max && nchunks > 1;  // one lane (pair) per chunk boundary: every surviving lane folds one bucket
+        // four lanes per group operation in every tail launch that does not fill the machine, one lane (Fq2: a lane pair) in those that do
+        const uint32_t quad_max = tail_quad_max();
+        const bool by_cuts = this->by_cuts();
         if (by_cuts) hipLaunchKernelGGL((k_msm_fill_empty<G>), dim3((NB + 255) / 256), dim3(256), 0, st, d_offsets, NB, d_buckets);
         if constexpr (pair_ok()) {
             if (by_cuts)
@@ -578,8 +598,7 @@ struct MsmJob {
             else
                 hipLaunchKernelGGL((k_msm_merge<G, true>), dim3((4 * NB + 63) / 64), dim3(64), 0, st, d_offsets, NB, d_buckets, d_partials, d_big_list, d_big_count, d_giant_list, d_giant_count, ZL_CHUNK, big_span);
         }
-        // a bucket cut into more than big_span (ZL_GIANT_SPAN) chunks needs that many chunks to exist: small jobs skip the launches (three of the ~22 of a small MSM's chain)
-        const bool may_big = nchunks > big_span, may_giant = nchunks > (uint32_t)ZL_GIANT_SPAN;
+        const bool may_big = this->may_big(), may_giant = this->may_giant();
         if constexpr (pair_ok()) {  // Fq2 groups: the block-tree kernels of the heavy buckets on lane pairs
             if (may_big) hipLaunchKernelGGL((k_msm_merge_big_pair<G>), dim3(std::min<uint32_t>(max_big, 1024)), dim3(2 * TreeLanes<G>::N), TreeLanes<G>::N * sizeof(X), st, d_offsets, d_buckets,
                                d_partials, d_big_list, d_big_count, ZL_CHUNK);

@@ -878,6 +878,23 @@ int zl_test_endo_split(zl_ctx* ctx, zl_curve_t curve, zl_group_t group, const ui
     return zl_test_endo_split_inf(ctx, curve, group, scalars, nullptr, n, out_records, endo_k, part_bits);
 }
 
+// the MSM planner's choices (zl_msm.hip holds the per-group instances of MsmJob)
+int zl_test_msm_plan(zl_ctx* ctx, uint64_t bases, size_t first, size_t n, zl_test_msm_plan_t* out) {
+    if (!ctx || !out || n == 0) return ZL_EINVAL;
+    const zl_bases* bp = zl_find_bases(ctx, bases);
+    if (!bp) return ZL_EHANDLE;
+    if (first > bp->n || n > bp->n - first) return ZL_EINVAL;
+    return ZL_DISPATCH(bp->curve, bp->group, zl_msm_plan_report, ctx, *bp, first, n, out);
+}
+int zl_test_msm_batch_form(size_t count, uint64_t biggest, int* side, int* lanes, int* phased) {
+    if (!side || !lanes || !phased || count < 2) return ZL_EINVAL;
+    const zl_msm_batch_form f = zl_msm_batch_form_of(count, biggest);
+    *side = f.side;
+    *lanes = (int)f.lanes;
+    *phased = f.phased;
+    return ZL_OK;
+}
+
 // the decoders of zl_decode.h: on the host, and their Fq2 square root alone on either side (zl_decode_dev.hip holds the per-curve instances)
 int zl_test_decode_points_host(zl_curve_t curve, zl_group_t group, const uint8_t* in, size_t count, uint64_t* out_xy, uint8_t* out_inf, int32_t* status) {
     using namespace openzl;

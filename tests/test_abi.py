@@ -50,6 +50,24 @@ def test_library_exports_every_declared_test_hook():
     assert L.zl_test_point_form_op(None, 1, 1, 5, 2, None, 0, None) == -1
 
 
+def test_msm_batch_form_hook_defaults(monkeypatch):
+    """zl_test_msm_batch_form (host only) reports the batch driver's own choice: side-by-side lanes up to 2^20 points, phase-major from 2^17 on when every job has
+    a lane, the three-stream pipeline above; the plan hook needs a ctx"""
+    from openzl_amd.backend import BackendError, hook_msm_batch_form
+
+    for k in ("ZL_TUNE_SIDE_BY_SIDE_LOG", "ZL_TUNE_SIDE_LANES", "ZL_TUNE_PHASED_MIN_LOG"):
+        monkeypatch.delenv(k, raising=False)
+    assert hook_msm_batch_form(5, 6000) == {"side": True, "lanes": 4, "phased": False}
+    assert hook_msm_batch_form(3, 1 << 20) == {"side": True, "lanes": 3, "phased": True}
+    assert hook_msm_batch_form(5, 1 << 20) == {"side": True, "lanes": 4, "phased": False}
+    assert hook_msm_batch_form(6, (1 << 20) + 1) == {"side": False, "lanes": 3, "phased": False}
+    monkeypatch.setenv("ZL_TUNE_SIDE_BY_SIDE_LOG", "0")
+    assert hook_msm_batch_form(2, 2) == {"side": False, "lanes": 3, "phased": False}
+    with pytest.raises(BackendError):
+        hook_msm_batch_form(1, 6000)
+    assert load_library().zl_test_msm_plan(None, 0, 0, 1, None) == -1
+
+
 def test_strerror_and_argument_checks():
     L = load_library()
     assert L.zl_strerror(0) == b"ok"

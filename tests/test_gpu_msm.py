@@ -397,8 +397,9 @@ def test_config4_eight_shards_of_2_23(backend):
 @pytest.mark.parametrize("curve", CURVES, ids=lambda c: c.name)
 @pytest.mark.parametrize("table", [False, True], ids=["plain", "table"])
 def test_msm_pipelined_batch_equals_single_calls(backend, curve, table):
-    """zl_msm_batch_partial_dev (three-stream pipeline over three rotating buffer sets) against one zl_msm_partial_dev per scalar vector, and the
-    oracle for the first one; 5 MSMs so that buffer sets are reused."""
+    """zl_msm_batch_partial_dev against one zl_msm_partial_dev per scalar vector, and the oracle for the first one.  At n = 6000 the batch driver runs the jobs SIDE BY
+    SIDE (jobs of at most 2^20 points: every job on the lane of its buffer set, four lanes), not on the three-stream pipeline; 5 MSMs so that the first lane's buffer
+    set is reused.  The three-stream pipeline at small n: test_gpu_msm_plan_geometry.py::test_pipeline_small_batches."""
     import torch
 
     n = 6000
