@@ -65,6 +65,25 @@ int zl_groth16_prove_batch_dev(zl_ctx* ctx, const zl_g16_pk* pk, uint64_t r1cs_h
  * other error codes and their order are those of zl_groth16_prove_batch. */
 int zl_groth16_prove_poseidon_chains(zl_ctx* ctx, const zl_g16_pk* pk, uint64_t r1cs_handle, uint32_t k, const uint64_t* x0, const uint64_t* x1, const uint64_t* r,
                                      const uint64_t* s, size_t count, zl_g16_proof* proofs, uint64_t* public_out);
+/* Merkle memberships in, proofs out: zl_groth16_prove_poseidon_chains with another producer.  proofs[j] = what zl_groth16_prove_resident returns for the
+ * assignment of zl_circuit_poseidon_merkle (zl_poseidon_merkle_assignments below) with r[j], s[j], byte for byte.
+ *   _paths:   leaves (count x 4 u64), indices (count u64) and paths (count x depth x 4 u64) in HOST memory; roots_out (may be NULL) receives the root of every
+ *             fold, the public input of proof j.  An index >= 2^depth is ZL_EINVAL before any work.
+ *   _members: a node array in DEVICE memory (zl_poseidon_merkle_build_dev: n leaves, `depth` levels) and HOST indices: proof j shows that leaf indices[j] is in
+ *             the tree.  Nothing but the indices and the blinding scalars goes up; root_out (may be NULL) receives the one root, every proof's public input.
+ *             n > 2^depth or an index >= n is ZL_EINVAL before any work.
+ * On the device path the trace kernel writes every chunk's rows straight into the chunk's block; off it, rows are produced at most 64 MiB at a time for the
+ * loop over the resident prover (_members: written by the device and downloaded).  The dispatch bounds are zl_groth16_prove_batch's and are not moved: depth <= 8
+ * has a domain of at most 2^11, so from 64 proofs on it stays on the device by default; deeper paths loop the resident prover -- there the gain is that
+ * synthesis and the assignments' way over the bus are gone, not the batched MSMs.  The resident circuit must have the SHAPE of a depth-d membership circuit
+ * (n_instance, n_witness, n_constraints) == (2, 1 + 238 d, 237 d + 1), else ZL_EINVAL; what its matrices hold cannot be checked.  No chain shape
+ * (2, 2 + 234 k, 234 k + 1) equals a membership shape for integers k, d >= 1: n_witness - n_constraints is 1 for a chain and d for a membership, so d = 1, and
+ * then 234 k = 237 has no solution -- keys of a chain are refused here and keys of a membership by zl_groth16_prove_poseidon_chains.  A depth outside 1..40 or
+ * an input >= r: ZL_EINVAL; the other error codes and their order are those of zl_groth16_prove_batch. */
+int zl_groth16_prove_merkle_paths(zl_ctx* ctx, const zl_g16_pk* pk, uint64_t r1cs_handle, unsigned depth, const uint64_t* leaves, const uint64_t* indices,
+                                  const uint64_t* paths, const uint64_t* r, const uint64_t* s, size_t count, zl_g16_proof* proofs, uint64_t* roots_out);
+int zl_groth16_prove_merkle_members(zl_ctx* ctx, const zl_g16_pk* pk, uint64_t r1cs_handle, const void* d_nodes, size_t n, unsigned depth, const uint64_t* indices,
+                                    const uint64_t* r, const uint64_t* s, size_t count, zl_g16_proof* proofs, uint64_t* root_out);
 int zl_partials_sum(zl_curve_t curve, zl_group_t group, const uint64_t* partials, size_t count, uint64_t* out_xy, uint8_t* out_inf);
 /* wrap a canonical affine point (all-zero = infinity) as a partial, e.g. to fold an extra term into zl_partials_sum */
 int zl_partial_from_affine(zl_curve_t curve, zl_group_t group, const uint64_t* xy, uint64_t* out_partial);
@@ -192,6 +211,33 @@ int zl_poseidon_merkle_paths(const uint64_t* nodes, size_t n, unsigned depth, co
  * left otherwise (Parity::join); one lane per path, `depth` dependent hashes each.  An index >= 2^depth is ZL_EINVAL.  Host pointers. */
 int zl_poseidon_merkle_roots_from_paths(zl_ctx* ctx, zl_curve_t curve, const uint64_t* leaves, const uint64_t* indices, const uint64_t* paths, unsigned depth,
                                         size_t count, uint64_t* roots);
+/* ---- Merkle membership in circuit: the reference's PathVar::verify_digest with the digest itself as the leaf (openzl-crypto/src/merkle_tree/path.rs:942-1126),
+ * folded with ConditionalSwap = two conditionally_selects per level (plugins/arkworks/src/constraint/mod.rs:354-390) over Boolean witnesses (mod.rs:242-258).
+ * Public input: the root.  Witnesses, LEVEL-major (the reference allocates all bits, then all digests, up front; level-major lets a device lane write its row
+ * front to back): the leaf, then for level j = 0..depth-1 the sibling path[j], the Boolean b_j = bit j of index (row (1 - b) b = 0), left = select(b, sib, cur),
+ * right = select(b, cur, sib) (row b (t - f) = out - f each), and the 234 S-box witnesses of cur = H(left, right); the last row is cur = root.
+ * Shape (n_instance, n_witness, n_constraints) = (2, 1 + 238 depth, 237 depth + 1).  depth outside 1..40, index >= 2^depth, a null pointer or an unknown curve:
+ * ZL_EINVAL.  _witness: the same circuit run by a witness-only compiler (see zl_circuit_poseidon_chain_witness); Boolean and select always allocate, so the two
+ * compilers' assignments are equal word for word. */
+int zl_circuit_poseidon_merkle(zl_curve_t curve, unsigned depth, const uint64_t* leaf, uint64_t index, const uint64_t* path, zl_circuit** out);
+int zl_circuit_poseidon_merkle_witness(zl_curve_t curve, unsigned depth, const uint64_t* leaf, uint64_t index, const uint64_t* path, zl_circuit** out);
+/* The complete ASSIGNMENT of zl_circuit_poseidon_merkle(curve, depth, leaves[i], indices[i], paths[i]) per membership, one device lane each (k_pos_merkle_trace):
+ *   [0] = 1   [1] = root   [2] = leaf   level j at 3 + 238 j: [+0] sibling  [+1] b_j (0 or 1)  [+2] left  [+3] right  [+4 .. +238) the 234 records of H(left, right)
+ * zl_poseidon_merkle_assignment_elems(depth) = 3 + 238 depth elements (0 for a depth outside 1..40).  indices are HOST memory in every form, as in
+ * zl_poseidon_merkle_paths_dev; an index >= 2^depth (>= n in the member form) is ZL_EINVAL before any work.  The host-pointer form writes count dense rows and
+ * follows the common rules of the batched Poseidon entry points (ctx == NULL or a count below ZL_TUNE_POSEIDON_DEV_MIN: the host mirror over the host pool;
+ * staged in chunks of ZL_TUNE_POSEIDON_CHUNK under the 256 MiB budget).  The _dev forms never take the host path (ctx == NULL is ZL_EINVAL): row i starts at
+ * d_out + i * stride_elems elements, stride_elems >= the row length, elements behind the row are not written, d_out must be 16-byte aligned and must not overlap
+ * the inputs.  _assignments_dev reads leaves (count elements) and paths (count x depth) from device memory; _member_assignments_dev reads both out of a node array
+ * of zl_poseidon_merkle_build_dev's layout (n leaves, `depth` levels): the leaf is node (0, index), the sibling at level k node (k, (index >> k) ^ 1), zero when
+ * the tree has no such node -- so [1] of every row is the tree's root. */
+size_t zl_poseidon_merkle_assignment_elems(unsigned depth);
+int zl_poseidon_merkle_assignments(zl_ctx* ctx, zl_curve_t curve, const uint64_t* leaves, const uint64_t* indices, const uint64_t* paths, unsigned depth, size_t count,
+                                   uint64_t* out);
+int zl_poseidon_merkle_assignments_dev(zl_ctx* ctx, zl_curve_t curve, const void* d_leaves, const uint64_t* indices, const void* d_paths, unsigned depth, size_t count,
+                                       void* d_out, size_t stride_elems);
+int zl_poseidon_merkle_member_assignments_dev(zl_ctx* ctx, zl_curve_t curve, const void* d_nodes, size_t n, unsigned depth, const uint64_t* indices, size_t count,
+                                              void* d_out, size_t stride_elems);
 /* Groth16::compile with rng = SplitMix64(seed): trapdoor setup, proving key generated on the device */
 int zl_groth16_compile(zl_ctx* ctx, const zl_circuit* c, uint64_t seed, zl_g16_keys** out);
 int zl_groth16_keys_trapdoor(const zl_g16_keys* k, uint64_t* out20); /* alpha, beta, gamma, delta, tau (canonical) */

@@ -40,6 +40,8 @@ ABI_SYMBOLS = [
     "zl_poseidon_merkle_roots_from_paths",
     "zl_poseidon_chain_assignment_elems", "zl_poseidon_chain_assignments_dev", "zl_poseidon_chain_assignments", "zl_groth16_prove_batch_dev",
     "zl_groth16_prove_poseidon_chains",
+    "zl_circuit_poseidon_merkle", "zl_circuit_poseidon_merkle_witness", "zl_poseidon_merkle_assignment_elems", "zl_poseidon_merkle_assignments",
+    "zl_poseidon_merkle_assignments_dev", "zl_poseidon_merkle_member_assignments_dev", "zl_groth16_prove_merkle_paths", "zl_groth16_prove_merkle_members",
 ]
 
 
@@ -149,6 +151,15 @@ def load_library(path: Optional[str] = None):
     L.zl_poseidon_merkle_paths_dev.argtypes = [vp, C.c_int, vp, C.c_size_t, C.c_uint, u64p, C.c_size_t, u64p]
     L.zl_poseidon_merkle_paths.argtypes = [u64p, C.c_size_t, C.c_uint, u64p, C.c_size_t, u64p]
     L.zl_poseidon_merkle_roots_from_paths.argtypes = [vp, C.c_int, u64p, u64p, u64p, C.c_uint, C.c_size_t, u64p]
+    L.zl_circuit_poseidon_merkle.argtypes = [C.c_int, C.c_uint, u64p, C.c_uint64, u64p, C.POINTER(vp)]
+    L.zl_circuit_poseidon_merkle_witness.argtypes = L.zl_circuit_poseidon_merkle.argtypes
+    L.zl_poseidon_merkle_assignment_elems.argtypes = [C.c_uint]
+    L.zl_poseidon_merkle_assignment_elems.restype = C.c_size_t
+    L.zl_poseidon_merkle_assignments.argtypes = [vp, C.c_int, u64p, u64p, u64p, C.c_uint, C.c_size_t, u64p]
+    L.zl_poseidon_merkle_assignments_dev.argtypes = [vp, C.c_int, vp, u64p, vp, C.c_uint, C.c_size_t, vp, C.c_size_t]
+    L.zl_poseidon_merkle_member_assignments_dev.argtypes = [vp, C.c_int, vp, C.c_size_t, C.c_uint, u64p, C.c_size_t, vp, C.c_size_t]
+    L.zl_groth16_prove_merkle_paths.argtypes = [vp, C.POINTER(G16PkC), C.c_uint64, C.c_uint, u64p, u64p, u64p, u64p, u64p, C.c_size_t, C.POINTER(G16ProofC), u64p]
+    L.zl_groth16_prove_merkle_members.argtypes = [vp, C.POINTER(G16PkC), C.c_uint64, vp, C.c_size_t, C.c_uint, u64p, u64p, u64p, C.c_size_t, C.POINTER(G16ProofC), u64p]
     L.zl_groth16_compile.argtypes = [vp, vp, C.c_uint64, C.POINTER(vp)]
     L.zl_groth16_keys_free.argtypes = [vp]
     L.zl_groth16_keys_free.restype = None
@@ -554,6 +565,27 @@ class Backend:
     def poseidon_merkle_roots_from_paths(self, curve: int, leaves: np.ndarray, indices, paths: np.ndarray, depth: int) -> np.ndarray:
         return _poseidon_roots_from_paths(self.L, self._ctx, curve, leaves, indices, paths, depth)
 
+    def poseidon_merkle_assignments(self, curve: int, leaves, indices, paths, depth: int) -> np.ndarray:
+        """zl_poseidon_merkle_assignments: (count, 3 + 238 depth, 4) canonical words, row i the complete assignment of
+        Circuit.merkle(curve, depth, leaves[i], indices[i], paths[i])"""
+        return _poseidon_merkle_assignments(self.L, self._ctx, curve, leaves, indices, paths, depth)
+
+    def poseidon_merkle_assignments_dev(self, curve: int, d_leaves: int, indices, d_paths: int, depth: int, d_out: int, stride_elems: Optional[int] = None):
+        """zl_poseidon_merkle_assignments_dev: leaves and paths at device addresses, indices in host memory -> row i at d_out + i * stride_elems elements
+        (default: the row length, poseidon_merkle_assignment_elems(depth)); finished on return"""
+        idx = np.ascontiguousarray(indices, dtype=np.uint64).reshape(-1)
+        stride = self.L.zl_poseidon_merkle_assignment_elems(depth) if stride_elems is None else stride_elems
+        self._check(self.L.zl_poseidon_merkle_assignments_dev(self._ctx, curve, C.c_void_p(d_leaves), _ptr_or_none(idx), C.c_void_p(d_paths), depth, idx.size,
+                                                              C.c_void_p(d_out), stride), "zl_poseidon_merkle_assignments_dev")
+
+    def poseidon_merkle_member_assignments_dev(self, curve: int, d_nodes: int, n: int, depth: int, indices, d_out: int, stride_elems: Optional[int] = None):
+        """zl_poseidon_merkle_member_assignments_dev: the memberships of the leaves `indices` (host memory) of the tree at the device address d_nodes
+        (poseidon_merkle_build_dev's node array) -> rows as poseidon_merkle_assignments_dev"""
+        idx = np.ascontiguousarray(indices, dtype=np.uint64).reshape(-1)
+        stride = self.L.zl_poseidon_merkle_assignment_elems(depth) if stride_elems is None else stride_elems
+        self._check(self.L.zl_poseidon_merkle_member_assignments_dev(self._ctx, curve, C.c_void_p(d_nodes), n, depth, _ptr_or_none(idx), idx.size, C.c_void_p(d_out),
+                                                                     stride), "zl_poseidon_merkle_member_assignments_dev")
+
     # ---- Groth16 ----------------------------------------------------------------------------------------------
     def groth16_prove(self, curve: int, pk: dict, r1cs: dict, assignment: np.ndarray, r: np.ndarray, s: np.ndarray):
         """pk: {'a_query','b_g1_query','h_query','l_query','b_g2_query': handles, 'alpha_g1','beta_g1','delta_g1','beta_g2',
@@ -629,6 +661,41 @@ class Backend:
         assignments are made on the device and never leave it"""
         pkc, keep_pk = _pk_struct(curve, pk)
         return self._prove_chains(pkc, curve, r1cs_handle, k, x0, x1, r, s)
+
+    def _prove_merkle_paths(self, pkc, curve: int, r1cs_handle: int, depth: int, leaves, indices, paths, r: np.ndarray, s: np.ndarray):
+        lv = _elems(leaves, 1)
+        idx = np.ascontiguousarray(indices, dtype=np.uint64).reshape(-1)
+        pa = np.ascontiguousarray(np.asarray(paths, dtype=np.uint64).reshape(-1, max(1, depth), 4))
+        count = idx.size
+        assert lv.shape[0] == count and pa.shape[0] == count
+        r, s = np.ascontiguousarray(r, dtype=np.uint64).reshape(count, 4), np.ascontiguousarray(s, dtype=np.uint64).reshape(count, 4)
+        out = (G16ProofC * max(1, count))()
+        roots = np.zeros((count, 4), dtype=np.uint64)
+        self._check(self.L.zl_groth16_prove_merkle_paths(self._ctx, C.byref(pkc), r1cs_handle, depth, _ptr_or_none(lv), _ptr_or_none(idx), _ptr_or_none(pa),
+                                                         _ptr_or_none(r), _ptr_or_none(s), count, out, _ptr_or_none(roots)), "zl_groth16_prove_merkle_paths")
+        return [_proof_tuple(curve, p) for p in out[:count]], roots
+
+    def groth16_prove_merkle_paths(self, curve: int, pk: dict, r1cs_handle: int, depth: int, leaves, indices, paths, r: np.ndarray, s: np.ndarray):
+        """zl_groth16_prove_merkle_paths: leaves (count, 4), indices (count,), paths (count, depth, 4) and blinding scalars -> (`count` proofs, the roots
+        (count, 4): each proof's public input); the assignments are made on the device and never leave it"""
+        pkc, keep_pk = _pk_struct(curve, pk)
+        return self._prove_merkle_paths(pkc, curve, r1cs_handle, depth, leaves, indices, paths, r, s)
+
+    def _prove_merkle_members(self, pkc, curve: int, r1cs_handle: int, d_nodes: int, n: int, depth: int, indices, r: np.ndarray, s: np.ndarray):
+        idx = np.ascontiguousarray(indices, dtype=np.uint64).reshape(-1)
+        count = idx.size
+        r, s = np.ascontiguousarray(r, dtype=np.uint64).reshape(count, 4), np.ascontiguousarray(s, dtype=np.uint64).reshape(count, 4)
+        out = (G16ProofC * max(1, count))()
+        root = np.zeros(4, dtype=np.uint64)
+        self._check(self.L.zl_groth16_prove_merkle_members(self._ctx, C.byref(pkc), r1cs_handle, C.c_void_p(d_nodes), n, depth, _ptr_or_none(idx), _ptr_or_none(r),
+                                                           _ptr_or_none(s), count, out, _p64(root)), "zl_groth16_prove_merkle_members")
+        return [_proof_tuple(curve, p) for p in out[:count]], root
+
+    def groth16_prove_merkle_members(self, curve: int, pk: dict, r1cs_handle: int, d_nodes: int, n: int, depth: int, indices, r: np.ndarray, s: np.ndarray):
+        """zl_groth16_prove_merkle_members: the tree at the device address d_nodes (n leaves, `depth` levels), leaf indices (count,) and blinding scalars ->
+        (`count` proofs of membership, the tree's root (4,): every proof's public input; zero when count == 0)"""
+        pkc, keep_pk = _pk_struct(curve, pk)
+        return self._prove_merkle_members(pkc, curve, r1cs_handle, d_nodes, n, depth, indices, r, s)
 
     def groth16_last_h(self, n: int) -> np.ndarray:
         out = np.zeros((n, 4), dtype=np.uint64)
@@ -1214,6 +1281,26 @@ def _poseidon_roots_from_paths(L, ctx, curve: int, leaves, indices, paths, depth
     return roots
 
 
+def _poseidon_merkle_assignments(L, ctx, curve: int, leaves, indices, paths, depth: int) -> np.ndarray:
+    lv = _elems(leaves, 1)
+    idx = np.ascontiguousarray(indices, dtype=np.uint64).reshape(-1)
+    pa = np.ascontiguousarray(np.asarray(paths, dtype=np.uint64).reshape(-1, max(1, depth), 4))
+    assert lv.shape[0] == idx.size == pa.shape[0]
+    out = np.zeros((idx.size, L.zl_poseidon_merkle_assignment_elems(depth), 4), dtype=np.uint64)
+    _pos_check(L, L.zl_poseidon_merkle_assignments(ctx, curve, _ptr_or_none(lv), _ptr_or_none(idx), _ptr_or_none(pa), depth, idx.size, _ptr_or_none(out)),
+               "zl_poseidon_merkle_assignments")
+    return out
+
+
+def poseidon_merkle_assignment_elems(depth: int) -> int:
+    """elements of one membership's assignment: 3 + 238 depth (0 for a depth outside 1..40)"""
+    return int(load_library().zl_poseidon_merkle_assignment_elems(depth))
+
+
+def poseidon_merkle_assignments_host(curve: int, leaves, indices, paths, depth: int) -> np.ndarray:
+    return _poseidon_merkle_assignments(load_library(), None, curve, leaves, indices, paths, depth)
+
+
 def poseidon_merkle_nodes(n: int, depth: int) -> int:
     """elements of the node array of a tree over n leaves with `depth` hash levels (0 for an invalid shape)"""
     return int(load_library().zl_poseidon_merkle_nodes(n, depth))
@@ -1373,10 +1460,34 @@ class Circuit:
         rc = fn(curve, k, _p64(a), _p64(b), C.byref(self._c))
         if rc:
             raise BackendError(rc, "zl_circuit_poseidon_chain")
+        self._export()
+
+    def _export(self):
         self._view = R1csC()
         zp = u64p()
         self.L.zl_circuit_export(self._c, C.byref(self._view), C.byref(zp))
         self._zp = zp
+
+    @classmethod
+    def merkle(cls, curve: int, depth: int, leaf: int, index: int, path, witness_only: bool = False) -> "Circuit":
+        """the Merkle-membership circuit (zl_circuit_poseidon_merkle): the fold of path (depth integers, bottom up) over leaf at position index equals the
+        public root.  witness_only: as in the constructor."""
+        self = cls.__new__(cls)
+        self.L = load_library()
+        self.curve = curve
+        self.witness_only = witness_only
+        self._c = C.c_void_p()
+        words = lambda v: [(int(v) >> (64 * j)) & (2**64 - 1) for j in range(4)]
+        lf = np.array([words(leaf)], dtype=np.uint64)
+        pa = np.array([words(v) for v in path], dtype=np.uint64).reshape(-1, 4)
+        if pa.shape[0] != depth or not 0 <= index < 2**64:
+            raise BackendError(-1, "zl_circuit_poseidon_merkle")
+        fn = self.L.zl_circuit_poseidon_merkle_witness if witness_only else self.L.zl_circuit_poseidon_merkle
+        rc = fn(curve, depth, _p64(lf), index, _ptr_or_none(pa), C.byref(self._c))
+        if rc:
+            raise BackendError(rc, "zl_circuit_poseidon_merkle")
+        self._export()
+        return self
 
     @property
     def shape(self):
@@ -1510,6 +1621,33 @@ class Groth16Keys:
         if not getattr(self, "_r1cs", 0):
             self._r1cs = self.backend.r1cs_upload(self.circuit.curve, self.circuit.arrays())
         return (lane or self.backend)._prove_chains(self.pk, self.circuit.curve, self._r1cs, k, x0, x1, r, s)
+
+    def merkle_depth(self) -> int:
+        """d when the keys' circuit has the shape of a depth-d Merkle-membership circuit (Circuit.merkle), else 0"""
+        n_c, n_i, n_w = self.circuit.shape
+        d = (n_w - 1) // 238
+        return d if 1 <= d <= 40 and (n_c, n_i, n_w) == (237 * d + 1, 2, 1 + 238 * d) else 0
+
+    def _merkle_ready(self, what: str) -> int:
+        d = self.merkle_depth()
+        if not d:
+            raise ValueError(what + ": the keys' circuit is not a Merkle-membership circuit")
+        if not getattr(self, "_r1cs", 0):
+            self._r1cs = self.backend.r1cs_upload(self.circuit.curve, self.circuit.arrays())
+        return d
+
+    def prove_merkle_paths(self, leaves, indices, paths, r: np.ndarray, s: np.ndarray, lane: Optional[Backend] = None):
+        """zl_groth16_prove_merkle_paths over this key: leaves (count, 4), indices (count,), paths (count, depth, 4) and blinding scalars r, s (count, 4) ->
+        (proofs, roots (count, 4)); proof j is prove_batch's for the assignment of Circuit.merkle(curve, depth, leaves[j], indices[j], paths[j]).  Keys of a
+        circuit that is no membership circuit are refused."""
+        d = self._merkle_ready("prove_merkle_paths")
+        return (lane or self.backend)._prove_merkle_paths(self.pk, self.circuit.curve, self._r1cs, d, leaves, indices, paths, r, s)
+
+    def prove_merkle_members(self, d_nodes: int, n: int, indices, r: np.ndarray, s: np.ndarray, lane: Optional[Backend] = None):
+        """zl_groth16_prove_merkle_members over this key: the tree of n leaves at the device address d_nodes (Backend.poseidon_merkle_build_dev with the keys'
+        depth) and leaf indices (count,) -> (proofs, the root (4,)): from tree to proofs with nothing but the indices going up"""
+        d = self._merkle_ready("prove_merkle_members")
+        return (lane or self.backend)._prove_merkle_members(self.pk, self.circuit.curve, self._r1cs, d_nodes, n, d, indices, r, s)
 
     def prove_many(self, seeds, circuits=None):
         """zl_groth16_prove_circuits: a stream of proofs over this key on two prover lanes (two host threads inside the library); proofs[i] is what

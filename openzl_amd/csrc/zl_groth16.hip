@@ -1040,7 +1040,7 @@ static int g16_batch_queries(zl_ctx* ctx, const zl_g16_pk* pk, const zl_bases* c
 #define ZL_G16_BATCH_BUDGET ((size_t)512 << 20)  // bytes of ZL_SLOT_G16_BATCH a chunk may take
 
 // Where the assignments of a batch come from: host memory (zl_groth16_prove_batch: one upload per chunk), device memory (zl_groth16_prove_batch_dev: one
-// device-to-device copy per chunk), or a producer (zl_groth16_prove_poseidon_chains) that writes the `ch` canonical rows of the chunk from proof c0 on in place
+// device-to-device copy per chunk), or a producer (zl_groth16_prove_poseidon_chains, zl_groth16_prove_merkle_paths / _members) that writes the `ch` canonical rows of the chunk from proof c0 on in place
 // (fill_dev: into the chunk's block of ZL_SLOT_G16_BATCH, on ctx->stream, finished on return) -- and, for the loop over the resident prover, into host rows.
 struct G16BatchSource {
     const uint64_t* host = nullptr;
@@ -1249,6 +1249,62 @@ extern "C" int zl_groth16_prove_poseidon_chains(zl_ctx* ctx, const zl_g16_pk* pk
         return rc;
     };
     return groth16_prove_batch_any(ctx, pk, rd, src, 0, r, s, count, proofs);
+}
+// the checks the two membership provers share, in zl_groth16_prove_batch's order; *rd_out = the resident circuit
+static int g16_merkle_checks(zl_ctx* ctx, const zl_g16_pk* pk, uint64_t r1cs_handle, unsigned depth, bool args_ok, const zl_r1cs_dev** rd_out) {
+    const size_t nv = zl_poseidon_merkle_assignment_elems(depth);
+    if (!ctx || !pk || nv == 0 || !args_ok) return ZL_EINVAL;
+    if (!pk->alpha_g1 || !pk->beta_g1 || !pk->delta_g1 || !pk->beta_g2 || !pk->delta_g2) return ZL_EINVAL;
+    const zl_r1cs_dev* rd = zl_find_r1cs(ctx, r1cs_handle);
+    if (!rd || rd->curve != (int)pk->curve) return ZL_EHANDLE;
+    if (pk->curve != ZL_BLS12_381 && pk->curve != ZL_BN254) return ZL_EINVAL;
+    // the shape of a depth-d membership circuit; what the matrices say cannot be checked, as with a witness-only compiler
+    if (rd->n_instance != 2 || rd->n_witness != nv - 2 || rd->n_constraints != nv - 2 - depth) return ZL_EINVAL;
+    *rd_out = rd;
+    return ZL_OK;
+}
+extern "C" int zl_groth16_prove_merkle_paths(zl_ctx* ctx, const zl_g16_pk* pk, uint64_t r1cs_handle, unsigned depth, const uint64_t* leaves, const uint64_t* indices,
+                                             const uint64_t* paths, const uint64_t* r, const uint64_t* s, size_t count, zl_g16_proof* proofs, uint64_t* roots_out) {
+    const zl_r1cs_dev* rd = nullptr;
+    const int rc0 = g16_merkle_checks(ctx, pk, r1cs_handle, depth, !(count && (!leaves || !indices || !paths || !r || !s || !proofs)), &rd);
+    if (rc0) return rc0;
+    for (size_t i = 0; i < count; i++)
+        if (indices[i] >> depth) return ZL_EINVAL;
+    if (count == 0) return ZL_OK;
+    const size_t nv = zl_poseidon_merkle_assignment_elems(depth);
+    const zl_curve_t curve = pk->curve;
+    G16BatchSource src;
+    src.fill_dev = [=](size_t c0, size_t ch, void* d_rows) {
+        return zl_poseidon_merkle_trace_rows(ctx, (int)curve, leaves + c0 * 4, indices + c0, paths + c0 * depth * 4, depth, ch, d_rows, nv, roots_out ? roots_out + c0 * 4 : nullptr);
+    };
+    src.fill_host = [=](size_t c0, size_t ch, uint64_t* rows) {
+        const int rc = zl_poseidon_merkle_assignments(ctx, curve, leaves + c0 * 4, indices + c0, paths + c0 * depth * 4, depth, ch, rows);
+        if (rc == ZL_OK && roots_out)
+            for (size_t j = 0; j < ch; j++) memcpy(roots_out + (c0 + j) * 4, rows + j * nv * 4 + 4, 32);
+        return rc;
+    };
+    return groth16_prove_batch_any(ctx, pk, rd, src, 0, r, s, count, proofs);
+}
+extern "C" int zl_groth16_prove_merkle_members(zl_ctx* ctx, const zl_g16_pk* pk, uint64_t r1cs_handle, const void* d_nodes, size_t n, unsigned depth, const uint64_t* indices,
+                                               const uint64_t* r, const uint64_t* s, size_t count, zl_g16_proof* proofs, uint64_t* root_out) {
+    const zl_r1cs_dev* rd = nullptr;
+    const int rc0 = g16_merkle_checks(ctx, pk, r1cs_handle, depth, !(count && (!d_nodes || !indices || !r || !s || !proofs)), &rd);
+    if (rc0) return rc0;
+    if (zl_poseidon_merkle_nodes(n, depth) == 0 && n != 0) return ZL_EINVAL;  // (n > 2^depth)
+    for (size_t i = 0; i < count; i++)
+        if (indices[i] >= n) return ZL_EINVAL;
+    if (count == 0) return ZL_OK;
+    const size_t nv = zl_poseidon_merkle_assignment_elems(depth);
+    const zl_curve_t curve = pk->curve;
+    G16BatchSource src;
+    src.fill_dev = [=](size_t c0, size_t ch, void* d_rows) { return zl_poseidon_merkle_member_rows(ctx, (int)curve, d_nodes, n, depth, indices + c0, ch, d_rows, nv, nullptr); };
+    src.fill_host = [=](size_t c0, size_t ch, uint64_t* rows) { return zl_poseidon_merkle_member_rows(ctx, (int)curve, d_nodes, n, depth, indices + c0, ch, nullptr, nv, rows); };
+    const int rc = groth16_prove_batch_any(ctx, pk, rd, src, 0, r, s, count, proofs);
+    if (rc == ZL_OK && root_out) {  // the one root of the tree: the last node of the array
+        ZL_HIP(ctx, hipMemcpyAsync(root_out, static_cast<const uint64_t*>(d_nodes) + (zl_poseidon_merkle_nodes(n, depth) - 1) * 4, 32, hipMemcpyDeviceToHost, ctx->stream));
+        ZL_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    }
+    return rc;
 }
 extern "C" int zl_groth16_last_h(zl_ctx* ctx, uint64_t* out, size_t n) {
     if (!ctx || !out || !ctx->g16_h || n > ctx->g16_h_n) return ZL_EINVAL;

@@ -172,6 +172,28 @@ public:
         B_.push_back(LC::constant(F::one()));
         C_.push_back(b.lc);
     }
+    // Boolean witness (constraint/mod.rs:242-258): one witness of value 0 or 1 and the row (ONE - b) * b = 0, C empty.  ALWAYS allocates, in every mode, so that
+    // a witness-only compiler lines up with the full one.
+    FpVar<FrP> new_boolean_witness(bool bit) {
+        FpVar<FrP> b = new_witness(bit ? F::one() : F::zero());
+        if (witness_only()) return b;
+        A_.push_back(LC::constant(F::one()).add(b.lc.scale(minus_one())));
+        B_.push_back(b.lc);
+        C_.push_back(LC{});
+        return b;
+    }
+    // out = b ? t : f (the plugin's conditionally_select on FpVar, constraint/mod.rs:354-390): one fresh witness and the row b * (t - f) = out - f.  No
+    // constant folding: it ALWAYS allocates, in every mode.  b must be Boolean (new_boolean_witness).
+    FpVar<FrP> select(const FpVar<FrP>& b, const FpVar<FrP>& t, const FpVar<FrP>& f) {
+        FpVar<FrP> out = new_witness(b.value.is_zero() ? f.value : t.value);
+        if (witness_only()) return out;
+        const LC neg_f = f.lc.scale(minus_one());
+        A_.push_back(b.lc);
+        B_.push_back(t.lc.add(neg_f));
+        C_.push_back(out.lc.add(neg_f));
+        return out;
+    }
+    static F minus_one() { return zl::sub(F::zero(), F::one()); }
     bool equalities_hold() const { return equal_ok_; }  // witness-only: every enforce_equal saw equal values
     // full compiler: every multiplication folded constants the way a witness-only run of the same circuit code will (see mul)
     bool witness_only_compatible() const { return !fold_rules_disagree_; }

@@ -671,6 +671,53 @@ static R1CS<FrP> poseidon_chain(uint32_t k, const Fp<FrP>& x0_canon, const Fp<Fr
     return cs;
 }
 
+// Merkle membership (the reference's PathVar::verify_digest with the digest itself as the leaf, openzl-crypto/src/merkle_tree/path.rs:942-1126): the fold of
+// `depth` siblings over the leaf equals the public root.  Per level, in this order: the sibling, the Boolean index bit, left = select(b, sib, cur),
+// right = select(b, cur, sib) (ConditionalSwap as two conditionally_selects, plugins/arkworks/src/constraint/mod.rs:354-390), cur = H(left, right).  The
+// allocation is LEVEL-major (the reference allocates all bits, then all digests, up front) so that a device lane writes its assignment row front to back
+// (k_pos_merkle_trace); every hash takes two plain witnesses, so every level has the same 238 witnesses and 237 rows.
+template <class FrP>
+static FpVar<FrP> merkle_levels(R1CS<FrP>& cs, unsigned depth, const Fp<FrP>& leaf_canon, uint64_t index, const Fp<FrP>* path_canon) {
+    static const poseidon::Constants<FrP> consts;
+    FpVar<FrP> cur = cs.new_witness(zl::to_mont(leaf_canon));
+    for (unsigned j = 0; j < depth; j++) {
+        const FpVar<FrP> sib = cs.new_witness(zl::to_mont(path_canon[j]));
+        const FpVar<FrP> b = cs.new_boolean_witness((index >> j) & 1);
+        const FpVar<FrP> left = cs.select(b, sib, cur);
+        const FpVar<FrP> right = cs.select(b, cur, sib);
+        cur = poseidon::hash(consts, left, right, cs);
+    }
+    return cur;
+}
+template <class FrP>
+static R1CS<FrP> poseidon_merkle_witness(unsigned depth, const Fp<FrP>& leaf_canon, uint64_t index, const Fp<FrP>* path_canon) {
+    R1CS<FrP> cs = R1CS<FrP>::for_witness();
+    const FpVar<FrP> cur = merkle_levels(cs, depth, leaf_canon, index, path_canon);
+    const FpVar<FrP> root = cs.new_input(cur.value);  // (the instance block is its own vector: allocating it last changes no index)
+    cs.enforce_equal(cur, root);
+    return cs;
+}
+template <class FrP>
+static R1CS<FrP> poseidon_merkle(unsigned depth, const Fp<FrP>& leaf_canon, uint64_t index, const Fp<FrP>* path_canon) {
+    using F = Fp<FrP>;
+    static const poseidon::Constants<FrP> consts;
+    R1CS<FrP> cs = R1CS<FrP>::for_proofs();
+    // the fold's value natively: the public input is allocated first, as the chain's h_k
+    F h = zl::to_mont(leaf_canon);
+    for (unsigned j = 0; j < depth; j++) {
+        const F sib = zl::to_mont(path_canon[j]);
+        const bool right = (index >> j) & 1;
+        F st[3] = {zl::from_u64<FrP>(3), right ? sib : h, right ? h : sib};
+        poseidon::permute_native(consts, st);
+        h = st[0];
+    }
+    const FpVar<FrP> root = cs.new_input(h);
+    // every level is synthesised symbolically: depth <= 40 levels of ~10^4 field multiplications each
+    const FpVar<FrP> cur = merkle_levels(cs, depth, leaf_canon, index, path_canon);
+    cs.enforce_equal(cur, root);
+    return cs;
+}
+
 }  // namespace openzl
 
 // ------------------------------------------------------------------------------------------------ C-ABI hooks
@@ -784,6 +831,37 @@ int zl_circuit_poseidon_chain_witness(zl_curve_t curve, uint32_t k, const uint64
     }
     *out = c;
     return ZL_OK;
+}
+static int circuit_merkle(zl_curve_t curve, unsigned depth, const uint64_t* leaf, uint64_t index, const uint64_t* path, bool witness_only, zl_circuit** out) {
+    if (!out || !leaf || !path || depth < 1 || depth > 40 || (index >> depth) || (curve != ZL_BLS12_381 && curve != ZL_BN254)) return ZL_EINVAL;
+    zl_circuit* c = new (std::nothrow) zl_circuit();
+    if (!c) return ZL_ENOMEM;
+    c->curve = curve;
+    if (curve == ZL_BLS12_381) {
+        Fp<BLS12_381_Fr> lf;
+        std::vector<Fp<BLS12_381_Fr>> pa(depth);
+        memcpy(lf.l, leaf, 32);
+        for (unsigned j = 0; j < depth; j++) memcpy(pa[j].l, path + 4 * j, 32);
+        c->bls = new R1CS<BLS12_381_Fr>(witness_only ? poseidon_merkle_witness<BLS12_381_Fr>(depth, lf, index, pa.data())
+                                                     : poseidon_merkle<BLS12_381_Fr>(depth, lf, index, pa.data()));
+        c->ex_bls.build(*c->bls);
+    } else {
+        Fp<BN254_Fr> lf;
+        std::vector<Fp<BN254_Fr>> pa(depth);
+        memcpy(lf.l, leaf, 32);
+        for (unsigned j = 0; j < depth; j++) memcpy(pa[j].l, path + 4 * j, 32);
+        c->bn = new R1CS<BN254_Fr>(witness_only ? poseidon_merkle_witness<BN254_Fr>(depth, lf, index, pa.data())
+                                                : poseidon_merkle<BN254_Fr>(depth, lf, index, pa.data()));
+        c->ex_bn.build(*c->bn);
+    }
+    *out = c;
+    return ZL_OK;
+}
+int zl_circuit_poseidon_merkle(zl_curve_t curve, unsigned depth, const uint64_t* leaf, uint64_t index, const uint64_t* path, zl_circuit** out) {
+    return circuit_merkle(curve, depth, leaf, index, path, false, out);
+}
+int zl_circuit_poseidon_merkle_witness(zl_curve_t curve, unsigned depth, const uint64_t* leaf, uint64_t index, const uint64_t* path, zl_circuit** out) {
+    return circuit_merkle(curve, depth, leaf, index, path, true, out);
 }
 void zl_circuit_free(zl_circuit* c) {
     if (!c) return;

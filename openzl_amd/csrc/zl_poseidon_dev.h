@@ -29,6 +29,12 @@ constexpr size_t FLAG_BYTES = 256;                  // the flag word's corner of
 constexpr int TRACE_PER_LINK = 3 * (FULL_ROUNDS * WIDTH + PARTIAL_ROUNDS - 1);
 static_assert(TRACE_PER_LINK == 234, "78 recorded S-boxes per link");
 
+// the membership circuit's assignment (zl_poseidon_merkle_assignments): 1, root, leaf, then per level sibling, index bit, left, right and the 234 records of
+// H(left, right)
+constexpr int MERKLE_PER_LEVEL = 4 + TRACE_PER_LINK;
+constexpr size_t merkle_row_elems(unsigned depth) { return 3 + (size_t)MERKLE_PER_LEVEL * depth; }
+static_assert(merkle_row_elems(1) == 241 && (merkle_row_elems(MAX_DEPTH) + MAX_DEPTH + 3) * 32 < STAGE_BUDGET, "a row and its inputs fit one staged chunk at every depth");
+
 constexpr bool geometry_ok(size_t n, unsigned depth) { return depth >= 1 && depth <= MAX_DEPTH && ((n >> depth) == 0 || n == ((size_t)1 << depth)); }
 constexpr size_t level_size(size_t n, unsigned k) { return k >= 64 ? (n ? 1 : 0) : (n >> k) + ((n & (((size_t)1 << k) - 1)) ? 1 : 0); }  // ceil(n / 2^k)
 constexpr size_t level_offset(size_t n, unsigned k) {  // elements in front of level k
@@ -44,3 +50,11 @@ constexpr size_t level_offset(size_t n, unsigned k) {  // elements in front of l
 // most ZL_TUNE_POSEIDON_CHUNK chains; finished on return, ZL_EINVAL for an input >= r.  ctx's device is current; curve and k are the caller's to check.
 struct zl_ctx;
 int zl_poseidon_trace_rows(zl_ctx* ctx, int curve, const uint64_t* x0, const uint64_t* x1, uint32_t k, size_t count, void* d_rows, size_t stride_elems, uint64_t* public_out);
+// The membership producers of the fused prover, under the same rules.  _merkle_trace_rows: HOST leaves, indices and paths -> rows in DEVICE memory, the root of
+// every fold to roots_out (host, may be null).  _merkle_member_rows: a node array in DEVICE memory (zl_poseidon_merkle_build_dev's layout) and HOST indices ->
+// rows at d_rows (device), or, when host_rows is not null, dense rows staged on the device and downloaded to host_rows (d_rows and stride_elems are then unused).
+// Curve, depth, n and the index bounds are the caller's to check.
+int zl_poseidon_merkle_trace_rows(zl_ctx* ctx, int curve, const uint64_t* leaves, const uint64_t* indices, const uint64_t* paths, unsigned depth, size_t count, void* d_rows,
+                                  size_t stride_elems, uint64_t* roots_out);
+int zl_poseidon_merkle_member_rows(zl_ctx* ctx, int curve, const void* d_nodes, size_t n, unsigned depth, const uint64_t* indices, size_t count, void* d_rows,
+                                   size_t stride_elems, uint64_t* host_rows);

@@ -9,6 +9,9 @@
 //                    addresses -- the compiler reads them with uniform loads -- already in the multiplier's Montgomery form (x R', R' = 2^261).
 //   k_pos_chain_trace  k_pos_chain that also WRITES what the lane computes on the way: the complete assignment of zl_circuit_poseidon_chain(curve, k, x0, x1)
 //                    -- 1, h_k, x0, x1, then x^2, x^4, x^5 of every S-box the circuit allocates -- as one row of canonical words per chain.
+//   k_pos_merkle_trace  k_pos_fold that writes the complete assignment of zl_circuit_poseidon_merkle(curve, depth, leaf, index, path) per path: 1, root, leaf,
+//                    then per level the sibling, the index bit, the two selected hash inputs and the 234 records of the hash.  Templated over where the
+//                    siblings come from: explicit paths, or the node array of a tree (membership of leaf `index`).
 //   k_pos_tail       one workgroup finishes ALL remaining levels of a Merkle tree once a level has at most T nodes: the level lives in LDS (two buffers,
 //                    canonical words), __syncthreads() between levels, every level is also written to the node array at the offsets the wide path uses.
 //   k_pos_gather     sibling digests of `count` leaves out of a device node array.
@@ -70,7 +73,10 @@ ZL_HD void store_canon(uint64_t* w, const Fp<FrP>& m) {
 //     (70 and 169: the static_assert below);
 //   * sums stay below 8r < 2^259: far inside the 261 bits of nine limbs and wred's limit of 128 r; the output is canon(mul(x, 1)): a product < 2r;
 //   * the values k_pos_chain_trace records -- x^2, x^4, x^5 of an S-box -- are products themselves (< 2r), so dstore's mul(x, 1) takes them at 2 * 1 and
-//     its canon sees a product again; recording reads the S-box's intermediates and changes none of them, so every bound above holds unchanged.
+//     its canon sees a product again; recording reads the S-box's intermediates and changes none of them, so every bound above holds unchanged;
+//   * k_pos_merkle_trace also records `left` and `right` of every level: each is a loaded element (the sibling, or the leaf at level 0: < 2r) or the digest of
+//     the level below (element 0 of an MDS product: < 6r).  dstore's mul(x, 1) takes that at 6 * 1, far below 64, and hands canon a product (< 2r) as before;
+//     the recorded copies are stored and the originals enter the permutation as in k_pos_fold, so no other bound changes.
 template <class FrP> struct LazyP;
 template <> struct LazyP<BLS12_381_Fr> { using P = BLS12_381_Fr29; };
 template <> struct LazyP<BN254_Fr> { using P = BN254_Fr29; };
@@ -351,6 +357,78 @@ __global__ __launch_bounds__(BLOCK) void k_pos_gather(const uint64_t* __restrict
 #pragma unroll
     for (int i = 0; i < 4; i++) paths[t * 4 + i] = present ? nodes[(lt.off[k] + sib) * 4 + i] : 0;
 }
+// Where k_pos_merkle_trace reads item p's leaf and its sibling at level k (nullptr: the tree has no such node, the sibling is the zero digest): explicit arrays
+// of one leaf and `depth` siblings per item, or the node array of a tree (zl_poseidon_merkle_build_dev's layout) addressed by the item's leaf index.
+struct PathSrc {
+    const uint64_t* leaves;
+    const uint64_t* paths;
+    unsigned depth;
+    __device__ __forceinline__ const uint64_t* leaf(size_t p, uint64_t) const { return leaves + p * 4; }
+    __device__ __forceinline__ const uint64_t* sibling(size_t p, uint64_t, unsigned k) const { return paths + (p * depth + k) * 4; }
+    PathSrc advanced(size_t first) const { return PathSrc{leaves + first * 4, paths + first * depth * 4, depth}; }  // the source of items first, first + 1, ...
+};
+struct TreeSrc {
+    const uint64_t* nodes;
+    LevelTable lt;
+    __device__ __forceinline__ const uint64_t* leaf(size_t, uint64_t idx) const { return nodes + idx * 4; }
+    __device__ __forceinline__ const uint64_t* sibling(size_t, uint64_t idx, unsigned k) const {
+        const uint64_t sib = (idx >> k) ^ 1;
+        return sib < lt.size[k] ? nodes + (lt.off[k] + sib) * 4 : nullptr;
+    }
+    TreeSrc advanced(size_t) const { return *this; }
+};
+__device__ __forceinline__ void copy16(uint64_t* dst16, uint64_t a, uint64_t b, uint64_t c, uint64_t d) {  // one element of canonical words, dst 16-byte aligned
+    ulonglong2* q = reinterpret_cast<ulonglong2*>(dst16);
+    q[0] = make_ulonglong2(a, b);
+    q[1] = make_ulonglong2(c, d);
+}
+// k_pos_fold with the witness written out: the complete assignment of zl_circuit_poseidon_merkle(curve, depth, leaf, index, path) per item, one lane each.
+// Row p = out + p * stride elements (16-byte aligned): [0] = 1, [1] = root, [2] = leaf, then per level j at 3 + 238 j: [+0] the sibling, [+1] the index bit,
+// [+2] left, [+3] right, [+4 .. +238) the 234 records of H(left, right); elements from 3 + 238 depth to the stride are not touched.  The lane writes its row
+// front to back (the root last).  The select copies limbs as k_pos_fold does; left and right go out through dstore16 -- one of them is the loaded sibling
+// (< 2r), the other the running digest (< 6r, or the loaded leaf): within mul(x, 1)'s bound, see above LazyP.  pub (may be null) receives the root, densely.
+template <class FrP, class Src>
+__global__ __launch_bounds__(BLOCK) void k_pos_merkle_trace(const uint32_t* __restrict__ tab, const Src src, const uint64_t* __restrict__ indices, unsigned depth, size_t n,
+                                                            uint64_t* __restrict__ out, size_t stride, uint64_t* __restrict__ pub, uint32_t* __restrict__ flag) {
+    const size_t p = (size_t)blockIdx.x * BLOCK + threadIdx.x;
+    if (p >= n) return;
+    const uint64_t idx = indices[p];
+    uint64_t* row = out + p * stride * 4;
+    El<FrP> cur;
+    const uint64_t* lw = src.leaf(p, idx);
+    bool ok = dload<FrP>(lw, cur);
+    copy16(row + 8, lw[0], lw[1], lw[2], lw[3]);
+    uint64_t* lv = row + 12;
+#pragma unroll 1
+    for (unsigned k = 0; k < depth; k++) {
+        const uint64_t* sw = src.sibling(p, idx, k);
+        El<FrP> sib = ezero<FrP>();
+        if (sw) {
+            ok &= dload<FrP>(sw, sib);
+            copy16(lv, sw[0], sw[1], sw[2], sw[3]);
+        } else {
+            copy16(lv, 0, 0, 0, 0);
+        }
+        const bool right = (idx >> k) & 1;
+        copy16(lv + 4, right ? 1 : 0, 0, 0, 0);
+        El<FrP> s0 = tab_ld<FrP>(tab, pd::TAB_TAG), x, y;
+#pragma unroll
+        for (int w = 0; w < El<FrP>::L; w++) {
+            x.l[w] = right ? sib.l[w] : cur.l[w];
+            y.l[w] = right ? cur.l[w] : sib.l[w];
+        }
+        dstore16<FrP>(lv + 8, x);
+        dstore16<FrP>(lv + 12, y);
+        RowRec<FrP> rec{lv + 16};
+        permute_dev<FrP>(tab, s0, x, y, rec);
+        cur = s0;
+        lv += (size_t)pd::MERKLE_PER_LEVEL * 4;
+    }
+    if (!ok) atomicOr(flag, 1u);
+    copy16(row, 1, 0, 0, 0);
+    dstore16<FrP>(row + 4, cur);
+    if (pub) dstore<FrP>(pub + p * 4, cur);
+}
 
 // ---------------------------------------------------------------------------------------------------------------- host path
 template <class FrP>
@@ -472,6 +550,40 @@ int host_fold(const uint64_t* leaves, const uint64_t* indices, const uint64_t* p
             memcpy(cur, nx, 32);
         }
         memcpy(roots + i * 4, cur, 32);
+        return ok;
+    }) ? ZL_OK : ZL_EINVAL;
+}
+// row i = the assignment of membership i (nv = 3 + 238 depth elements): what poseidon_merkle_witness allocates, level after level through permute_native_record
+template <class FrP>
+int host_merkle_assignments(const uint64_t* leaves, const uint64_t* indices, const uint64_t* paths, unsigned depth, size_t count, uint64_t* out, size_t nv) {
+    consts<FrP>();
+    return host_for(count, [&](size_t i) {
+        Fp<FrP> cur;
+        bool ok = load_canon<FrP>(leaves + i * 4, cur);
+        uint64_t* row = out + i * nv * 4;
+        memcpy(row + 8, leaves + i * 4, 32);
+        std::vector<Fp<FrP>> rec;
+        rec.reserve(pd::TRACE_PER_LINK);
+        for (unsigned k = 0; k < depth; k++) {
+            const uint64_t* sw = paths + (i * depth + k) * 4;
+            uint64_t* lv = row + 12 + (size_t)k * pd::MERKLE_PER_LEVEL * 4;
+            Fp<FrP> sib;
+            ok &= load_canon<FrP>(sw, sib);
+            const bool right = (indices[i] >> k) & 1;
+            memcpy(lv, sw, 32);
+            lv[4] = right ? 1 : 0;
+            lv[5] = lv[6] = lv[7] = 0;
+            Fp<FrP> st[3] = {zl::from_u64<FrP>(3), right ? sib : cur, right ? cur : sib};
+            store_canon<FrP>(lv + 8, st[1]);
+            store_canon<FrP>(lv + 12, st[2]);
+            rec.clear();
+            poseidon::permute_native_record(consts<FrP>(), st, rec);
+            cur = st[0];
+            for (size_t t = 0; t < rec.size(); t++) store_canon<FrP>(lv + 16 + 4 * t, rec[t]);
+        }
+        row[0] = 1;
+        row[1] = row[2] = row[3] = 0;
+        store_canon<FrP>(row + 4, cur);
         return ok;
     }) ? ZL_OK : ZL_EINVAL;
 }
@@ -811,12 +923,79 @@ int dev_paths(zl_ctx* ctx, const void* d_nodes, size_t n, unsigned depth, const 
     ZL_HIP(ctx, hipStreamSynchronize(ctx->stream));
     return ZL_OK;
 }
+// Every form of the membership trace.  Indices are host memory and are staged per chunk; a chunk is one launch (stage_items never exceeds the launch chunk).
+//   hp != null: leaves and paths are HOST memory too and are staged beside the indices (Src is PathSrc and `src` is ignored);
+//   host_rows != null: the rows are staged, dense, and downloaded (d_rows and stride are ignored), otherwise row i goes to d_rows + i * stride elements;
+//   host_pub != null: the root of every item is staged and downloaded.
+struct HostPaths {
+    const uint64_t* leaves;
+    const uint64_t* paths;
+};
+template <class FrP, class Src>
+int merkle_trace_run(zl_ctx* ctx, Src src, const HostPaths* hp, const uint64_t* indices, unsigned depth, size_t count, uint64_t* d_rows, size_t stride, uint64_t* host_rows,
+                     uint64_t* host_pub) {
+    const uint32_t* tab;
+    int rc = get_table<FrP>(ctx, &tab);
+    if (rc) return rc;
+    const size_t nv = pd::merkle_row_elems(depth);
+    const size_t per = 8 + 32 + (hp ? 32 + (size_t)depth * 32 : 0) + (host_rows ? nv * 32 : 0);
+    const size_t chunk = stage_items(per), m0 = count < chunk ? count : chunk;
+    const size_t o_pub = up256(m0 * 8), o_leaf = o_pub + up256(m0 * 32), o_path = o_leaf + (hp ? up256(m0 * 32) : 0), o_rows = o_path + (hp ? up256(m0 * depth * 32) : 0);
+    Stage s;
+    if ((rc = stage_get(ctx, o_rows + (host_rows ? m0 * nv * 32 : 0), &s))) return rc;
+    uint64_t* d_idx = reinterpret_cast<uint64_t*>(s.data);
+    uint64_t* d_pub = host_pub ? reinterpret_cast<uint64_t*>(s.data + o_pub) : nullptr;
+    uint64_t* d_leaf = reinterpret_cast<uint64_t*>(s.data + o_leaf);
+    uint64_t* d_path = reinterpret_cast<uint64_t*>(s.data + o_path);
+    uint64_t* d_stage_rows = reinterpret_cast<uint64_t*>(s.data + o_rows);
+    for (size_t first = 0; first < count; first += chunk) {
+        const size_t m = count - first < chunk ? count - first : chunk;
+        ZL_HIP(ctx, hipMemcpyAsync(d_idx, indices + first, m * 8, hipMemcpyHostToDevice, ctx->stream));
+        Src from = src.advanced(first);
+        if constexpr (std::is_same<Src, PathSrc>::value) {
+            if (hp) {
+                ZL_HIP(ctx, hipMemcpyAsync(d_leaf, hp->leaves + first * 4, m * 32, hipMemcpyHostToDevice, ctx->stream));
+                ZL_HIP(ctx, hipMemcpyAsync(d_path, hp->paths + first * depth * 4, m * depth * 32, hipMemcpyHostToDevice, ctx->stream));
+                from = PathSrc{d_leaf, d_path, depth};
+            }
+        }
+        uint64_t* rows = host_rows ? d_stage_rows : d_rows + first * stride * 4;
+        ZL_POS_LAUNCH(ctx, (k_pos_merkle_trace<FrP, Src>), blocks_of(m), BLOCK, 0, tab, from, d_idx, depth, m, rows, host_rows ? nv : stride, d_pub, s.flag);
+        if (host_rows) ZL_HIP(ctx, hipMemcpyAsync(host_rows + first * nv * 4, d_stage_rows, m * nv * 32, hipMemcpyDeviceToHost, ctx->stream));
+        if (host_pub) ZL_HIP(ctx, hipMemcpyAsync(host_pub + first * 4, d_pub, m * 32, hipMemcpyDeviceToHost, ctx->stream));
+    }
+    return finish(ctx, s.flag);
+}
+template <class FrP>
+int dev_merkle_from_host(zl_ctx* ctx, const uint64_t* leaves, const uint64_t* indices, const uint64_t* paths, unsigned depth, size_t count, uint64_t* d_rows, size_t stride,
+                         uint64_t* host_rows, uint64_t* host_pub) {
+    const HostPaths hp{leaves, paths};
+    return merkle_trace_run<FrP, PathSrc>(ctx, PathSrc{nullptr, nullptr, depth}, &hp, indices, depth, count, d_rows, stride, host_rows, host_pub);
+}
+template <class FrP>
+int dev_merkle_from_paths(zl_ctx* ctx, const void* d_leaves, const uint64_t* indices, const void* d_paths, unsigned depth, size_t count, void* d_rows, size_t stride) {
+    const PathSrc src{static_cast<const uint64_t*>(d_leaves), static_cast<const uint64_t*>(d_paths), depth};
+    return merkle_trace_run<FrP, PathSrc>(ctx, src, nullptr, indices, depth, count, static_cast<uint64_t*>(d_rows), stride, nullptr, nullptr);
+}
+template <class FrP>
+int dev_merkle_from_tree(zl_ctx* ctx, const void* d_nodes, size_t n, unsigned depth, const uint64_t* indices, size_t count, void* d_rows, size_t stride, uint64_t* host_rows) {
+    const TreeSrc src{static_cast<const uint64_t*>(d_nodes), level_table(n, depth)};
+    return merkle_trace_run<FrP, TreeSrc>(ctx, src, nullptr, indices, depth, count, static_cast<uint64_t*>(d_rows), stride, host_rows, nullptr);
+}
 }  // namespace
 
 #define ZL_POS_CURVE(curve, fn, ...) ((curve) == ZL_BLS12_381 ? fn<BLS12_381_Fr>(__VA_ARGS__) : fn<BN254_Fr>(__VA_ARGS__))
 
 int zl_poseidon_trace_rows(zl_ctx* ctx, int curve, const uint64_t* x0, const uint64_t* x1, uint32_t k, size_t count, void* d_rows, size_t stride_elems, uint64_t* public_out) {
     return ZL_POS_CURVE(curve, dev_trace_rows, ctx, x0, x1, k, count, static_cast<uint64_t*>(d_rows), stride_elems, public_out);
+}
+int zl_poseidon_merkle_trace_rows(zl_ctx* ctx, int curve, const uint64_t* leaves, const uint64_t* indices, const uint64_t* paths, unsigned depth, size_t count, void* d_rows,
+                                  size_t stride_elems, uint64_t* roots_out) {
+    return ZL_POS_CURVE(curve, dev_merkle_from_host, ctx, leaves, indices, paths, depth, count, static_cast<uint64_t*>(d_rows), stride_elems, nullptr, roots_out);
+}
+int zl_poseidon_merkle_member_rows(zl_ctx* ctx, int curve, const void* d_nodes, size_t n, unsigned depth, const uint64_t* indices, size_t count, void* d_rows,
+                                   size_t stride_elems, uint64_t* host_rows) {
+    return ZL_POS_CURVE(curve, dev_merkle_from_tree, ctx, d_nodes, n, depth, indices, count, d_rows, stride_elems, host_rows);
 }
 
 extern "C" {
@@ -945,6 +1124,43 @@ int zl_poseidon_merkle_roots_from_paths(zl_ctx* ctx, zl_curve_t curve, const uin
     if (on_host(ctx, count)) return ZL_POS_CURVE(curve, host_fold, leaves, indices, paths, depth, count, roots);
     ZL_HIP(ctx, hipSetDevice(ctx->device));
     return ZL_POS_CURVE(curve, dev_fold, ctx, leaves, indices, paths, depth, count, roots);
+}
+size_t zl_poseidon_merkle_assignment_elems(unsigned depth) {
+    return depth < 1 || depth > pd::MAX_DEPTH ? 0 : pd::merkle_row_elems(depth);
+}
+static int indices_below(const uint64_t* indices, size_t count, uint64_t bound) {
+    for (size_t i = 0; i < count; i++)
+        if (indices[i] >= bound) return 0;
+    return 1;
+}
+int zl_poseidon_merkle_assignments(zl_ctx* ctx, zl_curve_t curve, const uint64_t* leaves, const uint64_t* indices, const uint64_t* paths, unsigned depth, size_t count,
+                                   uint64_t* out) {
+    const size_t nv = zl_poseidon_merkle_assignment_elems(depth);
+    if (!valid_curve(curve) || nv == 0 || (count && (!leaves || !indices || !paths || !out)) || !indices_below(indices, count, (uint64_t)1 << depth)) return ZL_EINVAL;
+    if (count == 0) return ZL_OK;
+    if (on_host(ctx, count)) return ZL_POS_CURVE(curve, host_merkle_assignments, leaves, indices, paths, depth, count, out, nv);
+    ZL_HIP(ctx, hipSetDevice(ctx->device));
+    return ZL_POS_CURVE(curve, dev_merkle_from_host, ctx, leaves, indices, paths, depth, count, nullptr, nv, out, nullptr);
+}
+int zl_poseidon_merkle_assignments_dev(zl_ctx* ctx, zl_curve_t curve, const void* d_leaves, const uint64_t* indices, const void* d_paths, unsigned depth, size_t count,
+                                       void* d_out, size_t stride_elems) {
+    const size_t nv = zl_poseidon_merkle_assignment_elems(depth);
+    if (!ctx || !valid_curve(curve) || nv == 0 || stride_elems < nv || (count && (!d_leaves || !indices || !d_paths || !d_out)) || ((uintptr_t)d_out & 15) ||
+        !indices_below(indices, count, (uint64_t)1 << depth))
+        return ZL_EINVAL;
+    if (count == 0) return ZL_OK;
+    ZL_HIP(ctx, hipSetDevice(ctx->device));
+    return ZL_POS_CURVE(curve, dev_merkle_from_paths, ctx, d_leaves, indices, d_paths, depth, count, d_out, stride_elems);
+}
+int zl_poseidon_merkle_member_assignments_dev(zl_ctx* ctx, zl_curve_t curve, const void* d_nodes, size_t n, unsigned depth, const uint64_t* indices, size_t count,
+                                              void* d_out, size_t stride_elems) {
+    const size_t nv = zl_poseidon_merkle_assignment_elems(depth);
+    if (!ctx || !valid_curve(curve) || nv == 0 || !pd::geometry_ok(n, depth) || stride_elems < nv || (count && (!d_nodes || !indices || !d_out)) ||
+        ((uintptr_t)d_out & 15) || !indices_below(indices, count, n))
+        return ZL_EINVAL;
+    if (count == 0) return ZL_OK;
+    ZL_HIP(ctx, hipSetDevice(ctx->device));
+    return ZL_POS_CURVE(curve, dev_merkle_from_tree, ctx, d_nodes, n, depth, indices, count, d_out, stride_elems, nullptr);
 }
 
 }  // extern "C"
