@@ -17,7 +17,6 @@
 #include <vector>
 #include <chrono>
 #include <stdio.h>
-#include <stdlib.h>
 #include <functional>
 #include "zl_ctx.h"
 #include "zl_poseidon_dev.h"
@@ -32,33 +31,36 @@ __global__ void __launch_bounds__(256) k_fr_from_mont(const Fp<FrP>* __restrict_
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i < n) out[i] = zl::from_mont(in[i]);
 }
-// out[row] = sum_k val[k] * z[col[k]]  (Montgomery); rows >= n_rows: out[n_rows + j] = z[j] for j < tail (A only), else 0
+// out[row] = sum_k val[k] * z[col[k]]  (Montgomery); rows >= n_rows: out[n_rows + j] = z[j] for j < tail (A only), else 0.
+// blockIdx.y = proof: z of proof v at z_all + v nv, out at out_all + v N (a single proof is a launch with grid.y = 1)
 template <class FrP>
 __global__ void __launch_bounds__(256) k_r1cs_spmv(const uint32_t* __restrict__ ptr, const uint32_t* __restrict__ col, const Fp<FrP>* __restrict__ val,
-                                                    const Fp<FrP>* __restrict__ z, uint32_t n_rows, uint32_t tail, uint32_t N,
-                                                    Fp<FrP>* __restrict__ out) {
+                                                    const Fp<FrP>* __restrict__ z_all, uint32_t nv, uint32_t n_rows, uint32_t tail, uint32_t N,
+                                                    Fp<FrP>* __restrict__ out_all) {
     using F = Fp<FrP>;
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= N) return;
+    const F* z = z_all + (size_t)blockIdx.y * nv;
     F acc = F::zero();
     if (i < n_rows) {
         for (uint32_t k = ptr[i]; k < ptr[i + 1]; k++) acc = zl::add(acc, zl::mul(val[k], z[col[k]]));
     } else if (i - n_rows < tail) {
         acc = z[i - n_rows];
     }
-    out[i] = acc;
+    out_all[(size_t)blockIdx.y * N + i] = acc;
 }
 // The same product with EIGHT lanes per row (round 6): a row of the Poseidon circuit's A and B holds up to ~150 terms (the linear layers are merged into the rows), and one
 // lane per row walks them as a chain of dependent multiply-adds -- 91 + 68 us for the 235 rows of a one-hash proof, on the critical path in front of the h MSM.  Lane j of
 // a group takes the terms k = first + j, + 8, ...; the eight partial sums are folded by three xor-shuffle steps (fully reduced Fr: addition is exact in any order).
 template <class FrP>
 __global__ void __launch_bounds__(256) k_r1cs_spmv8(const uint32_t* __restrict__ ptr, const uint32_t* __restrict__ col, const Fp<FrP>* __restrict__ val,
-                                                     const Fp<FrP>* __restrict__ z, uint32_t n_rows, uint32_t tail, uint32_t N,
-                                                     Fp<FrP>* __restrict__ out) {
+                                                     const Fp<FrP>* __restrict__ z_all, uint32_t nv, uint32_t n_rows, uint32_t tail, uint32_t N,
+                                                     Fp<FrP>* __restrict__ out_all) {
     using F = Fp<FrP>;
     const uint32_t gt = blockIdx.x * blockDim.x + threadIdx.x;
     const uint32_t i = gt >> 3, j = gt & 7u;
     if (i >= N) return;  // (N is a multiple of 32: whole groups leave together)
+    const F* z = z_all + (size_t)blockIdx.y * nv;
     F acc = F::zero();
     if (i < n_rows) {
         const uint32_t e = ptr[i + 1];
@@ -73,7 +75,7 @@ __global__ void __launch_bounds__(256) k_r1cs_spmv8(const uint32_t* __restrict__
         for (int w = 0; w < F::N; w++) o.l[w] = (uint32_t)__shfl_xor((int)acc.l[w], d, 8);
         acc = zl::add(acc, o);
     }
-    if (j == 0) out[i] = acc;
+    if (j == 0) out_all[(size_t)blockIdx.y * N + i] = acc;
 }
 // a = (a*b - c) * zinv
 template <class FrP>
@@ -226,10 +228,7 @@ struct G16KeyCache {
     size_t fold_nv = 0, fold_nw = 0, fold_nh = 0;
     bool fold_built = false;
     void drop_fold() {
-        if (fold.d_pts) (void)hipFree(fold.d_pts);
-        if (fold.d_endo) (void)hipFree(fold.d_endo);
-        if (fold.d_inf) (void)hipFree(fold.d_inf);
-        fold = zl_bases{};
+        free_bases(fold);
         fold_built = false;
     }
     // the three extended queries of zl_groth16_prove_batch (g16_batch_queries below): a | delta1 | alpha1, b2 | delta2 | beta2, l | a | b1 | h | alpha1 | beta1 | delta1
@@ -248,6 +247,16 @@ struct G16KeyCache {
         bq_built = false;
     }
     ~G16KeyCache() { drop_fold(); drop_batch(); }
+    // a fresh object for the same key: the host tables come along, the device queries stay with this one (for the proofs of another lane that still use them)
+    std::shared_ptr<G16KeyCache> fresh_with_tables() const {
+        auto fresh = std::make_shared<G16KeyCache>();
+        fresh->key_words = key_words;
+        fresh->alpha1 = alpha1;
+        fresh->beta1 = beta1;
+        fresh->delta1 = delta1;
+        fresh->delta2 = delta2;
+        return fresh;
+    }
 };
 template <class G1, class G2>
 static std::vector<uint32_t> g16_key_words(const zl_g16_pk* pk) {
@@ -279,13 +288,7 @@ static int g16_key_cache(zl_ctx* ctx, const zl_g16_pk* pk, const zl_bases* const
     }
     if (want_fold && !(kc->fold_built && kc->fold_nv == nv && kc->fold_nw == nw && kc->fold_nh == nh && !memcmp(kc->fold_handles, hs, sizeof hs))) {
         if (kc.use_count() > 2) {  // a proof on another lane still works with the old folded query: a fresh cache object takes its place
-            auto fresh = std::make_shared<KC>();
-            fresh->key_words = kc->key_words;
-            fresh->alpha1 = kc->alpha1;
-            fresh->beta1 = kc->beta1;
-            fresh->delta1 = kc->delta1;
-            fresh->delta2 = kc->delta2;
-            kc = fresh;
+            kc = kc->fresh_with_tables();
             bs[3]->g16_cache = kc;
         }
         kc->drop_fold();
@@ -319,350 +322,440 @@ __global__ void __launch_bounds__(256) k_g16_fold_scalars(const Fp<FrP>* __restr
     if (i >= ni) out_zw[i - ni] = zc[i];
 }
 
-template <class G1, class G2>
-// `witness` (optional): the assignment arrives in two pieces, `assignment` = the instance block and `witness` = the witness block, as the
-// compiler holds them (openzl::Groth16::prove): two copies to the device instead of a host-side concatenation of tens of megabytes per proof
-// wm_only: the assignment goes to the device and the witness map runs (z canonical at ctx->g16_z, h at ctx->g16_h), no MSM, no proof: the first step of a proof
-// whose MSMs run on several devices (groth16_prove_sharded_t below); pk's handles are not looked at
-static int groth16_prove_t(zl_ctx* ctx, const zl_g16_pk* pk, const zl_r1cs_dev* cs, const uint64_t* assignment, unsigned flags, const uint64_t* r,
-                           const uint64_t* s, zl_g16_proof* out, const uint64_t* witness = nullptr, bool wm_only = false) {
-    using FrP = typename G1::FrP;
-    using Fr = Fp<FrP>;
-    using F1 = typename G1::F;
-    using F2 = typename G2::F;
+// ---- the checks every prover shares ----------------------------------------------------------------------------------------------------------------------
+// what a circuit's sizes make of a proof: nv variables (ni instance incl. the constant ONE, nw witness), domain N = 2^log_n >= nc + ni
+struct G16Shape {
+    uint32_t nc, ni, nw, nv;
+    unsigned log_n;
+    uint32_t N;
+};
+template <class FrP>
+static int g16_shape(const zl_r1cs_dev* cs, G16Shape* out) {
     const uint32_t nc = cs->n_constraints, ni = cs->n_instance, nw = cs->n_witness;
     const uint64_t nv64 = (uint64_t)ni + nw;
     if (ni < 1 || nv64 >= (1ull << 31)) return ZL_EINVAL;
-    const uint32_t nv = (uint32_t)nv64;
     unsigned log_n = 1;
     while ((1ull << log_n) < (uint64_t)nc + ni) log_n++;
     if (log_n > (unsigned)FrP::TWO_ADICITY || log_n > 28) return ZL_EINVAL;
-    const uint32_t N = 1u << log_n;
-    // handles
+    *out = G16Shape{nc, ni, nw, (uint32_t)nv64, log_n, 1u << log_n};
+    return ZL_OK;
+}
+// the key's five queries, bs = a, b1, h, l (G1), b2 (G2): found (a fork reads its parent's key), of the key's curve and their group, long enough for the shape
+static int g16_key_handles(const zl_ctx* ctx, const zl_g16_pk* pk, const G16Shape& sh, const zl_bases** bs) {
     const uint64_t hs[5] = {pk->a_query, pk->b_g1_query, pk->h_query, pk->l_query, pk->b_g2_query};
-    const zl_bases* bs[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
-    for (int i = 0; i < 5 && !wm_only; i++) {
-        const zl_bases* bp = zl_find_bases(ctx, hs[i]);  // (a fork reads its parent's key)
-        if (!bp) return ZL_EHANDLE;
-        if (bp->curve != (int)pk->curve || bp->group != (i == 4 ? ZL_G2 : ZL_G1)) return ZL_EHANDLE;
-        bs[i] = bp;
+    for (int i = 0; i < 5; i++) {
+        bs[i] = zl_find_bases(ctx, hs[i]);
+        if (!bs[i] || bs[i]->curve != (int)pk->curve || bs[i]->group != (i == 4 ? ZL_G2 : ZL_G1)) return ZL_EHANDLE;
     }
-    if (!wm_only && (bs[0]->n < nv || bs[1]->n < nv || bs[4]->n < nv || bs[2]->n < (size_t)N - 1 || bs[3]->n < nw)) return ZL_EINVAL;
+    if (bs[0]->n < sh.nv || bs[1]->n < sh.nv || bs[4]->n < sh.nv || bs[2]->n < (size_t)sh.N - 1 || bs[3]->n < sh.nw) return ZL_EINVAL;
+    return ZL_OK;
+}
+// what every entry point asks of (pk, r1cs handle) after its own argument checks: the key's five points are there, the circuit is resident and of the key's curve
+static int g16_entry(const zl_ctx* ctx, const zl_g16_pk* pk, uint64_t r1cs_handle, const zl_r1cs_dev** rd_out) {
+    if (!pk->alpha_g1 || !pk->beta_g1 || !pk->delta_g1 || !pk->beta_g2 || !pk->delta_g2) return ZL_EINVAL;
+    const zl_r1cs_dev* rd = zl_find_r1cs(ctx, r1cs_handle);
+    if (!rd || rd->curve != (int)pk->curve) return ZL_EHANDLE;
+    *rd_out = rd;
+    return ZL_OK;
+}
 
+// ---- the witness map: z -> h, for one proof or a chunk of them ---------------------------------------------------------------------------------------------
+// z arrived in one form (ZL_MONT: Montgomery at d_zm, else canonical at d_zc); the other one is made on the device.  n elements, on ctx->stream
+template <class FrP>
+static int g16_z_forms(zl_ctx* ctx, Fp<FrP>* d_zc, Fp<FrP>* d_zm, uint32_t n, unsigned flags) {
     hipStream_t st = ctx->stream;
-    static const bool trace = getenv("ZL_HOST_TRACE") != nullptr;  // developer aid: host-side phase times on stderr
-    const auto tp0 = std::chrono::steady_clock::now();
-    auto lap_us = [&](const char* what) {
-        if (trace) fprintf(stderr, "[zl_groth16 nc=%u] %-28s at %8.1f us\n", (unsigned)nc, what,
-                           (double)std::chrono::duration_cast<std::chrono::nanoseconds>(std::chrono::steady_clock::now() - tp0).count() / 1e3);
-    };
+    if (flags & ZL_MONT) {  // arkworks' in-memory assignment: Montgomery limbs; the canonical copy (MSM scalars) is made on the device
+        hipLaunchKernelGGL((k_fr_from_mont<FrP>), dim3((n + 255) / 256), dim3(256), 0, st, d_zm, d_zc, n);
+    } else {
+        ZL_HIP(ctx, hipMemcpyAsync(d_zm, d_zc, (size_t)n * 32, hipMemcpyDeviceToDevice, st));
+        hipLaunchKernelGGL((k_fr_to_mont<FrP>), dim3((n + 255) / 256), dim3(256), 0, st, d_zm, n);
+    }
+    return ZL_OK;
+}
+// 1 / (g^N - 1): the vanishing polynomial of the domain is constant on the coset g H
+template <class FrP>
+static Fp<FrP> g16_zinv(unsigned log_n) {
+    using Fr = Fp<FrP>;
+    Fr gN;
+    for (int i = 0; i < Fr::N; i++) gN.l[i] = FrP::generator(i);
+    for (unsigned i = 0; i < log_n; i++) gN = zl::sqr(gN);
+    return zl::inv(zl::sub(gN, Fr::one()));
+}
+// `nvec` vectors of 2^log_n elements, one after the other, through the transform steps `steps`: step by step with all vectors in one launch per pass, or
+// vector by vector, each through all its steps
+static int g16_transform(zl_ctx* ctx, int curve, unsigned char* d, unsigned nvec, unsigned log_n, std::initializer_list<unsigned> steps, bool batched) {
+    const size_t stride = (size_t)32 << log_n;
+    int rc;
+    if (batched && nvec > 1) {
+        for (unsigned flags : steps)
+            if ((rc = zl_ntt_run_batch(ctx, curve, d, log_n, flags, nvec, stride))) return rc;
+        return ZL_OK;
+    }
+    for (unsigned v = 0; v < nvec; v++)
+        for (unsigned flags : steps)
+            if ((rc = zl_ntt_run(ctx, curve, d + v * stride, log_n, flags))) return rc;
+    return ZL_OK;
+}
+// spmv, 3 x (ifft, coset fft), pointwise, coset ifft, issued on ctx->stream: z of proof v (Montgomery) at d_zm + v nv, a | b | c laid out [3][count][N] at d_abc;
+// leaves h of proof v, in Montgomery form, at d_abc + v N
+template <class FrP>
+static int g16_witness_map(zl_ctx* ctx, int curve, const zl_r1cs_dev* cs, const Fp<FrP>* d_zm, uint32_t nv, uint32_t count, Fp<FrP>* d_abc, unsigned log_n) {
+    using Fr = Fp<FrP>;
+    const uint32_t nc = cs->n_constraints, ni = cs->n_instance, N = 1u << log_n, tot = count * N;
+    const unsigned char* dm = reinterpret_cast<const unsigned char*>(cs->d_base);
+    hipStream_t st = ctx->stream;
+    for (int m = 0; m < 3; m++) {
+        const uint32_t* ptr = (const uint32_t*)(dm + cs->off_ptr[m]);
+        const uint32_t* col = (const uint32_t*)(dm + cs->off_col[m]);
+        const Fr* val = (const Fr*)(dm + cs->off_val[m]);
+        Fr* out = d_abc + (size_t)m * tot;
+        // rows of >= 4 terms on average (A and B of the Poseidon circuit: ~13): eight lanes per row; C (one term per row): one lane
+        if (cs->nnz[m] >= (size_t)4 * nc && zl_tune("ZL_TUNE_SPMV8", 1))
+            hipLaunchKernelGGL((k_r1cs_spmv8<FrP>), dim3((uint32_t)(((uint64_t)N * 8 + 255) / 256), count), dim3(256), 0, st, ptr, col, val, d_zm, nv, nc, m == 0 ? ni : 0u, N, out);
+        else
+            hipLaunchKernelGGL((k_r1cs_spmv<FrP>), dim3((N + 255) / 256, count), dim3(256), 0, st, ptr, col, val, d_zm, nv, nc, m == 0 ? ni : 0u, N, out);
+    }
+    ZL_HIP(ctx, hipGetLastError());
+    // a, b, c go through their inverse transform and their coset transform together (one launch per pass, grid.y = vector): a transform of <= 2^16 elements
+    // is a chain of passes of ~20 us each whatever its size (16 workgroups at 2^14), so six of a proof's seven transforms cost the latency of two
+    // (interleaved A/B, profiles/r06_ntt_batch_ab.log: 1 882 constraints 1.00 -> 0.86 ms, 14 977: 1.58 -> 1.45 (BN254 1.25 -> 1.10), 2^16 - 2^18: -2 %; at 2^20 the passes fill
+    // the machine and three at a time is 1-2 % SLOWER beside the G2 accumulation: a single proof's go together on domains up to 2^18 only)
+    const bool batched = count > 1 || log_n <= (unsigned)zl_tune("ZL_TUNE_NTT_BATCH_LOG_N", 18);
+    unsigned char* d = reinterpret_cast<unsigned char*>(d_abc);
+    int rc;
+    if ((rc = g16_transform(ctx, curve, d, 3 * count, log_n, {ZL_MONT | ZL_INVERSE, ZL_MONT | ZL_COSET}, batched))) return rc;
+    hipLaunchKernelGGL((k_qap_pointwise<FrP>), dim3((tot + 255) / 256), dim3(256), 0, st, d_abc, d_abc + (size_t)tot, d_abc + 2 * (size_t)tot, g16_zinv<FrP>(log_n), tot);
+    ZL_HIP(ctx, hipGetLastError());
+    return g16_transform(ctx, curve, d, count, log_n, {ZL_MONT | ZL_INVERSE | ZL_COSET}, batched);
+}
+
+// ---- one proof on one device (zl_groth16_prove_resident) -------------------------------------------------------------------------------------------------------
+static bool g16_host_trace() {
+    static const bool on = getenv("ZL_HOST_TRACE") != nullptr;  // developer aid: host-side phase times on stderr
+    return on;
+}
+// (r s) as words, from the product in Fr: (r s) delta1 is then a fixed-base product of its own, independent of the other ones
+template <class FrP>
+static void g16_rs(const uint32_t* rw, const uint32_t* sw, uint32_t* rsw) {
+    Fp<FrP> rm, sm;
+    memcpy(rm.l, rw, 32);
+    memcpy(sm.l, sw, 32);
+    const Fp<FrP> rs = zl::from_mont(zl::mul(zl::to_mont(rm), zl::to_mont(sm)));
+    memcpy(rsw, rs.l, 32);
+}
+// A, B1 and B are one sum each: blinding product + first query point (index 0 pairs with z_0 = 1; null when the MSM started at index 0) + MSM + key point
+template <class G>
+static XYZZ<typename G::F> g16_blinded_sum(const XYZZ<typename G::F>& blind, const uint64_t* first_xy, const XYZZ<typename G::F>& msm, const uint64_t* key_xy) {
+    XYZZ<typename G::F> p = blind;
+    if (first_xy) zl::add_full(p, affine_from_canon<G>(first_xy));
+    zl::add_full(p, msm);
+    zl::add_full(p, affine_from_canon<G>(key_xy));
+    return p;
+}
+// What the phases of a proof share.  It lives in the frame of the prover that runs them; the worker threads, the completion callback and the host threads get a
+// pointer to it, and every return of that prover first waits for all of them.
+template <class G1, class G2>
+struct G16Proof {
+    using Fr = Fp<typename G1::FrP>;
+    using F1 = typename G1::F;
+    using F2 = typename G2::F;
+    zl_ctx* ctx;
+    const zl_g16_pk* pk;
+    const zl_r1cs_dev* cs;
+    G16Shape sh;
+    const std::chrono::steady_clock::time_point tp0 = std::chrono::steady_clock::now();
+    // stage: device pointers into ZL_SLOT_GROTH16, the two events of the witness-map stream, the caller's timing switch
+    Fr *d_zc = nullptr, *d_zm = nullptr, *d_abc = nullptr, *d_h = nullptr;
+    bool fold = false;     // C from ONE folded query (G16KeyCache): its scalars z_w | s z | r z | h are one vector at d_h - fold_head
+    size_t fold_head = 0;
+    hipEvent_t ev_z = nullptr, ev_h = nullptr;
+    int timing_saved = 0;
+    // witness-map job: 4 once ev_h is recorded (the h job of the G1 pipeline, told by `recorded`, may then wait for it), negative on failure
+    std::atomic<int> h_recorded{0};
+    int rc_wm = ZL_OK;
+    // key: handles, first points of the a / b1 / b2 queries, host tables
+    const zl_bases* bs[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
+    uint64_t a0_xy[12], b0_xy[12], b20_xy[24];
+    std::shared_ptr<G16KeyCache<G1, G2>> kc;
+    // blinding scalars as words and their fixed-base products (threads pre, pre_g2)
+    uint32_t rw[8], sw[8], rsw[8];
+    std::thread pre, pre_g2;
+    XYZZ<F1> r_delta1, s_delta1, rs_delta, c_fixed;
+    XYZZ<F2> s_delta2;
+    // MSM partial sums where the pipelines put them, and what the G2 worker and the completion callback make of them
+    uint64_t g1_sums[4][ZL_PARTIAL_WORDS], g2_sum[ZL_PARTIAL_WORDS];
+    int rc_g2 = ZL_OK;
+    XYZZ<F1> g_c = XYZZ<F1>::inf();
+    bool have_c = false;
+    uint64_t a_words[12] = {0}, b_words[24] = {0};
+    uint8_t a_inf = 0, b_inf = 0;
+
+    G16Proof(zl_ctx* c, const zl_g16_pk* k, const zl_r1cs_dev* r1cs, const G16Shape& shape) : ctx(c), pk(k), cs(r1cs), sh(shape) {}
+    void lap(const char* what) const {
+        if (g16_host_trace()) fprintf(stderr, "[zl_groth16 nc=%u] %-28s at %8.1f us\n", (unsigned)sh.nc, what,
+                                      (double)std::chrono::duration_cast<std::chrono::nanoseconds>(std::chrono::steady_clock::now() - tp0).count() / 1e3);
+    }
+    // nothing of the witness map is in flight any more (its issuing thread works on this object): before every return after g16_issue_witness_map
+    hipError_t join_witness_map() {
+        zl_ctx_worker(ctx, 0).wait();
+        return hipStreamSynchronize(ctx->aux2->stream);
+    }
+};
+
+// Scratch layout and upload: z in both forms on the device, the folded form's scaled copies, ev_z recorded behind them on ctx->stream; the inner calls' timing off.
+// `witness` (optional): the assignment arrives in two pieces, `assignment` = the instance block and `witness` = the witness block, as the
+// compiler holds them (openzl::Groth16::prove): two copies to the device instead of a host-side concatenation of tens of megabytes per proof
+template <class G1, class G2>
+static int g16_stage(G16Proof<G1, G2>* p, const uint64_t* assignment, const uint64_t* witness, unsigned flags, const uint64_t* r, const uint64_t* s, bool fold,
+                     int ntt_fit_beside) {
+    using FrP = typename G1::FrP;
+    using Fr = Fp<FrP>;
+    zl_ctx* ctx = p->ctx;
+    const uint32_t ni = p->sh.ni, nw = p->sh.nw, nv = p->sh.nv, N = p->sh.N;
+    hipStream_t st = ctx->stream;
     ctx->g16_h = nullptr;  // the quotient of an earlier proof may live in a scratch block this call re-allocates
     ctx->g16_h_n = 0;
     if (ctx->timing_on) ZL_HIP(ctx, hipEventRecord(ctx->ev[0], st));
-    // ---- assignment + work vectors on the device (the matrices are already resident, zl_r1cs_upload) ------------------
+    memcpy(p->rw, r, 32);
+    memcpy(p->sw, s, 32);
+    // z canonical | z Montgomery | a | b | c | [z_w | s z | r z |] h (N entries written, N - 1 used)
+    p->fold = fold;
+    p->fold_head = fold ? (size_t)nw + 2 * (size_t)nv : 0;
     size_t bytes = 0;
     auto take = [&](size_t b) { size_t o = bytes; bytes += (b + 255) / 256 * 256; return o; };
-    const size_t off_zc = take((size_t)nv * 32), off_zm = take((size_t)nv * 32);
-    // a small proof's C comes from ONE folded query (G16KeyCache above): its scalars z_w | s z | r z | h are one vector, h (N entries written, N - 1 used) at its end
-    const bool fold = !wm_only && log_n <= (unsigned)zl_tune("ZL_TUNE_G16_FOLD_LOG_N", ZL_G16_FOLD_LOG_N);
-    const size_t fold_head = fold ? (size_t)nw + 2 * (size_t)nv : 0;
-    const size_t off_a = take((size_t)N * 32), off_b = take((size_t)N * 32), off_c = take((size_t)N * 32), off_h = take((fold_head + N) * 32) + fold_head * 32;
+    const size_t off_zc = take((size_t)nv * 32), off_zm = take((size_t)nv * 32), off_abc = take((size_t)3 * N * 32), off_h = take((p->fold_head + N) * 32) + p->fold_head * 32;
     void* base;
     int rc;
     if ((rc = zl_scratch_get(ctx, ZL_SLOT_GROTH16, bytes, &base))) return rc;
     unsigned char* d = reinterpret_cast<unsigned char*>(base);
-    const unsigned char* dm = reinterpret_cast<const unsigned char*>(cs->d_base);
-    const size_t* off_ptr = cs->off_ptr;
-    const size_t* off_col = cs->off_col;
-    const size_t* off_val = cs->off_val;
-    Fr* d_zc = (Fr*)(d + off_zc);
-    Fr* d_zm = (Fr*)(d + off_zm);
-    auto h2d = [&](Fr* dst) -> hipError_t {
-        if (!witness) return hipMemcpyAsync(dst, assignment, (size_t)nv * 32, hipMemcpyHostToDevice, st);
-        hipError_t e = hipMemcpyAsync(dst, assignment, (size_t)ni * 32, hipMemcpyHostToDevice, st);
-        if (e == hipSuccess && nw) e = hipMemcpyAsync(dst + ni, witness, (size_t)nw * 32, hipMemcpyHostToDevice, st);
-        return e;
-    };
-    if (flags & ZL_MONT) {  // arkworks' in-memory assignment: Montgomery limbs; the canonical copy (MSM scalars) is made on the device
-        ZL_HIP(ctx, h2d(d_zm));
-        hipLaunchKernelGGL((k_fr_from_mont<FrP>), dim3((nv + 255) / 256), dim3(256), 0, st, d_zm, d_zc, nv);
+    p->d_zc = (Fr*)(d + off_zc);
+    p->d_zm = (Fr*)(d + off_zm);
+    p->d_abc = (Fr*)(d + off_abc);
+    p->d_h = (Fr*)(d + off_h);
+    Fr* d_in = (flags & ZL_MONT) ? p->d_zm : p->d_zc;
+    if (!witness) {
+        ZL_HIP(ctx, hipMemcpyAsync(d_in, assignment, (size_t)nv * 32, hipMemcpyHostToDevice, st));
     } else {
-        ZL_HIP(ctx, h2d(d_zc));
-        ZL_HIP(ctx, hipMemcpyAsync(d_zm, d_zc, (size_t)nv * 32, hipMemcpyDeviceToDevice, st));
-        hipLaunchKernelGGL((k_fr_to_mont<FrP>), dim3((nv + 255) / 256), dim3(256), 0, st, d_zm, nv);
+        ZL_HIP(ctx, hipMemcpyAsync(d_in, assignment, (size_t)ni * 32, hipMemcpyHostToDevice, st));
+        if (nw) ZL_HIP(ctx, hipMemcpyAsync(d_in + ni, witness, (size_t)nw * 32, hipMemcpyHostToDevice, st));
     }
-    Fr *d_a = (Fr*)(d + off_a), *d_b = (Fr*)(d + off_b), *d_c = (Fr*)(d + off_c), *d_h = (Fr*)(d + off_h);
-    Fr* d_fold = d_h - fold_head;
+    if ((rc = g16_z_forms<FrP>(ctx, p->d_zc, p->d_zm, nv, flags))) return rc;
     if (fold) {
         Fr sf, rf;
         memcpy(sf.l, s, 32);
         memcpy(rf.l, r, 32);
-        hipLaunchKernelGGL((k_g16_fold_scalars<FrP>), dim3((nv + 255) / 256), dim3(256), 0, st, d_zc, d_zm, sf, rf, ni, nv, d_fold, d_fold + nw, d_fold + nw + nv);
+        Fr* d_fold = p->d_h - p->fold_head;
+        hipLaunchKernelGGL((k_g16_fold_scalars<FrP>), dim3((nv + 255) / 256), dim3(256), 0, st, p->d_zc, p->d_zm, sf, rf, ni, nv, d_fold, d_fold + nw, d_fold + nw + nv);
     }
-    Fr* dv[3] = {d_a, d_b, d_c};
-    // ---- witness map on its own context / stream: spmv, 3 x (ifft, coset fft), pointwise, coset ifft -> h -------------------------
-    // It only needs z, like four of the five MSMs, so it runs beside them (memory- and latency-bound kernels in the shadow of the
-    // bucket accumulation); the h MSM waits for ev_h inside the pipeline.
-    { const int rc_aux = zl_ctx_aux_init(ctx); if (rc_aux) return rc_aux; }
+    // The witness map runs on its own context / stream: it only needs z, like four of the five MSMs, so it runs beside them (memory- and latency-bound kernels
+    // in the shadow of the bucket accumulation) behind ev_z; the h MSM waits for ev_h inside the pipeline.
+    if ((rc = zl_ctx_aux_init(ctx))) return rc;
     zl_ctx* wm = ctx->aux2;
-    wm->ntt_fit_beside = wm_only ? 0 : 1;  // the witness map of a whole proof runs beside the G2 accumulation; on its own (sharded proofs) it takes the faster passes
-    hipStream_t s_wm = wm->stream;
-    hipEvent_t ev_z = wm->ev[0], ev_h = wm->ev[1];
-    ZL_HIP(ctx, hipEventRecord(ev_z, st));
-    const int timing_saved = ctx->timing_on;
+    wm->ntt_fit_beside = ntt_fit_beside;  // the witness map of a whole proof runs beside the G2 accumulation; on its own (sharded proofs) it takes the faster passes
+    p->ev_z = wm->ev[0];
+    p->ev_h = wm->ev[1];
+    ZL_HIP(ctx, hipEventRecord(p->ev_z, st));
+    p->timing_saved = ctx->timing_on;
     ctx->timing_on = 0;  // inner calls must not sync / overwrite the prover's events
     wm->timing_on = 0;
-    // The ~16 launches of the witness map are issued by a persistent thread of the ctx while this one goes on to the MSMs (0.15 ms of host
-    // time that stood in front of every MSM of a small proof).  h_recorded: 4 once ev_h is recorded (the h job, index 3 of the pipeline below,
-    // may then wait for it), negative on failure.
-    std::atomic<int> h_recorded{0};
-    int rc_wm = ZL_OK;
-    zl_worker& w_wm = zl_ctx_worker(ctx, 0);
-    w_wm.run([&]() {
-        auto fail = [&](int code) { rc_wm = code; h_recorded.store(-1, std::memory_order_release); };
-        if (hipSetDevice(ctx->device) != hipSuccess || hipStreamWaitEvent(s_wm, ev_z, 0) != hipSuccess) return fail(ZL_EHIP);
-        for (int m = 0; m < 3; m++) {
-            // rows of >= 4 terms on average (A and B of the Poseidon circuit: ~13): eight lanes per row; C (one term per row): one lane
-            if (cs->nnz[m] >= (size_t)4 * nc && zl_tune("ZL_TUNE_SPMV8", 1))
-                hipLaunchKernelGGL((k_r1cs_spmv8<FrP>), dim3((uint32_t)(((uint64_t)N * 8 + 255) / 256)), dim3(256), 0, s_wm, (const uint32_t*)(dm + off_ptr[m]), (const uint32_t*)(dm + off_col[m]),
-                                   (const Fr*)(dm + off_val[m]), d_zm, nc, m == 0 ? ni : 0u, N, dv[m]);
-            else
-                hipLaunchKernelGGL((k_r1cs_spmv<FrP>), dim3((N + 255) / 256), dim3(256), 0, s_wm, (const uint32_t*)(dm + off_ptr[m]), (const uint32_t*)(dm + off_col[m]),
-                                   (const Fr*)(dm + off_val[m]), d_zm, nc, m == 0 ? ni : 0u, N, dv[m]);
-        }
-        if (hipGetLastError() != hipSuccess) return fail(ZL_EHIP);
-        int r;
-        // a, b, c go through their inverse transform and their coset transform three at a time (one launch per pass, grid.y = vector): a transform of <= 2^16 elements
-        // is a chain of passes of ~20 us each whatever its size (16 workgroups at 2^14), so six of the witness map's seven transforms cost the latency of two
-        // (interleaved A/B, profiles/r06_ntt_batch_ab.log: 1 882 constraints 1.00 -> 0.86 ms, 14 977: 1.58 -> 1.45 (BN254 1.25 -> 1.10), 2^16 - 2^18: -2 %; at 2^20 the passes fill
-        // the machine and three at a time is 1-2 % SLOWER beside the G2 accumulation: domains up to 2^18 only)
-        if (off_c - off_b == off_b - off_a && log_n <= (unsigned)zl_tune("ZL_TUNE_NTT_BATCH_LOG_N", 18)) {
-            if ((r = zl_ntt_run_batch(wm, pk->curve, d_a, log_n, ZL_MONT | ZL_INVERSE, 3, off_b - off_a))) return fail(r);
-            if ((r = zl_ntt_run_batch(wm, pk->curve, d_a, log_n, ZL_MONT | ZL_COSET, 3, off_b - off_a))) return fail(r);
-        } else {
-            for (int m = 0; m < 3; m++) {
-                if ((r = zl_ntt_run(wm, pk->curve, dv[m], log_n, ZL_MONT | ZL_INVERSE))) return fail(r);
-                if ((r = zl_ntt_run(wm, pk->curve, dv[m], log_n, ZL_MONT | ZL_COSET))) return fail(r);
-            }
-        }
-        Fr g;
-        for (int i = 0; i < Fr::N; i++) g.l[i] = FrP::generator(i);
-        Fr gN = g;
-        for (unsigned i = 0; i < log_n; i++) gN = zl::sqr(gN);
-        const Fr zinv = zl::inv(zl::sub(gN, Fr::one()));
-        hipLaunchKernelGGL((k_qap_pointwise<FrP>), dim3((N + 255) / 256), dim3(256), 0, s_wm, d_a, d_b, d_c, zinv, N);
-        if ((r = zl_ntt_run(wm, pk->curve, d_a, log_n, ZL_MONT | ZL_INVERSE | ZL_COSET))) return fail(r);
-        hipLaunchKernelGGL((k_fr_from_mont<FrP>), dim3((N + 255) / 256), dim3(256), 0, s_wm, d_a, d_h, N);
-        if (hipGetLastError() != hipSuccess || hipEventRecord(ev_h, s_wm) != hipSuccess) return fail(ZL_EHIP);
-        h_recorded.store(4, std::memory_order_release);
+    return ZL_OK;
+}
+// The ~16 launches of the witness map are issued by a persistent thread of the ctx (worker 0) while the caller goes on to the MSMs (0.15 ms of host
+// time that stood in front of every MSM of a small proof): h, canonical, at d_h, ev_h recorded behind it
+template <class G1, class G2>
+static void g16_issue_witness_map(G16Proof<G1, G2>* p) {
+    using FrP = typename G1::FrP;
+    zl_ctx_worker(p->ctx, 0).run([p]() {
+        auto fail = [&](int code) { p->rc_wm = code; p->h_recorded.store(-1, std::memory_order_release); };
+        zl_ctx* wm = p->ctx->aux2;
+        const uint32_t N = p->sh.N;
+        if (hipSetDevice(p->ctx->device) != hipSuccess || hipStreamWaitEvent(wm->stream, p->ev_z, 0) != hipSuccess) return fail(ZL_EHIP);
+        const int rc = g16_witness_map<FrP>(wm, p->pk->curve, p->cs, p->d_zm, p->sh.nv, 1, p->d_abc, p->sh.log_n);
+        if (rc) return fail(rc);
+        hipLaunchKernelGGL((k_fr_from_mont<FrP>), dim3((N + 255) / 256), dim3(256), 0, wm->stream, p->d_abc, p->d_h, N);
+        if (hipGetLastError() != hipSuccess || hipEventRecord(p->ev_h, wm->stream) != hipSuccess) return fail(ZL_EHIP);
+        p->h_recorded.store(4, std::memory_order_release);
     });
+}
+// first points of the a / b queries (index 0 pairs with z[0] = 1): static per key, fetched from the device on the first proof only -- here, before the MSM
+// streams are busy (the download uses the ctx's own stream and sort scratch)
+template <class G1, class G2>
+static int g16_first_points(G16Proof<G1, G2>* p) {
+    const struct { const zl_bases* b; int group; uint64_t* out; size_t words; } firsts[3] = {
+        {p->bs[0], ZL_G1, p->a0_xy, 12}, {p->bs[1], ZL_G1, p->b0_xy, 12}, {p->bs[4], ZL_G2, p->b20_xy, 24}};
+    std::lock_guard<std::mutex> cache_lk(zl_bases_cache_mutex());  // (two lanes may prove over one key for the first time together)
+    for (const auto& f : firsts) {
+        if (f.b->first_xy.empty()) {
+            uint64_t tmp[24] = {0};
+            const int rc = ZL_DISPATCH(p->pk->curve, f.group, zl_bases_download, p->ctx, *f.b, 0, 1, tmp);
+            if (rc) return rc;
+            f.b->first_xy.assign(tmp, tmp + f.words);
+        }
+        memcpy(f.out, f.b->first_xy.data(), f.words * 8);
+    }
+    return ZL_OK;
+}
+// host work that does not depend on the MSMs -- the fixed-base products r delta1, s delta2 and (folded form) s alpha1 + r beta1 + r s delta1, or (four-MSM form)
+// s delta1 and -r s delta1 -- runs on two threads while the device is busy: at most 64 mixed additions each from the key's tables
+template <class G1, class G2>
+static void g16_start_fixed_base(G16Proof<G1, G2>* p) {
+    g16_rs<typename G1::FrP>(p->rw, p->sw, p->rsw);
+    p->pre = std::thread([p]() {
+        const G16KeyCache<G1, G2>& kc = *p->kc;
+        p->r_delta1 = kc.delta1.mul(p->rw);
+        p->lap("r delta1 done");
+        p->rs_delta = kc.delta1.mul(p->rsw);
+        if (p->fold) {
+            p->c_fixed = kc.alpha1.mul(p->sw);
+            zl::add_full(p->c_fixed, kc.beta1.mul(p->rw));
+            zl::add_full(p->c_fixed, p->rs_delta);
+        } else {
+            zl::neg_inplace(p->rs_delta);
+            p->s_delta1 = kc.delta1.mul(p->sw);
+        }
+        p->lap("G1 fixed-base products done");
+    });
+    p->pre_g2 = std::thread([p]() { p->s_delta2 = p->kc->delta2.mul(p->sw); p->lap("s delta2 done"); });
+}
+// The G2 MSM runs on an auxiliary stream with its own scratch, issued by worker 1, while the G1 MSMs run on the main streams: the two fill each other's gaps
+// (54 -> ~35 ms at 2^20).  Nobody waits for z on the host: the G2 stream waits for ev_z like the witness map.
+// (Tried: every MSM of a folded proof behind the witness map, so that the accumulations do not sit on the SIMDs its short passes need -- slower at every size, 235 constraints
+// 0.67 -> 0.74, 14 977: 1.58 -> 1.61 (profiles/r06_gate_ab.log): a 2^14 transform is two passes of ~20 us on 16 workgroups whether or not the machine is busy.  What helped
+// is running a, b, c through each transform in one launch, g16_witness_map.)
+template <class G1, class G2>
+static void g16_issue_g2(G16Proof<G1, G2>* p) {
+    zl_ctx_worker(p->ctx, 1).run([p]() {
+        zl_ctx* aux = p->ctx->aux;
+        if (hipSetDevice(aux->device) != hipSuccess || hipStreamWaitEvent(aux->stream, p->ev_z, 0) != hipSuccess) { p->rc_g2 = ZL_EHIP; return; }
+        p->rc_g2 = ZL_DISPATCH(p->pk->curve, ZL_G2, zl_msm_run, aux, *p->bs[4], 1, reinterpret_cast<const unsigned char*>(p->d_zc) + 32, p->sh.nv - 1, p->g2_sum);
+        if (p->rc_g2 != ZL_OK) return;
+        // B = beta2 + sum z_i b2_i + s delta2 is complete here: assembled and normalised (the Fq2 inversion) on this thread, beside the G1 pipeline
+        p->pre_g2.join();
+        store_canon<G2>(p->b_words, &p->b_inf, g16_blinded_sum<G2>(p->s_delta2, p->b20_xy, from_partial<typename G2::F>(p->g2_sum), p->pk->beta_g2));
+        p->lap("B done");
+    });
+}
+// The G1 pipeline, folded form: the a MSM (for A) and ONE MSM over l | a | b1 | h for all of C's sums; the second waits for the witness map's event.
+// All its streams start behind an event the pipeline records on ctx->stream (zl_msm.hip: ev_begin), so behind z.
+template <class G1, class G2>
+static int g16_run_g1_folded(G16Proof<G1, G2>* p) {
+    using F1 = typename G1::F;
+    const unsigned char* zc = reinterpret_cast<const unsigned char*>(p->d_zc);
+    const zl_bases* jb[2] = {p->bs[0], &p->kc->fold};
+    const size_t jf[2] = {1, 0};
+    const void* js[2] = {zc + 32, p->d_h - p->fold_head};
+    const size_t jn[2] = {(size_t)p->sh.nv - 1, p->fold_head + (size_t)p->sh.N - 1};
+    const hipEvent_t jw[2] = {nullptr, p->ev_h};
+    const std::function<void(size_t)> on_done = [p](size_t i) {
+        if (i != 0) return;
+        p->pre.join();
+        const XYZZ<F1> g_a = g16_blinded_sum<G1>(p->r_delta1, p->a0_xy, from_partial<F1>(p->g1_sums[0]), p->pk->alpha_g1);
+        store_canon<G1>(p->a_words, &p->a_inf, g_a);  // A is final: its normalisation (one inversion) runs under the second MSM
+        p->g_c = p->c_fixed;
+        p->have_c = true;
+        p->lap("A done");
+    };
+    return ZL_DISPATCH(p->pk->curve, ZL_G1, zl_msm_run_jobs, p->ctx, jb, jf, js, jn, jw, 2, &p->g1_sums[0][0], (const std::atomic<int>*)&p->h_recorded, &on_done);
+}
+// The G1 pipeline, four-MSM form (sort | accumulate | tail of consecutive MSMs overlap, zl_msm.hip): a, b1, l need only z; the h job waits for the witness map's
+// event.  Order a, b1, l, h: A and B1 are complete after the first two jobs, and their products s A and r B1 (256 doublings + 64 additions each on the host) run
+// on the pipeline's completion thread and one more while the l, h and G2 MSMs are still on the device
+template <class G1, class G2>
+static int g16_run_g1_four(G16Proof<G1, G2>* p) {
+    using F1 = typename G1::F;
+    const unsigned char* zc = reinterpret_cast<const unsigned char*>(p->d_zc);
+    const size_t nv = p->sh.nv;
+    const zl_bases* jb[4] = {p->bs[0], p->bs[1], p->bs[3], p->bs[2]};
+    const size_t jf[4] = {1, 1, 0, 0};
+    const void* js[4] = {zc + 32, zc + 32, zc + (size_t)p->sh.ni * 32, p->d_h};
+    const size_t jn[4] = {nv - 1, nv - 1, (size_t)p->sh.nw, (size_t)p->sh.N - 1};
+    const hipEvent_t jw[4] = {nullptr, nullptr, nullptr, p->ev_h};
+    const std::function<void(size_t)> on_done = [p](size_t i) {
+        if (i != 1) return;
+        p->lap("a, b1 delivered");
+        p->pre.join();
+        const XYZZ<F1> g_a = g16_blinded_sum<G1>(p->r_delta1, p->a0_xy, from_partial<F1>(p->g1_sums[0]), p->pk->alpha_g1);
+        const XYZZ<F1> g1_b = g16_blinded_sum<G1>(p->s_delta1, p->b0_xy, from_partial<F1>(p->g1_sums[1]), p->pk->beta_g1);
+        p->lap("a, b1 in: s A + r B1 starts");
+        {   // s A + r B1 as two single-scalar products side by side (0.3 ms) instead of one interleaved double-scalar product (0.45 ms)
+            XYZZ<F1> rb = XYZZ<F1>::inf();
+            std::thread t_rb([&]() { rb = zl::mul_scalar_w4(g1_b, p->rw); });
+            p->g_c = zl::mul_scalar_w4(g_a, p->sw);
+            t_rb.join();
+            zl::add_full(p->g_c, rb);
+        }
+        zl::add_full(p->g_c, p->rs_delta);
+        store_canon<G1>(p->a_words, &p->a_inf, g_a);  // A is final: its normalisation (one inversion) leaves the critical path too
+        p->have_c = true;
+        p->lap("s A + r B1 done");
+    };
+    return ZL_DISPATCH(p->pk->curve, ZL_G1, zl_msm_run_jobs, p->ctx, jb, jf, js, jn, jw, 4, &p->g1_sums[0][0], (const std::atomic<int>*)&p->h_recorded, &on_done);
+}
+// Host assembly: A (and, in the four-MSM form, s A + r B1 - r s delta1) were formed by the completion callback and B by the G2 worker; C needs the last MSMs --
+// every sum of it in the folded form's second job, l and h in the four-MSM form's third and fourth
+template <class G1, class G2>
+static void g16_assemble(G16Proof<G1, G2>* p, zl_g16_proof* out) {
+    using F1 = typename G1::F;
+    zl::add_full(p->g_c, from_partial<F1>(p->g1_sums[p->fold ? 1 : 2]));
+    if (!p->fold) zl::add_full(p->g_c, from_partial<F1>(p->g1_sums[3]));
+    p->lap("assembly");
+    memset(out, 0, sizeof *out);
+    memcpy(out->a, p->a_words, sizeof p->a_words);
+    out->a_inf = p->a_inf;
+    memcpy(out->b, p->b_words, sizeof p->b_words);
+    out->b_inf = p->b_inf;
+    store_canon<G1>(out->c, &out->c_inf, p->g_c);
+    p->lap("proof normalised");
+}
+
+template <class G1, class G2>
+static int groth16_prove_t(zl_ctx* ctx, const zl_g16_pk* pk, const zl_r1cs_dev* cs, const uint64_t* assignment, unsigned flags, const uint64_t* r,
+                           const uint64_t* s, zl_g16_proof* out, const uint64_t* witness = nullptr) {
+    G16Shape sh;
+    int rc;
+    if ((rc = g16_shape<typename G1::FrP>(cs, &sh))) return rc;
+    G16Proof<G1, G2> p(ctx, pk, cs, sh);
+    if ((rc = g16_key_handles(ctx, pk, sh, p.bs))) return rc;
+    // a small proof's C comes from ONE folded query (G16KeyCache above)
+    const bool fold = sh.log_n <= (unsigned)zl_tune("ZL_TUNE_G16_FOLD_LOG_N", ZL_G16_FOLD_LOG_N);
+    if ((rc = g16_stage(&p, assignment, witness, flags, r, s, fold, 1))) return rc;
+    g16_issue_witness_map(&p);
     // (every return below first waits for that thread: it works on this frame)
-    auto wm_fail = [&](int code) { w_wm.wait(); (void)hipStreamSynchronize(s_wm); ctx->timing_on = timing_saved; return code; };
-    if (wm_only) {
-        w_wm.wait();
-        const hipError_t e1 = hipStreamSynchronize(s_wm), e2 = hipStreamSynchronize(st);
-        ctx->timing_on = timing_saved;
-        if (rc_wm) return rc_wm;
-        if (e1 != hipSuccess || e2 != hipSuccess) { ctx->last_hip = (int)(e1 != hipSuccess ? e1 : e2); return ZL_EHIP; }
-        ctx->g16_h = d_h;
-        ctx->g16_h_n = N;
-        ctx->g16_z = d_zc;
-        return ZL_OK;
-    }
-    // ---- the five MSMs ----------------------------------------------------------------------------------------------
-    uint64_t part[5][ZL_PARTIAL_WORDS];
-    const unsigned char* zc = reinterpret_cast<const unsigned char*>(d_zc);
-    // The G2 MSM runs on an auxiliary stream with its own scratch while the G1 MSMs run on the main streams: the two fill each other's gaps (54 -> ~35 ms at 2^20).
-    // Nobody waits for z on the host: the G1 pipeline's streams all start behind an event it records on `st` (zl_msm.hip: ev_begin), the witness map and the G2
-    // stream wait for ev_z (a small proof spent ~35 us here, in front of every launch of its MSMs)
-    // first points of the a / b queries (index 0 pairs with z[0] = 1); fetched here, before the MSM streams are busy (the download uses the
-    // ctx's own stream and sort scratch)
-    uint64_t a0_xy[12], b0_xy[12], b20_xy[24];
-    {
-        // static per key: fetched from the device on the first proof only
-        const struct { const zl_bases* b; int group; uint64_t* out; size_t words; } firsts[3] = {
-            {bs[0], ZL_G1, a0_xy, 12}, {bs[1], ZL_G1, b0_xy, 12}, {bs[4], ZL_G2, b20_xy, 24}};
-        std::lock_guard<std::mutex> cache_lk(zl_bases_cache_mutex());  // (two lanes may prove over one key for the first time together)
-        for (const auto& f : firsts) {
-            if (f.b->first_xy.empty()) {
-                uint64_t tmp[24] = {0};
-                if ((rc = ZL_DISPATCH(pk->curve, f.group, zl_bases_download, ctx, *f.b, 0, 1, tmp))) return wm_fail(rc);
-                f.b->first_xy.assign(tmp, tmp + f.words);
-            }
-            memcpy(f.out, f.b->first_xy.data(), f.words * 8);
-        }
-    }
+    auto wm_fail = [&](int code) { (void)p.join_witness_map(); ctx->timing_on = p.timing_saved; return code; };
+    if ((rc = g16_first_points(&p))) return wm_fail(rc);
     // the key's host tables (and, for a small proof, its folded C query): built by the first proof over the key
-    std::shared_ptr<G16KeyCache<G1, G2>> kc;
-    if ((rc = g16_key_cache<G1, G2>(ctx, pk, bs, fold, nv, nw, (size_t)N - 1, &kc))) return wm_fail(rc);
-    // host work that does not depend on the MSMs -- the fixed-base products r delta1, s delta2 and (folded form) s alpha1 + r beta1 + r s delta1, or (four-MSM form)
-    // s delta1 and -r s delta1 -- runs on two threads while the device is busy: at most 64 mixed additions each from the key's tables
-    uint32_t rw[8], sw[8];
-    memcpy(rw, r, 32);
-    memcpy(sw, s, 32);
-    XYZZ<F1> r_delta1, s_delta1, rs_delta, c_fixed;
-    XYZZ<F2> s_delta2;
-    // (r s) delta1 from the product r s in Fr, so that the products are independent
-    uint32_t rsw[8];
-    {
-        using FrF = Fp<typename G1::FrP>;
-        FrF rm, sm;
-        memcpy(rm.l, rw, 32);
-        memcpy(sm.l, sw, 32);
-        const FrF rs = zl::from_mont(zl::mul(zl::to_mont(rm), zl::to_mont(sm)));
-        memcpy(rsw, rs.l, 32);
-    }
-    std::thread pre([&]() {
-        r_delta1 = kc->delta1.mul(rw);
-        lap_us("r delta1 done");
-        rs_delta = kc->delta1.mul(rsw);
-        if (fold) {
-            c_fixed = kc->alpha1.mul(sw);
-            zl::add_full(c_fixed, kc->beta1.mul(rw));
-            zl::add_full(c_fixed, rs_delta);
-        } else {
-            zl::neg_inplace(rs_delta);
-            s_delta1 = kc->delta1.mul(sw);
-        }
-        lap_us("G1 fixed-base products done");
-    });
-    std::thread pre_g2([&]() { s_delta2 = kc->delta2.mul(sw); lap_us("s delta2 done"); });
-    lap_us("z on device, host pre started");
-    int rc_g2 = ZL_OK;
-    XYZZ<F1> g_a = XYZZ<F1>::inf(), g1_b = XYZZ<F1>::inf(), g_c = XYZZ<F1>::inf();
-    bool have_c = false;
-    uint64_t a_words[12] = {0}, b_words[24] = {0};
-    uint8_t a_inf = 0, b_inf = 0;
-    {
-        zl_ctx* aux = ctx->aux;
-        const zl_bases* b2 = bs[4];
-        const int curve = pk->curve;
-        uint64_t* out2 = part[4];
-        zl_worker& g2 = zl_ctx_worker(ctx, 1);
-        // (Tried: every MSM of a folded proof behind the witness map, so that the accumulations do not sit on the SIMDs its short passes need -- slower at every size, 235 constraints
-        // 0.67 -> 0.74, 14 977: 1.58 -> 1.61 (profiles/r06_gate_ab.log): a 2^14 transform is two passes of ~20 us on 16 workgroups whether or not the machine is busy.  What helped
-        // is running a, b, c through each transform in one launch, above.)
-        g2.run([&, aux, b2, curve, out2]() {
-            if (hipSetDevice(aux->device) != hipSuccess || hipStreamWaitEvent(aux->stream, ev_z, 0) != hipSuccess) { rc_g2 = ZL_EHIP; return; }
-            rc_g2 = ZL_DISPATCH(curve, ZL_G2, zl_msm_run, aux, *b2, 1, zc + 32, nv - 1, out2);
-            if (rc_g2 != ZL_OK) return;
-            // B = beta2 + sum z_i b2_i + s delta2 is complete here: assembled and normalised (the Fq2 inversion) on this thread, beside the G1 pipeline
-            pre_g2.join();
-            XYZZ<F2> g2_b = s_delta2;
-            zl::add_full(g2_b, affine_from_canon<G2>(b20_xy));
-            zl::add_full(g2_b, from_partial<F2>(out2));
-            zl::add_full(g2_b, affine_from_canon<G2>(pk->beta_g2));
-            store_canon<G2>(b_words, &b_inf, g2_b);
-            lap_us("B done");
-        });
-        if (fold) {
-            // folded form: the a MSM (for A) and ONE MSM over l | a | b1 | h for all of C's sums; the second waits for the witness map's event
-            const zl_bases* jb[2] = {bs[0], &kc->fold};
-            const size_t jf[2] = {1, 0};
-            const void* js[2] = {zc + 32, d_fold};
-            const size_t jn[2] = {(size_t)nv - 1, fold_head + (size_t)N - 1};
-            const hipEvent_t jw[2] = {nullptr, ev_h};
-            uint64_t jp[2][ZL_PARTIAL_WORDS];
-            const std::function<void(size_t)> on_done = [&](size_t i) {
-                if (i != 0) return;
-                pre.join();
-                g_a = r_delta1;
-                zl::add_full(g_a, affine_from_canon<G1>(a0_xy));
-                zl::add_full(g_a, from_partial<F1>(jp[0]));
-                zl::add_full(g_a, affine_from_canon<G1>(pk->alpha_g1));
-                store_canon<G1>(a_words, &a_inf, g_a);  // A is final: its normalisation (one inversion) runs under the second MSM
-                g_c = c_fixed;
-                have_c = true;
-                lap_us("A done");
-            };
-            rc = ZL_DISPATCH(pk->curve, ZL_G1, zl_msm_run_jobs, ctx, jb, jf, js, jn, jw, 2, &jp[0][0], (const std::atomic<int>*)&h_recorded, &on_done);
-            memcpy(part[0], jp[0], sizeof jp[0]);
-            memcpy(part[3], jp[1], sizeof jp[1]);                 // every sum of C
-            { const XYZZ<F1> none = XYZZ<F1>::inf(); memset(part[2], 0, sizeof part[2]); memcpy(part[2], &none, sizeof none); }
-        } else {
-        // the four G1 MSMs as one pipeline (sort | accumulate | tail of consecutive MSMs overlap, zl_msm.hip): l, a, b1 need only z;
-        // the h job waits for the witness map's event
-        {
-            // order a, b1, l, h: A and B1 are complete after the first two jobs (their product s A + r B1 then runs under the other two)
-            const zl_bases* jb[4] = {bs[0], bs[1], bs[3], bs[2]};
-            const size_t jf[4] = {1, 1, 0, 0};
-            const void* js[4] = {zc + 32, zc + 32, zc + (size_t)ni * 32, d_h};
-            const size_t jn[4] = {(size_t)nv - 1, (size_t)nv - 1, (size_t)nw, (size_t)N - 1};
-            const hipEvent_t jw[4] = {nullptr, nullptr, nullptr, ev_h};
-            uint64_t jp[4][ZL_PARTIAL_WORDS];
-            // A and B1 are complete once the a and b1 MSMs (jobs 0, 1) are: their products s A and r B1 (256 doublings + 64 additions each on the host) run on
-            // the pipeline's completion thread and one more while the h MSM and the G2 MSM are still on the device
-            const std::function<void(size_t)> on_done = [&](size_t i) {
-                if (i != 1) return;
-                lap_us("a, b1 delivered");
-                pre.join();
-                g_a = r_delta1;
-                zl::add_full(g_a, affine_from_canon<G1>(a0_xy));
-                zl::add_full(g_a, from_partial<F1>(jp[0]));
-                zl::add_full(g_a, affine_from_canon<G1>(pk->alpha_g1));
-                g1_b = s_delta1;
-                zl::add_full(g1_b, affine_from_canon<G1>(b0_xy));
-                zl::add_full(g1_b, from_partial<F1>(jp[1]));
-                zl::add_full(g1_b, affine_from_canon<G1>(pk->beta_g1));
-                lap_us("a, b1 in: s A + r B1 starts");
-                {   // s A + r B1 as two single-scalar products side by side (0.3 ms) instead of one interleaved double-scalar product (0.45 ms)
-                    XYZZ<F1> rb = XYZZ<F1>::inf();
-                    std::thread t_rb([&]() { rb = zl::mul_scalar_w4(g1_b, rw); });
-                    g_c = zl::mul_scalar_w4(g_a, sw);
-                    t_rb.join();
-                    zl::add_full(g_c, rb);
-                }
-                zl::add_full(g_c, rs_delta);
-                store_canon<G1>(a_words, &a_inf, g_a);  // A is final: its normalisation (one inversion) leaves the critical path too
-                have_c = true;
-                lap_us("s A + r B1 done");
-            };
-            rc = ZL_DISPATCH(pk->curve, ZL_G1, zl_msm_run_jobs, ctx, jb, jf, js, jn, jw, 4, &jp[0][0], (const std::atomic<int>*)&h_recorded, &on_done);
-            memcpy(part[0], jp[0], sizeof jp[0]);
-            memcpy(part[1], jp[1], sizeof jp[1]);
-            memcpy(part[3], jp[2], sizeof jp[2]);
-            memcpy(part[2], jp[3], sizeof jp[3]);
-        }
-        }
-        lap_us("G1 pipeline returned");
-        w_wm.wait();
-        (void)hipStreamSynchronize(s_wm);  // also on the error path: nothing of this proof may still be running
-        g2.wait();
-        if (!rc) rc = rc_wm;
-        lap_us("G2 joined");
-    }
-    if (pre.joinable()) pre.join();
-    if (pre_g2.joinable()) pre_g2.join();
-    if (!rc) rc = rc_g2;
-    if (!rc && !have_c) rc = ZL_EHIP;  // (the completion callback did not run: cannot happen after a successful pipeline)
-    ctx->timing_on = timing_saved;
+    if ((rc = g16_key_cache<G1, G2>(ctx, pk, p.bs, fold, sh.nv, sh.nw, (size_t)sh.N - 1, &p.kc))) return wm_fail(rc);
+    g16_start_fixed_base(&p);
+    p.lap("z on device, host pre started");
+    g16_issue_g2(&p);
+    rc = fold ? g16_run_g1_folded(&p) : g16_run_g1_four(&p);
+    p.lap("G1 pipeline returned");
+    (void)p.join_witness_map();  // also on the error path: nothing of this proof may still be running
+    zl_ctx_worker(ctx, 1).wait();
+    if (!rc) rc = p.rc_wm;
+    p.lap("G2 joined");
+    if (p.pre.joinable()) p.pre.join();
+    if (p.pre_g2.joinable()) p.pre_g2.join();
+    if (!rc) rc = p.rc_g2;
+    if (!rc && !p.have_c) rc = ZL_EHIP;  // (the completion callback did not run: cannot happen after a successful pipeline)
+    ctx->timing_on = p.timing_saved;
     if (rc) return rc;
     if (ctx->timing_on) {
-        ZL_HIP(ctx, hipEventRecord(ctx->ev[1], st));
-        ZL_HIP(ctx, hipStreamSynchronize(st));
+        ZL_HIP(ctx, hipEventRecord(ctx->ev[1], ctx->stream));
+        ZL_HIP(ctx, hipStreamSynchronize(ctx->stream));
         ctx->timing = zl_timing{};
         ZL_HIP(ctx, hipEventElapsedTime(&ctx->timing.total_ms, ctx->ev[0], ctx->ev[1]));
         ctx->timing.launches = 5;
     }
-    ctx->g16_h = d_h;
-    ctx->g16_h_n = N;
-    // ---- host assembly: A (and, in the four-MSM form, s A + r B1 - r s delta1) were formed by the completion callback above and B by the G2 worker; C needs the last MSMs
-    zl::add_full(g_c, from_partial<F1>(part[3]));
-    zl::add_full(g_c, from_partial<F1>(part[2]));
-    lap_us("assembly");
-    memset(out, 0, sizeof *out);
-    memcpy(out->a, a_words, sizeof a_words);
-    out->a_inf = a_inf;
-    memcpy(out->b, b_words, sizeof b_words);
-    out->b_inf = b_inf;
-    store_canon<G1>(out->c, &out->c_inf, g_c);
-    lap_us("proof normalised");
+    ctx->g16_h = p.d_h;
+    ctx->g16_h_n = sh.N;
+    g16_assemble(&p, out);
     return ZL_OK;
 }
 
 // ---- one proof over the G devices of an mctx ---------------------------------------------------------------------------
 // Rank g holds, on zl_mctx_ctx(m, g), bases handles with ITS contiguous slice of every query (zl_g16_shard); rank 0 also holds the constraint matrices.
-//   1. rank 0: assignment -> device, witness map (spmv, 7 NTTs) -> h                                        (groth16_prove_t, wm_only)
+//   1. rank 0: assignment -> device, witness map (spmv, 7 NTTs) -> h                                        (g16_stage, g16_issue_witness_map; the key's handles are not looked at)
 //   2. every rank, on its own host thread: its slices of z and h arrive by device-to-device copy, then its five partial MSMs (a, b1, l, h in G1 and b2
 //      in G2) through the single-device pipeline (zl_msm_run) -> five un-normalised partial sums per rank
 //   3. host: the partials of each MSM are folded over the ranks (what an all-gather + fold does between processes: EC addition is not a collective's
@@ -677,10 +770,11 @@ static int groth16_prove_sharded_t(zl_mctx* m, const zl_g16_pk* pk, const zl_g16
     using F2 = typename G2::F;
     const int G = zl_mctx_size(m);
     zl_ctx* ctx0 = zl_mctx_ctx(m, 0);
-    const uint32_t ni = cs->n_instance, nw = cs->n_witness, nv = ni + nw;
-    unsigned log_n = 1;
-    while ((1ull << log_n) < (uint64_t)cs->n_constraints + ni) log_n++;
-    const size_t N = (size_t)1 << log_n;
+    G16Shape sh;
+    int rc;
+    if ((rc = g16_shape<FrP>(cs, &sh))) return rc;
+    const uint32_t ni = sh.ni, nw = sh.nw, nv = sh.nv;
+    const size_t N = sh.N;
     // the slices must tile [0, nv), [0, nw) and [0, N - 1) in rank order
     size_t v = 0, w = 0, hq = 0;
     for (int g = 0; g < G; g++) {
@@ -688,9 +782,19 @@ static int groth16_prove_sharded_t(zl_mctx* m, const zl_g16_pk* pk, const zl_g16
         v += shards[g].var_count; w += shards[g].wit_count; hq += shards[g].h_count;
     }
     if (v != nv || w != nw || hq != N - 1) return ZL_EINVAL;
-    int rc;
     ZL_HIP(ctx0, hipSetDevice(ctx0->device));
-    if ((rc = groth16_prove_t<G1, G2>(ctx0, pk, cs, assignment, flags, r, s, nullptr, nullptr, true))) return rc;
+    {   // step 1: no MSM follows on this ctx, so no folded scalars, the transforms' faster passes, and the host waits for h
+        G16Proof<G1, G2> p(ctx0, pk, cs, sh);
+        if ((rc = g16_stage(&p, assignment, nullptr, flags, r, s, false, 0))) return rc;
+        g16_issue_witness_map(&p);
+        const hipError_t e1 = p.join_witness_map(), e2 = hipStreamSynchronize(ctx0->stream);
+        ctx0->timing_on = p.timing_saved;
+        if (p.rc_wm) return p.rc_wm;
+        if (e1 != hipSuccess || e2 != hipSuccess) { ctx0->last_hip = (int)(e1 != hipSuccess ? e1 : e2); return ZL_EHIP; }
+        ctx0->g16_h = p.d_h;
+        ctx0->g16_h_n = N;
+        ctx0->g16_z = p.d_zc;
+    }
     const unsigned char* d_z0 = reinterpret_cast<const unsigned char*>(ctx0->g16_z);
     const unsigned char* d_h0 = reinterpret_cast<const unsigned char*>(ctx0->g16_h);
     std::vector<std::array<uint64_t, 5 * ZL_PARTIAL_WORDS>> parts((size_t)G);
@@ -745,25 +849,13 @@ static int groth16_prove_sharded_t(zl_mctx* m, const zl_g16_pk* pk, const zl_g16
     uint32_t rw[8], sw[8], rsw[8];
     memcpy(rw, r, 32);
     memcpy(sw, s, 32);
-    {
-        using FrF = Fp<FrP>;
-        FrF rm, sm;
-        memcpy(rm.l, rw, 32);
-        memcpy(sm.l, sw, 32);
-        const FrF rs = zl::from_mont(zl::mul(zl::to_mont(rm), zl::to_mont(sm)));
-        memcpy(rsw, rs.l, 32);
-    }
+    g16_rs<FrP>(rw, sw, rsw);
     const XYZZ<F1> delta1 = affine_from_canon<G1>(pk->delta_g1);
     const XYZZ<F2> delta2 = affine_from_canon<G2>(pk->delta_g2);
-    XYZZ<F1> g_a = zl::mul_scalar_w4(delta1, rw);           // A = alpha + sum z_i a_i + r delta
-    zl::add_full(g_a, sum1[0]);
-    zl::add_full(g_a, affine_from_canon<G1>(pk->alpha_g1));
-    XYZZ<F1> g1_b = zl::mul_scalar_w4(delta1, sw);          // B1 = beta + sum z_i b_i + s delta
-    zl::add_full(g1_b, sum1[1]);
-    zl::add_full(g1_b, affine_from_canon<G1>(pk->beta_g1));
-    XYZZ<F2> g2_b = zl::mul_scalar_w4(delta2, sw);          // B = the same in G2
-    zl::add_full(g2_b, sum2);
-    zl::add_full(g2_b, affine_from_canon<G2>(pk->beta_g2));
+    // (the ranks' MSMs start at index 0 of their slices: no first point to add)
+    const XYZZ<F1> g_a = g16_blinded_sum<G1>(zl::mul_scalar_w4(delta1, rw), nullptr, sum1[0], pk->alpha_g1);   // A = alpha + sum z_i a_i + r delta
+    const XYZZ<F1> g1_b = g16_blinded_sum<G1>(zl::mul_scalar_w4(delta1, sw), nullptr, sum1[1], pk->beta_g1);   // B1 = beta + sum z_i b_i + s delta
+    const XYZZ<F2> g2_b = g16_blinded_sum<G2>(zl::mul_scalar_w4(delta2, sw), nullptr, sum2, pk->beta_g2);      // B = the same in G2
     XYZZ<F1> g_c = zl::mul_scalar_w4(g_a, sw);              // C = s A + r B1 - r s delta + sum_w z_w l_w + sum h_i H_i
     zl::add_full(g_c, zl::mul_scalar_w4(g1_b, rw));
     XYZZ<F1> rs_delta = zl::mul_scalar_w4(delta1, rsw);
@@ -780,13 +872,13 @@ static int groth16_prove_sharded_t(zl_mctx* m, const zl_g16_pk* pk, const zl_g16
 extern "C" int zl_groth16_prove_sharded(zl_mctx* m, const zl_g16_pk* pk, const zl_g16_shard* shards, uint64_t r1cs_handle_rank0, const uint64_t* assignment,
                                         unsigned flags, const uint64_t* r, const uint64_t* s, zl_g16_proof* out) {
     if (!m || !pk || !shards || !assignment || !r || !s || !out || (flags & ~ZL_MONT)) return ZL_EINVAL;
-    if (!pk->alpha_g1 || !pk->beta_g1 || !pk->delta_g1 || !pk->beta_g2 || !pk->delta_g2) return ZL_EINVAL;
     zl_ctx* ctx0 = zl_mctx_ctx(m, 0);
     if (!ctx0) return ZL_EINVAL;
-    auto it = ctx0->r1cs.find(r1cs_handle_rank0);
-    if (it == ctx0->r1cs.end() || it->second.curve != (int)pk->curve) return ZL_EHANDLE;
-    if (pk->curve == ZL_BLS12_381) return groth16_prove_sharded_t<BlsG1, BlsG2>(m, pk, shards, &it->second, assignment, flags, r, s, out);
-    if (pk->curve == ZL_BN254) return groth16_prove_sharded_t<BnG1, BnG2>(m, pk, shards, &it->second, assignment, flags, r, s, out);
+    const zl_r1cs_dev* rd = nullptr;
+    const int rc = g16_entry(ctx0, pk, r1cs_handle_rank0, &rd);
+    if (rc) return rc;
+    if (pk->curve == ZL_BLS12_381) return groth16_prove_sharded_t<BlsG1, BlsG2>(m, pk, shards, rd, assignment, flags, r, s, out);
+    if (pk->curve == ZL_BN254) return groth16_prove_sharded_t<BnG1, BnG2>(m, pk, shards, rd, assignment, flags, r, s, out);
     return ZL_EINVAL;
 }
 
@@ -839,9 +931,9 @@ extern "C" int zl_r1cs_free(zl_ctx* ctx, uint64_t handle) {
 extern "C" int zl_groth16_prove_resident(zl_ctx* ctx, const zl_g16_pk* pk, uint64_t r1cs_handle, const uint64_t* assignment, unsigned flags,
                                          const uint64_t* r, const uint64_t* s, zl_g16_proof* out) {
     if (!ctx || !pk || !assignment || !r || !s || !out || (flags & ~ZL_MONT)) return ZL_EINVAL;
-    if (!pk->alpha_g1 || !pk->beta_g1 || !pk->delta_g1 || !pk->beta_g2 || !pk->delta_g2) return ZL_EINVAL;
-    const zl_r1cs_dev* rd = zl_find_r1cs(ctx, r1cs_handle);
-    if (!rd || rd->curve != (int)pk->curve) return ZL_EHANDLE;
+    const zl_r1cs_dev* rd = nullptr;
+    const int rc = g16_entry(ctx, pk, r1cs_handle, &rd);
+    if (rc) return rc;
     ZL_HIP(ctx, hipSetDevice(ctx->device));
     if (pk->curve == ZL_BLS12_381) return groth16_prove_t<BlsG1, BlsG2>(ctx, pk, rd, assignment, flags, r, s, out);
     if (pk->curve == ZL_BN254) return groth16_prove_t<BnG1, BnG2>(ctx, pk, rd, assignment, flags, r, s, out);
@@ -851,8 +943,9 @@ extern "C" int zl_groth16_prove_resident(zl_ctx* ctx, const zl_g16_pk* pk, uint6
 int zl_groth16_prove_split(zl_ctx* ctx, const zl_g16_pk* pk, uint64_t r1cs_handle, const uint64_t* instance, const uint64_t* witness, const uint64_t* r,
                            const uint64_t* s, zl_g16_proof* out) {
     if (!ctx || !pk || !instance || !r || !s || !out) return ZL_EINVAL;
-    const zl_r1cs_dev* rd = zl_find_r1cs(ctx, r1cs_handle);
-    if (!rd || rd->curve != (int)pk->curve) return ZL_EHANDLE;
+    const zl_r1cs_dev* rd = nullptr;
+    const int rc = g16_entry(ctx, pk, r1cs_handle, &rd);
+    if (rc) return rc;
     if (rd->n_witness && !witness) return ZL_EINVAL;
     ZL_HIP(ctx, hipSetDevice(ctx->device));
     static const uint64_t none[4] = {0, 0, 0, 0};
@@ -874,55 +967,13 @@ extern "C" int zl_groth16_prove(zl_ctx* ctx, const zl_g16_pk* pk, const zl_r1cs*
 // ---- many proofs over one key in one device pass (zl_groth16_prove_batch) -------------------------------------------------------------------------------------
 // The single small proof is ~16 launches of kernels that occupy a handful of workgroups, three MSMs of a few hundred points and six fixed-base products on host
 // threads.  A batch of witnesses over one key turns every one of those into ONE launch with a batch dimension:
-//   * witness map: a, b, c laid out [3][chunk][N]; the two transform steps are one zl_ntt_run_batch of 3 chunk vectors each, the pointwise step runs over chunk N
+//   * witness map (g16_witness_map, count = chunk): a, b, c laid out [3][chunk][N]; the two transform steps are one zl_ntt_run_batch of 3 chunk vectors each, the pointwise step runs over chunk N
 //     elements, the coset inverse is one more batch call;
 //   * the whole proof inside three multi-MSMs (zl_msm_multi.hip) over extended queries cached with the key:
 //       A = <(1, z_1.., r, 1),                      a | delta1 | alpha1>
 //       B = <(1, z_1.., s, 1),                      b2 | delta2 | beta2>
 //       C = <(z_w | s z | r z | h | s | r | r s),   l | a | b1 | h | alpha1 | beta1 | delta1>      (the folded form of C above with its three fixed-base terms inside)
 //     so the host does no point arithmetic and the proofs come back canonical.  Variable 0 enters unscaled as in k_g16_fold_scalars.
-// Batched variants of the matrix-vector products (blockIdx.y = proof): z of proof v at z + v nv, out at out + v N
-template <class FrP>
-__global__ void __launch_bounds__(256) k_r1cs_spmv_batch(const uint32_t* __restrict__ ptr, const uint32_t* __restrict__ col, const Fp<FrP>* __restrict__ val,
-                                                          const Fp<FrP>* __restrict__ z_all, uint32_t nv, uint32_t n_rows, uint32_t tail, uint32_t N,
-                                                          Fp<FrP>* __restrict__ out_all) {
-    using F = Fp<FrP>;
-    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= N) return;
-    const F* z = z_all + (size_t)blockIdx.y * nv;
-    F acc = F::zero();
-    if (i < n_rows) {
-        for (uint32_t k = ptr[i]; k < ptr[i + 1]; k++) acc = zl::add(acc, zl::mul(val[k], z[col[k]]));
-    } else if (i - n_rows < tail) {
-        acc = z[i - n_rows];
-    }
-    out_all[(size_t)blockIdx.y * N + i] = acc;
-}
-template <class FrP>
-__global__ void __launch_bounds__(256) k_r1cs_spmv8_batch(const uint32_t* __restrict__ ptr, const uint32_t* __restrict__ col, const Fp<FrP>* __restrict__ val,
-                                                           const Fp<FrP>* __restrict__ z_all, uint32_t nv, uint32_t n_rows, uint32_t tail, uint32_t N,
-                                                           Fp<FrP>* __restrict__ out_all) {
-    using F = Fp<FrP>;
-    const uint32_t gt = blockIdx.x * blockDim.x + threadIdx.x;
-    const uint32_t i = gt >> 3, j = gt & 7u;
-    if (i >= N) return;  // (N is a multiple of 32: whole groups leave together)
-    const F* z = z_all + (size_t)blockIdx.y * nv;
-    F acc = F::zero();
-    if (i < n_rows) {
-        const uint32_t e = ptr[i + 1];
-        for (uint32_t k = ptr[i] + j; k < e; k += 8) acc = zl::add(acc, zl::mul(val[k], z[col[k]]));
-    } else if (j == 0 && i - n_rows < tail) {
-        acc = z[i - n_rows];
-    }
-#pragma unroll
-    for (int d = 4; d >= 1; d >>= 1) {
-        F o;
-#pragma unroll
-        for (int w = 0; w < F::N; w++) o.l[w] = (uint32_t)__shfl_xor((int)acc.l[w], d, 8);
-        acc = zl::add(acc, o);
-    }
-    if (j == 0) out_all[(size_t)blockIdx.y * N + i] = acc;
-}
 // The three scalar matrices of a chunk, proof v = blockIdx.y (zc canonical, zm Montgomery, h Montgomery as the coset inverse leaves it; r, s canonical):
 //   sa[v] = (1, z_1.., r, 1)   sb[v] = (1, z_1.., s, 1)   sc[v] = (z_w | s z | r z | h[0 .. N - 1) | s | r | r s)
 template <class FrP>
@@ -1010,13 +1061,7 @@ static int g16_batch_queries(zl_ctx* ctx, const zl_g16_pk* pk, const zl_bases* c
         for (zl_bases& b : q) KC::free_bases(b);
     } else if (kc->bq_built && kc.use_count() > 2) {
         // another lane still proves with the queries of another shape: keep them with their object, hang ours on a fresh one
-        auto fresh = std::make_shared<KC>();
-        fresh->key_words = kc->key_words;
-        fresh->alpha1 = kc->alpha1;
-        fresh->beta1 = kc->beta1;
-        fresh->delta1 = kc->delta1;
-        fresh->delta2 = kc->delta2;
-        kc = fresh;
+        kc = kc->fresh_with_tables();
         bs[3]->g16_cache = kc;
     }
     if (!fits(*kc)) {
@@ -1051,11 +1096,11 @@ struct G16BatchSource {
 #define ZL_G16_BATCH_HOST_STAGE ((size_t)64 << 20)  // bytes of host staging the resident loop takes for assignments that are not in host memory
 
 template <class G1, class G2>
-static int groth16_prove_batch_dev_t(zl_ctx* ctx, const zl_g16_pk* pk, const zl_r1cs_dev* cs, const zl_bases* const* bs, unsigned log_n, const G16BatchSource& src,
+static int groth16_prove_batch_dev_t(zl_ctx* ctx, const zl_g16_pk* pk, const zl_r1cs_dev* cs, const zl_bases* const* bs, const G16Shape& sh, const G16BatchSource& src,
                                      unsigned flags, const uint64_t* r, const uint64_t* s, size_t count, zl_g16_proof* proofs) {
     using FrP = typename G1::FrP;
     using Fr = Fp<FrP>;
-    const uint32_t nc = cs->n_constraints, ni = cs->n_instance, nw = cs->n_witness, nv = ni + nw, N = 1u << log_n;
+    const uint32_t ni = sh.ni, nw = sh.nw, nv = sh.nv, N = sh.N;
     std::shared_ptr<G16KeyCache<G1, G2>> kc;
     int rc = g16_batch_queries<G1, G2>(ctx, pk, bs, nv, nw, (size_t)N - 1, &kc);
     if (rc) return rc;
@@ -1077,17 +1122,11 @@ static int groth16_prove_batch_dev_t(zl_ctx* ctx, const zl_g16_pk* pk, const zl_
     Fr* d_sa = d_s + chunk;
     Fr* d_sb = d_sa + chunk * na;
     Fr* d_sc = d_sb + chunk * na;
-    const unsigned char* dm = reinterpret_cast<const unsigned char*>(cs->d_base);
     hipStream_t st = ctx->stream;
     ctx->g16_h = nullptr;  // no single quotient to hand out after a batch
     ctx->g16_h_n = 0;
     const int timing_saved = ctx->timing_on;
     ctx->timing_on = 0;  // the inner calls must not record into the ctx's events
-    Fr g;
-    for (int i = 0; i < Fr::N; i++) g.l[i] = FrP::generator(i);
-    Fr gN = g;
-    for (unsigned i = 0; i < log_n; i++) gN = zl::sqr(gN);
-    const Fr zinv = zl::inv(zl::sub(gN, Fr::one()));
     constexpr size_t W1 = FieldIO<typename G1::F>::WORDS, W2 = FieldIO<typename G2::F>::WORDS;  // u64 words of a canonical G1 / G2 point (2 coordinates of WORDS u32)
     std::vector<uint64_t> xa(chunk * W1), xb(chunk * W2), xc(chunk * W1);
     std::vector<uint8_t> ia(chunk), ib(chunk), ic(chunk);
@@ -1105,29 +1144,9 @@ static int groth16_prove_batch_dev_t(zl_ctx* ctx, const zl_g16_pk* pk, const zl_
             }
             ZL_HIP(ctx, hipMemcpyAsync(d_r, r + c0 * 4, (size_t)ch * 32, hipMemcpyHostToDevice, st));
             ZL_HIP(ctx, hipMemcpyAsync(d_s, s + c0 * 4, (size_t)ch * 32, hipMemcpyHostToDevice, st));
-            if (flags & ZL_MONT) {
-                hipLaunchKernelGGL((k_fr_from_mont<FrP>), dim3((tot_z + 255) / 256), dim3(256), 0, st, d_zm, d_zc, tot_z);
-            } else {
-                ZL_HIP(ctx, hipMemcpyAsync(d_zm, d_zc, (size_t)tot_z * 32, hipMemcpyDeviceToDevice, st));
-                hipLaunchKernelGGL((k_fr_to_mont<FrP>), dim3((tot_z + 255) / 256), dim3(256), 0, st, d_zm, tot_z);
-            }
-            for (int m = 0; m < 3; m++) {
-                Fr* out = d_abc + (size_t)m * ch * N;
-                if (cs->nnz[m] >= (size_t)4 * nc && zl_tune("ZL_TUNE_SPMV8", 1))
-                    hipLaunchKernelGGL((k_r1cs_spmv8_batch<FrP>), dim3((uint32_t)(((uint64_t)N * 8 + 255) / 256), ch), dim3(256), 0, st, (const uint32_t*)(dm + cs->off_ptr[m]),
-                                       (const uint32_t*)(dm + cs->off_col[m]), (const Fr*)(dm + cs->off_val[m]), d_zm, nv, nc, m == 0 ? ni : 0u, N, out);
-                else
-                    hipLaunchKernelGGL((k_r1cs_spmv_batch<FrP>), dim3((N + 255) / 256, ch), dim3(256), 0, st, (const uint32_t*)(dm + cs->off_ptr[m]),
-                                       (const uint32_t*)(dm + cs->off_col[m]), (const Fr*)(dm + cs->off_val[m]), d_zm, nv, nc, m == 0 ? ni : 0u, N, out);
-            }
-            ZL_HIP(ctx, hipGetLastError());
             int e;
-            if ((e = zl_ntt_run_batch(ctx, pk->curve, d_abc, log_n, ZL_MONT | ZL_INVERSE, 3 * ch, (size_t)N * 32))) return e;
-            if ((e = zl_ntt_run_batch(ctx, pk->curve, d_abc, log_n, ZL_MONT | ZL_COSET, 3 * ch, (size_t)N * 32))) return e;
-            const uint32_t tot_n = ch * N;
-            hipLaunchKernelGGL((k_qap_pointwise<FrP>), dim3((tot_n + 255) / 256), dim3(256), 0, st, d_abc, d_abc + (size_t)tot_n, d_abc + 2 * (size_t)tot_n, zinv, tot_n);
-            ZL_HIP(ctx, hipGetLastError());
-            if ((e = zl_ntt_run_batch(ctx, pk->curve, d_abc, log_n, ZL_MONT | ZL_INVERSE | ZL_COSET, ch, (size_t)N * 32))) return e;
+            if ((e = g16_z_forms<FrP>(ctx, d_zc, d_zm, tot_z, flags))) return e;
+            if ((e = g16_witness_map<FrP>(ctx, pk->curve, cs, d_zm, nv, ch, d_abc, sh.log_n))) return e;
             hipLaunchKernelGGL((k_g16_batch_scalars<FrP>), dim3((std::max(nv, N) + 255) / 256, ch), dim3(256), 0, st, d_zc, d_zm, d_abc, d_r, d_s, ni, nv, N, d_sa, d_sb, d_sc);
             ZL_HIP(ctx, hipGetLastError());
             if ((e = ZL_DISPATCH(pk->curve, ZL_G1, zl_msm_multi_run, ctx, kc->bq[0], 0, d_sa, na, na, ch, xa.data(), ia.data()))) return e;
@@ -1155,24 +1174,14 @@ static int groth16_prove_batch_dev_t(zl_ctx* ctx, const zl_g16_pk* pk, const zl_
 template <class G1, class G2>
 static int groth16_prove_batch_t(zl_ctx* ctx, const zl_g16_pk* pk, const zl_r1cs_dev* cs, const G16BatchSource& src, unsigned flags, const uint64_t* r,
                                  const uint64_t* s, size_t count, zl_g16_proof* proofs) {
-    using FrP = typename G1::FrP;
-    // the resident prover's checks, in its order, so that both paths answer a bad key alike
-    const uint32_t nc = cs->n_constraints, ni = cs->n_instance, nw = cs->n_witness;
-    const uint64_t nv64 = (uint64_t)ni + nw;
-    if (ni < 1 || nv64 >= (1ull << 31)) return ZL_EINVAL;
-    const size_t nv = (size_t)nv64;
-    unsigned log_n = 1;
-    while ((1ull << log_n) < (uint64_t)nc + ni) log_n++;
-    if (log_n > (unsigned)FrP::TWO_ADICITY || log_n > 28) return ZL_EINVAL;
-    const uint64_t hs[5] = {pk->a_query, pk->b_g1_query, pk->h_query, pk->l_query, pk->b_g2_query};
+    // the resident prover's checks, so that both paths answer a bad circuit or key alike
+    G16Shape sh;
     const zl_bases* bs[5];
-    for (int i = 0; i < 5; i++) {
-        bs[i] = zl_find_bases(ctx, hs[i]);
-        if (!bs[i] || bs[i]->curve != (int)pk->curve || bs[i]->group != (i == 4 ? ZL_G2 : ZL_G1)) return ZL_EHANDLE;
-    }
-    if (bs[0]->n < nv || bs[1]->n < nv || bs[4]->n < nv || bs[2]->n < ((size_t)1 << log_n) - 1 || bs[3]->n < nw) return ZL_EINVAL;
-    if (log_n <= (unsigned)zl_tune("ZL_TUNE_G16_BATCH_LOG_N", ZL_G16_BATCH_LOG_N) && count >= (size_t)std::max(1, zl_tune("ZL_TUNE_G16_BATCH_MIN", ZL_G16_BATCH_MIN)))
-        return groth16_prove_batch_dev_t<G1, G2>(ctx, pk, cs, bs, log_n, src, flags, r, s, count, proofs);
+    int rc0;
+    if ((rc0 = g16_shape<typename G1::FrP>(cs, &sh)) || (rc0 = g16_key_handles(ctx, pk, sh, bs))) return rc0;
+    const size_t nv = sh.nv;
+    if (sh.log_n <= (unsigned)zl_tune("ZL_TUNE_G16_BATCH_LOG_N", ZL_G16_BATCH_LOG_N) && count >= (size_t)std::max(1, zl_tune("ZL_TUNE_G16_BATCH_MIN", ZL_G16_BATCH_MIN)))
+        return groth16_prove_batch_dev_t<G1, G2>(ctx, pk, cs, bs, sh, src, flags, r, s, count, proofs);
     // The resident prover takes its assignment from host memory: assignments that live on the device, or that a producer makes, come through host staging
     // of at most ZL_G16_BATCH_HOST_STAGE bytes at a time.
     const size_t block = src.host ? count : std::min(count, std::max<size_t>(1, ZL_G16_BATCH_HOST_STAGE / (nv * 32)));
@@ -1204,35 +1213,32 @@ static int groth16_prove_batch_any(zl_ctx* ctx, const zl_g16_pk* pk, const zl_r1
     if (pk->curve == ZL_BN254) return groth16_prove_batch_t<BnG1, BnG2>(ctx, pk, rd, src, flags, r, s, count, proofs);
     return ZL_EINVAL;
 }
+// the assignments of the batch are rows in host or device memory
+static int groth16_prove_batch_rows(zl_ctx* ctx, const zl_g16_pk* pk, uint64_t r1cs_handle, const void* rows, bool on_device, unsigned flags, const uint64_t* r,
+                                    const uint64_t* s, size_t count, zl_g16_proof* proofs) {
+    if (!ctx || !pk || (flags & ~ZL_MONT) || (count && (!rows || !r || !s || !proofs))) return ZL_EINVAL;
+    const zl_r1cs_dev* rd = nullptr;
+    const int rc = g16_entry(ctx, pk, r1cs_handle, &rd);
+    if (rc || count == 0) return rc;
+    G16BatchSource src;
+    (on_device ? src.dev : src.host) = static_cast<const uint64_t*>(rows);
+    return groth16_prove_batch_any(ctx, pk, rd, src, flags, r, s, count, proofs);
+}
 extern "C" int zl_groth16_prove_batch(zl_ctx* ctx, const zl_g16_pk* pk, uint64_t r1cs_handle, const uint64_t* assignments, unsigned flags, const uint64_t* r,
                                       const uint64_t* s, size_t count, zl_g16_proof* proofs) {
-    if (!ctx || !pk || (flags & ~ZL_MONT) || (count && (!assignments || !r || !s || !proofs))) return ZL_EINVAL;
-    if (!pk->alpha_g1 || !pk->beta_g1 || !pk->delta_g1 || !pk->beta_g2 || !pk->delta_g2) return ZL_EINVAL;
-    const zl_r1cs_dev* rd = zl_find_r1cs(ctx, r1cs_handle);
-    if (!rd || rd->curve != (int)pk->curve) return ZL_EHANDLE;
-    if (count == 0) return ZL_OK;
-    G16BatchSource src;
-    src.host = assignments;
-    return groth16_prove_batch_any(ctx, pk, rd, src, flags, r, s, count, proofs);
+    return groth16_prove_batch_rows(ctx, pk, r1cs_handle, assignments, false, flags, r, s, count, proofs);
 }
 extern "C" int zl_groth16_prove_batch_dev(zl_ctx* ctx, const zl_g16_pk* pk, uint64_t r1cs_handle, const void* d_assignments, unsigned flags, const uint64_t* r,
                                           const uint64_t* s, size_t count, zl_g16_proof* proofs) {
-    if (!ctx || !pk || (flags & ~ZL_MONT) || (count && (!d_assignments || !r || !s || !proofs))) return ZL_EINVAL;
-    if (!pk->alpha_g1 || !pk->beta_g1 || !pk->delta_g1 || !pk->beta_g2 || !pk->delta_g2) return ZL_EINVAL;
-    const zl_r1cs_dev* rd = zl_find_r1cs(ctx, r1cs_handle);
-    if (!rd || rd->curve != (int)pk->curve) return ZL_EHANDLE;
-    if (count == 0) return ZL_OK;
-    G16BatchSource src;
-    src.dev = static_cast<const uint64_t*>(d_assignments);
-    return groth16_prove_batch_any(ctx, pk, rd, src, flags, r, s, count, proofs);
+    return groth16_prove_batch_rows(ctx, pk, r1cs_handle, d_assignments, true, flags, r, s, count, proofs);
 }
 extern "C" int zl_groth16_prove_poseidon_chains(zl_ctx* ctx, const zl_g16_pk* pk, uint64_t r1cs_handle, uint32_t k, const uint64_t* x0, const uint64_t* x1, const uint64_t* r,
                                                 const uint64_t* s, size_t count, zl_g16_proof* proofs, uint64_t* public_out) {
     const size_t nv = zl_poseidon_chain_assignment_elems(k);
     if (!ctx || !pk || nv == 0 || (count && (!x0 || !x1 || !r || !s || !proofs))) return ZL_EINVAL;
-    if (!pk->alpha_g1 || !pk->beta_g1 || !pk->delta_g1 || !pk->beta_g2 || !pk->delta_g2) return ZL_EINVAL;
-    const zl_r1cs_dev* rd = zl_find_r1cs(ctx, r1cs_handle);
-    if (!rd || rd->curve != (int)pk->curve) return ZL_EHANDLE;
+    const zl_r1cs_dev* rd = nullptr;
+    const int rc0 = g16_entry(ctx, pk, r1cs_handle, &rd);
+    if (rc0) return rc0;
     if (pk->curve != ZL_BLS12_381 && pk->curve != ZL_BN254) return ZL_EINVAL;
     // the shape of a k-link chain; what the matrices say cannot be checked, as with a witness-only compiler
     if (rd->n_instance != 2 || rd->n_witness != nv - 2 || rd->n_constraints != nv - 3) return ZL_EINVAL;
@@ -1254,9 +1260,9 @@ extern "C" int zl_groth16_prove_poseidon_chains(zl_ctx* ctx, const zl_g16_pk* pk
 static int g16_merkle_checks(zl_ctx* ctx, const zl_g16_pk* pk, uint64_t r1cs_handle, unsigned depth, bool args_ok, const zl_r1cs_dev** rd_out) {
     const size_t nv = zl_poseidon_merkle_assignment_elems(depth);
     if (!ctx || !pk || nv == 0 || !args_ok) return ZL_EINVAL;
-    if (!pk->alpha_g1 || !pk->beta_g1 || !pk->delta_g1 || !pk->beta_g2 || !pk->delta_g2) return ZL_EINVAL;
-    const zl_r1cs_dev* rd = zl_find_r1cs(ctx, r1cs_handle);
-    if (!rd || rd->curve != (int)pk->curve) return ZL_EHANDLE;
+    const zl_r1cs_dev* rd = nullptr;
+    const int rc = g16_entry(ctx, pk, r1cs_handle, &rd);
+    if (rc) return rc;
     if (pk->curve != ZL_BLS12_381 && pk->curve != ZL_BN254) return ZL_EINVAL;
     // the shape of a depth-d membership circuit; what the matrices say cannot be checked, as with a witness-only compiler
     if (rd->n_instance != 2 || rd->n_witness != nv - 2 || rd->n_constraints != nv - 2 - depth) return ZL_EINVAL;
