@@ -758,6 +758,12 @@ class ShardedGroth16Keys:
             self.close()
             raise
 
+    def rank_handles(self, g: int) -> dict:
+        """rank g's shard: {query name: (handle on ranks[g], points in it)} for the queries it holds a slice of (e.g. for ranks[g].bases_precompute)"""
+        sh = self.shards[g]
+        counts = {"a_query": sh.var_count, "b_g1_query": sh.var_count, "h_query": sh.h_count, "l_query": sh.wit_count, "b_g2_query": sh.var_count}
+        return {name: (int(getattr(sh, name)), int(n)) for name, n in counts.items() if n}
+
     def prove(self, assignment: np.ndarray, r: np.ndarray, s: np.ndarray, mont: bool = False):
         proof = G16ProofC()
         z = np.ascontiguousarray(assignment, dtype=np.uint64)

@@ -364,10 +364,14 @@ Result<bool> Groth16<E>::verify(const VerifyingContext& vk, const Input& input, 
 // run on one merged bucket set each.  Measured at N = 2^20 (958 465 constraints): prove 33.5 -> 29.2 ms in round 1 with c = 20 for the G1
 // queries (13 windows) and c = 16 for the G2 query; re-measured in round 3 (19.4 ms): G1 c = 19 / 21 -> 20.9 / 22.6 ms, G2 c = 17 / 18 / 20 -> 19.4 / 19.2 / 20.5;
 // round 5 (18.1 ms, profiles/r05_g16_table_widths.log, two interleaved passes): G1 19 / 21 -> 19.4 / 20.6, G2 17 / 18 / 19 -> 18.4 / 17.9-18.35 / 19.0: the defaults stand.
-// Memory: 13 x 128 B per G1 point, 16 x 256 B per G2 point (about 11 GB for this key).  Small keys stay on the plain path.
+// Memory: 13 x 128 B per G1 point, 16 x 256 B per G2 point (about 11 GB for this key).  Small keys stay on the plain path: a query gets its table from
+// 2^19 points on (ZL_TUNE_G16_TABLE_MIN_LOG: unset, 0 or not a number = 19; any other value clamped to 1 .. 30 -- tests set it low, so that compile and
+// decode build tables for small keys).
 template <class E>
 int Groth16<E>::build_window_tables(const ProvingContext& pc) {
-    const size_t big = (size_t)1 << 19, nv = pc.n_instance + pc.n_witness;
+    const int tuned = zl_tune("ZL_TUNE_G16_TABLE_MIN_LOG", 19);
+    const int min_log = tuned == 0 ? 19 : std::clamp(tuned, 1, 30);
+    const size_t big = (size_t)1 << min_log, nv = pc.n_instance + pc.n_witness;
     const char* e1 = getenv("ZL_TUNE_G1_TABLE_C");
     const char* e2 = getenv("ZL_TUNE_G2_TABLE_C");
     const int c1 = e1 ? atoi(e1) : 20, c2 = e2 ? atoi(e2) : 16;
