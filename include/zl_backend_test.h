@@ -174,6 +174,12 @@ typedef struct zl_test_msm_plan_s {
 } zl_test_msm_plan_t;
 int zl_test_msm_plan(zl_ctx* ctx, uint64_t bases, size_t first, size_t n, zl_test_msm_plan_t* out);
 int zl_test_msm_batch_form(size_t count, uint64_t biggest, int* side, int* lanes, int* phased);
+/* The exact-cover window plan of split BLS12-381 G1 scalars (openzl_amd/csrc/zl_msm_cover_plan.h: widths 22, 21, 21, 21, 21, 22 over 15 sets of 2^19 buckets, the
+ * split inside the recoder), which the planner takes by itself only from 2^24 points on.  mode 1: every following plain BLS12-381 G1 MSM of this ctx (no table, no
+ * forced window, ZL_NO_GLV unset) runs on it whatever its size -- the same kernels and set layout as at 2^24; mode -1: none does; mode 0: the planner decides.
+ * *old_mode (optional) receives the previous mode.  zl_test_msm_plan reports such a plan as glv = 1, c = 20, W = 6, SETS = 15.  ZL_EINVAL for a null ctx or
+ * another mode. */
+int zl_test_msm_exact_cover(zl_ctx* ctx, int mode, int* old_mode);
 
 /* The point decoders behind zl_points_from_bytes_batch (openzl_amd/csrc/zl_decode.h: lane-uniform square roots, sign rule, multiplication by r), compiled
  * for the HOST: arguments, outputs and statuses as zl_points_from_bytes_batch, no ctx.  The device kernels run the same templates. */

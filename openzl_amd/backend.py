@@ -858,7 +858,7 @@ TEST_ABI_SYMBOLS = ["zl_test_poseidon_permute_dev", "zl_test_fp28_op", "zl_test_
                     "zl_test_miller_dev", "zl_test_final_exp", "zl_test_verify_batch_host", "zl_test_ntt_plan", "zl_test_ntt_fit_beside", "zl_test_fp2pair_op", "zl_test_point_form_op",
                     "zl_test_endo_split", "zl_test_endo_split_inf", "zl_test_decode_points_host", "zl_test_fq2_sqrt",
                     "zl_test_final_exp_dev", "zl_test_fq12_inverse", "zl_test_fq12_zeta", "zl_test_pairing_product_scaled",
-                    "zl_test_msm_plan", "zl_test_msm_batch_form"]
+                    "zl_test_msm_plan", "zl_test_msm_batch_form", "zl_test_msm_exact_cover"]
 
 
 def _p32(a: np.ndarray):
@@ -889,6 +889,14 @@ def hook_ntt_fit_beside(be: "Backend", on: bool) -> bool:
     if old < 0:
         raise BackendError(old, "zl_test_ntt_fit_beside")
     return bool(old)
+
+
+def hook_msm_exact_cover(be: "Backend", mode: int) -> int:
+    """force (1), forbid (-1) or leave to the planner (0) the exact-cover plan of BLS12-381 G1 MSMs on this ctx (zl_test_msm_exact_cover); returns the previous mode"""
+    old = C.c_int(0)
+    be.L.zl_test_msm_exact_cover.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_int)]
+    be._check(be.L.zl_test_msm_exact_cover(be._ctx, int(mode), C.byref(old)), "zl_test_msm_exact_cover")
+    return int(old.value)
 
 
 def hook_endo_split(be: "Backend", curve: int, group: int, scalars: np.ndarray, inf: Optional[np.ndarray] = None):

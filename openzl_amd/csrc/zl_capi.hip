@@ -114,6 +114,7 @@ int zl_ctx_fork(zl_ctx* parent, zl_ctx** out) {
     const int rc = zl_ctx_create(&c, parent->device);
     if (rc) return rc;
     c->msm_c = parent->msm_c;
+    c->msm_cover = parent->msm_cover;
     {
         std::unique_lock<std::shared_mutex> lk(parent->maps_mu);  // (two threads may fork one parent at once)
         c->parent = parent;

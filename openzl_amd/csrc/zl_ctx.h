@@ -225,6 +225,7 @@ struct zl_ctx {
     hipStream_t own_stream = nullptr;  // created by the ctx
     int last_hip = 0;
     int msm_c = 0;
+    int msm_cover = 0;  // TEST HOOK (zl_test_msm_exact_cover): > 0 plans BLS12-381 G1 MSMs on the exact-cover plan at any size, < 0 never; 0: the picker (zl_msm_job.h)
     int timing_on = 0;
     zl_timing timing{};
     hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};

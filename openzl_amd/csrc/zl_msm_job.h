@@ -69,6 +69,16 @@ static int zl_pick_window_quarter(size_t n_points) {
     return lg >= 10 && lg <= 18 ? best[lg - 10] : 0;
 }
 
+// The exact-cover plan of split BLS12-381 G1 scalars (zl_msm_cover_plan.h): widths 22, 21, 21, 21, 21, 22 over sets of 2^19 buckets -- what the device sees at
+// c = 20, with 15 sets for 13 and 12 entries per point for 13.  It trades one mixed addition per point for ~0.9 M more live buckets, the split and the sort of
+// 2 n records, which pays only where n entries outweigh them: from 2^ZL_COVER_MIN_LOG points on (profiles/exact_cover_ab.log).
+#ifndef ZL_COVER_MIN_LOG
+#define ZL_COVER_MIN_LOG 24
+#endif
+#define ZL_COVER_SET_LOG 19
+static const uint32_t ZL_COVER_WIDTHS[6] = {22, 21, 21, 21, 21, 22};
+static bool zl_pick_cover(size_t n_points) { return (uint64_t)n_points >= (1ull << ZL_COVER_MIN_LOG); }
+
 static int zl_pick_window_precomp(size_t n, int sc_bits) {
     // merged windows: n*W mixed adds + ONE bucket set of 2^(c-1) buckets (merge + reduce ~6 add-equivalents per bucket)
     // measured at 2^20: c = 16 and c = 20 tie for a single call (4.9 ms), 17..19 are slower (half-filled staging blocks), and inside a
@@ -111,6 +121,8 @@ struct MsmJob {
     int spread_t = -1;  // >= 0: the top window's entries are spread over its bucket set, weights = low spread_t bits + 1
     bool wide = false;  // three-level sort over (window, bucket) ids of up to 23 bits: table mode, or plain windows wider than 16 bits
     bool glv = false;   // the job runs on 2 n_real half-scalars of 127 bits over the points P_i and phi(P_i) (k_glv_split / k_glv_phi)
+    bool cover = false;  // a glv job on an exact-cover plan (cv): W digit rows of unequal widths over SETS uniform sets; the recoder splits, no half-scalar records
+    zl_cover_plan cv;
     bool phi_cached = false;  // d_phi is the handle's own copy (zl_bases::d_endo)
     bool phi_owner = false;  // this job computes the phi image of its bases in its sort phase (else it borrows d_phi from an earlier job of the call)
     int sc_bits = 0, endo_k = 1;  // endo_k: half-scalars per scalar (2: GLV on G1, 4: GLS on G2)
@@ -153,6 +165,7 @@ struct MsmJob {
         // (2^16: 1.07 -> 1.00 ms, 2^18: 1.67 -> 1.63 ms, Groth16 k = 64: 3.8 -> 3.6 ms); from 2^20 on the split, the phi image of the bases
         // (read + write of every point) and the three-level sort of 2 n records cost what the tail saves (2^20: 3.73 = 3.73 ms; 2^24 single
         // call 39.2 -> 39.7 ms, pipelined 36.7 = 36.7), so large inputs keep the plain 255-bit windows.
+        // (That was at EQUAL entry counts, one width for every window.  From 2^24 points on BLS12-381 G1 splits again, on widths that cover the half-scalar exactly: below.)
         static const size_t glv_max = (size_t)1 << zl_tune("ZL_TUNE_GLV_MAX_LOG", 19);
         if constexpr (G::GLV) try_glv = bs.precomp_c == 0 && !no_glv && n_ >= 1 && n_ <= glv_max && (uint64_t)n_ * G::ENDO_K < (1ull << 31);
         // BN254 G1 (round 6: two-dimensional split, k_glv_split_lattice): its host Horner is cheap (254 doublings at 0.3 us) against the split's extra device work (2 n
@@ -175,6 +188,21 @@ struct MsmJob {
                 if (((uint64_t)n_ >= (1ull << ZL_GLS_HOLE_LO_LOG) && (uint64_t)n_ < (1ull << ZL_GLS_HOLE_HI_LOG)) || (uint64_t)n_ >= (1ull << ZL_GLS_END_LOG)) try_glv = false;
             }
         }
+        // BLS12-381 G1 from 2^ZL_COVER_MIN_LOG points on: the split with an exact-cover plan (zl_pick_cover above).  A forced window (zl_ctx_set_msm_window) keeps its
+        // uniform windows; ctx->msm_cover is the tests' switch (zl_test_msm_exact_cover: > 0 the plan at any size, < 0 never).
+        if constexpr (G::GLV && G::ENDO_K == 2) {
+            if constexpr (!G::GLVP::LATTICE) {
+                const bool want = ctx->msm_cover > 0 || (ctx->msm_cover == 0 && zl_pick_cover(n_));
+                if (want && bs.precomp_c == 0 && !no_glv && ctx->msm_c <= 0 && n_ >= 1 && (uint64_t)n_ * 2 * ZL_CV_MAX_WINDOWS < (1ull << 32)) {
+                    int rc = plan_as(ctx, bs, first_, d_scalars, n_, true, true);
+                    if (!rc && cover) {
+                        phi_slot = phi_slot_;
+                        phi_owner = true;
+                        return rc;
+                    }
+                }
+            }
+        }
         int rc = plan_as(ctx, bs, first_, d_scalars, n_, try_glv);
         // (c <= 3: the top window of a 127-bit half-scalar can reach magnitude H + carry; not worth a special case)
         if (!rc && glv && c <= 3) rc = plan_as(ctx, bs, first_, d_scalars, n_, false);
@@ -184,8 +212,21 @@ struct MsmJob {
         phi_owner = glv;
         return rc;
     }
-    int plan_as(zl_ctx* ctx, const zl_bases& bs, size_t first_, const void* d_scalars, size_t n_, bool glv_) {
+    int plan_as(zl_ctx* ctx, const zl_bases& bs, size_t first_, const void* d_scalars, size_t n_, bool glv_, bool cover_ = false) {
         glv = glv_;
+        cover = false;
+        if constexpr (G::GLV && G::ENDO_K == 2) {
+            if constexpr (!G::GLVP::LATTICE) {
+                if (cover_ && glv_ && bs.precomp_c == 0) {
+                    using P = typename G::GLVP;
+                    uint32_t lam[4], bar[8], rm[8];
+                    for (int k = 0; k < 4; k++) lam[k] = P::lambda(k);
+                    for (int k = 0; k < 8; k++) { bar[k] = P::barrett(k); rm[k] = P::rmod(k); }
+                    // the obligations of the plan, from the split's constants: a plan that does not hold is not used
+                    cover = zl_cover_make(cv, ZL_COVER_WIDTHS, 6, ZL_COVER_SET_LOG, lam, bar, rm) == ZL_CV_OK;
+                }
+            }
+        }
         n_real = n_;
         endo_k = glv ? (int)G::ENDO_K : 1;
         n = (size_t)endo_k * n_;
@@ -208,8 +249,12 @@ struct MsmJob {
         if (c < 2) c = 2;
         if (c > 24) c = 24;
         W = (sc_bits + 1 + c - 1) / c;
+        if (cover) {  // W digit rows over SETS uniform sets of 2^set_log buckets: the device's view is that of c = set_log + 1
+            c = (int)cv.set_log + 1;
+            W = (int)cv.windows;
+        }
         H = 1u << (c - 1);
-        SETS = pre ? 1u : (uint32_t)W;  // bucket sets
+        SETS = pre ? 1u : (cover ? cv.nsets : (uint32_t)W);  // bucket sets
         const uint64_t NB64 = (uint64_t)SETS * H;
         maxE = (uint64_t)n * W;
         if (n >= (1ull << 31) || maxE >= (1ull << 32) || NB64 >= (1ull << 31)) return ZL_EINVAL;
@@ -257,7 +302,7 @@ struct MsmJob {
             // low spread_t bits of the bucket index: all of level 0's bits must be on one side of that boundary (a very narrow top
             // window, 0 < spread_t < log2 g0, shortens the level-0 blocks to 2^spread_t)
             spread_t = -1;
-            if ((wide || c <= 16) && !pre) {  // (the global-atomics sort of plain c >= 21 keeps its crowded top window)
+            if ((wide || c <= 16) && !pre && !cover) {  // (an exact-cover plan has no narrow top window; the global-atomics sort of plain c >= 21 keeps its crowded top window)
                 const int top_bits = sc_bits + 1 - (W - 1) * c;  // bits of the top window incl. the carry: magnitudes <= 2^(top_bits - 1)
                 if (top_bits - 1 < c - 1) {
                     spread_t = top_bits - 1;
@@ -302,10 +347,11 @@ struct MsmJob {
             lay.a_bytes = (size_t)n * W * 2 + (size_t)lay.nslices * NB * 4 + 256;  // (the trailing 256 covers the rounding of the digits)
         }  // plain c >= 21 (more than 255 sort groups): the global-atomics sort needs no temporaries
         if (lay.nslices) lay.per_slice = (uint32_t)((n + lay.nslices - 1) / lay.nslices);
-        if (glv) {
+        if (glv && !cover) {  // (an exact-cover plan splits inside its recoder: no half-scalar records)
             lay.vs = up256(lay.a_bytes);
             lay.a_bytes = lay.vs + up256((size_t)n * 32);
         }
+        if (cover && (!wide || Gn != (cv.nsets << (cv.set_log - ZL_CV_GROUP_LOG)) || Gn > 255)) return ZL_EINVAL;  // the recoder's group ids are the sort's (0xFF = zero digit)
         d_bases = pre ? reinterpret_cast<const Affine<F>*>(bs.d_table) : reinterpret_cast<const Affine<F>*>(bs.d_pts) + first;
         d_inf = bs.d_inf ? reinterpret_cast<const uint8_t*>(bs.d_inf) + first : nullptr;
         sc = reinterpret_cast<const uint32_t*>(d_scalars);
@@ -436,7 +482,12 @@ struct MsmJob {
         const uint32_t* sc_eff = sc;
         const uint8_t* inf_eff = d_inf;
         uint32_t* bad_eff = d_bad_scalar;
-        if (glv) {
+        if (cover) {  // the recoder reads the caller's scalars and splits them itself; only the phi image is left of the front end
+            if constexpr (G::GLV && G::ENDO_K == 2) {
+                if (phi_owner)
+                    hipLaunchKernelGGL((k_glv_phi<G>), dim3((uint32_t)((n_real + 127) / 128)), dim3(128), 0, st, d_bases, (uint32_t)n_real, const_cast<Affine<F>*>(d_phi));
+            }
+        } else if (glv) {
             d_vs = reinterpret_cast<uint32_t*>(d_sort_a + lay.vs);
             if constexpr (G::GLV && G::ENDO_K == 2) {
                 if constexpr (G::GLVP::LATTICE)
@@ -482,7 +533,13 @@ struct MsmJob {
         // one atomic per (window, group) it met -- 2048 blocks at 2^24 -- and still one block per 256 scalars below 2^19, where the launch is latency
         const uint32_t span = 256u * std::min<uint32_t>(32u, std::max<uint32_t>(1u, (uint32_t)(n >> 19)));
         (void)hipMemsetAsync(d_pcounts, 0, (size_t)P * 4, st);
-        hipLaunchKernelGGL(k_msm_recode_wide, dim3((per_slice + span - 1) / span, nslices), dim3(256), zl_recode_wide_lds(Gn, (uint32_t)W, pre ? 0u : (H >> 15)), st, sc_eff, (uint32_t)n, c, W, pre ? 0u : (H >> 15), spread_t, glv_i,
+        if (cover) {
+            // blocks over the n_real scalars; a block's records of either half meet at most two slices of the 2 n_real records (zl_msm_sort.h)
+            const uint32_t cspan = nslices > 1 ? std::min<uint32_t>(span, per_slice / 256u * 256u) : span;
+            hipLaunchKernelGGL(k_msm_recode_cover, dim3((uint32_t)((n_real + cspan - 1) / cspan)), dim3(256), zl_recode_cover_lds(Gn), st, sc_eff, (uint32_t)n_real, cv, d_lo16, d_hi8,
+                               d_ones_list, d_ones_count, inf_eff, (int)G::SC_BITS, bad_eff, Gn, per_slice, cspan, nslices, d_pcounts);
+        } else
+        hipLaunchKernelGGL(k_msm_recode_wide,dim3((per_slice + span - 1) / span, nslices), dim3(256), zl_recode_wide_lds(Gn, (uint32_t)W, pre ? 0u : (H >> 15)), st, sc_eff, (uint32_t)n, c, W, pre ? 0u : (H >> 15), spread_t, glv_i,
                            d_lo16, d_hi8, d_ones_list, d_ones_count, inf_eff, sc_bits, bad_eff, Gn, per_slice, span, nslices, d_pcounts);
         hipLaunchKernelGGL(k_scan_block_sums, dim3(pscan_blocks), dim3(SCAN_BLOCK), 0, st, d_pcounts, P, d_pblock);
         hipLaunchKernelGGL(k_scan_top, dim3(1), dim3(1024), 0, st, d_pblock, pscan_blocks, d_poff + P, (const uint32_t*)nullptr);
@@ -684,6 +741,29 @@ struct MsmJob {
         if (parallel && SETS >= 4) zl_pool_get().parallel_for(SETS, [&](size_t w) { V[w] = window_value((int)w); });
         else for (uint32_t w = 0; w < SETS; w++) V[w] = window_value((int)w);
         if (values_us) *values_us = (double)std::chrono::duration_cast<std::chrono::nanoseconds>(std::chrono::steady_clock::now() - t0).count() / 1e3;
+        if (cover) {
+            // Exact-cover plan: set j of window w holds the digits m in (j 2^set_log, (j + 1) 2^set_log] under the weights m - j 2^set_log, so the window sum is
+            // sum_j V_j + 2^set_log sum_j j T_j with T_j the set's total (root channel 0); sum_j j T_j = sum_(i >= 1) sum_(j >= i) T_j costs two additions per set.
+            // The windows then fold high to low, width[w] doublings between window w + 1 and window w.
+            X total = X::inf();
+            for (int w = (int)cv.windows - 1; w >= 0; w--) {
+                if (w != (int)cv.windows - 1) zl::dbl_n(total, (int)cv.width[w]);
+                X run = X::inf(), extra = X::inf(), plain = X::inf();
+                for (int j = (int)cv.sets[w] - 1; j >= 0; j--) {
+                    const uint32_t s = cv.base[w] + (uint32_t)j;
+                    zl::add_full(plain, V[s]);
+                    if (j >= 1) {
+                        zl::add_full(run, hw[(size_t)s * roots_per_set]);
+                        zl::add_full(extra, run);
+                    }
+                }
+                zl::dbl_n(extra, (int)cv.set_log);
+                zl::add_full(total, plain);
+                zl::add_full(total, extra);
+            }
+            zl::add_full(total, hw[(size_t)SETS * roots_per_set]);
+            return total;
+        }
         X total = V[SETS - 1];
         for (int w = (int)SETS - 2; w >= 0; w--) {
             zl::dbl_n(total, c);  // c doublings in Jacobian coordinates

@@ -2,6 +2,7 @@
 // (definitions: zl_msm_sort.hip, compiled ONCE; launched from MsmJob<G>::sort in zl_msm_job.h).
 #pragma once
 #include "zl_msm_common.h"
+#include "zl_msm_cover_plan.h"
 
 #define ZL_PT 4096      // entries of a staged partition tile (k_msm_part_scatter_st / k_msm_sub_scatter_st)
 #define ZL_BT 16384     // entries of a tile of an oversized sub-group (k_msm_fine_sort_big)
@@ -32,6 +33,15 @@ __global__ void __launch_bounds__(256) k_msm_recode_wide(const uint32_t* __restr
                                                                   uint32_t* __restrict__ counts);
 // its dynamic LDS: one counter per group (plain windows, gw > 0) or per (group, window) (a merged set)
 inline size_t zl_recode_wide_lds(uint32_t G, uint32_t W, uint32_t gw) { return (size_t)(gw ? G : G * W) * 4; }
+// the recoder of an exact-cover plan (zl_msm_cover_plan.h): reads the caller's n_real scalars, splits each in registers and writes the digits of both halves
+// (rows of n = 2 n_real codes: half h of scalar i is record i + h n_real); counts the first partition's histogram like k_msm_recode_wide.  span <= per_slice
+// unless nslices == 1.  Dynamic LDS: zl_recode_cover_lds.
+__global__ void __launch_bounds__(256) k_msm_recode_cover(const uint32_t* __restrict__ scalars, uint32_t n_real, zl_cover_plan plan,
+                                                                   uint16_t* __restrict__ lo16, uint8_t* __restrict__ hi8,
+                                                                   uint32_t* __restrict__ ones_list, uint32_t* __restrict__ ones_count, const uint8_t* __restrict__ inf,
+                                                                   int sc_bits, uint32_t* __restrict__ bad, uint32_t G, uint32_t per_slice, uint32_t span, uint32_t nslices,
+                                                                   uint32_t* __restrict__ counts);
+inline size_t zl_recode_cover_lds(uint32_t G) { return (size_t)4 * G * 4; }  // per half, the two slices a block can meet
 __global__ void __launch_bounds__(256) k_msm_sub_hist(const uint16_t* __restrict__ part_lo, const uint32_t* __restrict__ part_off, uint32_t G,
                                                                uint32_t stride, const uint32_t* __restrict__ total, uint32_t fslices,
                                                                uint32_t* __restrict__ counts);

@@ -314,6 +314,81 @@ __global__ void __launch_bounds__(256) k_msm_recode_wide(const uint32_t* __restr
         if (v) atomicAdd(&counts[(size_t)cell * nslices + slice], v);
     }
 }
+// ---- exact-cover plans (zl_msm_cover_plan.h): split in registers, both halves recoded by the lane that read the scalar ------------------------------------
+// What k_glv_split + k_msm_recode_wide do in two passes with 2 n_real 32-byte records between them, in one: block x walks scalars [x span, (x + 1) span); half h of
+// scalar i is record j = i + h n_real of the digit rows, so a block's records of half h lie in at most two slices of the partition (span <= per_slice) and the block keeps one LDS
+// histogram per (half, first / second slice, group).  Codes, zero marker and the counters' order are k_msm_recode_wide's; the bucket id is set << set_log | bucket
+// over the plan's uniform sets.  A top digit outside its live range (impossible for a half within the split's bound) sets bit 1 of *bad and leaves no entry.
+__global__ void __launch_bounds__(256) k_msm_recode_cover(const uint32_t* __restrict__ scalars, uint32_t n_real, zl_cover_plan plan,
+                                                                   uint16_t* __restrict__ lo16, uint8_t* __restrict__ hi8,
+                                                                   uint32_t* __restrict__ ones_list, uint32_t* __restrict__ ones_count, const uint8_t* __restrict__ inf,
+                                                                   int sc_bits, uint32_t* __restrict__ bad, uint32_t G, uint32_t per_slice, uint32_t span, uint32_t nslices,
+                                                                   uint32_t* __restrict__ counts) {
+    ZL_SIDE_PRIO();
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    uint32_t* hist = reinterpret_cast<uint32_t*>(smem);  // [half][first / second slice][group]: zl_recode_cover_lds
+    const uint32_t n = 2u * n_real, cells = 4u * G;
+    for (uint32_t k = threadIdx.x; k < cells; k += blockDim.x) hist[k] = 0;
+    __syncthreads();
+    const uint32_t b0 = min(n_real, blockIdx.x * span), b1 = min(n_real, b0 + span);
+    const uint32_t slice0[2] = {b0 / per_slice, (b0 + n_real) / per_slice};
+    const uint32_t edge[2] = {(slice0[0] + 1u) * per_slice, (slice0[1] + 1u) * per_slice};  // first record of the second slice
+    const uint32_t gshift = plan.set_log - ZL_CV_GROUP_LOG;
+    uint4 nlo = make_uint4(0, 0, 0, 0), nhi = nlo;
+    if (b0 + threadIdx.x < b1) {
+        const uint4* sp = reinterpret_cast<const uint4*>(scalars + (size_t)(b0 + threadIdx.x) * 8);
+        nlo = sp[0]; nhi = sp[1];
+    }
+    for (uint32_t base = b0; base < b1; base += blockDim.x) {  // (uniform bounds: the ballot of zl_take_one sees whole waves)
+        const uint32_t i = base + threadIdx.x;
+        const bool live = i < b1;
+        uint4 lo = nlo, hi = nhi;
+        if (i + blockDim.x < b1) {
+            const uint4* sp = reinterpret_cast<const uint4*>(scalars + (size_t)(i + blockDim.x) * 8);
+            nlo = sp[0]; nhi = sp[1];
+        }
+        if (live) zl_flag_wide_scalar(hi.w, sc_bits, bad);
+        if (!live || (inf && inf[i])) lo = hi = make_uint4(0, 0, 0, 0);  // a base at infinity contributes nothing
+        const uint32_t k[8] = {lo.x, lo.y, lo.z, lo.w, hi.x, hi.y, hi.z, hi.w};
+        uint32_t mag[2][4], sgn[2];
+        zl_cover_split(plan, k, mag[0], mag[1], sgn[0], sgn[1]);
+#pragma unroll
+        for (uint32_t h = 0; h < 2; h++) {
+            const uint32_t j = i + h * n_real;
+            uint32_t rec[8] = {mag[h][0], mag[h][1], mag[h][2], mag[h][3], 0u, 0u, 0u, sgn[h] << 31};
+            if (zl_take_one(rec, j, ones_list, ones_count)) rec[0] = 0;  // a half equal to +1: listed under its record, no digits
+            if (!live) continue;
+            const uint32_t m4[4] = {rec[0], rec[1], rec[2], rec[3]};
+            uint32_t* hh = hist + (h * 2u + (j >= edge[h] ? 1u : 0u)) * G;
+            uint32_t carry = 0;
+#pragma unroll
+            for (uint32_t w = 0; w < ZL_CV_MAX_WINDOWS; w++) {
+                if (w >= plan.windows) break;
+                uint32_t m, ng;
+                zl_cover_digit(plan, m4, sgn[h], w, carry, m, ng);
+                if (w + 1 == plan.windows && !zl_cover_top_ok(plan, m, carry)) {
+                    if (bad) atomicOr(bad, 2u);
+                    m = 0;
+                }
+                uint32_t set = 0, bucket = 0;
+                if (m) zl_cover_place(plan, w, m, set, bucket);
+                const uint32_t g = (set << gshift) | (bucket >> ZL_CV_GROUP_LOG);
+                const bool put = m != 0u && g < G;  // (g < G for every digit the plan admits: the test only states the bound of the LDS index)
+                lo16[(size_t)w * n + j] = (uint16_t)((bucket & 0x7FFFu) | (ng << 15));
+                hi8[(size_t)w * n + j] = put ? (uint8_t)g : (uint8_t)0xFF;
+                if (put) atomicAdd(&hh[g], 1u);
+            }
+        }
+    }
+    __syncthreads();
+    for (uint32_t c = threadIdx.x; c < cells; c += blockDim.x) {
+        const uint32_t v = hist[c];
+        if (!v) continue;
+        const uint32_t h = c / (2u * G), second = (c / G) & 1u, g = c % G;
+        const uint32_t slice = (h ? slice0[1] : slice0[0]) + second, w = zl_cover_window_of_set(plan, g >> gshift);
+        if (slice < nslices) atomicAdd(&counts[((size_t)g * plan.windows + w) * nslices + slice], v);
+    }
+}
 // group range [s, e) from the scanned partition counters
 __device__ __forceinline__ void zl_group_range(const uint32_t* __restrict__ part_off, uint32_t g, uint32_t G, uint32_t stride, uint32_t E, uint32_t& s,
                                                uint32_t& e) {

@@ -913,5 +913,11 @@ int zl_test_ntt_fit_beside(zl_ctx* ctx, int on) {
     ctx->ntt_fit_beside = on ? 1 : 0;
     return old;
 }
+int zl_test_msm_exact_cover(zl_ctx* ctx, int mode, int* old_mode) {
+    if (!ctx || mode < -1 || mode > 1) return ZL_EINVAL;
+    if (old_mode) *old_mode = ctx->msm_cover;
+    ctx->msm_cover = mode;
+    return ZL_OK;
+}
 
 }  // extern "C"
