@@ -148,7 +148,8 @@ int zl_groth16_last_h(zl_ctx* ctx, uint64_t* out, size_t n);
 
 /* ---- host mirror of the plugin interface (C hooks over the C++ classes of openzl_amd/csrc/zl_host.h) ------------
  * openzl::R1CS<F> / poseidon gadget / Groth16<E>::{compile, prove} restated in C++ (the reference is Rust; no Rust
- * toolchain here).  These hooks let a C / ctypes caller drive them; a C++ caller uses the classes directly. */
+ * toolchain here).  These hooks let a C / ctypes caller drive them; a C++ caller uses the classes directly.  Circuits, keys, proving and the wire
+ * formats are implemented in csrc/zl_host.hip; Groth16<E>::verify, zl_pairing*, zl_groth16_verify* in csrc/zl_verify.hip. */
 typedef struct zl_circuit zl_circuit;   /* an R1CS<F> compiler in proof mode holding the config-5 circuit */
 /* k chained Poseidon arity-2 hashes over the curve's Fr: h_1 = H(x0,x1), h_{j+1} = H(h_j,x1), public input h_k */
 int zl_circuit_poseidon_chain(zl_curve_t curve, uint32_t k, const uint64_t* x0, const uint64_t* x1, zl_circuit** out);

@@ -57,7 +57,7 @@ def _digest(paths, extra="") -> str:
 
 
 def _units():
-    units = [("zl_capi", "zl_capi.hip", []), ("zl_ntt", "zl_ntt.hip", ["-DZL_INLINE_MUL"]), ("zl_groth16", "zl_groth16.hip", []), ("zl_host", "zl_host.hip", []), ("zl_testhooks", "zl_testhooks.hip", []), ("zl_multi", "zl_multi.hip", []),
+    units = [("zl_capi", "zl_capi.hip", []), ("zl_ntt", "zl_ntt.hip", ["-DZL_INLINE_MUL"]), ("zl_groth16", "zl_groth16.hip", []), ("zl_host", "zl_host.hip", []), ("zl_verify", "zl_verify.hip", []), ("zl_testhooks", "zl_testhooks.hip", []), ("zl_multi", "zl_multi.hip", []),
              ("zl_msm_sort", "zl_msm_sort.hip", []),  # the curve-independent sort kernels of the MSM: once, not per group
              ("zl_pairing_dev_bls", "zl_pairing_dev.hip", ["-DZL_PAIR_CURVE=1"]), ("zl_pairing_dev_bn", "zl_pairing_dev.hip", ["-DZL_PAIR_CURVE=2"]),  # device Miller loops, once per curve
              ("zl_decode_dev_bls", "zl_decode_dev.hip", ["-DZL_DECODE_CURVE=1"]), ("zl_decode_dev_bn", "zl_decode_dev.hip", ["-DZL_DECODE_CURVE=2"]),  # device point / proof decoders, once per curve
@@ -117,12 +117,12 @@ def build(verbose: bool = True, jobs: int | None = None) -> str:
 
 
 # ---- sanitizer build of the HOST side (VERDICT r4 "next" item 7) -----------------------------------------------------------------------------
-# zl_host.hip holds every parser of untrusted bytes (zl_groth16_keys_from_bytes, zl_point_from_bytes*: zl_serialize.h), the host pairing (zl_pairing.h) and the
-# R1CS / Poseidon / Groth16 mirror; zl_capi.hip the handle and argument checks.  `python -m openzl_amd.build --host-asan` compiles the HOST half of those two
-# units with -fsanitize=address,undefined (device code and every other unit: the product objects) and links libzl_backend.asan.so against the shared ASan
+# zl_host.hip holds every parser of untrusted bytes (zl_groth16_keys_from_bytes, zl_point_from_bytes*: zl_serialize.h) and the R1CS / Poseidon / Groth16 mirror;
+# zl_verify.hip the host pairing (zl_pairing.h) and verification; zl_capi.hip the handle and argument checks.  `python -m openzl_amd.build --host-asan` compiles the
+# HOST half of those three units with -fsanitize=address,undefined (device code and every other unit: the product objects) and links libzl_backend.asan.so against the shared ASan
 # runtime; tests/test_sanitizers.py runs the serialisation / pairing / host-mirror tests (and, on a GPU box, the key-wire corruption fuzz) against it with
 # the runtime preloaded.  Any report aborts the process (-fno-sanitize-recover=all).
-ASAN_UNITS = ("zl_host", "zl_capi")
+ASAN_UNITS = ("zl_host", "zl_verify", "zl_capi")
 ASAN_FLAGS = ["-Xarch_host", "-fsanitize=address,undefined", "-Xarch_host", "-fno-sanitize-recover=all", "-Xarch_host", "-fno-omit-frame-pointer", "-Xarch_host", "-g"]
 ASAN_LIB = os.path.join(HERE, "libzl_backend.asan.so")
 

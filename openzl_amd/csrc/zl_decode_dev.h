@@ -1,4 +1,5 @@
-// zl_decode_dev.h -- internal interface of the device point / proof decoders (zl_decode_dev.hip, compiled once per curve); used by zl_host.hip and zl_testhooks.hip.
+// zl_decode_dev.h -- internal interface of the device point / proof decoders (zl_decode_dev.hip, compiled once per curve); used by zl_host.hip (the batch decoders; zl_verify.hip's bytes-in
+// verifier calls them through zl_groth16_proofs_from_bytes_batch) and zl_testhooks.hip.
 #pragma once
 #include <stddef.h>
 #include <stdint.h>

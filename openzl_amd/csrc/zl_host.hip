@@ -1,5 +1,6 @@
 // zl_host.hip -- implementation of the host-side plugin mirror (zl_host.h) + its C-ABI hooks (include/zl_backend.h,
-// "host mirror" section).  Host code only; compiled by hipcc because it shares zl_field.h with the kernels.
+// "host mirror" section): setup, the circuits, proving, the key / point / proof wire formats.  Verification (Groth16<E>::verify and the pairing entry points) is
+// zl_verify.hip.  Host code only; compiled by hipcc because it shares zl_field.h with the kernels.
 #include <stdlib.h>
 #include <string.h>
 #include <stdio.h>
@@ -8,10 +9,7 @@
 #include <new>
 #include <atomic>
 #include <thread>
-#include <sys/random.h>
-#include "zl_host.h"
-#include "zl_pairing_dev.h"
-#include "zl_fq12_inv.h"
+#include "zl_host_api.h"
 #include "zl_decode_dev.h"
 #include "zl_serialize.h"
 
@@ -311,52 +309,6 @@ Result<std::pair<typename Groth16<E>::ProvingContext, typename Groth16<E>::Verif
     }
     res.ok = true;
     res.value = {pc, vk};
-    return res;
-}
-
-template <class E>
-Result<bool> Groth16<E>::verify(const VerifyingContext& vk, const Input& input, const Proof& proof) {
-    using G1 = typename E::G1;
-    using F1 = typename G1::F;
-    using Eng = openzl::pairing::Engine<typename G1::FqP, typename E::PairingP>;
-    Result<bool> res{false, false, Error{ZL_EINVAL}};
-    const size_t q1 = 2 * G1::FQ64;
-    const size_t ni = vk.gamma_abc_g1.size() / q1;
-    if (ni == 0 || input.size() + 1 != ni) return res;  // ark: wrong number of public inputs -> Err(MalformedVerifyingKey)
-    constexpr int W1 = FieldIO<F1>::WORDS;
-    auto load = [&](const uint64_t* xy) {
-        const uint32_t* w = reinterpret_cast<const uint32_t*>(xy);
-        uint32_t acc = 0;
-        for (int k = 0; k < 2 * W1; k++) acc |= w[k];
-        if (!acc) return XYZZ<F1>::inf();
-        return XYZZ<F1>::from_affine(Affine<F1>{FieldIO<F1>::load_canon(w), FieldIO<F1>::load_canon(w + W1)});
-    };
-    // prepare_inputs: g_ic = gamma_abc[0] + sum_i x_i gamma_abc[i + 1]
-    XYZZ<F1> acc = load(vk.gamma_abc_g1.data());
-    for (size_t i = 0; i < input.size(); i++) {
-        uint32_t k[8];
-        memcpy(k, input[i].l, 32);
-        zl::add_full(acc, zl::mul_scalar(load(vk.gamma_abc_g1.data() + (i + 1) * q1), k));
-    }
-    auto neg_canon = [&](const XYZZ<F1>& p, std::vector<uint64_t>& out) {  // canonical affine of -p
-        out.assign(q1, 0);
-        if (p.is_inf()) return;
-        XYZZ<F1> n = p;
-        zl::neg_inplace(n);
-        const Affine<F1> a = zl::to_affine(n);
-        uint32_t* w = reinterpret_cast<uint32_t*>(out.data());
-        FieldIO<F1>::store_canon(w, a.x);
-        FieldIO<F1>::store_canon(w + W1, a.y);
-    };
-    std::vector<uint64_t> n_alpha, n_acc, n_c;
-    neg_canon(load(vk.alpha_g1.data()), n_alpha);
-    neg_canon(acc, n_acc);
-    neg_canon(load(proof.c), n_c);
-    // e(A, B) e(-alpha, beta) e(-g_ic, gamma) e(-C, delta) == 1, one final exponentiation
-    const auto gt = Eng::multi_pairing({proof.a, n_alpha.data(), n_acc.data(), n_c.data()},
-                                       {proof.b, vk.beta_g2.data(), vk.gamma_g2.data(), vk.delta_g2.data()});
-    res.ok = true;
-    res.value = !proof.a_inf && !proof.b_inf && Eng::eq(gt, Eng::one());
     return res;
 }
 
@@ -725,14 +677,8 @@ static R1CS<FrP> poseidon_merkle(unsigned depth, const Fp<FrP>& leaf_canon, uint
 }  // namespace openzl
 
 // ------------------------------------------------------------------------------------------------ C-ABI hooks
+// (struct zl_circuit and struct zl_g16_keys: zl_host_api.h)
 using namespace openzl;
-struct zl_circuit {
-    zl_curve_t curve;
-    R1CS<BLS12_381_Fr>* bls = nullptr;
-    R1CS<BN254_Fr>* bn = nullptr;
-    R1csExport<BLS12_381_Fr> ex_bls;
-    R1csExport<BN254_Fr> ex_bn;
-};
 // include/zl_backend_test.h: turn the circuit into a DIFFERENT circuit of the same shape (first coefficient of A's row 0 doubled); its
 // cached CSR export is dropped.  A proving context bound to the original circuit must refuse it (R1CS::structure_digest).
 extern "C" int zl_test_circuit_tweak(zl_circuit* c) {
@@ -741,14 +687,6 @@ extern "C" int zl_test_circuit_tweak(zl_circuit* c) {
     if (c->bn) { c->bn->tweak_for_tests(); c->ex_bn = R1csExport<BN254_Fr>(); c->ex_bn.build(*c->bn); }
     return ZL_OK;
 }
-struct zl_g16_keys {
-    zl_curve_t curve;
-    Groth16<Bls12_381>::ProvingContext pc_bls;
-    Groth16<Bn254>::ProvingContext pc_bn;
-    std::vector<uint64_t> gamma_abc;  // exponents, canonical
-    Groth16<Bls12_381>::VerifyingContext vk_bls;
-    Groth16<Bn254>::VerifyingContext vk_bn;
-};
 
 template <class E> static const R1CS<typename E::FrP>* cs_of(const zl_circuit* c);
 template <> const R1CS<BLS12_381_Fr>* cs_of<Bls12_381>(const zl_circuit* c) { return c->bls; }
@@ -1047,340 +985,6 @@ int zl_point_from_bytes_uncompressed(zl_curve_t curve, zl_group_t group, const u
     return group == ZL_G1 ? serialize::BnCodec::g1_from_uncompressed(in, check != 0, xy, inf) : serialize::BnCodec::g2_from_uncompressed(in, check != 0, xy, inf);
 }
 
-// e(P, Q) after the final exponentiation: 12 canonical Fq coefficients of the w-polynomial (tests vs the oracle)
-int zl_pairing(zl_curve_t curve, const uint64_t* p_xy, const uint64_t* q_xy, uint64_t* out12) {
-    if (!p_xy || !q_xy || !out12) return ZL_EINVAL;
-    bool degenerate = false;  // a zero Miller value (inputs that are not points of the pairing groups): ZL_ENOTCURVE instead of a made-up number
-    if (curve == ZL_BLS12_381) { pairing::BlsEngine::store(out12, pairing::BlsEngine::multi_pairing({p_xy}, {q_xy}, &degenerate)); return degenerate ? ZL_ENOTCURVE : ZL_OK; }
-    if (curve == ZL_BN254) { pairing::BnEngine::store(out12, pairing::BnEngine::multi_pairing({p_xy}, {q_xy}, &degenerate)); return degenerate ? ZL_ENOTCURVE : ZL_OK; }
-    return ZL_EINVAL;
-}
-// test hook (include/zl_backend_test.h): prod_i e(P_i, Q_i) through the lock-step Miller loops that Groth16::verify uses for its four pairings
-int zl_test_pairing_product(zl_curve_t curve, size_t n, const uint64_t* ps_xy, const uint64_t* qs_xy, uint64_t* out12) {
-    if (!out12 || ((!ps_xy || !qs_xy) && n) || n > 64) return ZL_EINVAL;
-    if (curve != ZL_BLS12_381 && curve != ZL_BN254) return ZL_EINVAL;
-    const size_t pw = curve == ZL_BLS12_381 ? 12 : 8;  // u64 words of a G1 point; a G2 point has twice as many
-    std::vector<const uint64_t*> ps(n), qs(n);
-    for (size_t i = 0; i < n; i++) { ps[i] = ps_xy + i * pw; qs[i] = qs_xy + i * 2 * pw; }
-    bool degenerate = false;
-    if (curve == ZL_BLS12_381) pairing::BlsEngine::store(out12, pairing::BlsEngine::multi_pairing(ps, qs, &degenerate));
-    else pairing::BnEngine::store(out12, pairing::BnEngine::multi_pairing(ps, qs, &degenerate));
-    return degenerate ? ZL_ENOTCURVE : ZL_OK;
-}
-}  // extern "C"
-
-// ---- device Miller loops + host final exponentiation (zl_pairing_dev.hip) --------------------------------------------------------------------------
-namespace {
-template <class E> struct PairDev;
-template <> struct PairDev<Bls12_381> {
-    static int product(zl_ctx* c, const uint64_t* p, const uint64_t* q, const uint32_t* s, size_t n, uint32_t* o) { return pairing_dev::miller_product_bls(c, p, q, s, n, o); }
-    static int groups(zl_ctx* c, const uint64_t* p, const uint64_t* q, size_t n, size_t g, uint32_t* o) { return pairing_dev::miller_groups_bls(c, p, q, nullptr, n, g, o); }
-    static int groups_fexp(zl_ctx* c, const uint64_t* p, const uint64_t* q, size_t n, size_t g, uint32_t* o, uint8_t* s) { return pairing_dev::pairing_groups_bls(c, p, q, nullptr, n, g, o, s); }
-    static int fexp(zl_ctx* c, const uint32_t* in, size_t n, uint32_t* o, uint8_t* s) { return pairing_dev::final_exp_bls(c, in, n, o, s); }
-};
-template <> struct PairDev<Bn254> {
-    static int product(zl_ctx* c, const uint64_t* p, const uint64_t* q, const uint32_t* s, size_t n, uint32_t* o) { return pairing_dev::miller_product_bn(c, p, q, s, n, o); }
-    static int groups(zl_ctx* c, const uint64_t* p, const uint64_t* q, size_t n, size_t g, uint32_t* o) { return pairing_dev::miller_groups_bn(c, p, q, nullptr, n, g, o); }
-    static int groups_fexp(zl_ctx* c, const uint64_t* p, const uint64_t* q, size_t n, size_t g, uint32_t* o, uint8_t* s) { return pairing_dev::pairing_groups_bn(c, p, q, nullptr, n, g, o, s); }
-    static int fexp(zl_ctx* c, const uint32_t* in, size_t n, uint32_t* o, uint8_t* s) { return pairing_dev::final_exp_bn(c, in, n, o, s); }
-};
-template <class E> using EngOf = pairing::Engine<typename E::G1::FqP, typename E::PairingP>;
-
-template <class E>
-int pairing_product_t(zl_ctx* ctx, const uint64_t* ps, const uint64_t* qs, size_t n, uint64_t* out12) {
-    using Eng = EngOf<E>;
-    typename Eng::Fq12 f;
-    const int rc = PairDev<E>::product(ctx, ps, qs, nullptr, n, reinterpret_cast<uint32_t*>(f.c));
-    if (rc) return rc;
-    bool degenerate = false;
-    Eng::store(out12, Eng::final_exp(f, &degenerate));
-    return degenerate ? ZL_ENOTCURVE : ZL_OK;
-}
-
-// T: the smallest reject-path chunk of verify_batch_t whose final exponentiations run on the device (ZL_TUNE_FEXP_DEV_MIN).  Measured: the smallest power of two
-// from which the device path beat the host threads in every repetition, on both curves (profiles/final_exp_bench.log, the table in DESIGN.md §4.6)
-constexpr int FEXP_DEV_MIN = 128;
-
-// zl_pairing_products: `count` independent products of `each` pairs, Miller loops and final exponentiations on the device
-template <class E>
-int pairing_products_t(zl_ctx* ctx, const uint64_t* ps, const uint64_t* qs, size_t count, size_t each, uint64_t* out12, int32_t* status) {
-    using Eng = EngOf<E>;
-    constexpr size_t q1 = 2 * E::G1::FQ64, q2 = 2 * q1, ow = 6 * q1;  // u64 words of a G1 point, a G2 point, an Fq12 value
-    if (each == 0) {
-        for (size_t j = 0; j < count; j++) {
-            Eng::store(out12 + j * ow, Eng::one());
-            if (status) status[j] = ZL_OK;
-        }
-        return ZL_OK;
-    }
-    // products per launch set: what MAX_PAIRS holds (the final exponentiations of a set run ZL_TUNE_FEXP_CHUNK values per launch inside groups_fexp).  Only a
-    // ZL_TUNE_FEXP_CHUNK that is SET also lowers the products per set, so that tests reach several sets at small counts.
-    const int tune = zl_tune("ZL_TUNE_FEXP_CHUNK", 0);
-    const size_t per = tune >= 1 ? std::min(pairing_dev::MAX_PAIRS / each, (size_t)tune) : pairing_dev::MAX_PAIRS / each;
-    std::vector<typename Eng::Fq12> fs(std::min(per, count));
-    std::vector<uint8_t> sing(fs.size());
-    std::vector<uint64_t> pp, qq;
-    for (size_t first = 0; first < count; first += per) {
-        const size_t m = std::min(per, count - first);
-        // pair i of product j sits at index i * m + j: group j of the launch (pair p belongs to group p % m)
-        pp.resize(m * each * q1);
-        qq.resize(m * each * q2);
-        for (size_t j = 0; j < m; j++)
-            for (size_t i = 0; i < each; i++) {
-                memcpy(&pp[(i * m + j) * q1], ps + ((first + j) * each + i) * q1, q1 * 8);
-                memcpy(&qq[(i * m + j) * q2], qs + ((first + j) * each + i) * q2, q2 * 8);
-            }
-        const int rc = PairDev<E>::groups_fexp(ctx, pp.data(), qq.data(), m * each, m, reinterpret_cast<uint32_t*>(fs.data()), sing.data());
-        if (rc) return rc;
-        for (size_t j = 0; j < m; j++) {
-            Eng::store(out12 + (first + j) * ow, fs[j]);
-            if (status) status[first + j] = sing[j] ? ZL_ENOTCURVE : ZL_OK;
-        }
-    }
-    return ZL_OK;
-}
-
-// The verifying key of a batch, canonical affine points (all-zero = infinity)
-struct BatchVk {
-    const uint64_t *alpha_g1, *beta_g2, *gamma_g2, *delta_g2, *gamma_abc;
-    size_t n_abc;
-};
-
-// Groth16::verify of `count` proofs in one random linear combination (include/zl_backend_ext.h zl_groth16_verify_batch).  ctx == NULL: everything on the
-// host (scalar multiplications, Engine::multi_pairing; the test hook); otherwise rho_i A_i is formed inside the device Miller loops, sum rho_i C_i is a device
-// MSM, the Miller loops run on the device and only the final exponentiation(s) on the host.
-template <class E>
-int verify_batch_t(zl_ctx* ctx, const BatchVk& vk, const uint64_t* pubs, size_t n_public, const zl_g16_proof* proofs, size_t count, const uint64_t* seed,
-                   int* ok, uint8_t* ok_each) {
-    using G1 = typename E::G1;
-    using F1 = typename G1::F;
-    using FrP = typename E::FrP;
-    using Fr = Fp<FrP>;
-    using Eng = EngOf<E>;
-    constexpr size_t q1 = 2 * G1::FQ64, q2 = 2 * q1;
-    constexpr int W1 = FieldIO<F1>::WORDS;
-    if (!ok || (count && !proofs) || (count && n_public && !pubs)) return ZL_EINVAL;
-    if (n_public + 1 != vk.n_abc) return ZL_EINVAL;
-    if (count == 0) {
-        *ok = 1;
-        return ZL_OK;
-    }
-    // rho_i: nonzero 128-bit scalars
-    std::vector<uint64_t> rho(2 * count);
-    if (seed) {
-        SplitMix64 rng(*seed);
-        for (size_t i = 0; i < count; i++)
-            do { rho[2 * i] = rng.next(); rho[2 * i + 1] = rng.next(); } while (!rho[2 * i] && !rho[2 * i + 1]);
-    } else {
-        unsigned char* b = reinterpret_cast<unsigned char*>(rho.data());
-        size_t got = 0;
-        while (got < rho.size() * 8) {
-            const ssize_t r = getrandom(b + got, rho.size() * 8 - got, 0);
-            if (r < 0) {
-                if (errno == EINTR) continue;
-                return ZL_EINVAL;
-            }
-            got += (size_t)r;
-        }
-        for (size_t i = 0; i < count; i++)
-            if (!rho[2 * i] && !rho[2 * i + 1]) rho[2 * i] = 1;
-    }
-    auto load = [&](const uint64_t* xy) {
-        const uint32_t* w = reinterpret_cast<const uint32_t*>(xy);
-        uint32_t acc = 0;
-        for (int k = 0; k < 2 * W1; k++) acc |= w[k];
-        if (!acc) return XYZZ<F1>::inf();
-        return XYZZ<F1>::from_affine(Affine<F1>{FieldIO<F1>::load_canon(w), FieldIO<F1>::load_canon(w + W1)});
-    };
-    auto store = [&](XYZZ<F1> p, bool negate, uint64_t* out) {  // canonical affine of (+/-) p, all-zero for infinity
-        for (size_t k = 0; k < q1; k++) out[k] = 0;
-        if (p.is_inf()) return;
-        if (negate) zl::neg_inplace(p);
-        const Affine<F1> a = zl::to_affine(p);
-        uint32_t* w = reinterpret_cast<uint32_t*>(out);
-        FieldIO<F1>::store_canon(w, a.x);
-        FieldIO<F1>::store_canon(w + W1, a.y);
-    };
-    auto words = [](const Fr& canon, uint32_t* k) { memcpy(k, canon.l, 32); };
-    auto to_fr = [](const uint64_t* w) { Fr c; memcpy(c.l, w, 32); return zl::to_mont(c); };
-    // IC of a combination: sum_j e_j gamma_abc[j] (e_0 multiplies the constant ONE)
-    auto ic_of = [&](const std::vector<Fr>& e) {
-        XYZZ<F1> acc = XYZZ<F1>::inf();
-        for (size_t j = 0; j < vk.n_abc; j++) {
-            uint32_t k[8];
-            words(zl::from_mont(e[j]), k);
-            zl::add_full(acc, zl::mul_scalar(load(vk.gamma_abc + j * q1), k));
-        }
-        return acc;
-    };
-    bool any_inf = false;
-    for (size_t i = 0; i < count; i++) any_inf = any_inf || proofs[i].a_inf || proofs[i].b_inf;
-    // e_j = sum_i rho_i x_ij (x_i0 = 1), sum_i rho_i C_i
-    std::vector<Fr> e(vk.n_abc, Fr::zero()), rf(count);
-    for (size_t i = 0; i < count; i++) {
-        const uint64_t rw[4] = {rho[2 * i], rho[2 * i + 1], 0, 0};
-        rf[i] = to_fr(rw);
-        e[0] = zl::add(e[0], rf[i]);
-        for (size_t j = 0; j < n_public; j++) e[j + 1] = zl::add(e[j + 1], zl::mul(rf[i], to_fr(pubs + (i * n_public + j) * 4)));
-    }
-    XYZZ<F1> sum_c = XYZZ<F1>::inf();
-    if (ctx) {
-        std::vector<uint64_t> cs(count * q1), sc(count * 4, 0);
-        for (size_t i = 0; i < count; i++) {
-            if (!proofs[i].c_inf) memcpy(&cs[i * q1], proofs[i].c, q1 * 8);
-            sc[4 * i] = rho[2 * i];
-            sc[4 * i + 1] = rho[2 * i + 1];
-        }
-        uint64_t h = 0;
-        int rc = zl_bases_upload(ctx, E::curve, ZL_G1, cs.data(), count, 0, -1, 0, &h);
-        std::vector<uint64_t> sxy(q1);
-        uint8_t sinf = 0;
-        if (!rc) rc = zl_msm(ctx, h, 0, sc.data(), count, sxy.data(), &sinf);
-        if (h) (void)zl_bases_free(ctx, h);
-        if (rc) return rc;
-        if (!sinf) sum_c = load(sxy.data());
-    } else {
-        for (size_t i = 0; i < count; i++) {
-            uint32_t k[8] = {0};
-            memcpy(k, &rho[2 * i], 16);
-            zl::add_full(sum_c, zl::mul_scalar(load(proofs[i].c), k));
-        }
-    }
-    // the count + 3 pairs: (rho_i A_i, B_i), (-sum rho_i C_i, delta), (-IC, gamma), (-(sum rho_i) alpha, beta)
-    const size_t np = count + 3;
-    std::vector<uint64_t> ps(np * q1, 0), qs(np * q2, 0);
-    std::vector<uint32_t> sc32;
-    for (size_t i = 0; i < count; i++) {
-        memcpy(&qs[i * q2], proofs[i].b, q2 * 8);
-        if (ctx) {
-            memcpy(&ps[i * q1], proofs[i].a, q1 * 8);
-        } else {
-            uint32_t k[8] = {0};
-            memcpy(k, &rho[2 * i], 16);
-            store(zl::mul_scalar(load(proofs[i].a), k), false, &ps[i * q1]);
-        }
-    }
-    store(sum_c, true, &ps[count * q1]);
-    store(ic_of(e), true, &ps[(count + 1) * q1]);
-    {
-        uint32_t k[8];
-        words(zl::from_mont(e[0]), k);
-        store(zl::mul_scalar(load(vk.alpha_g1), k), true, &ps[(count + 2) * q1]);
-    }
-    memcpy(&qs[count * q2], vk.delta_g2, q2 * 8);
-    memcpy(&qs[(count + 1) * q2], vk.gamma_g2, q2 * 8);
-    memcpy(&qs[(count + 2) * q2], vk.beta_g2, q2 * 8);
-    typename Eng::Fq12 gt;
-    if (ctx) {
-        sc32.assign(np * 4, 0);
-        for (size_t i = 0; i < np; i++) {
-            if (i < count) memcpy(&sc32[4 * i], &rho[2 * i], 16);
-            else sc32[4 * i] = 1;
-        }
-        typename Eng::Fq12 f;
-        const int rc = PairDev<E>::product(ctx, ps.data(), qs.data(), sc32.data(), np, reinterpret_cast<uint32_t*>(f.c));
-        if (rc) return rc;
-        gt = Eng::final_exp(f);
-    } else {
-        std::vector<const uint64_t*> pp(np), qq(np);
-        for (size_t i = 0; i < np; i++) { pp[i] = &ps[i * q1]; qq[i] = &qs[i * q2]; }
-        gt = Eng::multi_pairing(pp, qq);
-    }
-    *ok = !any_inf && Eng::eq(gt, Eng::one()) ? 1 : 0;
-    if (!ok_each) return ZL_OK;
-    if (*ok) {
-        memset(ok_each, 1, count);
-        return ZL_OK;
-    }
-    // rejected: one product of four pairings per proof, e(A, B) e(-C, delta) e(-IC_i, gamma) e(-alpha, beta), as zl_groth16_verify
-    std::vector<uint64_t> n_alpha(q1);
-    store(load(vk.alpha_g1), true, n_alpha.data());
-    // proofs per launch set: what MAX_PAIRS holds; only a ZL_TUNE_PAIR_SET that is SET lowers it (to a quarter of its pairs), the tests' way to several sets
-    const size_t set_pairs = getenv("ZL_TUNE_PAIR_SET") ? pairing_dev::pair_set(zl_tune("ZL_TUNE_PAIR_SET", 0)) : pairing_dev::MAX_PAIRS;
-    const size_t chunk = ctx ? std::max<size_t>(1, set_pairs / 4) : 1;
-    std::vector<typename Eng::Fq12> fs(chunk);
-    for (size_t first = 0; first < count; first += chunk) {
-        const size_t m = std::min(chunk, count - first);
-        // pair j of proof i sits at index j * m + i (group i of the device launch)
-        std::vector<uint64_t> pp(4 * m * q1, 0), qq(4 * m * q2, 0);
-        for (size_t i = 0; i < m; i++) {
-            const zl_g16_proof& pr = proofs[first + i];
-            std::vector<Fr> ei(vk.n_abc);
-            ei[0] = Fr::one();
-            for (size_t j = 0; j < n_public; j++) ei[j + 1] = to_fr(pubs + ((first + i) * n_public + j) * 4);
-            memcpy(&pp[i * q1], pr.a, q1 * 8);
-            memcpy(&qq[i * q2], pr.b, q2 * 8);
-            store(load(pr.c), true, &pp[(m + i) * q1]);
-            memcpy(&qq[(m + i) * q2], vk.delta_g2, q2 * 8);
-            store(ic_of(ei), true, &pp[(2 * m + i) * q1]);
-            memcpy(&qq[(2 * m + i) * q2], vk.gamma_g2, q2 * 8);
-            memcpy(&pp[(3 * m + i) * q1], n_alpha.data(), q1 * 8);
-            memcpy(&qq[(3 * m + i) * q2], vk.beta_g2, q2 * 8);
-        }
-        // a chunk of at least ZL_TUNE_FEXP_DEV_MIN proofs takes its final exponentiations on the device too: the Miller values never come to the host
-        const int dev_min = zl_tune("ZL_TUNE_FEXP_DEV_MIN", FEXP_DEV_MIN);
-        if (ctx && m >= (size_t)(dev_min < 1 ? 1 : dev_min)) {
-            // no singular flags: a zero Miller product (points outside the pairing groups) comes out as 0, which is not one -- rejected, as the host path does
-            const int rc = PairDev<E>::groups_fexp(ctx, pp.data(), qq.data(), 4 * m, m, reinterpret_cast<uint32_t*>(fs.data()), nullptr);
-            if (rc) return rc;
-            for (size_t i = 0; i < m; i++) {
-                const zl_g16_proof& pr = proofs[first + i];
-                ok_each[first + i] = !pr.a_inf && !pr.b_inf && Eng::eq(fs[i], Eng::one()) ? 1 : 0;
-            }
-            continue;
-        }
-        if (ctx) {
-            const int rc = PairDev<E>::groups(ctx, pp.data(), qq.data(), 4 * m, m, reinterpret_cast<uint32_t*>(fs.data()));
-            if (rc) return rc;
-        }
-        // the final exponentiations (and, for the host hook, the Miller loops) of the proofs of this chunk on a few host threads
-        std::atomic<size_t> next{0};
-        auto work = [&]() {
-            for (size_t i; (i = next.fetch_add(1)) < m;) {
-                typename Eng::Fq12 g;
-                if (ctx) {
-                    g = Eng::final_exp(fs[i]);
-                } else {
-                    std::vector<const uint64_t*> a(4), b(4);
-                    for (int j = 0; j < 4; j++) { a[j] = &pp[(j * m + i) * q1]; b[j] = &qq[(j * m + i) * q2]; }
-                    g = Eng::multi_pairing(a, b);
-                }
-                const zl_g16_proof& pr = proofs[first + i];
-                ok_each[first + i] = !pr.a_inf && !pr.b_inf && Eng::eq(g, Eng::one()) ? 1 : 0;
-            }
-        };
-        const size_t nt = std::min<size_t>(m, std::max(1u, std::min(16u, std::thread::hardware_concurrency())));
-        std::vector<std::thread> th;
-        for (size_t t = 1; t < nt; t++) th.emplace_back(work);
-        work();
-        for (auto& t : th) t.join();
-    }
-    return ZL_OK;
-}
-}  // namespace
-
-extern "C" {
-int zl_pairing_product(zl_ctx* ctx, zl_curve_t curve, const uint64_t* ps_xy, const uint64_t* qs_xy, size_t n, uint64_t* out12) {
-    if (!ctx || !out12 || (n && (!ps_xy || !qs_xy))) return ZL_EINVAL;
-    if (curve == ZL_BLS12_381) return pairing_product_t<Bls12_381>(ctx, ps_xy, qs_xy, n, out12);
-    if (curve == ZL_BN254) return pairing_product_t<Bn254>(ctx, ps_xy, qs_xy, n, out12);
-    return ZL_EINVAL;
-}
-int zl_pairing_products(zl_ctx* ctx, zl_curve_t curve, const uint64_t* ps_xy, const uint64_t* qs_xy, size_t count, size_t pairs_each, uint64_t* out12,
-                        int32_t* status) {
-    if (!ctx || (curve != ZL_BLS12_381 && curve != ZL_BN254) || pairs_each > pairing_dev::MAX_PAIRS) return ZL_EINVAL;
-    if (count == 0) return ZL_OK;
-    if (!out12 || (pairs_each && (!ps_xy || !qs_xy))) return ZL_EINVAL;
-    if (curve == ZL_BLS12_381) return pairing_products_t<Bls12_381>(ctx, ps_xy, qs_xy, count, pairs_each, out12, status);
-    return pairing_products_t<Bn254>(ctx, ps_xy, qs_xy, count, pairs_each, out12, status);
-}
-int zl_groth16_verify_batch(zl_ctx* ctx, const zl_g16_keys* k, const uint64_t* public_inputs, size_t n_public, const zl_g16_proof* proofs, size_t count,
-                            const uint64_t* seed, int* ok, uint8_t* ok_each) {
-    if (!ctx || !k) return ZL_EINVAL;
-    auto vk_of = [](const auto& v, size_t q1) { return BatchVk{v.alpha_g1.data(), v.beta_g2.data(), v.gamma_g2.data(), v.delta_g2.data(), v.gamma_abc_g1.data(), v.gamma_abc_g1.size() / q1}; };
-    if (k->curve == ZL_BLS12_381) return verify_batch_t<Bls12_381>(ctx, vk_of(k->vk_bls, 12), public_inputs, n_public, proofs, count, seed, ok, ok_each);
-    return verify_batch_t<Bn254>(ctx, vk_of(k->vk_bn, 8), public_inputs, n_public, proofs, count, seed, ok, ok_each);
-}
 // ---- wire proofs and points decoded on the device (zl_decode_dev.hip) ---------------------------------------------------------------------------------
 int zl_points_from_bytes_batch(zl_ctx* ctx, zl_curve_t curve, zl_group_t group, const uint8_t* in, size_t count, uint64_t* out_xy, uint8_t* out_inf,
                                int32_t* status) {
@@ -1391,157 +995,6 @@ int zl_groth16_proofs_from_bytes_batch(zl_ctx* ctx, zl_curve_t curve, const uint
     if (!ctx || !zl_groth16_proof_bytes(curve)) return ZL_EINVAL;
     return curve == ZL_BLS12_381 ? decode_dev::proofs_bls(ctx, in, count, proofs, status) : decode_dev::proofs_bn(ctx, in, count, proofs, status);
 }
-int zl_groth16_verify_batch_bytes(zl_ctx* ctx, const zl_g16_keys* k, const uint64_t* public_inputs, size_t n_public, const uint8_t* proofs_bytes, size_t count,
-                                  const uint64_t* seed, int* ok, uint8_t* ok_each, int32_t* status) {
-    if (!ctx || !k || !ok || (count && !proofs_bytes) || (count && n_public && !public_inputs)) return ZL_EINVAL;
-    const size_t n_abc = k->curve == ZL_BLS12_381 ? k->vk_bls.gamma_abc_g1.size() / 12 : k->vk_bn.gamma_abc_g1.size() / 8;
-    if (n_public + 1 != n_abc) return ZL_EINVAL;  // before any work, as zl_groth16_verify_batch
-    // decode -> host structs -> the existing combination over the proofs that decoded, with their public inputs
-    std::vector<zl_g16_proof> proofs(count);
-    std::vector<int32_t> st(count);
-    int rc = zl_groth16_proofs_from_bytes_batch(ctx, (zl_curve_t)k->curve, proofs_bytes, count, proofs.data(), st.data());
-    if (rc) return rc;
-    std::vector<size_t> live;
-    for (size_t i = 0; i < count; i++)
-        if (st[i] == ZL_OK) live.push_back(i);
-    if (live.size() != count) {
-        for (size_t j = 0; j < live.size(); j++) proofs[j] = proofs[live[j]];
-    }
-    std::vector<uint64_t> pubs;
-    const uint64_t* pp = public_inputs;
-    if (live.size() != count && n_public) {
-        pubs.resize(live.size() * n_public * 4);
-        for (size_t j = 0; j < live.size(); j++) memcpy(&pubs[j * n_public * 4], public_inputs + live[j] * n_public * 4, n_public * 32);
-        pp = pubs.data();
-    }
-    std::vector<uint8_t> each(ok_each ? live.size() : 0);
-    int vok = 0;
-    rc = zl_groth16_verify_batch(ctx, k, pp, n_public, proofs.data(), live.size(), seed, &vok, ok_each ? each.data() : nullptr);
-    if (rc) return rc;
-    *ok = vok && live.size() == count ? 1 : 0;
-    if (ok_each) {
-        memset(ok_each, 0, count);
-        for (size_t j = 0; j < live.size(); j++) ok_each[live[j]] = each[j];
-    }
-    if (status) memcpy(status, st.data(), count * sizeof(int32_t));
-    return ZL_OK;
-}
-// test hooks (include/zl_backend_test.h)
-int zl_test_verify_batch_host(zl_curve_t curve, const uint64_t* alpha_g1, const uint64_t* beta_g2, const uint64_t* gamma_g2, const uint64_t* delta_g2,
-                              const uint64_t* gamma_abc, size_t n_public, const zl_g16_proof* proofs, const uint64_t* public_inputs, size_t count,
-                              const uint64_t* seed, int* ok, uint8_t* ok_each) {
-    if (!alpha_g1 || !beta_g2 || !gamma_g2 || !delta_g2 || !gamma_abc) return ZL_EINVAL;
-    const BatchVk vk{alpha_g1, beta_g2, gamma_g2, delta_g2, gamma_abc, n_public + 1};
-    if (curve == ZL_BLS12_381) return verify_batch_t<Bls12_381>(nullptr, vk, public_inputs, n_public, proofs, count, seed, ok, ok_each);
-    if (curve == ZL_BN254) return verify_batch_t<Bn254>(nullptr, vk, public_inputs, n_public, proofs, count, seed, ok, ok_each);
-    return ZL_EINVAL;
-}
-int zl_test_miller_dev(zl_ctx* ctx, zl_curve_t curve, size_t n, const uint64_t* ps_xy, const uint64_t* qs_xy, uint64_t* out) {
-    if (!ctx || (n && (!ps_xy || !qs_xy || !out)) || (curve != ZL_BLS12_381 && curve != ZL_BN254)) return ZL_EINVAL;
-    const size_t fw = curve == ZL_BLS12_381 ? 6 : 4;  // u64 words per Fq
-    for (size_t first = 0; first < n; first += pairing_dev::MAX_PAIRS) {
-        const size_t m = std::min(n - first, pairing_dev::MAX_PAIRS);
-        uint64_t* o = out + first * 12 * fw;
-        const uint64_t *p = ps_xy + first * 2 * fw, *q = qs_xy + first * 4 * fw;
-        const int rc = curve == ZL_BLS12_381 ? PairDev<Bls12_381>::groups(ctx, p, q, m, m, reinterpret_cast<uint32_t*>(o))
-                                             : PairDev<Bn254>::groups(ctx, p, q, m, m, reinterpret_cast<uint32_t*>(o));
-        if (rc) return rc;
-        for (size_t i = 0; i < m * 12; i++) {  // Montgomery -> canonical
-            if (curve == ZL_BLS12_381) { Fp<BLS12_381_Fq> c; memcpy(c.l, o + i * fw, 48); c = zl::from_mont(c); memcpy(o + i * fw, c.l, 48); }
-            else { Fp<BN254_Fq> c; memcpy(c.l, o + i * fw, 32); c = zl::from_mont(c); memcpy(o + i * fw, c.l, 32); }
-        }
-    }
-    return ZL_OK;
-}
-int zl_test_pairing_product_scaled(zl_ctx* ctx, zl_curve_t curve, size_t n, const uint64_t* ps_xy, const uint64_t* qs_xy, const uint64_t* scalars128, uint64_t* out12) {
-    if (!ctx || !out12 || (n && (!ps_xy || !qs_xy)) || (curve != ZL_BLS12_381 && curve != ZL_BN254)) return ZL_EINVAL;
-    auto run = [&](auto e) {
-        using E = decltype(e);
-        using Eng = EngOf<E>;
-        typename Eng::Fq12 f;
-        const int rc = PairDev<E>::product(ctx, ps_xy, qs_xy, reinterpret_cast<const uint32_t*>(scalars128), n, reinterpret_cast<uint32_t*>(f.c));
-        if (rc) return rc;
-        bool degenerate = false;
-        Eng::store(out12, Eng::final_exp(f, &degenerate));
-        return degenerate ? (int)ZL_ENOTCURVE : (int)ZL_OK;
-    };
-    return curve == ZL_BLS12_381 ? run(Bls12_381{}) : run(Bn254{});
-}
-int zl_test_final_exp(zl_curve_t curve, const uint64_t* in12, uint64_t* out12) {
-    if (!in12 || !out12) return ZL_EINVAL;
-    auto run = [&](auto eng) {
-        using Eng = decltype(eng);
-        typename Eng::Fq12 f;
-        for (int i = 0; i < 12; i++) {
-            memcpy(f.c[i].l, reinterpret_cast<const unsigned char*>(in12) + i * sizeof(f.c[i]), sizeof(f.c[i]));
-            f.c[i] = zl::to_mont(f.c[i]);
-        }
-        bool degenerate = false;
-        Eng::store(out12, Eng::final_exp(f, &degenerate));
-        return degenerate ? ZL_ENOTCURVE : ZL_OK;
-    };
-    if (curve == ZL_BLS12_381) return run(pairing::BlsEngine{});
-    if (curve == ZL_BN254) return run(pairing::BnEngine{});
-    return ZL_EINVAL;
-}
-int zl_test_final_exp_dev(zl_ctx* ctx, zl_curve_t curve, size_t count, const uint64_t* in, uint64_t* out, uint8_t* singular) {
-    if (!ctx || (count && (!in || !out)) || (curve != ZL_BLS12_381 && curve != ZL_BN254)) return ZL_EINVAL;
-    auto run = [&](auto e) {
-        using E = decltype(e);
-        using F = Fp<typename E::G1::FqP>;
-        std::vector<F> v(count * 12);
-        memcpy(static_cast<void*>(v.data()), in, v.size() * sizeof(F));
-        for (auto& c : v) c = zl::to_mont(c);
-        const int rc = PairDev<E>::fexp(ctx, reinterpret_cast<const uint32_t*>(v.data()), count, reinterpret_cast<uint32_t*>(v.data()), singular);
-        if (rc) return rc;
-        for (auto& c : v) c = zl::from_mont(c);
-        memcpy(out, v.data(), v.size() * sizeof(F));
-        return (int)ZL_OK;
-    };
-    return curve == ZL_BLS12_381 ? run(Bls12_381{}) : run(Bn254{});
-}
-int zl_test_fq12_inverse(zl_curve_t curve, const uint64_t* in12, uint64_t* out12, uint8_t* singular) {
-    if (!in12 || !out12 || !singular || (curve != ZL_BLS12_381 && curve != ZL_BN254)) return ZL_EINVAL;
-    auto run = [&](auto fq, auto pp) {
-        using FqP = decltype(fq);
-        using PP = decltype(pp);
-        fq12inv::El<FqP> f;
-        memcpy(static_cast<void*>(f.c), in12, sizeof f.c);
-        for (auto& c : f.c) c = zl::to_mont(c);
-        bool sing = false;
-        fq12inv::El<FqP> g = fq12inv::inverse<FqP, PP>(f, &sing);
-        for (auto& c : g.c) c = zl::from_mont(c);
-        memcpy(out12, g.c, sizeof g.c);
-        *singular = sing ? 1 : 0;
-        return (int)ZL_OK;
-    };
-    return curve == ZL_BLS12_381 ? run(BLS12_381_Fq{}, BLS12_381_Pairing{}) : run(BN254_Fq{}, BN254_Pairing{});
-}
-int zl_test_fq12_zeta(zl_curve_t curve, uint64_t* out) {
-    if (!out || (curve != ZL_BLS12_381 && curve != ZL_BN254)) return ZL_EINVAL;
-    if (curve == ZL_BLS12_381) { const auto z = zl::from_mont(fq12inv::zeta<BLS12_381_Fq>()); memcpy(out, z.l, sizeof z.l); }
-    else { const auto z = zl::from_mont(fq12inv::zeta<BN254_Fq>()); memcpy(out, z.l, sizeof z.l); }
-    return ZL_OK;
-}
-// Groth16::verify: public_inputs = n x 4 u64 canonical (without the leading ONE); *ok = 1 / 0
-int zl_groth16_verify(const zl_g16_keys* k, const uint64_t* public_inputs, size_t n, const zl_g16_proof* proof, int* ok) {
-    if (!k || !proof || !ok || (!public_inputs && n)) return ZL_EINVAL;
-    if (k->curve == ZL_BLS12_381) {
-        std::vector<Fp<BLS12_381_Fr>> in(n);
-        for (size_t i = 0; i < n; i++) memcpy(in[i].l, public_inputs + 4 * i, 32);
-        auto r = Groth16<Bls12_381>::verify(k->vk_bls, in, *proof);
-        if (!r.ok) return r.error.code;
-        *ok = r.value ? 1 : 0;
-    } else {
-        std::vector<Fp<BN254_Fr>> in(n);
-        for (size_t i = 0; i < n; i++) memcpy(in[i].l, public_inputs + 4 * i, 32);
-        auto r = Groth16<Bn254>::verify(k->vk_bn, in, *proof);
-        if (!r.ok) return r.error.code;
-        *ok = r.value ? 1 : 0;
-    }
-    return ZL_OK;
-}
-
 // ---- wire formats (arkworks CanonicalSerialize, compressed; zl_serialize.h) -----------------------------------------------------
 size_t zl_point_bytes(zl_curve_t curve, zl_group_t group) {
     if ((curve != ZL_BLS12_381 && curve != ZL_BN254) || (group != ZL_G1 && group != ZL_G2)) return 0;

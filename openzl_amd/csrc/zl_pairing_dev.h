@@ -1,4 +1,4 @@
-// zl_pairing_dev.h -- internal interface of the device Miller loops (zl_pairing_dev.hip, compiled once per curve); used by zl_host.hip.
+// zl_pairing_dev.h -- internal interface of the device Miller loops (zl_pairing_dev.hip, compiled once per curve); used by zl_verify.hip.
 #pragma once
 #include <stddef.h>
 #include <stdint.h>

@@ -1,7 +1,7 @@
 // zl_pairing_dev.hip -- Miller loops of many pairings on the device (the product side of PairingEngine::product_of_pairings, which the plugin's
 // PairingEngineExt helpers and Groth16 verification call: the reference plugin's plugins/arkworks/src/pairing.rs:47-90, groth16.rs:459-466).
 // Compiled once per curve (ZL_PAIR_CURVE = 1 BLS12-381, 2 BN254); the host final exponentiation (zl_pairing.h Engine::final_exp) turns the
-// product into the pairing (zl_host.hip: zl_pairing_product, zl_groth16_verify_batch).
+// product into the pairing (zl_verify.hip: zl_pairing_product, zl_groth16_verify_batch).
 //
 // Same Fq12 as zl_pairing.h: Fq[w]/(w^12 - M6 w^6 + M0_NEG), 12 Fq coefficients, the same loop schedule (LOOP_BITS / loop_bit, BN_TAIL lines) and the same
 // line placement (put_fq2; TWIST_DIV: BLS12-381 M-type twist).  Differences to the host loop, all annihilated by the final exponentiation (q^12 - 1)/r:

@@ -1,5 +1,7 @@
 // zl_testhooks.hip -- the TEST-ONLY hooks declared in include/zl_backend_test.h: device Poseidon known-answer run, raw-limb access to the
-// lazily reduced 28-bit field and to the point formulas (host and device).  Nothing in the product path calls into this file.
+// lazily reduced 28-bit field and to the point formulas (host and device).  Nothing in the product path calls into this file.  The pairing and
+// verification hooks (zl_test_miller_dev, zl_test_final_exp*, zl_test_fq12_*, zl_test_pairing_product*, zl_test_verify_batch_host) need the templates
+// of zl_verify.hip and are the last section of that file; zl_test_circuit_tweak is with the circuits in zl_host.hip.
 #include <string.h>
 #include <type_traits>
 #include <vector>

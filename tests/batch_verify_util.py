@@ -89,6 +89,13 @@ def tampered(curve, proofs, pubs, how: str):
         p1[1] = 1
         proofs[1] = tuple(p1)
         return proofs, pubs, {1}
+    if how in ("b_inf", "c_inf"):  # the point as a decoder hands over infinity: all-zero words and the flag
+        p1 = list(proofs[1])
+        at = 2 if how == "b_inf" else 4
+        p1[at] = np.zeros_like(p1[at])
+        p1[at + 1] = 1
+        proofs[1] = tuple(p1)
+        return proofs, pubs, {1}
     if how == "offcurve_b":
         p1 = list(proofs[1])
         b = p1[2].copy()
@@ -100,3 +107,4 @@ def tampered(curve, proofs, pubs, how: str):
 
 
 TAMPER_CASES = ["public", "swap_c", "neg_b", "a_inf"]
+INF_CASES = ["b_inf", "c_inf"]  # B at infinity is invalid by rule, C at infinity by the pairing equation

@@ -1,12 +1,14 @@
 """Rejected batches of zl_groth16_verify_batch with per-proof verdicts from DEVICE final exponentiations (ZL_TUNE_FEXP_DEV_MIN = 1, three values per launch):
 235-constraint Poseidon proofs in batches of 5, 64 and 70 with the first, the last or several proofs tampered (A taken from another proof, a wrong C, a wrong
 public input, A at infinity).  The verdicts equal the host implementation of the same batch (zl_test_verify_batch_host), the host-thread path of the same
-entry point (ZL_TUNE_FEXP_DEV_MIN very large) and the set of tampered indices; once through the bytes-in verifier."""
+entry point (ZL_TUNE_FEXP_DEV_MIN very large) and the set of tampered indices; once through the bytes-in verifier.  B or C at infinity (zero words and
+the flag) on each of those paths and over several launch sets (ZL_TUNE_PAIR_SET), and a rejected batch under a combination drawn from the OS."""
 import os
 
 import numpy as np
 import pytest
 
+import batch_verify_util as bv
 import groth16_util as gu
 import oracle_lib as ol
 from oracle_lib import po
@@ -58,7 +60,10 @@ def _tamper(proofs, pubs, plan):
 
 
 def _with_env(dev_min, chunk, fn):
-    names = {"ZL_TUNE_FEXP_DEV_MIN": dev_min, "ZL_TUNE_FEXP_CHUNK": chunk}
+    return _with_vars({"ZL_TUNE_FEXP_DEV_MIN": dev_min, "ZL_TUNE_FEXP_CHUNK": chunk}, fn)
+
+
+def _with_vars(names, fn):
     old = {k: os.environ.get(k) for k in names}
     try:
         for k, v in names.items():
@@ -93,6 +98,32 @@ def test_device_verdicts_equal_the_host(poseidon, count, plan):
     assert each.tobytes() == heach.tobytes()
     ok2, each2 = _with_env(HOST_ONLY, 3, lambda: keys.verify_batch(bad, bpubs, seed=13, each=True))
     assert ok2 is False and each2.tobytes() == each.tobytes()
+
+
+@pytest.mark.parametrize("how", bv.INF_CASES)
+def test_b_or_c_at_infinity_rejects_that_proof_on_every_path(poseidon, how):
+    """B or C of one proof of three as a decoder hands over infinity (zero words, flag set): device final exponentiations, host threads, and two launch
+    sets of the combined product with one proof per reject-path set; the verdicts are the host implementation's and zl_groth16_verify's"""
+    curve, keys, proofs, pub, vk = poseidon
+    bad, bpubs, idx = bv.tampered(curve, proofs[:3], np.tile(pub[None], (3, 1, 1)), how)
+    expected = [i not in idx for i in range(3)]
+    hok, heach = hook_verify_batch_host(curve.cid, vk, bad, bpubs, 1, seed=17)
+    assert hok is False and [bool(e) for e in heach] == expected
+    assert [keys.verify(bad[i], bpubs[i]) for i in range(3)] == expected
+    for env in ({"ZL_TUNE_FEXP_DEV_MIN": 1}, {"ZL_TUNE_FEXP_DEV_MIN": HOST_ONLY}, {"ZL_TUNE_PAIR_SET": 4}):
+        ok, each = _with_vars(env, lambda: keys.verify_batch(bad, bpubs, seed=17, each=True))
+        assert ok is False, env
+        assert each.tobytes() == heach.tobytes(), env
+
+
+def test_combination_drawn_from_the_os_rejects_with_exact_verdicts(poseidon):
+    """no seed: rho comes from getrandom.  No tolerance: a 128-bit combination accepts a bad batch with probability 2^-128, and the per-proof verdicts
+    do not depend on rho at all"""
+    curve, keys, proofs, pub, vk = poseidon
+    bad, bpubs = _tamper(proofs[:5], np.tile(pub[None], (5, 1, 1)), {2: "public"})
+    ok, each = keys.verify_batch(bad, bpubs, each=True)
+    assert ok is False
+    assert [bool(e) for e in each] == [i != 2 for i in range(5)]
 
 
 def test_bytes_in_verifier_takes_the_device_path(poseidon):

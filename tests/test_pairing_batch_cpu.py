@@ -35,7 +35,7 @@ def test_host_batch_accepts_valid_batches(curve, kind):
 
 
 @pytest.mark.parametrize("curve", CURVES, ids=lambda c: c.name)
-@pytest.mark.parametrize("how", bv.TAMPER_CASES)
+@pytest.mark.parametrize("how", bv.TAMPER_CASES + bv.INF_CASES)
 def test_host_batch_rejects_tampering_with_per_proof_verdicts(curve, how):
     case, proofs = _case(curve, "poseidon")
     bad, pubs, idx = bv.tampered(curve, proofs[:3], case.pubs(3), how)
@@ -47,6 +47,17 @@ def test_host_batch_rejects_tampering_with_per_proof_verdicts(curve, how):
     # the verdicts do not depend on the combination's seed
     ok2, each2 = _run(case, bad, pubs, seed=0xDEADBEEF)
     assert ok2 == ok and (each2 == each).all()
+
+
+@pytest.mark.parametrize("curve", CURVES, ids=lambda c: c.name)
+def test_host_batch_rejects_under_a_combination_drawn_from_the_os(curve):
+    """no seed: rho comes from getrandom.  No tolerance: a 128-bit combination accepts a bad batch with probability 2^-128, and the per-proof verdicts
+    do not depend on rho at all"""
+    case, proofs = _case(curve, "poseidon")
+    bad, pubs, idx = bv.tampered(curve, proofs[:5], case.pubs(5), "public")
+    ok, each = _run(case, bad, pubs, seed=None)
+    assert not ok
+    assert [bool(e) for e in each] == [i not in idx for i in range(5)]
 
 
 @pytest.mark.parametrize("curve", CURVES, ids=lambda c: c.name)
