@@ -177,6 +177,24 @@ int zl_poseidon_permute_batch(zl_ctx* ctx, zl_curve_t curve, uint64_t* states, s
 int zl_poseidon_hash2_batch(zl_ctx* ctx, zl_curve_t curve, const uint64_t* xy, size_t count, uint64_t* out); /* out[i] = H(xy[2i], xy[2i+1]) */
 /* the same on DEVICE pointers (count x 2 elements in, count elements out; they may not overlap): never the host path, ctx == NULL is ZL_EINVAL */
 int zl_poseidon_hash2_batch_dev(zl_ctx* ctx, zl_curve_t curve, const void* d_xy, size_t count, void* d_out);
+/* ---- every arity the reference specifies (plugins/arkworks/src/poseidon/mod.rs:300-322): arity 2, 3, 4, 5 = width 3, 4, 5, 6 with 8 full and 55, 55, 56, 56
+ * partial rounds; the hash of `arity` inputs is element 0 of permute([2^arity - 1, x_1 .. x_arity]) (openzl-crypto/src/poseidon/hash.rs:64-135).  The round keys
+ * come from the reference's LFSR seeded with (field bits, width, full, partial) and the MDS entry [i][j] is 1 / (i + width + j), as at width 3.  The reference
+ * states the table for BN254; BLS12-381 Fr takes the same rows here.  The common rules above hold unchanged; at width 3 / arity 2 every call below returns byte
+ * for byte what its width-3 counterpart returns.  The in-circuit gadget (zl_circuit_poseidon_*) stays arity 2. */
+/* width, rounds and tag of an arity (a NULL output is skipped); ZL_EINVAL outside 2..5 */
+int zl_poseidon_spec(unsigned arity, unsigned* width, unsigned* full_rounds, unsigned* partial_rounds, uint64_t* tag);
+/* host, one state of `width` elements in place (width 3..6; elements are taken as zl_poseidon_permute takes them); width 3 == zl_poseidon_permute */
+int zl_poseidon_permute_w(zl_curve_t curve, unsigned width, uint64_t* state);
+/* the generated constants, canonical: width * (full + partial) keys [width * round + lane], width * width MDS entries row-major; either may be NULL */
+int zl_poseidon_constants(zl_curve_t curve, unsigned width, uint64_t* keys, uint64_t* mds);
+/* batched, host pointers: the common rules of zl_poseidon_permute_batch (NULL ctx / below ZL_TUNE_POSEIDON_DEV_MIN -> host pool; staged in chunks of
+ * ZL_TUNE_POSEIDON_CHUNK items of `width` resp. `arity` + 1 elements under the byte budget; finished on return).  states: count x width elements, in place;
+ * in: count x arity elements, out: count digests */
+int zl_poseidon_permute_batch_w(zl_ctx* ctx, zl_curve_t curve, unsigned width, uint64_t* states, size_t count);
+int zl_poseidon_hash_batch(zl_ctx* ctx, zl_curve_t curve, unsigned arity, const uint64_t* in, size_t count, uint64_t* out);
+/* device pointers, never the host path (ctx == NULL is ZL_EINVAL); in and out may not overlap */
+int zl_poseidon_hash_batch_dev(zl_ctx* ctx, zl_curve_t curve, unsigned arity, const void* d_in, size_t count, void* d_out);
 /* out[i] = h_k with h_1 = H(x0[i], x1[i]), h_{j+1} = H(h_j, x1[i]): the public input of zl_circuit_poseidon_chain(curve, k, x0[i], x1[i]); the k dependent
  * hashes of a chain run inside one kernel.  k == 0: ZL_EINVAL, as zl_circuit_poseidon_chain. */
 int zl_poseidon_chain_batch(zl_ctx* ctx, zl_curve_t curve, const uint64_t* x0, const uint64_t* x1, uint32_t k, size_t count, uint64_t* out);

@@ -42,6 +42,7 @@ ABI_SYMBOLS = [
     "zl_groth16_prove_poseidon_chains",
     "zl_circuit_poseidon_merkle", "zl_circuit_poseidon_merkle_witness", "zl_poseidon_merkle_assignment_elems", "zl_poseidon_merkle_assignments",
     "zl_poseidon_merkle_assignments_dev", "zl_poseidon_merkle_member_assignments_dev", "zl_groth16_prove_merkle_paths", "zl_groth16_prove_merkle_members",
+    "zl_poseidon_spec", "zl_poseidon_permute_w", "zl_poseidon_constants", "zl_poseidon_permute_batch_w", "zl_poseidon_hash_batch", "zl_poseidon_hash_batch_dev",
 ]
 
 
@@ -138,6 +139,12 @@ def load_library(path: Optional[str] = None):
     L.zl_poseidon_permute_batch.argtypes = [vp, C.c_int, u64p, C.c_size_t]
     L.zl_poseidon_hash2_batch.argtypes = [vp, C.c_int, u64p, C.c_size_t, u64p]
     L.zl_poseidon_hash2_batch_dev.argtypes = [vp, C.c_int, vp, C.c_size_t, vp]
+    L.zl_poseidon_spec.argtypes = [C.c_uint, C.POINTER(C.c_uint), C.POINTER(C.c_uint), C.POINTER(C.c_uint), u64p]
+    L.zl_poseidon_permute_w.argtypes = [C.c_int, C.c_uint, u64p]
+    L.zl_poseidon_constants.argtypes = [C.c_int, C.c_uint, u64p, u64p]
+    L.zl_poseidon_permute_batch_w.argtypes = [vp, C.c_int, C.c_uint, u64p, C.c_size_t]
+    L.zl_poseidon_hash_batch.argtypes = [vp, C.c_int, C.c_uint, u64p, C.c_size_t, u64p]
+    L.zl_poseidon_hash_batch_dev.argtypes = [vp, C.c_int, C.c_uint, vp, C.c_size_t, vp]
     L.zl_poseidon_chain_batch.argtypes = [vp, C.c_int, u64p, u64p, C.c_uint32, C.c_size_t, u64p]
     L.zl_poseidon_chain_assignment_elems.argtypes = [C.c_uint32]
     L.zl_poseidon_chain_assignment_elems.restype = C.c_size_t
@@ -515,8 +522,16 @@ class Backend:
 
     # ---- batched Poseidon (include/zl_backend_ext.h; the module-level poseidon_*_host functions are the same calls with ctx == NULL) ----------
     def poseidon_permute_batch(self, curve: int, states: np.ndarray) -> np.ndarray:
-        """(count, 3, 4) canonical states -> the permuted copy (zl_poseidon_permute_batch)"""
+        """(count, W, 4) canonical states, W in 3..6 -> the permuted copy (zl_poseidon_permute_batch / _w); any other shape is taken as width-3 states"""
         return _poseidon_permute_batch(self.L, self._ctx, curve, states)
+
+    def poseidon_hash(self, curve: int, inputs: np.ndarray) -> np.ndarray:
+        """(count, arity, 4) canonical inputs, arity in 2..5 -> (count, 4) digests: element 0 of permute([2^arity - 1, x_1 .. x_arity]) (zl_poseidon_hash_batch)"""
+        return _poseidon_hash(self.L, self._ctx, curve, inputs)
+
+    def poseidon_hash_dev(self, curve: int, arity: int, d_in: int, count: int, d_out: int):
+        """zl_poseidon_hash_batch_dev: count x arity elements at device address d_in -> count digests at d_out; finished on return"""
+        self._check(self.L.zl_poseidon_hash_batch_dev(self._ctx, curve, arity, C.c_void_p(d_in), count, C.c_void_p(d_out)), "zl_poseidon_hash_batch_dev")
 
     def poseidon_hash2(self, curve: int, xy: np.ndarray) -> np.ndarray:
         """(count, 2, 4) canonical pairs -> (count, 4) digests H(x, y)"""
@@ -1217,12 +1232,38 @@ def hook_acc_clock_read(be: "Backend") -> dict:
 
 # ---- host mirror (openzl::R1CS / poseidon / Groth16<E>, csrc/zl_host.h) through its C hooks ---------------------------
 def poseidon_permute(curve: int, state: np.ndarray) -> np.ndarray:
-    """native width-3 Poseidon permutation on canonical (3,4) uint64 limbs (host code, no GPU)."""
-    st = np.ascontiguousarray(state.copy(), dtype=np.uint64)
-    rc = load_library().zl_poseidon_permute(curve, _p64(st))
+    """native Poseidon permutation on canonical (W,4) uint64 limbs, W in 3..6 (host code, no GPU)."""
+    st = np.ascontiguousarray(np.array(state, dtype=np.uint64, copy=True))
+    if st.size == 12:  # (width 3: the shapes this function always took)
+        rc, what = load_library().zl_poseidon_permute(curve, _p64(st)), "zl_poseidon_permute"
+    else:
+        if st.ndim != 2 or st.shape[1] != 4:
+            raise ValueError("a state is (W, 4) uint64 words")
+        rc, what = load_library().zl_poseidon_permute_w(curve, st.shape[0], _p64(st)), "zl_poseidon_permute_w"
     if rc:
-        raise BackendError(rc, "zl_poseidon_permute")
+        raise BackendError(rc, what)
     return st
+
+
+def poseidon_spec(arity: int) -> dict:
+    """width, full_rounds, partial_rounds and tag of an arity in 2..5 (zl_poseidon_spec)"""
+    w, rf, rp, tag = C.c_uint(), C.c_uint(), C.c_uint(), C.c_uint64()
+    rc = load_library().zl_poseidon_spec(arity, C.byref(w), C.byref(rf), C.byref(rp), C.byref(tag))
+    if rc:
+        raise BackendError(rc, "zl_poseidon_spec")
+    return {"arity": arity, "width": w.value, "full_rounds": rf.value, "partial_rounds": rp.value, "tag": tag.value}
+
+
+def poseidon_constants(curve: int, width: int):
+    """the generated constants of a width in 3..6, canonical: (width * rounds, 4) round keys and (width, width, 4) MDS entries (zl_poseidon_constants)"""
+    L = load_library()
+    if not 3 <= width <= 6:
+        raise BackendError(-1, "zl_poseidon_constants")
+    sp = poseidon_spec(width - 1)
+    keys = np.zeros((width * (sp["full_rounds"] + sp["partial_rounds"]), 4), dtype=np.uint64)
+    mds = np.zeros((width, width, 4), dtype=np.uint64)
+    _pos_check(L, L.zl_poseidon_constants(curve, width, _p64(keys), _p64(mds)), "zl_poseidon_constants")
+    return keys, mds
 
 
 # ---- batched Poseidon: one implementation per call for Backend (its ctx) and for the host forms below (ctx == NULL: host thread pool, no device) ----
@@ -1241,9 +1282,23 @@ def _ptr_or_none(a: np.ndarray):
 
 
 def _poseidon_permute_batch(L, ctx, curve: int, states) -> np.ndarray:
+    a = np.asarray(states, dtype=np.uint64)
+    if a.ndim == 3 and a.shape[2] == 4 and a.shape[1] != 3:  # (count, W, 4): the width is the array's; every other shape is width-3 states as before
+        st = np.ascontiguousarray(a).copy()
+        _pos_check(L, L.zl_poseidon_permute_batch_w(ctx, curve, st.shape[1], _ptr_or_none(st), st.shape[0]), "zl_poseidon_permute_batch_w")
+        return st
     st = _elems(states, 3).copy()
     _pos_check(L, L.zl_poseidon_permute_batch(ctx, curve, _ptr_or_none(st), st.shape[0]), "zl_poseidon_permute_batch")
     return st
+
+
+def _poseidon_hash(L, ctx, curve: int, inputs) -> np.ndarray:
+    v = np.ascontiguousarray(np.asarray(inputs, dtype=np.uint64))
+    if v.ndim != 3 or v.shape[2] != 4:
+        raise ValueError("inputs are (count, arity, 4) uint64 words")
+    out = np.zeros((v.shape[0], 4), dtype=np.uint64)
+    _pos_check(L, L.zl_poseidon_hash_batch(ctx, curve, v.shape[1], _ptr_or_none(v), v.shape[0], _ptr_or_none(out)), "zl_poseidon_hash_batch")
+    return out
 
 
 def _poseidon_hash2(L, ctx, curve: int, xy) -> np.ndarray:
@@ -1326,6 +1381,10 @@ def poseidon_permute_batch_host(curve: int, states) -> np.ndarray:
 
 def poseidon_hash2_host(curve: int, xy) -> np.ndarray:
     return _poseidon_hash2(load_library(), None, curve, xy)
+
+
+def poseidon_hash_host(curve: int, inputs) -> np.ndarray:
+    return _poseidon_hash(load_library(), None, curve, inputs)
 
 
 def poseidon_chain_host(curve: int, x0, x1, k: int) -> np.ndarray:

@@ -258,7 +258,7 @@ struct zl_ctx {
     void* g16_h = nullptr;  // quotient polynomial of the last zl_groth16_prove (inside ZL_SLOT_GROTH16; reset when the next proof starts)
     size_t g16_h_n = 0;
     int ntt_fit_beside = 0;  // this ctx's transforms run beside a kernel that leaves 96 registers per SIMD (a proof's witness map: ctx->aux2): use the capped passes (zl_ntt.hip)
-    void* poseidon_tab[2] = {nullptr, nullptr};  // Poseidon round keys, MDS entries and the domain tag in Montgomery form, per curve (zl_poseidon_dev.hip): built once by the ROOT ctx, read by its forks, freed at destroy
+    void* poseidon_tab[2 * 4] = {};  // Poseidon round keys, MDS entries and the domain tag in Montgomery form, per curve and width ([4 * curve + width - 3], zl_poseidon_dev.hip): each built once by the ROOT ctx, read by its forks, freed at destroy
     void* g16_z = nullptr;  // the canonical assignment of the last witness-map-only run (sharded proofs: the other ranks copy their slices from here)
     // MEASUREMENT ONLY (zl_test_acc_clock): when non-null, large G1 accumulations run as k_msm_accumulate_clk and leave four clock reads per wave here
     void* acc_clk = nullptr;

@@ -18,6 +18,7 @@
 #include <mutex>
 #include "zl_ctx.h"
 #include "zl_pairing.h"
+#include "zl_poseidon_dev.h"  // poseidon_dev::spec: the (arity, width, rounds, tag) table
 
 namespace openzl {
 
@@ -315,10 +316,13 @@ private:
     bool update() { return set_next(bit(62) ^ bit(51) ^ bit(38) ^ bit(23) ^ bit(13) ^ bit(0)); }
 };
 
-template <class FrP>
+// The constants of one width (3..6: poseidon_dev::spec, zl_poseidon_dev.h); Constants<FrP> is the width-3, arity-2 instance of the in-circuit hash.
+template <class FrP, int W = 3>
 struct Constants {
     using F = Fp<FrP>;
-    static constexpr int WIDTH = 3, FULL_ROUNDS = 8, PARTIAL_ROUNDS = 55;  // arity 2 (plugins/arkworks/src/poseidon/mod.rs:300-304)
+    static_assert(poseidon_dev::width_ok(W), "widths 3..6: arity 2..5");
+    static constexpr poseidon_dev::Spec SPEC = poseidon_dev::spec_of_width(W);  // (plugins/arkworks/src/poseidon/mod.rs:300-322)
+    static constexpr int WIDTH = W, FULL_ROUNDS = (int)SPEC.full_rounds, PARTIAL_ROUNDS = (int)SPEC.partial_rounds;
     std::vector<F> round_keys;  // WIDTH * (RF + RP), Montgomery
     F mds[WIDTH][WIDTH];
     Constants() {
@@ -340,25 +344,25 @@ struct Constants {
             for (int j = 0; j < WIDTH; j++) mds[i][j] = zl::inv(zl::from_u64<FrP>((uint64_t)(i + WIDTH + j)));
     }
 };
-// native permutation (openzl-tutorials/src/poseidon.rs:165-222 schedule; COM = ())
-template <class FrP>
-void permute_native(const Constants<FrP>& c, Fp<FrP> state[3]) {
+// native permutation (openzl-tutorials/src/poseidon.rs:165-222 schedule; COM = ()), any width of the table
+template <class FrP, int W>
+void permute_native(const Constants<FrP, W>& c, Fp<FrP> state[W]) {
     using F = Fp<FrP>;
     const int half = c.FULL_ROUNDS / 2;
     for (int rnd = 0; rnd < c.FULL_ROUNDS + c.PARTIAL_ROUNDS; rnd++) {
-        for (int i = 0; i < 3; i++) state[i] = zl::add(state[i], c.round_keys[3 * rnd + i]);
-        const int lanes = (rnd < half || rnd >= half + c.PARTIAL_ROUNDS) ? 3 : 1;
+        for (int i = 0; i < W; i++) state[i] = zl::add(state[i], c.round_keys[W * rnd + i]);
+        const int lanes = (rnd < half || rnd >= half + c.PARTIAL_ROUNDS) ? W : 1;
         for (int i = 0; i < lanes; i++) {
             F x2 = zl::sqr(state[i]), x4 = zl::sqr(x2);
             state[i] = zl::mul(x4, state[i]);
         }
-        F nx[3];
-        for (int i = 0; i < 3; i++) {
+        F nx[W];
+        for (int i = 0; i < W; i++) {
             F acc = zl::mul(c.mds[i][0], state[0]);
-            acc = zl::add(acc, zl::mul(c.mds[i][1], state[1]));
-            nx[i] = zl::add(acc, zl::mul(c.mds[i][2], state[2]));
+            for (int j = 1; j < W; j++) acc = zl::add(acc, zl::mul(c.mds[i][j], state[j]));
+            nx[i] = acc;
         }
-        for (int i = 0; i < 3; i++) state[i] = nx[i];
+        for (int i = 0; i < W; i++) state[i] = nx[i];
     }
 }
 // the same permutation, recording what the in-circuit version allocates: x^2, x^4, x^5 of every S-box whose input is not a constant

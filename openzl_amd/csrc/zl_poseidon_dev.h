@@ -6,7 +6,31 @@
 
 namespace openzl {
 namespace poseidon_dev {
+// The specification table, per arity (plugins/arkworks/src/poseidon/mod.rs:300-322 states it for BN254; BLS12-381 Fr takes the same rows, as it does at arity 2):
+//   arity 2 3 4 5 -> width 3 4 5 6, 8 full rounds, 55 55 56 56 partial rounds, domain tag 2^arity - 1 (openzl-crypto/src/poseidon/hash.rs:64-135).
+// The host mirror (zl_host.h) and the device unit both read this one function.
+struct Spec {
+    unsigned arity, width, full_rounds, partial_rounds;
+    uint64_t tag;
+    constexpr unsigned rounds() const { return full_rounds + partial_rounds; }
+    constexpr unsigned keys() const { return width * rounds(); }
+};
+constexpr unsigned MIN_ARITY = 2, MAX_ARITY = 5, MIN_WIDTH = MIN_ARITY + 1, MAX_WIDTH = MAX_ARITY + 1, N_WIDTHS = MAX_WIDTH - MIN_WIDTH + 1;
+constexpr bool arity_ok(unsigned arity) { return arity >= MIN_ARITY && arity <= MAX_ARITY; }
+constexpr bool width_ok(unsigned width) { return width >= MIN_WIDTH && width <= MAX_WIDTH; }
+constexpr Spec spec(unsigned arity) { return Spec{arity, arity + 1, 8, arity <= 3 ? 55u : 56u, ((uint64_t)1 << arity) - 1}; }
+constexpr Spec spec_of_width(unsigned width) { return spec(width - 1); }
+static_assert(spec(2).width == 3 && spec(2).rounds() == 63 && spec(2).tag == 3 && spec(3).width == 4 && spec(3).rounds() == 63 && spec(3).tag == 7 &&
+                  spec(4).width == 5 && spec(4).rounds() == 64 && spec(4).tag == 15 && spec(5).width == 6 && spec(5).rounds() == 64 && spec(5).tag == 31,
+              "the reference's Spec table");
+// the device table of one (curve, width), in the entry format below: W * rounds round keys [W * round + lane], W * W MDS entries [W * row + column], the tag
+constexpr int tab_keys(unsigned) { return 0; }
+constexpr int tab_mds(unsigned width) { return (int)spec_of_width(width).keys(); }
+constexpr int tab_tag(unsigned width) { return tab_mds(width) + (int)(width * width); }
+constexpr int tab_entries(unsigned width) { return tab_tag(width) + 1; }
+
 constexpr int WIDTH = 3, FULL_ROUNDS = 8, PARTIAL_ROUNDS = 55, ROUNDS = FULL_ROUNDS + PARTIAL_ROUNDS;
+static_assert(spec(2).width == WIDTH && spec(2).full_rounds == FULL_ROUNDS && spec(2).partial_rounds == PARTIAL_ROUNDS, "the width-3 unit is the table's arity-2 row");
 // the device table of one curve: entries of TAB_WORDS u32 slots holding the nine 29-bit limbs of x R' mod r (R' = 2^261: the device multiplier's own Montgomery form)
 constexpr int TAB_KEYS = 0;                     // 189 round keys, [3 * round + lane]
 constexpr int TAB_MDS = WIDTH * ROUNDS;         // 9 MDS entries, [3 * row + column]
@@ -14,6 +38,8 @@ constexpr int TAB_TAG = TAB_MDS + WIDTH * WIDTH;  // the arity-2 domain tag 3
 constexpr int TAB_ENTRIES = TAB_TAG + 1;
 constexpr int TAB_WORDS = 10;
 constexpr size_t TAB_BYTES = (size_t)TAB_ENTRIES * TAB_WORDS * 4;
+static_assert(tab_mds(3) == TAB_MDS && tab_tag(3) == TAB_TAG && tab_entries(3) == TAB_ENTRIES, "one layout rule at every width");
+constexpr size_t tab_bytes(unsigned width) { return (size_t)tab_entries(width) * TAB_WORDS * 4; }
 
 constexpr unsigned MAX_DEPTH = 40;
 constexpr int TAIL_MAX = 1024;       // nodes the one-workgroup tail kernel can take over: (T + T / 2) x 32 B of LDS = 48 KB

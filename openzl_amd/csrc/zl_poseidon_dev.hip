@@ -15,6 +15,9 @@
 //   k_pos_tail       one workgroup finishes ALL remaining levels of a Merkle tree once a level has at most T nodes: the level lives in LDS (two buffers,
 //                    canonical words), __syncthreads() between levels, every level is also written to the node array at the offsets the wide path uses.
 //   k_pos_gather     sibling digests of `count` leaves out of a device node array.
+//   k_pos_permute_w / k_pos_hash_w   widths 4, 5, 6 (arity 3, 4, 5 of pd::spec): their own permutation permute_w<FrP, W> on W state registers and a table per
+//                    (curve, width); the S-box reduces its input weakly where the lazy bound requires it (the argument stands above WideBounds).  Width 3 keeps
+//                    the kernels above; the entry points of every arity forward to them at arity 2.
 // Arithmetic: the lazily reduced 9 x 29-bit Fr of zl_field28r.h (the NTT's multiplier), 1.29 - 1.46 x the carry-chain Fp<FrP> here and ahead of the 10 x 28 form at
 // every size measured (profiles/poseidon_field_ab.log); the bound argument stands beside the type below.  The host path stays on Fp<FrP>.
 // A lane at or above the item count returns before it reads or writes anything.  An input element >= r sets the flag word (atomicOr) and the lane goes on with
@@ -430,10 +433,121 @@ __global__ __launch_bounds__(BLOCK) void k_pos_merkle_trace(const uint32_t* __re
     if (pub) dstore<FrP>(pub + p * 4, cur);
 }
 
+// ---------------------------------------------------------------------------------------------------------------- widths 4, 5, 6 (arity 3, 4, 5)
+// The same schedule on W state elements (pd::spec: 8 + 55 rounds at width 4, 8 + 56 at widths 5 and 6), one lane per permutation, the state in registers, the
+// constants from the table of the (curve, width) at wave-uniform addresses.  The width-3 bound argument (above LazyP) does NOT carry over; restated in units of r:
+//   * a product, a loaded element and a table entry are < 2r as before; an MDS row is a sum of W products: < 2W r (8, 10, 12); a state element entering a
+//     round is that or a loaded element / the tag (< 2r); plus its round key: < (2W + 2) r = KEYED r (10, 12, 14);
+//   * squaring a keyed element would need KEYED^2 = 100, 144, 196: above MUL_BOUND = 70 of BLS12-381 at every width, above 169 of BN254 at width 6.  Exactly
+//     there (REDUCE) the S-box first reduces its input weakly: wred takes a carried value below 128 r (add carries; KEYED <= 14) and returns < 2r, so x^2
+//     needs 2 * 2, x^4 2 * 2, x^5 = mul(x^4, x) 2 * 2.  BN254 at widths 4 and 5 keeps the plain S-box: x^2 needs 100 resp. 144 <= 169, x^5 2 * KEYED.
+//     One wred per S-box, 8 W + partial rounds per permutation, is the least that the arithmetic allows: every S-box input is a fresh row sum plus a key;
+//   * the lanes a partial round leaves without S-box stay < KEYED r and enter the MDS product against an entry < 2r: 2 * KEYED = 20, 24, 28, fine everywhere,
+//     so they are NOT reduced; the S-boxed lanes enter it at 2 * 2;
+//   * the outputs are row sums (< 2W r): dstore's mul(x, 1) takes them at 2W * 1 and hands canon a product (< 2r);
+//   * sums stay below 14 r < 2^259: inside nine limbs.
+// WideBounds states this per (field, width) and asserts the largest bound product that reaches mul.
+constexpr int cmax(int a, int b) { return a > b ? a : b; }
+template <class FrP, int W>
+struct WideBounds {
+    using P = typename LazyP<FrP>::P;
+    static constexpr int ROW = 2 * W;                                // an MDS row sum
+    static constexpr int KEYED = ROW + 2;                            // ... plus a round key
+    static constexpr bool REDUCE = KEYED * KEYED > P::MUL_BOUND;     // the S-box reduces its input first
+    static constexpr int SBOX_IN = REDUCE ? 2 : KEYED;
+    static constexpr int SBOX_MUL = cmax(SBOX_IN * SBOX_IN, cmax(2 * 2, 2 * SBOX_IN));  // x^2, x^4, x^5
+    static constexpr int MDS_MUL = 2 * KEYED;                        // entry x a lane without S-box
+    static constexpr int STORE_MUL = ROW * 1;                        // dstore: mul(x, 1), then canon of a product (< 2r, wred's limit is 128 r)
+    static constexpr int MAX_MUL = cmax(SBOX_MUL, cmax(MDS_MUL, STORE_MUL));
+    static_assert(MAX_MUL <= P::MUL_BOUND, "a bound product above what mul takes: place a weak reduction");
+    static_assert(KEYED <= 128, "wred (and canon) take a value below 128 r");
+};
+#define ZL_POS_WIDE_BOUNDS(FrP, W, reduce, max_mul) \
+    static_assert(WideBounds<FrP, W>::REDUCE == reduce && WideBounds<FrP, W>::MAX_MUL == max_mul && WideBounds<FrP, W>::MAX_MUL <= LazyP<FrP>::P::MUL_BOUND, "bounds of " #FrP " at width " #W)
+ZL_POS_WIDE_BOUNDS(BLS12_381_Fr, 4, true, 20);   // keyed 10: 100 > 70, reduced; the largest product is the MDS's 2 * 10
+ZL_POS_WIDE_BOUNDS(BLS12_381_Fr, 5, true, 24);   // keyed 12: 144 > 70
+ZL_POS_WIDE_BOUNDS(BLS12_381_Fr, 6, true, 28);   // keyed 14: 196 > 70
+ZL_POS_WIDE_BOUNDS(BN254_Fr, 4, false, 100);     // 100 <= 169: no reduction
+ZL_POS_WIDE_BOUNDS(BN254_Fr, 5, false, 144);     // 144 <= 169: no reduction
+ZL_POS_WIDE_BOUNDS(BN254_Fr, 6, true, 28);       // 196 > 169, reduced
+#undef ZL_POS_WIDE_BOUNDS
+static_assert(!WideBounds<BLS12_381_Fr, 3>::REDUCE && !WideBounds<BN254_Fr, 3>::REDUCE && WideBounds<BLS12_381_Fr, 3>::MAX_MUL == 64,
+              "the same rule gives the width-3 unit's argument: no reduction, 64");
+
+template <class FrP, int W>
+__device__ __forceinline__ void sbox_w(El<FrP>& x) {
+    if constexpr (WideBounds<FrP, W>::REDUCE) x = zl::wred(x);
+    const El<FrP> x2 = zl::mul(x, x), x4 = zl::mul(x2, x2);
+    x = zl::mul(x4, x);
+}
+// 8 (3W + W^2) + partial (3 + W^2) multiplications: 1 288, 1 976, 2 616 at widths 4, 5, 6.  One rolled round loop; the ROWS of the MDS product are a rolled loop
+// too, so a round holds 3W + W inlined multiplier bodies instead of 3W + W^2 (24 instead of 54 at width 6): row i is accumulated against the W state registers
+// and shifted into nx from the top, all register indices static, and after W rows nx[k] is row k.  Table addresses depend on the round and the row only.
+template <class FrP, int W>
+__device__ __forceinline__ void permute_w(const uint32_t* __restrict__ tab, El<FrP> (&s)[W]) {
+    constexpr pd::Spec S = pd::spec_of_width(W);
+    constexpr int half = (int)S.full_rounds / 2, partial = (int)S.partial_rounds, rounds = (int)S.rounds();
+#pragma unroll 1
+    for (int rnd = 0; rnd < rounds; rnd++) {
+#pragma unroll
+        for (int i = 0; i < W; i++) s[i] = zl::add(s[i], tab_ld<FrP>(tab, pd::tab_keys(W) + W * rnd + i));
+        sbox_w<FrP, W>(s[0]);
+        if (rnd < half || rnd >= half + partial) {
+#pragma unroll
+            for (int i = 1; i < W; i++) sbox_w<FrP, W>(s[i]);
+        }
+        El<FrP> nx[W];
+#pragma unroll
+        for (int i = 0; i < W; i++) nx[i] = ezero<FrP>();
+#pragma unroll 1
+        for (int i = 0; i < W; i++) {
+            El<FrP> acc = zl::mul(tab_ld<FrP>(tab, pd::tab_mds(W) + W * i), s[0]);
+#pragma unroll
+            for (int j = 1; j < W; j++) acc = zl::add(acc, zl::mul(tab_ld<FrP>(tab, pd::tab_mds(W) + W * i + j), s[j]));
+#pragma unroll
+            for (int k = 0; k + 1 < W; k++) nx[k] = nx[k + 1];
+            nx[W - 1] = acc;
+        }
+#pragma unroll
+        for (int i = 0; i < W; i++) s[i] = nx[i];
+    }
+}
+// count x W elements, in place
+template <class FrP, int W>
+__global__ __launch_bounds__(BLOCK) void k_pos_permute_w(const uint32_t* __restrict__ tab, uint64_t* __restrict__ states, size_t n, uint32_t* __restrict__ flag) {
+    const size_t p = (size_t)blockIdx.x * BLOCK + threadIdx.x;
+    if (p >= n) return;
+    uint64_t* st = states + p * (4 * W);
+    El<FrP> s[W];
+    bool ok = true;
+#pragma unroll
+    for (int i = 0; i < W; i++) ok &= dload<FrP>(st + 4 * i, s[i]);
+    if (!ok) atomicOr(flag, 1u);
+    permute_w<FrP, W>(tab, s);
+#pragma unroll
+    for (int i = 0; i < W; i++) dstore<FrP>(st + 4 * i, s[i]);
+}
+// out[p] = element 0 of permute([tag, in[p][0], .., in[p][W - 2]]): the hash of W - 1 inputs
+template <class FrP, int W>
+__global__ __launch_bounds__(BLOCK) void k_pos_hash_w(const uint32_t* __restrict__ tab, const uint64_t* __restrict__ in, size_t n, uint64_t* __restrict__ out,
+                                                      uint32_t* __restrict__ flag) {
+    const size_t p = (size_t)blockIdx.x * BLOCK + threadIdx.x;
+    if (p >= n) return;
+    const uint64_t* x = in + p * (4 * (W - 1));
+    El<FrP> s[W];
+    s[0] = tab_ld<FrP>(tab, pd::tab_tag(W));
+    bool ok = true;
+#pragma unroll
+    for (int i = 1; i < W; i++) ok &= dload<FrP>(x + 4 * (i - 1), s[i]);
+    if (!ok) atomicOr(flag, 1u);
+    permute_w<FrP, W>(tab, s);
+    dstore<FrP>(out + p * 4, s[0]);
+}
+
 // ---------------------------------------------------------------------------------------------------------------- host path
-template <class FrP>
-const poseidon::Constants<FrP>& consts() {
-    static const poseidon::Constants<FrP> c;
+template <class FrP, int W = 3>
+const poseidon::Constants<FrP, W>& consts() {
+    static const poseidon::Constants<FrP, W> c;
     return c;
 }
 template <class FrP>
@@ -475,6 +589,54 @@ template <class FrP>
 int host_hash2_batch(const uint64_t* xy, size_t count, uint64_t* out) {
     consts<FrP>();
     return host_for(count, [&](size_t i) { return host_hash2<FrP>(xy + i * 8, xy + i * 8 + 4, out + i * 4); }) ? ZL_OK : ZL_EINVAL;
+}
+// widths 4..6: the host mirror's generic permute_native on the constants of the width
+template <class FrP, int W>
+int host_permute_w(uint64_t* states, size_t count) {
+    consts<FrP, W>();
+    return host_for(count, [&](size_t i) {
+        Fp<FrP> st[W];
+        bool ok = true;
+        for (int e = 0; e < W; e++) ok &= load_canon<FrP>(states + i * (4 * W) + 4 * e, st[e]);
+        poseidon::permute_native(consts<FrP, W>(), st);
+        for (int e = 0; e < W; e++) store_canon<FrP>(states + i * (4 * W) + 4 * e, st[e]);
+        return ok;
+    }) ? ZL_OK : ZL_EINVAL;
+}
+template <class FrP, int W>
+int host_hash_w(const uint64_t* in, size_t count, uint64_t* out) {
+    consts<FrP, W>();
+    return host_for(count, [&](size_t i) {
+        Fp<FrP> st[W];
+        st[0] = zl::from_u64<FrP>(pd::spec_of_width(W).tag);
+        bool ok = true;
+        for (int e = 1; e < W; e++) ok &= load_canon<FrP>(in + i * (4 * (W - 1)) + 4 * (e - 1), st[e]);
+        poseidon::permute_native(consts<FrP, W>(), st);
+        store_canon<FrP>(out + i * 4, st[0]);
+        return ok;
+    }) ? ZL_OK : ZL_EINVAL;
+}
+// one state on the calling thread (zl_poseidon_permute_w) and the constants themselves, canonical (zl_poseidon_constants)
+template <class FrP, int W>
+int host_permute_one(uint64_t* state) {
+    Fp<FrP> st[W];
+    for (int i = 0; i < W; i++) {  // (as zl_poseidon_permute: the words are taken as they are, a value >= r counts mod r)
+        memcpy(st[i].l, state + 4 * i, 32);
+        st[i] = zl::to_mont(st[i]);
+    }
+    poseidon::permute_native(consts<FrP, W>(), st);
+    for (int i = 0; i < W; i++) store_canon<FrP>(state + 4 * i, st[i]);
+    return ZL_OK;
+}
+template <class FrP, int W = 3>
+int constants_out(uint64_t* keys, uint64_t* mds) {
+    const poseidon::Constants<FrP, W>& c = consts<FrP, W>();
+    if (keys)
+        for (size_t i = 0; i < c.round_keys.size(); i++) store_canon<FrP>(keys + 4 * i, c.round_keys[i]);
+    if (mds)
+        for (int i = 0; i < W; i++)
+            for (int j = 0; j < W; j++) store_canon<FrP>(mds + 4 * (W * i + j), c.mds[i][j]);
+    return ZL_OK;
 }
 template <class FrP>
 int host_chain(const uint64_t* x0, const uint64_t* x1, uint32_t k, size_t count, uint64_t* out) {
@@ -616,28 +778,30 @@ std::mutex& tab_mutex() {
     static std::mutex m;
     return m;
 }
-// The constant table of the curve: built once by the first call on the ROOT ctx or any of its forks, owned by the root (zl_ctx_destroy frees it); the copy is
-// synchronous, so the table is complete before the lock is released and any lane launches against it.
-template <class FrP>
+// The constant table of the (curve, width): built once by the first call for it on the ROOT ctx or any of its forks, owned by the root (zl_ctx_destroy frees
+// it); the copy is synchronous, so the table is complete before the lock is released and any lane launches against it.
+template <class FrP, int W = 3>
 int get_table(zl_ctx* ctx, const uint32_t** out) {
+    static_assert(sizeof(zl_ctx::poseidon_tab) / sizeof(void*) == 2 * pd::N_WIDTHS, "a slot per curve and width");
+    constexpr pd::Spec S = pd::spec_of_width(W);
     zl_ctx* owner = ctx->parent ? ctx->parent : ctx;
     std::lock_guard<std::mutex> lk(tab_mutex());
-    void*& slot = owner->poseidon_tab[std::is_same<FrP, BLS12_381_Fr>::value ? 0 : 1];
+    void*& slot = owner->poseidon_tab[(std::is_same<FrP, BLS12_381_Fr>::value ? 0 : pd::N_WIDTHS) + (W - pd::MIN_WIDTH)];
     if (!slot) {
-        const poseidon::Constants<FrP>& c = consts<FrP>();
-        std::vector<uint32_t> w((size_t)pd::TAB_ENTRIES * TABW, 0u);
+        const poseidon::Constants<FrP, W>& c = consts<FrP, W>();
+        std::vector<uint32_t> w((size_t)pd::tab_entries(W) * TABW, 0u);
         auto put = [&](int e, const Fp<FrP>& m) {
             const Fp<FrP> cw = zl::from_mont(m);
             const El<FrP> v = to_lazy<FrP>(cw.l);
             for (int k = 0; k < El<FrP>::L; k++) w[(size_t)e * TABW + k] = v.l[k];
         };
-        for (int i = 0; i < pd::WIDTH * pd::ROUNDS; i++) put(pd::TAB_KEYS + i, c.round_keys[(size_t)i]);
-        for (int i = 0; i < 3; i++)
-            for (int j = 0; j < 3; j++) put(pd::TAB_MDS + 3 * i + j, c.mds[i][j]);
-        put(pd::TAB_TAG, zl::from_u64<FrP>(3));
+        for (int i = 0; i < (int)S.keys(); i++) put(pd::tab_keys(W) + i, c.round_keys[(size_t)i]);
+        for (int i = 0; i < W; i++)
+            for (int j = 0; j < W; j++) put(pd::tab_mds(W) + W * i + j, c.mds[i][j]);
+        put(pd::tab_tag(W), zl::from_u64<FrP>(S.tag));
         void* d = nullptr;
-        ZL_HIP(ctx, hipMalloc(&d, pd::TAB_BYTES));
-        const hipError_t e = hipMemcpy(d, w.data(), pd::TAB_BYTES, hipMemcpyHostToDevice);
+        ZL_HIP(ctx, hipMalloc(&d, pd::tab_bytes(W)));
+        const hipError_t e = hipMemcpy(d, w.data(), pd::tab_bytes(W), hipMemcpyHostToDevice);
         if (e != hipSuccess) {
             (void)hipFree(d);
             ctx->last_hip = (int)e;
@@ -726,6 +890,59 @@ int dev_hash2(zl_ctx* ctx, const uint64_t* xy, size_t count, uint64_t* out) {
         const size_t m = count - first < chunk ? count - first : chunk;
         ZL_HIP(ctx, hipMemcpyAsync(d_in, xy + first * 8, m * 64, hipMemcpyHostToDevice, ctx->stream));
         ZL_POS_LAUNCH(ctx, (k_pos_hash2<FrP>), blocks_of(m), BLOCK, 0, tab, d_in, m, d_out, s.flag);
+        ZL_HIP(ctx, hipMemcpyAsync(out + first * 4, d_out, m * 32, hipMemcpyDeviceToHost, ctx->stream));
+    }
+    return finish(ctx, s.flag);
+}
+// widths 4..6: the same staging with W (permute) resp. W - 1 + 1 (hash: inputs and digest) elements per item
+template <class FrP, int W>
+int dev_permute_w(zl_ctx* ctx, uint64_t* states, size_t count) {
+    const uint32_t* tab;
+    int rc = get_table<FrP, W>(ctx, &tab);
+    if (rc) return rc;
+    constexpr size_t per = 32 * W;
+    const size_t chunk = stage_items(per);
+    Stage s;
+    if ((rc = stage_get(ctx, (count < chunk ? count : chunk) * per, &s))) return rc;
+    uint64_t* d = reinterpret_cast<uint64_t*>(s.data);
+    for (size_t first = 0; first < count; first += chunk) {
+        const size_t m = count - first < chunk ? count - first : chunk;
+        ZL_HIP(ctx, hipMemcpyAsync(d, states + first * (4 * W), m * per, hipMemcpyHostToDevice, ctx->stream));
+        ZL_POS_LAUNCH(ctx, (k_pos_permute_w<FrP, W>), blocks_of(m), BLOCK, 0, tab, d, m, s.flag);
+        ZL_HIP(ctx, hipMemcpyAsync(states + first * (4 * W), d, m * per, hipMemcpyDeviceToHost, ctx->stream));
+    }
+    return finish(ctx, s.flag);
+}
+template <class FrP, int W>
+int dev_hash_w_dev(zl_ctx* ctx, const void* d_in, size_t count, void* d_out) {
+    const uint32_t* tab;
+    int rc = get_table<FrP, W>(ctx, &tab);
+    if (rc) return rc;
+    Stage s;
+    if ((rc = stage_get(ctx, 0, &s))) return rc;
+    const size_t chunk = tune_chunk();
+    for (size_t first = 0; first < count; first += chunk) {
+        const size_t m = count - first < chunk ? count - first : chunk;
+        ZL_POS_LAUNCH(ctx, (k_pos_hash_w<FrP, W>), blocks_of(m), BLOCK, 0, tab, static_cast<const uint64_t*>(d_in) + first * (4 * (W - 1)), m,
+                      static_cast<uint64_t*>(d_out) + first * 4, s.flag);
+    }
+    return finish(ctx, s.flag);
+}
+template <class FrP, int W>
+int dev_hash_w(zl_ctx* ctx, const uint64_t* in, size_t count, uint64_t* out) {
+    const uint32_t* tab;
+    int rc = get_table<FrP, W>(ctx, &tab);
+    if (rc) return rc;
+    constexpr size_t in_per = 32 * (W - 1);
+    const size_t chunk = stage_items(in_per + 32), m0 = count < chunk ? count : chunk;
+    Stage s;
+    if ((rc = stage_get(ctx, up256(m0 * in_per) + m0 * 32, &s))) return rc;
+    uint64_t* d_in = reinterpret_cast<uint64_t*>(s.data);
+    uint64_t* d_out = reinterpret_cast<uint64_t*>(s.data + up256(m0 * in_per));
+    for (size_t first = 0; first < count; first += chunk) {
+        const size_t m = count - first < chunk ? count - first : chunk;
+        ZL_HIP(ctx, hipMemcpyAsync(d_in, in + first * (4 * (W - 1)), m * in_per, hipMemcpyHostToDevice, ctx->stream));
+        ZL_POS_LAUNCH(ctx, (k_pos_hash_w<FrP, W>), blocks_of(m), BLOCK, 0, tab, d_in, m, d_out, s.flag);
         ZL_HIP(ctx, hipMemcpyAsync(out + first * 4, d_out, m * 32, hipMemcpyDeviceToHost, ctx->stream));
     }
     return finish(ctx, s.flag);
@@ -1019,6 +1236,56 @@ int zl_poseidon_hash2_batch_dev(zl_ctx* ctx, zl_curve_t curve, const void* d_xy,
     if (count == 0) return ZL_OK;
     ZL_HIP(ctx, hipSetDevice(ctx->device));
     return ZL_POS_CURVE(curve, dev_hash2_dev, ctx, d_xy, count, d_out);
+}
+// ---- every arity of the table (pd::spec).  Width 3 / arity 2 forwards to the entry points above; widths 4..6 run their own kernels and host loops.
+#define ZL_POS_WIDE(curve, width, fn, ...)                                                                    \
+    ((width) == 4 ? ((curve) == ZL_BLS12_381 ? fn<BLS12_381_Fr, 4>(__VA_ARGS__) : fn<BN254_Fr, 4>(__VA_ARGS__))   \
+     : (width) == 5 ? ((curve) == ZL_BLS12_381 ? fn<BLS12_381_Fr, 5>(__VA_ARGS__) : fn<BN254_Fr, 5>(__VA_ARGS__)) \
+                    : ((curve) == ZL_BLS12_381 ? fn<BLS12_381_Fr, 6>(__VA_ARGS__) : fn<BN254_Fr, 6>(__VA_ARGS__)))
+int zl_poseidon_spec(unsigned arity, unsigned* width, unsigned* full_rounds, unsigned* partial_rounds, uint64_t* tag) {
+    if (!pd::arity_ok(arity)) return ZL_EINVAL;
+    const pd::Spec s = pd::spec(arity);
+    if (width) *width = s.width;
+    if (full_rounds) *full_rounds = s.full_rounds;
+    if (partial_rounds) *partial_rounds = s.partial_rounds;
+    if (tag) *tag = s.tag;
+    return ZL_OK;
+}
+int zl_poseidon_permute_w(zl_curve_t curve, unsigned width, uint64_t* state) {
+    if (!valid_curve(curve) || !pd::width_ok(width) || !state) return ZL_EINVAL;
+    if (width == 3) return zl_poseidon_permute(curve, state);
+    return ZL_POS_WIDE(curve, width, host_permute_one, state);
+}
+int zl_poseidon_constants(zl_curve_t curve, unsigned width, uint64_t* keys, uint64_t* mds) {
+    if (!valid_curve(curve) || !pd::width_ok(width)) return ZL_EINVAL;
+    if (width == 3) return ZL_POS_CURVE(curve, constants_out, keys, mds);
+    return ZL_POS_WIDE(curve, width, constants_out, keys, mds);
+}
+int zl_poseidon_permute_batch_w(zl_ctx* ctx, zl_curve_t curve, unsigned width, uint64_t* states, size_t count) {
+    if (!pd::width_ok(width)) return ZL_EINVAL;
+    if (width == 3) return zl_poseidon_permute_batch(ctx, curve, states, count);
+    if (!valid_curve(curve) || (count && !states)) return ZL_EINVAL;
+    if (count == 0) return ZL_OK;
+    if (on_host(ctx, count)) return ZL_POS_WIDE(curve, width, host_permute_w, states, count);
+    ZL_HIP(ctx, hipSetDevice(ctx->device));
+    return ZL_POS_WIDE(curve, width, dev_permute_w, ctx, states, count);
+}
+int zl_poseidon_hash_batch(zl_ctx* ctx, zl_curve_t curve, unsigned arity, const uint64_t* in, size_t count, uint64_t* out) {
+    if (!pd::arity_ok(arity)) return ZL_EINVAL;
+    if (arity == 2) return zl_poseidon_hash2_batch(ctx, curve, in, count, out);
+    if (!valid_curve(curve) || (count && (!in || !out))) return ZL_EINVAL;
+    if (count == 0) return ZL_OK;
+    if (on_host(ctx, count)) return ZL_POS_WIDE(curve, arity + 1, host_hash_w, in, count, out);
+    ZL_HIP(ctx, hipSetDevice(ctx->device));
+    return ZL_POS_WIDE(curve, arity + 1, dev_hash_w, ctx, in, count, out);
+}
+int zl_poseidon_hash_batch_dev(zl_ctx* ctx, zl_curve_t curve, unsigned arity, const void* d_in, size_t count, void* d_out) {
+    if (!pd::arity_ok(arity)) return ZL_EINVAL;
+    if (arity == 2) return zl_poseidon_hash2_batch_dev(ctx, curve, d_in, count, d_out);
+    if (!ctx || !valid_curve(curve) || (count && (!d_in || !d_out))) return ZL_EINVAL;
+    if (count == 0) return ZL_OK;
+    ZL_HIP(ctx, hipSetDevice(ctx->device));
+    return ZL_POS_WIDE(curve, arity + 1, dev_hash_w_dev, ctx, d_in, count, d_out);
 }
 int zl_poseidon_chain_batch(zl_ctx* ctx, zl_curve_t curve, const uint64_t* x0, const uint64_t* x1, uint32_t k, size_t count, uint64_t* out) {
     if (!valid_curve(curve) || k == 0 || (count && (!x0 || !x1 || !out))) return ZL_EINVAL;

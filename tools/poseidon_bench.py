@@ -14,6 +14,11 @@ Every leg is checked before it is timed, its sides are interleaved in one proces
   merkle    zl_poseidon_merkle_build_dev at 2^10 .. 2^24 leaves (depth = log2 n) with the default tail; at 2^20 leaves the tail threshold T is swept over
             0, 16, 64, 256, 1024, and the upper T-leaf tree is also built alone with and without the tail kernel (the levels above the threshold).
   fold      zl_poseidon_merkle_roots_from_paths at depth 20 for 2^10 and 2^16 paths (host operands, copies included).
+  arity     (--arity: this leg alone, to profiles/poseidon_arity_bench.log) zl_poseidon_hash_batch at arities 2 .. 5 (widths 3 .. 6), 2^6 .. 2^22 items:
+            (dev) device operands, (hostptr) host operands, interleaved with (hash2 dev / hash2 hostptr) the width-3 hash2 leg as the scale and (loopT) the
+            loop a caller writes without the batch: zl_poseidon_permute_w sliced over the granted host threads (at most 2^12 permutations, scaled).  Up to
+            2^10 items also (pool) the ctx == NULL host path: a width whose device call at 64 items loses a repetition to it needs a larger DEV_MIN.
+            Derived: time per permutation against the product count of the plain schedule, 804 / 1 288 / 1 976 / 2 616.
 Checks: hash2 against the zl_poseidon_permute loop (all pairs up to 2^12, a sample of 256 above); trees up to 2^16 leaves against the host path node for
 node, larger ones by folding 32 gathered paths with the zl_poseidon_permute loop to the device's root; folds against the tree's root."""
 import argparse
@@ -141,6 +146,77 @@ def hash2_leg(be, curve, logs, threads, res):
             f"hostptr {row['worst_speedup_hostptr_vs_best_loop']:.1f}x, dev {row['worst_speedup_dev_vs_best_loop']:.1f}x")
 
 
+PRODUCTS = {3: 804, 4: 1288, 5: 1976, 6: 2616}  # 8 (3W + W^2) + partial (3 + W^2)
+
+
+def permute_w_loop(L, curve, width, states):
+    base = states.ctypes.data
+    u64p = C.POINTER(C.c_uint64)
+    f = L.zl_poseidon_permute_w
+    for i in range(states.shape[0]):
+        f(curve, width, C.cast(base + 32 * width * i, u64p))
+
+
+def arity_leg(be, curve, logs, threads, res):
+    L, name = be.L, NAMES[curve]
+    for lg in logs:
+        n = 1 << lg
+        xy = elems(2 * n, 100 + lg).reshape(n, 2, 4)
+        d_xy, d_h2 = dev_tensor(xy), dev_tensor(np.zeros((n, 4), dtype=np.uint64))
+        for arity in (2, 3, 4, 5):
+            width = arity + 1
+            xs = elems(arity * n, 900 + 10 * lg + arity).reshape(n, arity, 4)
+            d_in, d_out = dev_tensor(xs), dev_tensor(np.zeros((n, 4), dtype=np.uint64))
+            os.environ["ZL_TUNE_POSEIDON_DEV_MIN"] = "0"
+            got = be.poseidon_hash(curve, xs)
+            be.poseidon_hash_dev(curve, arity, d_in.data_ptr(), n, d_out.data_ptr())
+            assert np.array_equal(d_out.cpu().numpy().view(np.uint64).reshape(n, 4), got)
+            sample = np.arange(n) if n <= 256 else np.random.default_rng(lg).choice(n, 256, replace=False)
+            st = np.zeros((len(sample), width, 4), dtype=np.uint64)
+            st[:, 0, 0] = (1 << arity) - 1
+            st[:, 1:, :] = xs[sample]
+            permute_w_loop(L, curve, width, st)
+            assert np.array_equal(st[:, 0, :], got[sample]), "device digests differ from the zl_poseidon_permute_w loop"
+            m = min(n, 1 << 12)
+            lp = np.zeros((m, width, 4), dtype=np.uint64)
+            lp[:, 0, 0] = (1 << arity) - 1
+            lp[:, 1:, :] = xs[:m]
+            parts = [lp[i::threads].copy() for i in range(threads)] if m >= threads else [lp.copy()]
+            pool = ThreadPoolExecutor(max_workers=len(parts))
+
+            def loop_t():
+                list(pool.map(lambda p: permute_w_loop(L, curve, width, p), parts))
+
+            legs = {"dev": lambda: be.poseidon_hash_dev(curve, arity, d_in.data_ptr(), n, d_out.data_ptr()), "hostptr": lambda: be.poseidon_hash(curve, xs),
+                    "hash2_dev": lambda: be.poseidon_hash2_dev(curve, d_xy.data_ptr(), n, d_h2.data_ptr()), "hash2_hostptr": lambda: be.poseidon_hash2(curve, xy),
+                    "loopT": loop_t}
+            if n <= (1 << 10):
+                legs["pool"] = lambda: zb.poseidon_hash_host(curve, xs)
+            ts = interleaved(legs)
+            pool.shutdown()
+            ts["loopT"] = [t * (n / m) for t in ts["loopT"]]
+            row = {"curve": name, "log_n": lg, "arity": arity, "width": width}
+            for k, v in ts.items():
+                row[k + "_ms"] = statistics.median(v) * 1e3
+            row["dev_hashes_per_s"] = n / statistics.median(ts["dev"])
+            row["hostptr_hashes_per_s"] = n / statistics.median(ts["hostptr"])
+            row["dev_over_hash2_dev"] = statistics.median(ts["dev"]) / statistics.median(ts["hash2_dev"])
+            row["worst_dev_over_hash2_dev"] = max(ts["dev"]) / min(ts["hash2_dev"])
+            row["products_over_width3"] = PRODUCTS[width] / PRODUCTS[3]
+            row["worst_speedup_hostptr_vs_loopT"] = min(ts["loopT"]) / max(ts["hostptr"])
+            if "pool" in ts:
+                row["device_wins_every_repetition_vs_pool"] = max(ts["hostptr"]) < min(ts["pool"])
+            res["arity"].append(row)
+            say(f"arity {name} arity {arity} (width {width}) 2^{lg:<2d} dev {fmt(ts['dev'])} ({row['dev_hashes_per_s']:.3e} H/s) | hostptr {fmt(ts['hostptr'])} "
+                f"({row['hostptr_hashes_per_s']:.3e} H/s) | hash2 dev {fmt(ts['hash2_dev'])} | hash2 hostptr {fmt(ts['hash2_hostptr'])} | "
+                + (f"pool {fmt(ts['pool'])} (device wins every repetition: {row['device_wins_every_repetition_vs_pool']}) | " if "pool" in ts else "")
+                + f"loopT({len(parts)}) {fmt(ts['loopT'])} | dev / hash2 dev {row['dev_over_hash2_dev']:.2f} (worst pairing {row['worst_dev_over_hash2_dev']:.2f}; products "
+                f"{row['products_over_width3']:.2f}) | worst-case speedup of hostptr over loopT {row['worst_speedup_hostptr_vs_loopT']:.1f}x")
+            del d_in, d_out
+        del d_xy, d_h2
+        torch.cuda.empty_cache()
+
+
 def devmin_leg(be, curve, res):
     name = NAMES[curve]
     wins = {}
@@ -259,15 +335,21 @@ def fold_leg(be, curve, log_leaves, counts_log, res):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--quick", action="store_true", help="small sizes only (a functional pass of every leg)")
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "poseidon_bench.log"))
+    ap.add_argument("--arity", action="store_true", help="the arity leg alone (default output: profiles/poseidon_arity_bench.log)")
+    ap.add_argument("--out", default=None)
     args = ap.parse_args()
+    if args.out is None:
+        args.out = os.path.join(ROOT, "profiles", "poseidon_arity_bench.log" if args.arity else "poseidon_bench.log")
     torch.cuda.init()
     be = Backend(0)
     threads = max(1, min(16, len(os.sched_getaffinity(0))))
     say(f"# {be.describe()}")
     say(f"# host threads granted: {threads}; repetitions: {REPS}; legs interleaved in one process")
-    res = {"hash2": [], "devmin": [], "merkle": [], "merkle_top": [], "fold": []}
+    res = {"hash2": [], "devmin": [], "merkle": [], "merkle_top": [], "fold": [], "arity": []}
     for curve in (ZL_BLS12_381, ZL_BN254):
+        if args.arity:
+            arity_leg(be, curve, [6, 10] if args.quick else [6, 10, 14, 18, 22], threads, res)
+            continue
         hash2_leg(be, curve, [6, 10] if args.quick else [6, 10, 14, 18, 22], threads, res)
         devmin_leg(be, curve, res)
         merkle_leg(be, curve, [10, 12] if args.quick else [10, 16, 20, 24], 12 if args.quick else 20, res)
