@@ -84,6 +84,14 @@ int zl_groth16_prove_merkle_paths(zl_ctx* ctx, const zl_g16_pk* pk, uint64_t r1c
                                   const uint64_t* paths, const uint64_t* r, const uint64_t* s, size_t count, zl_g16_proof* proofs, uint64_t* roots_out);
 int zl_groth16_prove_merkle_members(zl_ctx* ctx, const zl_g16_pk* pk, uint64_t r1cs_handle, const void* d_nodes, size_t n, unsigned depth, const uint64_t* indices,
                                     const uint64_t* r, const uint64_t* s, size_t count, zl_g16_proof* proofs, uint64_t* root_out);
+/* The same out of a Merkle forest in device memory (zl_merkle_forest_* below): proof j shows that leaf indices[j] of tree tree_of[j] is in that tree, and is
+ * byte for byte what zl_groth16_prove_merkle_members returns on zl_merkle_forest_tree_nodes(f, tree_of[j]) with n = the forest's capacity and (r[j], s[j]).
+ * tree_of (count u32) and indices are HOST memory; roots_out (count x 4 u64, may be NULL) receives the root per proof -- the trees differ.  ctx is the forest's
+ * ctx or another lane of its device; the depth is the forest's.  Shape check, dispatch bounds and error order are zl_groth16_prove_merkle_members'; a NULL or
+ * host-mirror forest, a forest over another curve than the key's, a tree id >= trees or an index >= that tree's length: ZL_EINVAL before any work. */
+typedef struct zl_merkle_forest zl_merkle_forest;
+int zl_groth16_prove_forest_members(zl_ctx* ctx, const zl_g16_pk* pk, uint64_t r1cs_handle, const zl_merkle_forest* f, const uint32_t* tree_of, const uint64_t* indices,
+                                    const uint64_t* r, const uint64_t* s, size_t count, zl_g16_proof* proofs, uint64_t* roots_out);
 int zl_partials_sum(zl_curve_t curve, zl_group_t group, const uint64_t* partials, size_t count, uint64_t* out_xy, uint8_t* out_inf);
 /* wrap a canonical affine point (all-zero = infinity) as a partial, e.g. to fold an extra term into zl_partials_sum */
 int zl_partial_from_affine(zl_curve_t curve, zl_group_t group, const uint64_t* xy, uint64_t* out_partial);
@@ -257,6 +265,39 @@ int zl_poseidon_merkle_assignments_dev(zl_ctx* ctx, zl_curve_t curve, const void
                                        void* d_out, size_t stride_elems);
 int zl_poseidon_merkle_member_assignments_dev(zl_ctx* ctx, zl_curve_t curve, const void* d_nodes, size_t n, unsigned depth, const uint64_t* indices, size_t count,
                                               void* d_out, size_t stride_elems);
+/* ---- Merkle forest: `trees` (1 .. 65 536) growing trees in ONE allocation -- the reference's accumulator, trees that grow by push / extend
+ * (openzl-crypto/src/merkle_tree/tree.rs:287-345, 899-915) held as a fixed array with every leaf routed to one of them (forest.rs:30-40, 245-251, 465-565).
+ * Every tree has `depth` (1 .. 40) hash levels and room for `capacity` leaves (1 <= capacity <= 2^depth), over the arity-2 H and the rules of the Merkle family
+ * above: an absent right child is zero, a node with no leaf under it is zero (not H(0, 0)), the root is the node of level `depth`, zero for an empty tree.
+ * LAYOUT: tree t occupies S = zl_poseidon_merkle_nodes(capacity, depth) elements at element offset t * S; inside a tree the layout is that of
+ * zl_poseidon_merkle_build_dev for n = CAPACITY, whatever the tree's length.  The allocation is zero-filled at creation and only ever written where a leaf lies
+ * below.  So every _dev entry point above that takes (d_nodes, n, depth) -- zl_poseidon_merkle_paths_dev, zl_poseidon_merkle_member_assignments_dev,
+ * zl_groth16_prove_merkle_members -- works on ONE tree of the forest when called with zl_merkle_forest_tree_nodes(f, t) and n = capacity (they then accept an
+ * index up to the capacity; an index at or past the tree's length names an empty slot).  The trees' lengths live on the host.
+ * ctx == NULL: the HOST MIRROR -- the same layout in host memory, the same results byte for byte, updates through the host permutation over the host pool, no
+ * device opened.  Otherwise the ctx must outlive the forest (a fork of a ctx serves as well); work is issued on its stream (zl_ctx_set_stream is honoured)
+ * and has finished when a call returns.  One caller at a time per forest.  Staging goes through the ctx's Poseidon scratch under its 256 MiB budget and
+ * ZL_TUNE_POSEIDON_CHUNK (also the lanes of one launch); the node allocation is the forest's own.  An allocation that fails is ZL_ENOMEM, nothing leaked.
+ * _append: leaf i goes to tree tree_of[i], behind the leaves that tree already has, in input order (forest.rs push, leaf by leaf); then, level by level, ONE
+ *   launch hashes the parents of every touched tree that have a new leaf under them -- `depth` dependent permutations per append, however many trees it touches.
+ *   Checked on the host before any work: a tree id >= trees, an append that would take a tree past `capacity`, a host leaf >= r: ZL_EINVAL.  _append_dev reads the
+ *   leaves from DEVICE memory (count x 4 u64) and validates them in a pass of its own before the first node is written; a host-mirror forest is ZL_EINVAL there.
+ *   A refused append of either form leaves lengths and nodes exactly as they were.  count == 0: ZL_OK.
+ * _roots: trees x 4 u64.  _paths: the `depth` siblings of leaf indices[i] of tree tree_of[i], as zl_poseidon_merkle_paths on a fresh build of that tree's
+ *   leaves; an index >= that tree's length is ZL_EINVAL.  _tree_nodes: the address of tree t's node array (device memory; host memory for the mirror).
+ * _download: one tree's S elements.  _member_assignments_dev: row i = the row zl_poseidon_merkle_member_assignments_dev writes for leaf indices[i] of tree
+ *   tree_of[i] (word for word; d_out, stride_elems as there); host-mirror forest: ZL_EINVAL.  tree_of and indices are host memory everywhere. */
+int zl_merkle_forest_create(zl_ctx* ctx, zl_curve_t curve, uint32_t trees, unsigned depth, size_t capacity, zl_merkle_forest** out);
+void zl_merkle_forest_destroy(zl_merkle_forest* f); /* NULL is a no-op */
+int zl_merkle_forest_describe(const zl_merkle_forest* f, uint32_t* trees, unsigned* depth, size_t* capacity, size_t* tree_stride_elems); /* a NULL output is skipped */
+int zl_merkle_forest_lens(const zl_merkle_forest* f, uint64_t* lens);
+int zl_merkle_forest_append(zl_merkle_forest* f, const uint32_t* tree_of, const uint64_t* leaves, size_t count);
+int zl_merkle_forest_append_dev(zl_merkle_forest* f, const uint32_t* tree_of, const void* d_leaves, size_t count);
+int zl_merkle_forest_roots(const zl_merkle_forest* f, uint64_t* roots);
+int zl_merkle_forest_paths(const zl_merkle_forest* f, const uint32_t* tree_of, const uint64_t* indices, size_t count, uint64_t* paths);
+int zl_merkle_forest_tree_nodes(const zl_merkle_forest* f, uint32_t tree, const void** nodes);
+int zl_merkle_forest_download(const zl_merkle_forest* f, uint32_t tree, uint64_t* nodes);
+int zl_merkle_forest_member_assignments_dev(const zl_merkle_forest* f, const uint32_t* tree_of, const uint64_t* indices, size_t count, void* d_out, size_t stride_elems);
 /* Groth16::compile with rng = SplitMix64(seed): trapdoor setup, proving key generated on the device */
 int zl_groth16_compile(zl_ctx* ctx, const zl_circuit* c, uint64_t seed, zl_g16_keys** out);
 int zl_groth16_keys_trapdoor(const zl_g16_keys* k, uint64_t* out20); /* alpha, beta, gamma, delta, tau (canonical) */

@@ -6,7 +6,7 @@ bench; it never falls back to a CPU implementation: without the HIP library or w
 """
 from .backend import Backend, MultiBackend, BackendError, load_library, CURVES, ZL_BLS12_381, ZL_BN254, ZL_G1, ZL_G2  # noqa: F401
 from .backend import ZL_MONT, ZL_COSET, ZL_INVERSE, ZL_CHECK  # noqa: F401
-from .backend import Circuit, Groth16Keys, poseidon_permute, pairing, pairing_product  # noqa: F401
+from .backend import Circuit, Groth16Keys, MerkleForest, poseidon_permute, pairing, pairing_product  # noqa: F401
 from .backend import (poseidon_permute_batch_host, poseidon_hash2_host, poseidon_chain_host, poseidon_merkle_nodes, poseidon_merkle_root_host,  # noqa: F401
                       poseidon_merkle_build_host, poseidon_merkle_paths_host, poseidon_roots_from_paths_host, poseidon_chain_assignment_elems,
                       poseidon_chain_assignments_host, poseidon_merkle_assignment_elems, poseidon_merkle_assignments_host, poseidon_hash_host, poseidon_spec, poseidon_constants)

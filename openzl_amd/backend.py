@@ -43,6 +43,9 @@ ABI_SYMBOLS = [
     "zl_circuit_poseidon_merkle", "zl_circuit_poseidon_merkle_witness", "zl_poseidon_merkle_assignment_elems", "zl_poseidon_merkle_assignments",
     "zl_poseidon_merkle_assignments_dev", "zl_poseidon_merkle_member_assignments_dev", "zl_groth16_prove_merkle_paths", "zl_groth16_prove_merkle_members",
     "zl_poseidon_spec", "zl_poseidon_permute_w", "zl_poseidon_constants", "zl_poseidon_permute_batch_w", "zl_poseidon_hash_batch", "zl_poseidon_hash_batch_dev",
+    "zl_merkle_forest_create", "zl_merkle_forest_destroy", "zl_merkle_forest_describe", "zl_merkle_forest_lens", "zl_merkle_forest_append",
+    "zl_merkle_forest_append_dev", "zl_merkle_forest_roots", "zl_merkle_forest_paths", "zl_merkle_forest_tree_nodes", "zl_merkle_forest_download",
+    "zl_merkle_forest_member_assignments_dev", "zl_groth16_prove_forest_members",
 ]
 
 
@@ -167,6 +170,20 @@ def load_library(path: Optional[str] = None):
     L.zl_poseidon_merkle_member_assignments_dev.argtypes = [vp, C.c_int, vp, C.c_size_t, C.c_uint, u64p, C.c_size_t, vp, C.c_size_t]
     L.zl_groth16_prove_merkle_paths.argtypes = [vp, C.POINTER(G16PkC), C.c_uint64, C.c_uint, u64p, u64p, u64p, u64p, u64p, C.c_size_t, C.POINTER(G16ProofC), u64p]
     L.zl_groth16_prove_merkle_members.argtypes = [vp, C.POINTER(G16PkC), C.c_uint64, vp, C.c_size_t, C.c_uint, u64p, u64p, u64p, C.c_size_t, C.POINTER(G16ProofC), u64p]
+    u32p = C.POINTER(C.c_uint32)
+    L.zl_merkle_forest_create.argtypes = [vp, C.c_int, C.c_uint32, C.c_uint, C.c_size_t, C.POINTER(vp)]
+    L.zl_merkle_forest_destroy.argtypes = [vp]
+    L.zl_merkle_forest_destroy.restype = None
+    L.zl_merkle_forest_describe.argtypes = [vp, u32p, C.POINTER(C.c_uint), C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)]
+    L.zl_merkle_forest_lens.argtypes = [vp, u64p]
+    L.zl_merkle_forest_append.argtypes = [vp, u32p, u64p, C.c_size_t]
+    L.zl_merkle_forest_append_dev.argtypes = [vp, u32p, vp, C.c_size_t]
+    L.zl_merkle_forest_roots.argtypes = [vp, u64p]
+    L.zl_merkle_forest_paths.argtypes = [vp, u32p, u64p, C.c_size_t, u64p]
+    L.zl_merkle_forest_tree_nodes.argtypes = [vp, C.c_uint32, C.POINTER(vp)]
+    L.zl_merkle_forest_download.argtypes = [vp, C.c_uint32, u64p]
+    L.zl_merkle_forest_member_assignments_dev.argtypes = [vp, u32p, u64p, C.c_size_t, vp, C.c_size_t]
+    L.zl_groth16_prove_forest_members.argtypes = [vp, C.POINTER(G16PkC), C.c_uint64, vp, u32p, u64p, u64p, u64p, C.c_size_t, C.POINTER(G16ProofC), u64p]
     L.zl_groth16_compile.argtypes = [vp, vp, C.c_uint64, C.POINTER(vp)]
     L.zl_groth16_keys_free.argtypes = [vp]
     L.zl_groth16_keys_free.restype = None
@@ -711,6 +728,16 @@ class Backend:
         (`count` proofs of membership, the tree's root (4,): every proof's public input; zero when count == 0)"""
         pkc, keep_pk = _pk_struct(curve, pk)
         return self._prove_merkle_members(pkc, curve, r1cs_handle, d_nodes, n, depth, indices, r, s)
+
+    def _prove_forest_members(self, pkc, curve: int, r1cs_handle: int, forest: "MerkleForest", tree_of, indices, r: np.ndarray, s: np.ndarray):
+        tr, idx = _forest_items(tree_of, indices)
+        count = idx.size
+        r, s = np.ascontiguousarray(r, dtype=np.uint64).reshape(count, 4), np.ascontiguousarray(s, dtype=np.uint64).reshape(count, 4)
+        out = (G16ProofC * max(1, count))()
+        roots = np.zeros((count, 4), dtype=np.uint64)
+        self._check(self.L.zl_groth16_prove_forest_members(self._ctx, C.byref(pkc), r1cs_handle, forest._f, _p32(tr), _ptr_or_none(idx), _ptr_or_none(r), _ptr_or_none(s),
+                                                           count, out, _ptr_or_none(roots)), "zl_groth16_prove_forest_members")
+        return [_proof_tuple(curve, p) for p in out[:count]], roots
 
     def groth16_last_h(self, n: int) -> np.ndarray:
         out = np.zeros((n, 4), dtype=np.uint64)
@@ -1422,6 +1449,106 @@ def poseidon_roots_from_paths_host(curve: int, leaves, indices, paths, depth: in
     return _poseidon_roots_from_paths(load_library(), None, curve, leaves, indices, paths, depth)
 
 
+def _p32(a: np.ndarray):
+    return a.ctypes.data_as(C.POINTER(C.c_uint32)) if a.size else None
+
+
+def _forest_items(tree_of, indices):
+    """(tree_of as contiguous uint32, indices as contiguous uint64), one entry per item"""
+    tr = np.ascontiguousarray(tree_of, dtype=np.uint32).reshape(-1)
+    idx = np.ascontiguousarray(indices, dtype=np.uint64).reshape(-1)
+    if tr.size != idx.size:
+        raise ValueError("tree_of and indices name the same items")
+    return tr, idx
+
+
+class MerkleForest:
+    """zl_merkle_forest: `trees` growing Merkle trees of `depth` hash levels and room for `capacity` leaves each in one allocation -- device memory of `backend`
+    (which must outlive the forest), or host memory when backend is None (the host mirror: same layout, same bytes, no device).  Tree t's node array has the
+    layout of poseidon_merkle_build_dev for n = capacity, so tree_nodes(t) with n = capacity serves every (d_nodes, n, depth) entry point of Backend."""
+
+    def __init__(self, backend: Optional[Backend], curve: int, trees: int, depth: int, capacity: int):
+        self.L = backend.L if backend is not None else load_library()
+        self.backend, self.curve = backend, curve
+        self._f = C.c_void_p()
+        self._check(self.L.zl_merkle_forest_create(backend._ctx if backend is not None else None, curve, trees, depth, capacity, C.byref(self._f)), "zl_merkle_forest_create")
+        t, d, c, st = C.c_uint32(), C.c_uint(), C.c_size_t(), C.c_size_t()
+        self._check(self.L.zl_merkle_forest_describe(self._f, C.byref(t), C.byref(d), C.byref(c), C.byref(st)), "zl_merkle_forest_describe")
+        self.trees, self.depth, self.capacity, self.tree_stride = t.value, d.value, c.value, st.value
+
+    def _check(self, rc: int, what: str):
+        _pos_check(self.L, rc, what)
+
+    def append(self, tree_of, leaves):
+        """leaf i (host, (count, 4) canonical words) goes to tree tree_of[i], behind the leaves that tree already has, in input order"""
+        tr = np.ascontiguousarray(tree_of, dtype=np.uint32).reshape(-1)
+        lv = _elems(leaves, 1)
+        if lv.shape[0] != tr.size:
+            raise ValueError("one tree id per leaf")
+        self._check(self.L.zl_merkle_forest_append(self._f, _p32(tr), _ptr_or_none(lv), tr.size), "zl_merkle_forest_append")
+
+    def append_dev(self, tree_of, d_leaves: int, count: int):
+        """append with the `count` leaves at the device address d_leaves (validated on the device before anything is written)"""
+        tr = np.ascontiguousarray(tree_of, dtype=np.uint32).reshape(-1)
+        if tr.size != count:
+            raise ValueError("one tree id per leaf")
+        self._check(self.L.zl_merkle_forest_append_dev(self._f, _p32(tr), C.c_void_p(d_leaves) if count else None, count), "zl_merkle_forest_append_dev")
+
+    def lens(self) -> np.ndarray:
+        out = np.zeros(self.trees, dtype=np.uint64)
+        self._check(self.L.zl_merkle_forest_lens(self._f, _p64(out)), "zl_merkle_forest_lens")
+        return out
+
+    def roots(self) -> np.ndarray:
+        out = np.zeros((self.trees, 4), dtype=np.uint64)
+        self._check(self.L.zl_merkle_forest_roots(self._f, _p64(out)), "zl_merkle_forest_roots")
+        return out
+
+    def paths(self, tree_of, indices) -> np.ndarray:
+        """(count, depth, 4): the siblings of leaf indices[i] of tree tree_of[i], bottom up"""
+        tr, idx = _forest_items(tree_of, indices)
+        out = np.zeros((max(1, idx.size), self.depth, 4), dtype=np.uint64)
+        self._check(self.L.zl_merkle_forest_paths(self._f, _p32(tr), _ptr_or_none(idx), idx.size, _p64(out)), "zl_merkle_forest_paths")
+        return out[: idx.size]
+
+    def tree_nodes(self, tree: int) -> int:
+        """the address of tree `tree`'s node array (device memory; host memory for the mirror)"""
+        p = C.c_void_p()
+        self._check(self.L.zl_merkle_forest_tree_nodes(self._f, tree, C.byref(p)), "zl_merkle_forest_tree_nodes")
+        return p.value
+
+    def download(self, tree: int) -> np.ndarray:
+        """(tree_stride, 4): every node of one tree, in the capacity's layout"""
+        out = np.zeros((self.tree_stride, 4), dtype=np.uint64)
+        self._check(self.L.zl_merkle_forest_download(self._f, tree, _p64(out)), "zl_merkle_forest_download")
+        return out
+
+    def member_assignments_dev(self, tree_of, indices, d_out: int, stride_elems: Optional[int] = None):
+        """zl_merkle_forest_member_assignments_dev: row i (at d_out + i * stride_elems elements; default the row length) = the membership of leaf indices[i] of
+        tree tree_of[i], as Backend.poseidon_merkle_member_assignments_dev writes it for that tree"""
+        tr, idx = _forest_items(tree_of, indices)
+        stride = self.L.zl_poseidon_merkle_assignment_elems(self.depth) if stride_elems is None else stride_elems
+        self._check(self.L.zl_merkle_forest_member_assignments_dev(self._f, _p32(tr), _ptr_or_none(idx), idx.size, C.c_void_p(d_out), stride),
+                    "zl_merkle_forest_member_assignments_dev")
+
+    def close(self):
+        if self._f:
+            self.L.zl_merkle_forest_destroy(self._f)
+            self._f = C.c_void_p()
+
+    def __enter__(self) -> "MerkleForest":
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 def pairing_product(backend: "Backend", curve: int, ps: np.ndarray, qs: np.ndarray) -> np.ndarray:
     """prod_i e(P_i, Q_i) with the Miller loops on backend's GPU (Backend.pairing_product)"""
     return backend.pairing_product(curve, ps, qs)
@@ -1721,6 +1848,12 @@ class Groth16Keys:
         depth) and leaf indices (count,) -> (proofs, the root (4,)): from tree to proofs with nothing but the indices going up"""
         d = self._merkle_ready("prove_merkle_members")
         return (lane or self.backend)._prove_merkle_members(self.pk, self.circuit.curve, self._r1cs, d_nodes, n, d, indices, r, s)
+
+    def prove_forest_members(self, forest: "MerkleForest", tree_of, indices, r: np.ndarray, s: np.ndarray, lane: Optional[Backend] = None):
+        """zl_groth16_prove_forest_members over this key: proof j shows that leaf indices[j] of tree tree_of[j] of the device forest (of the keys' depth) is in that
+        tree -> (proofs, roots (count, 4): each proof's public input); byte for byte prove_merkle_members on forest.tree_nodes(tree_of[j]) with n = the capacity"""
+        self._merkle_ready("prove_forest_members")
+        return (lane or self.backend)._prove_forest_members(self.pk, self.circuit.curve, self._r1cs, forest, tree_of, indices, r, s)
 
     def prove_many(self, seeds, circuits=None):
         """zl_groth16_prove_circuits: a stream of proofs over this key on two prover lanes (two host threads inside the library); proofs[i] is what

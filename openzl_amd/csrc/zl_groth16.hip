@@ -1312,6 +1312,27 @@ extern "C" int zl_groth16_prove_merkle_members(zl_ctx* ctx, const zl_g16_pk* pk,
     }
     return rc;
 }
+// zl_groth16_prove_merkle_members with a tree per proof: the rows come out of a Merkle forest (ForestSrc of zl_poseidon_dev.hip), the roots with them
+extern "C" int zl_groth16_prove_forest_members(zl_ctx* ctx, const zl_g16_pk* pk, uint64_t r1cs_handle, const zl_merkle_forest* f, const uint32_t* tree_of,
+                                               const uint64_t* indices, const uint64_t* r, const uint64_t* s, size_t count, zl_g16_proof* proofs, uint64_t* roots_out) {
+    int fcurve = 0;
+    unsigned depth = 0;
+    if (zl_merkle_forest_prover_view(f, ctx, &fcurve, &depth)) return ZL_EINVAL;
+    const zl_r1cs_dev* rd = nullptr;
+    const int rc0 = g16_merkle_checks(ctx, pk, r1cs_handle, depth, !(count && (!tree_of || !indices || !r || !s || !proofs)), &rd);
+    if (rc0) return rc0;
+    if ((int)pk->curve != fcurve || zl_merkle_forest_members_ok(f, tree_of, indices, count)) return ZL_EINVAL;
+    if (count == 0) return ZL_OK;
+    const size_t nv = zl_poseidon_merkle_assignment_elems(depth);
+    G16BatchSource src;
+    src.fill_dev = [=](size_t c0, size_t ch, void* d_rows) {
+        return zl_merkle_forest_member_rows(ctx, f, tree_of + c0, indices + c0, ch, d_rows, nv, nullptr, roots_out ? roots_out + c0 * 4 : nullptr);
+    };
+    src.fill_host = [=](size_t c0, size_t ch, uint64_t* rows) {
+        return zl_merkle_forest_member_rows(ctx, f, tree_of + c0, indices + c0, ch, nullptr, nv, rows, roots_out ? roots_out + c0 * 4 : nullptr);
+    };
+    return groth16_prove_batch_any(ctx, pk, rd, src, 0, r, s, count, proofs);
+}
 extern "C" int zl_groth16_last_h(zl_ctx* ctx, uint64_t* out, size_t n) {
     if (!ctx || !out || !ctx->g16_h || n > ctx->g16_h_n) return ZL_EINVAL;
     ZL_HIP(ctx, hipMemcpyAsync(out, ctx->g16_h, n * 32, hipMemcpyDeviceToHost, ctx->stream));

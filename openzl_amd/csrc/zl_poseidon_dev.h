@@ -84,3 +84,12 @@ int zl_poseidon_merkle_trace_rows(zl_ctx* ctx, int curve, const uint64_t* leaves
                                   size_t stride_elems, uint64_t* roots_out);
 int zl_poseidon_merkle_member_rows(zl_ctx* ctx, int curve, const void* d_nodes, size_t n, unsigned depth, const uint64_t* indices, size_t count, void* d_rows,
                                    size_t stride_elems, uint64_t* host_rows);
+// The forest producer of the fused prover (zl_groth16_prove_forest_members).  _prover_view: ZL_EINVAL for a null or host-mirror forest or a ctx of another
+// device, else the forest's curve and depth.  _members_ok: ZL_EINVAL unless every (tree_of[i], indices[i]) names a leaf the forest holds.  _member_rows:
+// zl_poseidon_merkle_member_rows with a tree per item, issued on ctx (the forest's own ctx or another lane of its device); roots_out (host, may be null)
+// receives the root of every item.
+struct zl_merkle_forest;
+int zl_merkle_forest_prover_view(const zl_merkle_forest* f, const zl_ctx* ctx, int* curve, unsigned* depth);
+int zl_merkle_forest_members_ok(const zl_merkle_forest* f, const uint32_t* tree_of, const uint64_t* indices, size_t count);
+int zl_merkle_forest_member_rows(zl_ctx* ctx, const zl_merkle_forest* f, const uint32_t* tree_of, const uint64_t* indices, size_t count, void* d_rows, size_t stride_elems,
+                                 uint64_t* host_rows, uint64_t* roots_out);

@@ -15,6 +15,10 @@
 //   k_pos_tail       one workgroup finishes ALL remaining levels of a Merkle tree once a level has at most T nodes: the level lives in LDS (two buffers,
 //                    canonical words), __syncthreads() between levels, every level is also written to the node array at the offsets the wide path uses.
 //   k_pos_gather     sibling digests of `count` leaves out of a device node array.
+//   k_pos_forest_place / _level / _gather   the Merkle forest (zl_merkle_forest_*): many growing trees in one allocation, each in the node layout of its capacity.
+//                    An append places its leaves, then hashes per level the parents with a new leaf below them -- one lane each, ALL touched trees in one
+//                    launch, the lane's tree found by binary search in the level's prefix sums; no one-workgroup tail.  ForestSrc lets k_pos_merkle_trace
+//                    read memberships out of it.  With a null ctx the forest is its host mirror in host memory (host_forest_append).
 //   k_pos_permute_w / k_pos_hash_w   widths 4, 5, 6 (arity 3, 4, 5 of pd::spec): their own permutation permute_w<FrP, W> on W state registers and a table per
 //                    (curve, width); the S-box reduces its input weakly where the lazy bound requires it (the argument stands above WideBounds).  Width 3 keeps
 //                    the kernels above; the entry points of every arity forward to them at arity 2.
@@ -37,6 +41,19 @@
 
 using namespace openzl;
 namespace pd = openzl::poseidon_dev;
+
+// The Merkle forest behind zl_merkle_forest_* (include/zl_backend_ext.h): `trees` node arrays of `stride` = zl_poseidon_merkle_nodes(capacity, depth) elements
+// each in ONE allocation -- device memory of ctx's device, or host memory when ctx is null (the host mirror) -- and the trees' lengths, which live on the host.
+struct zl_merkle_forest {
+    zl_ctx* ctx = nullptr;
+    zl_curve_t curve = ZL_BLS12_381;
+    uint32_t trees = 0;
+    unsigned depth = 0;
+    size_t capacity = 0, stride = 0;
+    uint64_t* nodes = nullptr;
+    std::vector<uint64_t> lens;
+    std::vector<uint64_t> add;  // an append's leaves per tree while it is planned; all zero between calls
+};
 
 namespace {
 // ---------------------------------------------------------------------------------------------------------------- element I/O of the host path (Fp<FrP>)
@@ -380,6 +397,20 @@ struct TreeSrc {
     }
     TreeSrc advanced(size_t) const { return *this; }
 };
+// ... or one tree per item out of a Merkle forest: tree tree_of[p] starts `stride` elements after its predecessor and has the layout of the forest's CAPACITY
+// (lt), whatever its length; a node that no leaf lies under is stored as zero there, which is what an absent sibling reads as.
+struct ForestSrc {
+    const uint64_t* nodes;
+    size_t stride;
+    const uint32_t* tree_of;  // device memory, one entry per item of the launch
+    LevelTable lt;
+    __device__ __forceinline__ const uint64_t* leaf(size_t p, uint64_t idx) const { return nodes + ((size_t)tree_of[p] * stride + idx) * 4; }
+    __device__ __forceinline__ const uint64_t* sibling(size_t p, uint64_t idx, unsigned k) const {
+        const uint64_t sib = (idx >> k) ^ 1;
+        return sib < lt.size[k] ? nodes + ((size_t)tree_of[p] * stride + lt.off[k] + sib) * 4 : nullptr;
+    }
+    ForestSrc advanced(size_t) const { return *this; }  // (tree_of is staged per chunk: merkle_trace_run)
+};
 __device__ __forceinline__ void copy16(uint64_t* dst16, uint64_t a, uint64_t b, uint64_t c, uint64_t d) {  // one element of canonical words, dst 16-byte aligned
     ulonglong2* q = reinterpret_cast<ulonglong2*>(dst16);
     q[0] = make_ulonglong2(a, b);
@@ -431,6 +462,88 @@ __global__ __launch_bounds__(BLOCK) void k_pos_merkle_trace(const uint32_t* __re
     copy16(row, 1, 0, 0, 0);
     dstore16<FrP>(row + 4, cur);
     if (pub) dstore<FrP>(pub + p * 4, cur);
+}
+
+// ---------------------------------------------------------------------------------------------------------------- the Merkle forest (zl_merkle_forest_*)
+// `trees` trees side by side in one allocation, tree t at t * stride elements in the layout of zl_poseidon_merkle_build_dev for n = capacity; zero-filled at
+// creation and written only where a leaf lies below.  An append places its leaves, then hashes level after level the parents that have a new leaf under them:
+// ONE launch per level over all touched trees (split only at the launch chunk), never a one-workgroup tail -- a level costs one permutation latency whichever
+// way it is launched, so the trees of a batch share each level's latency instead of queueing behind each other.
+template <class FrP>
+ZL_HD bool canon_words(const uint64_t* w) {  // the value of four u64 words is below r
+    uint64_t br = 0;
+#pragma unroll
+    for (int i = 0; i < 8; i++) br = (((uint64_t)(uint32_t)(w[i / 2] >> (32 * (i & 1))) - FrP::mod(i) - br) >> 32) & 1;
+    return br != 0;
+}
+// one lane per new leaf: refuse it when it is not below r (the flag word; nothing is stored), else store it at element dst[p] of the allocation -- level 0 of
+// its tree, the slot the host computed.  nodes == nullptr: check only (the validation pass of zl_merkle_forest_append_dev; dst is not read).
+template <class FrP>
+__global__ __launch_bounds__(BLOCK) void k_pos_forest_place(const uint64_t* __restrict__ leaves, const uint64_t* __restrict__ dst, size_t n, uint64_t* __restrict__ nodes,
+                                                            uint32_t* __restrict__ flag) {
+    const size_t p = (size_t)blockIdx.x * BLOCK + threadIdx.x;
+    if (p >= n) return;
+    uint64_t w[4];
+#pragma unroll
+    for (int i = 0; i < 4; i++) w[i] = leaves[p * 4 + i];
+    if (!canon_words<FrP>(w)) {
+        atomicOr(flag, 1u);
+        return;
+    }
+    if (!nodes) return;
+    uint64_t* at = nodes + dst[p] * 4;
+#pragma unroll
+    for (int i = 0; i < 4; i++) at[i] = w[i];
+}
+// The trees an append touches: tree[s] grew from first[s] to some larger length, so at level k it has the dirty parents first[s] >> k .. (last leaf) >> k, and
+// pre[s] of them lie in the segments in front of s (pre has count + 1 entries, strictly increasing; pre[count] = the level's total).  All device memory.
+struct ForestSegs {
+    const uint32_t* tree;
+    const uint64_t* first;
+    const uint64_t* pre;  // the row of the launch's level
+    uint32_t count;
+};
+// the segment of dirty parent q: the largest s with pre[s] <= q (q < pre[count]); at most 17 steps for 65 536 trees
+ZL_HD uint32_t forest_seg(const uint64_t* pre, uint32_t count, uint64_t q) {
+    uint32_t lo = 0, hi = count;
+    while (hi - lo > 1) {
+        const uint32_t mid = lo + (hi - lo) / 2;
+        if (pre[mid] <= q) lo = mid;
+        else hi = mid;
+    }
+    return lo;
+}
+// one lane per dirty parent of level k, over every touched tree: parent j = H(child 2j, child 2j + 1 -- zero beyond the capacity's level k - 1).  Lane p of the
+// launch is dirty parent first + p of the level.  child_off / parent_off: the elements in front of levels k - 1 and k inside a tree.
+template <class FrP>
+__global__ __launch_bounds__(BLOCK) void k_pos_forest_level(const uint32_t* __restrict__ tab, uint64_t* nodes, size_t stride, const ForestSegs sg, unsigned k, size_t child_off,
+                                                            size_t child_size, size_t parent_off, size_t first, size_t n, uint32_t* __restrict__ flag) {
+    const size_t p = (size_t)blockIdx.x * BLOCK + threadIdx.x;
+    if (p >= n) return;
+    const uint64_t q = first + p;
+    const uint32_t s = forest_seg(sg.pre, sg.count, q);
+    const size_t j = (size_t)(sg.first[s] >> k) + (size_t)(q - sg.pre[s]);
+    uint64_t* tree = nodes + (size_t)sg.tree[s] * stride * 4;
+    const uint64_t* left = tree + (child_off + 2 * j) * 4;
+    uint64_t* parent = tree + (parent_off + j) * 4;
+    El<FrP> x, y = ezero<FrP>();
+    bool ok = dload<FrP>(left, x);
+    if (2 * j + 1 < child_size) ok &= dload<FrP>(left + 4, y);
+    if (!ok) atomicOr(flag, 1u);
+    dstore<FrP>(parent, hash2_dev<FrP>(tab, x, y));
+}
+// k_pos_gather with a tree per item: thread t = item t / depth, level t % depth
+__global__ __launch_bounds__(BLOCK) void k_pos_forest_gather(const uint64_t* __restrict__ nodes, size_t stride, LevelTable lt, unsigned depth, const uint32_t* __restrict__ tree_of,
+                                                             const uint64_t* __restrict__ indices, size_t total, uint64_t* __restrict__ paths) {
+    const size_t t = (size_t)blockIdx.x * BLOCK + threadIdx.x;
+    if (t >= total) return;
+    const size_t p = t / depth;
+    const unsigned k = (unsigned)(t % depth);
+    const uint64_t sib = (indices[p] >> k) ^ 1;
+    const bool present = sib < lt.size[k];
+    const uint64_t* tree = nodes + (size_t)tree_of[p] * stride * 4;
+#pragma unroll
+    for (int i = 0; i < 4; i++) paths[t * 4 + i] = present ? tree[(lt.off[k] + sib) * 4 + i] : 0;
 }
 
 // ---------------------------------------------------------------------------------------------------------------- widths 4, 5, 6 (arity 3, 4, 5)
@@ -1150,16 +1263,18 @@ struct HostPaths {
 };
 template <class FrP, class Src>
 int merkle_trace_run(zl_ctx* ctx, Src src, const HostPaths* hp, const uint64_t* indices, unsigned depth, size_t count, uint64_t* d_rows, size_t stride, uint64_t* host_rows,
-                     uint64_t* host_pub) {
+                     uint64_t* host_pub, const uint32_t* trees = nullptr) {
     const uint32_t* tab;
     int rc = get_table<FrP>(ctx, &tab);
     if (rc) return rc;
     const size_t nv = pd::merkle_row_elems(depth);
-    const size_t per = 8 + 32 + (hp ? 32 + (size_t)depth * 32 : 0) + (host_rows ? nv * 32 : 0);
+    constexpr bool forest = std::is_same<Src, ForestSrc>::value;  // `trees` (host memory): the tree of every item, staged behind everything else
+    const size_t per = 8 + 32 + (hp ? 32 + (size_t)depth * 32 : 0) + (host_rows ? nv * 32 : 0) + (forest ? 4 : 0);
     const size_t chunk = stage_items(per), m0 = count < chunk ? count : chunk;
     const size_t o_pub = up256(m0 * 8), o_leaf = o_pub + up256(m0 * 32), o_path = o_leaf + (hp ? up256(m0 * 32) : 0), o_rows = o_path + (hp ? up256(m0 * depth * 32) : 0);
+    const size_t o_tree = o_rows + (host_rows ? up256(m0 * nv * 32) : 0);
     Stage s;
-    if ((rc = stage_get(ctx, o_rows + (host_rows ? m0 * nv * 32 : 0), &s))) return rc;
+    if ((rc = stage_get(ctx, forest ? o_tree + m0 * 4 : o_rows + (host_rows ? m0 * nv * 32 : 0), &s))) return rc;
     uint64_t* d_idx = reinterpret_cast<uint64_t*>(s.data);
     uint64_t* d_pub = host_pub ? reinterpret_cast<uint64_t*>(s.data + o_pub) : nullptr;
     uint64_t* d_leaf = reinterpret_cast<uint64_t*>(s.data + o_leaf);
@@ -1175,6 +1290,11 @@ int merkle_trace_run(zl_ctx* ctx, Src src, const HostPaths* hp, const uint64_t* 
                 ZL_HIP(ctx, hipMemcpyAsync(d_path, hp->paths + first * depth * 4, m * depth * 32, hipMemcpyHostToDevice, ctx->stream));
                 from = PathSrc{d_leaf, d_path, depth};
             }
+        }
+        if constexpr (forest) {
+            uint32_t* d_tree = reinterpret_cast<uint32_t*>(s.data + o_tree);
+            ZL_HIP(ctx, hipMemcpyAsync(d_tree, trees + first, m * 4, hipMemcpyHostToDevice, ctx->stream));
+            from.tree_of = d_tree;
         }
         uint64_t* rows = host_rows ? d_stage_rows : d_rows + first * stride * 4;
         ZL_POS_LAUNCH(ctx, (k_pos_merkle_trace<FrP, Src>), blocks_of(m), BLOCK, 0, tab, from, d_idx, depth, m, rows, host_rows ? nv : stride, d_pub, s.flag);
@@ -1198,6 +1318,163 @@ template <class FrP>
 int dev_merkle_from_tree(zl_ctx* ctx, const void* d_nodes, size_t n, unsigned depth, const uint64_t* indices, size_t count, void* d_rows, size_t stride, uint64_t* host_rows) {
     const TreeSrc src{static_cast<const uint64_t*>(d_nodes), level_table(n, depth)};
     return merkle_trace_run<FrP, TreeSrc>(ctx, src, nullptr, indices, depth, count, static_cast<uint64_t*>(d_rows), stride, host_rows, nullptr);
+}
+
+// ---------------------------------------------------------------------------------------------------------------- the Merkle forest: host side
+// What an append does, worked out on the host before anything is written: the slot of every leaf, the touched trees (in the order the input first names them)
+// with their lengths before and after, and per level k = 1 .. depth the exclusive prefix sums of the trees' dirty ranges (row k - 1 of `pre`, T + 1 entries).
+struct ForestPlan {
+    std::vector<uint64_t> dst;
+    std::vector<uint32_t> seg_tree;
+    std::vector<uint64_t> seg_a, seg_b;
+    std::vector<uint64_t> pre;
+};
+// ZL_EINVAL for a tree id >= trees or a tree that would grow past the capacity; the forest's lengths are not changed here (forest_commit)
+int forest_plan(zl_merkle_forest* f, const uint32_t* tree_of, size_t count, ForestPlan& pl) {
+    try {
+        pl.dst.resize(count);
+        bool ok = true;
+        for (size_t i = 0; i < count && ok; i++) {
+            const uint32_t t = tree_of[i];
+            if (t >= f->trees) {
+                ok = false;
+                break;
+            }
+            if (f->add[t] == 0) pl.seg_tree.push_back(t);
+            pl.dst[i] = (uint64_t)t * f->stride + f->lens[t] + f->add[t];
+            f->add[t]++;
+        }
+        const size_t T = pl.seg_tree.size();
+        pl.seg_a.resize(T);
+        pl.seg_b.resize(T);
+        for (size_t s = 0; s < T; s++) {
+            const uint32_t t = pl.seg_tree[s];
+            pl.seg_a[s] = f->lens[t];
+            pl.seg_b[s] = f->lens[t] + f->add[t];
+            if (pl.seg_b[s] > f->capacity) ok = false;
+            f->add[t] = 0;
+        }
+        if (!ok) return ZL_EINVAL;
+        pl.pre.resize((size_t)f->depth * (T + 1));
+        for (unsigned k = 1; k <= f->depth; k++) {
+            uint64_t* row = pl.pre.data() + (size_t)(k - 1) * (T + 1);
+            row[0] = 0;
+            for (size_t s = 0; s < T; s++) row[s + 1] = row[s] + (((pl.seg_b[s] - 1) >> k) - (pl.seg_a[s] >> k) + 1);
+        }
+    } catch (const std::bad_alloc&) {
+        for (const uint32_t t : pl.seg_tree) f->add[t] = 0;
+        return ZL_ENOMEM;
+    }
+    return ZL_OK;
+}
+void forest_commit(zl_merkle_forest* f, const ForestPlan& pl) {
+    for (size_t s = 0; s < pl.seg_tree.size(); s++) f->lens[pl.seg_tree[s]] = pl.seg_b[s];
+}
+template <class FrP>
+bool host_all_canon(const uint64_t* elems, size_t count) {
+    for (size_t i = 0; i < count; i++)
+        if (!canon_words<FrP>(elems + i * 4)) return false;
+    return true;
+}
+// the host mirror's append: the leaves, then every level's dirty parents over the host pool -- the arithmetic of k_pos_forest_level through permute_native
+template <class FrP>
+int host_forest_append(zl_merkle_forest* f, const ForestPlan& pl, const uint64_t* leaves, size_t count) {
+    consts<FrP>();
+    for (size_t i = 0; i < count; i++) memcpy(f->nodes + pl.dst[i] * 4, leaves + i * 4, 32);
+    const uint32_t T = (uint32_t)pl.seg_tree.size();
+    bool ok = true;
+    for (unsigned k = 1; k <= f->depth; k++) {
+        const uint64_t* row = pl.pre.data() + (size_t)(k - 1) * (T + 1);
+        const size_t child_off = pd::level_offset(f->capacity, k - 1), child_size = pd::level_size(f->capacity, k - 1), parent_off = child_off + child_size;
+        ok &= host_for((size_t)row[T], [&](size_t q) {
+            const uint32_t s = forest_seg(row, T, q);
+            const size_t j = (size_t)(pl.seg_a[s] >> k) + (size_t)(q - row[s]);
+            uint64_t* tree = f->nodes + (size_t)pl.seg_tree[s] * f->stride * 4;
+            const uint64_t* child = tree + child_off * 4;
+            return host_hash2<FrP>(child + 2 * j * 4, 2 * j + 1 < child_size ? child + (2 * j + 1) * 4 : nullptr, tree + (parent_off + j) * 4);
+        });
+    }
+    return ok ? ZL_OK : ZL_EINVAL;
+}
+// The device append.  Staging (ZL_SLOT_POSEIDON): the touched-tree table and the prefix rows, uploaded once, then one chunk of leaves (host form) and their
+// slots at a time.  Device leaves are validated in launches of their own, and the flag is read back, before the first node is written; host leaves were
+// checked by the caller.  Every staged chunk is placed before level 1 is hashed; the launches of a level follow those of the level below on the stream.
+template <class FrP>
+int dev_forest_append(zl_merkle_forest* f, const ForestPlan& pl, const uint64_t* leaves, const uint64_t* d_leaves, size_t count) {
+    zl_ctx* ctx = f->ctx;
+    const uint32_t* tab;
+    int rc = get_table<FrP>(ctx, &tab);
+    if (rc) return rc;
+    const size_t T = pl.seg_tree.size(), launch = tune_chunk();
+    const size_t chunk = stage_items(leaves ? 40 : 8), m0 = count < chunk ? count : chunk;
+    const size_t o_first = up256(T * 4), o_pre = o_first + up256(T * 8), o_leaf = o_pre + up256(pl.pre.size() * 8), o_dst = o_leaf + (leaves ? up256(m0 * 32) : 0);
+    Stage s;
+    if ((rc = stage_get(ctx, o_dst + m0 * 8, &s))) return rc;
+    if (d_leaves) {
+        for (size_t first = 0; first < count; first += launch) {
+            const size_t m = count - first < launch ? count - first : launch;
+            ZL_POS_LAUNCH(ctx, (k_pos_forest_place<FrP>), blocks_of(m), BLOCK, 0, d_leaves + first * 4, nullptr, m, nullptr, s.flag);
+        }
+        if ((rc = finish(ctx, s.flag))) return rc;  // (the flag word is still zero when this passes)
+    }
+    uint32_t* d_tree = reinterpret_cast<uint32_t*>(s.data);
+    uint64_t* d_first = reinterpret_cast<uint64_t*>(s.data + o_first);
+    uint64_t* d_pre = reinterpret_cast<uint64_t*>(s.data + o_pre);
+    uint64_t* d_leaf = reinterpret_cast<uint64_t*>(s.data + o_leaf);
+    uint64_t* d_dst = reinterpret_cast<uint64_t*>(s.data + o_dst);
+    ZL_HIP(ctx, hipMemcpyAsync(d_tree, pl.seg_tree.data(), T * 4, hipMemcpyHostToDevice, ctx->stream));
+    ZL_HIP(ctx, hipMemcpyAsync(d_first, pl.seg_a.data(), T * 8, hipMemcpyHostToDevice, ctx->stream));
+    ZL_HIP(ctx, hipMemcpyAsync(d_pre, pl.pre.data(), pl.pre.size() * 8, hipMemcpyHostToDevice, ctx->stream));
+    for (size_t first = 0; first < count; first += chunk) {
+        const size_t m = count - first < chunk ? count - first : chunk;
+        if (leaves) ZL_HIP(ctx, hipMemcpyAsync(d_leaf, leaves + first * 4, m * 32, hipMemcpyHostToDevice, ctx->stream));
+        ZL_HIP(ctx, hipMemcpyAsync(d_dst, pl.dst.data() + first, m * 8, hipMemcpyHostToDevice, ctx->stream));
+        ZL_POS_LAUNCH(ctx, (k_pos_forest_place<FrP>), blocks_of(m), BLOCK, 0, leaves ? d_leaf : d_leaves + first * 4, d_dst, m, f->nodes, s.flag);
+    }
+    for (unsigned k = 1; k <= f->depth; k++) {
+        const ForestSegs sg{d_tree, d_first, d_pre + (size_t)(k - 1) * (T + 1), (uint32_t)T};
+        const size_t total = (size_t)pl.pre[(size_t)(k - 1) * (T + 1) + T];
+        const size_t child_off = pd::level_offset(f->capacity, k - 1), child_size = pd::level_size(f->capacity, k - 1), parent_off = child_off + child_size;
+        for (size_t first = 0; first < total; first += launch) {
+            const size_t m = total - first < launch ? total - first : launch;
+            ZL_POS_LAUNCH(ctx, (k_pos_forest_level<FrP>), blocks_of(m), BLOCK, 0, tab, f->nodes, f->stride, sg, k, child_off, child_size, parent_off, first, m, s.flag);
+        }
+    }
+    return finish(ctx, s.flag);
+}
+// ZL_EINVAL unless every (tree, index) names a leaf the forest holds
+int forest_members_ok(const zl_merkle_forest* f, const uint32_t* tree_of, const uint64_t* indices, size_t count) {
+    for (size_t i = 0; i < count; i++)
+        if (tree_of[i] >= f->trees || indices[i] >= f->lens[tree_of[i]]) return ZL_EINVAL;
+    return ZL_OK;
+}
+int dev_forest_paths(const zl_merkle_forest* f, const uint32_t* tree_of, const uint64_t* indices, size_t count, uint64_t* paths) {
+    zl_ctx* ctx = f->ctx;
+    const unsigned depth = f->depth;
+    const size_t chunk = stage_items(12 + (size_t)depth * 32), m0 = count < chunk ? count : chunk, o_tree = up256(m0 * 8), o_path = o_tree + up256(m0 * 4);
+    Stage s;
+    const int rc = stage_get(ctx, o_path + m0 * depth * 32, &s);
+    if (rc) return rc;
+    uint64_t* d_idx = reinterpret_cast<uint64_t*>(s.data);
+    uint32_t* d_tree = reinterpret_cast<uint32_t*>(s.data + o_tree);
+    uint64_t* d_path = reinterpret_cast<uint64_t*>(s.data + o_path);
+    const LevelTable lt = level_table(f->capacity, depth);
+    for (size_t first = 0; first < count; first += chunk) {
+        const size_t m = count - first < chunk ? count - first : chunk;
+        ZL_HIP(ctx, hipMemcpyAsync(d_idx, indices + first, m * 8, hipMemcpyHostToDevice, ctx->stream));
+        ZL_HIP(ctx, hipMemcpyAsync(d_tree, tree_of + first, m * 4, hipMemcpyHostToDevice, ctx->stream));
+        ZL_POS_LAUNCH(ctx, k_pos_forest_gather, blocks_of(m * depth), BLOCK, 0, f->nodes, f->stride, lt, depth, d_tree, d_idx, m * depth, d_path);
+        ZL_HIP(ctx, hipMemcpyAsync(paths + first * depth * 4, d_path, m * depth * 32, hipMemcpyDeviceToHost, ctx->stream));
+    }
+    ZL_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    return ZL_OK;
+}
+// rows (and, host_pub != null, the root of every item) of memberships out of the forest, on `ctx`: the forest's own ctx or another lane of its device
+template <class FrP>
+int dev_merkle_from_forest(zl_ctx* ctx, const zl_merkle_forest* f, const uint32_t* tree_of, const uint64_t* indices, size_t count, void* d_rows, size_t stride,
+                           uint64_t* host_rows, uint64_t* host_pub) {
+    const ForestSrc src{f->nodes, f->stride, nullptr, level_table(f->capacity, f->depth)};
+    return merkle_trace_run<FrP, ForestSrc>(ctx, src, nullptr, indices, f->depth, count, static_cast<uint64_t*>(d_rows), stride, host_rows, host_pub, tree_of);
 }
 }  // namespace
 
@@ -1430,4 +1707,161 @@ int zl_poseidon_merkle_member_assignments_dev(zl_ctx* ctx, zl_curve_t curve, con
     return ZL_POS_CURVE(curve, dev_merkle_from_tree, ctx, d_nodes, n, depth, indices, count, d_out, stride_elems, nullptr);
 }
 
+// ---- the Merkle forest
+int zl_merkle_forest_create(zl_ctx* ctx, zl_curve_t curve, uint32_t trees, unsigned depth, size_t capacity, zl_merkle_forest** out) {
+    if (!out) return ZL_EINVAL;
+    *out = nullptr;
+    if (!valid_curve(curve) || trees < 1 || trees > 65536 || capacity < 1 || !pd::geometry_ok(capacity, depth)) return ZL_EINVAL;
+    std::unique_ptr<zl_merkle_forest> f(new (std::nothrow) zl_merkle_forest);
+    if (!f) return ZL_ENOMEM;
+    f->ctx = ctx;
+    f->curve = curve;
+    f->trees = trees;
+    f->depth = depth;
+    f->capacity = capacity;
+    f->stride = pd::level_offset(capacity, depth + 1);
+    try {
+        f->lens.assign(trees, 0);
+        f->add.assign(trees, 0);
+    } catch (const std::bad_alloc&) {
+        return ZL_ENOMEM;
+    }
+    if (f->stride > (SIZE_MAX >> 5) / trees) return ZL_ENOMEM;
+    const size_t bytes = (size_t)trees * f->stride * 32;
+    if (!ctx) {
+        f->nodes = static_cast<uint64_t*>(calloc(bytes, 1));
+        if (!f->nodes) return ZL_ENOMEM;
+    } else {
+        ZL_HIP(ctx, hipSetDevice(ctx->device));
+        void* d = nullptr;
+        const hipError_t e = hipMalloc(&d, bytes);
+        if (e != hipSuccess) {
+            ctx->last_hip = (int)e;
+            return ZL_ENOMEM;
+        }
+        std::unique_ptr<void, DevFree> hold(d);  // (freed on the error returns below)
+        ZL_HIP(ctx, hipMemsetAsync(d, 0, bytes, ctx->stream));
+        ZL_HIP(ctx, hipStreamSynchronize(ctx->stream));
+        f->nodes = static_cast<uint64_t*>(hold.release());
+    }
+    *out = f.release();
+    return ZL_OK;
+}
+void zl_merkle_forest_destroy(zl_merkle_forest* f) {
+    if (!f) return;
+    if (!f->ctx) {
+        free(f->nodes);
+    } else {
+        (void)hipSetDevice(f->ctx->device);
+        (void)hipFree(f->nodes);  // (every call on the forest had finished when it returned; hipFree waits for the device besides)
+    }
+    delete f;
+}
+int zl_merkle_forest_describe(const zl_merkle_forest* f, uint32_t* trees, unsigned* depth, size_t* capacity, size_t* tree_stride_elems) {
+    if (!f) return ZL_EINVAL;
+    if (trees) *trees = f->trees;
+    if (depth) *depth = f->depth;
+    if (capacity) *capacity = f->capacity;
+    if (tree_stride_elems) *tree_stride_elems = f->stride;
+    return ZL_OK;
+}
+int zl_merkle_forest_lens(const zl_merkle_forest* f, uint64_t* lens) {
+    if (!f || !lens) return ZL_EINVAL;
+    memcpy(lens, f->lens.data(), (size_t)f->trees * 8);
+    return ZL_OK;
+}
+int zl_merkle_forest_append(zl_merkle_forest* f, const uint32_t* tree_of, const uint64_t* leaves, size_t count) {
+    if (!f || (count && (!tree_of || !leaves))) return ZL_EINVAL;
+    if (count == 0) return ZL_OK;
+    if (!ZL_POS_CURVE(f->curve, host_all_canon, leaves, count)) return ZL_EINVAL;
+    ForestPlan pl;
+    int rc = forest_plan(f, tree_of, count, pl);
+    if (rc) return rc;
+    if (!f->ctx) {
+        rc = ZL_POS_CURVE(f->curve, host_forest_append, f, pl, leaves, count);
+    } else {
+        ZL_HIP(f->ctx, hipSetDevice(f->ctx->device));
+        rc = ZL_POS_CURVE(f->curve, dev_forest_append, f, pl, leaves, nullptr, count);
+    }
+    if (rc == ZL_OK) forest_commit(f, pl);
+    return rc;
+}
+int zl_merkle_forest_append_dev(zl_merkle_forest* f, const uint32_t* tree_of, const void* d_leaves, size_t count) {
+    if (!f || !f->ctx || (count && (!tree_of || !d_leaves))) return ZL_EINVAL;
+    if (count == 0) return ZL_OK;
+    ForestPlan pl;
+    int rc = forest_plan(f, tree_of, count, pl);
+    if (rc) return rc;
+    ZL_HIP(f->ctx, hipSetDevice(f->ctx->device));
+    rc = ZL_POS_CURVE(f->curve, dev_forest_append, f, pl, nullptr, static_cast<const uint64_t*>(d_leaves), count);
+    if (rc == ZL_OK) forest_commit(f, pl);
+    return rc;
+}
+int zl_merkle_forest_roots(const zl_merkle_forest* f, uint64_t* roots) {
+    if (!f || !roots) return ZL_EINVAL;
+    const uint64_t* first = f->nodes + (f->stride - 1) * 4;  // the root is a tree's last node
+    if (!f->ctx) {
+        for (uint32_t t = 0; t < f->trees; t++) memcpy(roots + (size_t)t * 4, first + (size_t)t * f->stride * 4, 32);
+        return ZL_OK;
+    }
+    zl_ctx* ctx = f->ctx;
+    ZL_HIP(ctx, hipSetDevice(ctx->device));
+    ZL_HIP(ctx, hipMemcpy2DAsync(roots, 32, first, f->stride * 32, 32, f->trees, hipMemcpyDeviceToHost, ctx->stream));  // one strided copy, no kernel
+    ZL_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    return ZL_OK;
+}
+int zl_merkle_forest_paths(const zl_merkle_forest* f, const uint32_t* tree_of, const uint64_t* indices, size_t count, uint64_t* paths) {
+    if (!f || (count && (!tree_of || !indices || !paths)) || forest_members_ok(f, tree_of, indices, count)) return ZL_EINVAL;
+    if (count == 0) return ZL_OK;
+    if (!f->ctx) {
+        for (size_t i = 0; i < count; i++) {
+            const int rc = zl_poseidon_merkle_paths(f->nodes + (size_t)tree_of[i] * f->stride * 4, f->capacity, f->depth, indices + i, 1, paths + i * f->depth * 4);
+            if (rc) return rc;
+        }
+        return ZL_OK;
+    }
+    ZL_HIP(f->ctx, hipSetDevice(f->ctx->device));
+    return dev_forest_paths(f, tree_of, indices, count, paths);
+}
+int zl_merkle_forest_tree_nodes(const zl_merkle_forest* f, uint32_t tree, const void** nodes) {
+    if (!f || !nodes || tree >= f->trees) return ZL_EINVAL;
+    *nodes = f->nodes + (size_t)tree * f->stride * 4;
+    return ZL_OK;
+}
+int zl_merkle_forest_download(const zl_merkle_forest* f, uint32_t tree, uint64_t* nodes) {
+    if (!f || !nodes || tree >= f->trees) return ZL_EINVAL;
+    const uint64_t* from = f->nodes + (size_t)tree * f->stride * 4;
+    if (!f->ctx) {
+        memcpy(nodes, from, f->stride * 32);
+        return ZL_OK;
+    }
+    zl_ctx* ctx = f->ctx;
+    ZL_HIP(ctx, hipSetDevice(ctx->device));
+    ZL_HIP(ctx, hipMemcpyAsync(nodes, from, f->stride * 32, hipMemcpyDeviceToHost, ctx->stream));
+    ZL_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    return ZL_OK;
+}
+int zl_merkle_forest_member_assignments_dev(const zl_merkle_forest* f, const uint32_t* tree_of, const uint64_t* indices, size_t count, void* d_out, size_t stride_elems) {
+    if (!f || !f->ctx || stride_elems < pd::merkle_row_elems(f->depth) || (count && (!tree_of || !indices || !d_out)) || ((uintptr_t)d_out & 15) ||
+        forest_members_ok(f, tree_of, indices, count))
+        return ZL_EINVAL;
+    if (count == 0) return ZL_OK;
+    ZL_HIP(f->ctx, hipSetDevice(f->ctx->device));
+    return ZL_POS_CURVE(f->curve, dev_merkle_from_forest, f->ctx, f, tree_of, indices, count, d_out, stride_elems, nullptr, nullptr);
+}
+
 }  // extern "C"
+
+int zl_merkle_forest_prover_view(const zl_merkle_forest* f, const zl_ctx* ctx, int* curve, unsigned* depth) {
+    if (!f || !f->ctx || !ctx || ctx->device != f->ctx->device) return ZL_EINVAL;
+    *curve = (int)f->curve;
+    *depth = f->depth;
+    return ZL_OK;
+}
+int zl_merkle_forest_members_ok(const zl_merkle_forest* f, const uint32_t* tree_of, const uint64_t* indices, size_t count) {
+    return forest_members_ok(f, tree_of, indices, count);
+}
+int zl_merkle_forest_member_rows(zl_ctx* ctx, const zl_merkle_forest* f, const uint32_t* tree_of, const uint64_t* indices, size_t count, void* d_rows, size_t stride_elems,
+                                 uint64_t* host_rows, uint64_t* roots_out) {
+    return ZL_POS_CURVE(f->curve, dev_merkle_from_forest, ctx, f, tree_of, indices, count, d_rows, stride_elems, host_rows, roots_out);
+}
