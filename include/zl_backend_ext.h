@@ -92,6 +92,26 @@ int zl_groth16_prove_merkle_members(zl_ctx* ctx, const zl_g16_pk* pk, uint64_t r
 typedef struct zl_merkle_forest zl_merkle_forest;
 int zl_groth16_prove_forest_members(zl_ctx* ctx, const zl_g16_pk* pk, uint64_t r1cs_handle, const zl_merkle_forest* f, const uint32_t* tree_of, const uint64_t* indices,
                                     const uint64_t* r, const uint64_t* s, size_t count, zl_g16_proof* proofs, uint64_t* roots_out);
+/* The same three producers for the arity-general circuits (zl_circuit_poseidon_hash / _merkle_leaf below): proofs[j] = what zl_groth16_prove_resident returns
+ * for row j of zl_poseidon_hash_assignments resp. zl_poseidon_merkle_leaf_assignments with r[j], s[j], byte for byte.
+ *   _poseidon_hashes:      in (count x arity x 4 u64, HOST); public_out (may be NULL) receives the digest per proof.
+ *   _merkle_leaf_paths:    preimages (count x arity), indices (count u64) and paths (count x depth) in HOST memory; roots_out (may be NULL) the root per proof.
+ *   _merkle_leaf_members:  a node array (zl_poseidon_merkle_build_dev: n leaves, `depth` levels) and the n x arity preimages of its leaves in DEVICE memory, HOST
+ *                          indices; root_out (may be NULL) receives the one root.  A preimage that does not hash to its leaf is ZL_EINVAL, as in
+ *                          zl_poseidon_merkle_leaf_member_assignments_dev.
+ * Each call checks that the resident circuit has the SHAPE of the stated (arity, depth) -- (2, a + 3 S(a), 3 S(a) + 1) resp. (2, a + 3 S(a) + 238 d,
+ * 3 S(a) + 237 d + 1) -- else ZL_EINVAL; the shapes of the four families are told apart in the note at zl_circuit_poseidon_hash.  Error order and dispatch
+ * bounds are zl_groth16_prove_batch's and are not moved (a hash circuit has a domain of 2^8 or 2^9, a leaf membership of depth <= 7 at most 2^11); off the
+ * device path the rows come through host staging as for the membership producers.  arity outside 2..5, depth outside 1..40, an index >= 2^depth (>= n), n >
+ * 2^depth or an input >= r: ZL_EINVAL. */
+int zl_groth16_prove_poseidon_hashes(zl_ctx* ctx, const zl_g16_pk* pk, uint64_t r1cs_handle, unsigned arity, const uint64_t* in, const uint64_t* r, const uint64_t* s,
+                                     size_t count, zl_g16_proof* proofs, uint64_t* public_out);
+int zl_groth16_prove_merkle_leaf_paths(zl_ctx* ctx, const zl_g16_pk* pk, uint64_t r1cs_handle, unsigned arity, unsigned depth, const uint64_t* preimages,
+                                       const uint64_t* indices, const uint64_t* paths, const uint64_t* r, const uint64_t* s, size_t count, zl_g16_proof* proofs,
+                                       uint64_t* roots_out);
+int zl_groth16_prove_merkle_leaf_members(zl_ctx* ctx, const zl_g16_pk* pk, uint64_t r1cs_handle, unsigned arity, const void* d_nodes, const void* d_preimages, size_t n,
+                                         unsigned depth, const uint64_t* indices, const uint64_t* r, const uint64_t* s, size_t count, zl_g16_proof* proofs,
+                                         uint64_t* root_out);
 int zl_partials_sum(zl_curve_t curve, zl_group_t group, const uint64_t* partials, size_t count, uint64_t* out_xy, uint8_t* out_inf);
 /* wrap a canonical affine point (all-zero = infinity) as a partial, e.g. to fold an extra term into zl_partials_sum */
 int zl_partial_from_affine(zl_curve_t curve, zl_group_t group, const uint64_t* xy, uint64_t* out_partial);
@@ -189,7 +209,8 @@ int zl_poseidon_hash2_batch_dev(zl_ctx* ctx, zl_curve_t curve, const void* d_xy,
  * partial rounds; the hash of `arity` inputs is element 0 of permute([2^arity - 1, x_1 .. x_arity]) (openzl-crypto/src/poseidon/hash.rs:64-135).  The round keys
  * come from the reference's LFSR seeded with (field bits, width, full, partial) and the MDS entry [i][j] is 1 / (i + width + j), as at width 3.  The reference
  * states the table for BN254; BLS12-381 Fr takes the same rows here.  The common rules above hold unchanged; at width 3 / arity 2 every call below returns byte
- * for byte what its width-3 counterpart returns.  The in-circuit gadget (zl_circuit_poseidon_*) stays arity 2. */
+ * for byte what its width-3 counterpart returns.  In circuit, the chain and the inner hash of the Merkle levels stay arity 2; zl_circuit_poseidon_hash and
+ * zl_circuit_poseidon_merkle_leaf below prove one hash, and a membership whose leaf is hashed from a preimage, at every arity of the table. */
 /* width, rounds and tag of an arity (a NULL output is skipped); ZL_EINVAL outside 2..5 */
 int zl_poseidon_spec(unsigned arity, unsigned* width, unsigned* full_rounds, unsigned* partial_rounds, uint64_t* tag);
 /* host, one state of `width` elements in place (width 3..6; elements are taken as zl_poseidon_permute takes them); width 3 == zl_poseidon_permute */
@@ -265,6 +286,57 @@ int zl_poseidon_merkle_assignments_dev(zl_ctx* ctx, zl_curve_t curve, const void
                                        void* d_out, size_t stride_elems);
 int zl_poseidon_merkle_member_assignments_dev(zl_ctx* ctx, zl_curve_t curve, const void* d_nodes, size_t n, unsigned depth, const uint64_t* indices, size_t count,
                                               void* d_out, size_t stride_elems);
+/* ---- in circuit at every arity of the table: the reference's Spec<F, ARITY> (plugins/arkworks/src/poseidon/mod.rs:225-322).  S(a) = 8 (a + 1) + partial - 1 =
+ * 78, 86, 95, 103 is the number of S-boxes one arity-a hash allocates: every S-box of the permutation in round order, lane order within a round, each as x^2,
+ * x^4, x^5, except lane 0 of round 0, whose input -- the domain tag 2^a - 1 plus a round key -- is a constant the circuit folds.  3 S(a) = 234, 258, 285, 309
+ * record elements; the rule of the arity-2 gadget, at width a + 1.
+ * zl_circuit_poseidon_hash: ONE hash of `arity` inputs (in: arity x 4 u64).  Public input: the digest.  Witnesses: the inputs, then the 3 S(a) records; the
+ *   last row is digest = public input.  Shape (n_instance, n_witness, n_constraints) = (2, a + 3 S(a), 3 S(a) + 1).  At arity 2 this is the circuit of
+ *   zl_circuit_poseidon_chain(curve, 1, in, in + 4) word for word: the same matrices and the same assignment.
+ * zl_circuit_poseidon_merkle_leaf: a membership whose leaf is hashed from its preimage INSIDE the circuit -- the reference's PathVar::verify,
+ *   parameters.digest_with(leaf) followed by verify_digest (openzl-crypto/src/merkle_tree/path.rs:1109-1125): "I know the opening of a commitment that is in
+ *   the tree".  Public input: the root.  Witnesses: the `arity` preimage elements; the 3 S(a) records of leaf = H_a(preimage) -- the leaf digest itself is a
+ *   linear combination and is NOT allocated, as h_j inside a chain; then the levels exactly as zl_circuit_poseidon_merkle lays them out (sibling, Boolean bit,
+ *   left, right, 234 records: arity 2 at every level).  Shape (2, a + 3 S(a) + 238 d, 3 S(a) + 237 d + 1).
+ * arity outside 2..5, depth outside 1..40, index >= 2^depth, an element >= r, a null pointer or an unknown curve: ZL_EINVAL.  _witness: the same circuits run by
+ * a witness-only compiler (see zl_circuit_poseidon_chain_witness); the two compilers' assignments are equal word for word.
+ * SHAPES.  Four families now share n_instance == 2: chain(k) (2 + 234 k, 234 k + 1), membership(d) (1 + 238 d, 237 d + 1), hash(a) and leaf(a, d) above.
+ * n_witness - n_constraints is 1, d, a - 1 and a - 1 + d.  hash(a) against chain(k): a = 2, then 236 = 2 + 234 k gives k = 1 -- the ONE coincidence, and there the
+ * circuits are identical, so keys of either serve both provers.  hash against membership: d = a - 1, and a + 3 S(a) = 236, 261, 289, 314 is never 1 + 238 (a - 1)
+ * = 239, 477, 715, 953.  leaf against chain: a - 1 + d >= 2.  leaf(a, d) against membership(d'): d' = a - 1 + d, which needs a + 3 S(a) = 1 + 238 (a - 1) again.
+ * leaf(a, d) against leaf(a', d') or hash(a') (take d' = 0): equal differences give d - d' = a' - a, equal witness counts then need (a' + 3 S(a')) - (a + 3 S(a))
+ * = 238 (a' - a), but those values lie within 314 - 236 = 78 of each other, so a' = a and d' = d.  So every prover below refuses the keys of every other
+ * family, chain(1) / hash(2) apart. */
+int zl_circuit_poseidon_hash(zl_curve_t curve, unsigned arity, const uint64_t* in, zl_circuit** out);
+int zl_circuit_poseidon_hash_witness(zl_curve_t curve, unsigned arity, const uint64_t* in, zl_circuit** out);
+int zl_circuit_poseidon_merkle_leaf(zl_curve_t curve, unsigned arity, unsigned depth, const uint64_t* preimage, uint64_t index, const uint64_t* path, zl_circuit** out);
+int zl_circuit_poseidon_merkle_leaf_witness(zl_curve_t curve, unsigned arity, unsigned depth, const uint64_t* preimage, uint64_t index, const uint64_t* path,
+                                            zl_circuit** out);
+/* The complete ASSIGNMENTS of the two circuits, one device lane per row (k_pos_hash_trace / k_pos_leaf_merkle_trace), word for word what both compilers export:
+ *   hash row:             [0] = 1   [1] = digest   [2 .. 2 + a) the inputs    then the 3 S(a) records
+ *   leaf-membership row:  [0] = 1   [1] = root     [2 .. 2 + a) the preimage  the 3 S(a) records of the leaf hash   level j at 2 + a + 3 S(a) + 238 j, laid
+ *                         out as in zl_poseidon_merkle_assignments: [+0] sibling  [+1] b_j  [+2] left  [+3] right  [+4 .. +238) the records of H(left, right)
+ * zl_poseidon_hash_assignment_elems(arity) = 2 + a + 3 S(a) = 238, 263, 291, 316; zl_poseidon_merkle_leaf_assignment_elems(arity, depth) = that + 238 depth; 0
+ * for a parameter out of range.  At arity 2 the hash rows are zl_poseidon_chain_assignments' for k = 1 byte for byte.  in / preimages: count x arity elements;
+ * paths: count x depth; indices are HOST memory in every form.  The host-pointer forms write count dense rows under the common rules of the batched Poseidon
+ * entry points (ctx == NULL or a count below ZL_TUNE_POSEIDON_DEV_MIN: the host mirror over the host pool; staged in chunks of ZL_TUNE_POSEIDON_CHUNK under
+ * the 256 MiB budget; finished on return; an element >= r is ZL_EINVAL through the flag word).  The _dev forms never take the host path (ctx == NULL is
+ * ZL_EINVAL): row i starts at d_out + i * stride_elems elements, stride_elems >= the row length, elements behind the row are not written, d_out must be 16-byte
+ * aligned and must not overlap the inputs.  An index >= 2^depth (>= n in the member form) is ZL_EINVAL before any work.
+ * _member_assignments_dev reads a node array of zl_poseidon_merkle_build_dev's layout (n leaves, `depth` levels) and the n x arity preimages of its leaves,
+ * preimage of leaf i at element i * arity of d_preimages: the siblings as in zl_poseidon_merkle_member_assignments_dev, so [1] of every row is the tree's root.
+ * An item whose H_a(preimage) differs from node (0, index) makes the call ZL_EINVAL (a second bit of the flag word): without the comparison the call would
+ * quietly write a valid row for ANOTHER root. */
+size_t zl_poseidon_hash_assignment_elems(unsigned arity);
+size_t zl_poseidon_merkle_leaf_assignment_elems(unsigned arity, unsigned depth);
+int zl_poseidon_hash_assignments(zl_ctx* ctx, zl_curve_t curve, unsigned arity, const uint64_t* in, size_t count, uint64_t* out);
+int zl_poseidon_hash_assignments_dev(zl_ctx* ctx, zl_curve_t curve, unsigned arity, const void* d_in, size_t count, void* d_out, size_t stride_elems);
+int zl_poseidon_merkle_leaf_assignments(zl_ctx* ctx, zl_curve_t curve, unsigned arity, const uint64_t* preimages, const uint64_t* indices, const uint64_t* paths,
+                                        unsigned depth, size_t count, uint64_t* out);
+int zl_poseidon_merkle_leaf_assignments_dev(zl_ctx* ctx, zl_curve_t curve, unsigned arity, const void* d_preimages, const uint64_t* indices, const void* d_paths,
+                                            unsigned depth, size_t count, void* d_out, size_t stride_elems);
+int zl_poseidon_merkle_leaf_member_assignments_dev(zl_ctx* ctx, zl_curve_t curve, unsigned arity, const void* d_nodes, const void* d_preimages, size_t n, unsigned depth,
+                                                   const uint64_t* indices, size_t count, void* d_out, size_t stride_elems);
 /* ---- Merkle forest: `trees` (1 .. 65 536) growing trees in ONE allocation -- the reference's accumulator, trees that grow by push / extend
  * (openzl-crypto/src/merkle_tree/tree.rs:287-345, 899-915) held as a fixed array with every leaf routed to one of them (forest.rs:30-40, 245-251, 465-565).
  * Every tree has `depth` (1 .. 40) hash levels and room for `capacity` leaves (1 <= capacity <= 2^depth), over the arity-2 H and the rules of the Merkle family

@@ -10,3 +10,5 @@ from .backend import Circuit, Groth16Keys, MerkleForest, poseidon_permute, pairi
 from .backend import (poseidon_permute_batch_host, poseidon_hash2_host, poseidon_chain_host, poseidon_merkle_nodes, poseidon_merkle_root_host,  # noqa: F401
                       poseidon_merkle_build_host, poseidon_merkle_paths_host, poseidon_roots_from_paths_host, poseidon_chain_assignment_elems,
                       poseidon_chain_assignments_host, poseidon_merkle_assignment_elems, poseidon_merkle_assignments_host, poseidon_hash_host, poseidon_spec, poseidon_constants)
+from .backend import (poseidon_hash_assignment_elems, poseidon_hash_assignments_host, poseidon_merkle_leaf_assignment_elems,  # noqa: F401
+                      poseidon_merkle_leaf_assignments_host)

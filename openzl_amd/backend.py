@@ -46,6 +46,10 @@ ABI_SYMBOLS = [
     "zl_merkle_forest_create", "zl_merkle_forest_destroy", "zl_merkle_forest_describe", "zl_merkle_forest_lens", "zl_merkle_forest_append",
     "zl_merkle_forest_append_dev", "zl_merkle_forest_roots", "zl_merkle_forest_paths", "zl_merkle_forest_tree_nodes", "zl_merkle_forest_download",
     "zl_merkle_forest_member_assignments_dev", "zl_groth16_prove_forest_members",
+    "zl_circuit_poseidon_hash", "zl_circuit_poseidon_hash_witness", "zl_circuit_poseidon_merkle_leaf", "zl_circuit_poseidon_merkle_leaf_witness",
+    "zl_poseidon_hash_assignment_elems", "zl_poseidon_merkle_leaf_assignment_elems", "zl_poseidon_hash_assignments", "zl_poseidon_hash_assignments_dev",
+    "zl_poseidon_merkle_leaf_assignments", "zl_poseidon_merkle_leaf_assignments_dev", "zl_poseidon_merkle_leaf_member_assignments_dev",
+    "zl_groth16_prove_poseidon_hashes", "zl_groth16_prove_merkle_leaf_paths", "zl_groth16_prove_merkle_leaf_members",
 ]
 
 
@@ -171,6 +175,24 @@ def load_library(path: Optional[str] = None):
     L.zl_groth16_prove_merkle_paths.argtypes = [vp, C.POINTER(G16PkC), C.c_uint64, C.c_uint, u64p, u64p, u64p, u64p, u64p, C.c_size_t, C.POINTER(G16ProofC), u64p]
     L.zl_groth16_prove_merkle_members.argtypes = [vp, C.POINTER(G16PkC), C.c_uint64, vp, C.c_size_t, C.c_uint, u64p, u64p, u64p, C.c_size_t, C.POINTER(G16ProofC), u64p]
     u32p = C.POINTER(C.c_uint32)
+    L.zl_circuit_poseidon_hash.argtypes = [C.c_int, C.c_uint, u64p, C.POINTER(vp)]
+    L.zl_circuit_poseidon_hash_witness.argtypes = L.zl_circuit_poseidon_hash.argtypes
+    L.zl_circuit_poseidon_merkle_leaf.argtypes = [C.c_int, C.c_uint, C.c_uint, u64p, C.c_uint64, u64p, C.POINTER(vp)]
+    L.zl_circuit_poseidon_merkle_leaf_witness.argtypes = L.zl_circuit_poseidon_merkle_leaf.argtypes
+    L.zl_poseidon_hash_assignment_elems.argtypes = [C.c_uint]
+    L.zl_poseidon_hash_assignment_elems.restype = C.c_size_t
+    L.zl_poseidon_merkle_leaf_assignment_elems.argtypes = [C.c_uint, C.c_uint]
+    L.zl_poseidon_merkle_leaf_assignment_elems.restype = C.c_size_t
+    L.zl_poseidon_hash_assignments.argtypes = [vp, C.c_int, C.c_uint, u64p, C.c_size_t, u64p]
+    L.zl_poseidon_hash_assignments_dev.argtypes = [vp, C.c_int, C.c_uint, vp, C.c_size_t, vp, C.c_size_t]
+    L.zl_poseidon_merkle_leaf_assignments.argtypes = [vp, C.c_int, C.c_uint, u64p, u64p, u64p, C.c_uint, C.c_size_t, u64p]
+    L.zl_poseidon_merkle_leaf_assignments_dev.argtypes = [vp, C.c_int, C.c_uint, vp, u64p, vp, C.c_uint, C.c_size_t, vp, C.c_size_t]
+    L.zl_poseidon_merkle_leaf_member_assignments_dev.argtypes = [vp, C.c_int, C.c_uint, vp, vp, C.c_size_t, C.c_uint, u64p, C.c_size_t, vp, C.c_size_t]
+    L.zl_groth16_prove_poseidon_hashes.argtypes = [vp, C.POINTER(G16PkC), C.c_uint64, C.c_uint, u64p, u64p, u64p, C.c_size_t, C.POINTER(G16ProofC), u64p]
+    L.zl_groth16_prove_merkle_leaf_paths.argtypes = [vp, C.POINTER(G16PkC), C.c_uint64, C.c_uint, C.c_uint, u64p, u64p, u64p, u64p, u64p, C.c_size_t,
+                                                     C.POINTER(G16ProofC), u64p]
+    L.zl_groth16_prove_merkle_leaf_members.argtypes = [vp, C.POINTER(G16PkC), C.c_uint64, C.c_uint, vp, vp, C.c_size_t, C.c_uint, u64p, u64p, u64p, C.c_size_t,
+                                                       C.POINTER(G16ProofC), u64p]
     L.zl_merkle_forest_create.argtypes = [vp, C.c_int, C.c_uint32, C.c_uint, C.c_size_t, C.POINTER(vp)]
     L.zl_merkle_forest_destroy.argtypes = [vp]
     L.zl_merkle_forest_destroy.restype = None
@@ -618,6 +640,42 @@ class Backend:
         self._check(self.L.zl_poseidon_merkle_member_assignments_dev(self._ctx, curve, C.c_void_p(d_nodes), n, depth, _ptr_or_none(idx), idx.size, C.c_void_p(d_out),
                                                                      stride), "zl_poseidon_merkle_member_assignments_dev")
 
+    def poseidon_hash_assignments(self, curve: int, inputs) -> np.ndarray:
+        """zl_poseidon_hash_assignments: inputs (count, arity, 4) -> (count, 2 + arity + 3 S(arity), 4) canonical words, row i the complete assignment of
+        Circuit.poseidon_hash(curve, inputs[i])"""
+        return _poseidon_hash_assignments(self.L, self._ctx, curve, inputs)
+
+    def poseidon_hash_assignments_dev(self, curve: int, arity: int, d_in: int, count: int, d_out: int, stride_elems: Optional[int] = None):
+        """zl_poseidon_hash_assignments_dev: count x arity inputs at the device address d_in -> row i at d_out + i * stride_elems elements (default: the row
+        length, poseidon_hash_assignment_elems(arity)); finished on return"""
+        stride = self.L.zl_poseidon_hash_assignment_elems(arity) if stride_elems is None else stride_elems
+        self._check(self.L.zl_poseidon_hash_assignments_dev(self._ctx, curve, arity, C.c_void_p(d_in), count, C.c_void_p(d_out), stride), "zl_poseidon_hash_assignments_dev")
+
+    def poseidon_merkle_leaf_assignments(self, curve: int, preimages, indices, paths, depth: int) -> np.ndarray:
+        """zl_poseidon_merkle_leaf_assignments: preimages (count, arity, 4), indices (count,), paths (count, depth, 4) -> (count, 2 + arity + 3 S(arity) +
+        238 depth, 4), row i the complete assignment of Circuit.merkle_leaf(curve, depth, preimages[i], indices[i], paths[i])"""
+        return _poseidon_merkle_leaf_assignments(self.L, self._ctx, curve, preimages, indices, paths, depth)
+
+    def poseidon_merkle_leaf_assignments_dev(self, curve: int, arity: int, d_preimages: int, indices, d_paths: int, depth: int, d_out: int,
+                                             stride_elems: Optional[int] = None):
+        """zl_poseidon_merkle_leaf_assignments_dev: preimages (count x arity) and paths (count x depth) at device addresses, indices in host memory -> row i at
+        d_out + i * stride_elems elements (default: the row length)"""
+        idx = np.ascontiguousarray(indices, dtype=np.uint64).reshape(-1)
+        stride = self.L.zl_poseidon_merkle_leaf_assignment_elems(arity, depth) if stride_elems is None else stride_elems
+        self._check(self.L.zl_poseidon_merkle_leaf_assignments_dev(self._ctx, curve, arity, C.c_void_p(d_preimages), _ptr_or_none(idx), C.c_void_p(d_paths), depth,
+                                                                   idx.size, C.c_void_p(d_out), stride), "zl_poseidon_merkle_leaf_assignments_dev")
+
+    def poseidon_merkle_leaf_member_assignments_dev(self, curve: int, arity: int, d_nodes: int, d_preimages: int, n: int, depth: int, indices, d_out: int,
+                                                    stride_elems: Optional[int] = None):
+        """zl_poseidon_merkle_leaf_member_assignments_dev: the memberships of the leaves `indices` (host memory) of the tree at the device address d_nodes, whose
+        leaf i is the arity-`arity` hash of the preimage at element i * arity of d_preimages -> rows as poseidon_merkle_leaf_assignments_dev; a preimage that
+        does not hash to its leaf is refused"""
+        idx = np.ascontiguousarray(indices, dtype=np.uint64).reshape(-1)
+        stride = self.L.zl_poseidon_merkle_leaf_assignment_elems(arity, depth) if stride_elems is None else stride_elems
+        self._check(self.L.zl_poseidon_merkle_leaf_member_assignments_dev(self._ctx, curve, arity, C.c_void_p(d_nodes), C.c_void_p(d_preimages), n, depth,
+                                                                          _ptr_or_none(idx), idx.size, C.c_void_p(d_out), stride),
+                    "zl_poseidon_merkle_leaf_member_assignments_dev")
+
     # ---- Groth16 ----------------------------------------------------------------------------------------------
     def groth16_prove(self, curve: int, pk: dict, r1cs: dict, assignment: np.ndarray, r: np.ndarray, s: np.ndarray):
         """pk: {'a_query','b_g1_query','h_query','l_query','b_g2_query': handles, 'alpha_g1','beta_g1','delta_g1','beta_g2',
@@ -728,6 +786,59 @@ class Backend:
         (`count` proofs of membership, the tree's root (4,): every proof's public input; zero when count == 0)"""
         pkc, keep_pk = _pk_struct(curve, pk)
         return self._prove_merkle_members(pkc, curve, r1cs_handle, d_nodes, n, depth, indices, r, s)
+
+    def _prove_hashes(self, pkc, curve: int, r1cs_handle: int, arity: int, inputs, r: np.ndarray, s: np.ndarray):
+        v = _elems(inputs, max(1, arity))
+        count = v.shape[0]
+        r, s = np.ascontiguousarray(r, dtype=np.uint64).reshape(count, 4), np.ascontiguousarray(s, dtype=np.uint64).reshape(count, 4)
+        out = (G16ProofC * max(1, count))()
+        pub = np.zeros((count, 4), dtype=np.uint64)
+        self._check(self.L.zl_groth16_prove_poseidon_hashes(self._ctx, C.byref(pkc), r1cs_handle, arity, _ptr_or_none(v), _ptr_or_none(r), _ptr_or_none(s), count, out,
+                                                            _ptr_or_none(pub)), "zl_groth16_prove_poseidon_hashes")
+        return [_proof_tuple(curve, p) for p in out[:count]], pub
+
+    def groth16_prove_poseidon_hashes(self, curve: int, pk: dict, r1cs_handle: int, arity: int, inputs, r: np.ndarray, s: np.ndarray):
+        """zl_groth16_prove_poseidon_hashes: inputs (count, arity, 4) and blinding scalars -> (`count` proofs, the digests (count, 4): each proof's public input)"""
+        pkc, keep_pk = _pk_struct(curve, pk)
+        return self._prove_hashes(pkc, curve, r1cs_handle, arity, inputs, r, s)
+
+    def _prove_merkle_leaf_paths(self, pkc, curve: int, r1cs_handle: int, arity: int, depth: int, preimages, indices, paths, r: np.ndarray, s: np.ndarray):
+        pre = _elems(preimages, max(1, arity))
+        idx = np.ascontiguousarray(indices, dtype=np.uint64).reshape(-1)
+        pa = np.ascontiguousarray(np.asarray(paths, dtype=np.uint64).reshape(-1, max(1, depth), 4))
+        count = idx.size
+        assert pre.shape[0] == count and pa.shape[0] == count
+        r, s = np.ascontiguousarray(r, dtype=np.uint64).reshape(count, 4), np.ascontiguousarray(s, dtype=np.uint64).reshape(count, 4)
+        out = (G16ProofC * max(1, count))()
+        roots = np.zeros((count, 4), dtype=np.uint64)
+        self._check(self.L.zl_groth16_prove_merkle_leaf_paths(self._ctx, C.byref(pkc), r1cs_handle, arity, depth, _ptr_or_none(pre), _ptr_or_none(idx), _ptr_or_none(pa),
+                                                              _ptr_or_none(r), _ptr_or_none(s), count, out, _ptr_or_none(roots)), "zl_groth16_prove_merkle_leaf_paths")
+        return [_proof_tuple(curve, p) for p in out[:count]], roots
+
+    def groth16_prove_merkle_leaf_paths(self, curve: int, pk: dict, r1cs_handle: int, arity: int, depth: int, preimages, indices, paths, r: np.ndarray, s: np.ndarray):
+        """zl_groth16_prove_merkle_leaf_paths: preimages (count, arity, 4), indices (count,), paths (count, depth, 4) and blinding scalars -> (`count` proofs, the
+        roots (count, 4): each proof's public input)"""
+        pkc, keep_pk = _pk_struct(curve, pk)
+        return self._prove_merkle_leaf_paths(pkc, curve, r1cs_handle, arity, depth, preimages, indices, paths, r, s)
+
+    def _prove_merkle_leaf_members(self, pkc, curve: int, r1cs_handle: int, arity: int, d_nodes: int, d_preimages: int, n: int, depth: int, indices, r: np.ndarray,
+                                   s: np.ndarray):
+        idx = np.ascontiguousarray(indices, dtype=np.uint64).reshape(-1)
+        count = idx.size
+        r, s = np.ascontiguousarray(r, dtype=np.uint64).reshape(count, 4), np.ascontiguousarray(s, dtype=np.uint64).reshape(count, 4)
+        out = (G16ProofC * max(1, count))()
+        root = np.zeros(4, dtype=np.uint64)
+        self._check(self.L.zl_groth16_prove_merkle_leaf_members(self._ctx, C.byref(pkc), r1cs_handle, arity, C.c_void_p(d_nodes), C.c_void_p(d_preimages), n, depth,
+                                                                _ptr_or_none(idx), _ptr_or_none(r), _ptr_or_none(s), count, out, _p64(root)),
+                    "zl_groth16_prove_merkle_leaf_members")
+        return [_proof_tuple(curve, p) for p in out[:count]], root
+
+    def groth16_prove_merkle_leaf_members(self, curve: int, pk: dict, r1cs_handle: int, arity: int, d_nodes: int, d_preimages: int, n: int, depth: int, indices,
+                                          r: np.ndarray, s: np.ndarray):
+        """zl_groth16_prove_merkle_leaf_members: the tree at the device address d_nodes (n leaves, `depth` levels), the n x arity preimages of its leaves at
+        d_preimages, leaf indices (count,) and blinding scalars -> (`count` proofs, the tree's root (4,))"""
+        pkc, keep_pk = _pk_struct(curve, pk)
+        return self._prove_merkle_leaf_members(pkc, curve, r1cs_handle, arity, d_nodes, d_preimages, n, depth, indices, r, s)
 
     def _prove_forest_members(self, pkc, curve: int, r1cs_handle: int, forest: "MerkleForest", tree_of, indices, r: np.ndarray, s: np.ndarray):
         tr, idx = _forest_items(tree_of, indices)
@@ -1397,6 +1508,53 @@ def poseidon_merkle_assignments_host(curve: int, leaves, indices, paths, depth: 
     return _poseidon_merkle_assignments(load_library(), None, curve, leaves, indices, paths, depth)
 
 
+# arity -> 3 S(arity): the record elements of one in-circuit hash (x^2, x^4, x^5 of 8 (arity + 1) + partial - 1 S-boxes)
+_ARITY_RECORDS = {2: 234, 3: 258, 4: 285, 5: 309}
+
+
+def _arity_inputs(inputs) -> np.ndarray:
+    v = np.ascontiguousarray(np.asarray(inputs, dtype=np.uint64))
+    if v.ndim != 3 or v.shape[2] != 4:
+        raise ValueError("inputs are (count, arity, 4) uint64 words")
+    return v
+
+
+def _poseidon_hash_assignments(L, ctx, curve: int, inputs) -> np.ndarray:
+    v = _arity_inputs(inputs)
+    out = np.zeros((v.shape[0], L.zl_poseidon_hash_assignment_elems(v.shape[1]), 4), dtype=np.uint64)
+    _pos_check(L, L.zl_poseidon_hash_assignments(ctx, curve, v.shape[1], _ptr_or_none(v), v.shape[0], _ptr_or_none(out)), "zl_poseidon_hash_assignments")
+    return out
+
+
+def _poseidon_merkle_leaf_assignments(L, ctx, curve: int, preimages, indices, paths, depth: int) -> np.ndarray:
+    pre = _arity_inputs(preimages)
+    idx = np.ascontiguousarray(indices, dtype=np.uint64).reshape(-1)
+    pa = np.ascontiguousarray(np.asarray(paths, dtype=np.uint64).reshape(-1, max(1, depth), 4))
+    assert pre.shape[0] == idx.size == pa.shape[0]
+    out = np.zeros((idx.size, L.zl_poseidon_merkle_leaf_assignment_elems(pre.shape[1], depth), 4), dtype=np.uint64)
+    _pos_check(L, L.zl_poseidon_merkle_leaf_assignments(ctx, curve, pre.shape[1], _ptr_or_none(pre), _ptr_or_none(idx), _ptr_or_none(pa), depth, idx.size,
+                                                        _ptr_or_none(out)), "zl_poseidon_merkle_leaf_assignments")
+    return out
+
+
+def poseidon_hash_assignment_elems(arity: int) -> int:
+    """elements of one hash circuit's assignment: 2 + arity + 3 S(arity) = 238, 263, 291, 316 (0 for an arity outside 2..5)"""
+    return int(load_library().zl_poseidon_hash_assignment_elems(arity))
+
+
+def poseidon_merkle_leaf_assignment_elems(arity: int, depth: int) -> int:
+    """elements of one leaf membership's assignment: poseidon_hash_assignment_elems(arity) + 238 depth (0 for a parameter out of range)"""
+    return int(load_library().zl_poseidon_merkle_leaf_assignment_elems(arity, depth))
+
+
+def poseidon_hash_assignments_host(curve: int, inputs) -> np.ndarray:
+    return _poseidon_hash_assignments(load_library(), None, curve, inputs)
+
+
+def poseidon_merkle_leaf_assignments_host(curve: int, preimages, indices, paths, depth: int) -> np.ndarray:
+    return _poseidon_merkle_leaf_assignments(load_library(), None, curve, preimages, indices, paths, depth)
+
+
 def poseidon_merkle_nodes(n: int, depth: int) -> int:
     """elements of the node array of a tree over n leaves with `depth` hash levels (0 for an invalid shape)"""
     return int(load_library().zl_poseidon_merkle_nodes(n, depth))
@@ -1689,6 +1847,44 @@ class Circuit:
         self._export()
         return self
 
+    @classmethod
+    def _arity(cls, curve: int, inputs, depth: int, index: int, path, witness_only: bool, what: str) -> "Circuit":
+        self = cls.__new__(cls)
+        self.L = load_library()
+        self.curve = curve
+        self.witness_only = witness_only
+        self._c = C.c_void_p()
+        words = lambda v: [(int(v) >> (64 * j)) & (2**64 - 1) for j in range(4)]
+        x = np.array([words(v) for v in inputs], dtype=np.uint64).reshape(-1, 4)
+        arity = x.shape[0]
+        if any(not 0 <= int(v) < 2**256 for v in list(inputs) + list(path)) or not 0 <= index < 2**64:
+            raise BackendError(-1, what)
+        if depth is None:
+            fn = self.L.zl_circuit_poseidon_hash_witness if witness_only else self.L.zl_circuit_poseidon_hash
+            rc = fn(curve, arity, _ptr_or_none(x), C.byref(self._c))
+        else:
+            pa = np.array([words(v) for v in path], dtype=np.uint64).reshape(-1, 4)
+            if pa.shape[0] != depth:
+                raise BackendError(-1, what)
+            fn = self.L.zl_circuit_poseidon_merkle_leaf_witness if witness_only else self.L.zl_circuit_poseidon_merkle_leaf
+            rc = fn(curve, arity, depth, _ptr_or_none(x), index, _ptr_or_none(pa), C.byref(self._c))
+        if rc:
+            raise BackendError(rc, what)
+        self._export()
+        return self
+
+    @classmethod
+    def poseidon_hash(cls, curve: int, inputs, witness_only: bool = False) -> "Circuit":
+        """the hash circuit (zl_circuit_poseidon_hash): the Poseidon hash of `inputs` (2..5 integers: the arity) equals the public digest.  At arity 2 it is
+        Circuit(curve, 1, inputs[0], inputs[1]).  witness_only: as in the constructor."""
+        return cls._arity(curve, inputs, None, 0, [], witness_only, "zl_circuit_poseidon_hash")
+
+    @classmethod
+    def merkle_leaf(cls, curve: int, depth: int, preimage, index: int, path, witness_only: bool = False) -> "Circuit":
+        """the leaf-membership circuit (zl_circuit_poseidon_merkle_leaf): the fold of path (depth integers, bottom up) over the Poseidon hash of `preimage`
+        (2..5 integers: the arity) at position index equals the public root.  witness_only: as in the constructor."""
+        return cls._arity(curve, preimage, depth, index, path, witness_only, "zl_circuit_poseidon_merkle_leaf")
+
     @property
     def shape(self):
         return self._view.n_constraints, self._view.n_instance, self._view.n_witness
@@ -1854,6 +2050,56 @@ class Groth16Keys:
         tree -> (proofs, roots (count, 4): each proof's public input); byte for byte prove_merkle_members on forest.tree_nodes(tree_of[j]) with n = the capacity"""
         self._merkle_ready("prove_forest_members")
         return (lane or self.backend)._prove_forest_members(self.pk, self.circuit.curve, self._r1cs, forest, tree_of, indices, r, s)
+
+    def hash_arity(self) -> int:
+        """a when the keys' circuit has the shape of an arity-a hash circuit (Circuit.poseidon_hash), else 0; arity 2 is also the one-link chain"""
+        n_c, n_i, n_w = self.circuit.shape
+        for a, s3 in _ARITY_RECORDS.items():
+            if (n_c, n_i, n_w) == (s3 + 1, 2, a + s3):
+                return a
+        return 0
+
+    def merkle_leaf_shape(self):
+        """(a, d) when the keys' circuit has the shape of a leaf-membership circuit of arity a and depth d (Circuit.merkle_leaf), else None"""
+        n_c, n_i, n_w = self.circuit.shape
+        d = n_w - n_c - 1
+        for a, s3 in _ARITY_RECORDS.items():
+            dd = d - (a - 2)
+            if 1 <= dd <= 40 and (n_c, n_i, n_w) == (s3 + 237 * dd + 1, 2, a + s3 + 238 * dd):
+                return a, dd
+        return None
+
+    def _upload_r1cs(self):
+        if not getattr(self, "_r1cs", 0):
+            self._r1cs = self.backend.r1cs_upload(self.circuit.curve, self.circuit.arrays())
+
+    def prove_hashes(self, inputs, r: np.ndarray, s: np.ndarray, lane: Optional[Backend] = None):
+        """zl_groth16_prove_poseidon_hashes over this key: inputs (count, arity, 4) and blinding scalars r, s (count, 4) -> (proofs, digests (count, 4));
+        proof j is prove_batch's for the assignment of Circuit.poseidon_hash(curve, inputs[j]).  Keys of a circuit that is no hash circuit are refused."""
+        a = self.hash_arity()
+        if not a:
+            raise ValueError("prove_hashes: the keys' circuit is not a Poseidon hash circuit")
+        self._upload_r1cs()
+        return (lane or self.backend)._prove_hashes(self.pk, self.circuit.curve, self._r1cs, a, inputs, r, s)
+
+    def _leaf_ready(self, what: str):
+        shape = self.merkle_leaf_shape()
+        if shape is None:
+            raise ValueError(what + ": the keys' circuit is not a leaf-membership circuit")
+        self._upload_r1cs()
+        return shape
+
+    def prove_merkle_leaf_paths(self, preimages, indices, paths, r: np.ndarray, s: np.ndarray, lane: Optional[Backend] = None):
+        """zl_groth16_prove_merkle_leaf_paths over this key: preimages (count, arity, 4), indices (count,), paths (count, depth, 4) and blinding scalars ->
+        (proofs, roots (count, 4)); proof j is prove_batch's for the assignment of Circuit.merkle_leaf(curve, depth, preimages[j], indices[j], paths[j])"""
+        a, d = self._leaf_ready("prove_merkle_leaf_paths")
+        return (lane or self.backend)._prove_merkle_leaf_paths(self.pk, self.circuit.curve, self._r1cs, a, d, preimages, indices, paths, r, s)
+
+    def prove_merkle_leaf_members(self, d_nodes: int, d_preimages: int, n: int, indices, r: np.ndarray, s: np.ndarray, lane: Optional[Backend] = None):
+        """zl_groth16_prove_merkle_leaf_members over this key: the tree of n leaves at the device address d_nodes (of the keys' depth), the n x arity preimages
+        of its leaves at d_preimages and leaf indices (count,) -> (proofs, the root (4,))"""
+        a, d = self._leaf_ready("prove_merkle_leaf_members")
+        return (lane or self.backend)._prove_merkle_leaf_members(self.pk, self.circuit.curve, self._r1cs, a, d_nodes, d_preimages, n, d, indices, r, s)
 
     def prove_many(self, seeds, circuits=None):
         """zl_groth16_prove_circuits: a stream of proofs over this key on two prover lanes (two host threads inside the library); proofs[i] is what

@@ -1333,6 +1333,89 @@ extern "C" int zl_groth16_prove_forest_members(zl_ctx* ctx, const zl_g16_pk* pk,
     };
     return groth16_prove_batch_any(ctx, pk, rd, src, 0, r, s, count, proofs);
 }
+// the checks the three arity-general provers share, in zl_groth16_prove_batch's order; nv = the row length of the stated (arity, depth), depth == 0 for the
+// hash circuit; *rd_out = the resident circuit
+static int g16_arity_checks(zl_ctx* ctx, const zl_g16_pk* pk, uint64_t r1cs_handle, unsigned arity, size_t nv, unsigned depth, bool args_ok,
+                            const zl_r1cs_dev** rd_out) {
+    if (!ctx || !pk || nv == 0 || !args_ok) return ZL_EINVAL;
+    const zl_r1cs_dev* rd = nullptr;
+    const int rc = g16_entry(ctx, pk, r1cs_handle, &rd);
+    if (rc) return rc;
+    if (pk->curve != ZL_BLS12_381 && pk->curve != ZL_BN254) return ZL_EINVAL;
+    // the shape (2, a + 3 S(a) + 238 d, 3 S(a) + 237 d + 1) with nv = 2 + a + 3 S(a) + 238 d; what the matrices say cannot be checked, as with a witness-only compiler
+    if (rd->n_instance != 2 || rd->n_witness != nv - 2 || rd->n_constraints != nv - 1 - arity - depth) return ZL_EINVAL;
+    *rd_out = rd;
+    return ZL_OK;
+}
+extern "C" int zl_groth16_prove_poseidon_hashes(zl_ctx* ctx, const zl_g16_pk* pk, uint64_t r1cs_handle, unsigned arity, const uint64_t* in, const uint64_t* r,
+                                                const uint64_t* s, size_t count, zl_g16_proof* proofs, uint64_t* public_out) {
+    const size_t nv = zl_poseidon_hash_assignment_elems(arity);
+    const zl_r1cs_dev* rd = nullptr;
+    const int rc0 = g16_arity_checks(ctx, pk, r1cs_handle, arity, nv, 0, !(count && (!in || !r || !s || !proofs)), &rd);
+    if (rc0 || count == 0) return rc0;
+    const zl_curve_t curve = pk->curve;
+    G16BatchSource src;
+    src.fill_dev = [=](size_t c0, size_t ch, void* d_rows) {
+        return zl_poseidon_hash_trace_rows(ctx, (int)curve, arity, in + c0 * arity * 4, ch, d_rows, nv, public_out ? public_out + c0 * 4 : nullptr);
+    };
+    src.fill_host = [=](size_t c0, size_t ch, uint64_t* rows) {
+        const int rc = zl_poseidon_hash_assignments(ctx, curve, arity, in + c0 * arity * 4, ch, rows);
+        if (rc == ZL_OK && public_out)
+            for (size_t j = 0; j < ch; j++) memcpy(public_out + (c0 + j) * 4, rows + j * nv * 4 + 4, 32);
+        return rc;
+    };
+    return groth16_prove_batch_any(ctx, pk, rd, src, 0, r, s, count, proofs);
+}
+extern "C" int zl_groth16_prove_merkle_leaf_paths(zl_ctx* ctx, const zl_g16_pk* pk, uint64_t r1cs_handle, unsigned arity, unsigned depth, const uint64_t* preimages,
+                                                  const uint64_t* indices, const uint64_t* paths, const uint64_t* r, const uint64_t* s, size_t count, zl_g16_proof* proofs,
+                                                  uint64_t* roots_out) {
+    const size_t nv = zl_poseidon_merkle_leaf_assignment_elems(arity, depth);
+    const zl_r1cs_dev* rd = nullptr;
+    const int rc0 = g16_arity_checks(ctx, pk, r1cs_handle, arity, nv, depth, !(count && (!preimages || !indices || !paths || !r || !s || !proofs)), &rd);
+    if (rc0) return rc0;
+    for (size_t i = 0; i < count; i++)
+        if (indices[i] >> depth) return ZL_EINVAL;
+    if (count == 0) return ZL_OK;
+    const zl_curve_t curve = pk->curve;
+    G16BatchSource src;
+    src.fill_dev = [=](size_t c0, size_t ch, void* d_rows) {
+        return zl_poseidon_merkle_leaf_trace_rows(ctx, (int)curve, arity, preimages + c0 * arity * 4, indices + c0, paths + c0 * depth * 4, depth, ch, d_rows, nv,
+                                                  roots_out ? roots_out + c0 * 4 : nullptr);
+    };
+    src.fill_host = [=](size_t c0, size_t ch, uint64_t* rows) {
+        const int rc = zl_poseidon_merkle_leaf_assignments(ctx, curve, arity, preimages + c0 * arity * 4, indices + c0, paths + c0 * depth * 4, depth, ch, rows);
+        if (rc == ZL_OK && roots_out)
+            for (size_t j = 0; j < ch; j++) memcpy(roots_out + (c0 + j) * 4, rows + j * nv * 4 + 4, 32);
+        return rc;
+    };
+    return groth16_prove_batch_any(ctx, pk, rd, src, 0, r, s, count, proofs);
+}
+extern "C" int zl_groth16_prove_merkle_leaf_members(zl_ctx* ctx, const zl_g16_pk* pk, uint64_t r1cs_handle, unsigned arity, const void* d_nodes, const void* d_preimages,
+                                                    size_t n, unsigned depth, const uint64_t* indices, const uint64_t* r, const uint64_t* s, size_t count,
+                                                    zl_g16_proof* proofs, uint64_t* root_out) {
+    const size_t nv = zl_poseidon_merkle_leaf_assignment_elems(arity, depth);
+    const zl_r1cs_dev* rd = nullptr;
+    const int rc0 = g16_arity_checks(ctx, pk, r1cs_handle, arity, nv, depth, !(count && (!d_nodes || !d_preimages || !indices || !r || !s || !proofs)), &rd);
+    if (rc0) return rc0;
+    if (zl_poseidon_merkle_nodes(n, depth) == 0 && n != 0) return ZL_EINVAL;  // (n > 2^depth)
+    for (size_t i = 0; i < count; i++)
+        if (indices[i] >= n) return ZL_EINVAL;
+    if (count == 0) return ZL_OK;
+    const zl_curve_t curve = pk->curve;
+    G16BatchSource src;
+    src.fill_dev = [=](size_t c0, size_t ch, void* d_rows) {
+        return zl_poseidon_merkle_leaf_member_rows(ctx, (int)curve, arity, d_nodes, d_preimages, n, depth, indices + c0, ch, d_rows, nv, nullptr);
+    };
+    src.fill_host = [=](size_t c0, size_t ch, uint64_t* rows) {
+        return zl_poseidon_merkle_leaf_member_rows(ctx, (int)curve, arity, d_nodes, d_preimages, n, depth, indices + c0, ch, nullptr, nv, rows);
+    };
+    const int rc = groth16_prove_batch_any(ctx, pk, rd, src, 0, r, s, count, proofs);
+    if (rc == ZL_OK && root_out) {  // the one root of the tree: the last node of the array
+        ZL_HIP(ctx, hipMemcpyAsync(root_out, static_cast<const uint64_t*>(d_nodes) + (zl_poseidon_merkle_nodes(n, depth) - 1) * 4, 32, hipMemcpyDeviceToHost, ctx->stream));
+        ZL_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    }
+    return rc;
+}
 extern "C" int zl_groth16_last_h(zl_ctx* ctx, uint64_t* out, size_t n) {
     if (!ctx || !out || !ctx->g16_h || n > ctx->g16_h_n) return ZL_EINVAL;
     ZL_HIP(ctx, hipMemcpyAsync(out, ctx->g16_h, n * 32, hipMemcpyDeviceToHost, ctx->stream));

@@ -366,51 +366,61 @@ void permute_native(const Constants<FrP, W>& c, Fp<FrP> state[W]) {
     }
 }
 // the same permutation, recording what the in-circuit version allocates: x^2, x^4, x^5 of every S-box whose input is not a constant
-// (lane 0 of the first round is: the capacity element 2^arity - 1 plus a round key), in allocation order
-template <class FrP>
-void permute_native_record(const Constants<FrP>& c, Fp<FrP> state[3], std::vector<Fp<FrP>>& rec) {
+// (lane 0 of the first round is: the capacity element 2^arity - 1 plus a round key), in allocation order -- round order, lane order within a round;
+// 8 W + partial - 1 S-boxes at width W: 78, 86, 95, 103 at widths 3..6
+template <class FrP, int W>
+void permute_native_record(const Constants<FrP, W>& c, Fp<FrP> state[W], std::vector<Fp<FrP>>& rec) {
     using F = Fp<FrP>;
     const int half = c.FULL_ROUNDS / 2;
     for (int rnd = 0; rnd < c.FULL_ROUNDS + c.PARTIAL_ROUNDS; rnd++) {
-        for (int i = 0; i < 3; i++) state[i] = zl::add(state[i], c.round_keys[3 * rnd + i]);
-        const int lanes = (rnd < half || rnd >= half + c.PARTIAL_ROUNDS) ? 3 : 1;
+        for (int i = 0; i < W; i++) state[i] = zl::add(state[i], c.round_keys[W * rnd + i]);
+        const int lanes = (rnd < half || rnd >= half + c.PARTIAL_ROUNDS) ? W : 1;
         for (int i = 0; i < lanes; i++) {
             const F x2 = zl::sqr(state[i]), x4 = zl::sqr(x2);
             state[i] = zl::mul(x4, state[i]);
             if (rnd != 0 || i != 0) { rec.push_back(x2); rec.push_back(x4); rec.push_back(state[i]); }
         }
-        F nx[3];
-        for (int i = 0; i < 3; i++) {
+        F nx[W];
+        for (int i = 0; i < W; i++) {
             F acc = zl::mul(c.mds[i][0], state[0]);
-            acc = zl::add(acc, zl::mul(c.mds[i][1], state[1]));
-            nx[i] = zl::add(acc, zl::mul(c.mds[i][2], state[2]));
+            for (int j = 1; j < W; j++) acc = zl::add(acc, zl::mul(c.mds[i][j], state[j]));
+            nx[i] = acc;
         }
-        for (int i = 0; i < 3; i++) state[i] = nx[i];
+        for (int i = 0; i < W; i++) state[i] = nx[i];
     }
 }
-// in-circuit arity-2 hash (Hasher::hash, hash.rs:123-135): state = (2^arity - 1, x, y), output = lane 0
-template <class FrP>
-FpVar<FrP> hash(const Constants<FrP>& c, const FpVar<FrP>& x, const FpVar<FrP>& y, R1CS<FrP>& compiler) {
+// in-circuit hash of W - 1 inputs (Hasher::hash, hash.rs:123-135; Spec<F, ARITY>, plugins/arkworks/src/poseidon/mod.rs:225-322): state =
+// (2^arity - 1, in[0] .. in[W - 2]), output = lane 0.  S-boxes are allocated in round order, lane order within a round, each as x^2, x^4, x^5
+template <class FrP, int W>
+FpVar<FrP> hash(const Constants<FrP, W>& c, const FpVar<FrP>* in, R1CS<FrP>& compiler) {
     using V = FpVar<FrP>;
-    V state[3] = {compiler.constant(zl::from_u64<FrP>(3)), x, y};
+    V state[W];
+    state[0] = compiler.constant(zl::from_u64<FrP>(c.SPEC.tag));
+    for (int i = 1; i < W; i++) state[i] = in[i - 1];
     const int half = c.FULL_ROUNDS / 2;
     for (int rnd = 0; rnd < c.FULL_ROUNDS + c.PARTIAL_ROUNDS; rnd++) {
-        for (int i = 0; i < 3; i++) state[i] = compiler.add_const(state[i], c.round_keys[3 * rnd + i]);
-        const int lanes = (rnd < half || rnd >= half + c.PARTIAL_ROUNDS) ? 3 : 1;
+        for (int i = 0; i < W; i++) state[i] = compiler.add_const(state[i], c.round_keys[W * rnd + i]);
+        const int lanes = (rnd < half || rnd >= half + c.PARTIAL_ROUNDS) ? W : 1;
         for (int i = 0; i < lanes; i++) {  // apply_sbox = x^5 (plugins/arkworks/src/poseidon/mod.rs:287-298)
             V x2 = compiler.mul(state[i], state[i]);
             V x4 = compiler.mul(x2, x2);
             state[i] = compiler.mul(x4, state[i]);
         }
-        V nx[3];
-        for (int i = 0; i < 3; i++) {
+        V nx[W];
+        for (int i = 0; i < W; i++) {
             V acc = compiler.mul_const(state[0], c.mds[i][0]);
-            acc = compiler.add(acc, compiler.mul_const(state[1], c.mds[i][1]));
-            nx[i] = compiler.add(acc, compiler.mul_const(state[2], c.mds[i][2]));
+            for (int j = 1; j < W; j++) acc = compiler.add(acc, compiler.mul_const(state[j], c.mds[i][j]));
+            nx[i] = acc;
         }
-        for (int i = 0; i < 3; i++) state[i] = nx[i];
+        for (int i = 0; i < W; i++) state[i] = nx[i];
     }
     return state[0];
+}
+// the arity-2 form the chain and the Merkle levels call: the W = 3 instance
+template <class FrP>
+FpVar<FrP> hash(const Constants<FrP>& c, const FpVar<FrP>& x, const FpVar<FrP>& y, R1CS<FrP>& compiler) {
+    const FpVar<FrP> in[2] = {x, y};
+    return hash<FrP, 3>(c, in, compiler);
 }
 }  // namespace poseidon
 

@@ -632,10 +632,10 @@ static R1CS<FrP> poseidon_chain(uint32_t k, const Fp<FrP>& x0_canon, const Fp<Fr
 // right = select(b, cur, sib) (ConditionalSwap as two conditionally_selects, plugins/arkworks/src/constraint/mod.rs:354-390), cur = H(left, right).  The
 // allocation is LEVEL-major (the reference allocates all bits, then all digests, up front) so that a device lane writes its assignment row front to back
 // (k_pos_merkle_trace); every hash takes two plain witnesses, so every level has the same 238 witnesses and 237 rows.
+// the levels over a running digest the caller made: a witness (the leaf of poseidon_merkle) or a linear combination (the leaf hash of poseidon_merkle_leaf)
 template <class FrP>
-static FpVar<FrP> merkle_levels(R1CS<FrP>& cs, unsigned depth, const Fp<FrP>& leaf_canon, uint64_t index, const Fp<FrP>* path_canon) {
+static FpVar<FrP> merkle_levels_over(R1CS<FrP>& cs, FpVar<FrP> cur, unsigned depth, uint64_t index, const Fp<FrP>* path_canon) {
     static const poseidon::Constants<FrP> consts;
-    FpVar<FrP> cur = cs.new_witness(zl::to_mont(leaf_canon));
     for (unsigned j = 0; j < depth; j++) {
         const FpVar<FrP> sib = cs.new_witness(zl::to_mont(path_canon[j]));
         const FpVar<FrP> b = cs.new_boolean_witness((index >> j) & 1);
@@ -644,6 +644,10 @@ static FpVar<FrP> merkle_levels(R1CS<FrP>& cs, unsigned depth, const Fp<FrP>& le
         cur = poseidon::hash(consts, left, right, cs);
     }
     return cur;
+}
+template <class FrP>
+static FpVar<FrP> merkle_levels(R1CS<FrP>& cs, unsigned depth, const Fp<FrP>& leaf_canon, uint64_t index, const Fp<FrP>* path_canon) {
+    return merkle_levels_over(cs, cs.new_witness(zl::to_mont(leaf_canon)), depth, index, path_canon);
 }
 template <class FrP>
 static R1CS<FrP> poseidon_merkle_witness(unsigned depth, const Fp<FrP>& leaf_canon, uint64_t index, const Fp<FrP>* path_canon) {
@@ -671,6 +675,42 @@ static R1CS<FrP> poseidon_merkle(unsigned depth, const Fp<FrP>& leaf_canon, uint
     // every level is synthesised symbolically: depth <= 40 levels of ~10^4 field multiplications each
     const FpVar<FrP> cur = merkle_levels(cs, depth, leaf_canon, index, path_canon);
     cs.enforce_equal(cur, root);
+    return cs;
+}
+
+// One hash of W - 1 inputs (the reference's Spec<F, ARITY> at arity 2..5): public input the digest, witnesses the inputs and the hash's S-box records.  With
+// depth > 0 the digest is the LEAF of a Merkle membership instead (the reference's PathVar::verify: parameters.digest_with(leaf), then verify_digest,
+// openzl-crypto/src/merkle_tree/path.rs:1109-1125): it stays a linear combination -- nothing is allocated for it, as for h_j inside a chain -- and the
+// levels of poseidon_merkle fold the path over it; the public input is then the root.  One function for the full and the witness-only compiler: the full
+// one allocates its public input first (the value computed natively), the witness-only one last, as the chain and the membership do.
+template <class FrP, int W>
+static R1CS<FrP> poseidon_arity(bool witness_only, const Fp<FrP>* in_canon, unsigned depth, uint64_t index, const Fp<FrP>* path_canon) {
+    using F = Fp<FrP>;
+    static const poseidon::Constants<FrP, W> consts;
+    static const poseidon::Constants<FrP> consts2;
+    R1CS<FrP> cs = witness_only ? R1CS<FrP>::for_witness() : R1CS<FrP>::for_proofs();
+    FpVar<FrP> pub;
+    if (!witness_only) {
+        F st[W];
+        st[0] = zl::from_u64<FrP>(consts.SPEC.tag);
+        for (int i = 1; i < W; i++) st[i] = zl::to_mont(in_canon[i - 1]);
+        poseidon::permute_native(consts, st);
+        F h = st[0];
+        for (unsigned j = 0; j < depth; j++) {
+            const F sib = zl::to_mont(path_canon[j]);
+            const bool right = (index >> j) & 1;
+            F lv[3] = {zl::from_u64<FrP>(3), right ? sib : h, right ? h : sib};
+            poseidon::permute_native(consts2, lv);
+            h = lv[0];
+        }
+        pub = cs.new_input(h);
+    }
+    FpVar<FrP> in[W - 1];
+    for (int i = 0; i < W - 1; i++) in[i] = cs.new_witness(zl::to_mont(in_canon[i]));
+    FpVar<FrP> cur = poseidon::hash<FrP, W>(consts, in, cs);
+    if (depth) cur = merkle_levels_over(cs, cur, depth, index, path_canon);
+    if (witness_only) pub = cs.new_input(cur.value);
+    cs.enforce_equal(cur, pub);
     return cs;
 }
 
@@ -726,6 +766,51 @@ static int prove_circuits_t(zl_ctx* ctx, const typename Groth16<E>::ProvingConte
         work(ctx);
     }
     return first_err.load();
+}
+
+// n canonical elements -> Fp words (still canonical); false when one is not below r
+template <class FrP>
+static bool elems_below_r(const uint64_t* w, size_t n, std::vector<Fp<FrP>>& out) {
+    out.resize(n);
+    for (size_t e = 0; e < n; e++) {
+        memcpy(out[e].l, w + 4 * e, 32);
+        bool lt = false;
+        for (int i = FrP::N - 1; i >= 0; i--) {
+            if (out[e].l[i] < FrP::mod(i)) { lt = true; break; }
+            if (out[e].l[i] > FrP::mod(i)) break;
+        }
+        if (!lt) return false;
+    }
+    return true;
+}
+static void circuit_set(zl_circuit* c, R1CS<BLS12_381_Fr>&& cs) { c->bls = new R1CS<BLS12_381_Fr>(std::move(cs)); c->ex_bls.build(*c->bls); }
+static void circuit_set(zl_circuit* c, R1CS<BN254_Fr>&& cs) { c->bn = new R1CS<BN254_Fr>(std::move(cs)); c->ex_bn.build(*c->bn); }
+template <class FrP>
+static int circuit_arity_t(zl_circuit* c, unsigned arity, const uint64_t* in, unsigned depth, uint64_t index, const uint64_t* path, bool witness_only) {
+    std::vector<Fp<FrP>> x, pa;
+    if (!elems_below_r<FrP>(in, arity, x) || !elems_below_r<FrP>(path, depth, pa)) return ZL_EINVAL;
+    switch (arity) {
+    case 2: circuit_set(c, poseidon_arity<FrP, 3>(witness_only, x.data(), depth, index, pa.data())); break;
+    case 3: circuit_set(c, poseidon_arity<FrP, 4>(witness_only, x.data(), depth, index, pa.data())); break;
+    case 4: circuit_set(c, poseidon_arity<FrP, 5>(witness_only, x.data(), depth, index, pa.data())); break;
+    default: circuit_set(c, poseidon_arity<FrP, 6>(witness_only, x.data(), depth, index, pa.data())); break;
+    }
+    return ZL_OK;
+}
+// depth == 0: the hash circuit (no index, no path); otherwise the leaf-membership circuit
+static int circuit_arity(zl_curve_t curve, unsigned arity, const uint64_t* in, unsigned depth, uint64_t index, const uint64_t* path, bool witness_only, zl_circuit** out) {
+    if (!out || !in || arity < 2 || arity > 5 || (depth && !path) || depth > 40 || (index >> depth) || (curve != ZL_BLS12_381 && curve != ZL_BN254)) return ZL_EINVAL;
+    zl_circuit* c = new (std::nothrow) zl_circuit();
+    if (!c) return ZL_ENOMEM;
+    c->curve = curve;
+    const int rc = curve == ZL_BLS12_381 ? circuit_arity_t<BLS12_381_Fr>(c, arity, in, depth, index, path, witness_only)
+                                         : circuit_arity_t<BN254_Fr>(c, arity, in, depth, index, path, witness_only);
+    if (rc) {
+        zl_circuit_free(c);
+        return rc;
+    }
+    *out = c;
+    return ZL_OK;
 }
 
 extern "C" {
@@ -804,6 +889,21 @@ int zl_circuit_poseidon_merkle(zl_curve_t curve, unsigned depth, const uint64_t*
 }
 int zl_circuit_poseidon_merkle_witness(zl_curve_t curve, unsigned depth, const uint64_t* leaf, uint64_t index, const uint64_t* path, zl_circuit** out) {
     return circuit_merkle(curve, depth, leaf, index, path, true, out);
+}
+int zl_circuit_poseidon_hash(zl_curve_t curve, unsigned arity, const uint64_t* in, zl_circuit** out) {
+    return circuit_arity(curve, arity, in, 0, 0, nullptr, false, out);
+}
+int zl_circuit_poseidon_hash_witness(zl_curve_t curve, unsigned arity, const uint64_t* in, zl_circuit** out) {
+    return circuit_arity(curve, arity, in, 0, 0, nullptr, true, out);
+}
+int zl_circuit_poseidon_merkle_leaf(zl_curve_t curve, unsigned arity, unsigned depth, const uint64_t* preimage, uint64_t index, const uint64_t* path, zl_circuit** out) {
+    if (depth < 1) return ZL_EINVAL;
+    return circuit_arity(curve, arity, preimage, depth, index, path, false, out);
+}
+int zl_circuit_poseidon_merkle_leaf_witness(zl_curve_t curve, unsigned arity, unsigned depth, const uint64_t* preimage, uint64_t index, const uint64_t* path,
+                                            zl_circuit** out) {
+    if (depth < 1) return ZL_EINVAL;
+    return circuit_arity(curve, arity, preimage, depth, index, path, true, out);
 }
 void zl_circuit_free(zl_circuit* c) {
     if (!c) return;

@@ -61,6 +61,16 @@ constexpr int MERKLE_PER_LEVEL = 4 + TRACE_PER_LINK;
 constexpr size_t merkle_row_elems(unsigned depth) { return 3 + (size_t)MERKLE_PER_LEVEL * depth; }
 static_assert(merkle_row_elems(1) == 241 && (merkle_row_elems(MAX_DEPTH) + MAX_DEPTH + 3) * 32 < STAGE_BUDGET, "a row and its inputs fit one staged chunk at every depth");
 
+// the hash circuit's assignment at an arity (zl_poseidon_hash_assignments): 1, digest, the inputs, then x^2, x^4, x^5 of the hash's 8 W + partial S-boxes less
+// the constant one; and the leaf-membership circuit's (zl_poseidon_merkle_leaf_assignments): 1, root, the preimage, the leaf hash's records, then the levels of
+// the membership circuit
+constexpr size_t trace_per_hash(unsigned arity) { return 3 * (size_t)(spec(arity).full_rounds * spec(arity).width + spec(arity).partial_rounds - 1); }
+static_assert(trace_per_hash(2) == TRACE_PER_LINK && trace_per_hash(3) == 258 && trace_per_hash(4) == 285 && trace_per_hash(5) == 309, "78, 86, 95, 103 recorded S-boxes");
+constexpr size_t hash_row_elems(unsigned arity) { return 2 + arity + trace_per_hash(arity); }
+constexpr size_t leaf_row_elems(unsigned arity, unsigned depth) { return hash_row_elems(arity) + (size_t)MERKLE_PER_LEVEL * depth; }
+static_assert(hash_row_elems(2) == 4 + TRACE_PER_LINK, "at arity 2 the hash row is the row of a one-link chain");
+static_assert((leaf_row_elems(MAX_ARITY, MAX_DEPTH) + MAX_ARITY + MAX_DEPTH + 2) * 32 < STAGE_BUDGET, "a row and its inputs fit one staged chunk at every arity and depth");
+
 constexpr bool geometry_ok(size_t n, unsigned depth) { return depth >= 1 && depth <= MAX_DEPTH && ((n >> depth) == 0 || n == ((size_t)1 << depth)); }
 constexpr size_t level_size(size_t n, unsigned k) { return k >= 64 ? (n ? 1 : 0) : (n >> k) + ((n & (((size_t)1 << k) - 1)) ? 1 : 0); }  // ceil(n / 2^k)
 constexpr size_t level_offset(size_t n, unsigned k) {  // elements in front of level k
@@ -84,6 +94,16 @@ int zl_poseidon_merkle_trace_rows(zl_ctx* ctx, int curve, const uint64_t* leaves
                                   size_t stride_elems, uint64_t* roots_out);
 int zl_poseidon_merkle_member_rows(zl_ctx* ctx, int curve, const void* d_nodes, size_t n, unsigned depth, const uint64_t* indices, size_t count, void* d_rows,
                                    size_t stride_elems, uint64_t* host_rows);
+// The producers of the arity-general provers (zl_groth16_prove_poseidon_hashes, zl_groth16_prove_merkle_leaf_paths / _members), under the same rules; arity
+// (2..5) is the caller's to check too.  _hash_trace_rows: HOST inputs (count x arity) -> rows in DEVICE memory, the digests to public_out.  _merkle_leaf_trace_rows:
+// HOST preimages (count x arity), indices and paths -> rows in DEVICE memory, the roots to roots_out.  _merkle_leaf_member_rows: a node array and the n x arity
+// preimages of its leaves in DEVICE memory, HOST indices -> rows at d_rows, or staged and downloaded to host_rows when that is not null; ZL_EINVAL when a
+// preimage does not hash to its leaf.
+int zl_poseidon_hash_trace_rows(zl_ctx* ctx, int curve, unsigned arity, const uint64_t* in, size_t count, void* d_rows, size_t stride_elems, uint64_t* public_out);
+int zl_poseidon_merkle_leaf_trace_rows(zl_ctx* ctx, int curve, unsigned arity, const uint64_t* preimages, const uint64_t* indices, const uint64_t* paths, unsigned depth,
+                                       size_t count, void* d_rows, size_t stride_elems, uint64_t* roots_out);
+int zl_poseidon_merkle_leaf_member_rows(zl_ctx* ctx, int curve, unsigned arity, const void* d_nodes, const void* d_preimages, size_t n, unsigned depth,
+                                        const uint64_t* indices, size_t count, void* d_rows, size_t stride_elems, uint64_t* host_rows);
 // The forest producer of the fused prover (zl_groth16_prove_forest_members).  _prover_view: ZL_EINVAL for a null or host-mirror forest or a ctx of another
 // device, else the forest's curve and depth.  _members_ok: ZL_EINVAL unless every (tree_of[i], indices[i]) names a leaf the forest holds.  _member_rows:
 // zl_poseidon_merkle_member_rows with a tree per item, issued on ctx (the forest's own ctx or another lane of its device); roots_out (host, may be null)

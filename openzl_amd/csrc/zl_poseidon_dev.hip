@@ -22,6 +22,10 @@
 //   k_pos_permute_w / k_pos_hash_w   widths 4, 5, 6 (arity 3, 4, 5 of pd::spec): their own permutation permute_w<FrP, W> on W state registers and a table per
 //                    (curve, width); the S-box reduces its input weakly where the lazy bound requires it (the argument stands above WideBounds).  Width 3 keeps
 //                    the kernels above; the entry points of every arity forward to them at arity 2.
+//   k_pos_hash_trace / k_pos_leaf_merkle_trace   the assignments of the arity-general circuits (zl_circuit_poseidon_hash / _merkle_leaf), widths 3..6, one lane per
+//                    row: permute_w with a recorder writes the S-box records of the hash; the leaf-membership kernel then hands the digest -- reduced weakly
+//                    (HandOver) -- to `depth` width-3 levels laid out as k_pos_merkle_trace's.  Sources: explicit preimages and paths, or a tree's node array beside
+//                    its leaves' preimages, where a preimage that does not hash to its leaf raises a second flag bit.
 // Arithmetic: the lazily reduced 9 x 29-bit Fr of zl_field28r.h (the NTT's multiplier), 1.29 - 1.46 x the carry-chain Fp<FrP> here and ahead of the 10 x 28 form at
 // every size measured (profiles/poseidon_field_ab.log); the bound argument stands beside the type below.  The host path stays on Fp<FrP>.
 // A lane at or above the item count returns before it reads or writes anything.  An input element >= r sets the flag word (atomicOr) and the lane goes on with
@@ -587,28 +591,38 @@ ZL_POS_WIDE_BOUNDS(BN254_Fr, 6, true, 28);       // 196 > 169, reduced
 static_assert(!WideBounds<BLS12_381_Fr, 3>::REDUCE && !WideBounds<BN254_Fr, 3>::REDUCE && WideBounds<BLS12_381_Fr, 3>::MAX_MUL == 64,
               "the same rule gives the width-3 unit's argument: no reduction, 64");
 
-template <class FrP, int W>
-__device__ __forceinline__ void sbox_w(El<FrP>& x) {
+// With REDUCE the recorder sees x^2, x^4, x^5 of the reduced input: the same field element, and all three are products (< 2r) whichever way the input came.
+template <class FrP, int W, class Rec>
+__device__ __forceinline__ void sbox_w(El<FrP>& x, Rec& rec, bool recorded) {
     if constexpr (WideBounds<FrP, W>::REDUCE) x = zl::wred(x);
     const El<FrP> x2 = zl::mul(x, x), x4 = zl::mul(x2, x2);
     x = zl::mul(x4, x);
+    if (recorded) rec(x2, x4, x);
+}
+// the S-boxes of lanes I .. W - 1 of a full round, one after the other.  A compile-time recursion, not a loop: with a recorder the body holds six multiplier
+// bodies per lane, and at width 6 the loop unroller gives up on it -- the state would then be indexed at run time and leave its registers.
+template <class FrP, int W, int I, class Rec>
+__device__ __forceinline__ void sbox_lanes(El<FrP> (&s)[W], Rec& rec) {
+    if constexpr (I < W) {
+        sbox_w<FrP, W>(s[I], rec, true);
+        sbox_lanes<FrP, W, I + 1>(s, rec);
+    }
 }
 // 8 (3W + W^2) + partial (3 + W^2) multiplications: 1 288, 1 976, 2 616 at widths 4, 5, 6.  One rolled round loop; the ROWS of the MDS product are a rolled loop
 // too, so a round holds 3W + W inlined multiplier bodies instead of 3W + W^2 (24 instead of 54 at width 6): row i is accumulated against the W state registers
 // and shifted into nx from the top, all register indices static, and after W rows nx[k] is row k.  Table addresses depend on the round and the row only.
-template <class FrP, int W>
-__device__ __forceinline__ void permute_w(const uint32_t* __restrict__ tab, El<FrP> (&s)[W]) {
+// `rec` (NoRec, or RowRec in the trace kernels) sees the S-boxes in round order, lane order within a round, without lane 0 of round 0 -- the order in which
+// poseidon::hash<FrP, W> of zl_host.h allocates them, as permute_dev's recorder does at width 3.
+template <class FrP, int W, class Rec>
+__device__ __forceinline__ void permute_w(const uint32_t* __restrict__ tab, El<FrP> (&s)[W], Rec& rec) {
     constexpr pd::Spec S = pd::spec_of_width(W);
     constexpr int half = (int)S.full_rounds / 2, partial = (int)S.partial_rounds, rounds = (int)S.rounds();
 #pragma unroll 1
     for (int rnd = 0; rnd < rounds; rnd++) {
 #pragma unroll
         for (int i = 0; i < W; i++) s[i] = zl::add(s[i], tab_ld<FrP>(tab, pd::tab_keys(W) + W * rnd + i));
-        sbox_w<FrP, W>(s[0]);
-        if (rnd < half || rnd >= half + partial) {
-#pragma unroll
-            for (int i = 1; i < W; i++) sbox_w<FrP, W>(s[i]);
-        }
+        sbox_w<FrP, W>(s[0], rec, rnd != 0);
+        if (rnd < half || rnd >= half + partial) sbox_lanes<FrP, W, 1>(s, rec);
         El<FrP> nx[W];
 #pragma unroll
         for (int i = 0; i < W; i++) nx[i] = ezero<FrP>();
@@ -636,7 +650,8 @@ __global__ __launch_bounds__(BLOCK) void k_pos_permute_w(const uint32_t* __restr
 #pragma unroll
     for (int i = 0; i < W; i++) ok &= dload<FrP>(st + 4 * i, s[i]);
     if (!ok) atomicOr(flag, 1u);
-    permute_w<FrP, W>(tab, s);
+    NoRec none;
+    permute_w<FrP, W>(tab, s, none);
 #pragma unroll
     for (int i = 0; i < W; i++) dstore<FrP>(st + 4 * i, s[i]);
 }
@@ -653,8 +668,159 @@ __global__ __launch_bounds__(BLOCK) void k_pos_hash_w(const uint32_t* __restrict
 #pragma unroll
     for (int i = 1; i < W; i++) ok &= dload<FrP>(x + 4 * (i - 1), s[i]);
     if (!ok) atomicOr(flag, 1u);
-    permute_w<FrP, W>(tab, s);
+    NoRec none;
+    permute_w<FrP, W>(tab, s, none);
     dstore<FrP>(out + p * 4, s[0]);
+}
+// the recording permutation of any width of the table: width 3 is the width-3 unit's own permute_dev (what k_pos_chain_trace and k_pos_merkle_trace run), the
+// wider ones permute_w
+template <class FrP, int W, class Rec>
+__device__ __forceinline__ void permute_any(const uint32_t* __restrict__ tab, El<FrP> (&s)[W], Rec& rec) {
+    if constexpr (W == 3) permute_dev<FrP>(tab, s[0], s[1], s[2], rec);
+    else permute_w<FrP, W>(tab, s, rec);
+}
+// k_pos_hash_w with the witness written out: the complete assignment of zl_circuit_poseidon_hash(curve, W - 1, in) per item, one lane each.  Row p = out +
+// p * stride elements (16-byte aligned): [0] = 1, [1] = the digest, [2 .. W + 1) the inputs, then the 3 (8 W + partial - 1) records of the hash; elements
+// behind them are not touched.  The inputs are copied before the permutation (rows and inputs do not overlap), [0] and [1] go out last.  pub (may be null)
+// receives the digest, densely.  At W = 3 the row is k_pos_chain_trace's for k = 1: the same permutation (permute_any), the same recorder, the same layout.
+template <class FrP, int W>
+__global__ __launch_bounds__(BLOCK) void k_pos_hash_trace(const uint32_t* __restrict__ tab, const uint64_t* __restrict__ in, size_t n, uint64_t* __restrict__ out,
+                                                          size_t stride, uint64_t* __restrict__ pub, uint32_t* __restrict__ flag) {
+    const size_t p = (size_t)blockIdx.x * BLOCK + threadIdx.x;
+    if (p >= n) return;
+    const uint64_t* x = in + p * (4 * (W - 1));
+    uint64_t* row = out + p * stride * 4;
+    El<FrP> s[W];
+    s[0] = tab_ld<FrP>(tab, pd::tab_tag(W));
+    bool ok = true;
+#pragma unroll
+    for (int i = 1; i < W; i++) {
+        const uint64_t* xi = x + 4 * (i - 1);
+        ok &= dload<FrP>(xi, s[i]);
+        copy16(row + 4 * (i + 1), xi[0], xi[1], xi[2], xi[3]);
+    }
+    if (!ok) atomicOr(flag, 1u);
+    RowRec<FrP> rec{row + 4 * (W + 1)};
+    permute_any<FrP, W>(tab, s, rec);
+    copy16(row, 1, 0, 0, 0);
+    dstore16<FrP>(row + 4, s[0]);
+    if (pub) dstore<FrP>(pub + p * 4, s[0]);
+}
+// The hand-over from the wide permutation into the width-3 levels of k_pos_leaf_merkle_trace.  The leaf digest is element 0 of the wide permutation's output:
+// a row sum below ROW r = 2 W r (8, 10, 12).  The width-3 unit's argument (above LazyP) takes a state element entering a round at < 6r; an unreduced
+// digest plus its round key would be squared at (ROW + 2)^2 = 100, 144, 196 -- above MUL_BOUND on BLS12-381 at every width and on BN254 at width 6.  So the
+// digest is reduced weakly (wred: below 128 r in, < 2r out) before it becomes `cur`, at every width above 3 and on both fields: the bound holds by
+// construction, not because inputs happen to stay small.  At width 3 the digest is the row sum of three products (< 6r), the running digest k_pos_merkle_trace
+// has, and goes over as it is.
+template <class FrP, int W>
+struct HandOver {
+    static constexpr int LEVEL_IN = 6;                         // what the width-3 unit's argument assumes of a state element entering a round
+    static constexpr int DIGEST = WideBounds<FrP, W>::ROW;     // the wide permutation's output
+    static constexpr bool REDUCE = DIGEST > LEVEL_IN;
+    static constexpr int CUR = REDUCE ? 2 : DIGEST;            // what enters the first level as left or right
+    static constexpr int LEVEL_SQ = (CUR + 2) * (CUR + 2);     // x^2 of it plus a round key
+    static_assert(DIGEST <= 128, "wred takes a value below 128 r");
+    static_assert(CUR <= LEVEL_IN && LEVEL_SQ <= 64 && LEVEL_SQ <= LazyP<FrP>::P::MUL_BOUND, "the width-3 levels take their first running digest within their bound");
+};
+#define ZL_POS_HAND_OVER(FrP, W, reduce, cur) static_assert(HandOver<FrP, W>::REDUCE == reduce && HandOver<FrP, W>::CUR == cur, "hand-over of " #FrP " at width " #W)
+ZL_POS_HAND_OVER(BLS12_381_Fr, 3, false, 6);  // a width-3 row sum: the running digest of k_pos_merkle_trace
+ZL_POS_HAND_OVER(BLS12_381_Fr, 4, true, 2);   // 8 r: (8 + 2)^2 = 100 > 70
+ZL_POS_HAND_OVER(BLS12_381_Fr, 5, true, 2);   // 10 r: 144 > 70
+ZL_POS_HAND_OVER(BLS12_381_Fr, 6, true, 2);   // 12 r: 196 > 70
+ZL_POS_HAND_OVER(BN254_Fr, 3, false, 6);
+ZL_POS_HAND_OVER(BN254_Fr, 4, true, 2);       // 100 <= 169 would pass the square, but not the 6 r the levels' argument is written for
+ZL_POS_HAND_OVER(BN254_Fr, 5, true, 2);
+ZL_POS_HAND_OVER(BN254_Fr, 6, true, 2);       // 196 > 169
+#undef ZL_POS_HAND_OVER
+// Where k_pos_leaf_merkle_trace reads item p's preimage (`per` = W - 1 elements), the digest its hash must equal (nullptr: nothing to compare with) and its
+// sibling at level k: explicit arrays, or a tree's node array beside the preimages of the tree's leaves, preimage of leaf i at element i * per.
+struct LeafPathSrc {
+    const uint64_t* preimages;
+    const uint64_t* paths;
+    unsigned depth;
+    __device__ __forceinline__ const uint64_t* preimage(size_t p, uint64_t, unsigned per) const { return preimages + p * per * 4; }
+    __device__ __forceinline__ const uint64_t* leaf_digest(uint64_t) const { return nullptr; }
+    __device__ __forceinline__ const uint64_t* sibling(size_t p, uint64_t, unsigned k) const { return paths + (p * depth + k) * 4; }
+    LeafPathSrc advanced(size_t first, unsigned per) const { return LeafPathSrc{preimages + first * per * 4, paths + first * depth * 4, depth}; }
+};
+struct LeafTreeSrc {
+    const uint64_t* nodes;
+    const uint64_t* preimages;
+    LevelTable lt;
+    __device__ __forceinline__ const uint64_t* preimage(size_t, uint64_t idx, unsigned per) const { return preimages + idx * per * 4; }
+    __device__ __forceinline__ const uint64_t* leaf_digest(uint64_t idx) const { return nodes + idx * 4; }
+    __device__ __forceinline__ const uint64_t* sibling(size_t, uint64_t idx, unsigned k) const {
+        const uint64_t sib = (idx >> k) ^ 1;
+        return sib < lt.size[k] ? nodes + (lt.off[k] + sib) * 4 : nullptr;
+    }
+    LeafTreeSrc advanced(size_t, unsigned) const { return *this; }
+};
+// The complete assignment of zl_circuit_poseidon_merkle_leaf(curve, W - 1, depth, preimage, index, path) per item, one lane each: the leaf hash through
+// permute_any (tab: the table of width W), then `depth` levels through permute_dev (tab3: the width-3 table), exactly k_pos_merkle_trace's.  Row p = out +
+// p * stride elements (16-byte aligned): [0] = 1, [1] = root, [2 .. W + 1) the preimage, the leaf hash's records, then level j at W + 1 + records + 238 j:
+// [+0] sibling, [+1] index bit, [+2] left, [+3] right, [+4 .. +238) the records of H(left, right); nothing behind the row is touched.  The leaf digest is not
+// part of the row (the circuit keeps it a linear combination); where the source knows the digest the tree holds for the leaf, a hash that differs from it sets
+// bit 1 of the flag word -- the row would otherwise be a valid one for another root.  pub (may be null) receives the root, densely.
+template <class FrP, int W, class Src>
+__global__ __launch_bounds__(BLOCK) void k_pos_leaf_merkle_trace(const uint32_t* __restrict__ tab, const uint32_t* __restrict__ tab3, const Src src,
+                                                                 const uint64_t* __restrict__ indices, unsigned depth, size_t n, uint64_t* __restrict__ out, size_t stride,
+                                                                 uint64_t* __restrict__ pub, uint32_t* __restrict__ flag) {
+    const size_t p = (size_t)blockIdx.x * BLOCK + threadIdx.x;
+    if (p >= n) return;
+    const uint64_t idx = indices[p];
+    uint64_t* row = out + p * stride * 4;
+    bool ok = true;
+    El<FrP> cur;
+    {
+        const uint64_t* x = src.preimage(p, idx, W - 1);
+        El<FrP> s[W];
+        s[0] = tab_ld<FrP>(tab, pd::tab_tag(W));
+#pragma unroll
+        for (int i = 1; i < W; i++) {
+            const uint64_t* xi = x + 4 * (i - 1);
+            ok &= dload<FrP>(xi, s[i]);
+            copy16(row + 4 * (i + 1), xi[0], xi[1], xi[2], xi[3]);
+        }
+        RowRec<FrP> rec{row + 4 * (W + 1)};
+        permute_any<FrP, W>(tab, s, rec);
+        if (const uint64_t* lw = src.leaf_digest(idx)) {
+            uint64_t d[4];
+            dstore<FrP>(d, s[0]);
+            if (d[0] != lw[0] || d[1] != lw[1] || d[2] != lw[2] || d[3] != lw[3]) atomicOr(flag, 2u);
+        }
+        if constexpr (HandOver<FrP, W>::REDUCE) cur = zl::wred(s[0]);
+        else cur = s[0];
+    }
+    uint64_t* lv = row + 4 * pd::hash_row_elems(W - 1);
+#pragma unroll 1
+    for (unsigned k = 0; k < depth; k++) {
+        const uint64_t* sw = src.sibling(p, idx, k);
+        El<FrP> sib = ezero<FrP>();
+        if (sw) {
+            ok &= dload<FrP>(sw, sib);
+            copy16(lv, sw[0], sw[1], sw[2], sw[3]);
+        } else {
+            copy16(lv, 0, 0, 0, 0);
+        }
+        const bool right = (idx >> k) & 1;
+        copy16(lv + 4, right ? 1 : 0, 0, 0, 0);
+        El<FrP> s0 = tab_ld<FrP>(tab3, pd::TAB_TAG), x, y;
+#pragma unroll
+        for (int w = 0; w < El<FrP>::L; w++) {
+            x.l[w] = right ? sib.l[w] : cur.l[w];
+            y.l[w] = right ? cur.l[w] : sib.l[w];
+        }
+        dstore16<FrP>(lv + 8, x);
+        dstore16<FrP>(lv + 12, y);
+        RowRec<FrP> rec{lv + 16};
+        permute_dev<FrP>(tab3, s0, x, y, rec);
+        cur = s0;
+        lv += (size_t)pd::MERKLE_PER_LEVEL * 4;
+    }
+    if (!ok) atomicOr(flag, 1u);
+    copy16(row, 1, 0, 0, 0);
+    dstore16<FrP>(row + 4, cur);
+    if (pub) dstore<FrP>(pub + p * 4, cur);
 }
 
 // ---------------------------------------------------------------------------------------------------------------- host path
@@ -842,6 +1008,71 @@ int host_merkle_assignments(const uint64_t* leaves, const uint64_t* indices, con
         for (unsigned k = 0; k < depth; k++) {
             const uint64_t* sw = paths + (i * depth + k) * 4;
             uint64_t* lv = row + 12 + (size_t)k * pd::MERKLE_PER_LEVEL * 4;
+            Fp<FrP> sib;
+            ok &= load_canon<FrP>(sw, sib);
+            const bool right = (indices[i] >> k) & 1;
+            memcpy(lv, sw, 32);
+            lv[4] = right ? 1 : 0;
+            lv[5] = lv[6] = lv[7] = 0;
+            Fp<FrP> st[3] = {zl::from_u64<FrP>(3), right ? sib : cur, right ? cur : sib};
+            store_canon<FrP>(lv + 8, st[1]);
+            store_canon<FrP>(lv + 12, st[2]);
+            rec.clear();
+            poseidon::permute_native_record(consts<FrP>(), st, rec);
+            cur = st[0];
+            for (size_t t = 0; t < rec.size(); t++) store_canon<FrP>(lv + 16 + 4 * t, rec[t]);
+        }
+        row[0] = 1;
+        row[1] = row[2] = row[3] = 0;
+        store_canon<FrP>(row + 4, cur);
+        return ok;
+    }) ? ZL_OK : ZL_EINVAL;
+}
+// the leaf hash of the two arity-general rows: inputs at row[2 ..), the records behind them; returns the digest (Montgomery) in *digest
+template <class FrP, int W>
+bool host_hash_records(const uint64_t* in, uint64_t* row, Fp<FrP>* digest) {
+    Fp<FrP> st[W];
+    st[0] = zl::from_u64<FrP>(pd::spec_of_width(W).tag);
+    bool ok = true;
+    for (int e = 1; e < W; e++) ok &= load_canon<FrP>(in + 4 * (e - 1), st[e]);
+    memcpy(row + 8, in, 32 * (W - 1));
+    std::vector<Fp<FrP>> rec;
+    rec.reserve(pd::trace_per_hash(W - 1));
+    poseidon::permute_native_record(consts<FrP, W>(), st, rec);
+    for (size_t t = 0; t < rec.size(); t++) store_canon<FrP>(row + 4 * (W + 1) + 4 * t, rec[t]);
+    *digest = st[0];
+    return ok;
+}
+// row i = the assignment of hash circuit i (2 + arity + 3 S(arity) elements): what poseidon_arity allocates at depth 0
+template <class FrP, int W>
+int host_hash_assignments(const uint64_t* in, size_t count, uint64_t* out) {
+    consts<FrP, W>();
+    constexpr size_t nv = pd::hash_row_elems(W - 1);
+    return host_for(count, [&](size_t i) {
+        uint64_t* row = out + i * nv * 4;
+        Fp<FrP> h;
+        const bool ok = host_hash_records<FrP, W>(in + i * (4 * (W - 1)), row, &h);
+        row[0] = 1;
+        row[1] = row[2] = row[3] = 0;
+        store_canon<FrP>(row + 4, h);
+        return ok;
+    }) ? ZL_OK : ZL_EINVAL;
+}
+// row i = the assignment of leaf membership i: the leaf hash as above, then the levels of host_merkle_assignments over its digest
+template <class FrP, int W>
+int host_leaf_assignments(const uint64_t* preimages, const uint64_t* indices, const uint64_t* paths, unsigned depth, size_t count, uint64_t* out) {
+    consts<FrP, W>();
+    consts<FrP>();
+    const size_t nv = pd::leaf_row_elems(W - 1, depth);
+    return host_for(count, [&](size_t i) {
+        uint64_t* row = out + i * nv * 4;
+        Fp<FrP> cur;
+        bool ok = host_hash_records<FrP, W>(preimages + i * (4 * (W - 1)), row, &cur);
+        std::vector<Fp<FrP>> rec;
+        rec.reserve(pd::TRACE_PER_LINK);
+        for (unsigned k = 0; k < depth; k++) {
+            const uint64_t* sw = paths + (i * depth + k) * 4;
+            uint64_t* lv = row + (pd::hash_row_elems(W - 1) + (size_t)k * pd::MERKLE_PER_LEVEL) * 4;
             Fp<FrP> sib;
             ok &= load_canon<FrP>(sw, sib);
             const bool right = (indices[i] >> k) & 1;
@@ -1319,6 +1550,96 @@ int dev_merkle_from_tree(zl_ctx* ctx, const void* d_nodes, size_t n, unsigned de
     const TreeSrc src{static_cast<const uint64_t*>(d_nodes), level_table(n, depth)};
     return merkle_trace_run<FrP, TreeSrc>(ctx, src, nullptr, indices, depth, count, static_cast<uint64_t*>(d_rows), stride, host_rows, nullptr);
 }
+// Every form of the hash trace at width W.  in: count x (W - 1) elements, staged per chunk when in_on_host, else device memory; host_rows != null: the rows
+// are staged, dense, and downloaded (d_rows and stride are ignored), otherwise row i goes to d_rows + i * stride elements; host_pub != null: the digest of
+// every item is staged and downloaded.  A chunk is one launch.
+template <class FrP, int W>
+int hash_trace_run(zl_ctx* ctx, const uint64_t* in, bool in_on_host, size_t count, uint64_t* d_rows, size_t stride, uint64_t* host_rows, uint64_t* host_pub) {
+    const uint32_t* tab;
+    int rc = get_table<FrP, W>(ctx, &tab);
+    if (rc) return rc;
+    constexpr size_t nv = pd::hash_row_elems(W - 1), in_per = 32 * (W - 1);
+    const size_t per = 32 + (in_on_host ? in_per : 0) + (host_rows ? nv * 32 : 0);
+    const size_t chunk = stage_items(per), m0 = count < chunk ? count : chunk;
+    const size_t o_in = up256(m0 * 32), o_rows = o_in + (in_on_host ? up256(m0 * in_per) : 0);
+    Stage s;
+    if ((rc = stage_get(ctx, o_rows + (host_rows ? m0 * nv * 32 : 0), &s))) return rc;
+    uint64_t* d_pub = host_pub ? reinterpret_cast<uint64_t*>(s.data) : nullptr;
+    uint64_t* d_in = reinterpret_cast<uint64_t*>(s.data + o_in);
+    uint64_t* d_stage_rows = reinterpret_cast<uint64_t*>(s.data + o_rows);
+    for (size_t first = 0; first < count; first += chunk) {
+        const size_t m = count - first < chunk ? count - first : chunk;
+        const uint64_t* from = in + first * (4 * (W - 1));
+        if (in_on_host) {
+            ZL_HIP(ctx, hipMemcpyAsync(d_in, from, m * in_per, hipMemcpyHostToDevice, ctx->stream));
+            from = d_in;
+        }
+        uint64_t* rows = host_rows ? d_stage_rows : d_rows + first * stride * 4;
+        ZL_POS_LAUNCH(ctx, (k_pos_hash_trace<FrP, W>), blocks_of(m), BLOCK, 0, tab, from, m, rows, host_rows ? nv : stride, d_pub, s.flag);
+        if (host_rows) ZL_HIP(ctx, hipMemcpyAsync(host_rows + first * nv * 4, d_stage_rows, m * nv * 32, hipMemcpyDeviceToHost, ctx->stream));
+        if (host_pub) ZL_HIP(ctx, hipMemcpyAsync(host_pub + first * 4, d_pub, m * 32, hipMemcpyDeviceToHost, ctx->stream));
+    }
+    return finish(ctx, s.flag);
+}
+// Every form of the leaf-membership trace at width W, as merkle_trace_run: indices are host memory and staged per chunk; hp != null: preimages and paths
+// are HOST memory and staged beside them (Src is LeafPathSrc and `src` is ignored); host_rows / host_pub as in hash_trace_run.
+struct HostLeafPaths {
+    const uint64_t* preimages;
+    const uint64_t* paths;
+};
+template <class FrP, int W, class Src>
+int leaf_trace_run(zl_ctx* ctx, Src src, const HostLeafPaths* hp, const uint64_t* indices, unsigned depth, size_t count, uint64_t* d_rows, size_t stride,
+                   uint64_t* host_rows, uint64_t* host_pub) {
+    const uint32_t *tab, *tab3;
+    int rc = get_table<FrP, W>(ctx, &tab);
+    if (rc || (rc = get_table<FrP>(ctx, &tab3))) return rc;
+    constexpr size_t pre_per = 32 * (W - 1);
+    const size_t nv = pd::leaf_row_elems(W - 1, depth);
+    const size_t per = 8 + 32 + (hp ? pre_per + (size_t)depth * 32 : 0) + (host_rows ? nv * 32 : 0);
+    const size_t chunk = stage_items(per), m0 = count < chunk ? count : chunk;
+    const size_t o_pub = up256(m0 * 8), o_pre = o_pub + up256(m0 * 32), o_path = o_pre + (hp ? up256(m0 * pre_per) : 0), o_rows = o_path + (hp ? up256(m0 * depth * 32) : 0);
+    Stage s;
+    if ((rc = stage_get(ctx, o_rows + (host_rows ? m0 * nv * 32 : 0), &s))) return rc;
+    uint64_t* d_idx = reinterpret_cast<uint64_t*>(s.data);
+    uint64_t* d_pub = host_pub ? reinterpret_cast<uint64_t*>(s.data + o_pub) : nullptr;
+    uint64_t* d_pre = reinterpret_cast<uint64_t*>(s.data + o_pre);
+    uint64_t* d_path = reinterpret_cast<uint64_t*>(s.data + o_path);
+    uint64_t* d_stage_rows = reinterpret_cast<uint64_t*>(s.data + o_rows);
+    for (size_t first = 0; first < count; first += chunk) {
+        const size_t m = count - first < chunk ? count - first : chunk;
+        ZL_HIP(ctx, hipMemcpyAsync(d_idx, indices + first, m * 8, hipMemcpyHostToDevice, ctx->stream));
+        Src from = src.advanced(first, W - 1);
+        if constexpr (std::is_same<Src, LeafPathSrc>::value) {
+            if (hp) {
+                ZL_HIP(ctx, hipMemcpyAsync(d_pre, hp->preimages + first * (4 * (W - 1)), m * pre_per, hipMemcpyHostToDevice, ctx->stream));
+                ZL_HIP(ctx, hipMemcpyAsync(d_path, hp->paths + first * depth * 4, m * depth * 32, hipMemcpyHostToDevice, ctx->stream));
+                from = LeafPathSrc{d_pre, d_path, depth};
+            }
+        }
+        uint64_t* rows = host_rows ? d_stage_rows : d_rows + first * stride * 4;
+        ZL_POS_LAUNCH(ctx, (k_pos_leaf_merkle_trace<FrP, W, Src>), blocks_of(m), BLOCK, 0, tab, tab3, from, d_idx, depth, m, rows, host_rows ? nv : stride, d_pub, s.flag);
+        if (host_rows) ZL_HIP(ctx, hipMemcpyAsync(host_rows + first * nv * 4, d_stage_rows, m * nv * 32, hipMemcpyDeviceToHost, ctx->stream));
+        if (host_pub) ZL_HIP(ctx, hipMemcpyAsync(host_pub + first * 4, d_pub, m * 32, hipMemcpyDeviceToHost, ctx->stream));
+    }
+    return finish(ctx, s.flag);
+}
+template <class FrP, int W>
+int dev_leaf_from_host(zl_ctx* ctx, const uint64_t* preimages, const uint64_t* indices, const uint64_t* paths, unsigned depth, size_t count, uint64_t* d_rows, size_t stride,
+                       uint64_t* host_rows, uint64_t* host_pub) {
+    const HostLeafPaths hp{preimages, paths};
+    return leaf_trace_run<FrP, W, LeafPathSrc>(ctx, LeafPathSrc{nullptr, nullptr, depth}, &hp, indices, depth, count, d_rows, stride, host_rows, host_pub);
+}
+template <class FrP, int W>
+int dev_leaf_from_paths(zl_ctx* ctx, const void* d_preimages, const uint64_t* indices, const void* d_paths, unsigned depth, size_t count, void* d_rows, size_t stride) {
+    const LeafPathSrc src{static_cast<const uint64_t*>(d_preimages), static_cast<const uint64_t*>(d_paths), depth};
+    return leaf_trace_run<FrP, W, LeafPathSrc>(ctx, src, nullptr, indices, depth, count, static_cast<uint64_t*>(d_rows), stride, nullptr, nullptr);
+}
+template <class FrP, int W>
+int dev_leaf_from_tree(zl_ctx* ctx, const void* d_nodes, const void* d_preimages, size_t n, unsigned depth, const uint64_t* indices, size_t count, void* d_rows,
+                       size_t stride, uint64_t* host_rows) {
+    const LeafTreeSrc src{static_cast<const uint64_t*>(d_nodes), static_cast<const uint64_t*>(d_preimages), level_table(n, depth)};
+    return leaf_trace_run<FrP, W, LeafTreeSrc>(ctx, src, nullptr, indices, depth, count, static_cast<uint64_t*>(d_rows), stride, host_rows, nullptr);
+}
 
 // ---------------------------------------------------------------------------------------------------------------- the Merkle forest: host side
 // What an append does, worked out on the host before anything is written: the slot of every leaf, the touched trees (in the order the input first names them)
@@ -1490,6 +1811,22 @@ int zl_poseidon_merkle_trace_rows(zl_ctx* ctx, int curve, const uint64_t* leaves
 int zl_poseidon_merkle_member_rows(zl_ctx* ctx, int curve, const void* d_nodes, size_t n, unsigned depth, const uint64_t* indices, size_t count, void* d_rows,
                                    size_t stride_elems, uint64_t* host_rows) {
     return ZL_POS_CURVE(curve, dev_merkle_from_tree, ctx, d_nodes, n, depth, indices, count, d_rows, stride_elems, host_rows);
+}
+// every width of the table, 3 included (the arity-general traces at arity 2)
+#define ZL_POS_ANYW_OF(FrP, width, fn, ...) \
+    ((width) == 3 ? fn<FrP, 3>(__VA_ARGS__) : (width) == 4 ? fn<FrP, 4>(__VA_ARGS__) : (width) == 5 ? fn<FrP, 5>(__VA_ARGS__) : fn<FrP, 6>(__VA_ARGS__))
+#define ZL_POS_ANYW(curve, width, fn, ...) \
+    ((curve) == ZL_BLS12_381 ? ZL_POS_ANYW_OF(BLS12_381_Fr, width, fn, __VA_ARGS__) : ZL_POS_ANYW_OF(BN254_Fr, width, fn, __VA_ARGS__))
+int zl_poseidon_hash_trace_rows(zl_ctx* ctx, int curve, unsigned arity, const uint64_t* in, size_t count, void* d_rows, size_t stride_elems, uint64_t* public_out) {
+    return ZL_POS_ANYW(curve, arity + 1, hash_trace_run, ctx, in, true, count, static_cast<uint64_t*>(d_rows), stride_elems, nullptr, public_out);
+}
+int zl_poseidon_merkle_leaf_trace_rows(zl_ctx* ctx, int curve, unsigned arity, const uint64_t* preimages, const uint64_t* indices, const uint64_t* paths, unsigned depth,
+                                       size_t count, void* d_rows, size_t stride_elems, uint64_t* roots_out) {
+    return ZL_POS_ANYW(curve, arity + 1, dev_leaf_from_host, ctx, preimages, indices, paths, depth, count, static_cast<uint64_t*>(d_rows), stride_elems, nullptr, roots_out);
+}
+int zl_poseidon_merkle_leaf_member_rows(zl_ctx* ctx, int curve, unsigned arity, const void* d_nodes, const void* d_preimages, size_t n, unsigned depth,
+                                        const uint64_t* indices, size_t count, void* d_rows, size_t stride_elems, uint64_t* host_rows) {
+    return ZL_POS_ANYW(curve, arity + 1, dev_leaf_from_tree, ctx, d_nodes, d_preimages, n, depth, indices, count, d_rows, stride_elems, host_rows);
 }
 
 extern "C" {
@@ -1705,6 +2042,56 @@ int zl_poseidon_merkle_member_assignments_dev(zl_ctx* ctx, zl_curve_t curve, con
     if (count == 0) return ZL_OK;
     ZL_HIP(ctx, hipSetDevice(ctx->device));
     return ZL_POS_CURVE(curve, dev_merkle_from_tree, ctx, d_nodes, n, depth, indices, count, d_out, stride_elems, nullptr);
+}
+// ---- the assignments of the arity-general circuits (zl_circuit_poseidon_hash, zl_circuit_poseidon_merkle_leaf)
+size_t zl_poseidon_hash_assignment_elems(unsigned arity) {
+    return pd::arity_ok(arity) ? pd::hash_row_elems(arity) : 0;
+}
+size_t zl_poseidon_merkle_leaf_assignment_elems(unsigned arity, unsigned depth) {
+    return !pd::arity_ok(arity) || depth < 1 || depth > pd::MAX_DEPTH ? 0 : pd::leaf_row_elems(arity, depth);
+}
+int zl_poseidon_hash_assignments(zl_ctx* ctx, zl_curve_t curve, unsigned arity, const uint64_t* in, size_t count, uint64_t* out) {
+    if (!valid_curve(curve) || !pd::arity_ok(arity) || (count && (!in || !out))) return ZL_EINVAL;
+    if (count == 0) return ZL_OK;
+    if (on_host(ctx, count)) return ZL_POS_ANYW(curve, arity + 1, host_hash_assignments, in, count, out);
+    ZL_HIP(ctx, hipSetDevice(ctx->device));
+    return ZL_POS_ANYW(curve, arity + 1, hash_trace_run, ctx, in, true, count, nullptr, 0, out, nullptr);
+}
+int zl_poseidon_hash_assignments_dev(zl_ctx* ctx, zl_curve_t curve, unsigned arity, const void* d_in, size_t count, void* d_out, size_t stride_elems) {
+    const size_t nv = zl_poseidon_hash_assignment_elems(arity);
+    if (!ctx || !valid_curve(curve) || nv == 0 || stride_elems < nv || (count && (!d_in || !d_out)) || ((uintptr_t)d_out & 15)) return ZL_EINVAL;
+    if (count == 0) return ZL_OK;
+    ZL_HIP(ctx, hipSetDevice(ctx->device));
+    return ZL_POS_ANYW(curve, arity + 1, hash_trace_run, ctx, static_cast<const uint64_t*>(d_in), false, count, static_cast<uint64_t*>(d_out), stride_elems, nullptr, nullptr);
+}
+int zl_poseidon_merkle_leaf_assignments(zl_ctx* ctx, zl_curve_t curve, unsigned arity, const uint64_t* preimages, const uint64_t* indices, const uint64_t* paths,
+                                        unsigned depth, size_t count, uint64_t* out) {
+    const size_t nv = zl_poseidon_merkle_leaf_assignment_elems(arity, depth);
+    if (!valid_curve(curve) || nv == 0 || (count && (!preimages || !indices || !paths || !out)) || !indices_below(indices, count, (uint64_t)1 << depth)) return ZL_EINVAL;
+    if (count == 0) return ZL_OK;
+    if (on_host(ctx, count)) return ZL_POS_ANYW(curve, arity + 1, host_leaf_assignments, preimages, indices, paths, depth, count, out);
+    ZL_HIP(ctx, hipSetDevice(ctx->device));
+    return ZL_POS_ANYW(curve, arity + 1, dev_leaf_from_host, ctx, preimages, indices, paths, depth, count, nullptr, nv, out, nullptr);
+}
+int zl_poseidon_merkle_leaf_assignments_dev(zl_ctx* ctx, zl_curve_t curve, unsigned arity, const void* d_preimages, const uint64_t* indices, const void* d_paths,
+                                            unsigned depth, size_t count, void* d_out, size_t stride_elems) {
+    const size_t nv = zl_poseidon_merkle_leaf_assignment_elems(arity, depth);
+    if (!ctx || !valid_curve(curve) || nv == 0 || stride_elems < nv || (count && (!d_preimages || !indices || !d_paths || !d_out)) || ((uintptr_t)d_out & 15) ||
+        !indices_below(indices, count, (uint64_t)1 << depth))
+        return ZL_EINVAL;
+    if (count == 0) return ZL_OK;
+    ZL_HIP(ctx, hipSetDevice(ctx->device));
+    return ZL_POS_ANYW(curve, arity + 1, dev_leaf_from_paths, ctx, d_preimages, indices, d_paths, depth, count, d_out, stride_elems);
+}
+int zl_poseidon_merkle_leaf_member_assignments_dev(zl_ctx* ctx, zl_curve_t curve, unsigned arity, const void* d_nodes, const void* d_preimages, size_t n, unsigned depth,
+                                                   const uint64_t* indices, size_t count, void* d_out, size_t stride_elems) {
+    const size_t nv = zl_poseidon_merkle_leaf_assignment_elems(arity, depth);
+    if (!ctx || !valid_curve(curve) || nv == 0 || !pd::geometry_ok(n, depth) || stride_elems < nv || (count && (!d_nodes || !d_preimages || !indices || !d_out)) ||
+        ((uintptr_t)d_out & 15) || !indices_below(indices, count, n))
+        return ZL_EINVAL;
+    if (count == 0) return ZL_OK;
+    ZL_HIP(ctx, hipSetDevice(ctx->device));
+    return ZL_POS_ANYW(curve, arity + 1, dev_leaf_from_tree, ctx, d_nodes, d_preimages, n, depth, indices, count, d_out, stride_elems, nullptr);
 }
 
 // ---- the Merkle forest
