@@ -145,7 +145,10 @@ int zl_groth16_keys_pk(const zl_g16_keys* k, zl_g16_pk* pk);
 
 /* The proof points are taken as given: callers that accept proofs from outside deserialize them with zl_groth16_proof_from_bytes, which
  * checks curve membership and the subgroup (as arkworks' deserialization does); A or B at infinity is rejected here.
- * Groth16::verify (host pairing; public_inputs: n x 4 u64 canonical, without the leading ONE): *ok = 1 accepted, 0 rejected */
+ * Groth16::verify (host pairing; public_inputs: n x 4 u64 canonical (each < r; otherwise ZL_EINVAL, nothing computed, outputs untouched), without the
+ * leading ONE): *ok = 1 accepted, 0 rejected.  A value at or above r is an error and not a verdict of 0: x + k r is the residue x, so the pairing equation
+ * cannot tell the two encodings apart while a caller that stores the 32 bytes can; the reference's typed field elements fail at deserialisation, and
+ * zl_msm and the batched Poseidon entry points refuse over-wide scalars the same way. */
 int zl_groth16_verify(const zl_g16_keys* k, const uint64_t* public_inputs, size_t n, const zl_g16_proof* proof, int* ok);
 size_t zl_groth16_proof_bytes(zl_curve_t curve);
 int zl_groth16_proof_to_bytes(zl_curve_t curve, const zl_g16_proof* proof, uint8_t* out);

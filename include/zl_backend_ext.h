@@ -408,7 +408,8 @@ int zl_pairing_products(zl_ctx* ctx, zl_curve_t curve, const uint64_t* ps_xy, co
  *   prod_i e(rho_i A_i, B_i) * e(-sum_i rho_i C_i, delta) * e(-sum_i rho_i IC_i, gamma) * e(-(sum_i rho_i) alpha, beta) == 1,
  * IC_i = gamma_abc[0] + sum_j x_ij gamma_abc[j+1], so the last three pairs are shared by the whole batch (count + 3 Miller loops, one final exponentiation).
  * rho_i: nonzero 128-bit scalars from SplitMix64(*seed), or from the OS (getrandom) when seed == NULL.  A seed the prover can predict voids soundness:
- * pass NULL in production.  public_inputs: count x n_public x 4 u64 canonical (without the leading ONE).
+ * pass NULL in production.  public_inputs: count x n_public x 4 u64 canonical (each < r; otherwise ZL_EINVAL, nothing computed, outputs untouched),
+ * without the leading ONE.  One value at or above r refuses the whole call, before rho is drawn: an error as in zl_groth16_verify, not a verdict.
  * *ok = 1 iff every proof verifies.  ok_each (optional, count bytes): per-proof verdicts, each equal to what zl_groth16_verify returns for that proof;
  * computed from the batch when it accepts, by per-proof products (device Miller loops, host final exponentiations) when it rejects.
  * A proof with A or B at infinity is invalid, as in zl_groth16_verify.  n_public + 1 != the key's gamma_abc length: ZL_EINVAL.  count == 0: *ok = 1.
@@ -438,7 +439,9 @@ int zl_groth16_proofs_from_bytes_batch(zl_ctx* ctx, zl_curve_t curve, const uint
 /* zl_groth16_verify_batch over wire proofs: the records are decoded on the device (as above), then the proofs that decoded go through the random linear
  * combination of zl_groth16_verify_batch with their public inputs.  ok_each[i] (optional) = 1 iff record i decodes AND verifies, i.e. what
  * zl_groth16_proof_from_bytes followed by zl_groth16_verify gives; *ok = 1 iff every record does; status (optional, count codes) = the decode statuses.
- * public_inputs, n_public, seed: as zl_groth16_verify_batch (n_public + 1 != the key's gamma_abc length: ZL_EINVAL; count == 0: *ok = 1). */
+ * public_inputs, n_public, seed: as zl_groth16_verify_batch (n_public + 1 != the key's gamma_abc length: ZL_EINVAL; count == 0: *ok = 1).  public_inputs
+ * are canonical (each < r; otherwise ZL_EINVAL, nothing computed, outputs untouched): all count x n_public values are checked ahead of the decoder, those
+ * of a record that would not decode included, and status is among the outputs left untouched. */
 int zl_groth16_verify_batch_bytes(zl_ctx* ctx, const zl_g16_keys* k, const uint64_t* public_inputs, size_t n_public, const uint8_t* proofs_bytes,
                                   size_t count, const uint64_t* seed, int* ok, uint8_t* ok_each, int32_t* status);
 /* Uncompressed form (ark's serialize_uncompressed / serialize_unchecked): x then y, flags on the last byte of y; a finite point

@@ -128,7 +128,7 @@ int zl_test_fq12_inverse(zl_curve_t curve, const uint64_t* in12, uint64_t* out12
 int zl_test_fq12_zeta(zl_curve_t curve, uint64_t* out);
 /* zl_groth16_verify_batch's random linear combination computed entirely on the host (lock-step Engine::multi_pairing, host scalar multiplications), against
  * a verifying key given as points: alpha_g1 (x||y), beta_g2 / gamma_g2 / delta_g2 (x.c0||x.c1||y.c0||y.c1), gamma_abc (n_public + 1 G1 points).  Same rho
- * derivation, rules and outputs as zl_groth16_verify_batch. */
+ * derivation, rules and outputs as zl_groth16_verify_batch; public_inputs canonical (each < r; otherwise ZL_EINVAL, nothing computed, outputs untouched). */
 int zl_test_verify_batch_host(zl_curve_t curve, const uint64_t* alpha_g1, const uint64_t* beta_g2, const uint64_t* gamma_g2, const uint64_t* delta_g2,
                               const uint64_t* gamma_abc, size_t n_public, const zl_g16_proof* proofs, const uint64_t* public_inputs, size_t count,
                               const uint64_t* seed, int* ok, uint8_t* ok_each);

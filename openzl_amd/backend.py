@@ -2116,7 +2116,8 @@ class Groth16Keys:
                 for p in out[:n]]
 
     def verify(self, proof, public_inputs: np.ndarray) -> bool:
-        """Groth16::verify(vk, input, proof) with the host pairing; proof = (a, a_inf, b, b_inf, c, c_inf)"""
+        """Groth16::verify(vk, input, proof) with the host pairing; proof = (a, a_inf, b, b_inf, c, c_inf); public_inputs: (n_public, 4) canonical words
+        (each < r; otherwise ZL_EINVAL, nothing computed, outputs untouched): a BackendError, not a verdict"""
         pc = _proof_struct(proof)
         pub = np.ascontiguousarray(public_inputs, dtype=np.uint64).reshape(-1, 4)
         ok = C.c_int(0)
@@ -2125,8 +2126,9 @@ class Groth16Keys:
 
     def verify_batch(self, proofs, public_inputs, seed: Optional[int] = None, each: bool = False):
         """Groth16::verify of many proofs in one random linear combination (zl_groth16_verify_batch): device Miller loops and MSM, one host final
-        exponentiation.  public_inputs: (count, n_public, 4) canonical words (or anything that reshapes to it); seed=None draws the combination from
-        the OS (what a verifier must do); an int makes it reproducible (tests).  Returns ok, or (ok, per-proof verdicts) with each=True."""
+        exponentiation.  public_inputs: (count, n_public, 4) canonical words (each < r; otherwise ZL_EINVAL, nothing computed, outputs untouched: a
+        BackendError for the whole batch, not a verdict), or anything that reshapes to it; seed=None draws the combination from the OS (what a verifier
+        must do); an int makes it reproducible (tests).  Returns ok, or (ok, per-proof verdicts) with each=True."""
         n = len(proofs)
         pub_arr = np.asarray(public_inputs, dtype=np.uint64)
         if pub_arr.ndim == 3:
@@ -2146,7 +2148,8 @@ class Groth16Keys:
 
     def verify_batch_bytes(self, data, count: int, public_inputs, seed: Optional[int] = None, each: bool = False, n_public: Optional[int] = None):
         """zl_groth16_verify_batch_bytes: verify_batch over `count` WIRE proofs (packed proof_to_bytes records): decoded on the device, then the random linear
-        combination over the records that decoded.  public_inputs / seed as verify_batch; n_public overrides what the shape of public_inputs implies.
+        combination over the records that decoded.  public_inputs / seed as verify_batch: canonical (each < r; otherwise ZL_EINVAL, nothing computed, outputs
+        untouched), those of a record that does not decode included; n_public overrides what the shape of public_inputs implies.
         Returns ok, or (ok, per-record verdicts, decode statuses (count,) int32) with each=True; a record that does not decode is a rejected proof."""
         pub_arr = np.asarray(public_inputs, dtype=np.uint64)
         if n_public is None:

@@ -72,6 +72,23 @@ void g1_store(G1Of<E> p, bool negate, uint64_t* out) {
 // combination of the batch, sum_rho_c, skips the words when the flag is set; every other user of C comes through here and never looks at the flag.)
 template <class E>
 G1Of<E> proof_c(const zl_g16_proof& pr) { return g1_load<E>(pr.c); }
+// The public-input contract of every verifying entry point: n values of 4 u64 words, each below r.  x + k r is the residue x -- the Montgomery products of the
+// combination reduce it, and the 256 scalar bits of the per-proof IC walk over a point of order r -- so without this check x and x + k r would verify as one
+// statement, while a caller that keys on the 32 bytes it handed over has two.  A plain word comparison, made before anything is drawn, allocated or launched;
+// a call that fails it is refused whole (ZL_EINVAL, no output written), as the reference's typed field elements fail at deserialisation and as the MSM and
+// the batched Poseidon entry points refuse the same kind of input.
+template <class E>
+bool publics_canonical(const uint64_t* pubs, size_t n) {
+    using FrP = typename E::FrP;
+    static_assert(FrP::N == 8, "scalar fields are 8 x 32 bits");
+    for (size_t i = 0; i < n; i++) {
+        const uint64_t* w = pubs + 4 * i;
+        uint64_t br = 0;
+        for (int j = 0; j < 8; j++) br = (((w[j / 2] >> (32 * (j % 2))) & 0xffffffffu) - FrP::mod(j) - br) >> 63;
+        if (!br) return false;  // no borrow out of w - r: w >= r
+    }
+    return true;
+}
 template <class E>
 FrOf<E> fr_canon(const uint64_t* w4) {
     FrOf<E> c;
@@ -180,6 +197,7 @@ Result<bool> Groth16<E>::verify(const VerifyingContext& vk, const Input& input, 
     const BatchVk v = batch_vk<E>(vk);
     if (v.n_abc == 0 || input.size() + 1 != v.n_abc) return res;  // ark: wrong number of public inputs -> Err(MalformedVerifyingKey)
     static_assert(sizeof(F) == 32, "the public inputs are handed on as 4 u64 words each");
+    if (!publics_canonical<E>(reinterpret_cast<const uint64_t*>(input.data()), input.size())) return res;  // ark: such an input fails to deserialise
     uint64_t ps[4 * Q1<E>], qs[8 * Q1<E>];
     four_pairs<E>(v, &proof, reinterpret_cast<const uint64_t*>(input.data()), 1, ps, qs);
     res.ok = true;
@@ -405,6 +423,7 @@ int verify_batch_t(zl_ctx* ctx, const BatchVk& vk, const uint64_t* pubs, size_t 
         *ok = 1;
         return ZL_OK;
     }
+    if (!publics_canonical<E>(pubs, count * n_public)) return ZL_EINVAL;
     std::vector<uint64_t> rho(2 * count), ps, qs;
     int rc = draw_rho(seed, rho);
     if (rc) return rc;
@@ -474,6 +493,9 @@ int zl_groth16_verify_batch_bytes(zl_ctx* ctx, const zl_g16_keys* k, const uint6
     if (!ctx || !k || !ok || (count && !proofs_bytes) || (count && n_public && !public_inputs)) return ZL_EINVAL;
     const size_t n_abc = k->curve == ZL_BLS12_381 ? batch_vk<Bls12_381>(k).n_abc : batch_vk<Bn254>(k).n_abc;
     if (n_public + 1 != n_abc) return ZL_EINVAL;  // before any work, as zl_groth16_verify_batch
+    // every public input, ahead of the decoder and whether or not its record will decode (count == 0 reads none)
+    const int canonical = by_curve(k->curve, [&](auto e) { return publics_canonical<decltype(e)>(public_inputs, count * n_public) ? (int)ZL_OK : (int)ZL_EINVAL; });
+    if (canonical) return canonical;
     // decode -> host structs -> the existing combination over the proofs that decoded, with their public inputs
     std::vector<zl_g16_proof> proofs(count);
     std::vector<int32_t> st(count);

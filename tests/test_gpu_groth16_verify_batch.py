@@ -2,15 +2,13 @@
 R1CS shapes are accepted; verdicts equal per-proof zl_groth16_verify and the host implementation of the same random linear combination
 (zl_test_verify_batch_host); tampered batches are rejected with exactly the tampered proofs marked; NULL seed, empty batches, a wrong n_public and a key
 round-tripped through its wire format behave."""
-import ctypes as C
-
 import numpy as np
 import pytest
 
 import batch_verify_util as bv
 from oracle_lib import po
 from openzl_amd import Circuit, Groth16Keys
-from openzl_amd.backend import BackendError, _proofs_array, _pubs_of, hook_verify_batch_host, _p64, u8p
+from openzl_amd.backend import BackendError, hook_verify_batch_host
 
 CURVES = [po.BLS12_381, po.BN254]
 
@@ -86,68 +84,22 @@ def test_duplicates_wrong_n_public_and_key_round_trip(poseidon, backend):
         k2.close()
 
 
-def _g1_pts(curve, arr):
-    import oracle_lib as ol
-
-    arr = np.asarray(arr).reshape(-1, 2 * ol.nlq(curve))
-    return [ol.limbs_to_point(curve, row, int(not row.any())) for row in arr]
-
-
-def _g2_pts(curve, arr):
-    import oracle_lib as ol
-
-    nq = ol.nlq(curve)
-    out = []
-    for row in np.asarray(arr).reshape(-1, 4 * nq):
-        v = ol.limbs_to_ints(row.reshape(4, nq))
-        out.append(None if not row.any() else ((v[0], v[1]), (v[2], v[3])))
-    return out
-
-
-def _oracle_keys(backend, case):
-    """the oracle's proving key of a generic shape, encoded by the Python restatement and decoded by zl_groth16_keys_from_bytes"""
-    c = case.curve
-    pk = case.pk
-    vk = {"alpha_g1": _g1_pts(c, pk["alpha_g1"])[0], "beta_g2": _g2_pts(c, pk["beta_g2"])[0], "gamma_g2": _g2_pts(c, case.vk["gamma_g2"])[0],
-          "delta_g2": _g2_pts(c, pk["delta_g2"])[0], "gamma_abc_g1": _g1_pts(c, case.vk["gamma_abc"])}
-    pts = {"vk": vk, "beta_g1": _g1_pts(c, pk["beta_g1"])[0], "delta_g1": _g1_pts(c, pk["delta_g1"])[0], "a_query": _g1_pts(c, pk["a_query"]),
-           "b_g1_query": _g1_pts(c, pk["b_g1_query"]), "b_g2_query": _g2_pts(c, pk["b_g2_query"]), "h_query": _g1_pts(c, pk["h_query"]),
-           "l_query": _g1_pts(c, pk["l_query"])}
-    data = po.groth16_pk_bytes(c, pts)
-    buf = (C.c_uint8 * len(data)).from_buffer_copy(data)
-    k = C.c_void_p()
-    backend._check(backend.L.zl_groth16_keys_from_bytes(backend._ctx, c.cid, buf, len(data), 0, C.byref(k)), "zl_groth16_keys_from_bytes")
-    return k
-
-
-def _verify_raw(backend, k, proofs, pubs, n_public, seed):
-    n = len(proofs)
-    arr = _proofs_array(proofs)
-    pub = _pubs_of(pubs, n, n_public)
-    sd = np.array([seed], dtype=np.uint64)
-    ok = C.c_int(0)
-    each = np.zeros(max(1, n), dtype=np.uint8)
-    backend._check(backend.L.zl_groth16_verify_batch(backend._ctx, k, _p64(pub), n_public, arr, n, _p64(sd), C.byref(ok), each.ctypes.data_as(u8p)),
-                   "zl_groth16_verify_batch")
-    return bool(ok.value), each[:n].astype(bool)
-
-
 @pytest.mark.gpu
 @pytest.mark.parametrize("curve", CURVES, ids=lambda c: c.name)
 @pytest.mark.parametrize("kind", ["smallest", "many_publics"])
 def test_generic_shapes_oracle_proofs(backend, curve, kind):
     case = bv.Case(curve, kind)
     proofs = case.proofs(64, seed=4)
-    k = _oracle_keys(backend, case)
+    k = bv.oracle_keys(backend, case)
     try:
         for count in (1, 7, 64):
             pubs = case.pubs(count)
-            ok, each = _verify_raw(backend, k, proofs[:count], pubs, case.n_public, seed=11)
+            ok, each = bv.verify_raw(backend, k, proofs[:count], pubs, case.n_public, seed=11)
             assert ok and each.all(), count
             hok, heach = hook_verify_batch_host(curve.cid, case.vk, proofs[:count], pubs, case.n_public, seed=11)
             assert hok and (heach == each).all()
         bad, bpubs, idx = bv.tampered(curve, proofs[:7], case.pubs(7), "public" if case.n_public else "swap_c")
-        ok, each = _verify_raw(backend, k, bad, bpubs, case.n_public, seed=11)
+        ok, each = bv.verify_raw(backend, k, bad, bpubs, case.n_public, seed=11)
         assert not ok and [bool(e) for e in each] == [i not in idx for i in range(7)]
     finally:
         backend.L.zl_groth16_keys_free(k)

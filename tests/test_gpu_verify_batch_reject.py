@@ -3,8 +3,6 @@
 public input, A at infinity).  The verdicts equal the host implementation of the same batch (zl_test_verify_batch_host), the host-thread path of the same
 entry point (ZL_TUNE_FEXP_DEV_MIN very large) and the set of tampered indices; once through the bytes-in verifier.  B or C at infinity (zero words and
 the flag) on each of those paths and over several launch sets (ZL_TUNE_PAIR_SET), and a rejected batch under a combination drawn from the OS."""
-import os
-
 import numpy as np
 import pytest
 
@@ -63,18 +61,7 @@ def _with_env(dev_min, chunk, fn):
     return _with_vars({"ZL_TUNE_FEXP_DEV_MIN": dev_min, "ZL_TUNE_FEXP_CHUNK": chunk}, fn)
 
 
-def _with_vars(names, fn):
-    old = {k: os.environ.get(k) for k in names}
-    try:
-        for k, v in names.items():
-            os.environ[k] = str(v)
-        return fn()
-    finally:
-        for k, v in old.items():
-            if v is None:
-                os.environ.pop(k, None)
-            else:
-                os.environ[k] = v
+_with_vars = bv.with_vars
 
 
 SCENARIOS = [
