@@ -224,6 +224,53 @@ int zl_poseidon_permute_batch_w(zl_ctx* ctx, zl_curve_t curve, unsigned width, u
 int zl_poseidon_hash_batch(zl_ctx* ctx, zl_curve_t curve, unsigned arity, const uint64_t* in, size_t count, uint64_t* out);
 /* device pointers, never the host path (ctx == NULL is ZL_EINVAL); in and out may not overlap */
 int zl_poseidon_hash_batch_dev(zl_ctx* ctx, zl_curve_t curve, unsigned arity, const void* d_in, size_t count, void* d_out);
+/* ---- the duplex-sponge authenticated cipher over the same permutation: the reference's FixedDuplexer<N, Spec<F, ARITY>> (openzl-crypto/src/permutation/duplex.rs,
+ * sponge.rs; poseidon/encryption.rs), width W = ARITY + 1 in 3..6, rate W - 1: lanes 1 .. W - 1 of the state, lane 0 is never written.  Per message:
+ *   setup blocks  padded_chunks_with(key, rate, 0) followed by padded_chunks_with(header, rate, 0) (openzl-util/src/vec.rs:60-77), which ALWAYS ends in one more,
+ *                 zero-padded chunk: a key of exactly `rate` elements gives its block and an all-zero block, an empty header one all-zero block;
+ *                 SB = key_len / rate + 1 + header_len / rate + 1 >= 2.  Absorbing block b: state[1 + i] += b[i], then permute;
+ *   encrypt j     state[1 + i] += p[j][i]; c[j][i] = state[1 + i], read before the permutation; then permute;
+ *   decrypt j     p[j][i] = c[j][i] - state[1 + i]; state[1 + i] = c[j][i]; then permute;
+ *   tag           state[1] after the last permutation (Tag::read).
+ * SB + blocks dependent permutations per message (zl_poseidon_duplex_permutations; 0 for a parameter out of range), all inside one launch, one device lane per
+ * message (k_pos_duplex).  initial_state: W elements shared by the batch (FixedEncryption::initial_state), host memory in every form, NULL = the zero state.
+ * Dense layouts: item i's key at element i * key_len, its header at i * header_len, its text at i * blocks * rate, its tag at i; keys may be NULL when key_len is 0,
+ * headers when header_len is 0.  A fixed-length message: the caller pads.  The output text may be exactly the input text pointer (in place); any other overlap is
+ * the caller's error.  Decryption writes the plaintext of EVERY item and reports per item whether the computed tag equals the given one (ok_each[i] = 1 / 0, the
+ * reference's (bool, plaintext)): a tag mismatch is not an error, the call returns ZL_OK.
+ * The common rules of the batched Poseidon entry points hold (count == 0 is ZL_OK and writes nothing; ctx == NULL or a count below ZL_TUNE_POSEIDON_DEV_MIN runs
+ * the host mirror, poseidon::duplex_encrypt / duplex_decrypt of csrc/zl_host.h, over the host pool; otherwise staged in chunks of ZL_TUNE_POSEIDON_CHUNK items
+ * under the byte budget; finished on return; results are byte-identical on every path).  ZL_EINVAL: width outside 3..6, key_len or header_len above 64, blocks
+ * outside 1..1024 (one launch is one dependent chain: the cap keeps it near a second at width 6), a null required pointer, an unknown curve, any element >= r --
+ * initial_state is checked on the host before any work, the rest through the flag word.  The _dev forms take DEVICE pointers for keys, headers, texts and tags
+ * (never the host path: ctx == NULL is ZL_EINVAL); initial_state and ok_each stay host memory. */
+size_t zl_poseidon_duplex_permutations(unsigned width, size_t key_len, size_t header_len, size_t blocks);
+int zl_poseidon_duplex_encrypt_batch(zl_ctx* ctx, zl_curve_t curve, unsigned width, const uint64_t* initial_state, const uint64_t* keys, size_t key_len,
+                                     const uint64_t* headers, size_t header_len, const uint64_t* plaintexts, size_t blocks, size_t count, uint64_t* ciphertexts,
+                                     uint64_t* tags);
+int zl_poseidon_duplex_decrypt_batch(zl_ctx* ctx, zl_curve_t curve, unsigned width, const uint64_t* initial_state, const uint64_t* keys, size_t key_len,
+                                     const uint64_t* headers, size_t header_len, const uint64_t* ciphertexts, const uint64_t* tags, size_t blocks, size_t count,
+                                     uint64_t* plaintexts, uint8_t* ok_each);
+int zl_poseidon_duplex_encrypt_batch_dev(zl_ctx* ctx, zl_curve_t curve, unsigned width, const uint64_t* initial_state, const void* d_keys, size_t key_len,
+                                         const void* d_headers, size_t header_len, const void* d_plaintexts, size_t blocks, size_t count, void* d_ciphertexts,
+                                         void* d_tags);
+int zl_poseidon_duplex_decrypt_batch_dev(zl_ctx* ctx, zl_curve_t curve, unsigned width, const uint64_t* initial_state, const void* d_keys, size_t key_len,
+                                         const void* d_headers, size_t header_len, const void* d_ciphertexts, const void* d_tags, size_t blocks, size_t count,
+                                         void* d_plaintexts, uint8_t* ok_each);
+/* The cipher in circuit (host compilers): "the public ciphertext and tag are the encryption, under a secret key and the public header, of a secret plaintext".
+ * initial_state (NULL = zero) and the padding are constants; key_len >= 1 (with no key nothing is secret and leading permutations would fold away).
+ * Public inputs: the tag, the blocks x rate ciphertext elements (Ciphertext::extend: tag, then message), the header_len header elements.  Witnesses: the key, the
+ * plaintext, then the S-box records (x^2, x^4, x^5) of the SB + blocks permutations in execution order, round order, lane order within a round.  Rows: the
+ * records', then tag = public tag, then one row a * 1 = c per ciphertext element.  Additions are linear and allocate nothing; constant folding decides which
+ * S-boxes exist: in the first permutation lane 0 of round 0 folds and so does every rate lane without a key element, Z = max(0, rate - key_len) of them; every
+ * later permutation records all F = 8 W + partial S-boxes.  S = (F - 1 - Z) + (SB + blocks - 1) F, and the shape (n_instance, n_witness, n_constraints) is
+ * (2 + blocks rate + header_len, key_len + blocks rate + 3 S, 3 S + 1 + blocks rate).  n_instance >= 4 where every other circuit family has 2: no family's prover
+ * takes another's keys.  _witness: the same circuit in the witness-only compiler, assignments equal word for word.  These circuits go through
+ * zl_groth16_compile, zl_groth16_prove_circuit and the batched prover as any circuit does.  ZL_EINVAL as above, and for key_len == 0. */
+int zl_circuit_poseidon_encrypt(zl_curve_t curve, unsigned width, const uint64_t* initial_state, const uint64_t* key, size_t key_len, const uint64_t* header,
+                                size_t header_len, const uint64_t* plaintext, size_t blocks, zl_circuit** out);
+int zl_circuit_poseidon_encrypt_witness(zl_curve_t curve, unsigned width, const uint64_t* initial_state, const uint64_t* key, size_t key_len, const uint64_t* header,
+                                        size_t header_len, const uint64_t* plaintext, size_t blocks, zl_circuit** out);
 /* out[i] = h_k with h_1 = H(x0[i], x1[i]), h_{j+1} = H(h_j, x1[i]): the public input of zl_circuit_poseidon_chain(curve, k, x0[i], x1[i]); the k dependent
  * hashes of a chain run inside one kernel.  k == 0: ZL_EINVAL, as zl_circuit_poseidon_chain. */
 int zl_poseidon_chain_batch(zl_ctx* ctx, zl_curve_t curve, const uint64_t* x0, const uint64_t* x1, uint32_t k, size_t count, uint64_t* out);

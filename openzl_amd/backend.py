@@ -50,6 +50,8 @@ ABI_SYMBOLS = [
     "zl_poseidon_hash_assignment_elems", "zl_poseidon_merkle_leaf_assignment_elems", "zl_poseidon_hash_assignments", "zl_poseidon_hash_assignments_dev",
     "zl_poseidon_merkle_leaf_assignments", "zl_poseidon_merkle_leaf_assignments_dev", "zl_poseidon_merkle_leaf_member_assignments_dev",
     "zl_groth16_prove_poseidon_hashes", "zl_groth16_prove_merkle_leaf_paths", "zl_groth16_prove_merkle_leaf_members",
+    "zl_poseidon_duplex_permutations", "zl_poseidon_duplex_encrypt_batch", "zl_poseidon_duplex_decrypt_batch", "zl_poseidon_duplex_encrypt_batch_dev",
+    "zl_poseidon_duplex_decrypt_batch_dev", "zl_circuit_poseidon_encrypt", "zl_circuit_poseidon_encrypt_witness",
 ]
 
 
@@ -152,6 +154,14 @@ def load_library(path: Optional[str] = None):
     L.zl_poseidon_permute_batch_w.argtypes = [vp, C.c_int, C.c_uint, u64p, C.c_size_t]
     L.zl_poseidon_hash_batch.argtypes = [vp, C.c_int, C.c_uint, u64p, C.c_size_t, u64p]
     L.zl_poseidon_hash_batch_dev.argtypes = [vp, C.c_int, C.c_uint, vp, C.c_size_t, vp]
+    L.zl_poseidon_duplex_permutations.argtypes = [C.c_uint, C.c_size_t, C.c_size_t, C.c_size_t]
+    L.zl_poseidon_duplex_permutations.restype = C.c_size_t
+    L.zl_poseidon_duplex_encrypt_batch.argtypes = [vp, C.c_int, C.c_uint, u64p, u64p, C.c_size_t, u64p, C.c_size_t, u64p, C.c_size_t, C.c_size_t, u64p, u64p]
+    L.zl_poseidon_duplex_decrypt_batch.argtypes = [vp, C.c_int, C.c_uint, u64p, u64p, C.c_size_t, u64p, C.c_size_t, u64p, u64p, C.c_size_t, C.c_size_t, u64p, u8p]
+    L.zl_poseidon_duplex_encrypt_batch_dev.argtypes = [vp, C.c_int, C.c_uint, u64p, vp, C.c_size_t, vp, C.c_size_t, vp, C.c_size_t, C.c_size_t, vp, vp]
+    L.zl_poseidon_duplex_decrypt_batch_dev.argtypes = [vp, C.c_int, C.c_uint, u64p, vp, C.c_size_t, vp, C.c_size_t, vp, vp, C.c_size_t, C.c_size_t, vp, u8p]
+    L.zl_circuit_poseidon_encrypt.argtypes = [C.c_int, C.c_uint, u64p, u64p, C.c_size_t, u64p, C.c_size_t, u64p, C.c_size_t, C.POINTER(vp)]
+    L.zl_circuit_poseidon_encrypt_witness.argtypes = L.zl_circuit_poseidon_encrypt.argtypes
     L.zl_poseidon_chain_batch.argtypes = [vp, C.c_int, u64p, u64p, C.c_uint32, C.c_size_t, u64p]
     L.zl_poseidon_chain_assignment_elems.argtypes = [C.c_uint32]
     L.zl_poseidon_chain_assignment_elems.restype = C.c_size_t
@@ -571,6 +581,34 @@ class Backend:
     def poseidon_hash_dev(self, curve: int, arity: int, d_in: int, count: int, d_out: int):
         """zl_poseidon_hash_batch_dev: count x arity elements at device address d_in -> count digests at d_out; finished on return"""
         self._check(self.L.zl_poseidon_hash_batch_dev(self._ctx, curve, arity, C.c_void_p(d_in), count, C.c_void_p(d_out)), "zl_poseidon_hash_batch_dev")
+
+    def poseidon_duplex_encrypt(self, curve: int, initial_state, keys, headers, plaintexts):
+        """the duplex cipher (zl_poseidon_duplex_encrypt_batch): plaintexts (count, N, W - 1, 4) -- which fixes the width W --, keys (count, K, 4), headers
+        (count, H, 4), initial_state (W, 4) or None (zero) -> (ciphertexts shaped as plaintexts, tags (count, 4))"""
+        return _poseidon_duplex(self.L, self._ctx, curve, initial_state, keys, headers, plaintexts, None)
+
+    def poseidon_duplex_decrypt(self, curve: int, initial_state, keys, headers, ciphertexts, tags):
+        """zl_poseidon_duplex_decrypt_batch -> (plaintexts, ok): ok[i] is whether tags[i] is the tag of item i; the plaintexts are returned either way"""
+        return _poseidon_duplex(self.L, self._ctx, curve, initial_state, keys, headers, ciphertexts, tags)
+
+    def poseidon_duplex_encrypt_dev(self, curve: int, width: int, initial_state, d_keys: int, key_len: int, d_headers: int, header_len: int, d_plaintexts: int,
+                                    blocks: int, count: int, d_ciphertexts: int, d_tags: int):
+        """zl_poseidon_duplex_encrypt_batch_dev on device addresses (d_ciphertexts may be d_plaintexts); initial_state stays host memory; finished on return"""
+        st = _duplex_state(initial_state, width)
+        self._check(self.L.zl_poseidon_duplex_encrypt_batch_dev(self._ctx, curve, width, None if st is None else _p64(st), C.c_void_p(d_keys), key_len,
+                                                                C.c_void_p(d_headers), header_len, C.c_void_p(d_plaintexts), blocks, count, C.c_void_p(d_ciphertexts),
+                                                                C.c_void_p(d_tags)), "zl_poseidon_duplex_encrypt_batch_dev")
+
+    def poseidon_duplex_decrypt_dev(self, curve: int, width: int, initial_state, d_keys: int, key_len: int, d_headers: int, header_len: int, d_ciphertexts: int,
+                                    d_tags: int, blocks: int, count: int, d_plaintexts: int) -> np.ndarray:
+        """zl_poseidon_duplex_decrypt_batch_dev on device addresses -> the (count,) bool verdicts (host memory)"""
+        st = _duplex_state(initial_state, width)
+        ok = np.zeros(count, dtype=np.uint8)
+        self._check(self.L.zl_poseidon_duplex_decrypt_batch_dev(self._ctx, curve, width, None if st is None else _p64(st), C.c_void_p(d_keys), key_len,
+                                                                C.c_void_p(d_headers), header_len, C.c_void_p(d_ciphertexts), C.c_void_p(d_tags), blocks, count,
+                                                                C.c_void_p(d_plaintexts), ok.ctypes.data_as(C.POINTER(C.c_uint8)) if count else None),
+                    "zl_poseidon_duplex_decrypt_batch_dev")
+        return ok.astype(bool)
 
     def poseidon_hash2(self, curve: int, xy: np.ndarray) -> np.ndarray:
         """(count, 2, 4) canonical pairs -> (count, 4) digests H(x, y)"""
@@ -1439,6 +1477,54 @@ def _poseidon_hash(L, ctx, curve: int, inputs) -> np.ndarray:
     return out
 
 
+def _duplex_state(initial_state, width: int):
+    if initial_state is None:
+        return None
+    st = np.ascontiguousarray(np.asarray(initial_state, dtype=np.uint64))
+    if st.shape != (width, 4):
+        raise ValueError("initial_state is (W, 4) uint64 words")
+    return st
+
+
+def _poseidon_duplex(L, ctx, curve: int, initial_state, keys, headers, texts, tags):
+    """tags None: encrypt -> (ciphertexts, tags); otherwise decrypt -> (plaintexts, ok)"""
+    t = np.ascontiguousarray(np.asarray(texts, dtype=np.uint64))
+    k = np.ascontiguousarray(np.asarray(keys, dtype=np.uint64))
+    h = np.ascontiguousarray(np.asarray(headers, dtype=np.uint64))
+    if t.ndim != 4 or t.shape[3] != 4 or k.ndim != 3 or h.ndim != 3 or k.shape[2] != 4 or h.shape[2] != 4 or not k.shape[0] == h.shape[0] == t.shape[0]:
+        raise ValueError("texts are (count, N, W - 1, 4), keys (count, K, 4), headers (count, H, 4) uint64 words")
+    count, blocks, width = t.shape[0], t.shape[1], t.shape[2] + 1
+    st = _duplex_state(initial_state, width)
+    stp = None if st is None else _p64(st)
+    out = np.zeros_like(t)
+    if tags is None:
+        tg = np.zeros((count, 4), dtype=np.uint64)
+        _pos_check(L, L.zl_poseidon_duplex_encrypt_batch(ctx, curve, width, stp, _ptr_or_none(k), k.shape[1], _ptr_or_none(h), h.shape[1], _ptr_or_none(t), blocks, count,
+                                                         _ptr_or_none(out), _ptr_or_none(tg)), "zl_poseidon_duplex_encrypt_batch")
+        return out, tg
+    tg = np.ascontiguousarray(np.asarray(tags, dtype=np.uint64).reshape(count, 4))
+    ok = np.zeros(count, dtype=np.uint8)
+    _pos_check(L, L.zl_poseidon_duplex_decrypt_batch(ctx, curve, width, stp, _ptr_or_none(k), k.shape[1], _ptr_or_none(h), h.shape[1], _ptr_or_none(t), _ptr_or_none(tg),
+                                                     blocks, count, _ptr_or_none(out), ok.ctypes.data_as(C.POINTER(C.c_uint8)) if count else None),
+               "zl_poseidon_duplex_decrypt_batch")
+    return out, ok.astype(bool)
+
+
+def poseidon_duplex_permutations(width: int, key_len: int, header_len: int, blocks: int) -> int:
+    """dependent permutations per message: key_len // rate + 1 + header_len // rate + 1 + blocks (0 for a parameter out of range)"""
+    if min(width, key_len, header_len, blocks) < 0:
+        return 0
+    return int(load_library().zl_poseidon_duplex_permutations(width, key_len, header_len, blocks))
+
+
+def poseidon_duplex_encrypt_host(curve: int, initial_state, keys, headers, plaintexts):
+    return _poseidon_duplex(load_library(), None, curve, initial_state, keys, headers, plaintexts, None)
+
+
+def poseidon_duplex_decrypt_host(curve: int, initial_state, keys, headers, ciphertexts, tags):
+    return _poseidon_duplex(load_library(), None, curve, initial_state, keys, headers, ciphertexts, tags)
+
+
 def _poseidon_hash2(L, ctx, curve: int, xy) -> np.ndarray:
     v = _elems(xy, 2)
     out = np.zeros((v.shape[0], 4), dtype=np.uint64)
@@ -1884,6 +1970,34 @@ class Circuit:
         """the leaf-membership circuit (zl_circuit_poseidon_merkle_leaf): the fold of path (depth integers, bottom up) over the Poseidon hash of `preimage`
         (2..5 integers: the arity) at position index equals the public root.  witness_only: as in the constructor."""
         return cls._arity(curve, preimage, depth, index, path, witness_only, "zl_circuit_poseidon_merkle_leaf")
+
+    @classmethod
+    def poseidon_encrypt(cls, curve: int, initial_state, key, header, plaintext, witness_only: bool = False) -> "Circuit":
+        """the duplex-encryption circuit (zl_circuit_poseidon_encrypt): the public tag and ciphertext are the encryption of the secret `plaintext` -- N blocks of
+        W - 1 integers each, which fixes the width W -- under the secret `key` (>= 1 integers) and the public `header`; initial_state: W integers or None (zero).
+        Public inputs: tag, ciphertext, header.  witness_only: as in the constructor."""
+        what = "zl_circuit_poseidon_encrypt"
+        self = cls.__new__(cls)
+        self.L = load_library()
+        self.curve = curve
+        self.witness_only = witness_only
+        self._c = C.c_void_p()
+        blocks = [list(b) for b in plaintext]
+        width = len(blocks[0]) + 1 if blocks else 0
+        flat = [v for b in blocks for v in b]
+        st = None if initial_state is None else list(initial_state)
+        if any(len(b) != width - 1 for b in blocks) or (st is not None and len(st) != width) or any(
+                not 0 <= int(v) < 2**256 for v in flat + list(key) + list(header) + (st or [])):
+            raise BackendError(-1, what)
+        arr = lambda vs: np.array([[(int(v) >> (64 * j)) & (2**64 - 1) for j in range(4)] for v in vs], dtype=np.uint64).reshape(-1, 4)
+        k, h, p, s0 = arr(key), arr(header), arr(flat), arr(st or [])
+        fn = self.L.zl_circuit_poseidon_encrypt_witness if witness_only else self.L.zl_circuit_poseidon_encrypt
+        rc = fn(curve, width, None if st is None else _p64(s0), _ptr_or_none(k), k.shape[0], _ptr_or_none(h), h.shape[0], _ptr_or_none(p), len(blocks),
+                C.byref(self._c))
+        if rc:
+            raise BackendError(rc, what)
+        self._export()
+        return self
 
     @property
     def shape(self):

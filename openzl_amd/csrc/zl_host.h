@@ -389,14 +389,11 @@ void permute_native_record(const Constants<FrP, W>& c, Fp<FrP> state[W], std::ve
         for (int i = 0; i < W; i++) state[i] = nx[i];
     }
 }
-// in-circuit hash of W - 1 inputs (Hasher::hash, hash.rs:123-135; Spec<F, ARITY>, plugins/arkworks/src/poseidon/mod.rs:225-322): state =
-// (2^arity - 1, in[0] .. in[W - 2]), output = lane 0.  S-boxes are allocated in round order, lane order within a round, each as x^2, x^4, x^5
+// the in-circuit permutation on W variables, in place: what hash runs on (tag, inputs) and the duplex cipher's circuit (poseidon_encrypt, zl_host.hip) on
+// its running state.  S-boxes are allocated in round order, lane order within a round, each as x^2, x^4, x^5; one whose input is a constant folds
 template <class FrP, int W>
-FpVar<FrP> hash(const Constants<FrP, W>& c, const FpVar<FrP>* in, R1CS<FrP>& compiler) {
+void permute(const Constants<FrP, W>& c, FpVar<FrP> state[W], R1CS<FrP>& compiler) {
     using V = FpVar<FrP>;
-    V state[W];
-    state[0] = compiler.constant(zl::from_u64<FrP>(c.SPEC.tag));
-    for (int i = 1; i < W; i++) state[i] = in[i - 1];
     const int half = c.FULL_ROUNDS / 2;
     for (int rnd = 0; rnd < c.FULL_ROUNDS + c.PARTIAL_ROUNDS; rnd++) {
         for (int i = 0; i < W; i++) state[i] = compiler.add_const(state[i], c.round_keys[W * rnd + i]);
@@ -414,6 +411,15 @@ FpVar<FrP> hash(const Constants<FrP, W>& c, const FpVar<FrP>* in, R1CS<FrP>& com
         }
         for (int i = 0; i < W; i++) state[i] = nx[i];
     }
+}
+// in-circuit hash of W - 1 inputs (Hasher::hash, hash.rs:123-135; Spec<F, ARITY>, plugins/arkworks/src/poseidon/mod.rs:225-322): state =
+// (2^arity - 1, in[0] .. in[W - 2]), output = lane 0
+template <class FrP, int W>
+FpVar<FrP> hash(const Constants<FrP, W>& c, const FpVar<FrP>* in, R1CS<FrP>& compiler) {
+    FpVar<FrP> state[W];
+    state[0] = compiler.constant(zl::from_u64<FrP>(c.SPEC.tag));
+    for (int i = 1; i < W; i++) state[i] = in[i - 1];
+    permute<FrP, W>(c, state, compiler);
     return state[0];
 }
 // the arity-2 form the chain and the Merkle levels call: the W = 3 instance
@@ -421,6 +427,53 @@ template <class FrP>
 FpVar<FrP> hash(const Constants<FrP>& c, const FpVar<FrP>& x, const FpVar<FrP>& y, R1CS<FrP>& compiler) {
     const FpVar<FrP> in[2] = {x, y};
     return hash<FrP, 3>(c, in, compiler);
+}
+
+// ---- the duplex-sponge authenticated cipher over the permutation (openzl-crypto/src/permutation/duplex.rs, sponge.rs; poseidon/encryption.rs) ----
+// Rate W - 1, lanes 1 .. W - 1; lane 0 is never written.  The setup blocks are padded_chunks_with(key, rate, 0) followed by padded_chunks_with(header,
+// rate, 0) (openzl-util/src/vec.rs:60-77): ALWAYS one last, zero-padded chunk per sequence, also when nothing is left over -- floor(K / rate) + 1 key blocks,
+// floor(H / rate) + 1 header blocks.  Every block is added into the rate and the state permuted; a message block's ciphertext is the rate read BEFORE the
+// permutation.  The tag is lane 1 after the last permutation.  Elements are Montgomery; the padding zeros are skipped, not added.
+constexpr size_t duplex_setup_blocks(unsigned width, size_t key_len, size_t header_len) { return key_len / (width - 1) + 1 + header_len / (width - 1) + 1; }
+template <class FrP, int W>
+void duplex_setup(const Constants<FrP, W>& c, Fp<FrP> state[W], const Fp<FrP>* key, size_t key_len, const Fp<FrP>* header, size_t header_len) {
+    constexpr size_t rate = W - 1;
+    for (int part = 0; part < 2; part++) {
+        const Fp<FrP>* src = part ? header : key;
+        const size_t len = part ? header_len : key_len;
+        for (size_t b = 0; b <= len / rate; b++) {
+            for (size_t i = 0; i < rate && b * rate + i < len; i++) state[1 + i] = zl::add(state[1 + i], src[b * rate + i]);
+            permute_native(c, state);
+        }
+    }
+}
+// text: blocks x rate elements, plaintext in, ciphertext out; state: the initial state in, left as the cipher leaves it; returns the tag
+template <class FrP, int W>
+Fp<FrP> duplex_encrypt(const Constants<FrP, W>& c, Fp<FrP> state[W], const Fp<FrP>* key, size_t key_len, const Fp<FrP>* header, size_t header_len, Fp<FrP>* text,
+                       size_t blocks) {
+    constexpr size_t rate = W - 1;
+    duplex_setup(c, state, key, key_len, header, header_len);
+    for (size_t j = 0; j < blocks; j++) {
+        for (size_t i = 0; i < rate; i++) text[j * rate + i] = state[1 + i] = zl::add(state[1 + i], text[j * rate + i]);
+        permute_native(c, state);
+    }
+    return state[1];
+}
+// text: ciphertext in, plaintext out; returns the COMPUTED tag, which the caller compares with the one it was given (Verify)
+template <class FrP, int W>
+Fp<FrP> duplex_decrypt(const Constants<FrP, W>& c, Fp<FrP> state[W], const Fp<FrP>* key, size_t key_len, const Fp<FrP>* header, size_t header_len, Fp<FrP>* text,
+                       size_t blocks) {
+    constexpr size_t rate = W - 1;
+    duplex_setup(c, state, key, key_len, header, header_len);
+    for (size_t j = 0; j < blocks; j++) {
+        for (size_t i = 0; i < rate; i++) {
+            const Fp<FrP> ct = text[j * rate + i];
+            text[j * rate + i] = zl::sub(ct, state[1 + i]);
+            state[1 + i] = ct;
+        }
+        permute_native(c, state);
+    }
+    return state[1];
 }
 }  // namespace poseidon
 

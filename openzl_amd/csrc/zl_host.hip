@@ -714,6 +714,64 @@ static R1CS<FrP> poseidon_arity(bool witness_only, const Fp<FrP>* in_canon, unsi
     return cs;
 }
 
+// The duplex cipher in circuit (poseidon::duplex_encrypt is its native form): "the public ciphertext and tag are the encryption, under a secret key and the
+// public header, of a secret plaintext".  The initial state and the padding are constants; additions into the rate are linear and allocate nothing; the
+// compiler's constant folding decides which S-boxes of the first permutation exist (lane 0 of round 0 and every rate lane without a key element fold).
+// Public inputs: the tag, the blocks x rate ciphertext elements (Ciphertext::extend: tag, then message), the header.  Witnesses: the key, the plaintext, then
+// the S-box records of the permutations in execution order.  Rows: the records', then tag = public tag, then one row per ciphertext element.  The full
+// compiler allocates its public inputs first (the native values), the witness-only one last, as the other circuits do.  All inputs canonical, below r.
+template <class FrP, int W>
+static R1CS<FrP> poseidon_encrypt(bool witness_only, const Fp<FrP>* init_canon, const Fp<FrP>* key_canon, size_t key_len, const Fp<FrP>* header_canon, size_t header_len,
+                                  const Fp<FrP>* text_canon, size_t blocks) {
+    using F = Fp<FrP>;
+    using V = FpVar<FrP>;
+    static const poseidon::Constants<FrP, W> consts;
+    constexpr size_t rate = W - 1;
+    const size_t n_text = blocks * rate;
+    std::vector<F> key(key_len), header(header_len), text(n_text);
+    for (size_t i = 0; i < key_len; i++) key[i] = zl::to_mont(key_canon[i]);
+    for (size_t i = 0; i < header_len; i++) header[i] = zl::to_mont(header_canon[i]);
+    for (size_t i = 0; i < n_text; i++) text[i] = zl::to_mont(text_canon[i]);
+    R1CS<FrP> cs = witness_only ? R1CS<FrP>::for_witness() : R1CS<FrP>::for_proofs();
+    V pub_tag;
+    std::vector<V> pub_ct(n_text), hv(header_len);
+    if (!witness_only) {
+        F st[W];
+        for (int i = 0; i < W; i++) st[i] = zl::to_mont(init_canon[i]);
+        std::vector<F> ct = text;
+        pub_tag = cs.new_input(poseidon::duplex_encrypt<FrP, W>(consts, st, key.data(), key_len, header.data(), header_len, ct.data(), blocks));
+        for (size_t i = 0; i < n_text; i++) pub_ct[i] = cs.new_input(ct[i]);
+        for (size_t i = 0; i < header_len; i++) hv[i] = cs.new_input(header[i]);
+    }
+    std::vector<V> kv(key_len), pv(n_text), cv(n_text);
+    for (size_t i = 0; i < key_len; i++) kv[i] = cs.new_witness(key[i]);
+    for (size_t i = 0; i < n_text; i++) pv[i] = cs.new_witness(text[i]);
+    // (a witness-only compiler keeps no linear combinations, so the header's VALUES can enter the state before its variables exist)
+    if (witness_only)
+        for (size_t i = 0; i < header_len; i++) hv[i] = V{typename R1CS<FrP>::LC{}, header[i], false};
+    V state[W];
+    for (int i = 0; i < W; i++) state[i] = cs.constant(zl::to_mont(init_canon[i]));
+    for (int part = 0; part < 2; part++) {
+        const std::vector<V>& src = part ? hv : kv;
+        for (size_t b = 0; b <= src.size() / rate; b++) {
+            for (size_t i = 0; i < rate && b * rate + i < src.size(); i++) state[1 + i] = cs.add(state[1 + i], src[b * rate + i]);
+            poseidon::permute<FrP, W>(consts, state, cs);
+        }
+    }
+    for (size_t j = 0; j < blocks; j++) {
+        for (size_t i = 0; i < rate; i++) cv[j * rate + i] = state[1 + i] = cs.add(state[1 + i], pv[j * rate + i]);
+        poseidon::permute<FrP, W>(consts, state, cs);
+    }
+    if (witness_only) {
+        pub_tag = cs.new_input(state[1].value);
+        for (size_t i = 0; i < n_text; i++) pub_ct[i] = cs.new_input(cv[i].value);
+        for (size_t i = 0; i < header_len; i++) cs.new_input(header[i]);
+    }
+    cs.enforce_equal(state[1], pub_tag);
+    for (size_t i = 0; i < n_text; i++) cs.enforce_equal(cv[i], pub_ct[i]);
+    return cs;
+}
+
 }  // namespace openzl
 
 // ------------------------------------------------------------------------------------------------ C-ABI hooks
@@ -812,9 +870,50 @@ static int circuit_arity(zl_curve_t curve, unsigned arity, const uint64_t* in, u
     *out = c;
     return ZL_OK;
 }
+template <class FrP>
+static int circuit_encrypt_t(zl_circuit* c, unsigned width, const uint64_t* initial_state, const uint64_t* key, size_t key_len, const uint64_t* header, size_t header_len,
+                             const uint64_t* plaintext, size_t blocks, bool witness_only) {
+    std::vector<Fp<FrP>> st, k, h, p;
+    const uint64_t zero_state[4 * 6] = {0};
+    if (!elems_below_r<FrP>(initial_state ? initial_state : zero_state, width, st) || !elems_below_r<FrP>(key, key_len, k) ||
+        !elems_below_r<FrP>(header, header_len, h) || !elems_below_r<FrP>(plaintext, blocks * (width - 1), p))
+        return ZL_EINVAL;
+    switch (width) {
+    case 3: circuit_set(c, poseidon_encrypt<FrP, 3>(witness_only, st.data(), k.data(), key_len, h.data(), header_len, p.data(), blocks)); break;
+    case 4: circuit_set(c, poseidon_encrypt<FrP, 4>(witness_only, st.data(), k.data(), key_len, h.data(), header_len, p.data(), blocks)); break;
+    case 5: circuit_set(c, poseidon_encrypt<FrP, 5>(witness_only, st.data(), k.data(), key_len, h.data(), header_len, p.data(), blocks)); break;
+    default: circuit_set(c, poseidon_encrypt<FrP, 6>(witness_only, st.data(), k.data(), key_len, h.data(), header_len, p.data(), blocks)); break;
+    }
+    return ZL_OK;
+}
+static int circuit_encrypt(zl_curve_t curve, unsigned width, const uint64_t* initial_state, const uint64_t* key, size_t key_len, const uint64_t* header, size_t header_len,
+                           const uint64_t* plaintext, size_t blocks, bool witness_only, zl_circuit** out) {
+    if (!out || !key || key_len < 1 || (header_len && !header) || !plaintext || (curve != ZL_BLS12_381 && curve != ZL_BN254) ||
+        zl_poseidon_duplex_permutations(width, key_len, header_len, blocks) == 0)
+        return ZL_EINVAL;
+    zl_circuit* c = new (std::nothrow) zl_circuit();
+    if (!c) return ZL_ENOMEM;
+    c->curve = curve;
+    const int rc = curve == ZL_BLS12_381 ? circuit_encrypt_t<BLS12_381_Fr>(c, width, initial_state, key, key_len, header, header_len, plaintext, blocks, witness_only)
+                                         : circuit_encrypt_t<BN254_Fr>(c, width, initial_state, key, key_len, header, header_len, plaintext, blocks, witness_only);
+    if (rc) {
+        zl_circuit_free(c);
+        return rc;
+    }
+    *out = c;
+    return ZL_OK;
+}
 
 extern "C" {
 
+int zl_circuit_poseidon_encrypt(zl_curve_t curve, unsigned width, const uint64_t* initial_state, const uint64_t* key, size_t key_len, const uint64_t* header,
+                                size_t header_len, const uint64_t* plaintext, size_t blocks, zl_circuit** out) {
+    return circuit_encrypt(curve, width, initial_state, key, key_len, header, header_len, plaintext, blocks, false, out);
+}
+int zl_circuit_poseidon_encrypt_witness(zl_curve_t curve, unsigned width, const uint64_t* initial_state, const uint64_t* key, size_t key_len, const uint64_t* header,
+                                        size_t header_len, const uint64_t* plaintext, size_t blocks, zl_circuit** out) {
+    return circuit_encrypt(curve, width, initial_state, key, key_len, header, header_len, plaintext, blocks, true, out);
+}
 int zl_circuit_poseidon_chain(zl_curve_t curve, uint32_t k, const uint64_t* x0, const uint64_t* x1, zl_circuit** out) {
     if (!out || !x0 || !x1 || k == 0 || (curve != ZL_BLS12_381 && curve != ZL_BN254)) return ZL_EINVAL;
     zl_circuit* c = new (std::nothrow) zl_circuit();

@@ -26,6 +26,9 @@
 //                    row: permute_w with a recorder writes the S-box records of the hash; the leaf-membership kernel then hands the digest -- reduced weakly
 //                    (HandOver) -- to `depth` width-3 levels laid out as k_pos_merkle_trace's.  Sources: explicit preimages and paths, or a tree's node array beside
 //                    its leaves' preimages, where a preimage that does not hash to its leaf raises a second flag bit.
+//   k_pos_duplex     the duplex-sponge cipher (zl_poseidon_duplex_*), widths 3..6: one lane per message, its key, header and message blocks absorbed into the rate
+//                    between the SB + N dependent permutations of ONE launch (permute_any); encrypt and decrypt are one template with a wave-uniform mode.  The
+//                    absorbed lanes are outside the permutations' bound arguments and are reduced weakly at once (DuplexBounds).
 // Arithmetic: the lazily reduced 9 x 29-bit Fr of zl_field28r.h (the NTT's multiplier), 1.29 - 1.46 x the carry-chain Fp<FrP> here and ahead of the 10 x 28 form at
 // every size measured (profiles/poseidon_field_ab.log); the bound argument stands beside the type below.  The host path stays on Fp<FrP>.
 // A lane at or above the item count returns before it reads or writes anything.  An input element >= r sets the flag word (atomicOr) and the lane goes on with
@@ -823,6 +826,128 @@ __global__ __launch_bounds__(BLOCK) void k_pos_leaf_merkle_trace(const uint32_t*
     if (pub) dstore<FrP>(pub + p * 4, cur);
 }
 
+// ---------------------------------------------------------------------------------------------------------------- the duplex cipher (zl_poseidon_duplex_*)
+// One lane per message, the whole dependent chain of SB + N permutations in one launch (include/zl_backend_ext.h states the construction).  Between two
+// permutations the lane adds a block into the rate -- lanes 1 .. W - 1 -- or, decrypting, overwrites the rate with the ciphertext.  None of this is covered by
+// the permutations' bound arguments (above LazyP and above WideBounds), which know a state element entering a round as a row sum (< ROW r = 2 W r) or a loaded
+// element (< 2r) and never as their SUM.  In units of r:
+//   * an absorbed lane is a row sum -- or, in front of the first permutation, a loaded element of the initial state -- plus a loaded element: < (ROW + 2) r = SUM r
+//     (8, 10, 12, 14).  With a round key that would be (2 W + 4) r, squared 100 at width 3 against the 64 the width-3 unit is argued for and BLS12-381's
+//     MUL_BOUND of 70.  So the sum is reduced weakly AT ONCE, on both fields and at every width: wred takes a carried value below 128 r (add carries) and returns
+//     < 2r, and the lane enters the permutation as a loaded element does -- the bound holds by construction.  rate wred per permutation against 804 .. 2 616
+//     products.  A lane that absorbs nothing (lane 0; the rate lanes of a padding zero, which is skipped, not added) stays the row sum it was;
+//   * the stored ciphertext is that reduced sum: dstore's mul(x, 1) takes it at 2 * 1 and hands canon a product (< 2r);
+//   * decrypting, the plaintext is c - state with c loaded (< 2r) and state a row sum (message blocks follow SB >= 2 permutations), carried: subk with the
+//     biased limbs of 2^J r, 2^J >= ROW + 2 (J = 3 at width 3, 4 above), gives a value < (2 + 2^J) r = DIFF r (10, 18), which dstore takes at DIFF * 1;
+//   * the lane overwritten with a loaded ciphertext element is < 2r: a loaded element again;
+//   * the tag is lane 1 of the last permutation's output, a row sum: dstore takes it at ROW * 1, as k_pos_permute_w stores its outputs.
+// Every output goes through dstore's canon; the tag comparison is on canonical words.
+constexpr int ceil_log2(int v) { return v <= 1 ? 0 : 1 + ceil_log2((v + 1) / 2); }
+template <class FrP, int W>
+struct DuplexBounds {
+    using P = typename LazyP<FrP>::P;
+    static constexpr int ROW = WideBounds<FrP, W>::ROW;      // a lane after a permutation
+    static constexpr int LOADED = 2;                         // dload's product
+    static constexpr int SUM = ROW + LOADED;                 // what wred sees (the first block: LOADED + LOADED)
+    static constexpr int ABSORBED = 2;                       // ... and returns: the lane that enters the permutation
+    static constexpr int CIPHER_STORE_MUL = ABSORBED * 1;
+    static constexpr int SUB_J = ceil_log2(ROW + 2);         // the bias 2^J r of c - state
+    static constexpr int DIFF = LOADED + (1 << SUB_J);
+    static constexpr int PLAIN_STORE_MUL = DIFF * 1;
+    static constexpr int OVERWRITTEN = LOADED;
+    static constexpr int TAG_STORE_MUL = ROW * 1;
+    static constexpr int MAX_MUL = cmax(CIPHER_STORE_MUL, cmax(PLAIN_STORE_MUL, TAG_STORE_MUL));
+    static_assert(SUM <= 128 && DIFF <= 128, "wred and canon take a value below 128 r");
+    static_assert((1 << SUB_J) >= ROW + 2 && SUB_J <= P::KQ_MAX, "subk: the bias covers the subtrahend, and the table holds it");
+    static_assert(ABSORBED <= LOADED && OVERWRITTEN <= LOADED, "a rate lane enters the permutation within the bound of a loaded element");
+    static_assert(MAX_MUL <= P::MUL_BOUND, "a bound product above what mul takes");
+};
+#define ZL_POS_DUPLEX_BOUNDS(FrP, W, sum, j, diff) \
+    static_assert(DuplexBounds<FrP, W>::SUM == sum && DuplexBounds<FrP, W>::SUB_J == j && DuplexBounds<FrP, W>::DIFF == diff && DuplexBounds<FrP, W>::MAX_MUL == diff && \
+                  DuplexBounds<FrP, W>::MAX_MUL <= LazyP<FrP>::P::MUL_BOUND, "duplex bounds of " #FrP " at width " #W)
+ZL_POS_DUPLEX_BOUNDS(BLS12_381_Fr, 3, 8, 3, 10);   // unreduced: (8 + 2)^2 = 100 > 70
+ZL_POS_DUPLEX_BOUNDS(BLS12_381_Fr, 4, 10, 4, 18);
+ZL_POS_DUPLEX_BOUNDS(BLS12_381_Fr, 5, 12, 4, 18);
+ZL_POS_DUPLEX_BOUNDS(BLS12_381_Fr, 6, 14, 4, 18);
+ZL_POS_DUPLEX_BOUNDS(BN254_Fr, 3, 8, 3, 10);       // 100 <= 169 would pass the square, but not the 6 r the width-3 argument is written for
+ZL_POS_DUPLEX_BOUNDS(BN254_Fr, 4, 10, 4, 18);
+ZL_POS_DUPLEX_BOUNDS(BN254_Fr, 5, 12, 4, 18);
+ZL_POS_DUPLEX_BOUNDS(BN254_Fr, 6, 14, 4, 18);
+#undef ZL_POS_DUPLEX_BOUNDS
+// the initial state, canonical words, by value in the kernel's arguments: wave-uniform loads, nothing to stage
+struct DuplexInit {
+    uint64_t w[4 * pd::MAX_WIDTH];
+};
+// rate lanes I .. W - 2 of one block, one after the other (a compile-time recursion for the reason sbox_lanes gives: the state keeps static indices).  Lane i
+// takes element i of the block when i < avail: a setup block is added; a message block is added and stored (encrypt) or subtracted from, stored and
+// overwritten (decrypt).  src and dst may be the same address: element i is read before it is written.
+template <class FrP, int W, int I>
+__device__ __forceinline__ void duplex_lanes(El<FrP> (&s)[W], const uint64_t* src, uint64_t* dst, uint32_t avail, bool message, bool decrypt, bool& ok) {
+    if constexpr (I < W - 1) {
+        using P = typename LazyP<FrP>::P;
+        if ((uint32_t)I < avail) {
+            El<FrP> e;
+            ok &= dload<FrP>(src + 4 * I, e);
+            El<FrP> nx = zl::wred(zl::add(s[1 + I], e));
+            if (message) {
+                El<FrP> o = nx;
+                if (decrypt) {
+                    uint32_t K[P::L];
+#pragma unroll
+                    for (int k = 0; k < P::L; k++) K[k] = P::kq(DuplexBounds<FrP, W>::SUB_J, k);
+                    o = zl::subk(e, s[1 + I], K);
+                    nx = e;
+                }
+                dstore<FrP>(dst + 4 * I, o);
+            }
+            s[1 + I] = nx;
+        }
+        duplex_lanes<FrP, W, I + 1>(s, src, dst, avail, message, decrypt, ok);
+    }
+}
+// Message p: K key elements at keys + p K, H header elements, N blocks of W - 1 text elements at text_in + p N (W - 1), written to the same offset of text_out
+// (which may BE text_in).  Block t of the lane's SB + N is a key block (t < kb = K / rate + 1), a header block (t < sb) or a message block; all of it is
+// wave-uniform, as is `decrypt`.  Encrypting, tags[p] receives the tag; decrypting, tags[p] is read and ok_each[p] = 1 when it equals the computed one.
+template <class FrP, int W>
+__global__ __launch_bounds__(BLOCK) void k_pos_duplex(const uint32_t* __restrict__ tab, const DuplexInit init, const uint64_t* __restrict__ keys, uint32_t K,
+                                                      const uint64_t* __restrict__ headers, uint32_t H, const uint64_t* text_in, uint32_t N, size_t n, uint64_t* text_out,
+                                                      uint64_t* tags, uint8_t* __restrict__ ok_each, bool decrypt, uint32_t* __restrict__ flag) {
+    const size_t p = (size_t)blockIdx.x * BLOCK + threadIdx.x;
+    if (p >= n) return;
+    constexpr uint32_t RATE = W - 1;
+    El<FrP> s[W];
+#pragma unroll
+    for (int i = 0; i < W; i++) (void)dload<FrP>(init.w + 4 * i, s[i]);  // (checked on the host)
+    const uint32_t kb = K / RATE + 1, sb = kb + H / RATE + 1, total = sb + N;
+    const uint64_t* key = keys + p * K * 4;
+    const uint64_t* header = headers + p * H * 4;
+    const uint64_t* tin = text_in + p * N * RATE * 4;
+    uint64_t* tout = text_out + p * N * RATE * 4;
+    bool ok = true;
+    NoRec none;
+#pragma unroll 1
+    for (uint32_t t = 0; t < total; t++) {
+        const bool message = t >= sb;
+        const uint32_t b = message ? t - sb : t < kb ? t : t - kb;       // the block's number within its sequence
+        const uint32_t len = message ? N * RATE : t < kb ? K : H;         // ... and the sequence's length: b * RATE <= len
+        const uint64_t* src = (message ? tin : t < kb ? key : header) + (size_t)b * RATE * 4;
+        const uint32_t left = len - b * RATE;
+        duplex_lanes<FrP, W, 0>(s, src, tout + (size_t)b * RATE * 4, left < RATE ? left : RATE, message, decrypt, ok);
+        permute_any<FrP, W>(tab, s, none);
+    }
+    uint64_t tg[4];
+    dstore<FrP>(tg, s[1]);
+    uint64_t* tag = tags + p * 4;
+    if (decrypt) {
+        ok &= canon_words<FrP>(tag);
+        ok_each[p] = tg[0] == tag[0] && tg[1] == tag[1] && tg[2] == tag[2] && tg[3] == tag[3];
+    } else {
+#pragma unroll
+        for (int i = 0; i < 4; i++) tag[i] = tg[i];
+    }
+    if (!ok) atomicOr(flag, 1u);
+}
+
 // ---------------------------------------------------------------------------------------------------------------- host path
 template <class FrP, int W = 3>
 const poseidon::Constants<FrP, W>& consts() {
@@ -1090,6 +1215,37 @@ int host_leaf_assignments(const uint64_t* preimages, const uint64_t* indices, co
         row[0] = 1;
         row[1] = row[2] = row[3] = 0;
         store_canon<FrP>(row + 4, cur);
+        return ok;
+    }) ? ZL_OK : ZL_EINVAL;
+}
+// the duplex cipher over the host pool: the host mirror's duplex_encrypt / duplex_decrypt per message.  init: W canonical elements (checked by the caller).
+// tags is written (encrypt) or read (decrypt, with ok_each written); text_out may be text_in -- a message is read whole before it is written.
+template <class FrP, int W>
+int host_duplex(const uint64_t* init, const uint64_t* keys, size_t K, const uint64_t* headers, size_t H, const uint64_t* text_in, size_t N, size_t count,
+                uint64_t* text_out, uint64_t* tags, uint8_t* ok_each, bool decrypt) {
+    consts<FrP, W>();
+    const size_t T = N * (W - 1);
+    Fp<FrP> st0[W];
+    for (int e = 0; e < W; e++) (void)load_canon<FrP>(init + 4 * e, st0[e]);
+    return host_for(count, [&](size_t i) {
+        std::vector<Fp<FrP>> v(K + H + T);
+        Fp<FrP>* key = v.data();
+        Fp<FrP>* header = key + K;
+        Fp<FrP>* text = header + H;
+        bool ok = true;
+        for (size_t e = 0; e < K; e++) ok &= load_canon<FrP>(keys + (i * K + e) * 4, key[e]);
+        for (size_t e = 0; e < H; e++) ok &= load_canon<FrP>(headers + (i * H + e) * 4, header[e]);
+        for (size_t e = 0; e < T; e++) ok &= load_canon<FrP>(text_in + (i * T + e) * 4, text[e]);
+        Fp<FrP> st[W];
+        for (int e = 0; e < W; e++) st[e] = st0[e];
+        if (decrypt) {
+            Fp<FrP> given;
+            ok &= load_canon<FrP>(tags + i * 4, given);
+            ok_each[i] = poseidon::duplex_decrypt<FrP, W>(consts<FrP, W>(), st, key, K, header, H, text, N) == given;
+        } else {
+            store_canon<FrP>(tags + i * 4, poseidon::duplex_encrypt<FrP, W>(consts<FrP, W>(), st, key, K, header, H, text, N));
+        }
+        for (size_t e = 0; e < T; e++) store_canon<FrP>(text_out + (i * T + e) * 4, text[e]);
         return ok;
     }) ? ZL_OK : ZL_EINVAL;
 }
@@ -1797,6 +1953,83 @@ int dev_merkle_from_forest(zl_ctx* ctx, const zl_merkle_forest* f, const uint32_
     const ForestSrc src{f->nodes, f->stride, nullptr, level_table(f->capacity, f->depth)};
     return merkle_trace_run<FrP, ForestSrc>(ctx, src, nullptr, indices, f->depth, count, static_cast<uint64_t*>(d_rows), stride, host_rows, host_pub, tree_of);
 }
+// ---- the duplex cipher.  What a call is, beside its operands; init: W canonical elements, checked
+struct DuplexCall {
+    const uint64_t* init;
+    size_t K, H, N;
+    bool decrypt;
+};
+template <class FrP, int W>
+int launch_duplex(zl_ctx* ctx, const uint32_t* tab, const DuplexCall& c, const uint64_t* d_keys, const uint64_t* d_headers, const uint64_t* d_in, size_t m, uint64_t* d_out,
+                  uint64_t* d_tags, uint8_t* d_ok, uint32_t* flag) {
+    DuplexInit init{};
+    memcpy(init.w, c.init, 32 * W);
+    ZL_POS_LAUNCH(ctx, (k_pos_duplex<FrP, W>), blocks_of(m), BLOCK, 0, tab, init, d_keys, (uint32_t)c.K, d_headers, (uint32_t)c.H, d_in, (uint32_t)c.N, m, d_out, d_tags, d_ok,
+                  c.decrypt, flag);
+    return ZL_OK;
+}
+// device operands, launches of at most one chunk; the verdicts of a decryption go through the staging area to ok_each (host memory)
+template <class FrP, int W>
+int dev_duplex_dev(zl_ctx* ctx, const DuplexCall& c, const void* d_keys, const void* d_headers, const void* d_in, size_t count, void* d_out, void* d_tags, uint8_t* ok_each) {
+    const uint32_t* tab;
+    int rc = get_table<FrP, W>(ctx, &tab);
+    if (rc) return rc;
+    const size_t chunk = tune_chunk(), T = c.N * (W - 1);
+    Stage s;
+    if ((rc = stage_get(ctx, c.decrypt ? (count < chunk ? count : chunk) : 0, &s))) return rc;
+    for (size_t first = 0; first < count; first += chunk) {
+        const size_t m = count - first < chunk ? count - first : chunk;
+        if ((rc = launch_duplex<FrP, W>(ctx, tab, c, static_cast<const uint64_t*>(d_keys) + first * c.K * 4, static_cast<const uint64_t*>(d_headers) + first * c.H * 4,
+                                        static_cast<const uint64_t*>(d_in) + first * T * 4, m, static_cast<uint64_t*>(d_out) + first * T * 4,
+                                        static_cast<uint64_t*>(d_tags) + first * 4, s.data, s.flag)))
+            return rc;
+        if (c.decrypt) ZL_HIP(ctx, hipMemcpyAsync(ok_each + first, s.data, m, hipMemcpyDeviceToHost, ctx->stream));
+    }
+    return finish(ctx, s.flag);
+}
+// host operands: keys, headers, texts (in place in the staging area), tags and verdicts of a chunk side by side
+template <class FrP, int W>
+int dev_duplex(zl_ctx* ctx, const DuplexCall& c, const uint64_t* keys, const uint64_t* headers, const uint64_t* text_in, size_t count, uint64_t* text_out, uint64_t* tags,
+               uint8_t* ok_each) {
+    const uint32_t* tab;
+    int rc = get_table<FrP, W>(ctx, &tab);
+    if (rc) return rc;
+    const size_t T = c.N * (W - 1), per = (c.K + c.H + T + 1) * 32 + 1;
+    const size_t chunk = stage_items(per), m0 = count < chunk ? count : chunk;
+    const size_t o_hdr = up256(m0 * c.K * 32), o_text = o_hdr + up256(m0 * c.H * 32), o_tag = o_text + up256(m0 * T * 32), o_ok = o_tag + up256(m0 * 32);
+    Stage s;
+    if ((rc = stage_get(ctx, o_ok + m0, &s))) return rc;
+    uint64_t* d_key = reinterpret_cast<uint64_t*>(s.data);
+    uint64_t* d_hdr = reinterpret_cast<uint64_t*>(s.data + o_hdr);
+    uint64_t* d_text = reinterpret_cast<uint64_t*>(s.data + o_text);
+    uint64_t* d_tag = reinterpret_cast<uint64_t*>(s.data + o_tag);
+    uint8_t* d_ok = s.data + o_ok;
+    for (size_t first = 0; first < count; first += chunk) {
+        const size_t m = count - first < chunk ? count - first : chunk;
+        if (c.K) ZL_HIP(ctx, hipMemcpyAsync(d_key, keys + first * c.K * 4, m * c.K * 32, hipMemcpyHostToDevice, ctx->stream));
+        if (c.H) ZL_HIP(ctx, hipMemcpyAsync(d_hdr, headers + first * c.H * 4, m * c.H * 32, hipMemcpyHostToDevice, ctx->stream));
+        ZL_HIP(ctx, hipMemcpyAsync(d_text, text_in + first * T * 4, m * T * 32, hipMemcpyHostToDevice, ctx->stream));
+        if (c.decrypt) ZL_HIP(ctx, hipMemcpyAsync(d_tag, tags + first * 4, m * 32, hipMemcpyHostToDevice, ctx->stream));
+        if ((rc = launch_duplex<FrP, W>(ctx, tab, c, d_key, d_hdr, d_text, m, d_text, d_tag, d_ok, s.flag))) return rc;
+        ZL_HIP(ctx, hipMemcpyAsync(text_out + first * T * 4, d_text, m * T * 32, hipMemcpyDeviceToHost, ctx->stream));
+        if (c.decrypt) ZL_HIP(ctx, hipMemcpyAsync(ok_each + first, d_ok, m, hipMemcpyDeviceToHost, ctx->stream));
+        else ZL_HIP(ctx, hipMemcpyAsync(tags + first * 4, d_tag, m * 32, hipMemcpyDeviceToHost, ctx->stream));
+    }
+    return finish(ctx, s.flag);
+}
+// the parameters of a call: ZL_EINVAL, or ZL_OK with the initial state's words (zero for a null pointer) in init_out
+template <class FrP>
+bool duplex_init_ok(const uint64_t* w, unsigned width) {
+    for (unsigned i = 0; i < width; i++)
+        if (!canon_words<FrP>(w + 4 * i)) return false;
+    return true;
+}
+int duplex_params(zl_curve_t curve, unsigned width, const uint64_t* initial_state, size_t key_len, size_t header_len, size_t blocks, uint64_t* init_out) {
+    if (!valid_curve(curve) || zl_poseidon_duplex_permutations(width, key_len, header_len, blocks) == 0) return ZL_EINVAL;
+    memset(init_out, 0, 32 * pd::MAX_WIDTH);
+    if (initial_state) memcpy(init_out, initial_state, 32 * width);
+    return (curve == ZL_BLS12_381 ? duplex_init_ok<BLS12_381_Fr>(init_out, width) : duplex_init_ok<BN254_Fr>(init_out, width)) ? ZL_OK : ZL_EINVAL;
+}
 }  // namespace
 
 #define ZL_POS_CURVE(curve, fn, ...) ((curve) == ZL_BLS12_381 ? fn<BLS12_381_Fr>(__VA_ARGS__) : fn<BN254_Fr>(__VA_ARGS__))
@@ -1900,6 +2133,56 @@ int zl_poseidon_hash_batch_dev(zl_ctx* ctx, zl_curve_t curve, unsigned arity, co
     if (count == 0) return ZL_OK;
     ZL_HIP(ctx, hipSetDevice(ctx->device));
     return ZL_POS_WIDE(curve, arity + 1, dev_hash_w_dev, ctx, d_in, count, d_out);
+}
+// ---- the duplex cipher: one validation (duplex_params), then the host mirror, the staged device path or the device-pointer path
+size_t zl_poseidon_duplex_permutations(unsigned width, size_t key_len, size_t header_len, size_t blocks) {
+    if (!pd::width_ok(width) || key_len > 64 || header_len > 64 || blocks < 1 || blocks > 1024) return 0;
+    return poseidon::duplex_setup_blocks(width, key_len, header_len) + blocks;
+}
+static int duplex_batch(zl_ctx* ctx, zl_curve_t curve, unsigned width, const uint64_t* initial_state, const uint64_t* keys, size_t key_len, const uint64_t* headers,
+                        size_t header_len, const uint64_t* text_in, size_t blocks, size_t count, uint64_t* text_out, uint64_t* tags, uint8_t* ok_each, bool decrypt) {
+    uint64_t init[4 * pd::MAX_WIDTH];
+    const int rc = duplex_params(curve, width, initial_state, key_len, header_len, blocks, init);
+    if (rc) return rc;
+    if (count && ((key_len && !keys) || (header_len && !headers) || !text_in || !text_out || !tags || (decrypt && !ok_each))) return ZL_EINVAL;
+    if (count == 0) return ZL_OK;
+    if (on_host(ctx, count)) return ZL_POS_ANYW(curve, width, host_duplex, init, keys, key_len, headers, header_len, text_in, blocks, count, text_out, tags, ok_each, decrypt);
+    ZL_HIP(ctx, hipSetDevice(ctx->device));
+    const DuplexCall c{init, key_len, header_len, blocks, decrypt};
+    return ZL_POS_ANYW(curve, width, dev_duplex, ctx, c, keys, headers, text_in, count, text_out, tags, ok_each);
+}
+static int duplex_batch_dev(zl_ctx* ctx, zl_curve_t curve, unsigned width, const uint64_t* initial_state, const void* d_keys, size_t key_len, const void* d_headers,
+                            size_t header_len, const void* d_in, size_t blocks, size_t count, void* d_out, void* d_tags, uint8_t* ok_each, bool decrypt) {
+    uint64_t init[4 * pd::MAX_WIDTH];
+    const int rc = ctx ? duplex_params(curve, width, initial_state, key_len, header_len, blocks, init) : ZL_EINVAL;
+    if (rc) return rc;
+    if (count && ((key_len && !d_keys) || (header_len && !d_headers) || !d_in || !d_out || !d_tags || (decrypt && !ok_each))) return ZL_EINVAL;
+    if (count == 0) return ZL_OK;
+    ZL_HIP(ctx, hipSetDevice(ctx->device));
+    const DuplexCall c{init, key_len, header_len, blocks, decrypt};
+    return ZL_POS_ANYW(curve, width, dev_duplex_dev, ctx, c, d_keys, d_headers, d_in, count, d_out, d_tags, ok_each);
+}
+int zl_poseidon_duplex_encrypt_batch(zl_ctx* ctx, zl_curve_t curve, unsigned width, const uint64_t* initial_state, const uint64_t* keys, size_t key_len,
+                                     const uint64_t* headers, size_t header_len, const uint64_t* plaintexts, size_t blocks, size_t count, uint64_t* ciphertexts,
+                                     uint64_t* tags) {
+    return duplex_batch(ctx, curve, width, initial_state, keys, key_len, headers, header_len, plaintexts, blocks, count, ciphertexts, tags, nullptr, false);
+}
+int zl_poseidon_duplex_decrypt_batch(zl_ctx* ctx, zl_curve_t curve, unsigned width, const uint64_t* initial_state, const uint64_t* keys, size_t key_len,
+                                     const uint64_t* headers, size_t header_len, const uint64_t* ciphertexts, const uint64_t* tags, size_t blocks, size_t count,
+                                     uint64_t* plaintexts, uint8_t* ok_each) {
+    return duplex_batch(ctx, curve, width, initial_state, keys, key_len, headers, header_len, ciphertexts, blocks, count, plaintexts, const_cast<uint64_t*>(tags), ok_each,
+                        true);  // (tags is only read when decrypting)
+}
+int zl_poseidon_duplex_encrypt_batch_dev(zl_ctx* ctx, zl_curve_t curve, unsigned width, const uint64_t* initial_state, const void* d_keys, size_t key_len,
+                                         const void* d_headers, size_t header_len, const void* d_plaintexts, size_t blocks, size_t count, void* d_ciphertexts,
+                                         void* d_tags) {
+    return duplex_batch_dev(ctx, curve, width, initial_state, d_keys, key_len, d_headers, header_len, d_plaintexts, blocks, count, d_ciphertexts, d_tags, nullptr, false);
+}
+int zl_poseidon_duplex_decrypt_batch_dev(zl_ctx* ctx, zl_curve_t curve, unsigned width, const uint64_t* initial_state, const void* d_keys, size_t key_len,
+                                         const void* d_headers, size_t header_len, const void* d_ciphertexts, const void* d_tags, size_t blocks, size_t count,
+                                         void* d_plaintexts, uint8_t* ok_each) {
+    return duplex_batch_dev(ctx, curve, width, initial_state, d_keys, key_len, d_headers, header_len, d_ciphertexts, blocks, count, d_plaintexts, const_cast<void*>(d_tags),
+                            ok_each, true);
 }
 int zl_poseidon_chain_batch(zl_ctx* ctx, zl_curve_t curve, const uint64_t* x0, const uint64_t* x1, uint32_t k, size_t count, uint64_t* out) {
     if (!valid_curve(curve) || k == 0 || (count && (!x0 || !x1 || !out))) return ZL_EINVAL;
