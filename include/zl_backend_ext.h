@@ -271,6 +271,38 @@ int zl_circuit_poseidon_encrypt(zl_curve_t curve, unsigned width, const uint64_t
                                 size_t header_len, const uint64_t* plaintext, size_t blocks, zl_circuit** out);
 int zl_circuit_poseidon_encrypt_witness(zl_curve_t curve, unsigned width, const uint64_t* initial_state, const uint64_t* key, size_t key_len, const uint64_t* header,
                                         size_t header_len, const uint64_t* plaintext, size_t blocks, zl_circuit** out);
+/* The complete ASSIGNMENTS of the encryption circuit, one device lane per row (k_pos_duplex_trace: the cipher's SB + blocks dependent permutations of one launch
+ * under a recorder), word for word what both compilers export, rate = W - 1:
+ *   [0] = 1   [1] = tag   [2 .. 2 + blocks rate) ciphertext   [.. + header_len) header   [.. + key_len) key   [.. + blocks rate) plaintext   then the 3 S records
+ * zl_poseidon_encrypt_assignment_elems = n_instance + n_witness = 2 + 2 blocks rate + header_len + key_len + 3 S; 0 for a parameter out of range (width outside
+ * 3..6, key_len 0 or above 64, header_len above 64, blocks outside 1..1024) or a count that does not fit 31 bits.  Dense layouts as the cipher's.  The host-pointer
+ * form writes count dense rows under the common rules of the batched Poseidon entry points (ctx == NULL or a count below ZL_TUNE_POSEIDON_DEV_MIN: the host
+ * mirror over the host pool, byte-identical; staged in chunks of ZL_TUNE_POSEIDON_CHUNK under the 256 MiB budget; finished on return; an element >= r is ZL_EINVAL
+ * through the flag word; every row within the limits fits the budget with its inputs, so the chains' refusal of an over-long row has no case here).  The _dev
+ * form takes DEVICE pointers and never the host path (ctx == NULL is ZL_EINVAL): row i starts at d_out + i * stride_elems elements, stride_elems >= the row length,
+ * elements behind the row are not written, d_out must be 16-byte aligned and must not overlap the inputs.  initial_state is HOST memory in every form, NULL =
+ * zero, checked on the host before any work.  ZL_EINVAL: the cipher's errors plus the circuit's -- a parameter out of range as above, a null required pointer
+ * (headers may be NULL when header_len is 0), an unknown curve.
+ * zl_groth16_prove_poseidon_encryptions: from HOST keys, headers and plaintexts to proofs -- proofs[j] is byte for byte what zl_groth16_prove_resident returns for
+ * row j with (r[j], s[j]); tags_out (count x 4 u64) and ciphertexts_out (count x blocks rate x 4 u64), either may be NULL, receive what
+ * zl_poseidon_duplex_encrypt_batch computes: the cipher runs ONCE.  On the device path the kernel writes each chunk's rows into the chunk's block; off it the rows
+ * come through host staging of at most 64 MiB at a time.  The resident circuit must have the SHAPE (2 + N rate + H, K + N rate + 3 S, 3 S + 1 + N rate) of the
+ * stated parameters, else ZL_EINVAL; error order and dispatch bounds are zl_groth16_prove_batch's and are not moved ((K, H, N) = (2, 0, 1) has a domain of 2^10 at
+ * every width).  Device-resident inputs: _assignments_dev, then zl_groth16_prove_batch_dev.
+ * SHAPES.  n_instance >= 4 tells this family from every other (2).  Within it the shape fixes K, N rate, H and S: n_witness - (n_constraints - 1) = K, then
+ * n_witness = K + N rate + 3 S and n_constraints = 3 S + 1 + N rate give N rate and S, and n_instance = 2 + N rate + H gives H.  At ONE width two tuples of one
+ * shape are therefore the same tuple.  Across widths they need N (W - 1) = N' (W' - 1) and S(W, K, H, N) = S(W', K, H, N'); an exhaustive walk over the limits
+ * (tests/test_poseidon_encrypt_assignments_cpu.py repeats it) finds exactly ONE such pair: (W, K, H, N) = (5, 15, 15, 5) and (6, 15, 15, 4), both with 20 text
+ * elements and S = 1 247.  Those two are different circuits of one shape: the call cannot refuse the keys of one for the parameters of the other, and the proofs
+ * do not verify -- as for keys compiled from ANY other circuit of the same shape, in every family.  Every other tuple's keys are refused. */
+size_t zl_poseidon_encrypt_assignment_elems(unsigned width, size_t key_len, size_t header_len, size_t blocks);
+int zl_poseidon_encrypt_assignments(zl_ctx* ctx, zl_curve_t curve, unsigned width, const uint64_t* initial_state, const uint64_t* keys, size_t key_len,
+                                    const uint64_t* headers, size_t header_len, const uint64_t* plaintexts, size_t blocks, size_t count, uint64_t* out);
+int zl_poseidon_encrypt_assignments_dev(zl_ctx* ctx, zl_curve_t curve, unsigned width, const uint64_t* initial_state, const void* d_keys, size_t key_len,
+                                        const void* d_headers, size_t header_len, const void* d_plaintexts, size_t blocks, size_t count, void* d_out, size_t stride_elems);
+int zl_groth16_prove_poseidon_encryptions(zl_ctx* ctx, const zl_g16_pk* pk, uint64_t r1cs_handle, unsigned width, const uint64_t* initial_state, const uint64_t* keys,
+                                          size_t key_len, const uint64_t* headers, size_t header_len, const uint64_t* plaintexts, size_t blocks, const uint64_t* r,
+                                          const uint64_t* s, size_t count, zl_g16_proof* proofs, uint64_t* tags_out, uint64_t* ciphertexts_out);
 /* out[i] = h_k with h_1 = H(x0[i], x1[i]), h_{j+1} = H(h_j, x1[i]): the public input of zl_circuit_poseidon_chain(curve, k, x0[i], x1[i]); the k dependent
  * hashes of a chain run inside one kernel.  k == 0: ZL_EINVAL, as zl_circuit_poseidon_chain. */
 int zl_poseidon_chain_batch(zl_ctx* ctx, zl_curve_t curve, const uint64_t* x0, const uint64_t* x1, uint32_t k, size_t count, uint64_t* out);

@@ -13,3 +13,4 @@ from .backend import (poseidon_permute_batch_host, poseidon_hash2_host, poseidon
 from .backend import (poseidon_hash_assignment_elems, poseidon_hash_assignments_host, poseidon_merkle_leaf_assignment_elems,  # noqa: F401
                       poseidon_merkle_leaf_assignments_host)
 from .backend import poseidon_duplex_permutations, poseidon_duplex_encrypt_host, poseidon_duplex_decrypt_host  # noqa: F401
+from .backend import poseidon_encrypt_assignment_elems, poseidon_encrypt_assignments_host  # noqa: F401

@@ -52,6 +52,7 @@ ABI_SYMBOLS = [
     "zl_groth16_prove_poseidon_hashes", "zl_groth16_prove_merkle_leaf_paths", "zl_groth16_prove_merkle_leaf_members",
     "zl_poseidon_duplex_permutations", "zl_poseidon_duplex_encrypt_batch", "zl_poseidon_duplex_decrypt_batch", "zl_poseidon_duplex_encrypt_batch_dev",
     "zl_poseidon_duplex_decrypt_batch_dev", "zl_circuit_poseidon_encrypt", "zl_circuit_poseidon_encrypt_witness",
+    "zl_poseidon_encrypt_assignment_elems", "zl_poseidon_encrypt_assignments", "zl_poseidon_encrypt_assignments_dev", "zl_groth16_prove_poseidon_encryptions",
 ]
 
 
@@ -162,6 +163,12 @@ def load_library(path: Optional[str] = None):
     L.zl_poseidon_duplex_decrypt_batch_dev.argtypes = [vp, C.c_int, C.c_uint, u64p, vp, C.c_size_t, vp, C.c_size_t, vp, vp, C.c_size_t, C.c_size_t, vp, u8p]
     L.zl_circuit_poseidon_encrypt.argtypes = [C.c_int, C.c_uint, u64p, u64p, C.c_size_t, u64p, C.c_size_t, u64p, C.c_size_t, C.POINTER(vp)]
     L.zl_circuit_poseidon_encrypt_witness.argtypes = L.zl_circuit_poseidon_encrypt.argtypes
+    L.zl_poseidon_encrypt_assignment_elems.argtypes = [C.c_uint, C.c_size_t, C.c_size_t, C.c_size_t]
+    L.zl_poseidon_encrypt_assignment_elems.restype = C.c_size_t
+    L.zl_poseidon_encrypt_assignments.argtypes = [vp, C.c_int, C.c_uint, u64p, u64p, C.c_size_t, u64p, C.c_size_t, u64p, C.c_size_t, C.c_size_t, u64p]
+    L.zl_poseidon_encrypt_assignments_dev.argtypes = [vp, C.c_int, C.c_uint, u64p, vp, C.c_size_t, vp, C.c_size_t, vp, C.c_size_t, C.c_size_t, vp, C.c_size_t]
+    L.zl_groth16_prove_poseidon_encryptions.argtypes = [vp, C.POINTER(G16PkC), C.c_uint64, C.c_uint, u64p, u64p, C.c_size_t, u64p, C.c_size_t, u64p, C.c_size_t, u64p, u64p,
+                                                        C.c_size_t, C.POINTER(G16ProofC), u64p, u64p]
     L.zl_poseidon_chain_batch.argtypes = [vp, C.c_int, u64p, u64p, C.c_uint32, C.c_size_t, u64p]
     L.zl_poseidon_chain_assignment_elems.argtypes = [C.c_uint32]
     L.zl_poseidon_chain_assignment_elems.restype = C.c_size_t
@@ -678,6 +685,21 @@ class Backend:
         self._check(self.L.zl_poseidon_merkle_member_assignments_dev(self._ctx, curve, C.c_void_p(d_nodes), n, depth, _ptr_or_none(idx), idx.size, C.c_void_p(d_out),
                                                                      stride), "zl_poseidon_merkle_member_assignments_dev")
 
+    def poseidon_encrypt_assignments(self, curve: int, initial_state, keys, headers, plaintexts) -> np.ndarray:
+        """zl_poseidon_encrypt_assignments: operands as poseidon_duplex_encrypt (keys (count, K, 4) with K >= 1) -> (count, poseidon_encrypt_assignment_elems(W, K,
+        H, N), 4) canonical words, row i the complete assignment of Circuit.poseidon_encrypt(curve, initial_state, keys[i], headers[i], plaintexts[i])"""
+        return _poseidon_encrypt_assignments(self.L, self._ctx, curve, initial_state, keys, headers, plaintexts)
+
+    def poseidon_encrypt_assignments_dev(self, curve: int, width: int, initial_state, d_keys: int, key_len: int, d_headers: int, header_len: int, d_plaintexts: int,
+                                         blocks: int, count: int, d_out: int, stride_elems: Optional[int] = None):
+        """zl_poseidon_encrypt_assignments_dev on device addresses -> row i at d_out + i * stride_elems elements (default: the row length); initial_state stays
+        host memory; finished on return"""
+        st = _duplex_state(initial_state, width)
+        stride = self.L.zl_poseidon_encrypt_assignment_elems(width, key_len, header_len, blocks) if stride_elems is None else stride_elems
+        self._check(self.L.zl_poseidon_encrypt_assignments_dev(self._ctx, curve, width, None if st is None else _p64(st), C.c_void_p(d_keys), key_len,
+                                                               C.c_void_p(d_headers), header_len, C.c_void_p(d_plaintexts), blocks, count, C.c_void_p(d_out), stride),
+                    "zl_poseidon_encrypt_assignments_dev")
+
     def poseidon_hash_assignments(self, curve: int, inputs) -> np.ndarray:
         """zl_poseidon_hash_assignments: inputs (count, arity, 4) -> (count, 2 + arity + 3 S(arity), 4) canonical words, row i the complete assignment of
         Circuit.poseidon_hash(curve, inputs[i])"""
@@ -834,6 +856,24 @@ class Backend:
         self._check(self.L.zl_groth16_prove_poseidon_hashes(self._ctx, C.byref(pkc), r1cs_handle, arity, _ptr_or_none(v), _ptr_or_none(r), _ptr_or_none(s), count, out,
                                                             _ptr_or_none(pub)), "zl_groth16_prove_poseidon_hashes")
         return [_proof_tuple(curve, p) for p in out[:count]], pub
+
+    def _prove_encryptions(self, pkc, curve: int, r1cs_handle: int, initial_state, keys, headers, plaintexts, r: np.ndarray, s: np.ndarray):
+        k, h, t = _duplex_operands(keys, headers, plaintexts)
+        count, blocks, width = t.shape[0], t.shape[1], t.shape[2] + 1
+        st = _duplex_state(initial_state, width)
+        r, s = np.ascontiguousarray(r, dtype=np.uint64).reshape(count, 4), np.ascontiguousarray(s, dtype=np.uint64).reshape(count, 4)
+        out = (G16ProofC * max(1, count))()
+        tags, cts = np.zeros((count, 4), dtype=np.uint64), np.zeros_like(t)
+        self._check(self.L.zl_groth16_prove_poseidon_encryptions(self._ctx, C.byref(pkc), r1cs_handle, width, None if st is None else _p64(st), _ptr_or_none(k), k.shape[1],
+                                                                 _ptr_or_none(h), h.shape[1], _ptr_or_none(t), blocks, _ptr_or_none(r), _ptr_or_none(s), count, out,
+                                                                 _ptr_or_none(tags), _ptr_or_none(cts)), "zl_groth16_prove_poseidon_encryptions")
+        return [_proof_tuple(curve, p) for p in out[:count]], tags, cts
+
+    def groth16_prove_poseidon_encryptions(self, curve: int, pk: dict, r1cs_handle: int, initial_state, keys, headers, plaintexts, r: np.ndarray, s: np.ndarray):
+        """zl_groth16_prove_poseidon_encryptions: operands as poseidon_duplex_encrypt and blinding scalars -> (`count` proofs, tags (count, 4), ciphertexts (count,
+        N, W - 1, 4)): the public inputs of proof j are tags[j], ciphertexts[j] and headers[j]"""
+        pkc, keep_pk = _pk_struct(curve, pk)
+        return self._prove_encryptions(pkc, curve, r1cs_handle, initial_state, keys, headers, plaintexts, r, s)
 
     def groth16_prove_poseidon_hashes(self, curve: int, pk: dict, r1cs_handle: int, arity: int, inputs, r: np.ndarray, s: np.ndarray):
         """zl_groth16_prove_poseidon_hashes: inputs (count, arity, 4) and blinding scalars -> (`count` proofs, the digests (count, 4): each proof's public input)"""
@@ -1486,13 +1526,18 @@ def _duplex_state(initial_state, width: int):
     return st
 
 
-def _poseidon_duplex(L, ctx, curve: int, initial_state, keys, headers, texts, tags):
-    """tags None: encrypt -> (ciphertexts, tags); otherwise decrypt -> (plaintexts, ok)"""
+def _duplex_operands(keys, headers, texts):
     t = np.ascontiguousarray(np.asarray(texts, dtype=np.uint64))
     k = np.ascontiguousarray(np.asarray(keys, dtype=np.uint64))
     h = np.ascontiguousarray(np.asarray(headers, dtype=np.uint64))
     if t.ndim != 4 or t.shape[3] != 4 or k.ndim != 3 or h.ndim != 3 or k.shape[2] != 4 or h.shape[2] != 4 or not k.shape[0] == h.shape[0] == t.shape[0]:
         raise ValueError("texts are (count, N, W - 1, 4), keys (count, K, 4), headers (count, H, 4) uint64 words")
+    return k, h, t
+
+
+def _poseidon_duplex(L, ctx, curve: int, initial_state, keys, headers, texts, tags):
+    """tags None: encrypt -> (ciphertexts, tags); otherwise decrypt -> (plaintexts, ok)"""
+    k, h, t = _duplex_operands(keys, headers, texts)
     count, blocks, width = t.shape[0], t.shape[1], t.shape[2] + 1
     st = _duplex_state(initial_state, width)
     stp = None if st is None else _p64(st)
@@ -1508,6 +1553,27 @@ def _poseidon_duplex(L, ctx, curve: int, initial_state, keys, headers, texts, ta
                                                      blocks, count, _ptr_or_none(out), ok.ctypes.data_as(C.POINTER(C.c_uint8)) if count else None),
                "zl_poseidon_duplex_decrypt_batch")
     return out, ok.astype(bool)
+
+
+def _poseidon_encrypt_assignments(L, ctx, curve: int, initial_state, keys, headers, plaintexts) -> np.ndarray:
+    k, h, t = _duplex_operands(keys, headers, plaintexts)
+    count, blocks, width = t.shape[0], t.shape[1], t.shape[2] + 1
+    st = _duplex_state(initial_state, width)
+    out = np.zeros((count, L.zl_poseidon_encrypt_assignment_elems(width, k.shape[1], h.shape[1], blocks), 4), dtype=np.uint64)
+    _pos_check(L, L.zl_poseidon_encrypt_assignments(ctx, curve, width, None if st is None else _p64(st), _ptr_or_none(k), k.shape[1], _ptr_or_none(h), h.shape[1],
+                                                    _ptr_or_none(t), blocks, count, _ptr_or_none(out)), "zl_poseidon_encrypt_assignments")
+    return out
+
+
+def poseidon_encrypt_assignment_elems(width: int, key_len: int, header_len: int, blocks: int) -> int:
+    """elements of one encryption's assignment: 2 + 2 N (W - 1) + H + K + 3 S (0 for a parameter out of range)"""
+    if min(width, key_len, header_len, blocks) < 0:
+        return 0
+    return int(load_library().zl_poseidon_encrypt_assignment_elems(width, key_len, header_len, blocks))
+
+
+def poseidon_encrypt_assignments_host(curve: int, initial_state, keys, headers, plaintexts) -> np.ndarray:
+    return _poseidon_encrypt_assignments(load_library(), None, curve, initial_state, keys, headers, plaintexts)
 
 
 def poseidon_duplex_permutations(width: int, key_len: int, header_len: int, blocks: int) -> int:
@@ -2195,6 +2261,13 @@ class Groth16Keys:
             raise ValueError("prove_hashes: the keys' circuit is not a Poseidon hash circuit")
         self._upload_r1cs()
         return (lane or self.backend)._prove_hashes(self.pk, self.circuit.curve, self._r1cs, a, inputs, r, s)
+
+    def prove_encryptions(self, initial_state, keys, headers, plaintexts, r: np.ndarray, s: np.ndarray, lane: Optional[Backend] = None):
+        """zl_groth16_prove_poseidon_encryptions over this key: operands as Backend.poseidon_duplex_encrypt and blinding scalars r, s (count, 4) -> (proofs, tags
+        (count, 4), ciphertexts (count, N, W - 1, 4)); proof j is prove_batch's for the assignment of Circuit.poseidon_encrypt(curve, initial_state, keys[j],
+        headers[j], plaintexts[j]).  Keys of a circuit that has not the shape of the operands' (W, K, H, N) are refused by the library (ZL_EINVAL)."""
+        self._upload_r1cs()
+        return (lane or self.backend)._prove_encryptions(self.pk, self.circuit.curve, self._r1cs, initial_state, keys, headers, plaintexts, r, s)
 
     def _leaf_ready(self, what: str):
         shape = self.merkle_leaf_shape()

@@ -1416,6 +1416,41 @@ extern "C" int zl_groth16_prove_merkle_leaf_members(zl_ctx* ctx, const zl_g16_pk
     }
     return rc;
 }
+// Encryptions from key, header and plaintext: the trace kernel writes each chunk's rows into the chunk's block; tag and ciphertext of every proof come out beside them
+extern "C" int zl_groth16_prove_poseidon_encryptions(zl_ctx* ctx, const zl_g16_pk* pk, uint64_t r1cs_handle, unsigned width, const uint64_t* initial_state,
+                                                     const uint64_t* keys, size_t key_len, const uint64_t* headers, size_t header_len, const uint64_t* plaintexts, size_t blocks,
+                                                     const uint64_t* r, const uint64_t* s, size_t count, zl_g16_proof* proofs, uint64_t* tags_out, uint64_t* ciphertexts_out) {
+    const size_t nv = zl_poseidon_encrypt_assignment_elems(width, key_len, header_len, blocks);
+    if (!ctx || !pk || nv == 0 || (count && (!keys || (header_len && !headers) || !plaintexts || !r || !s || !proofs))) return ZL_EINVAL;
+    const zl_r1cs_dev* rd = nullptr;
+    const int rc0 = g16_entry(ctx, pk, r1cs_handle, &rd);
+    if (rc0) return rc0;
+    if (pk->curve != ZL_BLS12_381 && pk->curve != ZL_BN254) return ZL_EINVAL;
+    // the shape (2 + N rate + H, K + N rate + 3 S, 3 S + 1 + N rate) with nv = 2 + 2 N rate + H + K + 3 S; what the matrices say cannot be checked, as with a
+    // witness-only compiler
+    const size_t T = blocks * (width - 1), ni = 2 + T + header_len;
+    if (rd->n_instance != ni || rd->n_witness != nv - ni || rd->n_constraints != nv - ni - key_len + 1) return ZL_EINVAL;
+    const zl_curve_t curve = pk->curve;
+    // initial_state is checked here, before any work and whatever the count (a call of no rows validates the parameters and writes nothing)
+    const int rc1 = zl_poseidon_encrypt_assignments(nullptr, curve, width, initial_state, nullptr, key_len, nullptr, header_len, nullptr, blocks, 0, nullptr);
+    if (rc1 || count == 0) return rc1;
+    G16BatchSource src;
+    src.fill_dev = [=](size_t c0, size_t ch, void* d_rows) {
+        return zl_poseidon_encrypt_trace_rows(ctx, (int)curve, width, initial_state, keys + c0 * key_len * 4, key_len, headers + c0 * header_len * 4, header_len,
+                                              plaintexts + c0 * T * 4, blocks, ch, d_rows, nv, tags_out ? tags_out + c0 * 4 : nullptr,
+                                              ciphertexts_out ? ciphertexts_out + c0 * T * 4 : nullptr);
+    };
+    src.fill_host = [=](size_t c0, size_t ch, uint64_t* rows) {
+        const int rc = zl_poseidon_encrypt_assignments(ctx, curve, width, initial_state, keys + c0 * key_len * 4, key_len, headers + c0 * header_len * 4, header_len,
+                                                       plaintexts + c0 * T * 4, blocks, ch, rows);
+        for (size_t j = 0; rc == ZL_OK && j < ch; j++) {
+            if (tags_out) memcpy(tags_out + (c0 + j) * 4, rows + j * nv * 4 + 4, 32);
+            if (ciphertexts_out) memcpy(ciphertexts_out + (c0 + j) * T * 4, rows + j * nv * 4 + 8, T * 32);
+        }
+        return rc;
+    };
+    return groth16_prove_batch_any(ctx, pk, rd, src, 0, r, s, count, proofs);
+}
 extern "C" int zl_groth16_last_h(zl_ctx* ctx, uint64_t* out, size_t n) {
     if (!ctx || !out || !ctx->g16_h || n > ctx->g16_h_n) return ZL_EINVAL;
     ZL_HIP(ctx, hipMemcpyAsync(out, ctx->g16_h, n * 32, hipMemcpyDeviceToHost, ctx->stream));

@@ -367,9 +367,11 @@ void permute_native(const Constants<FrP, W>& c, Fp<FrP> state[W]) {
 }
 // the same permutation, recording what the in-circuit version allocates: x^2, x^4, x^5 of every S-box whose input is not a constant
 // (lane 0 of the first round is: the capacity element 2^arity - 1 plus a round key), in allocation order -- round order, lane order within a round;
-// 8 W + partial - 1 S-boxes at width W: 78, 86, 95, 103 at widths 3..6
+// 8 W + partial - 1 S-boxes at width W: 78, 86, 95, 103 at widths 3..6.  skip0: the lanes of round 0 that are NOT recorded, one bit per lane -- lane 0 alone for
+// a hash; the duplex cipher's circuit (poseidon_encrypt, zl_host.hip) also folds the rate lanes of its first permutation that hold no key element, and
+// records every S-box of its later permutations (skip0 = 0)
 template <class FrP, int W>
-void permute_native_record(const Constants<FrP, W>& c, Fp<FrP> state[W], std::vector<Fp<FrP>>& rec) {
+void permute_native_record(const Constants<FrP, W>& c, Fp<FrP> state[W], std::vector<Fp<FrP>>& rec, unsigned skip0 = 1u) {
     using F = Fp<FrP>;
     const int half = c.FULL_ROUNDS / 2;
     for (int rnd = 0; rnd < c.FULL_ROUNDS + c.PARTIAL_ROUNDS; rnd++) {
@@ -378,7 +380,7 @@ void permute_native_record(const Constants<FrP, W>& c, Fp<FrP> state[W], std::ve
         for (int i = 0; i < lanes; i++) {
             const F x2 = zl::sqr(state[i]), x4 = zl::sqr(x2);
             state[i] = zl::mul(x4, state[i]);
-            if (rnd != 0 || i != 0) { rec.push_back(x2); rec.push_back(x4); rec.push_back(state[i]); }
+            if (rnd != 0 || !((skip0 >> i) & 1)) { rec.push_back(x2); rec.push_back(x4); rec.push_back(state[i]); }
         }
         F nx[W];
         for (int i = 0; i < W; i++) {

@@ -71,6 +71,24 @@ constexpr size_t leaf_row_elems(unsigned arity, unsigned depth) { return hash_ro
 static_assert(hash_row_elems(2) == 4 + TRACE_PER_LINK, "at arity 2 the hash row is the row of a one-link chain");
 static_assert((leaf_row_elems(MAX_ARITY, MAX_DEPTH) + MAX_ARITY + MAX_DEPTH + 2) * 32 < STAGE_BUDGET, "a row and its inputs fit one staged chunk at every arity and depth");
 
+// the encryption circuit's assignment (zl_poseidon_encrypt_assignments), rate = W - 1: 1, tag, the N rate ciphertext elements, the H header elements, the K key
+// elements, the N rate plaintext elements, then x^2, x^4, x^5 of the S = (F - 1 - Z) + (SB + N - 1) F recorded S-boxes: F = 8 W + partial per permutation, less
+// lane 0 of round 0 and the Z = max(0, rate - K) rate lanes without a key element in the first one.  The limits are the cipher's, with K >= 1.
+constexpr size_t MAX_DUPLEX_KEY = 64, MAX_DUPLEX_HEADER = 64, MAX_DUPLEX_BLOCKS = 1024;
+constexpr bool encrypt_shape_ok(unsigned width, size_t K, size_t H, size_t N) {
+    return width_ok(width) && K >= 1 && K <= MAX_DUPLEX_KEY && H <= MAX_DUPLEX_HEADER && N >= 1 && N <= MAX_DUPLEX_BLOCKS;
+}
+constexpr size_t sboxes_per_permutation(unsigned width) { return (size_t)spec_of_width(width).full_rounds * width + spec_of_width(width).partial_rounds; }
+constexpr size_t encrypt_sboxes(unsigned width, size_t K, size_t H, size_t N) {
+    return sboxes_per_permutation(width) - 1 - (K < width - 1 ? width - 1 - K : 0) + (K / (width - 1) + 1 + H / (width - 1) + 1 + N - 1) * sboxes_per_permutation(width);
+}
+constexpr size_t encrypt_row_elems(unsigned width, size_t K, size_t H, size_t N) { return 2 + 2 * N * (width - 1) + H + K + 3 * encrypt_sboxes(width, K, H, N); }
+static_assert(encrypt_row_elems(3, 2, 0, 1) == 1 + 3 + 2 + 2 + 948 - 3 && encrypt_row_elems(6, 2, 0, 1) == 1 + 6 + 2 + 5 + 930 - 6, "(2, 0, 1): 948 and 930 constraints at widths 3 and 6");
+static_assert(encrypt_row_elems(MAX_WIDTH, MAX_DUPLEX_KEY, MAX_DUPLEX_HEADER, MAX_DUPLEX_BLOCKS) < ((size_t)1 << 31) &&
+                  (encrypt_row_elems(MAX_WIDTH, MAX_DUPLEX_KEY, MAX_DUPLEX_HEADER, MAX_DUPLEX_BLOCKS) + MAX_DUPLEX_KEY + MAX_DUPLEX_HEADER + 2 * MAX_DUPLEX_BLOCKS * (MAX_WIDTH - 1) + 1) * 32 <
+                      STAGE_BUDGET,
+              "the longest row fits 31 bits, and with its inputs and dense outputs one staged chunk");
+
 constexpr bool geometry_ok(size_t n, unsigned depth) { return depth >= 1 && depth <= MAX_DEPTH && ((n >> depth) == 0 || n == ((size_t)1 << depth)); }
 constexpr size_t level_size(size_t n, unsigned k) { return k >= 64 ? (n ? 1 : 0) : (n >> k) + ((n & (((size_t)1 << k) - 1)) ? 1 : 0); }  // ceil(n / 2^k)
 constexpr size_t level_offset(size_t n, unsigned k) {  // elements in front of level k
@@ -104,6 +122,12 @@ int zl_poseidon_merkle_leaf_trace_rows(zl_ctx* ctx, int curve, unsigned arity, c
                                        size_t count, void* d_rows, size_t stride_elems, uint64_t* roots_out);
 int zl_poseidon_merkle_leaf_member_rows(zl_ctx* ctx, int curve, unsigned arity, const void* d_nodes, const void* d_preimages, size_t n, unsigned depth,
                                         const uint64_t* indices, size_t count, void* d_rows, size_t stride_elems, uint64_t* host_rows);
+// The encryption producer of the fused prover (zl_groth16_prove_poseidon_encryptions), under the same rules: HOST keys (count x key_len), headers (count x
+// header_len) and plaintexts (count x blocks x (width - 1)) -> rows in DEVICE memory; tags_out / ciphertexts_out (host, may be null) receive the tag and the
+// ciphertext of every item.  Curve, width, the lengths and initial_state (NULL = zero, each element below r) are checked here as zl_poseidon_encrypt_assignments does.
+int zl_poseidon_encrypt_trace_rows(zl_ctx* ctx, int curve, unsigned width, const uint64_t* initial_state, const uint64_t* keys, size_t key_len, const uint64_t* headers,
+                                   size_t header_len, const uint64_t* plaintexts, size_t blocks, size_t count, void* d_rows, size_t stride_elems, uint64_t* tags_out,
+                                   uint64_t* ciphertexts_out);
 // The forest producer of the fused prover (zl_groth16_prove_forest_members).  _prover_view: ZL_EINVAL for a null or host-mirror forest or a ctx of another
 // device, else the forest's curve and depth.  _members_ok: ZL_EINVAL unless every (tree_of[i], indices[i]) names a leaf the forest holds.  _member_rows:
 // zl_poseidon_merkle_member_rows with a tree per item, issued on ctx (the forest's own ctx or another lane of its device); roots_out (host, may be null)

@@ -29,6 +29,9 @@
 //   k_pos_duplex     the duplex-sponge cipher (zl_poseidon_duplex_*), widths 3..6: one lane per message, its key, header and message blocks absorbed into the rate
 //                    between the SB + N dependent permutations of ONE launch (permute_any); encrypt and decrypt are one template with a wave-uniform mode.  The
 //                    absorbed lanes are outside the permutations' bound arguments and are reduced weakly at once (DuplexBounds).
+//   k_pos_duplex_trace   k_pos_duplex, encrypting, with the witness written out: the complete assignment of zl_circuit_poseidon_encrypt per message -- 1, tag,
+//                    ciphertext, header, key, plaintext, then the records of the SB + N permutations -- under the circuit's round-0 record mask (rec0_mask): the
+//                    first permutation drops lane 0 and the rate lanes without a key element, every later one records all of its S-boxes (DuplexTraceBounds).
 // Arithmetic: the lazily reduced 9 x 29-bit Fr of zl_field28r.h (the NTT's multiplier), 1.29 - 1.46 x the carry-chain Fp<FrP> here and ahead of the 10 x 28 form at
 // every size measured (profiles/poseidon_field_ab.log); the bound argument stands beside the type below.  The host path stays on Fp<FrP>.
 // A lane at or above the item count returns before it reads or writes anything.  An input element >= r sets the flag word (atomicOr) and the lane goes on with
@@ -185,18 +188,23 @@ __device__ __forceinline__ void sbox(El<FrP>& x, Rec& rec, bool recorded) {
 // 63 rounds of add-round-key / x^5 / MDS: 8 * (9 + 9) + 55 * (3 + 9) = 804 multiplications.  One rolled loop (18 inlined multiplier bodies), the full / partial
 // choice is a wave-uniform branch.  `rec` sees the S-boxes in the order the in-circuit hash allocates them, without lane 0 of round 0: its input is the domain
 // tag plus a round key, a constant, and the circuit folds it (poseidon::hash in zl_host.h; permute_native_record is the host's form of this).
+// skip0 is that rule as a mask: bit i set = lane i of round 0 is NOT recorded.  Every caller but k_pos_duplex_trace leaves it at the compile-time default, lane 0
+// alone, which folds to the `rnd != 0` / `true` the S-boxes were written with; the encryption circuit folds more lanes of its first permutation and none of
+// the later ones (rec0_mask).
+constexpr uint32_t SKIP0_HASH = 1u;
+__device__ __forceinline__ bool rec_lane(int rnd, uint32_t skip0, int lane) { return rnd != 0 || !((skip0 >> lane) & 1u); }
 template <class FrP, class Rec>
-__device__ __forceinline__ void permute_dev(const uint32_t* __restrict__ tab, El<FrP>& s0, El<FrP>& s1, El<FrP>& s2, Rec& rec) {
+__device__ __forceinline__ void permute_dev(const uint32_t* __restrict__ tab, El<FrP>& s0, El<FrP>& s1, El<FrP>& s2, Rec& rec, const uint32_t skip0 = SKIP0_HASH) {
     constexpr int half = pd::FULL_ROUNDS / 2;
 #pragma unroll 1
     for (int rnd = 0; rnd < pd::ROUNDS; rnd++) {
         s0 = zl::add(s0, tab_ld<FrP>(tab, pd::TAB_KEYS + 3 * rnd));
         s1 = zl::add(s1, tab_ld<FrP>(tab, pd::TAB_KEYS + 3 * rnd + 1));
         s2 = zl::add(s2, tab_ld<FrP>(tab, pd::TAB_KEYS + 3 * rnd + 2));
-        sbox<FrP>(s0, rec, rnd != 0);
+        sbox<FrP>(s0, rec, rec_lane(rnd, skip0, 0));
         if (rnd < half || rnd >= half + pd::PARTIAL_ROUNDS) {
-            sbox<FrP>(s1, rec, true);
-            sbox<FrP>(s2, rec, true);
+            sbox<FrP>(s1, rec, rec_lane(rnd, skip0, 1));
+            sbox<FrP>(s2, rec, rec_lane(rnd, skip0, 2));
         }
         El<FrP> nx[3];
 #pragma unroll
@@ -605,27 +613,27 @@ __device__ __forceinline__ void sbox_w(El<FrP>& x, Rec& rec, bool recorded) {
 // the S-boxes of lanes I .. W - 1 of a full round, one after the other.  A compile-time recursion, not a loop: with a recorder the body holds six multiplier
 // bodies per lane, and at width 6 the loop unroller gives up on it -- the state would then be indexed at run time and leave its registers.
 template <class FrP, int W, int I, class Rec>
-__device__ __forceinline__ void sbox_lanes(El<FrP> (&s)[W], Rec& rec) {
+__device__ __forceinline__ void sbox_lanes(El<FrP> (&s)[W], Rec& rec, int rnd, const uint32_t skip0) {
     if constexpr (I < W) {
-        sbox_w<FrP, W>(s[I], rec, true);
-        sbox_lanes<FrP, W, I + 1>(s, rec);
+        sbox_w<FrP, W>(s[I], rec, rec_lane(rnd, skip0, I));
+        sbox_lanes<FrP, W, I + 1>(s, rec, rnd, skip0);
     }
 }
 // 8 (3W + W^2) + partial (3 + W^2) multiplications: 1 288, 1 976, 2 616 at widths 4, 5, 6.  One rolled round loop; the ROWS of the MDS product are a rolled loop
 // too, so a round holds 3W + W inlined multiplier bodies instead of 3W + W^2 (24 instead of 54 at width 6): row i is accumulated against the W state registers
 // and shifted into nx from the top, all register indices static, and after W rows nx[k] is row k.  Table addresses depend on the round and the row only.
 // `rec` (NoRec, or RowRec in the trace kernels) sees the S-boxes in round order, lane order within a round, without lane 0 of round 0 -- the order in which
-// poseidon::hash<FrP, W> of zl_host.h allocates them, as permute_dev's recorder does at width 3.
+// poseidon::hash<FrP, W> of zl_host.h allocates them, as permute_dev's recorder does at width 3; skip0 as there.
 template <class FrP, int W, class Rec>
-__device__ __forceinline__ void permute_w(const uint32_t* __restrict__ tab, El<FrP> (&s)[W], Rec& rec) {
+__device__ __forceinline__ void permute_w(const uint32_t* __restrict__ tab, El<FrP> (&s)[W], Rec& rec, const uint32_t skip0 = SKIP0_HASH) {
     constexpr pd::Spec S = pd::spec_of_width(W);
     constexpr int half = (int)S.full_rounds / 2, partial = (int)S.partial_rounds, rounds = (int)S.rounds();
 #pragma unroll 1
     for (int rnd = 0; rnd < rounds; rnd++) {
 #pragma unroll
         for (int i = 0; i < W; i++) s[i] = zl::add(s[i], tab_ld<FrP>(tab, pd::tab_keys(W) + W * rnd + i));
-        sbox_w<FrP, W>(s[0], rec, rnd != 0);
-        if (rnd < half || rnd >= half + partial) sbox_lanes<FrP, W, 1>(s, rec);
+        sbox_w<FrP, W>(s[0], rec, rec_lane(rnd, skip0, 0));
+        if (rnd < half || rnd >= half + partial) sbox_lanes<FrP, W, 1>(s, rec, rnd, skip0);
         El<FrP> nx[W];
 #pragma unroll
         for (int i = 0; i < W; i++) nx[i] = ezero<FrP>();
@@ -678,9 +686,9 @@ __global__ __launch_bounds__(BLOCK) void k_pos_hash_w(const uint32_t* __restrict
 // the recording permutation of any width of the table: width 3 is the width-3 unit's own permute_dev (what k_pos_chain_trace and k_pos_merkle_trace run), the
 // wider ones permute_w
 template <class FrP, int W, class Rec>
-__device__ __forceinline__ void permute_any(const uint32_t* __restrict__ tab, El<FrP> (&s)[W], Rec& rec) {
-    if constexpr (W == 3) permute_dev<FrP>(tab, s[0], s[1], s[2], rec);
-    else permute_w<FrP, W>(tab, s, rec);
+__device__ __forceinline__ void permute_any(const uint32_t* __restrict__ tab, El<FrP> (&s)[W], Rec& rec, const uint32_t skip0 = SKIP0_HASH) {
+    if constexpr (W == 3) permute_dev<FrP>(tab, s[0], s[1], s[2], rec, skip0);
+    else permute_w<FrP, W>(tab, s, rec, skip0);
 }
 // k_pos_hash_w with the witness written out: the complete assignment of zl_circuit_poseidon_hash(curve, W - 1, in) per item, one lane each.  Row p = out +
 // p * stride elements (16-byte aligned): [0] = 1, [1] = the digest, [2 .. W + 1) the inputs, then the 3 (8 W + partial - 1) records of the hash; elements
@@ -946,6 +954,123 @@ __global__ __launch_bounds__(BLOCK) void k_pos_duplex(const uint32_t* __restrict
         for (int i = 0; i < 4; i++) tag[i] = tg[i];
     }
     if (!ok) atomicOr(flag, 1u);
+}
+// ---- the encryption with its witness written out (zl_poseidon_encrypt_assignments): k_pos_duplex's chain, encrypting, under a recorder.
+// What the trace stores that k_pos_duplex does not, in units of r:
+//   * the records x^2, x^4, x^5 of an S-box: products (< 2r) whichever way the input came (with WideBounds::REDUCE: of the reduced input, the same element);
+//     the canonical store's mul(x, 1) takes them at 2 * 1, as in every trace kernel;
+//   * the public ciphertext cell: the absorbed lane, wred's result (< ABSORBED r = 2r) -- the value k_pos_duplex stores as the ciphertext, at 2 * 1;
+//   * the tag cell: lane 1 of the last permutation's output, a row sum, at ROW * 1 as k_pos_duplex's tag;
+//   * key, header and plaintext cells are the input words copied as they are (an input >= r raises the flag and the call fails).
+// Recording reads the S-box's intermediates and changes none of them: every bound of DuplexBounds and of the permutations holds unchanged.  The permutations
+// after the first enter round 0 with lane 0 a row sum (< ROW r) plus a round key -- what WideBounds (KEYED) and the width-3 argument (< 6r entering a round)
+// already assume of any lane; that its S-box is now RECORDED there changes no operand.
+template <class FrP, int W>
+struct DuplexTraceBounds {
+    using P = typename LazyP<FrP>::P;
+    static constexpr int RECORD = 2;                                             // a product
+    static constexpr int RECORD_STORE_MUL = RECORD * 1;
+    static constexpr int CIPHER_CELL_MUL = DuplexBounds<FrP, W>::ABSORBED * 1;   // the reduced sum
+    static constexpr int TAG_CELL_MUL = DuplexBounds<FrP, W>::TAG_STORE_MUL;
+    static constexpr int MAX_MUL = cmax(RECORD_STORE_MUL, cmax(CIPHER_CELL_MUL, TAG_CELL_MUL));
+    static_assert(MAX_MUL <= P::MUL_BOUND, "a bound product above what mul takes");
+    static_assert(RECORD <= 128 && DuplexBounds<FrP, W>::ABSORBED <= 128 && WideBounds<FrP, W>::ROW <= 128, "canon takes a value below 128 r");
+};
+#define ZL_POS_DUPLEX_TRACE_BOUNDS(FrP, W, tag_mul) \
+    static_assert(DuplexTraceBounds<FrP, W>::RECORD_STORE_MUL == 2 && DuplexTraceBounds<FrP, W>::CIPHER_CELL_MUL == 2 && DuplexTraceBounds<FrP, W>::TAG_CELL_MUL == tag_mul && \
+                  DuplexTraceBounds<FrP, W>::MAX_MUL == tag_mul && DuplexTraceBounds<FrP, W>::MAX_MUL <= LazyP<FrP>::P::MUL_BOUND, "duplex trace bounds of " #FrP " at width " #W)
+ZL_POS_DUPLEX_TRACE_BOUNDS(BLS12_381_Fr, 3, 6);
+ZL_POS_DUPLEX_TRACE_BOUNDS(BLS12_381_Fr, 4, 8);
+ZL_POS_DUPLEX_TRACE_BOUNDS(BLS12_381_Fr, 5, 10);
+ZL_POS_DUPLEX_TRACE_BOUNDS(BLS12_381_Fr, 6, 12);
+ZL_POS_DUPLEX_TRACE_BOUNDS(BN254_Fr, 3, 6);
+ZL_POS_DUPLEX_TRACE_BOUNDS(BN254_Fr, 4, 8);
+ZL_POS_DUPLEX_TRACE_BOUNDS(BN254_Fr, 5, 10);
+ZL_POS_DUPLEX_TRACE_BOUNDS(BN254_Fr, 6, 12);
+#undef ZL_POS_DUPLEX_TRACE_BOUNDS
+// The round-0 lanes the encryption circuit does NOT record in its first permutation: lane 0 (the capacity constant) and the rate lanes without a key element,
+// 1 + K .. W - 1 when K < rate -- their input is a constant of the initial state plus a round key whatever that constant is.  Later permutations: none.
+ZL_HD uint32_t rec0_mask(unsigned width, size_t key_len, bool first) {
+    if (!first) return 0u;
+    const unsigned kk = key_len < width - 1 ? (unsigned)key_len : width - 1;
+    return 1u | (((1u << width) - 1u) ^ ((1u << (1 + kk)) - 1u));
+}
+// rate lanes I .. W - 2 of one block under the trace (duplex_lanes, encrypting): lane i takes element i of the block when i < avail, the element's words go to
+// cell i of `in_cells` (16-byte aligned) as they are, and a message block's reduced sum -- the ciphertext -- to cell i of ct_cells and, densely, to ct_pub
+// (may be null): one canonical store, written twice.
+template <class FrP, int W, int I>
+__device__ __forceinline__ void duplex_trace_lanes(El<FrP> (&s)[W], const uint64_t* src, uint64_t* in_cells, uint64_t* ct_cells, uint64_t* ct_pub, uint32_t avail, bool message,
+                                                   bool& ok) {
+    if constexpr (I < W - 1) {
+        if ((uint32_t)I < avail) {
+            const uint64_t* x = src + 4 * I;
+            El<FrP> e;
+            ok &= dload<FrP>(x, e);
+            copy16(in_cells + 4 * I, x[0], x[1], x[2], x[3]);
+            s[1 + I] = zl::wred(zl::add(s[1 + I], e));
+            if (message) {
+                uint64_t c[4];
+                dstore<FrP>(c, s[1 + I]);
+                copy16(ct_cells + 4 * I, c[0], c[1], c[2], c[3]);
+                if (ct_pub) {
+#pragma unroll
+                    for (int k = 0; k < 4; k++) ct_pub[4 * I + k] = c[k];
+                }
+            }
+        }
+        duplex_trace_lanes<FrP, W, I + 1>(s, src, in_cells, ct_cells, ct_pub, avail, message, ok);
+    }
+}
+// k_pos_duplex, encrypting, with the witness written out: the complete assignment of zl_circuit_poseidon_encrypt(curve, W, init, key, header, plaintext) per
+// message, one lane each, the SB + N dependent permutations in one launch.  Row p = out + p * stride elements (16-byte aligned), rate = W - 1:
+//   [0] = 1   [1] = tag   [2 .. 2 + N rate) ciphertext   [.. + H) header   [.. + K) key   [.. + N rate) plaintext   then 3 S record elements in execution order;
+// elements behind the row are not touched.  The lane writes the input cells and the ciphertext cells as it absorbs their blocks, the records as the
+// permutations run, [0] and [1] last.  Rows and inputs do not overlap.  tags / cts (may be null) receive the tag and the N rate ciphertext elements, densely.
+// K >= 1; block selection as in k_pos_duplex, all wave-uniform, and so is the record mask.
+template <class FrP, int W>
+__global__ __launch_bounds__(BLOCK) void k_pos_duplex_trace(const uint32_t* __restrict__ tab, const DuplexInit init, const uint64_t* __restrict__ keys, uint32_t K,
+                                                            const uint64_t* __restrict__ headers, uint32_t H, const uint64_t* __restrict__ texts, uint32_t N, size_t n,
+                                                            uint64_t* __restrict__ out, size_t stride, uint64_t* __restrict__ tags, uint64_t* __restrict__ cts,
+                                                            uint32_t* __restrict__ flag) {
+    const size_t p = (size_t)blockIdx.x * BLOCK + threadIdx.x;
+    if (p >= n) return;
+    constexpr uint32_t RATE = W - 1;
+    El<FrP> s[W];
+#pragma unroll
+    for (int i = 0; i < W; i++) (void)dload<FrP>(init.w + 4 * i, s[i]);  // (checked on the host)
+    const uint32_t kb = K / RATE + 1, sb = kb + H / RATE + 1, total = sb + N, T = N * RATE;
+    const uint64_t* key = keys + p * K * 4;
+    const uint64_t* header = headers + p * H * 4;
+    const uint64_t* text = texts + p * T * 4;
+    uint64_t* row = out + p * stride * 4;
+    uint64_t* ct_cells = row + 8;
+    uint64_t* h_cells = ct_cells + (size_t)T * 4;
+    uint64_t* k_cells = h_cells + (size_t)H * 4;
+    uint64_t* p_cells = k_cells + (size_t)K * 4;
+    uint64_t* ct_pub = cts ? cts + p * T * 4 : nullptr;
+    RowRec<FrP> rec{p_cells + (size_t)T * 4};
+    bool ok = true;
+#pragma unroll 1
+    for (uint32_t t = 0; t < total; t++) {
+        const bool message = t >= sb;
+        const uint32_t b = message ? t - sb : t < kb ? t : t - kb;       // the block's number within its sequence
+        const uint32_t len = message ? T : t < kb ? K : H;                // ... and the sequence's length: b * RATE <= len
+        const size_t at = (size_t)b * RATE * 4;
+        const uint64_t* src = (message ? text : t < kb ? key : header) + at;
+        uint64_t* in_cells = (message ? p_cells : t < kb ? k_cells : h_cells) + at;
+        const uint32_t left = len - b * RATE;
+        duplex_trace_lanes<FrP, W, 0>(s, src, in_cells, message ? ct_cells + at : nullptr, message && ct_pub ? ct_pub + at : nullptr, left < RATE ? left : RATE, message, ok);
+        permute_any<FrP, W>(tab, s, rec, rec0_mask(W, K, t == 0));
+    }
+    if (!ok) atomicOr(flag, 1u);
+    uint64_t tg[4];
+    dstore<FrP>(tg, s[1]);
+    copy16(row, 1, 0, 0, 0);
+    copy16(row + 4, tg[0], tg[1], tg[2], tg[3]);
+    if (tags) {
+#pragma unroll
+        for (int i = 0; i < 4; i++) tags[p * 4 + i] = tg[i];
+    }
 }
 
 // ---------------------------------------------------------------------------------------------------------------- host path
@@ -1246,6 +1371,65 @@ int host_duplex(const uint64_t* init, const uint64_t* keys, size_t K, const uint
             store_canon<FrP>(tags + i * 4, poseidon::duplex_encrypt<FrP, W>(consts<FrP, W>(), st, key, K, header, H, text, N));
         }
         for (size_t e = 0; e < T; e++) store_canon<FrP>(text_out + (i * T + e) * 4, text[e]);
+        return ok;
+    }) ? ZL_OK : ZL_EINVAL;
+}
+// row i = the assignment of encryption i (nv = pd::encrypt_row_elems elements): what poseidon_encrypt (zl_host.hip) allocates -- duplex_setup's and
+// duplex_encrypt's block walk with permute_native_record in place of permute_native, under the circuit's round-0 mask (rec0_mask)
+template <class FrP, int W>
+int host_encrypt_assignments(const uint64_t* init, const uint64_t* keys, size_t K, const uint64_t* headers, size_t H, const uint64_t* texts, size_t N, size_t count,
+                             uint64_t* out, size_t nv) {
+    consts<FrP, W>();
+    constexpr size_t rate = W - 1;
+    const size_t T = N * rate;
+    Fp<FrP> st0[W];
+    for (int e = 0; e < W; e++) (void)load_canon<FrP>(init + 4 * e, st0[e]);
+    return host_for(count, [&](size_t i) {
+        uint64_t* row = out + i * nv * 4;
+        uint64_t* ct_cells = row + 8;
+        uint64_t* h_cells = ct_cells + T * 4;
+        uint64_t* k_cells = h_cells + H * 4;
+        uint64_t* p_cells = k_cells + K * 4;
+        uint64_t* rec_cells = p_cells + T * 4;
+        if (H) memcpy(h_cells, headers + i * H * 4, H * 32);
+        memcpy(k_cells, keys + i * K * 4, K * 32);
+        memcpy(p_cells, texts + i * T * 4, T * 32);
+        Fp<FrP> st[W];
+        for (int e = 0; e < W; e++) st[e] = st0[e];
+        std::vector<Fp<FrP>> rec;
+        rec.reserve(3 * (size_t)(consts<FrP, W>().FULL_ROUNDS * W + consts<FrP, W>().PARTIAL_ROUNDS));
+        bool ok = true, first = true;
+        auto permute = [&]() {
+            rec.clear();
+            poseidon::permute_native_record(consts<FrP, W>(), st, rec, rec0_mask(W, K, first));
+            first = false;
+            for (size_t t = 0; t < rec.size(); t++) store_canon<FrP>(rec_cells + 4 * t, rec[t]);
+            rec_cells += 4 * rec.size();
+        };
+        for (int part = 0; part < 2; part++) {
+            const uint64_t* src = part ? h_cells : k_cells;
+            const size_t len = part ? H : K;
+            for (size_t b = 0; b <= len / rate; b++) {
+                for (size_t l = 0; l < rate && b * rate + l < len; l++) {
+                    Fp<FrP> e;
+                    ok &= load_canon<FrP>(src + (b * rate + l) * 4, e);
+                    st[1 + l] = zl::add(st[1 + l], e);
+                }
+                permute();
+            }
+        }
+        for (size_t j = 0; j < N; j++) {
+            for (size_t l = 0; l < rate; l++) {
+                Fp<FrP> e;
+                ok &= load_canon<FrP>(p_cells + (j * rate + l) * 4, e);
+                st[1 + l] = zl::add(st[1 + l], e);
+                store_canon<FrP>(ct_cells + (j * rate + l) * 4, st[1 + l]);
+            }
+            permute();
+        }
+        row[0] = 1;
+        row[1] = row[2] = row[3] = 0;
+        store_canon<FrP>(row + 4, st[1]);
         return ok;
     }) ? ZL_OK : ZL_EINVAL;
 }
@@ -2017,6 +2201,52 @@ int dev_duplex(zl_ctx* ctx, const DuplexCall& c, const uint64_t* keys, const uin
     }
     return finish(ctx, s.flag);
 }
+// Every form of the encryption trace at width W (c.decrypt is unused).  keys / headers / texts: dense per item, staged per chunk when in_on_host, else device
+// memory; host_rows != null: the rows are staged, dense, and downloaded (d_rows and stride are ignored), otherwise row i goes to d_rows + i * stride
+// elements; host_tags / host_cts != null: the tag resp. the ciphertext of every item is staged and downloaded.  A chunk is one launch.
+template <class FrP, int W>
+int encrypt_trace_run(zl_ctx* ctx, const DuplexCall& c, const uint64_t* keys, const uint64_t* headers, const uint64_t* texts, bool in_on_host, size_t count, uint64_t* d_rows,
+                      size_t stride, uint64_t* host_rows, uint64_t* host_tags, uint64_t* host_cts) {
+    const uint32_t* tab;
+    int rc = get_table<FrP, W>(ctx, &tab);
+    if (rc) return rc;
+    const size_t T = c.N * (W - 1), nv = pd::encrypt_row_elems(W, c.K, c.H, c.N);
+    const size_t per = (host_tags ? 32 : 0) + (host_cts ? T * 32 : 0) + (in_on_host ? (c.K + c.H + T) * 32 : 0) + (host_rows ? nv * 32 : 0);
+    const size_t chunk = stage_items(per ? per : 1), m0 = count < chunk ? count : chunk;
+    const size_t o_ct = host_tags ? up256(m0 * 32) : 0, o_key = o_ct + (host_cts ? up256(m0 * T * 32) : 0), o_hdr = o_key + (in_on_host ? up256(m0 * c.K * 32) : 0),
+                 o_text = o_hdr + (in_on_host ? up256(m0 * c.H * 32) : 0), o_rows = o_text + (in_on_host ? up256(m0 * T * 32) : 0);
+    Stage s;
+    if ((rc = stage_get(ctx, o_rows + (host_rows ? m0 * nv * 32 : 0), &s))) return rc;
+    uint64_t* d_tag = host_tags ? reinterpret_cast<uint64_t*>(s.data) : nullptr;
+    uint64_t* d_ct = host_cts ? reinterpret_cast<uint64_t*>(s.data + o_ct) : nullptr;
+    uint64_t* d_key = reinterpret_cast<uint64_t*>(s.data + o_key);
+    uint64_t* d_hdr = reinterpret_cast<uint64_t*>(s.data + o_hdr);
+    uint64_t* d_text = reinterpret_cast<uint64_t*>(s.data + o_text);
+    uint64_t* d_stage_rows = reinterpret_cast<uint64_t*>(s.data + o_rows);
+    DuplexInit init{};
+    memcpy(init.w, c.init, 32 * W);
+    for (size_t first = 0; first < count; first += chunk) {
+        const size_t m = count - first < chunk ? count - first : chunk;
+        const uint64_t* k_from = keys + first * c.K * 4;
+        const uint64_t* h_from = headers + first * c.H * 4;
+        const uint64_t* t_from = texts + first * T * 4;
+        if (in_on_host) {
+            ZL_HIP(ctx, hipMemcpyAsync(d_key, k_from, m * c.K * 32, hipMemcpyHostToDevice, ctx->stream));
+            if (c.H) ZL_HIP(ctx, hipMemcpyAsync(d_hdr, h_from, m * c.H * 32, hipMemcpyHostToDevice, ctx->stream));
+            ZL_HIP(ctx, hipMemcpyAsync(d_text, t_from, m * T * 32, hipMemcpyHostToDevice, ctx->stream));
+            k_from = d_key;
+            h_from = d_hdr;
+            t_from = d_text;
+        }
+        uint64_t* rows = host_rows ? d_stage_rows : d_rows + first * stride * 4;
+        ZL_POS_LAUNCH(ctx, (k_pos_duplex_trace<FrP, W>), blocks_of(m), BLOCK, 0, tab, init, k_from, (uint32_t)c.K, h_from, (uint32_t)c.H, t_from, (uint32_t)c.N, m, rows,
+                      host_rows ? nv : stride, d_tag, d_ct, s.flag);
+        if (host_rows) ZL_HIP(ctx, hipMemcpyAsync(host_rows + first * nv * 4, d_stage_rows, m * nv * 32, hipMemcpyDeviceToHost, ctx->stream));
+        if (host_tags) ZL_HIP(ctx, hipMemcpyAsync(host_tags + first * 4, d_tag, m * 32, hipMemcpyDeviceToHost, ctx->stream));
+        if (host_cts) ZL_HIP(ctx, hipMemcpyAsync(host_cts + first * T * 4, d_ct, m * T * 32, hipMemcpyDeviceToHost, ctx->stream));
+    }
+    return finish(ctx, s.flag);
+}
 // the parameters of a call: ZL_EINVAL, or ZL_OK with the initial state's words (zero for a null pointer) in init_out
 template <class FrP>
 bool duplex_init_ok(const uint64_t* w, unsigned width) {
@@ -2060,6 +2290,21 @@ int zl_poseidon_merkle_leaf_trace_rows(zl_ctx* ctx, int curve, unsigned arity, c
 int zl_poseidon_merkle_leaf_member_rows(zl_ctx* ctx, int curve, unsigned arity, const void* d_nodes, const void* d_preimages, size_t n, unsigned depth,
                                         const uint64_t* indices, size_t count, void* d_rows, size_t stride_elems, uint64_t* host_rows) {
     return ZL_POS_ANYW(curve, arity + 1, dev_leaf_from_tree, ctx, d_nodes, d_preimages, n, depth, indices, count, d_rows, stride_elems, host_rows);
+}
+// one validation for every form of the encryption trace: the cipher's limits with key_len >= 1, the curve, the initial state (-> init_out, W elements)
+static int encrypt_params(zl_curve_t curve, unsigned width, const uint64_t* initial_state, size_t key_len, size_t header_len, size_t blocks, uint64_t* init_out) {
+    if (!pd::encrypt_shape_ok(width, key_len, header_len, blocks)) return ZL_EINVAL;
+    return duplex_params(curve, width, initial_state, key_len, header_len, blocks, init_out);
+}
+int zl_poseidon_encrypt_trace_rows(zl_ctx* ctx, int curve, unsigned width, const uint64_t* initial_state, const uint64_t* keys, size_t key_len, const uint64_t* headers,
+                                   size_t header_len, const uint64_t* plaintexts, size_t blocks, size_t count, void* d_rows, size_t stride_elems, uint64_t* tags_out,
+                                   uint64_t* ciphertexts_out) {
+    uint64_t init[4 * pd::MAX_WIDTH];
+    const int rc = encrypt_params((zl_curve_t)curve, width, initial_state, key_len, header_len, blocks, init);
+    if (rc) return rc;
+    const DuplexCall c{init, key_len, header_len, blocks, false};
+    return ZL_POS_ANYW(curve, width, encrypt_trace_run, ctx, c, keys, headers, plaintexts, true, count, static_cast<uint64_t*>(d_rows), stride_elems, nullptr, tags_out,
+                       ciphertexts_out);
 }
 
 extern "C" {
@@ -2183,6 +2428,36 @@ int zl_poseidon_duplex_decrypt_batch_dev(zl_ctx* ctx, zl_curve_t curve, unsigned
                                          void* d_plaintexts, uint8_t* ok_each) {
     return duplex_batch_dev(ctx, curve, width, initial_state, d_keys, key_len, d_headers, header_len, d_ciphertexts, blocks, count, d_plaintexts, const_cast<void*>(d_tags),
                             ok_each, true);
+}
+// ---- the encryption circuit's assignments: the cipher's validation plus the circuit's (encrypt_params), then the host mirror or the trace kernel
+size_t zl_poseidon_encrypt_assignment_elems(unsigned width, size_t key_len, size_t header_len, size_t blocks) {
+    return pd::encrypt_shape_ok(width, key_len, header_len, blocks) ? pd::encrypt_row_elems(width, key_len, header_len, blocks) : 0;
+}
+int zl_poseidon_encrypt_assignments(zl_ctx* ctx, zl_curve_t curve, unsigned width, const uint64_t* initial_state, const uint64_t* keys, size_t key_len,
+                                    const uint64_t* headers, size_t header_len, const uint64_t* plaintexts, size_t blocks, size_t count, uint64_t* out) {
+    uint64_t init[4 * pd::MAX_WIDTH];
+    const int rc = encrypt_params(curve, width, initial_state, key_len, header_len, blocks, init);
+    if (rc) return rc;
+    const size_t nv = pd::encrypt_row_elems(width, key_len, header_len, blocks);  // (with its inputs within the staging budget at every shape: zl_poseidon_dev.h)
+    if (count && (!keys || (header_len && !headers) || !plaintexts || !out)) return ZL_EINVAL;
+    if (count == 0) return ZL_OK;
+    if (on_host(ctx, count)) return ZL_POS_ANYW(curve, width, host_encrypt_assignments, init, keys, key_len, headers, header_len, plaintexts, blocks, count, out, nv);
+    ZL_HIP(ctx, hipSetDevice(ctx->device));
+    const DuplexCall c{init, key_len, header_len, blocks, false};
+    return ZL_POS_ANYW(curve, width, encrypt_trace_run, ctx, c, keys, headers, plaintexts, true, count, nullptr, 0, out, nullptr, nullptr);
+}
+int zl_poseidon_encrypt_assignments_dev(zl_ctx* ctx, zl_curve_t curve, unsigned width, const uint64_t* initial_state, const void* d_keys, size_t key_len,
+                                        const void* d_headers, size_t header_len, const void* d_plaintexts, size_t blocks, size_t count, void* d_out, size_t stride_elems) {
+    uint64_t init[4 * pd::MAX_WIDTH];
+    const int rc = ctx ? encrypt_params(curve, width, initial_state, key_len, header_len, blocks, init) : ZL_EINVAL;
+    if (rc) return rc;
+    if (stride_elems < pd::encrypt_row_elems(width, key_len, header_len, blocks) || ((uintptr_t)d_out & 15)) return ZL_EINVAL;
+    if (count && (!d_keys || (header_len && !d_headers) || !d_plaintexts || !d_out)) return ZL_EINVAL;
+    if (count == 0) return ZL_OK;
+    ZL_HIP(ctx, hipSetDevice(ctx->device));
+    const DuplexCall c{init, key_len, header_len, blocks, false};
+    return ZL_POS_ANYW(curve, width, encrypt_trace_run, ctx, c, static_cast<const uint64_t*>(d_keys), static_cast<const uint64_t*>(d_headers),
+                       static_cast<const uint64_t*>(d_plaintexts), false, count, static_cast<uint64_t*>(d_out), stride_elems, nullptr, nullptr, nullptr);
 }
 int zl_poseidon_chain_batch(zl_ctx* ctx, zl_curve_t curve, const uint64_t* x0, const uint64_t* x1, uint32_t k, size_t count, uint64_t* out) {
     if (!valid_curve(curve) || k == 0 || (count && (!x0 || !x1 || !out))) return ZL_EINVAL;
