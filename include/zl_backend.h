@@ -144,7 +144,10 @@ void zl_groth16_keys_free(zl_g16_keys* k); /* must be called BEFORE zl_ctx_destr
 int zl_groth16_keys_pk(const zl_g16_keys* k, zl_g16_pk* pk);
 
 /* The proof points are taken as given: callers that accept proofs from outside deserialize them with zl_groth16_proof_from_bytes, which
- * checks curve membership and the subgroup (as arkworks' deserialization does); A or B at infinity is rejected here.
+ * checks curve membership and the subgroup (as arkworks' deserialization does); A or B at infinity is rejected here.  "As given" includes the words of
+ * a coordinate: one written at or above q (x + k q, anything that fits the coordinate's words) is read as its residue mod q on EVERY path -- host pairing,
+ * device Miller loops, the batch verifier, zl_pairing*, zl_bases_upload -- so it names the same point everywhere.  The entry points that refuse
+ * non-canonical input (the decoders, Poseidon, the public inputs below, zl_msm's scalar width) keep refusing it.
  * Groth16::verify (host pairing; public_inputs: n x 4 u64 canonical (each < r; otherwise ZL_EINVAL, nothing computed, outputs untouched), without the
  * leading ONE): *ok = 1 accepted, 0 rejected.  A value at or above r is an error and not a verdict of 0: x + k r is the residue x, so the pairing equation
  * cannot tell the two encodings apart while a caller that stores the 32 bytes can; the reference's typed field elements fail at deserialisation, and

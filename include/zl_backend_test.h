@@ -40,6 +40,19 @@ int zl_test_fp28_op(zl_ctx* ctx, int op, const uint32_t* in, size_t n, uint32_t*
  * ops 17 / 18 move 8 canonical words.  (muladd4 and the Fq2 helpers are not used by BN254 G1; op 15 still computes.) */
 int zl_test_fp28_bn_op(zl_ctx* ctx, int op, const uint32_t* in, size_t n, uint32_t* out);
 
+/* Raw-limb access to the fully reduced carry-chain field Fp<P> (openzl_amd/csrc/zl_field.h: N words of 32 bits, R = 2^(32 N)) and to Fp2<P> over it
+ * (zl_curve.h, Fq[u] / (u^2 + 1)).  No conversion and no reduction happens on the way in: the caller places operands anywhere in N words, at or above p included.
+ * field: 0 BLS12-381 Fr (N = 8)  1 BLS12-381 Fq (N = 12)  2 BN254 Fr (N = 8)  3 BN254 Fq (N = 8)
+ * form:  the multiplier under every op that multiplies:  0 zl::mul / zl::sqr as the hook's unit builds them (device: the out-of-line call, host: the
+ *        64-bit-limb loop)  1 mul_impl directly (device: the product scan inlined, as the Poseidon, NTT and G1 units compile it)  2 the portable 32-bit loop mul_body
+ * in:    n records of four operands a, b, c, d x N words; out: n x N words (predicates: 0 / 1 in word 0, the other words 0), Fp2 ops n x 2 N words
+ * op:    0 mul(a,b)  1 sqr(a)  2 add(a,b)  3 sub(a,b)  4 dbl(a)  5 neg(a)  6 to_mont(a)  7 from_mont(a)  8 inv(a)  9 a.is_zero()  10 a == b
+ *        11 reduce_once(a) (a < 2p)  12 from_u64(a.l[0] | a.l[1] << 32)
+ *        Fp2, fields 1 and 3 only, x = (a, b), y = (c, d):  20 mul(x,y)  21 sqr(x)  22 inv(x)  23 add(x,y)  24 sub(x,y)  25 neg(x)  26 to_mont(x)  27 from_mont(x)
+ * ctx == NULL runs the host code, otherwise one lane per record in blocks of 64.  ZL_EINVAL: an unknown field, form or op, an Fp2 op on a scalar field, a null
+ * pointer with n > 0, n >= 2^24. */
+int zl_test_fp_op(zl_ctx* ctx, int field, int form, int op, const uint32_t* in, size_t n, uint32_t* out);
+
 /* Point formulas of zl_curve.h over that field.  group: ZL_G1 (coordinate = 14 words) or ZL_G2 (coordinate = 2 x 14 words);
  * hot != 0 selects, for G2, the flavour with inlined product scans that the bucket accumulation kernel uses.
  * in: n records of two XYZZ points p, q (x, y, zz, zzz each), raw limbs, zz == 0 encodes infinity; out: n XYZZ points.

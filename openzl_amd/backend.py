@@ -271,6 +271,7 @@ def load_library(path: Optional[str] = None):
     L.zl_test_poseidon_permute_dev.argtypes = [vp, C.c_int, u64p]
     L.zl_test_fp28_op.argtypes = [vp, C.c_int, u32p, C.c_size_t, u32p]
     L.zl_test_fp28_bn_op.argtypes = [vp, C.c_int, u32p, C.c_size_t, u32p]
+    L.zl_test_fp_op.argtypes = [vp, C.c_int, C.c_int, C.c_int, u32p, C.c_size_t, u32p]
     L.zl_test_pairing_product.argtypes = [C.c_int, C.c_size_t, u64p, u64p, u64p]
     L.zl_test_miller_dev.argtypes = [vp, C.c_int, C.c_size_t, u64p, u64p, u64p]
     L.zl_test_pairing_product_scaled.argtypes = [vp, C.c_int, C.c_size_t, u64p, u64p, u64p, u64p]
@@ -1089,7 +1090,7 @@ TEST_ABI_SYMBOLS = ["zl_test_poseidon_permute_dev", "zl_test_fp28_op", "zl_test_
                     "zl_test_miller_dev", "zl_test_final_exp", "zl_test_verify_batch_host", "zl_test_ntt_plan", "zl_test_ntt_fit_beside", "zl_test_fp2pair_op", "zl_test_point_form_op",
                     "zl_test_endo_split", "zl_test_endo_split_inf", "zl_test_decode_points_host", "zl_test_fq2_sqrt",
                     "zl_test_final_exp_dev", "zl_test_fq12_inverse", "zl_test_fq12_zeta", "zl_test_pairing_product_scaled",
-                    "zl_test_msm_plan", "zl_test_msm_batch_form", "zl_test_msm_exact_cover"]
+                    "zl_test_msm_plan", "zl_test_msm_batch_form", "zl_test_msm_exact_cover", "zl_test_fp_op"]
 
 
 def _p32(a: np.ndarray):
@@ -1401,6 +1402,27 @@ def hook_fr28_op(be: Optional["Backend"], curve: int, op: int, ab: np.ndarray, j
     rc = fn(be._ctx if be is not None else None, curve, op, j, _p32(a), n, _p32(out))
     if rc:
         raise BackendError(rc, "zl_test_fr28_op" if bits == 28 else "zl_test_fr29_op")
+    return out
+
+
+FP_FIELD_WORDS = {0: 8, 1: 12, 2: 8, 3: 8}  # zl_test_fp_op: BLS12-381 Fr, BLS12-381 Fq, BN254 Fr, BN254 Fq
+
+
+def hook_fp_op(be: Optional["Backend"], field: int, form: int, op: int, abcd: np.ndarray, n: Optional[int] = None, out: Optional[np.ndarray] = None) -> np.ndarray:
+    """the carry-chain field Fp<P> / Fp2<P> on raw words (zl_test_fp_op): abcd (n, 4, N) uint32 -> (n, N), or (n, 2 N) for the Fp2 ops (op >= 20);
+    form 0 zl::mul as the unit builds it, 1 mul_impl, 2 mul_body; be = None runs the host code.  n: the records to process (default all);
+    out: a caller's buffer of at least n rows, written in place (rows from n on are the caller's to inspect)"""
+    a = np.ascontiguousarray(abcd, dtype=np.uint32)
+    N = FP_FIELD_WORDS.get(field, 8)
+    n = a.shape[0] if n is None else n
+    assert a.ndim == 3 and a.shape[1:] == (4, N) and n <= a.shape[0]
+    W = 2 * N if op >= 20 else N
+    if out is None:
+        out = np.zeros((n, W), dtype=np.uint32)
+    assert out.dtype == np.uint32 and out.flags["C_CONTIGUOUS"] and out.shape[0] >= n and out.shape[1] == W
+    rc = load_library().zl_test_fp_op(be._ctx if be is not None else None, field, form, op, _p32(a), n, _p32(out))
+    if rc:
+        raise BackendError(rc, "zl_test_fp_op")
     return out
 
 

@@ -9,6 +9,7 @@
 // are written so that each inner step is exactly one such mad plus a 64-bit carry add.
 #pragma once
 #include <stdint.h>
+#include <type_traits>
 #if defined(__HIPCC__)
 #include <hip/hip_runtime.h>
 #define ZL_HD __host__ __device__ __forceinline__
@@ -137,8 +138,17 @@ ZL_HD Fp<P> negk(const Fp<P>& a) {
     return neg(a);
 }
 
-// Montgomery product a*b*R^-1 mod p, CIOS on 32-bit limbs.  All moduli have their top bit clear, so the
-// running value stays < 2p < 2^(32N) and no extra carry word is needed.
+// ---- THE MULTIPLIER'S CONTRACT (every form: mul_body, mul_host64, mul_dev; mul / sqr / mul_impl on top of them) ----------------------------------
+//   mul(a, b) is the fully reduced residue a b R^-1 mod p (R = 2^(32N)) whenever  a < p  and b is ANY N-word value.
+// The FIRST operand is the multiplicand of the CIOS loops below: their running value is T_i = (a (b mod 2^(32i)) + M_i p) / 2^(32i) with M_i < 2^(32i), so
+// T_i < a + p.  For a < p that is < 2p < 2^(32N) (all moduli have their top bit clear): N words hold it, and one conditional subtraction reduces the result.
+// For a >= p it can reach 2^(32N) and the top carry is lost -- whatever b is.  The device's product scan computes (a b + m p) / R < 2p when EITHER operand is
+// below p, but callers rely on the first-operand form only.  A product with both operands at or above p is outside the contract.
+// So a value nobody range-checked goes SECOND: to_mont(c) = mul(R^2, c), from_mont(a) = mul(1, a), and with them from_u64 and every load of a caller's
+// words (Engine::load_g1 / load_g2, load_canon64, FieldIO::load_canon, k_fr_to_mont, the blinding scalars) are exact for any N-word input: c is read as c mod p.
+// tests/test_fp_carry_chain_host.py and tests/test_gpu_fp_carry_chain.py hold every form to this against Python integers.
+//
+// Montgomery product a*b*R^-1 mod p, CIOS on 32-bit limbs; no extra carry word (a < p, see above).
 template <class P>
 ZL_HD Fp<P> mul_body(const Fp<P>& a, const Fp<P>& b) {
     constexpr int N = P::N;
@@ -147,7 +157,7 @@ ZL_HD Fp<P> mul_body(const Fp<P>& a, const Fp<P>& b) {
     for (int i = 0; i < N; i++) t[i] = 0;
 #pragma unroll
     for (int i = 0; i < N; i++) {
-        // invariant: T = sum t[j] 2^(32j) < 2p < 2^(32N)  (T_i = (a*(b mod 2^(32i)) + M_i*p) / 2^(32i), M_i < 2^(32i))
+        // invariant: T = sum t[j] 2^(32j) < a + p < 2p < 2^(32N) for the multiplicand a < p  (T_i = (a*(b mod 2^(32i)) + M_i*p) / 2^(32i), M_i < 2^(32i))
         uint64_t c = 0;
         const uint32_t bi = b.l[i];
 #pragma unroll
@@ -156,7 +166,7 @@ ZL_HD Fp<P> mul_body(const Fp<P>& a, const Fp<P>& b) {
             t[j] = (uint32_t)p;
             c = p >> 32;
         }
-        const uint32_t tn = (uint32_t)c;  // T + a*b_i < 2p + p*2^32: top word fits 32 bits
+        const uint32_t tn = (uint32_t)c;  // T + a*b_i < 2p + p*2^32 (a < p): top word fits 32 bits
         const uint32_t m = t[0] * P::INV;
         uint64_t p = (uint64_t)m * P::mod(0) + t[0];
         c = p >> 32;
@@ -166,7 +176,7 @@ ZL_HD Fp<P> mul_body(const Fp<P>& a, const Fp<P>& b) {
             t[j - 1] = (uint32_t)p;
             c = p >> 32;
         }
-        t[N - 1] = tn + (uint32_t)c;  // new T < 2p: no carry out
+        t[N - 1] = tn + (uint32_t)c;  // new T < a + p < 2p: no carry out (a >= p: the carry that is dropped here)
     }
     Fp<P> r;
 #pragma unroll
@@ -236,7 +246,7 @@ inline Fp<P> mul_host64(const Fp<P>& a, const Fp<P>& b) {
             t[j - 1] = (uint64_t)c;
             c >>= 64;
         }
-        t[M - 1] = tn + (uint64_t)c;  // < 2p: no carry out (top bit of every modulus is clear)
+        t[M - 1] = tn + (uint64_t)c;  // < x + p < 2p for the multiplicand x = a < p: no carry out (top bit of every modulus is clear)
     }
     Fp<P> r;
 #pragma unroll
@@ -284,8 +294,16 @@ ZL_NOINLINE_HD Fp<P> sqr_call12(uint32_t a0, uint32_t a1, uint32_t a2, uint32_t 
     a.l[0] = a0; a.l[1] = a1; a.l[2] = a2; a.l[3] = a3; a.l[4] = a4; a.l[5] = a5; a.l[6] = a6; a.l[7] = a7; a.l[8] = a8; a.l[9] = a9; a.l[10] = a10; a.l[11] = a11;
     return mul_impl(a, a);
 }
+// Which multiplier mul / sqr run on.  The product's parameter classes say nothing and get form 0, the choice of the unit's build below; a class that carries
+// MUL_FORM (the test hook zl_test_fp_op derives such classes) gets mul_impl (1) or mul_body (2) under everything built on mul: to_mont, inv, Fp2, ...
+template <class P, class = void> struct MulForm { static constexpr int value = 0; };
+template <class P> struct MulForm<P, std::void_t<decltype(P::MUL_FORM)>> { static constexpr int value = P::MUL_FORM; };
+
 template <class P>
 ZL_HD Fp<P> mul(const Fp<P>& a, const Fp<P>& b) {
+    if constexpr (MulForm<P>::value == 1) return mul_impl(a, b);
+    else if constexpr (MulForm<P>::value == 2) return mul_body(a, b);
+    else {
 #if !defined(__HIP_DEVICE_COMPILE__)
     return mul_impl(a, b);  // host: the 64-bit product inline (the out-of-line entry with its 16 scalar arguments exists for the device's register allocation)
 #elif !defined(ZL_INLINE_MUL) && !(defined(ZL_INLINE_MUL_DEVICE) && defined(__HIP_DEVICE_COMPILE__))
@@ -294,9 +312,13 @@ ZL_HD Fp<P> mul(const Fp<P>& a, const Fp<P>& b) {
 #else
     return mul_impl(a, b);
 #endif
+    }
 }
 template <class P>
 ZL_HD Fp<P> sqr(const Fp<P>& a) {
+    if constexpr (MulForm<P>::value == 1) return mul_impl(a, a);
+    else if constexpr (MulForm<P>::value == 2) return mul_body(a, a);
+    else {
 #if !defined(__HIP_DEVICE_COMPILE__)
     return mul_impl(a, a);
 #elif !defined(ZL_INLINE_MUL) && !(defined(ZL_INLINE_MUL_DEVICE) && defined(__HIP_DEVICE_COMPILE__))
@@ -305,17 +327,18 @@ ZL_HD Fp<P> sqr(const Fp<P>& a) {
 #else
     return mul_impl(a, a);
 #endif
+    }
 }
 
 template <class P>
 ZL_HD Fp<P> to_mont(const Fp<P>& canon) {
-    return mul(canon, Fp<P>::r2());
+    return mul(Fp<P>::r2(), canon);  // the caller's words go second: any N-word value, read as its residue (the multiplier's contract)
 }
 template <class P>
 ZL_HD Fp<P> from_mont(const Fp<P>& a) {
     Fp<P> o = Fp<P>::zero();
     o.l[0] = 1;
-    return mul(a, o);
+    return mul(o, a);
 }
 // a^e for a little-endian exponent of `nbits` bits held in 32-bit words
 template <class P>

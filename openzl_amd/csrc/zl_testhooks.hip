@@ -598,6 +598,82 @@ static int test_fp28_op_t(zl_ctx* ctx, int op, const uint32_t* in, size_t n, uin
         hipLaunchKernelGGL((k_test_fp28<F>), dim3((uint32_t)((n + 63) / 64)), dim3(64), 0, st, op, d_in, (uint32_t)n, d_out);
     });
 }
+// ------------------------------------------------------------------------------------------------ the carry-chain field (zl_field.h) and Fp2 over it (zl_curve.h)
+// One op on raw words: nothing is converted or reduced on the way in.  The multiplier under mul / sqr -- and so under to_mont, from_mont, inv and the Fp2 ops -- is
+// chosen by the parameter class: P itself (form 0: zl::mul as this unit builds it) or FpFormP<P, 1 / 2> (zl_field.h's MulForm: mul_impl / mul_body).
+template <class P, int FORM> struct FpFormP : P { static constexpr int MUL_FORM = FORM; };
+template <class P>
+ZL_HD static void fpc_op(int op, const uint32_t* in, uint32_t* out) {
+    constexpr int N = P::N;
+    using F = Fp<P>;
+    F a, b, c, d;
+    for (int i = 0; i < N; i++) { a.l[i] = in[i]; b.l[i] = in[N + i]; c.l[i] = in[2 * N + i]; d.l[i] = in[3 * N + i]; }
+    if (op >= 20) {
+        const Fp2<P> x{a, b}, y{c, d};
+        Fp2<P> r = Fp2<P>::zero();
+        switch (op) {
+        case 20: r = zl::mul(x, y); break;
+        case 21: r = zl::sqr(x); break;
+        case 22: r = zl::inv(x); break;
+        case 23: r = zl::add(x, y); break;
+        case 24: r = zl::sub(x, y); break;
+        case 25: r = zl::neg(x); break;
+        case 26: r = zl::to_mont(x); break;
+        case 27: r = zl::from_mont(x); break;
+        default: break;
+        }
+        for (int i = 0; i < N; i++) { out[i] = r.c0.l[i]; out[N + i] = r.c1.l[i]; }
+        return;
+    }
+    F r = F::zero();
+    switch (op) {
+    case 0: r = zl::mul(a, b); break;
+    case 1: r = zl::sqr(a); break;
+    case 2: r = zl::add(a, b); break;
+    case 3: r = zl::sub(a, b); break;
+    case 4: r = zl::dbl(a); break;
+    case 5: r = zl::neg(a); break;
+    case 6: r = zl::to_mont(a); break;
+    case 7: r = zl::from_mont(a); break;
+    case 8: r = zl::inv(a); break;
+    case 9: r.l[0] = a.is_zero() ? 1u : 0u; break;
+    case 10: r.l[0] = (a == b) ? 1u : 0u; break;
+    case 11: r = a; zl::reduce_once<P>(r.l); break;
+    case 12: r = zl::from_u64<P>((uint64_t)a.l[0] | ((uint64_t)a.l[1] << 32)); break;
+    default: break;
+    }
+    for (int i = 0; i < N; i++) out[i] = r.l[i];
+}
+template <class P>
+static __global__ void __launch_bounds__(64) k_test_fpc(int op, const uint32_t* __restrict__ in, uint32_t n, uint32_t out_words, uint32_t* __restrict__ out) {
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    fpc_op<P>(op, in + (size_t)i * 4 * P::N, out + (size_t)i * out_words);
+}
+template <class P>
+static int test_fpc_run(zl_ctx* ctx, int op, const uint32_t* in, size_t n, uint32_t* out) {
+    constexpr size_t N = P::N;
+    const size_t ow = op >= 20 ? 2 * N : N;
+    if (!ctx) {
+        for (size_t i = 0; i < n; i++) fpc_op<P>(op, in + i * 4 * N, out + i * ow);
+        return ZL_OK;
+    }
+    ZL_HIP(ctx, hipSetDevice(ctx->device));
+    // the word behind the device's output is cleared before the launch and must come back clear (run_dev_flag): record n would begin there
+    return run_dev_flag(ctx, in, n * 4 * N, out, n * ow, [&](const uint32_t* d_in, uint32_t* d_out, uint32_t*, hipStream_t st) {
+        hipLaunchKernelGGL((k_test_fpc<P>), dim3((uint32_t)((n + 63) / 64)), dim3(64), 0, st, op, d_in, (uint32_t)n, (uint32_t)ow, d_out);
+    });
+}
+template <class P>
+static int test_fpc_form(zl_ctx* ctx, int form, int op, const uint32_t* in, size_t n, uint32_t* out) {
+    switch (form) {
+    case 0: return test_fpc_run<P>(ctx, op, in, n, out);
+    case 1: return test_fpc_run<FpFormP<P, 1>>(ctx, op, in, n, out);
+    case 2: return test_fpc_run<FpFormP<P, 2>>(ctx, op, in, n, out);
+    default: return ZL_EINVAL;
+    }
+}
+
 // The split kernel of a group's plain MSM, alone: what MsmJob::sort launches in front of the recoder (zl_msm_job.h), on the ctx's stream.
 template <class G>
 static int endo_split_run(zl_ctx* ctx, const uint64_t* scalars, const uint8_t* inf, size_t n, uint32_t* out, int* endo_k, int* part_bits) {
@@ -662,6 +738,20 @@ int zl_test_poseidon_permute_dev28r(zl_ctx* ctx, zl_curve_t curve, uint64_t* sta
 
 int zl_test_fp28_op(zl_ctx* ctx, int op, const uint32_t* in, size_t n, uint32_t* out) { return test_fp28_op_t<F28>(ctx, op, in, n, out); }
 int zl_test_fp28_bn_op(zl_ctx* ctx, int op, const uint32_t* in, size_t n, uint32_t* out) { return test_fp28_op_t<BnG1::F>(ctx, op, in, n, out); }
+
+int zl_test_fp_op(zl_ctx* ctx, int field, int form, int op, const uint32_t* in, size_t n, uint32_t* out) {
+    if ((!in || !out) && n) return ZL_EINVAL;
+    const bool fp2 = op >= 20 && op <= 27;
+    if (field < 0 || field > 3 || form < 0 || form > 2 || !((op >= 0 && op <= 12) || fp2) || n >= (1u << 24)) return ZL_EINVAL;
+    if (fp2 && field != 1 && field != 3) return ZL_EINVAL;  // Fp2 exists over the base fields
+    if (!n) return ZL_OK;
+    switch (field) {
+    case 0: return test_fpc_form<BLS12_381_Fr>(ctx, form, op, in, n, out);
+    case 1: return test_fpc_form<BLS12_381_Fq>(ctx, form, op, in, n, out);
+    case 2: return test_fpc_form<BN254_Fr>(ctx, form, op, in, n, out);
+    default: return test_fpc_form<BN254_Fq>(ctx, form, op, in, n, out);
+    }
+}
 
 int zl_test_point_op(zl_ctx* ctx, zl_group_t group, int hot, int op, const uint32_t* in, size_t n, uint32_t* out) {
     if ((!in || !out) && n) return ZL_EINVAL;
