@@ -23,22 +23,14 @@ constexpr Spec spec_of_width(unsigned width) { return spec(width - 1); }
 static_assert(spec(2).width == 3 && spec(2).rounds() == 63 && spec(2).tag == 3 && spec(3).width == 4 && spec(3).rounds() == 63 && spec(3).tag == 7 &&
                   spec(4).width == 5 && spec(4).rounds() == 64 && spec(4).tag == 15 && spec(5).width == 6 && spec(5).rounds() == 64 && spec(5).tag == 31,
               "the reference's Spec table");
-// the device table of one (curve, width), in the entry format below: W * rounds round keys [W * round + lane], W * W MDS entries [W * row + column], the tag
+// the device table of one (curve, width): W * rounds round keys [W * round + lane], W * W MDS entries [W * row + column], the tag; entries of TAB_WORDS u32
+// slots holding the nine 29-bit limbs of x R' mod r (R' = 2^261: the device multiplier's own Montgomery form).  Width 3: 189 keys, 9 MDS entries, the tag 3.
 constexpr int tab_keys(unsigned) { return 0; }
 constexpr int tab_mds(unsigned width) { return (int)spec_of_width(width).keys(); }
 constexpr int tab_tag(unsigned width) { return tab_mds(width) + (int)(width * width); }
 constexpr int tab_entries(unsigned width) { return tab_tag(width) + 1; }
-
-constexpr int WIDTH = 3, FULL_ROUNDS = 8, PARTIAL_ROUNDS = 55, ROUNDS = FULL_ROUNDS + PARTIAL_ROUNDS;
-static_assert(spec(2).width == WIDTH && spec(2).full_rounds == FULL_ROUNDS && spec(2).partial_rounds == PARTIAL_ROUNDS, "the width-3 unit is the table's arity-2 row");
-// the device table of one curve: entries of TAB_WORDS u32 slots holding the nine 29-bit limbs of x R' mod r (R' = 2^261: the device multiplier's own Montgomery form)
-constexpr int TAB_KEYS = 0;                     // 189 round keys, [3 * round + lane]
-constexpr int TAB_MDS = WIDTH * ROUNDS;         // 9 MDS entries, [3 * row + column]
-constexpr int TAB_TAG = TAB_MDS + WIDTH * WIDTH;  // the arity-2 domain tag 3
-constexpr int TAB_ENTRIES = TAB_TAG + 1;
+static_assert(tab_entries(3) == 199, "the width-3 table");
 constexpr int TAB_WORDS = 10;
-constexpr size_t TAB_BYTES = (size_t)TAB_ENTRIES * TAB_WORDS * 4;
-static_assert(tab_mds(3) == TAB_MDS && tab_tag(3) == TAB_TAG && tab_entries(3) == TAB_ENTRIES, "one layout rule at every width");
 constexpr size_t tab_bytes(unsigned width) { return (size_t)tab_entries(width) * TAB_WORDS * 4; }
 
 constexpr unsigned MAX_DEPTH = 40;
@@ -51,9 +43,11 @@ constexpr int DEFAULT_CHUNK = 1 << 20, DEFAULT_TAIL = 256, DEFAULT_DEV_MIN = 64;
 constexpr size_t STAGE_BUDGET = (size_t)256 << 20;  // bytes of ZL_SLOT_POSEIDON one staged chunk may take
 constexpr size_t FLAG_BYTES = 256;                  // the flag word's corner of the slot
 
-// the chain circuit's assignment (zl_poseidon_chain_assignments): 1, h_k, x0, x1, then per link x^2, x^4, x^5 of its 79 S-boxes less the constant one
-constexpr int TRACE_PER_LINK = 3 * (FULL_ROUNDS * WIDTH + PARTIAL_ROUNDS - 1);
-static_assert(TRACE_PER_LINK == 234, "78 recorded S-boxes per link");
+// what a hash records at an arity: x^2, x^4, x^5 of its 8 W + partial S-boxes less the constant one
+constexpr size_t trace_per_hash(unsigned arity) { return 3 * (size_t)(spec(arity).full_rounds * spec(arity).width + spec(arity).partial_rounds - 1); }
+static_assert(trace_per_hash(2) == 234 && trace_per_hash(3) == 258 && trace_per_hash(4) == 285 && trace_per_hash(5) == 309, "78, 86, 95, 103 recorded S-boxes");
+// the chain circuit's assignment (zl_poseidon_chain_assignments): 1, h_k, x0, x1, then per link the records of its arity-2 hash
+constexpr int TRACE_PER_LINK = (int)trace_per_hash(2);
 
 // the membership circuit's assignment (zl_poseidon_merkle_assignments): 1, root, leaf, then per level sibling, index bit, left, right and the 234 records of
 // H(left, right)
@@ -61,11 +55,8 @@ constexpr int MERKLE_PER_LEVEL = 4 + TRACE_PER_LINK;
 constexpr size_t merkle_row_elems(unsigned depth) { return 3 + (size_t)MERKLE_PER_LEVEL * depth; }
 static_assert(merkle_row_elems(1) == 241 && (merkle_row_elems(MAX_DEPTH) + MAX_DEPTH + 3) * 32 < STAGE_BUDGET, "a row and its inputs fit one staged chunk at every depth");
 
-// the hash circuit's assignment at an arity (zl_poseidon_hash_assignments): 1, digest, the inputs, then x^2, x^4, x^5 of the hash's 8 W + partial S-boxes less
-// the constant one; and the leaf-membership circuit's (zl_poseidon_merkle_leaf_assignments): 1, root, the preimage, the leaf hash's records, then the levels of
-// the membership circuit
-constexpr size_t trace_per_hash(unsigned arity) { return 3 * (size_t)(spec(arity).full_rounds * spec(arity).width + spec(arity).partial_rounds - 1); }
-static_assert(trace_per_hash(2) == TRACE_PER_LINK && trace_per_hash(3) == 258 && trace_per_hash(4) == 285 && trace_per_hash(5) == 309, "78, 86, 95, 103 recorded S-boxes");
+// the hash circuit's assignment at an arity (zl_poseidon_hash_assignments): 1, digest, the inputs, then the hash's records; and the leaf-membership circuit's
+// (zl_poseidon_merkle_leaf_assignments): 1, root, the preimage, the leaf hash's records, then the levels of the membership circuit
 constexpr size_t hash_row_elems(unsigned arity) { return 2 + arity + trace_per_hash(arity); }
 constexpr size_t leaf_row_elems(unsigned arity, unsigned depth) { return hash_row_elems(arity) + (size_t)MERKLE_PER_LEVEL * depth; }
 static_assert(hash_row_elems(2) == 4 + TRACE_PER_LINK, "at arity 2 the hash row is the row of a one-link chain");

@@ -1,12 +1,13 @@
-// zl_poseidon_dev.hip -- batched Poseidon on the device (include/zl_backend_ext.h): many width-3 permutations, arity-2 hashes, hash chains
-// and Merkle trees per call, one lane per permutation, with a host path (the host mirror's permute_native over the library's thread pool) behind the same
-// entry points.  One unit for both scalar fields; built with the multiplier inlined (ZL_INLINE_MUL_DEVICE).
+// zl_poseidon_dev.hip -- batched Poseidon on the device (include/zl_backend_ext.h): many permutations and hashes (widths 3..6), arity-2 hash
+// chains and Merkle trees per call, one lane per permutation, with a host path (the host mirror's permute_native over the library's thread pool) behind the same
+// entry points.  One unit for both scalar fields; built with the multiplier inlined (ZL_INLINE_MUL_DEVICE).  Every staged or chunked call goes through ONE
+// runner, run_chunks (segments, upload, one launch per chunk, download, the flag read once); the width-3 entry points are the width-general ones at W = 3.
 //
 // Kernels (all templates over the scalar-field parameters FrP):
-//   k_pos_permute / k_pos_hash2 / k_pos_chain / k_pos_fold / k_pos_level   one lane per permutation (chain and fold: per chain / path, the dependent hashes in a
-//                    loop inside the lane).  Thin wrappers around ONE __device__ permutation, permute_dev: the three state elements stay in registers for
-//                    all 63 rounds; round keys, MDS entries and the domain tag come from a 199-entry device table (zl_poseidon_dev.h) at wave-uniform
-//                    addresses -- the compiler reads them with uniform loads -- already in the multiplier's Montgomery form (x R', R' = 2^261).
+//   k_pos_chain / k_pos_fold / k_pos_level   one lane per chain / path / parent node (chain and fold: the dependent hashes in a loop inside the lane).  Thin
+//                    wrappers around ONE __device__ width-3 permutation, permute_dev: the three state elements stay in registers for all 63 rounds; round
+//                    keys, MDS entries and the domain tag come from a 199-entry device table (zl_poseidon_dev.h) at wave-uniform addresses -- the compiler
+//                    reads them with uniform loads -- already in the multiplier's Montgomery form (x R', R' = 2^261).
 //   k_pos_chain_trace  k_pos_chain that also WRITES what the lane computes on the way: the complete assignment of zl_circuit_poseidon_chain(curve, k, x0, x1)
 //                    -- 1, h_k, x0, x1, then x^2, x^4, x^5 of every S-box the circuit allocates -- as one row of canonical words per chain.
 //   k_pos_merkle_trace  k_pos_fold that writes the complete assignment of zl_circuit_poseidon_merkle(curve, depth, leaf, index, path) per path: 1, root, leaf,
@@ -19,9 +20,9 @@
 //                    An append places its leaves, then hashes per level the parents with a new leaf below them -- one lane each, ALL touched trees in one
 //                    launch, the lane's tree found by binary search in the level's prefix sums; no one-workgroup tail.  ForestSrc lets k_pos_merkle_trace
 //                    read memberships out of it.  With a null ctx the forest is its host mirror in host memory (host_forest_append).
-//   k_pos_permute_w / k_pos_hash_w   widths 4, 5, 6 (arity 3, 4, 5 of pd::spec): their own permutation permute_w<FrP, W> on W state registers and a table per
-//                    (curve, width); the S-box reduces its input weakly where the lazy bound requires it (the argument stands above WideBounds).  Width 3 keeps
-//                    the kernels above; the entry points of every arity forward to them at arity 2.
+//   k_pos_permute_w / k_pos_hash_w   the batched permutation and hash at every width of pd::spec (3..6: arity 2..5), one lane per permutation, through
+//                    permute_any<FrP, W>: width 3 is permute_dev, widths 4, 5, 6 their own permutation permute_w<FrP, W> on W state registers and a table
+//                    per (curve, width); there the S-box reduces its input weakly where the lazy bound requires it (the argument stands above WideBounds).
 //   k_pos_hash_trace / k_pos_leaf_merkle_trace   the assignments of the arity-general circuits (zl_circuit_poseidon_hash / _merkle_leaf), widths 3..6, one lane per
 //                    row: permute_w with a recorder writes the S-box records of the hash; the leaf-membership kernel then hands the digest -- reduced weakly
 //                    (HandOver) -- to `depth` width-3 levels laid out as k_pos_merkle_trace's.  Sources: explicit preimages and paths, or a tree's node array beside
@@ -39,6 +40,7 @@
 #include <string.h>
 #include <atomic>
 #include <functional>
+#include <initializer_list>
 #include <memory>
 #include <mutex>
 #include <new>
@@ -195,23 +197,24 @@ constexpr uint32_t SKIP0_HASH = 1u;
 __device__ __forceinline__ bool rec_lane(int rnd, uint32_t skip0, int lane) { return rnd != 0 || !((skip0 >> lane) & 1u); }
 template <class FrP, class Rec>
 __device__ __forceinline__ void permute_dev(const uint32_t* __restrict__ tab, El<FrP>& s0, El<FrP>& s1, El<FrP>& s2, Rec& rec, const uint32_t skip0 = SKIP0_HASH) {
-    constexpr int half = pd::FULL_ROUNDS / 2;
+    constexpr pd::Spec S = pd::spec(2);
+    constexpr int half = (int)S.full_rounds / 2, partial = (int)S.partial_rounds, rounds = (int)S.rounds();
 #pragma unroll 1
-    for (int rnd = 0; rnd < pd::ROUNDS; rnd++) {
-        s0 = zl::add(s0, tab_ld<FrP>(tab, pd::TAB_KEYS + 3 * rnd));
-        s1 = zl::add(s1, tab_ld<FrP>(tab, pd::TAB_KEYS + 3 * rnd + 1));
-        s2 = zl::add(s2, tab_ld<FrP>(tab, pd::TAB_KEYS + 3 * rnd + 2));
+    for (int rnd = 0; rnd < rounds; rnd++) {
+        s0 = zl::add(s0, tab_ld<FrP>(tab, pd::tab_keys(3) + 3 * rnd));
+        s1 = zl::add(s1, tab_ld<FrP>(tab, pd::tab_keys(3) + 3 * rnd + 1));
+        s2 = zl::add(s2, tab_ld<FrP>(tab, pd::tab_keys(3) + 3 * rnd + 2));
         sbox<FrP>(s0, rec, rec_lane(rnd, skip0, 0));
-        if (rnd < half || rnd >= half + pd::PARTIAL_ROUNDS) {
+        if (rnd < half || rnd >= half + partial) {
             sbox<FrP>(s1, rec, rec_lane(rnd, skip0, 1));
             sbox<FrP>(s2, rec, rec_lane(rnd, skip0, 2));
         }
         El<FrP> nx[3];
 #pragma unroll
         for (int i = 0; i < 3; i++) {
-            El<FrP> acc = zl::mul(tab_ld<FrP>(tab, pd::TAB_MDS + 3 * i), s0);
-            acc = zl::add(acc, zl::mul(tab_ld<FrP>(tab, pd::TAB_MDS + 3 * i + 1), s1));
-            nx[i] = zl::add(acc, zl::mul(tab_ld<FrP>(tab, pd::TAB_MDS + 3 * i + 2), s2));
+            El<FrP> acc = zl::mul(tab_ld<FrP>(tab, pd::tab_mds(3) + 3 * i), s0);
+            acc = zl::add(acc, zl::mul(tab_ld<FrP>(tab, pd::tab_mds(3) + 3 * i + 1), s1));
+            nx[i] = zl::add(acc, zl::mul(tab_ld<FrP>(tab, pd::tab_mds(3) + 3 * i + 2), s2));
         }
         s0 = nx[0];
         s1 = nx[1];
@@ -221,7 +224,7 @@ __device__ __forceinline__ void permute_dev(const uint32_t* __restrict__ tab, El
 // H(x, y) on Montgomery operands
 template <class FrP>
 __device__ __forceinline__ El<FrP> hash2_dev(const uint32_t* __restrict__ tab, const El<FrP>& x, const El<FrP>& y) {
-    El<FrP> s0 = tab_ld<FrP>(tab, pd::TAB_TAG), s1 = x, s2 = y;
+    El<FrP> s0 = tab_ld<FrP>(tab, pd::tab_tag(3)), s1 = x, s2 = y;
     NoRec none;
     permute_dev<FrP>(tab, s0, s1, s2, none);
     return s0;
@@ -230,33 +233,6 @@ __device__ __forceinline__ El<FrP> hash2_dev(const uint32_t* __restrict__ tab, c
 // ---------------------------------------------------------------------------------------------------------------- kernels
 constexpr int BLOCK = 64;
 
-template <class FrP>
-__global__ __launch_bounds__(BLOCK) void k_pos_permute(const uint32_t* __restrict__ tab, uint64_t* __restrict__ states, size_t n, uint32_t* __restrict__ flag) {
-    const size_t p = (size_t)blockIdx.x * BLOCK + threadIdx.x;
-    if (p >= n) return;
-    uint64_t* st = states + p * 12;
-    El<FrP> s0, s1, s2;
-    bool ok = dload<FrP>(st, s0);
-    ok &= dload<FrP>(st + 4, s1);
-    ok &= dload<FrP>(st + 8, s2);
-    if (!ok) atomicOr(flag, 1u);
-    NoRec none;
-    permute_dev<FrP>(tab, s0, s1, s2, none);
-    dstore<FrP>(st, s0);
-    dstore<FrP>(st + 4, s1);
-    dstore<FrP>(st + 8, s2);
-}
-template <class FrP>
-__global__ __launch_bounds__(BLOCK) void k_pos_hash2(const uint32_t* __restrict__ tab, const uint64_t* __restrict__ xy, size_t n, uint64_t* __restrict__ out,
-                                                     uint32_t* __restrict__ flag) {
-    const size_t p = (size_t)blockIdx.x * BLOCK + threadIdx.x;
-    if (p >= n) return;
-    El<FrP> x, y;
-    bool ok = dload<FrP>(xy + p * 8, x);
-    ok &= dload<FrP>(xy + p * 8 + 4, y);
-    if (!ok) atomicOr(flag, 1u);
-    dstore<FrP>(out + p * 4, hash2_dev<FrP>(tab, x, y));
-}
 template <class FrP>
 __global__ __launch_bounds__(BLOCK) void k_pos_chain(const uint32_t* __restrict__ tab, const uint64_t* __restrict__ x0, const uint64_t* __restrict__ x1, uint32_t k,
                                                      size_t n, uint64_t* __restrict__ out, uint32_t* __restrict__ flag) {
@@ -288,7 +264,7 @@ __global__ __launch_bounds__(BLOCK) void k_pos_chain_trace(const uint32_t* __res
     RowRec<FrP> rec{row + 16};
 #pragma unroll 1
     for (uint32_t j = 0; j < k; j++) {
-        El<FrP> s0 = tab_ld<FrP>(tab, pd::TAB_TAG), s2 = b;
+        El<FrP> s0 = tab_ld<FrP>(tab, pd::tab_tag(3)), s2 = b;
         permute_dev<FrP>(tab, s0, h, s2, rec);
         h = s0;
     }
@@ -460,7 +436,7 @@ __global__ __launch_bounds__(BLOCK) void k_pos_merkle_trace(const uint32_t* __re
         }
         const bool right = (idx >> k) & 1;
         copy16(lv + 4, right ? 1 : 0, 0, 0, 0);
-        El<FrP> s0 = tab_ld<FrP>(tab, pd::TAB_TAG), x, y;
+        El<FrP> s0 = tab_ld<FrP>(tab, pd::tab_tag(3)), x, y;
 #pragma unroll
         for (int w = 0; w < El<FrP>::L; w++) {
             x.l[w] = right ? sib.l[w] : cur.l[w];
@@ -590,15 +566,15 @@ struct WideBounds {
     static_assert(MAX_MUL <= P::MUL_BOUND, "a bound product above what mul takes: place a weak reduction");
     static_assert(KEYED <= 128, "wred (and canon) take a value below 128 r");
 };
-#define ZL_POS_WIDE_BOUNDS(FrP, W, reduce, max_mul) \
+#define ZL_POS_W_BOUNDS(FrP, W, reduce, max_mul) \
     static_assert(WideBounds<FrP, W>::REDUCE == reduce && WideBounds<FrP, W>::MAX_MUL == max_mul && WideBounds<FrP, W>::MAX_MUL <= LazyP<FrP>::P::MUL_BOUND, "bounds of " #FrP " at width " #W)
-ZL_POS_WIDE_BOUNDS(BLS12_381_Fr, 4, true, 20);   // keyed 10: 100 > 70, reduced; the largest product is the MDS's 2 * 10
-ZL_POS_WIDE_BOUNDS(BLS12_381_Fr, 5, true, 24);   // keyed 12: 144 > 70
-ZL_POS_WIDE_BOUNDS(BLS12_381_Fr, 6, true, 28);   // keyed 14: 196 > 70
-ZL_POS_WIDE_BOUNDS(BN254_Fr, 4, false, 100);     // 100 <= 169: no reduction
-ZL_POS_WIDE_BOUNDS(BN254_Fr, 5, false, 144);     // 144 <= 169: no reduction
-ZL_POS_WIDE_BOUNDS(BN254_Fr, 6, true, 28);       // 196 > 169, reduced
-#undef ZL_POS_WIDE_BOUNDS
+ZL_POS_W_BOUNDS(BLS12_381_Fr, 4, true, 20);   // keyed 10: 100 > 70, reduced; the largest product is the MDS's 2 * 10
+ZL_POS_W_BOUNDS(BLS12_381_Fr, 5, true, 24);   // keyed 12: 144 > 70
+ZL_POS_W_BOUNDS(BLS12_381_Fr, 6, true, 28);   // keyed 14: 196 > 70
+ZL_POS_W_BOUNDS(BN254_Fr, 4, false, 100);     // 100 <= 169: no reduction
+ZL_POS_W_BOUNDS(BN254_Fr, 5, false, 144);     // 144 <= 169: no reduction
+ZL_POS_W_BOUNDS(BN254_Fr, 6, true, 28);       // 196 > 169, reduced
+#undef ZL_POS_W_BOUNDS
 static_assert(!WideBounds<BLS12_381_Fr, 3>::REDUCE && !WideBounds<BN254_Fr, 3>::REDUCE && WideBounds<BLS12_381_Fr, 3>::MAX_MUL == 64,
               "the same rule gives the width-3 unit's argument: no reduction, 64");
 
@@ -650,6 +626,13 @@ __device__ __forceinline__ void permute_w(const uint32_t* __restrict__ tab, El<F
         for (int i = 0; i < W; i++) s[i] = nx[i];
     }
 }
+// the permutation of any width of the table: width 3 is the width-3 unit's own permute_dev (what k_pos_chain_trace and k_pos_merkle_trace run), the wider
+// ones permute_w
+template <class FrP, int W, class Rec>
+__device__ __forceinline__ void permute_any(const uint32_t* __restrict__ tab, El<FrP> (&s)[W], Rec& rec, const uint32_t skip0 = SKIP0_HASH) {
+    if constexpr (W == 3) permute_dev<FrP>(tab, s[0], s[1], s[2], rec, skip0);
+    else permute_w<FrP, W>(tab, s, rec, skip0);
+}
 // count x W elements, in place
 template <class FrP, int W>
 __global__ __launch_bounds__(BLOCK) void k_pos_permute_w(const uint32_t* __restrict__ tab, uint64_t* __restrict__ states, size_t n, uint32_t* __restrict__ flag) {
@@ -662,7 +645,7 @@ __global__ __launch_bounds__(BLOCK) void k_pos_permute_w(const uint32_t* __restr
     for (int i = 0; i < W; i++) ok &= dload<FrP>(st + 4 * i, s[i]);
     if (!ok) atomicOr(flag, 1u);
     NoRec none;
-    permute_w<FrP, W>(tab, s, none);
+    permute_any<FrP, W>(tab, s, none);
 #pragma unroll
     for (int i = 0; i < W; i++) dstore<FrP>(st + 4 * i, s[i]);
 }
@@ -680,15 +663,8 @@ __global__ __launch_bounds__(BLOCK) void k_pos_hash_w(const uint32_t* __restrict
     for (int i = 1; i < W; i++) ok &= dload<FrP>(x + 4 * (i - 1), s[i]);
     if (!ok) atomicOr(flag, 1u);
     NoRec none;
-    permute_w<FrP, W>(tab, s, none);
+    permute_any<FrP, W>(tab, s, none);
     dstore<FrP>(out + p * 4, s[0]);
-}
-// the recording permutation of any width of the table: width 3 is the width-3 unit's own permute_dev (what k_pos_chain_trace and k_pos_merkle_trace run), the
-// wider ones permute_w
-template <class FrP, int W, class Rec>
-__device__ __forceinline__ void permute_any(const uint32_t* __restrict__ tab, El<FrP> (&s)[W], Rec& rec, const uint32_t skip0 = SKIP0_HASH) {
-    if constexpr (W == 3) permute_dev<FrP>(tab, s[0], s[1], s[2], rec, skip0);
-    else permute_w<FrP, W>(tab, s, rec, skip0);
 }
 // k_pos_hash_w with the witness written out: the complete assignment of zl_circuit_poseidon_hash(curve, W - 1, in) per item, one lane each.  Row p = out +
 // p * stride elements (16-byte aligned): [0] = 1, [1] = the digest, [2 .. W + 1) the inputs, then the 3 (8 W + partial - 1) records of the hash; elements
@@ -815,7 +791,7 @@ __global__ __launch_bounds__(BLOCK) void k_pos_leaf_merkle_trace(const uint32_t*
         }
         const bool right = (idx >> k) & 1;
         copy16(lv + 4, right ? 1 : 0, 0, 0, 0);
-        El<FrP> s0 = tab_ld<FrP>(tab3, pd::TAB_TAG), x, y;
+        El<FrP> s0 = tab_ld<FrP>(tab3, pd::tab_tag(3)), x, y;
 #pragma unroll
         for (int w = 0; w < El<FrP>::L; w++) {
             x.l[w] = right ? sib.l[w] : cur.l[w];
@@ -1102,27 +1078,10 @@ bool host_for(size_t n, const Fn& f) {
     zl_pool_get().parallel_for((n + B - 1) / B, g);
     return bad.load() == 0;
 }
-template <class FrP>
-int host_permute(uint64_t* states, size_t count) {
-    consts<FrP>();  // (built before the pool's threads ask for it)
-    return host_for(count, [&](size_t i) {
-        Fp<FrP> st[3];
-        bool ok = true;
-        for (int e = 0; e < 3; e++) ok &= load_canon<FrP>(states + i * 12 + 4 * e, st[e]);
-        poseidon::permute_native(consts<FrP>(), st);
-        for (int e = 0; e < 3; e++) store_canon<FrP>(states + i * 12 + 4 * e, st[e]);
-        return ok;
-    }) ? ZL_OK : ZL_EINVAL;
-}
-template <class FrP>
-int host_hash2_batch(const uint64_t* xy, size_t count, uint64_t* out) {
-    consts<FrP>();
-    return host_for(count, [&](size_t i) { return host_hash2<FrP>(xy + i * 8, xy + i * 8 + 4, out + i * 4); }) ? ZL_OK : ZL_EINVAL;
-}
-// widths 4..6: the host mirror's generic permute_native on the constants of the width
+// the batched permutation and hash at width W: the host mirror's permute_native on the constants of the width
 template <class FrP, int W>
 int host_permute_w(uint64_t* states, size_t count) {
-    consts<FrP, W>();
+    consts<FrP, W>();  // (built before the pool's threads ask for it)
     return host_for(count, [&](size_t i) {
         Fp<FrP> st[W];
         bool ok = true;
@@ -1157,7 +1116,7 @@ int host_permute_one(uint64_t* state) {
     for (int i = 0; i < W; i++) store_canon<FrP>(state + 4 * i, st[i]);
     return ZL_OK;
 }
-template <class FrP, int W = 3>
+template <class FrP, int W>
 int constants_out(uint64_t* keys, uint64_t* mds) {
     const poseidon::Constants<FrP, W>& c = consts<FrP, W>();
     if (keys)
@@ -1523,222 +1482,135 @@ int finish(zl_ctx* ctx, const uint32_t* d_flag) {
         ZL_HIP(ctx, hipGetLastError());                                            \
     } while (0)
 
-template <class FrP>
-int dev_permute(zl_ctx* ctx, uint64_t* states, size_t count) {
-    const uint32_t* tab;
-    int rc = get_table<FrP>(ctx, &tab);
-    if (rc) return rc;
-    const size_t chunk = stage_items(96);
+// ---- the one staged-chunk runner: stage, chunk, upload, launch, download, finish.
+// A staged segment of a call: `per` bytes per item, dense; item i of a chunk starting at `first` is up / down + (first + i) * per on the host.  per == 0: the
+// segment is absent -- it takes no space and its device pointer is null, which is what the kernels' optional parameters (pub, tags, cts) expect.
+struct Seg {
+    size_t per;
+    const void* up;  // host source, uploaded before the chunk's launch (may be null)
+    void* down;      // host destination, downloaded behind it (may be null)
+};
+constexpr size_t MAX_SEGS = 6;
+uint64_t* u64(void* p) { return static_cast<uint64_t*>(p); }
+// Runs `count` items in chunks on ctx's stream and returns when they have finished (finish).  The chunk is the launch chunk, cut to the slot's byte budget by
+// the bytes per item of the PRESENT segments (nothing staged: the launch chunk itself), so a chunk is never more than one launch.  Segment j lies at a 256-byte
+// boundary of ONE stage_get; the flag word is cleared once, there, and read once, at the end.  Per chunk, in stream order: the uploads, then
+// launch(first, m, d, flag) -- d[j] the device pointer of segment j, items first .. first + m - 1 of the call -- then the downloads.  A HIP error, or a non-zero
+// return of `launch`, ends the call at that point.
+// (Only present segments are charged.  The trace runners used to charge the 32 bytes of their optional public output whether it was asked for or not; without it
+// a chunk may now be larger where the byte budget is the limit -- m0 * per <= STAGE_BUDGET holds as before.)
+// Not through this runner: launch_merkle and the forest append (not this loop), and the two gathers dev_paths / dev_forest_paths, which raise no flag and end
+// on a plain stream synchronise -- finish's read of the flag word cost them 20 us on calls of 33 - 54 us when they were tried here
+// (profiles/poseidon_refactor_ab.log).
+template <class Launch>
+int run_chunks(zl_ctx* ctx, size_t count, std::initializer_list<Seg> segs, const Launch& launch) {
+    if (segs.size() > MAX_SEGS) return ZL_EINVAL;
+    size_t per = 0;
+    for (const Seg& g : segs) per += g.per;
+    const size_t chunk = per ? stage_items(per) : tune_chunk(), m0 = count < chunk ? count : chunk;
+    size_t off[MAX_SEGS + 1] = {0}, ns = 0;
+    for (const Seg& g : segs) {
+        off[ns + 1] = off[ns] + up256(m0 * g.per);
+        ns++;
+    }
     Stage s;
-    if ((rc = stage_get(ctx, (count < chunk ? count : chunk) * 96, &s))) return rc;
-    uint64_t* d = reinterpret_cast<uint64_t*>(s.data);
+    int rc = stage_get(ctx, off[ns], &s);
+    if (rc) return rc;
+    void* d[MAX_SEGS] = {};
+    const Seg* sg = segs.begin();
+    for (size_t j = 0; j < ns; j++) d[j] = sg[j].per ? s.data + off[j] : nullptr;
     for (size_t first = 0; first < count; first += chunk) {
         const size_t m = count - first < chunk ? count - first : chunk;
-        ZL_HIP(ctx, hipMemcpyAsync(d, states + first * 12, m * 96, hipMemcpyHostToDevice, ctx->stream));
-        ZL_POS_LAUNCH(ctx, (k_pos_permute<FrP>), blocks_of(m), BLOCK, 0, tab, d, m, s.flag);
-        ZL_HIP(ctx, hipMemcpyAsync(states + first * 12, d, m * 96, hipMemcpyDeviceToHost, ctx->stream));
+        for (size_t j = 0; j < ns; j++)
+            if (sg[j].per && sg[j].up)
+                ZL_HIP(ctx, hipMemcpyAsync(d[j], static_cast<const unsigned char*>(sg[j].up) + first * sg[j].per, m * sg[j].per, hipMemcpyHostToDevice, ctx->stream));
+        if ((rc = launch(first, m, d, s.flag))) return rc;
+        for (size_t j = 0; j < ns; j++)
+            if (sg[j].per && sg[j].down)
+                ZL_HIP(ctx, hipMemcpyAsync(static_cast<unsigned char*>(sg[j].down) + first * sg[j].per, d[j], m * sg[j].per, hipMemcpyDeviceToHost, ctx->stream));
     }
     return finish(ctx, s.flag);
 }
-// device operands, launches of at most one chunk
-template <class FrP>
-int launch_hash2(zl_ctx* ctx, const uint32_t* tab, const uint64_t* d_xy, size_t count, uint64_t* d_out, uint32_t* flag) {
-    const size_t chunk = tune_chunk();
-    for (size_t first = 0; first < count; first += chunk) {
-        const size_t m = count - first < chunk ? count - first : chunk;
-        ZL_POS_LAUNCH(ctx, (k_pos_hash2<FrP>), blocks_of(m), BLOCK, 0, tab, d_xy + first * 8, m, d_out + first * 4, flag);
-    }
-    return ZL_OK;
+// where a trace runner's chunk writes its rows: the staged segment (dense, nv elements apart) when the rows go to the host, else the caller's device rows
+struct Rows {
+    uint64_t* at;
+    size_t stride;
+};
+Rows rows_of(void* d_staged, size_t nv, uint64_t* d_rows, size_t stride, size_t first) {
+    return d_staged ? Rows{u64(d_staged), nv} : Rows{d_rows + first * stride * 4, stride};
 }
-template <class FrP>
-int dev_hash2_dev(zl_ctx* ctx, const void* d_xy, size_t count, void* d_out) {
-    const uint32_t* tab;
-    int rc = get_table<FrP>(ctx, &tab);
-    if (rc) return rc;
-    Stage s;
-    if ((rc = stage_get(ctx, 0, &s))) return rc;
-    if ((rc = launch_hash2<FrP>(ctx, tab, static_cast<const uint64_t*>(d_xy), count, static_cast<uint64_t*>(d_out), s.flag))) return rc;
-    return finish(ctx, s.flag);
-}
-template <class FrP>
-int dev_hash2(zl_ctx* ctx, const uint64_t* xy, size_t count, uint64_t* out) {
-    const uint32_t* tab;
-    int rc = get_table<FrP>(ctx, &tab);
-    if (rc) return rc;
-    const size_t chunk = stage_items(96), m0 = count < chunk ? count : chunk;
-    Stage s;
-    if ((rc = stage_get(ctx, up256(m0 * 64) + m0 * 32, &s))) return rc;
-    uint64_t* d_in = reinterpret_cast<uint64_t*>(s.data);
-    uint64_t* d_out = reinterpret_cast<uint64_t*>(s.data + up256(m0 * 64));
-    for (size_t first = 0; first < count; first += chunk) {
-        const size_t m = count - first < chunk ? count - first : chunk;
-        ZL_HIP(ctx, hipMemcpyAsync(d_in, xy + first * 8, m * 64, hipMemcpyHostToDevice, ctx->stream));
-        ZL_POS_LAUNCH(ctx, (k_pos_hash2<FrP>), blocks_of(m), BLOCK, 0, tab, d_in, m, d_out, s.flag);
-        ZL_HIP(ctx, hipMemcpyAsync(out + first * 4, d_out, m * 32, hipMemcpyDeviceToHost, ctx->stream));
-    }
-    return finish(ctx, s.flag);
-}
-// widths 4..6: the same staging with W (permute) resp. W - 1 + 1 (hash: inputs and digest) elements per item
+
+// the batched permutation and hash at width W: W resp. W - 1 + 1 (inputs and digest) elements per item
 template <class FrP, int W>
 int dev_permute_w(zl_ctx* ctx, uint64_t* states, size_t count) {
     const uint32_t* tab;
-    int rc = get_table<FrP, W>(ctx, &tab);
+    const int rc = get_table<FrP, W>(ctx, &tab);
     if (rc) return rc;
-    constexpr size_t per = 32 * W;
-    const size_t chunk = stage_items(per);
-    Stage s;
-    if ((rc = stage_get(ctx, (count < chunk ? count : chunk) * per, &s))) return rc;
-    uint64_t* d = reinterpret_cast<uint64_t*>(s.data);
-    for (size_t first = 0; first < count; first += chunk) {
-        const size_t m = count - first < chunk ? count - first : chunk;
-        ZL_HIP(ctx, hipMemcpyAsync(d, states + first * (4 * W), m * per, hipMemcpyHostToDevice, ctx->stream));
-        ZL_POS_LAUNCH(ctx, (k_pos_permute_w<FrP, W>), blocks_of(m), BLOCK, 0, tab, d, m, s.flag);
-        ZL_HIP(ctx, hipMemcpyAsync(states + first * (4 * W), d, m * per, hipMemcpyDeviceToHost, ctx->stream));
-    }
-    return finish(ctx, s.flag);
+    return run_chunks(ctx, count, {{32 * W, states, states}}, [&](size_t, size_t m, void* const* d, uint32_t* flag) {
+        ZL_POS_LAUNCH(ctx, (k_pos_permute_w<FrP, W>), blocks_of(m), BLOCK, 0, tab, u64(d[0]), m, flag);
+        return ZL_OK;
+    });
 }
 template <class FrP, int W>
 int dev_hash_w_dev(zl_ctx* ctx, const void* d_in, size_t count, void* d_out) {
     const uint32_t* tab;
-    int rc = get_table<FrP, W>(ctx, &tab);
+    const int rc = get_table<FrP, W>(ctx, &tab);
     if (rc) return rc;
-    Stage s;
-    if ((rc = stage_get(ctx, 0, &s))) return rc;
-    const size_t chunk = tune_chunk();
-    for (size_t first = 0; first < count; first += chunk) {
-        const size_t m = count - first < chunk ? count - first : chunk;
+    return run_chunks(ctx, count, {}, [&](size_t first, size_t m, void* const*, uint32_t* flag) {
         ZL_POS_LAUNCH(ctx, (k_pos_hash_w<FrP, W>), blocks_of(m), BLOCK, 0, tab, static_cast<const uint64_t*>(d_in) + first * (4 * (W - 1)), m,
-                      static_cast<uint64_t*>(d_out) + first * 4, s.flag);
-    }
-    return finish(ctx, s.flag);
+                      static_cast<uint64_t*>(d_out) + first * 4, flag);
+        return ZL_OK;
+    });
 }
 template <class FrP, int W>
 int dev_hash_w(zl_ctx* ctx, const uint64_t* in, size_t count, uint64_t* out) {
     const uint32_t* tab;
-    int rc = get_table<FrP, W>(ctx, &tab);
+    const int rc = get_table<FrP, W>(ctx, &tab);
     if (rc) return rc;
-    constexpr size_t in_per = 32 * (W - 1);
-    const size_t chunk = stage_items(in_per + 32), m0 = count < chunk ? count : chunk;
-    Stage s;
-    if ((rc = stage_get(ctx, up256(m0 * in_per) + m0 * 32, &s))) return rc;
-    uint64_t* d_in = reinterpret_cast<uint64_t*>(s.data);
-    uint64_t* d_out = reinterpret_cast<uint64_t*>(s.data + up256(m0 * in_per));
-    for (size_t first = 0; first < count; first += chunk) {
-        const size_t m = count - first < chunk ? count - first : chunk;
-        ZL_HIP(ctx, hipMemcpyAsync(d_in, in + first * (4 * (W - 1)), m * in_per, hipMemcpyHostToDevice, ctx->stream));
-        ZL_POS_LAUNCH(ctx, (k_pos_hash_w<FrP, W>), blocks_of(m), BLOCK, 0, tab, d_in, m, d_out, s.flag);
-        ZL_HIP(ctx, hipMemcpyAsync(out + first * 4, d_out, m * 32, hipMemcpyDeviceToHost, ctx->stream));
-    }
-    return finish(ctx, s.flag);
+    return run_chunks(ctx, count, {{32 * (W - 1), in, nullptr}, {32, nullptr, out}}, [&](size_t, size_t m, void* const* d, uint32_t* flag) {
+        ZL_POS_LAUNCH(ctx, (k_pos_hash_w<FrP, W>), blocks_of(m), BLOCK, 0, tab, u64(d[0]), m, u64(d[1]), flag);
+        return ZL_OK;
+    });
 }
 template <class FrP>
 int dev_chain(zl_ctx* ctx, const uint64_t* x0, const uint64_t* x1, uint32_t k, size_t count, uint64_t* out) {
     const uint32_t* tab;
-    int rc = get_table<FrP>(ctx, &tab);
+    const int rc = get_table<FrP>(ctx, &tab);
     if (rc) return rc;
-    const size_t chunk = stage_items(96), m0 = count < chunk ? count : chunk, seg = up256(m0 * 32);
-    Stage s;
-    if ((rc = stage_get(ctx, 3 * seg, &s))) return rc;
-    uint64_t* d0 = reinterpret_cast<uint64_t*>(s.data);
-    uint64_t* d1 = reinterpret_cast<uint64_t*>(s.data + seg);
-    uint64_t* d_out = reinterpret_cast<uint64_t*>(s.data + 2 * seg);
-    for (size_t first = 0; first < count; first += chunk) {
-        const size_t m = count - first < chunk ? count - first : chunk;
-        ZL_HIP(ctx, hipMemcpyAsync(d0, x0 + first * 4, m * 32, hipMemcpyHostToDevice, ctx->stream));
-        ZL_HIP(ctx, hipMemcpyAsync(d1, x1 + first * 4, m * 32, hipMemcpyHostToDevice, ctx->stream));
-        ZL_POS_LAUNCH(ctx, (k_pos_chain<FrP>), blocks_of(m), BLOCK, 0, tab, d0, d1, k, m, d_out, s.flag);
-        ZL_HIP(ctx, hipMemcpyAsync(out + first * 4, d_out, m * 32, hipMemcpyDeviceToHost, ctx->stream));
-    }
-    return finish(ctx, s.flag);
+    return run_chunks(ctx, count, {{32, x0, nullptr}, {32, x1, nullptr}, {32, nullptr, out}}, [&](size_t, size_t m, void* const* d, uint32_t* flag) {
+        ZL_POS_LAUNCH(ctx, (k_pos_chain<FrP>), blocks_of(m), BLOCK, 0, tab, u64(d[0]), u64(d[1]), k, m, u64(d[2]), flag);
+        return ZL_OK;
+    });
 }
-// device operands, launches of at most one chunk: row i at d_out + i * stride elements, h_k of chain i also at d_pub + i when d_pub is not null
+// Every form of the chain trace.  x0, x1: staged per chunk when in_on_host, else device memory; host_rows != null: the rows (nv = 4 + 234 k elements) are
+// staged, dense, and downloaded (d_rows and stride are ignored), otherwise row i goes to d_rows + i * stride elements; host_pub != null: h_k of every chain is
+// staged and downloaded.  A chunk is one launch.
 template <class FrP>
-int launch_trace(zl_ctx* ctx, const uint32_t* tab, const uint64_t* d_x0, const uint64_t* d_x1, uint32_t k, size_t count, uint64_t* d_out, size_t stride, uint64_t* d_pub,
-                 uint32_t* flag) {
-    const size_t chunk = tune_chunk();
-    for (size_t first = 0; first < count; first += chunk) {
-        const size_t m = count - first < chunk ? count - first : chunk;
-        uint64_t* pub = d_pub ? d_pub + first * 4 : nullptr;
-        ZL_POS_LAUNCH(ctx, (k_pos_chain_trace<FrP>), blocks_of(m), BLOCK, 0, tab, d_x0 + first * 4, d_x1 + first * 4, k, m, d_out + first * stride * 4, stride, pub, flag);
-    }
-    return ZL_OK;
-}
-template <class FrP>
-int dev_assignments_dev(zl_ctx* ctx, const void* d_x0, const void* d_x1, uint32_t k, size_t count, void* d_out, size_t stride) {
+int chain_trace_run(zl_ctx* ctx, const uint64_t* x0, const uint64_t* x1, bool in_on_host, uint32_t k, size_t count, uint64_t* d_rows, size_t stride, uint64_t* host_rows,
+                    uint64_t* host_pub) {
     const uint32_t* tab;
-    int rc = get_table<FrP>(ctx, &tab);
+    const int rc = get_table<FrP>(ctx, &tab);
     if (rc) return rc;
-    Stage s;
-    if ((rc = stage_get(ctx, 0, &s))) return rc;
-    if ((rc = launch_trace<FrP>(ctx, tab, static_cast<const uint64_t*>(d_x0), static_cast<const uint64_t*>(d_x1), k, count, static_cast<uint64_t*>(d_out), stride, nullptr,
-                                s.flag)))
-        return rc;
-    return finish(ctx, s.flag);
-}
-// host inputs, rows in DEVICE memory (the fused prover's chunk: zl_poseidon_dev.h), h_k of every chain to host_pub when it is not null
-template <class FrP>
-int dev_trace_rows(zl_ctx* ctx, const uint64_t* x0, const uint64_t* x1, uint32_t k, size_t count, uint64_t* d_rows, size_t stride, uint64_t* host_pub) {
-    const uint32_t* tab;
-    int rc = get_table<FrP>(ctx, &tab);
-    if (rc) return rc;
-    const size_t chunk = stage_items(96), m0 = count < chunk ? count : chunk, seg = up256(m0 * 32);
-    Stage s;
-    if ((rc = stage_get(ctx, 3 * seg, &s))) return rc;
-    uint64_t* d0 = reinterpret_cast<uint64_t*>(s.data);
-    uint64_t* d1 = reinterpret_cast<uint64_t*>(s.data + seg);
-    uint64_t* d_pub = host_pub ? reinterpret_cast<uint64_t*>(s.data + 2 * seg) : nullptr;
-    for (size_t first = 0; first < count; first += chunk) {
-        const size_t m = count - first < chunk ? count - first : chunk;
-        ZL_HIP(ctx, hipMemcpyAsync(d0, x0 + first * 4, m * 32, hipMemcpyHostToDevice, ctx->stream));
-        ZL_HIP(ctx, hipMemcpyAsync(d1, x1 + first * 4, m * 32, hipMemcpyHostToDevice, ctx->stream));
-        if ((rc = launch_trace<FrP>(ctx, tab, d0, d1, k, m, d_rows + first * stride * 4, stride, d_pub, s.flag))) return rc;
-        if (host_pub) ZL_HIP(ctx, hipMemcpyAsync(host_pub + first * 4, d_pub, m * 32, hipMemcpyDeviceToHost, ctx->stream));
-    }
-    return finish(ctx, s.flag);
-}
-template <class FrP>
-int dev_assignments(zl_ctx* ctx, const uint64_t* x0, const uint64_t* x1, uint32_t k, size_t count, uint64_t* out, size_t nv) {
-    const uint32_t* tab;
-    int rc = get_table<FrP>(ctx, &tab);
-    if (rc) return rc;
-    const size_t chunk = stage_items(64 + nv * 32), m0 = count < chunk ? count : chunk, seg = up256(m0 * 32);
-    Stage s;
-    if ((rc = stage_get(ctx, 2 * seg + m0 * nv * 32, &s))) return rc;
-    uint64_t* d0 = reinterpret_cast<uint64_t*>(s.data);
-    uint64_t* d1 = reinterpret_cast<uint64_t*>(s.data + seg);
-    uint64_t* d_out = reinterpret_cast<uint64_t*>(s.data + 2 * seg);
-    for (size_t first = 0; first < count; first += chunk) {
-        const size_t m = count - first < chunk ? count - first : chunk;
-        ZL_HIP(ctx, hipMemcpyAsync(d0, x0 + first * 4, m * 32, hipMemcpyHostToDevice, ctx->stream));
-        ZL_HIP(ctx, hipMemcpyAsync(d1, x1 + first * 4, m * 32, hipMemcpyHostToDevice, ctx->stream));
-        if ((rc = launch_trace<FrP>(ctx, tab, d0, d1, k, m, d_out, nv, nullptr, s.flag))) return rc;
-        ZL_HIP(ctx, hipMemcpyAsync(out + first * nv * 4, d_out, m * nv * 32, hipMemcpyDeviceToHost, ctx->stream));
-    }
-    return finish(ctx, s.flag);
+    const size_t nv = zl_poseidon_chain_assignment_elems(k), in_per = in_on_host ? 32 : 0;
+    return run_chunks(ctx, count, {{in_per, x0, nullptr}, {in_per, x1, nullptr}, {host_rows ? nv * 32 : 0, nullptr, host_rows}, {host_pub ? 32u : 0u, nullptr, host_pub}},
+                      [&](size_t first, size_t m, void* const* d, uint32_t* flag) {
+                          const uint64_t* a = in_on_host ? u64(d[0]) : x0 + first * 4;
+                          const uint64_t* b = in_on_host ? u64(d[1]) : x1 + first * 4;
+                          const Rows rows = rows_of(d[2], nv, d_rows, stride, first);
+                          ZL_POS_LAUNCH(ctx, (k_pos_chain_trace<FrP>), blocks_of(m), BLOCK, 0, tab, a, b, k, m, rows.at, rows.stride, u64(d[3]), flag);
+                          return ZL_OK;
+                      });
 }
 template <class FrP>
 int dev_fold(zl_ctx* ctx, const uint64_t* leaves, const uint64_t* indices, const uint64_t* paths, unsigned depth, size_t count, uint64_t* roots) {
     const uint32_t* tab;
-    int rc = get_table<FrP>(ctx, &tab);
+    const int rc = get_table<FrP>(ctx, &tab);
     if (rc) return rc;
-    const size_t per = 32 + 8 + (size_t)depth * 32 + 32;
-    const size_t chunk = stage_items(per), m0 = count < chunk ? count : chunk;
-    const size_t o_idx = up256(m0 * 32), o_path = o_idx + up256(m0 * 8), o_root = o_path + up256(m0 * depth * 32);
-    Stage s;
-    if ((rc = stage_get(ctx, o_root + m0 * 32, &s))) return rc;
-    uint64_t* d_leaf = reinterpret_cast<uint64_t*>(s.data);
-    uint64_t* d_idx = reinterpret_cast<uint64_t*>(s.data + o_idx);
-    uint64_t* d_path = reinterpret_cast<uint64_t*>(s.data + o_path);
-    uint64_t* d_root = reinterpret_cast<uint64_t*>(s.data + o_root);
-    for (size_t first = 0; first < count; first += chunk) {
-        const size_t m = count - first < chunk ? count - first : chunk;
-        ZL_HIP(ctx, hipMemcpyAsync(d_leaf, leaves + first * 4, m * 32, hipMemcpyHostToDevice, ctx->stream));
-        ZL_HIP(ctx, hipMemcpyAsync(d_idx, indices + first, m * 8, hipMemcpyHostToDevice, ctx->stream));
-        ZL_HIP(ctx, hipMemcpyAsync(d_path, paths + first * depth * 4, m * depth * 32, hipMemcpyHostToDevice, ctx->stream));
-        ZL_POS_LAUNCH(ctx, (k_pos_fold<FrP>), blocks_of(m), BLOCK, 0, tab, d_leaf, d_idx, d_path, depth, m, d_root, s.flag);
-        ZL_HIP(ctx, hipMemcpyAsync(roots + first * 4, d_root, m * 32, hipMemcpyDeviceToHost, ctx->stream));
-    }
-    return finish(ctx, s.flag);
+    return run_chunks(ctx, count, {{32, leaves, nullptr}, {8, indices, nullptr}, {(size_t)depth * 32, paths, nullptr}, {32, nullptr, roots}},
+                      [&](size_t, size_t m, void* const* d, uint32_t* flag) {
+                          ZL_POS_LAUNCH(ctx, (k_pos_fold<FrP>), blocks_of(m), BLOCK, 0, tab, u64(d[0]), u64(d[1]), u64(d[2]), depth, m, u64(d[3]), flag);
+                          return ZL_OK;
+                      });
 }
 // every level of the tree in device memory (n >= 1): wide launches per level while a level has more than T nodes, then the one-workgroup tail
 template <class FrP>
@@ -1836,43 +1708,27 @@ template <class FrP, class Src>
 int merkle_trace_run(zl_ctx* ctx, Src src, const HostPaths* hp, const uint64_t* indices, unsigned depth, size_t count, uint64_t* d_rows, size_t stride, uint64_t* host_rows,
                      uint64_t* host_pub, const uint32_t* trees = nullptr) {
     const uint32_t* tab;
-    int rc = get_table<FrP>(ctx, &tab);
+    const int rc = get_table<FrP>(ctx, &tab);
     if (rc) return rc;
     const size_t nv = pd::merkle_row_elems(depth);
-    constexpr bool forest = std::is_same<Src, ForestSrc>::value;  // `trees` (host memory): the tree of every item, staged behind everything else
-    const size_t per = 8 + 32 + (hp ? 32 + (size_t)depth * 32 : 0) + (host_rows ? nv * 32 : 0) + (forest ? 4 : 0);
-    const size_t chunk = stage_items(per), m0 = count < chunk ? count : chunk;
-    const size_t o_pub = up256(m0 * 8), o_leaf = o_pub + up256(m0 * 32), o_path = o_leaf + (hp ? up256(m0 * 32) : 0), o_rows = o_path + (hp ? up256(m0 * depth * 32) : 0);
-    const size_t o_tree = o_rows + (host_rows ? up256(m0 * nv * 32) : 0);
-    Stage s;
-    if ((rc = stage_get(ctx, forest ? o_tree + m0 * 4 : o_rows + (host_rows ? m0 * nv * 32 : 0), &s))) return rc;
-    uint64_t* d_idx = reinterpret_cast<uint64_t*>(s.data);
-    uint64_t* d_pub = host_pub ? reinterpret_cast<uint64_t*>(s.data + o_pub) : nullptr;
-    uint64_t* d_leaf = reinterpret_cast<uint64_t*>(s.data + o_leaf);
-    uint64_t* d_path = reinterpret_cast<uint64_t*>(s.data + o_path);
-    uint64_t* d_stage_rows = reinterpret_cast<uint64_t*>(s.data + o_rows);
-    for (size_t first = 0; first < count; first += chunk) {
-        const size_t m = count - first < chunk ? count - first : chunk;
-        ZL_HIP(ctx, hipMemcpyAsync(d_idx, indices + first, m * 8, hipMemcpyHostToDevice, ctx->stream));
-        Src from = src.advanced(first);
-        if constexpr (std::is_same<Src, PathSrc>::value) {
-            if (hp) {
-                ZL_HIP(ctx, hipMemcpyAsync(d_leaf, hp->leaves + first * 4, m * 32, hipMemcpyHostToDevice, ctx->stream));
-                ZL_HIP(ctx, hipMemcpyAsync(d_path, hp->paths + first * depth * 4, m * depth * 32, hipMemcpyHostToDevice, ctx->stream));
-                from = PathSrc{d_leaf, d_path, depth};
-            }
-        }
-        if constexpr (forest) {
-            uint32_t* d_tree = reinterpret_cast<uint32_t*>(s.data + o_tree);
-            ZL_HIP(ctx, hipMemcpyAsync(d_tree, trees + first, m * 4, hipMemcpyHostToDevice, ctx->stream));
-            from.tree_of = d_tree;
-        }
-        uint64_t* rows = host_rows ? d_stage_rows : d_rows + first * stride * 4;
-        ZL_POS_LAUNCH(ctx, (k_pos_merkle_trace<FrP, Src>), blocks_of(m), BLOCK, 0, tab, from, d_idx, depth, m, rows, host_rows ? nv : stride, d_pub, s.flag);
-        if (host_rows) ZL_HIP(ctx, hipMemcpyAsync(host_rows + first * nv * 4, d_stage_rows, m * nv * 32, hipMemcpyDeviceToHost, ctx->stream));
-        if (host_pub) ZL_HIP(ctx, hipMemcpyAsync(host_pub + first * 4, d_pub, m * 32, hipMemcpyDeviceToHost, ctx->stream));
-    }
-    return finish(ctx, s.flag);
+    constexpr bool forest = std::is_same<Src, ForestSrc>::value;  // `trees` (host memory): the tree of every item, staged too
+    return run_chunks(ctx, count,
+                      {{8, indices, nullptr},
+                       {hp ? 32u : 0u, hp ? hp->leaves : nullptr, nullptr},
+                       {hp ? (size_t)depth * 32 : 0, hp ? hp->paths : nullptr, nullptr},
+                       {forest ? 4u : 0u, trees, nullptr},
+                       {host_rows ? nv * 32 : 0, nullptr, host_rows},
+                       {host_pub ? 32u : 0u, nullptr, host_pub}},
+                      [&](size_t first, size_t m, void* const* d, uint32_t* flag) {
+                          Src from = src.advanced(first);
+                          if constexpr (std::is_same<Src, PathSrc>::value) {
+                              if (hp) from = PathSrc{u64(d[1]), u64(d[2]), depth};
+                          }
+                          if constexpr (forest) from.tree_of = static_cast<const uint32_t*>(d[3]);
+                          const Rows rows = rows_of(d[4], nv, d_rows, stride, first);
+                          ZL_POS_LAUNCH(ctx, (k_pos_merkle_trace<FrP, Src>), blocks_of(m), BLOCK, 0, tab, from, u64(d[0]), depth, m, rows.at, rows.stride, u64(d[5]), flag);
+                          return ZL_OK;
+                      });
 }
 template <class FrP>
 int dev_merkle_from_host(zl_ctx* ctx, const uint64_t* leaves, const uint64_t* indices, const uint64_t* paths, unsigned depth, size_t count, uint64_t* d_rows, size_t stride,
@@ -1896,30 +1752,16 @@ int dev_merkle_from_tree(zl_ctx* ctx, const void* d_nodes, size_t n, unsigned de
 template <class FrP, int W>
 int hash_trace_run(zl_ctx* ctx, const uint64_t* in, bool in_on_host, size_t count, uint64_t* d_rows, size_t stride, uint64_t* host_rows, uint64_t* host_pub) {
     const uint32_t* tab;
-    int rc = get_table<FrP, W>(ctx, &tab);
+    const int rc = get_table<FrP, W>(ctx, &tab);
     if (rc) return rc;
     constexpr size_t nv = pd::hash_row_elems(W - 1), in_per = 32 * (W - 1);
-    const size_t per = 32 + (in_on_host ? in_per : 0) + (host_rows ? nv * 32 : 0);
-    const size_t chunk = stage_items(per), m0 = count < chunk ? count : chunk;
-    const size_t o_in = up256(m0 * 32), o_rows = o_in + (in_on_host ? up256(m0 * in_per) : 0);
-    Stage s;
-    if ((rc = stage_get(ctx, o_rows + (host_rows ? m0 * nv * 32 : 0), &s))) return rc;
-    uint64_t* d_pub = host_pub ? reinterpret_cast<uint64_t*>(s.data) : nullptr;
-    uint64_t* d_in = reinterpret_cast<uint64_t*>(s.data + o_in);
-    uint64_t* d_stage_rows = reinterpret_cast<uint64_t*>(s.data + o_rows);
-    for (size_t first = 0; first < count; first += chunk) {
-        const size_t m = count - first < chunk ? count - first : chunk;
-        const uint64_t* from = in + first * (4 * (W - 1));
-        if (in_on_host) {
-            ZL_HIP(ctx, hipMemcpyAsync(d_in, from, m * in_per, hipMemcpyHostToDevice, ctx->stream));
-            from = d_in;
-        }
-        uint64_t* rows = host_rows ? d_stage_rows : d_rows + first * stride * 4;
-        ZL_POS_LAUNCH(ctx, (k_pos_hash_trace<FrP, W>), blocks_of(m), BLOCK, 0, tab, from, m, rows, host_rows ? nv : stride, d_pub, s.flag);
-        if (host_rows) ZL_HIP(ctx, hipMemcpyAsync(host_rows + first * nv * 4, d_stage_rows, m * nv * 32, hipMemcpyDeviceToHost, ctx->stream));
-        if (host_pub) ZL_HIP(ctx, hipMemcpyAsync(host_pub + first * 4, d_pub, m * 32, hipMemcpyDeviceToHost, ctx->stream));
-    }
-    return finish(ctx, s.flag);
+    return run_chunks(ctx, count, {{in_on_host ? in_per : 0, in, nullptr}, {host_rows ? nv * 32 : 0, nullptr, host_rows}, {host_pub ? 32u : 0u, nullptr, host_pub}},
+                      [&](size_t first, size_t m, void* const* d, uint32_t* flag) {
+                          const uint64_t* from = in_on_host ? u64(d[0]) : in + first * (4 * (W - 1));
+                          const Rows rows = rows_of(d[1], nv, d_rows, stride, first);
+                          ZL_POS_LAUNCH(ctx, (k_pos_hash_trace<FrP, W>), blocks_of(m), BLOCK, 0, tab, from, m, rows.at, rows.stride, u64(d[2]), flag);
+                          return ZL_OK;
+                      });
 }
 // Every form of the leaf-membership trace at width W, as merkle_trace_run: indices are host memory and staged per chunk; hp != null: preimages and paths
 // are HOST memory and staged beside them (Src is LeafPathSrc and `src` is ignored); host_rows / host_pub as in hash_trace_run.
@@ -1933,35 +1775,23 @@ int leaf_trace_run(zl_ctx* ctx, Src src, const HostLeafPaths* hp, const uint64_t
     const uint32_t *tab, *tab3;
     int rc = get_table<FrP, W>(ctx, &tab);
     if (rc || (rc = get_table<FrP>(ctx, &tab3))) return rc;
-    constexpr size_t pre_per = 32 * (W - 1);
     const size_t nv = pd::leaf_row_elems(W - 1, depth);
-    const size_t per = 8 + 32 + (hp ? pre_per + (size_t)depth * 32 : 0) + (host_rows ? nv * 32 : 0);
-    const size_t chunk = stage_items(per), m0 = count < chunk ? count : chunk;
-    const size_t o_pub = up256(m0 * 8), o_pre = o_pub + up256(m0 * 32), o_path = o_pre + (hp ? up256(m0 * pre_per) : 0), o_rows = o_path + (hp ? up256(m0 * depth * 32) : 0);
-    Stage s;
-    if ((rc = stage_get(ctx, o_rows + (host_rows ? m0 * nv * 32 : 0), &s))) return rc;
-    uint64_t* d_idx = reinterpret_cast<uint64_t*>(s.data);
-    uint64_t* d_pub = host_pub ? reinterpret_cast<uint64_t*>(s.data + o_pub) : nullptr;
-    uint64_t* d_pre = reinterpret_cast<uint64_t*>(s.data + o_pre);
-    uint64_t* d_path = reinterpret_cast<uint64_t*>(s.data + o_path);
-    uint64_t* d_stage_rows = reinterpret_cast<uint64_t*>(s.data + o_rows);
-    for (size_t first = 0; first < count; first += chunk) {
-        const size_t m = count - first < chunk ? count - first : chunk;
-        ZL_HIP(ctx, hipMemcpyAsync(d_idx, indices + first, m * 8, hipMemcpyHostToDevice, ctx->stream));
-        Src from = src.advanced(first, W - 1);
-        if constexpr (std::is_same<Src, LeafPathSrc>::value) {
-            if (hp) {
-                ZL_HIP(ctx, hipMemcpyAsync(d_pre, hp->preimages + first * (4 * (W - 1)), m * pre_per, hipMemcpyHostToDevice, ctx->stream));
-                ZL_HIP(ctx, hipMemcpyAsync(d_path, hp->paths + first * depth * 4, m * depth * 32, hipMemcpyHostToDevice, ctx->stream));
-                from = LeafPathSrc{d_pre, d_path, depth};
-            }
-        }
-        uint64_t* rows = host_rows ? d_stage_rows : d_rows + first * stride * 4;
-        ZL_POS_LAUNCH(ctx, (k_pos_leaf_merkle_trace<FrP, W, Src>), blocks_of(m), BLOCK, 0, tab, tab3, from, d_idx, depth, m, rows, host_rows ? nv : stride, d_pub, s.flag);
-        if (host_rows) ZL_HIP(ctx, hipMemcpyAsync(host_rows + first * nv * 4, d_stage_rows, m * nv * 32, hipMemcpyDeviceToHost, ctx->stream));
-        if (host_pub) ZL_HIP(ctx, hipMemcpyAsync(host_pub + first * 4, d_pub, m * 32, hipMemcpyDeviceToHost, ctx->stream));
-    }
-    return finish(ctx, s.flag);
+    return run_chunks(ctx, count,
+                      {{8, indices, nullptr},
+                       {hp ? 32u * (W - 1) : 0u, hp ? hp->preimages : nullptr, nullptr},
+                       {hp ? (size_t)depth * 32 : 0, hp ? hp->paths : nullptr, nullptr},
+                       {host_rows ? nv * 32 : 0, nullptr, host_rows},
+                       {host_pub ? 32u : 0u, nullptr, host_pub}},
+                      [&](size_t first, size_t m, void* const* d, uint32_t* flag) {
+                          Src from = src.advanced(first, W - 1);
+                          if constexpr (std::is_same<Src, LeafPathSrc>::value) {
+                              if (hp) from = LeafPathSrc{u64(d[1]), u64(d[2]), depth};
+                          }
+                          const Rows rows = rows_of(d[3], nv, d_rows, stride, first);
+                          ZL_POS_LAUNCH(ctx, (k_pos_leaf_merkle_trace<FrP, W, Src>), blocks_of(m), BLOCK, 0, tab, tab3, from, u64(d[0]), depth, m, rows.at, rows.stride, u64(d[4]),
+                                        flag);
+                          return ZL_OK;
+                      });
 }
 template <class FrP, int W>
 int dev_leaf_from_host(zl_ctx* ctx, const uint64_t* preimages, const uint64_t* indices, const uint64_t* paths, unsigned depth, size_t count, uint64_t* d_rows, size_t stride,
@@ -2156,50 +1986,32 @@ int launch_duplex(zl_ctx* ctx, const uint32_t* tab, const DuplexCall& c, const u
 template <class FrP, int W>
 int dev_duplex_dev(zl_ctx* ctx, const DuplexCall& c, const void* d_keys, const void* d_headers, const void* d_in, size_t count, void* d_out, void* d_tags, uint8_t* ok_each) {
     const uint32_t* tab;
-    int rc = get_table<FrP, W>(ctx, &tab);
+    const int rc = get_table<FrP, W>(ctx, &tab);
     if (rc) return rc;
-    const size_t chunk = tune_chunk(), T = c.N * (W - 1);
-    Stage s;
-    if ((rc = stage_get(ctx, c.decrypt ? (count < chunk ? count : chunk) : 0, &s))) return rc;
-    for (size_t first = 0; first < count; first += chunk) {
-        const size_t m = count - first < chunk ? count - first : chunk;
-        if ((rc = launch_duplex<FrP, W>(ctx, tab, c, static_cast<const uint64_t*>(d_keys) + first * c.K * 4, static_cast<const uint64_t*>(d_headers) + first * c.H * 4,
-                                        static_cast<const uint64_t*>(d_in) + first * T * 4, m, static_cast<uint64_t*>(d_out) + first * T * 4,
-                                        static_cast<uint64_t*>(d_tags) + first * 4, s.data, s.flag)))
-            return rc;
-        if (c.decrypt) ZL_HIP(ctx, hipMemcpyAsync(ok_each + first, s.data, m, hipMemcpyDeviceToHost, ctx->stream));
-    }
-    return finish(ctx, s.flag);
+    const size_t T = c.N * (W - 1);
+    return run_chunks(ctx, count, {{c.decrypt ? 1u : 0u, nullptr, ok_each}}, [&](size_t first, size_t m, void* const* d, uint32_t* flag) {
+        return launch_duplex<FrP, W>(ctx, tab, c, static_cast<const uint64_t*>(d_keys) + first * c.K * 4, static_cast<const uint64_t*>(d_headers) + first * c.H * 4,
+                                     static_cast<const uint64_t*>(d_in) + first * T * 4, m, static_cast<uint64_t*>(d_out) + first * T * 4,
+                                     static_cast<uint64_t*>(d_tags) + first * 4, static_cast<uint8_t*>(d[0]), flag);
+    });
 }
 // host operands: keys, headers, texts (in place in the staging area), tags and verdicts of a chunk side by side
 template <class FrP, int W>
 int dev_duplex(zl_ctx* ctx, const DuplexCall& c, const uint64_t* keys, const uint64_t* headers, const uint64_t* text_in, size_t count, uint64_t* text_out, uint64_t* tags,
                uint8_t* ok_each) {
     const uint32_t* tab;
-    int rc = get_table<FrP, W>(ctx, &tab);
+    const int rc = get_table<FrP, W>(ctx, &tab);
     if (rc) return rc;
-    const size_t T = c.N * (W - 1), per = (c.K + c.H + T + 1) * 32 + 1;
-    const size_t chunk = stage_items(per), m0 = count < chunk ? count : chunk;
-    const size_t o_hdr = up256(m0 * c.K * 32), o_text = o_hdr + up256(m0 * c.H * 32), o_tag = o_text + up256(m0 * T * 32), o_ok = o_tag + up256(m0 * 32);
-    Stage s;
-    if ((rc = stage_get(ctx, o_ok + m0, &s))) return rc;
-    uint64_t* d_key = reinterpret_cast<uint64_t*>(s.data);
-    uint64_t* d_hdr = reinterpret_cast<uint64_t*>(s.data + o_hdr);
-    uint64_t* d_text = reinterpret_cast<uint64_t*>(s.data + o_text);
-    uint64_t* d_tag = reinterpret_cast<uint64_t*>(s.data + o_tag);
-    uint8_t* d_ok = s.data + o_ok;
-    for (size_t first = 0; first < count; first += chunk) {
-        const size_t m = count - first < chunk ? count - first : chunk;
-        if (c.K) ZL_HIP(ctx, hipMemcpyAsync(d_key, keys + first * c.K * 4, m * c.K * 32, hipMemcpyHostToDevice, ctx->stream));
-        if (c.H) ZL_HIP(ctx, hipMemcpyAsync(d_hdr, headers + first * c.H * 4, m * c.H * 32, hipMemcpyHostToDevice, ctx->stream));
-        ZL_HIP(ctx, hipMemcpyAsync(d_text, text_in + first * T * 4, m * T * 32, hipMemcpyHostToDevice, ctx->stream));
-        if (c.decrypt) ZL_HIP(ctx, hipMemcpyAsync(d_tag, tags + first * 4, m * 32, hipMemcpyHostToDevice, ctx->stream));
-        if ((rc = launch_duplex<FrP, W>(ctx, tab, c, d_key, d_hdr, d_text, m, d_text, d_tag, d_ok, s.flag))) return rc;
-        ZL_HIP(ctx, hipMemcpyAsync(text_out + first * T * 4, d_text, m * T * 32, hipMemcpyDeviceToHost, ctx->stream));
-        if (c.decrypt) ZL_HIP(ctx, hipMemcpyAsync(ok_each + first, d_ok, m, hipMemcpyDeviceToHost, ctx->stream));
-        else ZL_HIP(ctx, hipMemcpyAsync(tags + first * 4, d_tag, m * 32, hipMemcpyDeviceToHost, ctx->stream));
-    }
-    return finish(ctx, s.flag);
+    const size_t T = c.N * (W - 1);
+    return run_chunks(ctx, count,
+                      {{c.K * 32, keys, nullptr},
+                       {c.H * 32, headers, nullptr},
+                       {T * 32, text_in, text_out},
+                       {32, c.decrypt ? tags : nullptr, c.decrypt ? nullptr : tags},
+                       {1, nullptr, c.decrypt ? ok_each : nullptr}},
+                      [&](size_t, size_t m, void* const* d, uint32_t* flag) {
+                          return launch_duplex<FrP, W>(ctx, tab, c, u64(d[0]), u64(d[1]), u64(d[2]), m, u64(d[2]), u64(d[3]), static_cast<uint8_t*>(d[4]), flag);
+                      });
 }
 // Every form of the encryption trace at width W (c.decrypt is unused).  keys / headers / texts: dense per item, staged per chunk when in_on_host, else device
 // memory; host_rows != null: the rows are staged, dense, and downloaded (d_rows and stride are ignored), otherwise row i goes to d_rows + i * stride
@@ -2208,44 +2020,27 @@ template <class FrP, int W>
 int encrypt_trace_run(zl_ctx* ctx, const DuplexCall& c, const uint64_t* keys, const uint64_t* headers, const uint64_t* texts, bool in_on_host, size_t count, uint64_t* d_rows,
                       size_t stride, uint64_t* host_rows, uint64_t* host_tags, uint64_t* host_cts) {
     const uint32_t* tab;
-    int rc = get_table<FrP, W>(ctx, &tab);
+    const int rc = get_table<FrP, W>(ctx, &tab);
     if (rc) return rc;
-    const size_t T = c.N * (W - 1), nv = pd::encrypt_row_elems(W, c.K, c.H, c.N);
-    const size_t per = (host_tags ? 32 : 0) + (host_cts ? T * 32 : 0) + (in_on_host ? (c.K + c.H + T) * 32 : 0) + (host_rows ? nv * 32 : 0);
-    const size_t chunk = stage_items(per ? per : 1), m0 = count < chunk ? count : chunk;
-    const size_t o_ct = host_tags ? up256(m0 * 32) : 0, o_key = o_ct + (host_cts ? up256(m0 * T * 32) : 0), o_hdr = o_key + (in_on_host ? up256(m0 * c.K * 32) : 0),
-                 o_text = o_hdr + (in_on_host ? up256(m0 * c.H * 32) : 0), o_rows = o_text + (in_on_host ? up256(m0 * T * 32) : 0);
-    Stage s;
-    if ((rc = stage_get(ctx, o_rows + (host_rows ? m0 * nv * 32 : 0), &s))) return rc;
-    uint64_t* d_tag = host_tags ? reinterpret_cast<uint64_t*>(s.data) : nullptr;
-    uint64_t* d_ct = host_cts ? reinterpret_cast<uint64_t*>(s.data + o_ct) : nullptr;
-    uint64_t* d_key = reinterpret_cast<uint64_t*>(s.data + o_key);
-    uint64_t* d_hdr = reinterpret_cast<uint64_t*>(s.data + o_hdr);
-    uint64_t* d_text = reinterpret_cast<uint64_t*>(s.data + o_text);
-    uint64_t* d_stage_rows = reinterpret_cast<uint64_t*>(s.data + o_rows);
+    const size_t T = c.N * (W - 1), nv = pd::encrypt_row_elems(W, c.K, c.H, c.N), in_elem = in_on_host ? 32 : 0;
     DuplexInit init{};
     memcpy(init.w, c.init, 32 * W);
-    for (size_t first = 0; first < count; first += chunk) {
-        const size_t m = count - first < chunk ? count - first : chunk;
-        const uint64_t* k_from = keys + first * c.K * 4;
-        const uint64_t* h_from = headers + first * c.H * 4;
-        const uint64_t* t_from = texts + first * T * 4;
-        if (in_on_host) {
-            ZL_HIP(ctx, hipMemcpyAsync(d_key, k_from, m * c.K * 32, hipMemcpyHostToDevice, ctx->stream));
-            if (c.H) ZL_HIP(ctx, hipMemcpyAsync(d_hdr, h_from, m * c.H * 32, hipMemcpyHostToDevice, ctx->stream));
-            ZL_HIP(ctx, hipMemcpyAsync(d_text, t_from, m * T * 32, hipMemcpyHostToDevice, ctx->stream));
-            k_from = d_key;
-            h_from = d_hdr;
-            t_from = d_text;
-        }
-        uint64_t* rows = host_rows ? d_stage_rows : d_rows + first * stride * 4;
-        ZL_POS_LAUNCH(ctx, (k_pos_duplex_trace<FrP, W>), blocks_of(m), BLOCK, 0, tab, init, k_from, (uint32_t)c.K, h_from, (uint32_t)c.H, t_from, (uint32_t)c.N, m, rows,
-                      host_rows ? nv : stride, d_tag, d_ct, s.flag);
-        if (host_rows) ZL_HIP(ctx, hipMemcpyAsync(host_rows + first * nv * 4, d_stage_rows, m * nv * 32, hipMemcpyDeviceToHost, ctx->stream));
-        if (host_tags) ZL_HIP(ctx, hipMemcpyAsync(host_tags + first * 4, d_tag, m * 32, hipMemcpyDeviceToHost, ctx->stream));
-        if (host_cts) ZL_HIP(ctx, hipMemcpyAsync(host_cts + first * T * 4, d_ct, m * T * 32, hipMemcpyDeviceToHost, ctx->stream));
-    }
-    return finish(ctx, s.flag);
+    return run_chunks(ctx, count,
+                      {{c.K * in_elem, keys, nullptr},
+                       {c.H * in_elem, headers, nullptr},
+                       {T * in_elem, texts, nullptr},
+                       {host_rows ? nv * 32 : 0, nullptr, host_rows},
+                       {host_tags ? 32u : 0u, nullptr, host_tags},
+                       {host_cts ? T * 32 : 0, nullptr, host_cts}},
+                      [&](size_t first, size_t m, void* const* d, uint32_t* flag) {
+                          const uint64_t* k_from = in_on_host ? u64(d[0]) : keys + first * c.K * 4;
+                          const uint64_t* h_from = in_on_host ? u64(d[1]) : headers + first * c.H * 4;
+                          const uint64_t* t_from = in_on_host ? u64(d[2]) : texts + first * T * 4;
+                          const Rows rows = rows_of(d[3], nv, d_rows, stride, first);
+                          ZL_POS_LAUNCH(ctx, (k_pos_duplex_trace<FrP, W>), blocks_of(m), BLOCK, 0, tab, init, k_from, (uint32_t)c.K, h_from, (uint32_t)c.H, t_from, (uint32_t)c.N, m,
+                                        rows.at, rows.stride, u64(d[4]), u64(d[5]), flag);
+                          return ZL_OK;
+                      });
 }
 // the parameters of a call: ZL_EINVAL, or ZL_OK with the initial state's words (zero for a null pointer) in init_out
 template <class FrP>
@@ -2265,7 +2060,7 @@ int duplex_params(zl_curve_t curve, unsigned width, const uint64_t* initial_stat
 #define ZL_POS_CURVE(curve, fn, ...) ((curve) == ZL_BLS12_381 ? fn<BLS12_381_Fr>(__VA_ARGS__) : fn<BN254_Fr>(__VA_ARGS__))
 
 int zl_poseidon_trace_rows(zl_ctx* ctx, int curve, const uint64_t* x0, const uint64_t* x1, uint32_t k, size_t count, void* d_rows, size_t stride_elems, uint64_t* public_out) {
-    return ZL_POS_CURVE(curve, dev_trace_rows, ctx, x0, x1, k, count, static_cast<uint64_t*>(d_rows), stride_elems, public_out);
+    return ZL_POS_CURVE(curve, chain_trace_run, ctx, x0, x1, true, k, count, static_cast<uint64_t*>(d_rows), stride_elems, nullptr, public_out);
 }
 int zl_poseidon_merkle_trace_rows(zl_ctx* ctx, int curve, const uint64_t* leaves, const uint64_t* indices, const uint64_t* paths, unsigned depth, size_t count, void* d_rows,
                                   size_t stride_elems, uint64_t* roots_out) {
@@ -2275,7 +2070,7 @@ int zl_poseidon_merkle_member_rows(zl_ctx* ctx, int curve, const void* d_nodes, 
                                    size_t stride_elems, uint64_t* host_rows) {
     return ZL_POS_CURVE(curve, dev_merkle_from_tree, ctx, d_nodes, n, depth, indices, count, d_rows, stride_elems, host_rows);
 }
-// every width of the table, 3 included (the arity-general traces at arity 2)
+// every width of the table (3..6)
 #define ZL_POS_ANYW_OF(FrP, width, fn, ...) \
     ((width) == 3 ? fn<FrP, 3>(__VA_ARGS__) : (width) == 4 ? fn<FrP, 4>(__VA_ARGS__) : (width) == 5 ? fn<FrP, 5>(__VA_ARGS__) : fn<FrP, 6>(__VA_ARGS__))
 #define ZL_POS_ANYW(curve, width, fn, ...) \
@@ -2309,31 +2104,7 @@ int zl_poseidon_encrypt_trace_rows(zl_ctx* ctx, int curve, unsigned width, const
 
 extern "C" {
 
-int zl_poseidon_permute_batch(zl_ctx* ctx, zl_curve_t curve, uint64_t* states, size_t count) {
-    if (!valid_curve(curve) || (count && !states)) return ZL_EINVAL;
-    if (count == 0) return ZL_OK;
-    if (on_host(ctx, count)) return ZL_POS_CURVE(curve, host_permute, states, count);
-    ZL_HIP(ctx, hipSetDevice(ctx->device));
-    return ZL_POS_CURVE(curve, dev_permute, ctx, states, count);
-}
-int zl_poseidon_hash2_batch(zl_ctx* ctx, zl_curve_t curve, const uint64_t* xy, size_t count, uint64_t* out) {
-    if (!valid_curve(curve) || (count && (!xy || !out))) return ZL_EINVAL;
-    if (count == 0) return ZL_OK;
-    if (on_host(ctx, count)) return ZL_POS_CURVE(curve, host_hash2_batch, xy, count, out);
-    ZL_HIP(ctx, hipSetDevice(ctx->device));
-    return ZL_POS_CURVE(curve, dev_hash2, ctx, xy, count, out);
-}
-int zl_poseidon_hash2_batch_dev(zl_ctx* ctx, zl_curve_t curve, const void* d_xy, size_t count, void* d_out) {
-    if (!ctx || !valid_curve(curve) || (count && (!d_xy || !d_out))) return ZL_EINVAL;
-    if (count == 0) return ZL_OK;
-    ZL_HIP(ctx, hipSetDevice(ctx->device));
-    return ZL_POS_CURVE(curve, dev_hash2_dev, ctx, d_xy, count, d_out);
-}
-// ---- every arity of the table (pd::spec).  Width 3 / arity 2 forwards to the entry points above; widths 4..6 run their own kernels and host loops.
-#define ZL_POS_WIDE(curve, width, fn, ...)                                                                    \
-    ((width) == 4 ? ((curve) == ZL_BLS12_381 ? fn<BLS12_381_Fr, 4>(__VA_ARGS__) : fn<BN254_Fr, 4>(__VA_ARGS__))   \
-     : (width) == 5 ? ((curve) == ZL_BLS12_381 ? fn<BLS12_381_Fr, 5>(__VA_ARGS__) : fn<BN254_Fr, 5>(__VA_ARGS__)) \
-                    : ((curve) == ZL_BLS12_381 ? fn<BLS12_381_Fr, 6>(__VA_ARGS__) : fn<BN254_Fr, 6>(__VA_ARGS__)))
+// ---- every arity of the table (pd::spec); the width-3 / arity-2 entry points are these at width 3
 int zl_poseidon_spec(unsigned arity, unsigned* width, unsigned* full_rounds, unsigned* partial_rounds, uint64_t* tag) {
     if (!pd::arity_ok(arity)) return ZL_EINVAL;
     const pd::Spec s = pd::spec(arity);
@@ -2345,39 +2116,36 @@ int zl_poseidon_spec(unsigned arity, unsigned* width, unsigned* full_rounds, uns
 }
 int zl_poseidon_permute_w(zl_curve_t curve, unsigned width, uint64_t* state) {
     if (!valid_curve(curve) || !pd::width_ok(width) || !state) return ZL_EINVAL;
-    if (width == 3) return zl_poseidon_permute(curve, state);
-    return ZL_POS_WIDE(curve, width, host_permute_one, state);
+    return ZL_POS_ANYW(curve, width, host_permute_one, state);
 }
 int zl_poseidon_constants(zl_curve_t curve, unsigned width, uint64_t* keys, uint64_t* mds) {
     if (!valid_curve(curve) || !pd::width_ok(width)) return ZL_EINVAL;
-    if (width == 3) return ZL_POS_CURVE(curve, constants_out, keys, mds);
-    return ZL_POS_WIDE(curve, width, constants_out, keys, mds);
+    return ZL_POS_ANYW(curve, width, constants_out, keys, mds);
 }
 int zl_poseidon_permute_batch_w(zl_ctx* ctx, zl_curve_t curve, unsigned width, uint64_t* states, size_t count) {
-    if (!pd::width_ok(width)) return ZL_EINVAL;
-    if (width == 3) return zl_poseidon_permute_batch(ctx, curve, states, count);
-    if (!valid_curve(curve) || (count && !states)) return ZL_EINVAL;
+    if (!pd::width_ok(width) || !valid_curve(curve) || (count && !states)) return ZL_EINVAL;
     if (count == 0) return ZL_OK;
-    if (on_host(ctx, count)) return ZL_POS_WIDE(curve, width, host_permute_w, states, count);
+    if (on_host(ctx, count)) return ZL_POS_ANYW(curve, width, host_permute_w, states, count);
     ZL_HIP(ctx, hipSetDevice(ctx->device));
-    return ZL_POS_WIDE(curve, width, dev_permute_w, ctx, states, count);
+    return ZL_POS_ANYW(curve, width, dev_permute_w, ctx, states, count);
 }
 int zl_poseidon_hash_batch(zl_ctx* ctx, zl_curve_t curve, unsigned arity, const uint64_t* in, size_t count, uint64_t* out) {
-    if (!pd::arity_ok(arity)) return ZL_EINVAL;
-    if (arity == 2) return zl_poseidon_hash2_batch(ctx, curve, in, count, out);
-    if (!valid_curve(curve) || (count && (!in || !out))) return ZL_EINVAL;
+    if (!pd::arity_ok(arity) || !valid_curve(curve) || (count && (!in || !out))) return ZL_EINVAL;
     if (count == 0) return ZL_OK;
-    if (on_host(ctx, count)) return ZL_POS_WIDE(curve, arity + 1, host_hash_w, in, count, out);
+    if (on_host(ctx, count)) return ZL_POS_ANYW(curve, arity + 1, host_hash_w, in, count, out);
     ZL_HIP(ctx, hipSetDevice(ctx->device));
-    return ZL_POS_WIDE(curve, arity + 1, dev_hash_w, ctx, in, count, out);
+    return ZL_POS_ANYW(curve, arity + 1, dev_hash_w, ctx, in, count, out);
 }
 int zl_poseidon_hash_batch_dev(zl_ctx* ctx, zl_curve_t curve, unsigned arity, const void* d_in, size_t count, void* d_out) {
-    if (!pd::arity_ok(arity)) return ZL_EINVAL;
-    if (arity == 2) return zl_poseidon_hash2_batch_dev(ctx, curve, d_in, count, d_out);
-    if (!ctx || !valid_curve(curve) || (count && (!d_in || !d_out))) return ZL_EINVAL;
+    if (!pd::arity_ok(arity) || !ctx || !valid_curve(curve) || (count && (!d_in || !d_out))) return ZL_EINVAL;
     if (count == 0) return ZL_OK;
     ZL_HIP(ctx, hipSetDevice(ctx->device));
-    return ZL_POS_WIDE(curve, arity + 1, dev_hash_w_dev, ctx, d_in, count, d_out);
+    return ZL_POS_ANYW(curve, arity + 1, dev_hash_w_dev, ctx, d_in, count, d_out);
+}
+int zl_poseidon_permute_batch(zl_ctx* ctx, zl_curve_t curve, uint64_t* states, size_t count) { return zl_poseidon_permute_batch_w(ctx, curve, 3, states, count); }
+int zl_poseidon_hash2_batch(zl_ctx* ctx, zl_curve_t curve, const uint64_t* xy, size_t count, uint64_t* out) { return zl_poseidon_hash_batch(ctx, curve, 2, xy, count, out); }
+int zl_poseidon_hash2_batch_dev(zl_ctx* ctx, zl_curve_t curve, const void* d_xy, size_t count, void* d_out) {
+    return zl_poseidon_hash_batch_dev(ctx, curve, 2, d_xy, count, d_out);
 }
 // ---- the duplex cipher: one validation (duplex_params), then the host mirror, the staged device path or the device-pointer path
 size_t zl_poseidon_duplex_permutations(unsigned width, size_t key_len, size_t header_len, size_t blocks) {
@@ -2475,7 +2243,8 @@ int zl_poseidon_chain_assignments_dev(zl_ctx* ctx, zl_curve_t curve, const void*
     if (!ctx || !valid_curve(curve) || nv == 0 || stride_elems < nv || (count && (!d_x0 || !d_x1 || !d_out)) || ((uintptr_t)d_out & 15)) return ZL_EINVAL;
     if (count == 0) return ZL_OK;
     ZL_HIP(ctx, hipSetDevice(ctx->device));
-    return ZL_POS_CURVE(curve, dev_assignments_dev, ctx, d_x0, d_x1, k, count, d_out, stride_elems);
+    return ZL_POS_CURVE(curve, chain_trace_run, ctx, static_cast<const uint64_t*>(d_x0), static_cast<const uint64_t*>(d_x1), false, k, count, static_cast<uint64_t*>(d_out),
+                        stride_elems, nullptr, nullptr);
 }
 int zl_poseidon_chain_assignments(zl_ctx* ctx, zl_curve_t curve, const uint64_t* x0, const uint64_t* x1, uint32_t k, size_t count, uint64_t* out) {
     const size_t nv = zl_poseidon_chain_assignment_elems(k);
@@ -2484,7 +2253,7 @@ int zl_poseidon_chain_assignments(zl_ctx* ctx, zl_curve_t curve, const uint64_t*
     if (count == 0) return ZL_OK;
     if (on_host(ctx, count)) return ZL_POS_CURVE(curve, host_assignments, x0, x1, k, count, out, nv);
     ZL_HIP(ctx, hipSetDevice(ctx->device));
-    return ZL_POS_CURVE(curve, dev_assignments, ctx, x0, x1, k, count, out, nv);
+    return ZL_POS_CURVE(curve, chain_trace_run, ctx, x0, x1, true, k, count, nullptr, 0, out, nullptr);
 }
 size_t zl_poseidon_merkle_nodes(size_t n, unsigned depth) {
     return pd::geometry_ok(n, depth) ? pd::level_offset(n, depth + 1) : 0;
