@@ -546,6 +546,55 @@ int zl_groth16_keys_parse(zl_curve_t curve, const uint8_t* in, size_t len, unsig
  * verifier built from it recomputes the other three (zl_groth16_verify does). */
 int zl_groth16_vk_to_bytes(const zl_g16_keys* k, uint8_t* out, size_t cap, size_t* len);
 
+/* ---- the embedded twisted Edwards curves and hybrid encryption (csrc/zl_edwards.h, csrc/zl_edwards_dev.hip) ----------------------------
+ * The two embedded curves the reference's arkworks plugin re-exports over this backend's scalar fields: ed_on_bls12_381 (Jubjub) for ZL_BLS12_381 and ed-on-bn254
+ * (Baby Jubjub) for ZL_BN254: a x^2 + y^2 = 1 + d x^2 y^2 over F_q, q = the pairing curve's r, subgroup order l, cofactor 8.  Both are complete: the identity
+ * is the ordinary point (0, 1) and there is no point at infinity.  The constants are the published parameters of the two arkworks crates; they are not compared
+ * with arkworks bytes -- the reference holds no vectors for these curves.  The generator is not a constant: the reference's DiffieHellman carries it as a
+ * field (openzl-crypto/src/algebra/diffie_hellman.rs), here it is an argument.
+ * A point is 8 words, x then y, canonical (each below q); a scalar is 4 canonical words below l.  Strides are 0 (one operand for all items) or 1.
+ * zl_ed_params: a, d, order, cofactor, 4 words each, canonical; a NULL output is skipped.  zl_ed_add / zl_ed_scalar_mul: host, one item; ZL_EINVAL for an operand
+ * that is out of range or not on the curve.
+ * zl_ed_scalar_mul_batch: out[i] = scalars[i * scalar_stride] * points[i * point_stride].  status[i]: 0 ok, 1 a coordinate >= q, 2 not on the curve, 3 not in
+ * the prime-order subgroup (only with ZL_ED_CHECK_SUBGROUP, which adds the test l P = (0, 1): a second multiplication), 4 scalar >= l; the LOWEST code that
+ * applies.  An item with a non-zero status writes (0, 1) and leaves every other item untouched.  status == NULL: any such item makes the whole call ZL_EINVAL
+ * (through the flag word on the device), the outputs are then unspecified.  count == 0 is ZL_OK and writes nothing; a null required pointer, an unknown curve, an
+ * unknown flag or a stride above 1 is ZL_EINVAL.  ctx == NULL or a count below ZL_TUNE_ED_DEV_MIN runs the host mirror over the host pool; otherwise the call
+ * is staged in chunks of at most ZL_TUNE_ED_CHUNK items under a byte budget (one window table of 2304 B per lane lives in the ctx's scratch) and has finished on
+ * return.  A shared point (point_stride == 0) takes the fixed-base kernel from ZL_TUNE_ED_FIXED_MIN items; a shared scalar reads its digits wave-uniformly.
+ * Results are byte-identical on every path.  The _dev form takes DEVICE pointers for points, scalars, out and status (never the host path: ctx == NULL is
+ * ZL_EINVAL); with a shared point on the fixed-base path it copies that one point to the host on the ctx's stream and waits for it, because the table is built
+ * on the host.
+ * Hybrid encryption: the reference's encryption::hybrid::Hybrid<DiffieHellman, FixedDuplexer>.  Encrypt: epk_i = esk_i G, S_i = esk_i pk_i (GenerateSecret),
+ * then the duplex cipher above under the key (S_i.x, S_i.y), key_len = 2 -- the reference leaves group -> key to the caller's converter
+ * (openzl-crypto/src/encryption/convert/key.rs); here it is the two affine coordinates.  Decrypt: S_i = sk epk_i (ReconstructSecret), then the duplex
+ * decryption and its tag verdict; sk_stride == 0 is the scan of a ledger with one key.  Width, header_len, blocks, initial_state and the element range of
+ * headers, texts and tags are the duplex call's, with its ZL_EINVAL.  status[i] as above (encrypt: of pk_i, esk_i and the generator; decrypt: of epk_i and
+ * sk).  An item with a non-zero status has epk = (0, 1) (encrypt) and ok_each[i] = 0 (decrypt); its texts and tag are computed from some key and are
+ * unspecified.  Decryption never fails the batch for such an item -- ledger data is untrusted -- and status may be NULL there; encryption with status == NULL
+ * returns ZL_EINVAL for one.  On the device the shared secrets stay in the ctx's scratch and the duplex kernel reads them there: no bus round trip.  The _dev
+ * forms take DEVICE pointers for scalars, points, headers, texts, tags and status; generator_xy, initial_state and ok_each stay host memory. */
+#define ZL_ED_CHECK_SUBGROUP 1u
+int zl_ed_params(zl_curve_t curve, uint64_t* a, uint64_t* d, uint64_t* order, uint64_t* cofactor);
+int zl_ed_add(zl_curve_t curve, const uint64_t* p_xy, const uint64_t* q_xy, uint64_t* out_xy);
+int zl_ed_scalar_mul(zl_curve_t curve, const uint64_t* p_xy, const uint64_t* k, uint64_t* out_xy);
+int zl_ed_scalar_mul_batch(zl_ctx* ctx, zl_curve_t curve, const uint64_t* points_xy, size_t point_stride, const uint64_t* scalars, size_t scalar_stride, size_t count,
+                           unsigned flags, uint64_t* out_xy, uint8_t* status);
+int zl_ed_scalar_mul_batch_dev(zl_ctx* ctx, zl_curve_t curve, const void* d_points_xy, size_t point_stride, const void* d_scalars, size_t scalar_stride, size_t count,
+                               unsigned flags, void* d_out_xy, void* d_status);
+int zl_hybrid_encrypt_batch(zl_ctx* ctx, zl_curve_t curve, unsigned width, const uint64_t* initial_state, const uint64_t* generator_xy, const uint64_t* esk,
+                            const uint64_t* pks_xy, size_t pk_stride, const uint64_t* headers, size_t header_len, const uint64_t* plaintexts, size_t blocks, size_t count,
+                            unsigned flags, uint64_t* epks_xy, uint64_t* ciphertexts, uint64_t* tags, uint8_t* status);
+int zl_hybrid_encrypt_batch_dev(zl_ctx* ctx, zl_curve_t curve, unsigned width, const uint64_t* initial_state, const uint64_t* generator_xy, const void* d_esk,
+                                const void* d_pks_xy, size_t pk_stride, const void* d_headers, size_t header_len, const void* d_plaintexts, size_t blocks, size_t count,
+                                unsigned flags, void* d_epks_xy, void* d_ciphertexts, void* d_tags, void* d_status);
+int zl_hybrid_decrypt_batch(zl_ctx* ctx, zl_curve_t curve, unsigned width, const uint64_t* initial_state, const uint64_t* sks, size_t sk_stride, const uint64_t* epks_xy,
+                            const uint64_t* headers, size_t header_len, const uint64_t* ciphertexts, const uint64_t* tags, size_t blocks, size_t count, unsigned flags,
+                            uint64_t* plaintexts, uint8_t* ok_each, uint8_t* status);
+int zl_hybrid_decrypt_batch_dev(zl_ctx* ctx, zl_curve_t curve, unsigned width, const uint64_t* initial_state, const void* d_sks, size_t sk_stride, const void* d_epks_xy,
+                                const void* d_headers, size_t header_len, const void* d_ciphertexts, const void* d_tags, size_t blocks, size_t count, unsigned flags,
+                                void* d_plaintexts, uint8_t* ok_each, void* d_status);
+
 /* ---- per-call device timing (HIP events on the ctx's stream) -------------------------------------------- */
 typedef struct zl_timing {
     float total_ms;      /* first kernel start -> last kernel end of the last zl_msm* / zl_ntt* call */

@@ -53,7 +53,10 @@ ABI_SYMBOLS = [
     "zl_poseidon_duplex_permutations", "zl_poseidon_duplex_encrypt_batch", "zl_poseidon_duplex_decrypt_batch", "zl_poseidon_duplex_encrypt_batch_dev",
     "zl_poseidon_duplex_decrypt_batch_dev", "zl_circuit_poseidon_encrypt", "zl_circuit_poseidon_encrypt_witness",
     "zl_poseidon_encrypt_assignment_elems", "zl_poseidon_encrypt_assignments", "zl_poseidon_encrypt_assignments_dev", "zl_groth16_prove_poseidon_encryptions",
+    "zl_ed_params", "zl_ed_add", "zl_ed_scalar_mul", "zl_ed_scalar_mul_batch", "zl_ed_scalar_mul_batch_dev",
+    "zl_hybrid_encrypt_batch", "zl_hybrid_encrypt_batch_dev", "zl_hybrid_decrypt_batch", "zl_hybrid_decrypt_batch_dev",
 ]
+ZL_ED_CHECK_SUBGROUP = 1
 
 
 class BackendError(RuntimeError):
@@ -161,6 +164,17 @@ def load_library(path: Optional[str] = None):
     L.zl_poseidon_duplex_decrypt_batch.argtypes = [vp, C.c_int, C.c_uint, u64p, u64p, C.c_size_t, u64p, C.c_size_t, u64p, u64p, C.c_size_t, C.c_size_t, u64p, u8p]
     L.zl_poseidon_duplex_encrypt_batch_dev.argtypes = [vp, C.c_int, C.c_uint, u64p, vp, C.c_size_t, vp, C.c_size_t, vp, C.c_size_t, C.c_size_t, vp, vp]
     L.zl_poseidon_duplex_decrypt_batch_dev.argtypes = [vp, C.c_int, C.c_uint, u64p, vp, C.c_size_t, vp, C.c_size_t, vp, vp, C.c_size_t, C.c_size_t, vp, u8p]
+    L.zl_ed_params.argtypes = [C.c_int, u64p, u64p, u64p, u64p]
+    L.zl_ed_add.argtypes = [C.c_int, u64p, u64p, u64p]
+    L.zl_ed_scalar_mul.argtypes = [C.c_int, u64p, u64p, u64p]
+    L.zl_ed_scalar_mul_batch.argtypes = [vp, C.c_int, u64p, C.c_size_t, u64p, C.c_size_t, C.c_size_t, C.c_uint, u64p, u8p]
+    L.zl_ed_scalar_mul_batch_dev.argtypes = [vp, C.c_int, vp, C.c_size_t, vp, C.c_size_t, C.c_size_t, C.c_uint, vp, vp]
+    L.zl_hybrid_encrypt_batch.argtypes = [vp, C.c_int, C.c_uint, u64p, u64p, u64p, u64p, C.c_size_t, u64p, C.c_size_t, u64p, C.c_size_t, C.c_size_t, C.c_uint, u64p, u64p,
+                                          u64p, u8p]
+    L.zl_hybrid_encrypt_batch_dev.argtypes = [vp, C.c_int, C.c_uint, u64p, u64p, vp, vp, C.c_size_t, vp, C.c_size_t, vp, C.c_size_t, C.c_size_t, C.c_uint, vp, vp, vp, vp]
+    L.zl_hybrid_decrypt_batch.argtypes = [vp, C.c_int, C.c_uint, u64p, u64p, C.c_size_t, u64p, u64p, C.c_size_t, u64p, u64p, C.c_size_t, C.c_size_t, C.c_uint, u64p, u8p,
+                                          u8p]
+    L.zl_hybrid_decrypt_batch_dev.argtypes = [vp, C.c_int, C.c_uint, u64p, vp, C.c_size_t, vp, vp, C.c_size_t, vp, vp, C.c_size_t, C.c_size_t, C.c_uint, vp, u8p, vp]
     L.zl_circuit_poseidon_encrypt.argtypes = [C.c_int, C.c_uint, u64p, u64p, C.c_size_t, u64p, C.c_size_t, u64p, C.c_size_t, C.POINTER(vp)]
     L.zl_circuit_poseidon_encrypt_witness.argtypes = L.zl_circuit_poseidon_encrypt.argtypes
     L.zl_poseidon_encrypt_assignment_elems.argtypes = [C.c_uint, C.c_size_t, C.c_size_t, C.c_size_t]
@@ -616,6 +630,49 @@ class Backend:
                                                                 C.c_void_p(d_headers), header_len, C.c_void_p(d_ciphertexts), C.c_void_p(d_tags), blocks, count,
                                                                 C.c_void_p(d_plaintexts), ok.ctypes.data_as(C.POINTER(C.c_uint8)) if count else None),
                     "zl_poseidon_duplex_decrypt_batch_dev")
+        return ok.astype(bool)
+
+    def ed_scalar_mul(self, curve: int, points, scalars, check_subgroup: bool = False):
+        """zl_ed_scalar_mul_batch on the embedded curve of `curve`: points (count, 2, 4) or one point (2, 4), scalars (count, 4) or one scalar (4,) -- a single
+        operand broadcasts through stride 0 -> (out (count, 2, 4), status (count,) uint8: 0 ok, 1 coordinate >= q, 2 off the curve, 3 outside the subgroup (with
+        check_subgroup), 4 scalar >= l; a refused item is (0, 1))"""
+        return _ed_scalar_mul(self.L, self._ctx, curve, points, scalars, check_subgroup)
+
+    def ed_scalar_mul_dev(self, curve: int, d_points: int, point_stride: int, d_scalars: int, scalar_stride: int, count: int, d_out: int, d_status: int,
+                          check_subgroup: bool = False):
+        """zl_ed_scalar_mul_batch_dev on device addresses (d_status may be 0: a refused item then fails the call); finished on return"""
+        self._check(self.L.zl_ed_scalar_mul_batch_dev(self._ctx, curve, C.c_void_p(d_points), point_stride, C.c_void_p(d_scalars), scalar_stride, count,
+                                                      ZL_ED_CHECK_SUBGROUP if check_subgroup else 0, C.c_void_p(d_out), C.c_void_p(d_status)), "zl_ed_scalar_mul_batch_dev")
+
+    def hybrid_encrypt(self, curve: int, initial_state, generator, esk, pks, headers, plaintexts, check_subgroup: bool = False):
+        """zl_hybrid_encrypt_batch: generator (2, 4), esk (count, 4), pks (count, 2, 4) or one (2, 4), headers (count, H, 4), plaintexts (count, N, W - 1, 4) ->
+        (epks (count, 2, 4), ciphertexts, tags (count, 4), status (count,)): epk = esk G, the duplex cipher under the key (x, y) of esk pk"""
+        return _hybrid_encrypt(self.L, self._ctx, curve, initial_state, generator, esk, pks, headers, plaintexts, check_subgroup)
+
+    def hybrid_decrypt(self, curve: int, initial_state, sks, epks, headers, ciphertexts, tags, check_subgroup: bool = False):
+        """zl_hybrid_decrypt_batch: sks (count, 4) or ONE key (4,) -- the scan --, epks (count, 2, 4) -> (plaintexts, ok (count,) bool, status (count,)): the key
+        is (x, y) of sk epk; ok[i] is False for a tag mismatch and for a refused point"""
+        return _hybrid_decrypt(self.L, self._ctx, curve, initial_state, sks, epks, headers, ciphertexts, tags, check_subgroup)
+
+    def hybrid_encrypt_dev(self, curve: int, width: int, initial_state, generator, d_esk: int, d_pks: int, pk_stride: int, d_headers: int, header_len: int,
+                           d_plaintexts: int, blocks: int, count: int, d_epks: int, d_ciphertexts: int, d_tags: int, d_status: int, check_subgroup: bool = False):
+        """zl_hybrid_encrypt_batch_dev on device addresses; generator and initial_state stay host memory; finished on return"""
+        st = _duplex_state(initial_state, width)
+        g = np.ascontiguousarray(np.asarray(generator, dtype=np.uint64).reshape(2, 4))
+        self._check(self.L.zl_hybrid_encrypt_batch_dev(self._ctx, curve, width, None if st is None else _p64(st), _p64(g), C.c_void_p(d_esk), C.c_void_p(d_pks), pk_stride,
+                                                       C.c_void_p(d_headers), header_len, C.c_void_p(d_plaintexts), blocks, count,
+                                                       ZL_ED_CHECK_SUBGROUP if check_subgroup else 0, C.c_void_p(d_epks), C.c_void_p(d_ciphertexts), C.c_void_p(d_tags),
+                                                       C.c_void_p(d_status)), "zl_hybrid_encrypt_batch_dev")
+
+    def hybrid_decrypt_dev(self, curve: int, width: int, initial_state, d_sks: int, sk_stride: int, d_epks: int, d_headers: int, header_len: int, d_ciphertexts: int,
+                           d_tags: int, blocks: int, count: int, d_plaintexts: int, d_status: int, check_subgroup: bool = False) -> np.ndarray:
+        """zl_hybrid_decrypt_batch_dev on device addresses -> the (count,) bool verdicts (host memory)"""
+        st = _duplex_state(initial_state, width)
+        ok = np.zeros(count, dtype=np.uint8)
+        self._check(self.L.zl_hybrid_decrypt_batch_dev(self._ctx, curve, width, None if st is None else _p64(st), C.c_void_p(d_sks), sk_stride, C.c_void_p(d_epks),
+                                                       C.c_void_p(d_headers), header_len, C.c_void_p(d_ciphertexts), C.c_void_p(d_tags), blocks, count,
+                                                       ZL_ED_CHECK_SUBGROUP if check_subgroup else 0, C.c_void_p(d_plaintexts),
+                                                       ok.ctypes.data_as(C.POINTER(C.c_uint8)) if count else None, C.c_void_p(d_status)), "zl_hybrid_decrypt_batch_dev")
         return ok.astype(bool)
 
     def poseidon_hash2(self, curve: int, xy: np.ndarray) -> np.ndarray:
@@ -1611,6 +1668,111 @@ def poseidon_duplex_encrypt_host(curve: int, initial_state, keys, headers, plain
 
 def poseidon_duplex_decrypt_host(curve: int, initial_state, keys, headers, ciphertexts, tags):
     return _poseidon_duplex(load_library(), None, curve, initial_state, keys, headers, ciphertexts, tags)
+
+
+# ---- the embedded twisted Edwards curves and hybrid encryption (zl_ed_*, zl_hybrid_*) ---------------------------------------------------------------------
+def _u8p(a: np.ndarray):
+    return a.ctypes.data_as(C.POINTER(C.c_uint8)) if a.size else None
+
+
+def _ed_operand(a, per: int, what: str):
+    """(count, per, 4) words and stride 1 -- scalars also as (count, 4) --, or ONE operand and stride 0: a point (2, 4), a scalar (4,).  A (1, 4) scalar array is
+    a batch of one, not the broadcast form."""
+    v = np.ascontiguousarray(np.asarray(a, dtype=np.uint64))
+    if v.shape == ((4,) if per == 1 else (per, 4)):
+        return v.reshape(1, per, 4), 0
+    if per == 1 and v.ndim == 2 and v.shape[1] == 4:
+        v = v.reshape(-1, 1, 4)
+    if v.ndim != 3 or v.shape[1:] != (per, 4):
+        raise ValueError(f"{what} are (count, {per}, 4) uint64 words, or one operand for all items")
+    return v, 1
+
+
+def _ed_count(*ops):
+    counts = {v.shape[0] for v, stride in ops if stride}
+    if len(counts) > 1:
+        raise ValueError("operands of different counts")
+    return counts.pop() if counts else 1
+
+
+def ed_params(curve: int) -> dict:
+    """zl_ed_params: {"a", "d", "order", "cofactor"} of the embedded curve a x^2 + y^2 = 1 + d x^2 y^2 over `curve`'s scalar field, as Python integers"""
+    L = load_library()
+    out = np.zeros((4, 4), dtype=np.uint64)
+    _pos_check(L, L.zl_ed_params(curve, _p64(out[0]), _p64(out[1]), _p64(out[2]), _p64(out[3])), "zl_ed_params")
+    vals = [sum(int(w) << (64 * i) for i, w in enumerate(row)) for row in out]
+    return dict(zip(("a", "d", "order", "cofactor"), vals))
+
+
+def ed_add_host(curve: int, p, q) -> np.ndarray:
+    """zl_ed_add: p + q for two points (2, 4) of the embedded curve -> (2, 4)"""
+    L = load_library()
+    a = np.ascontiguousarray(np.asarray(p, dtype=np.uint64).reshape(2, 4))
+    b = np.ascontiguousarray(np.asarray(q, dtype=np.uint64).reshape(2, 4))
+    out = np.zeros((2, 4), dtype=np.uint64)
+    _pos_check(L, L.zl_ed_add(curve, _p64(a), _p64(b), _p64(out)), "zl_ed_add")
+    return out
+
+
+def _ed_scalar_mul(L, ctx, curve: int, points, scalars, check_subgroup: bool):
+    (p, ps), (k, ks) = _ed_operand(points, 2, "points"), _ed_operand(scalars, 1, "scalars")
+    count = _ed_count((p, ps), (k, ks))
+    out = np.zeros((count, 2, 4), dtype=np.uint64)
+    status = np.zeros(count, dtype=np.uint8)
+    _pos_check(L, L.zl_ed_scalar_mul_batch(ctx, curve, _p64(p), ps, _p64(k), ks, count, ZL_ED_CHECK_SUBGROUP if check_subgroup else 0, _p64(out), _u8p(status)),
+               "zl_ed_scalar_mul_batch")
+    return out, status
+
+
+def ed_scalar_mul_host(curve: int, points, scalars, check_subgroup: bool = False):
+    """Backend.ed_scalar_mul on the host mirror"""
+    return _ed_scalar_mul(load_library(), None, curve, points, scalars, check_subgroup)
+
+
+def _hybrid_encrypt(L, ctx, curve: int, initial_state, generator, esk, pks, headers, plaintexts, check_subgroup: bool):
+    t = np.ascontiguousarray(np.asarray(plaintexts, dtype=np.uint64))
+    h = np.ascontiguousarray(np.asarray(headers, dtype=np.uint64))
+    if t.ndim != 4 or t.shape[3] != 4 or h.ndim != 3 or h.shape[2] != 4 or h.shape[0] != t.shape[0]:
+        raise ValueError("plaintexts are (count, N, W - 1, 4), headers (count, H, 4) uint64 words")
+    count, blocks, width = t.shape[0], t.shape[1], t.shape[2] + 1
+    g = np.ascontiguousarray(np.asarray(generator, dtype=np.uint64).reshape(2, 4))
+    e = np.ascontiguousarray(np.asarray(esk, dtype=np.uint64).reshape(count, 4))
+    pk, ps = _ed_operand(pks, 2, "pks")
+    if ps and pk.shape[0] != count:
+        raise ValueError("one public key per item, or one for all")
+    st = _duplex_state(initial_state, width)
+    epks, out, tags, status = np.zeros((count, 2, 4), dtype=np.uint64), np.zeros_like(t), np.zeros((count, 4), dtype=np.uint64), np.zeros(count, dtype=np.uint8)
+    _pos_check(L, L.zl_hybrid_encrypt_batch(ctx, curve, width, None if st is None else _p64(st), _p64(g), _ptr_or_none(e), _p64(pk), ps, _ptr_or_none(h), h.shape[1],
+                                            _ptr_or_none(t), blocks, count, ZL_ED_CHECK_SUBGROUP if check_subgroup else 0, _ptr_or_none(epks), _ptr_or_none(out),
+                                            _ptr_or_none(tags), _u8p(status)), "zl_hybrid_encrypt_batch")
+    return epks, out, tags, status
+
+
+def _hybrid_decrypt(L, ctx, curve: int, initial_state, sks, epks, headers, ciphertexts, tags, check_subgroup: bool):
+    t = np.ascontiguousarray(np.asarray(ciphertexts, dtype=np.uint64))
+    h = np.ascontiguousarray(np.asarray(headers, dtype=np.uint64))
+    if t.ndim != 4 or t.shape[3] != 4 or h.ndim != 3 or h.shape[2] != 4 or h.shape[0] != t.shape[0]:
+        raise ValueError("ciphertexts are (count, N, W - 1, 4), headers (count, H, 4) uint64 words")
+    count, blocks, width = t.shape[0], t.shape[1], t.shape[2] + 1
+    sk, ks = _ed_operand(sks, 1, "sks")
+    if ks and sk.shape[0] != count:
+        raise ValueError("one secret key per item, or one for all")
+    ep = np.ascontiguousarray(np.asarray(epks, dtype=np.uint64).reshape(count, 2, 4))
+    tg = np.ascontiguousarray(np.asarray(tags, dtype=np.uint64).reshape(count, 4))
+    st = _duplex_state(initial_state, width)
+    out, ok, status = np.zeros_like(t), np.zeros(count, dtype=np.uint8), np.zeros(count, dtype=np.uint8)
+    _pos_check(L, L.zl_hybrid_decrypt_batch(ctx, curve, width, None if st is None else _p64(st), _p64(sk), ks, _ptr_or_none(ep), _ptr_or_none(h), h.shape[1],
+                                            _ptr_or_none(t), _ptr_or_none(tg), blocks, count, ZL_ED_CHECK_SUBGROUP if check_subgroup else 0, _ptr_or_none(out),
+                                            _u8p(ok), _u8p(status)), "zl_hybrid_decrypt_batch")
+    return out, ok.astype(bool), status
+
+
+def hybrid_encrypt_host(curve: int, initial_state, generator, esk, pks, headers, plaintexts, check_subgroup: bool = False):
+    return _hybrid_encrypt(load_library(), None, curve, initial_state, generator, esk, pks, headers, plaintexts, check_subgroup)
+
+
+def hybrid_decrypt_host(curve: int, initial_state, sks, epks, headers, ciphertexts, tags, check_subgroup: bool = False):
+    return _hybrid_decrypt(load_library(), None, curve, initial_state, sks, epks, headers, ciphertexts, tags, check_subgroup)
 
 
 def _poseidon_hash2(L, ctx, curve: int, xy) -> np.ndarray:

@@ -61,7 +61,8 @@ def _units():
              ("zl_msm_sort", "zl_msm_sort.hip", []),  # the curve-independent sort kernels of the MSM: once, not per group
              ("zl_pairing_dev_bls", "zl_pairing_dev.hip", ["-DZL_PAIR_CURVE=1"]), ("zl_pairing_dev_bn", "zl_pairing_dev.hip", ["-DZL_PAIR_CURVE=2"]),  # device Miller loops, once per curve
              ("zl_decode_dev_bls", "zl_decode_dev.hip", ["-DZL_DECODE_CURVE=1"]), ("zl_decode_dev_bn", "zl_decode_dev.hip", ["-DZL_DECODE_CURVE=2"]),  # device point / proof decoders, once per curve
-             ("zl_poseidon_dev", "zl_poseidon_dev.hip", ["-DZL_INLINE_MUL_DEVICE"])]  # batched Poseidon, both curves in one unit; the multiplier inlined in the round loop
+             ("zl_poseidon_dev", "zl_poseidon_dev.hip", ["-DZL_INLINE_MUL_DEVICE"]),  # batched Poseidon, both curves in one unit; the multiplier inlined in the round loop
+             ("zl_edwards_dev", "zl_edwards_dev.hip", ["-DZL_INLINE_MUL_DEVICE"])]  # embedded-curve scalar multiplication and hybrid encryption, both curves in one unit
     for g in GROUPS:
         # G1 device code inlines the multiplier: -4.5 % on the accumulate kernel vs the out-of-line call (host code keeps the call).
         extra = ["-DZL_INLINE_MUL_DEVICE"] if g.endswith("G1") else []

@@ -136,6 +136,8 @@ struct zl_scratch {
 //     matrices its multi-MSMs read; the transforms in between use ZL_SLOT_NTT_VEC, the multi-MSMs ZL_SLOT_MSM_MULTI, one after the other on ctx->stream.
 //   * ZL_SLOT_POSEIDON: the flag word and one staged chunk (inputs, outputs) of the batched Poseidon entry points (zl_poseidon_dev.hip), under a byte budget;
 //     the chunks of a call follow each other on ctx->stream.  Its own slot: a caller may hold device operands for the _dev forms in any other block.
+//   * ZL_SLOT_EDWARDS: the flag word, the per-lane window tables and one staged chunk of the embedded-curve entry points (zl_edwards_dev.hip), under a byte
+//     budget.  Its own slot: the hybrid calls keep the shared secrets of a chunk here while the duplex call underneath stages through ZL_SLOT_POSEIDON.
 enum zl_slot : int {
     ZL_SLOT_SET0_COUNTS = 0, ZL_SLOT_SET0_ENTRIES = 1, ZL_SLOT_SET0_BUCKETS = 2, ZL_SLOT_SET0_PARTIALS = 3, ZL_SLOT_SET0_TAIL = 4,
     ZL_SLOT_SORT_A = 5, ZL_SLOT_SORT_B = 6,
@@ -155,7 +157,8 @@ enum zl_slot : int {
     ZL_SLOT_MSM_MULTI = 42, ZL_SLOT_G16_BATCH = 43,
     ZL_SLOT_PAIR_FEXP = 44,
     ZL_SLOT_POSEIDON = 45,
-    ZL_SLOT_COUNT = 46
+    ZL_SLOT_EDWARDS = 46,
+    ZL_SLOT_COUNT = 47
 };
 // the slots of MSM buffer set 0..3; sort_a / sort_b are used by a job that owns its sort (side by side), every other job sorts in set 0's pair
 struct zl_msm_set_slots {
@@ -176,7 +179,7 @@ constexpr bool zl_slots_disjoint() {
             owners[x]++;
         }
     for (zl_slot x : {ZL_SLOT_PHI_ONE_KEY, ZL_SLOT_STAGING, ZL_SLOT_GROTH16, ZL_SLOT_TESTHOOK, ZL_SLOT_PAIR_IN, ZL_SLOT_PAIR_LINES, ZL_SLOT_PAIR_ACC, ZL_SLOT_PAIR_PREP,
-                      ZL_SLOT_DECODE_IN, ZL_SLOT_DECODE_OUT, ZL_SLOT_MSM_MULTI, ZL_SLOT_G16_BATCH, ZL_SLOT_PAIR_FEXP, ZL_SLOT_POSEIDON}) {
+                      ZL_SLOT_DECODE_IN, ZL_SLOT_DECODE_OUT, ZL_SLOT_MSM_MULTI, ZL_SLOT_G16_BATCH, ZL_SLOT_PAIR_FEXP, ZL_SLOT_POSEIDON, ZL_SLOT_EDWARDS}) {
         if (x < 0 || x >= ZL_SLOT_COUNT) return false;
         owners[x]++;
     }
@@ -190,6 +193,7 @@ static_assert(ZL_SLOT_DECODE_IN != ZL_SLOT_PAIR_IN && ZL_SLOT_DECODE_OUT != ZL_S
 static_assert(ZL_SLOT_PAIR_FEXP != ZL_SLOT_PAIR_ACC && ZL_SLOT_PAIR_FEXP != ZL_SLOT_PAIR_IN && ZL_SLOT_PAIR_FEXP != ZL_SLOT_PAIR_PREP && ZL_SLOT_PAIR_FEXP != ZL_SLOT_PAIR_LINES &&
                   ZL_SLOT_PAIR_FEXP != ZL_SLOT_DECODE_IN && ZL_SLOT_PAIR_FEXP != ZL_SLOT_DECODE_OUT,
               "the final exponentiations read a groups launch's accumulators in place and run inside the bytes-in verifier: their own slot");
+static_assert(ZL_SLOT_EDWARDS != ZL_SLOT_POSEIDON, "a hybrid call holds its shared secrets while the duplex call underneath stages its own chunk");
 static_assert(ZL_SLOT_TMP_A == ZL_MSM_SET[0].sort_a && ZL_SLOT_TMP_B == ZL_MSM_SET[0].sort_b && ZL_SLOT_NTT_VEC == ZL_MSM_SET[0].sort_b,
               "the general temporaries and the transform's vector are set 0's sort pair and nothing else (see the map)");
 struct zl_twiddles {
