@@ -289,7 +289,8 @@ int zl_circuit_poseidon_encrypt_witness(zl_curve_t curve, unsigned width, const 
  * come through host staging of at most 64 MiB at a time.  The resident circuit must have the SHAPE (2 + N rate + H, K + N rate + 3 S, 3 S + 1 + N rate) of the
  * stated parameters, else ZL_EINVAL; error order and dispatch bounds are zl_groth16_prove_batch's and are not moved ((K, H, N) = (2, 0, 1) has a domain of 2^10 at
  * every width).  Device-resident inputs: _assignments_dev, then zl_groth16_prove_batch_dev.
- * SHAPES.  n_instance >= 4 tells this family from every other (2).  Within it the shape fixes K, N rate, H and S: n_witness - (n_constraints - 1) = K, then
+ * SHAPES.  n_instance >= 4 tells this family from every other (2) but one: the scalar-multiplication circuits (zl_circuit_ed_scalar_mul) have n_instance = 5,
+ * and cannot share a shape with an encryption -- theirs is (5, 14 bits - 10, 14 bits - 8), which would need K = n_witness - (n_constraints - 1) = -1.  Within it the shape fixes K, N rate, H and S: n_witness - (n_constraints - 1) = K, then
  * n_witness = K + N rate + 3 S and n_constraints = 3 S + 1 + N rate give N rate and S, and n_instance = 2 + N rate + H gives H.  At ONE width two tuples of one
  * shape are therefore the same tuple.  Across widths they need N (W - 1) = N' (W' - 1) and S(W, K, H, N) = S(W', K, H, N'); an exhaustive walk over the limits
  * (tests/test_poseidon_encrypt_assignments_cpu.py repeats it) finds exactly ONE such pair: (W, K, H, N) = (5, 15, 15, 5) and (6, 15, 15, 4), both with 20 text
@@ -594,6 +595,43 @@ int zl_hybrid_decrypt_batch(zl_ctx* ctx, zl_curve_t curve, unsigned width, const
 int zl_hybrid_decrypt_batch_dev(zl_ctx* ctx, zl_curve_t curve, unsigned width, const uint64_t* initial_state, const void* d_sks, size_t sk_stride, const void* d_epks_xy,
                                 const void* d_headers, size_t header_len, const void* d_ciphertexts, const void* d_tags, size_t blocks, size_t count, unsigned flags,
                                 void* d_plaintexts, uint8_t* ok_each, void* d_status);
+/* The scalar multiplication in circuit (host compilers): "the public point Q is s P for the public point P and a secret scalar s" -- what the reference's
+ * DiffieHellman<S, G> runs under a compiler in derive, agree, generate_secret and reconstruct_secret.  The gadget (csrc/zl_host.h, namespace edwards) follows
+ * r1cs-std's affine twisted-Edwards variable and its default double-and-add scalar_mul_le; it is restated from the published formulas and NOT compared with
+ * arkworks matrices: the reference holds none.  1 <= bits <= the bit length of l (252 for ZL_BLS12_381, 251 for ZL_BN254); s < 2^bits and s < l.
+ * Public inputs: P.x, P.y, Q.x, Q.y.  Witnesses: s, its bits b_0 .. b_{bits-1} (Boolean, least significant first), then R_1 = (select(b_0, P.x, 0),
+ * select(b_0, P.y, 1)), then per step i = 1 .. bits - 1 thirteen records: xy, xx, yy, M.x, M.y of M_i = 2 M_{i-1} (M_0 = P; (a xx + yy) M.x = 2 xy,
+ * (2 - a xx - yy) M.y = yy - a xx), u, v0, v1, w, T.x, T.y of T = R_i + M_i (u = (y1 - a x1)(x2 + y2), v0 = x1 y2, v1 = x2 y1, w = v0 v1,
+ * (1 + d w) T.x = v0 + v1, (1 - d w) T.y = u + a v0 - v1), and R_{i+1} = (select(b_i, T.x, R_i.x), select(b_i, T.y, R_i.y)).  Rows: one per bit, sum 2^i b_i
+ * = s, one per record, Q.x and Q.y bound last.  SHAPE, derived again: n_instance = 1 + 4; n_witness = 1 + bits + 2 + 13 (bits - 1) = 14 bits - 10;
+ * n_constraints = bits + 1 + 2 + 13 (bits - 1) + 2 = 14 bits - 8: 3 520 rows on Jubjub and 3 506 on Baby Jubjub at full width.  P is a public input: the
+ * verifier checks that it is on the curve, the circuit does not.  n_instance = 5 cannot be an encryption's shape either: that family has K = n_witness -
+ * (n_constraints - 1) >= 1, here it is -1 (tests/test_ed_circuit_host.py repeats the arithmetic); every other family has n_instance = 2.
+ * _witness: the same circuit in the witness-only compiler, assignments equal word for word.  zl_circuit_witness_only_compatible: 1 when a FULL compiler
+ * folded constants the way a witness-only run of the same circuit code will (it holds for every circuit of this header), else 0.
+ * ZL_EINVAL: an unknown curve, bits out of range, a coordinate >= q, a point off the curve, a scalar >= l or >= 2^bits, a null pointer.
+ * The complete ASSIGNMENTS, one device lane per row (k_ed_mul_trace: the ladder in extended coordinates, one inversion a lane, the affine records by
+ * Montgomery's trick), word for word what both compilers export:
+ *   [0] = 1   [1 .. 5) P, Q   [5] s   [6 .. 6 + bits) the bits   then R_1   then the 13 records of every step in the order above
+ * zl_ed_scalar_mul_assignment_elems = 14 bits - 5; 0 for a parameter out of range.  The host-pointer form writes count dense rows: ctx == NULL or a count below
+ * ZL_TUNE_ED_DEV_MIN runs the byte-identical host mirror over the host pool; otherwise staged in chunks of ZL_TUNE_ED_CHUNK rows under the 256 MiB budget (a row
+ * at full width is about 113 KB: some 2 300 rows a chunk); finished on return; an item the circuit would refuse is ZL_EINVAL through the flag word.  The _dev
+ * form takes DEVICE pointers and never the host path (ctx == NULL is ZL_EINVAL): row i starts at d_out + i * stride_elems elements, stride_elems >= the row
+ * length, elements behind the row are not written, d_out must be 16-byte aligned and must not overlap the inputs.  point_stride is 0 (one point for all) or 1.
+ * zl_groth16_prove_ed_scalar_muls: from HOST points and scalars to proofs -- proofs[j] is byte for byte what zl_groth16_prove_resident returns for row j with
+ * (r[j], s[j]); results_out (count x 8 words, may be NULL) receives Q; the multiplication runs ONCE.  The resident circuit must have the shape (5, 14 bits - 10,
+ * 14 bits - 8), else ZL_EINVAL; error order and dispatch bounds are zl_groth16_prove_batch's and are not moved: bits <= 146 has a domain of at most 2^11 and takes
+ * the device batch path from 64 proofs, full width (2^12) loops the resident prover over rows staged at most 64 MiB at a time. */
+int zl_circuit_ed_scalar_mul(zl_curve_t curve, unsigned bits, const uint64_t* point_xy, const uint64_t* scalar, zl_circuit** out);
+int zl_circuit_ed_scalar_mul_witness(zl_curve_t curve, unsigned bits, const uint64_t* point_xy, const uint64_t* scalar, zl_circuit** out);
+int zl_circuit_witness_only_compatible(const zl_circuit* c); /* 1 / 0 */
+size_t zl_ed_scalar_mul_assignment_elems(zl_curve_t curve, unsigned bits);
+int zl_ed_scalar_mul_assignments(zl_ctx* ctx, zl_curve_t curve, unsigned bits, const uint64_t* points_xy, size_t point_stride, const uint64_t* scalars, size_t count,
+                                 uint64_t* out);
+int zl_ed_scalar_mul_assignments_dev(zl_ctx* ctx, zl_curve_t curve, unsigned bits, const void* d_points_xy, size_t point_stride, const void* d_scalars, size_t count,
+                                     void* d_out, size_t stride_elems);
+int zl_groth16_prove_ed_scalar_muls(zl_ctx* ctx, const zl_g16_pk* pk, uint64_t r1cs_handle, unsigned bits, const uint64_t* points_xy, size_t point_stride,
+                                    const uint64_t* scalars, const uint64_t* r, const uint64_t* s, size_t count, zl_g16_proof* proofs, uint64_t* results_out);
 
 /* ---- per-call device timing (HIP events on the ctx's stream) -------------------------------------------- */
 typedef struct zl_timing {

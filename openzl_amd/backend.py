@@ -55,6 +55,8 @@ ABI_SYMBOLS = [
     "zl_poseidon_encrypt_assignment_elems", "zl_poseidon_encrypt_assignments", "zl_poseidon_encrypt_assignments_dev", "zl_groth16_prove_poseidon_encryptions",
     "zl_ed_params", "zl_ed_add", "zl_ed_scalar_mul", "zl_ed_scalar_mul_batch", "zl_ed_scalar_mul_batch_dev",
     "zl_hybrid_encrypt_batch", "zl_hybrid_encrypt_batch_dev", "zl_hybrid_decrypt_batch", "zl_hybrid_decrypt_batch_dev",
+    "zl_circuit_ed_scalar_mul", "zl_circuit_ed_scalar_mul_witness", "zl_circuit_witness_only_compatible", "zl_ed_scalar_mul_assignment_elems",
+    "zl_ed_scalar_mul_assignments", "zl_ed_scalar_mul_assignments_dev", "zl_groth16_prove_ed_scalar_muls",
 ]
 ZL_ED_CHECK_SUBGROUP = 1
 
@@ -175,6 +177,14 @@ def load_library(path: Optional[str] = None):
     L.zl_hybrid_decrypt_batch.argtypes = [vp, C.c_int, C.c_uint, u64p, u64p, C.c_size_t, u64p, u64p, C.c_size_t, u64p, u64p, C.c_size_t, C.c_size_t, C.c_uint, u64p, u8p,
                                           u8p]
     L.zl_hybrid_decrypt_batch_dev.argtypes = [vp, C.c_int, C.c_uint, u64p, vp, C.c_size_t, vp, vp, C.c_size_t, vp, vp, C.c_size_t, C.c_size_t, C.c_uint, vp, u8p, vp]
+    L.zl_circuit_ed_scalar_mul.argtypes = [C.c_int, C.c_uint, u64p, u64p, C.POINTER(vp)]
+    L.zl_circuit_ed_scalar_mul_witness.argtypes = L.zl_circuit_ed_scalar_mul.argtypes
+    L.zl_circuit_witness_only_compatible.argtypes = [vp]
+    L.zl_ed_scalar_mul_assignment_elems.argtypes = [C.c_int, C.c_uint]
+    L.zl_ed_scalar_mul_assignment_elems.restype = C.c_size_t
+    L.zl_ed_scalar_mul_assignments.argtypes = [vp, C.c_int, C.c_uint, u64p, C.c_size_t, u64p, C.c_size_t, u64p]
+    L.zl_ed_scalar_mul_assignments_dev.argtypes = [vp, C.c_int, C.c_uint, vp, C.c_size_t, vp, C.c_size_t, vp, C.c_size_t]
+    L.zl_groth16_prove_ed_scalar_muls.argtypes = [vp, C.POINTER(G16PkC), C.c_uint64, C.c_uint, u64p, C.c_size_t, u64p, u64p, u64p, C.c_size_t, C.POINTER(G16ProofC), u64p]
     L.zl_circuit_poseidon_encrypt.argtypes = [C.c_int, C.c_uint, u64p, u64p, C.c_size_t, u64p, C.c_size_t, u64p, C.c_size_t, C.POINTER(vp)]
     L.zl_circuit_poseidon_encrypt_witness.argtypes = L.zl_circuit_poseidon_encrypt.argtypes
     L.zl_poseidon_encrypt_assignment_elems.argtypes = [C.c_uint, C.c_size_t, C.c_size_t, C.c_size_t]
@@ -643,6 +653,36 @@ class Backend:
         """zl_ed_scalar_mul_batch_dev on device addresses (d_status may be 0: a refused item then fails the call); finished on return"""
         self._check(self.L.zl_ed_scalar_mul_batch_dev(self._ctx, curve, C.c_void_p(d_points), point_stride, C.c_void_p(d_scalars), scalar_stride, count,
                                                       ZL_ED_CHECK_SUBGROUP if check_subgroup else 0, C.c_void_p(d_out), C.c_void_p(d_status)), "zl_ed_scalar_mul_batch_dev")
+
+    def ed_scalar_mul_assignments(self, curve: int, points, scalars, bits: Optional[int] = None) -> np.ndarray:
+        """zl_ed_scalar_mul_assignments: points (count, 2, 4) or one point (2, 4), scalars (count, 4) -> (count, ed_scalar_mul_assignment_elems(curve, bits), 4)
+        canonical words, row i the complete assignment of Circuit.ed_scalar_mul(curve, points[i], scalars[i], bits); bits None: the full width of the curve"""
+        return _ed_scalar_mul_assignments(self.L, self._ctx, curve, points, scalars, bits)
+
+    def ed_scalar_mul_assignments_dev(self, curve: int, bits: int, d_points: int, point_stride: int, d_scalars: int, count: int, d_out: int,
+                                      stride_elems: Optional[int] = None):
+        """zl_ed_scalar_mul_assignments_dev on device addresses -> row i at d_out + i * stride_elems elements (default: the row length); finished on return"""
+        stride = self.L.zl_ed_scalar_mul_assignment_elems(curve, bits) if stride_elems is None else stride_elems
+        self._check(self.L.zl_ed_scalar_mul_assignments_dev(self._ctx, curve, bits, C.c_void_p(d_points), point_stride, C.c_void_p(d_scalars), count, C.c_void_p(d_out),
+                                                            stride), "zl_ed_scalar_mul_assignments_dev")
+
+    def _prove_scalar_muls(self, pkc, curve: int, r1cs_handle: int, bits: int, points, scalars, r: np.ndarray, s: np.ndarray):
+        (p, ps), k = _ed_operand(points, 2, "points"), np.ascontiguousarray(np.asarray(scalars, dtype=np.uint64)).reshape(-1, 4)
+        count = k.shape[0]
+        if ps and p.shape[0] != count:
+            raise ValueError("operands of different counts")
+        r, s = np.ascontiguousarray(r, dtype=np.uint64).reshape(count, 4), np.ascontiguousarray(s, dtype=np.uint64).reshape(count, 4)
+        out = (G16ProofC * max(1, count))()
+        q = np.zeros((count, 2, 4), dtype=np.uint64)
+        self._check(self.L.zl_groth16_prove_ed_scalar_muls(self._ctx, C.byref(pkc), r1cs_handle, bits, _p64(p), ps, _ptr_or_none(k), _ptr_or_none(r), _ptr_or_none(s), count,
+                                                           out, _ptr_or_none(q)), "zl_groth16_prove_ed_scalar_muls")
+        return [_proof_tuple(curve, pr) for pr in out[:count]], q
+
+    def groth16_prove_ed_scalar_muls(self, curve: int, pk: dict, r1cs_handle: int, bits: int, points, scalars, r: np.ndarray, s: np.ndarray):
+        """zl_groth16_prove_ed_scalar_muls: points (count, 2, 4) or one (2, 4), scalars (count, 4) and blinding scalars -> (`count` proofs, Q (count, 2, 4)): the
+        public inputs of proof j are points[j] and Q[j]"""
+        pkc, keep_pk = _pk_struct(curve, pk)
+        return self._prove_scalar_muls(pkc, curve, r1cs_handle, bits, points, scalars, r, s)
 
     def hybrid_encrypt(self, curve: int, initial_state, generator, esk, pks, headers, plaintexts, check_subgroup: bool = False):
         """zl_hybrid_encrypt_batch: generator (2, 4), esk (count, 4), pks (count, 2, 4) or one (2, 4), headers (count, H, 4), plaintexts (count, N, W - 1, 4) ->
@@ -1729,6 +1769,34 @@ def ed_scalar_mul_host(curve: int, points, scalars, check_subgroup: bool = False
     return _ed_scalar_mul(load_library(), None, curve, points, scalars, check_subgroup)
 
 
+def ed_order_bits(curve: int) -> int:
+    """bit length of the embedded curve's subgroup order: the full width of a scalar-multiplication circuit (252 Jubjub, 251 Baby Jubjub)"""
+    return ed_params(curve)["order"].bit_length()
+
+
+def ed_scalar_mul_assignment_elems(curve: int, bits: int) -> int:
+    """elements of one scalar-multiplication assignment: 14 bits - 5 (0 for a parameter out of range)"""
+    if not 0 <= bits < 2**32:
+        return 0
+    return int(load_library().zl_ed_scalar_mul_assignment_elems(curve, bits))
+
+
+def _ed_scalar_mul_assignments(L, ctx, curve: int, points, scalars, bits) -> np.ndarray:
+    (p, ps), k = _ed_operand(points, 2, "points"), np.ascontiguousarray(np.asarray(scalars, dtype=np.uint64)).reshape(-1, 4)
+    count = k.shape[0]
+    if ps and p.shape[0] != count:
+        raise ValueError("operands of different counts")
+    bits = ed_order_bits(curve) if bits is None else bits
+    out = np.zeros((count, ed_scalar_mul_assignment_elems(curve, bits), 4), dtype=np.uint64)
+    _pos_check(L, L.zl_ed_scalar_mul_assignments(ctx, curve, bits, _p64(p), ps, _ptr_or_none(k), count, _ptr_or_none(out)), "zl_ed_scalar_mul_assignments")
+    return out
+
+
+def ed_scalar_mul_assignments_host(curve: int, points, scalars, bits=None) -> np.ndarray:
+    """Backend.ed_scalar_mul_assignments on the host mirror"""
+    return _ed_scalar_mul_assignments(load_library(), None, curve, points, scalars, bits)
+
+
 def _hybrid_encrypt(L, ctx, curve: int, initial_state, generator, esk, pks, headers, plaintexts, check_subgroup: bool):
     t = np.ascontiguousarray(np.asarray(plaintexts, dtype=np.uint64))
     h = np.ascontiguousarray(np.asarray(headers, dtype=np.uint64))
@@ -2249,6 +2317,33 @@ class Circuit:
         self._export()
         return self
 
+    @classmethod
+    def ed_scalar_mul(cls, curve: int, point, scalar: int, bits: Optional[int] = None, witness_only: bool = False) -> "Circuit":
+        """the scalar-multiplication circuit (zl_circuit_ed_scalar_mul): the public point Q is `scalar` times the public `point` (x, y) of the embedded curve, for a
+        secret scalar below the subgroup order and below 2^bits; bits None: the full width of the curve.  Public inputs: P.x, P.y, Q.x, Q.y.  witness_only: as
+        in the constructor."""
+        what = "zl_circuit_ed_scalar_mul"
+        self = cls.__new__(cls)
+        self.L = load_library()
+        self.curve = curve
+        self.witness_only = witness_only
+        self._c = C.c_void_p()
+        bits = ed_order_bits(curve) if bits is None else bits
+        vals = [int(point[0]), int(point[1]), int(scalar)]
+        if any(not 0 <= v < 2**256 for v in vals) or not 0 <= bits < 2**32:
+            raise BackendError(-1, what)
+        w = np.array([[(v >> (64 * j)) & (2**64 - 1) for j in range(4)] for v in vals], dtype=np.uint64)
+        fn = self.L.zl_circuit_ed_scalar_mul_witness if witness_only else self.L.zl_circuit_ed_scalar_mul
+        rc = fn(curve, bits, _p64(w[:2]), _p64(w[2]), C.byref(self._c))
+        if rc:
+            raise BackendError(rc, what)
+        self._export()
+        return self
+
+    def witness_only_compatible(self) -> bool:
+        """a full compiler folded constants the way a witness-only run of the same circuit will (R1CS::witness_only_compatible)"""
+        return self.L.zl_circuit_witness_only_compatible(self._c) == 1
+
     @property
     def shape(self):
         return self._view.n_constraints, self._view.n_instance, self._view.n_witness
@@ -2452,6 +2547,14 @@ class Groth16Keys:
         headers[j], plaintexts[j]).  Keys of a circuit that has not the shape of the operands' (W, K, H, N) are refused by the library (ZL_EINVAL)."""
         self._upload_r1cs()
         return (lane or self.backend)._prove_encryptions(self.pk, self.circuit.curve, self._r1cs, initial_state, keys, headers, plaintexts, r, s)
+
+    def prove_scalar_muls(self, points, scalars, r: np.ndarray, s: np.ndarray, bits: Optional[int] = None, lane: Optional[Backend] = None):
+        """zl_groth16_prove_ed_scalar_muls over this key: points (count, 2, 4) or one point (2, 4), scalars (count, 4) and blinding scalars r, s (count, 4) ->
+        (proofs, Q (count, 2, 4)); proof j is prove_batch's for the assignment of Circuit.ed_scalar_mul(curve, points[j], scalars[j], bits).  bits None: the
+        full width.  Keys of a circuit of another `bits` are refused by the library (ZL_EINVAL)."""
+        self._upload_r1cs()
+        bits = ed_order_bits(self.circuit.curve) if bits is None else bits
+        return (lane or self.backend)._prove_scalar_muls(self.pk, self.circuit.curve, self._r1cs, bits, points, scalars, r, s)
 
     def _leaf_ready(self, what: str):
         shape = self.merkle_leaf_shape()

@@ -138,6 +138,9 @@ struct zl_scratch {
 //     the chunks of a call follow each other on ctx->stream.  Its own slot: a caller may hold device operands for the _dev forms in any other block.
 //   * ZL_SLOT_EDWARDS: the flag word, the per-lane window tables and one staged chunk of the embedded-curve entry points (zl_edwards_dev.hip), under a byte
 //     budget.  Its own slot: the hybrid calls keep the shared secrets of a chunk here while the duplex call underneath stages through ZL_SLOT_POSEIDON.
+//     The assignment trace (k_ed_mul_trace) takes NO bytes of it for its kernel: the points it keeps between its passes live in the row's own step cells
+//     (8 elements of 48 B in the 416 B of a step).  Only its staged operands count: 64 + 32 B of inputs, and, in the host-pointer form, the row itself
+//     (14 bits - 5 elements: 112 736 B at 252 bits, so some 2 300 rows a chunk under the 256 MiB budget) and 64 B for Q.
 enum zl_slot : int {
     ZL_SLOT_SET0_COUNTS = 0, ZL_SLOT_SET0_ENTRIES = 1, ZL_SLOT_SET0_BUCKETS = 2, ZL_SLOT_SET0_PARTIALS = 3, ZL_SLOT_SET0_TAIL = 4,
     ZL_SLOT_SORT_A = 5, ZL_SLOT_SORT_B = 6,

@@ -81,14 +81,18 @@ struct EdBounds {
     static constexpr int DBL_MUL = ed_max(ed_max(A < 0 ? PROD * DBL_NEGY : PROD * PROD, DBL_E * DBL_F), ed_max(ed_max(DBL_G * DBL_H, DBL_E * DBL_H), DBL_F * DBL_G));
     // on-curve test and identity test: what canon sees
     static constexpr int CANON = ed_max(PROD + (1 << ed_bias(PROD)), SUM2);
-    static constexpr int MAX_MUL = ed_max(ADD_MUL, DBL_MUL);
-    static constexpr int MAX_J = ed_max(ed_max(ADD_J_E, ADD_J_F), ed_max(ed_max(ADD_J_H, DBL_J_NEG), ed_max(DBL_J_D, DBL_J_F)));
+    // the assignment trace (trace_item): u = (y1 - a x1)(x2 + y2) from loaded affine values, every other record a product of two of them
+    static constexpr int TRACE_J_U = ed_bias(PROD), TRACE_U_LEFT = A < 0 ? SUM2 : PROD + (1 << TRACE_J_U);  // a = +1 only: y1 - x1
+    static constexpr int TRACE_MUL = ed_max(TRACE_U_LEFT * SUM2, PROD * PROD);
+    static constexpr int MAX_MUL = ed_max(ed_max(ADD_MUL, DBL_MUL), TRACE_MUL);
+    static constexpr int MAX_J = ed_max(ed_max(ed_max(ADD_J_E, ADD_J_F), TRACE_J_U), ed_max(ed_max(ADD_J_H, DBL_J_NEG), ed_max(DBL_J_D, DBL_J_F)));
     static_assert(MAX_MUL <= P::MUL_BOUND, "a bound product above what mul takes");
     static_assert(MAX_J <= P::KQ_MAX, "subk: the table holds every bias");
     static_assert(CANON <= 128 && DBL_F <= 128 && ADD_E <= 128, "canon and the carried sums stay below 128 q");
 };
 static_assert(EdBounds<BLS12_381_Fr>::ADD_MUL == 60 && EdBounds<BLS12_381_Fr>::DBL_MUL == 60 && EdBounds<BLS12_381_Fr>::MAX_J == 3, "Jubjub: 60 of 70");
 static_assert(EdBounds<BN254_Fr>::ADD_MUL == 60 && EdBounds<BN254_Fr>::DBL_MUL == 48 && EdBounds<BN254_Fr>::MAX_J == 3, "Baby Jubjub: 60 of 169");
+static_assert(EdBounds<BLS12_381_Fr>::TRACE_MUL == 16 && EdBounds<BN254_Fr>::TRACE_MUL == 24, "the assignment trace: 16 and 24, below the group law's 60");
 
 // ---- elements
 template <class FrP>
@@ -342,6 +346,186 @@ ZL_HD uint8_t mul_item(const uint64_t* p_xy, const uint64_t* k, bool check_subgr
     else store_identity(out_xy);
     return st;
 }
+// ---- the complete assignment of zl_circuit_ed_scalar_mul (zl_host.h edwards::scalar_mul_le), one item: row = 14 bits - 5 elements of 4 canonical words,
+//   [0] 1   [1..5) P.x P.y Q.x Q.y   [5] s   [6 .. 6 + bits) the bits   then R_1 = (select(b_0, P.x, 0), select(b_0, P.y, 1))   then per step i = 1 .. bits - 1
+//   the 13 records   xy xx yy M.x M.y | u v0 v1 w T.x T.y | R.x R.y   of M_i = 2 M_{i-1} (M_0 = P), T = R_i + M_i, R_{i+1} = b_i ? T : R_i.
+// Every record is an AFFINE coordinate or a product of affine coordinates; an inversion per group operation would cost 2 (bits - 1) Fermat ladders.  Instead:
+//   pass 1  the ladder in extended coordinates (dbl, add, a select of registers by b_i); X, Y, Z of every M_i and T_i and the product of all Z in FRONT of each
+//           are kept as raw limbs (x R', bounded, 9 words padded to 12) in the step's OWN 13 cells -- 8 elements of 48 B in 416 B; nothing else lives there yet;
+//   one inversion of the product of all Z (skipped at bits = 1: no step);
+//   pass 2  back down the steps (Montgomery's trick: Z^-1 = run * prefix, run *= Z): all 8 kept elements of a step are read before the step's M.x M.y T.x T.y
+//           are stored in their cells, canonical;
+//   pass 3  up again: the other 9 records of each step by plain products of the canonical affine values read back from those four cells (R_i is carried: it
+//           is only known going up), the selects as copies of words.
+// Bounds (units of q): a cell read back is loaded (a product: < 2); xy xx yy v0 v1 w: 2 * 2; x2 + y2 < 4; y1 - a x1: a = -1 a sum < 4, a = +1 a difference
+// with bias 4 < 6: u at 6 * 4 = 24; pass 2's run * prefix, run * Z, X Z^-1 are products of products: EdBounds::TRACE_MUL.  Per step 19 + 12 + 18 products.
+// An item with a coordinate >= q, a point off the curve or a scalar >= l or >= 2^bits returns false; its row is computed by the same instructions from
+// whatever the operands are (no address depends on data) and is unspecified.
+constexpr int STEP_RECORDS = 13, KEPT_WORDS64 = 6;  // a kept element: 9 limbs in 48 bytes
+static_assert(8 * KEPT_WORDS64 <= STEP_RECORDS * 4, "the 8 kept elements of a step fit the step's 13 cells");
+template <class FrP>
+constexpr unsigned order_bits() {  // bit length of l: 252 (Jubjub), 251 (Baby Jubjub)
+    unsigned n = 0;
+    for (uint32_t top = Curve<FrP>::l(7); top; top >>= 1) n++;
+    return 224 + n;
+}
+static_assert(order_bits<BLS12_381_Fr>() == 252 && order_bits<BN254_Fr>() == 251, "the scalar widths of the two curves");
+constexpr size_t trace_row_elems(unsigned bits) { return 14 * (size_t)bits - 5; }
+static_assert(trace_row_elems(252) == 3523 && trace_row_elems(251) == 3509, "n_instance + n_witness = 5 + (14 bits - 10); 3 520 and 3 506 rows at full width");
+ZL_HD void put_cell(uint64_t* cell, uint64_t a, uint64_t b, uint64_t c, uint64_t d) {  // one element of canonical words; 16-byte aligned on the device
+#ifdef __HIP_DEVICE_COMPILE__
+    ulonglong2* q = reinterpret_cast<ulonglong2*>(cell);
+    q[0] = make_ulonglong2(a, b);
+    q[1] = make_ulonglong2(c, d);
+#else
+    cell[0] = a; cell[1] = b; cell[2] = c; cell[3] = d;
+#endif
+}
+template <class FrP>
+ZL_HD void put_elem(uint64_t* cell, const El<FrP>& m) {
+    uint64_t w[4];
+    store<FrP>(w, m);
+    put_cell(cell, w[0], w[1], w[2], w[3]);
+}
+template <class FrP>
+ZL_HD void keep(uint64_t* at, const El<FrP>& e) {  // raw limbs, as they are
+    static_assert(El<FrP>::L == 9, "nine limbs in 48 bytes");
+    put_cell(at, (uint64_t)e.l[0] | ((uint64_t)e.l[1] << 32), (uint64_t)e.l[2] | ((uint64_t)e.l[3] << 32), (uint64_t)e.l[4] | ((uint64_t)e.l[5] << 32),
+             (uint64_t)e.l[6] | ((uint64_t)e.l[7] << 32));
+    at[4] = e.l[8];
+}
+template <class FrP>
+ZL_HD El<FrP> kept(const uint64_t* at) {
+    El<FrP> e;
+#pragma unroll
+    for (int i = 0; i < 4; i++) {
+        e.l[2 * i] = (uint32_t)at[i];
+        e.l[2 * i + 1] = (uint32_t)(at[i] >> 32);
+    }
+    e.l[8] = (uint32_t)at[4];
+    return e;
+}
+ZL_HD bool scalar_bit(const uint64_t* k, unsigned i) { return (k[i >> 6] >> (i & 63)) & 1u; }
+template <class FrP>
+ZL_HD El<FrP> pick(bool take, const El<FrP>& a, const El<FrP>& b) {  // limb by limb: registers, never a copy through memory
+    El<FrP> r;
+#pragma unroll
+    for (int i = 0; i < El<FrP>::L; i++) r.l[i] = take ? a.l[i] : b.l[i];
+    return r;
+}
+template <class FrP>
+ZL_HD Pt<FrP> pick(bool take, const Pt<FrP>& a, const Pt<FrP>& b) {
+    return Pt<FrP>{pick<FrP>(take, a.X, b.X), pick<FrP>(take, a.Y, b.Y), pick<FrP>(take, a.Z, b.Z), pick<FrP>(take, a.T, b.T)};
+}
+template <class FrP>
+ZL_HD bool trace_item(const uint64_t* p_xy, const uint64_t* k, unsigned bits, uint64_t* row, uint64_t* q_out) {
+    using B = EdBounds<FrP>;
+    El<FrP> x, y;
+    bool ok = load<FrP>(p_xy, x);
+    ok &= load<FrP>(p_xy + 4, y);
+    ok &= on_curve<FrP>(x, y);
+    ok &= scalar_ok<FrP>(k);
+#pragma unroll 1
+    for (unsigned i = bits; i < 256; i++) ok &= !scalar_bit(k, i);
+    uint64_t* bit_cells = row + 24;
+    uint64_t* sel0 = bit_cells + (size_t)bits * 4;
+    uint64_t* steps = sel0 + 8;
+    put_cell(row, 1, 0, 0, 0);
+    put_cell(row + 4, p_xy[0], p_xy[1], p_xy[2], p_xy[3]);
+    put_cell(row + 8, p_xy[4], p_xy[5], p_xy[6], p_xy[7]);
+    put_cell(row + 20, k[0], k[1], k[2], k[3]);
+#pragma unroll 1
+    for (unsigned i = 0; i < bits; i++) put_cell(bit_cells + (size_t)i * 4, scalar_bit(k, i) ? 1 : 0, 0, 0, 0);
+    const bool b0 = scalar_bit(k, 0);
+    if (b0) {
+        put_cell(sel0, p_xy[0], p_xy[1], p_xy[2], p_xy[3]);
+        put_cell(sel0 + 4, p_xy[4], p_xy[5], p_xy[6], p_xy[7]);
+    } else {
+        put_cell(sel0, 0, 0, 0, 0);
+        put_cell(sel0 + 4, 1, 0, 0, 0);
+    }
+    if (bits > 1) {
+        const El<FrP> d = coeff_d<FrP>();
+        // pass 1
+        Pt<FrP> m = from_affine<FrP>(x, y), r = pick<FrP>(b0, m, identity<FrP>());
+        El<FrP> pre = small<FrP>(1);
+#pragma unroll 1
+        for (unsigned i = 1; i < bits; i++) {
+            uint64_t* at = steps + (size_t)(i - 1) * STEP_RECORDS * 4;
+            m = dbl<FrP>(m, true);
+            keep<FrP>(at, m.X);
+            keep<FrP>(at + KEPT_WORDS64, m.Y);
+            keep<FrP>(at + 2 * KEPT_WORDS64, m.Z);
+            keep<FrP>(at + 3 * KEPT_WORDS64, pre);
+            pre = zl::mul(pre, m.Z);
+            const Pt<FrP> t = add<FrP>(r, m, d);
+            keep<FrP>(at + 4 * KEPT_WORDS64, t.X);
+            keep<FrP>(at + 5 * KEPT_WORDS64, t.Y);
+            keep<FrP>(at + 6 * KEPT_WORDS64, t.Z);
+            keep<FrP>(at + 7 * KEPT_WORDS64, pre);
+            pre = zl::mul(pre, t.Z);
+            r = pick<FrP>(scalar_bit(k, i), t, r);
+        }
+        El<FrP> run = inv<FrP>(pre);  // (no Z of an on-curve item is zero: the law is complete)
+        // pass 2
+#pragma unroll 1
+        for (unsigned i = bits - 1; i >= 1; i--) {
+            uint64_t* at = steps + (size_t)(i - 1) * STEP_RECORDS * 4;
+            El<FrP> zi = zl::mul(run, kept<FrP>(at + 7 * KEPT_WORDS64));
+            run = zl::mul(run, kept<FrP>(at + 6 * KEPT_WORDS64));
+            const El<FrP> tx = zl::mul(kept<FrP>(at + 4 * KEPT_WORDS64), zi), ty = zl::mul(kept<FrP>(at + 5 * KEPT_WORDS64), zi);
+            zi = zl::mul(run, kept<FrP>(at + 3 * KEPT_WORDS64));
+            run = zl::mul(run, kept<FrP>(at + 2 * KEPT_WORDS64));
+            const El<FrP> mx = zl::mul(kept<FrP>(at), zi), my = zl::mul(kept<FrP>(at + KEPT_WORDS64), zi);
+            put_elem<FrP>(at + 3 * 4, mx);   // (every kept element of the step has been read)
+            put_elem<FrP>(at + 4 * 4, my);
+            put_elem<FrP>(at + 9 * 4, tx);
+            put_elem<FrP>(at + 10 * 4, ty);
+        }
+        // pass 3
+        El<FrP> px = x, py = y;  // M_{i-1} and R_i, affine
+        El<FrP> rx = pick<FrP>(b0, x, identity<FrP>().X), ry = pick<FrP>(b0, y, small<FrP>(1));
+        const uint64_t* sel = sel0;
+#pragma unroll 1
+        for (unsigned i = 1; i < bits; i++) {
+            uint64_t* at = steps + (size_t)(i - 1) * STEP_RECORDS * 4;
+            El<FrP> mx, my, tx, ty;
+            (void)load<FrP>(at + 3 * 4, mx);
+            (void)load<FrP>(at + 4 * 4, my);
+            put_elem<FrP>(at, zl::mul(px, py));
+            put_elem<FrP>(at + 4, zl::mul(px, px));
+            put_elem<FrP>(at + 2 * 4, zl::mul(py, py));
+            El<FrP> left;
+            if constexpr (B::A < 0) left = zl::add(ry, rx);
+            else left = sub<FrP, B::TRACE_J_U>(ry, rx);
+            put_elem<FrP>(at + 5 * 4, zl::mul(left, zl::add(mx, my)));
+            const El<FrP> v0 = zl::mul(rx, my), v1 = zl::mul(mx, ry);
+            put_elem<FrP>(at + 6 * 4, v0);
+            put_elem<FrP>(at + 7 * 4, v1);
+            put_elem<FrP>(at + 8 * 4, zl::mul(v0, v1));
+            (void)load<FrP>(at + 9 * 4, tx);  // (loaded whatever the bit: a wave does not diverge on the scalar)
+            (void)load<FrP>(at + 10 * 4, ty);
+            const bool take = scalar_bit(k, i);
+            rx = pick<FrP>(take, tx, rx);
+            ry = pick<FrP>(take, ty, ry);
+            const uint64_t* from = take ? at + 9 * 4 : sel;
+            put_cell(at + 11 * 4, from[0], from[1], from[2], from[3]);
+            put_cell(at + 12 * 4, from[4], from[5], from[6], from[7]);
+            sel = at + 11 * 4;
+            px = mx;
+            py = my;
+        }
+    }
+    const uint64_t* q = bits > 1 ? steps + ((size_t)(bits - 2) * STEP_RECORDS + 11) * 4 : sel0;
+    uint64_t qw[8];
+    for (int i = 0; i < 8; i++) qw[i] = q[i];
+    put_cell(row + 12, qw[0], qw[1], qw[2], qw[3]);
+    put_cell(row + 16, qw[4], qw[5], qw[6], qw[7]);
+    if (q_out)
+        for (int i = 0; i < 8; i++) q_out[i] = qw[i];
+    return ok;
+}
+
 // the host's table
 template <class FrP>
 struct LocalTab {

@@ -12,6 +12,8 @@
 //                    windows need no recoding -- come through wave-uniform loads.
 //   k_ed_mul_fixed<FrP>  k P for ONE point shared by the call (point_stride == 0): the host mirror builds the 63 x 16 table d 16^w P once per call, affine with d x y
 //                    precomputed (batch-inverted: one inversion), uploads it once, and every lane does 63 mixed additions and no doubling.
+//   k_ed_mul_trace<FrP>  the complete assignment of zl_circuit_ed_scalar_mul per item (ed::trace_item): the double-and-add ladder of the in-circuit gadget in extended
+//                    coordinates, ONE inversion a lane, every affine record by Montgomery's trick; no table, no scratch slot.
 // A lane at or above the item count returns before it reads or writes anything; a table is only touched by the lane that owns it.
 #include <string.h>
 #include <atomic>
@@ -19,6 +21,7 @@
 #include <vector>
 #include "zl_ctx.h"
 #include "zl_edwards.h"
+#include "zl_edwards_dev.h"
 
 using namespace openzl;
 
@@ -113,6 +116,20 @@ __global__ __launch_bounds__(BLOCK) void k_ed_mul_fixed(const uint32_t* __restri
     if (st == ed::ST_OK) ed::store_affine<FrP>(o, acc);
     else ed::store_identity(o);
     finish_item(p, st, o, out, status, keep, flag);
+}
+
+// The complete assignment of zl_circuit_ed_scalar_mul per item, one lane a row (ed::trace_item: the ladder in extended coordinates, ONE inversion a lane, the
+// affine records by Montgomery's trick -- the points kept between the passes live in the row's own not yet written step cells, so the kernel needs no scratch
+// slot).  Row p = out + p * stride elements, 16-byte aligned; a lane stores its 32-byte records directly at a stride of one row, the layout k_pos_chain_trace
+// kept (profiles/chain_trace_layout_ab.log: staging a block's records through LDS lost 12 - 15 % up to 2^16 rows); elements behind the row are not touched.
+// q_out (may be null): Q of every item, densely.  Rows and inputs do not overlap.
+template <class FrP>
+__global__ __launch_bounds__(BLOCK) void k_ed_mul_trace(const uint64_t* __restrict__ points, uint32_t point_stride, const uint64_t* __restrict__ scalars, uint32_t bits, size_t n,
+                                                        uint64_t* __restrict__ out, size_t stride, uint64_t* __restrict__ q_out, uint32_t* __restrict__ flag) {
+    const size_t p = (size_t)blockIdx.x * BLOCK + threadIdx.x;
+    if (p >= n) return;
+    const bool ok = ed::trace_item<FrP>(points + p * point_stride * 8, scalars + p * 4, bits, out + p * stride * 4, q_out ? q_out + p * 8 : nullptr);
+    if (!ok) atomicOr(flag, 1u);
 }
 
 // ---------------------------------------------------------------------------------------------------------------- host mirror
@@ -375,6 +392,37 @@ int dev_mul(zl_ctx* ctx, bool on_host_ptrs, const uint64_t* points, size_t ps, c
     });
 }
 
+// ---- the scalar-multiplication circuit's assignments: the kernel's text over the host pool, or the kernel
+template <class FrP>
+int host_trace(const uint64_t* points, size_t ps, const uint64_t* scalars, unsigned bits, size_t count, uint64_t* out, size_t nv) {
+    std::atomic<int> bad{0};
+    host_for(count, [&](size_t i) {
+        if (!ed::trace_item<FrP>(points + i * ps * 8, scalars + i * 4, bits, out + i * nv * 4, nullptr)) bad.store(1);
+    });
+    return bad.load() ? ZL_EINVAL : ZL_OK;
+}
+// Every device form.  points / scalars: staged per chunk when in_on_host, else device memory; host_rows != null: the rows are staged, dense, and downloaded
+// (d_rows and stride are ignored), otherwise row i goes to d_rows + i * stride elements; host_q != null: Q of every item is staged and downloaded.  A chunk is
+// one launch; a staged row counts nv * 32 bytes against the budget, so a full-width call of host rows runs about 2 300 rows a chunk.
+template <class FrP>
+int trace_run(zl_ctx* ctx, const uint64_t* points, size_t ps, const uint64_t* scalars, bool in_on_host, unsigned bits, size_t count, uint64_t* d_rows, size_t stride,
+              uint64_t* host_rows, uint64_t* host_q) {
+    const size_t nv = ed::trace_row_elems(bits);
+    std::vector<Seg> segs;
+    if (in_on_host) segs = {ps ? staged(64, points, nullptr) : staged_once(64, points), staged(32, scalars, nullptr)};
+    else segs = {device(ps * 64, points), device(32, scalars)};
+    segs.push_back(host_rows ? staged(nv * 32, nullptr, host_rows) : device(stride * 32, d_rows));
+    segs.push_back(staged(host_q ? 64 : 0, nullptr, host_q));
+    return run_chunks(ctx, count, false, segs, [&](size_t, size_t m, void* const* d, uint32_t*, uint32_t* flag) -> int {
+        ZL_ED_LAUNCH(ctx, (k_ed_mul_trace<FrP>), blocks_of(m), u64(d[0]), (uint32_t)ps, u64(d[1]), (uint32_t)bits, m, u64(d[2]), host_rows ? nv : stride, u64(d[3]), flag);
+        return ZL_OK;
+    });
+}
+template <class FrP>
+size_t trace_elems(unsigned bits) {
+    return bits >= 1 && bits <= ed::order_bits<FrP>() ? ed::trace_row_elems(bits) : 0;
+}
+
 // ---- hybrid encryption.  What a call is, beside its operands (checked by the entry points)
 struct HybridCall {
     zl_curve_t curve;
@@ -492,7 +540,35 @@ int hybrid_params(zl_curve_t curve, unsigned width, size_t header_len, size_t bl
 
 #define ZL_ED_CURVE(curve, fn, ...) ((curve) == ZL_BLS12_381 ? fn<BLS12_381_Fr>(__VA_ARGS__) : fn<BN254_Fr>(__VA_ARGS__))
 
+int zl_ed_scalar_mul_trace_rows(zl_ctx* ctx, int curve, unsigned bits, const uint64_t* points_xy, size_t point_stride, const uint64_t* scalars, size_t count, void* d_rows,
+                                size_t stride_elems, uint64_t* results_out) {
+    return ZL_ED_CURVE(curve, trace_run, ctx, points_xy, point_stride, scalars, true, bits, count, static_cast<uint64_t*>(d_rows), stride_elems, nullptr, results_out);
+}
+
 extern "C" {
+
+size_t zl_ed_scalar_mul_assignment_elems(zl_curve_t curve, unsigned bits) {
+    if (!valid_curve(curve)) return 0;
+    return ZL_ED_CURVE(curve, trace_elems, bits);
+}
+int zl_ed_scalar_mul_assignments(zl_ctx* ctx, zl_curve_t curve, unsigned bits, const uint64_t* points_xy, size_t point_stride, const uint64_t* scalars, size_t count,
+                                 uint64_t* out) {
+    const size_t nv = zl_ed_scalar_mul_assignment_elems(curve, bits);
+    if (nv == 0 || point_stride > 1 || (count && (!points_xy || !scalars || !out))) return ZL_EINVAL;
+    if (count == 0) return ZL_OK;
+    if (on_host(ctx, count)) return ZL_ED_CURVE(curve, host_trace, points_xy, point_stride, scalars, bits, count, out, nv);
+    ZL_HIP(ctx, hipSetDevice(ctx->device));
+    return ZL_ED_CURVE(curve, trace_run, ctx, points_xy, point_stride, scalars, true, bits, count, nullptr, 0, out, nullptr);
+}
+int zl_ed_scalar_mul_assignments_dev(zl_ctx* ctx, zl_curve_t curve, unsigned bits, const void* d_points_xy, size_t point_stride, const void* d_scalars, size_t count,
+                                     void* d_out, size_t stride_elems) {
+    const size_t nv = zl_ed_scalar_mul_assignment_elems(curve, bits);
+    if (!ctx || nv == 0 || point_stride > 1 || stride_elems < nv || ((uintptr_t)d_out & 15) || (count && (!d_points_xy || !d_scalars || !d_out))) return ZL_EINVAL;
+    if (count == 0) return ZL_OK;
+    ZL_HIP(ctx, hipSetDevice(ctx->device));
+    return ZL_ED_CURVE(curve, trace_run, ctx, static_cast<const uint64_t*>(d_points_xy), point_stride, static_cast<const uint64_t*>(d_scalars), false, bits, count,
+                       static_cast<uint64_t*>(d_out), stride_elems, nullptr, nullptr);
+}
 
 int zl_ed_params(zl_curve_t curve, uint64_t* a, uint64_t* d, uint64_t* order, uint64_t* cofactor) {
     if (!valid_curve(curve)) return ZL_EINVAL;

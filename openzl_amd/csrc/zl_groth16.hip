@@ -20,6 +20,7 @@
 #include <functional>
 #include "zl_ctx.h"
 #include "zl_poseidon_dev.h"
+#include "zl_edwards_dev.h"
 
 template <class FrP>
 __global__ void __launch_bounds__(256) k_fr_to_mont(Fp<FrP>* __restrict__ v, uint32_t n) {
@@ -1447,6 +1448,30 @@ extern "C" int zl_groth16_prove_poseidon_encryptions(zl_ctx* ctx, const zl_g16_p
             if (tags_out) memcpy(tags_out + (c0 + j) * 4, rows + j * nv * 4 + 4, 32);
             if (ciphertexts_out) memcpy(ciphertexts_out + (c0 + j) * T * 4, rows + j * nv * 4 + 8, T * 32);
         }
+        return rc;
+    };
+    return groth16_prove_batch_any(ctx, pk, rd, src, 0, r, s, count, proofs);
+}
+// Scalar multiplications on the embedded curve from point and scalar: the trace kernel writes each chunk's rows into the chunk's block, Q comes out beside them
+extern "C" int zl_groth16_prove_ed_scalar_muls(zl_ctx* ctx, const zl_g16_pk* pk, uint64_t r1cs_handle, unsigned bits, const uint64_t* points_xy, size_t point_stride,
+                                               const uint64_t* scalars, const uint64_t* r, const uint64_t* s, size_t count, zl_g16_proof* proofs, uint64_t* results_out) {
+    if (!ctx || !pk || point_stride > 1 || (count && (!points_xy || !scalars || !r || !s || !proofs))) return ZL_EINVAL;
+    const zl_r1cs_dev* rd = nullptr;
+    const int rc0 = g16_entry(ctx, pk, r1cs_handle, &rd);
+    if (rc0) return rc0;
+    const zl_curve_t curve = pk->curve;
+    const size_t nv = zl_ed_scalar_mul_assignment_elems(curve, bits);  // (0 for an unknown curve as well)
+    // the shape (5, 14 bits - 10, 14 bits - 8) with nv = 14 bits - 5; what the matrices say cannot be checked, as with a witness-only compiler
+    if (nv == 0 || rd->n_instance != 5 || rd->n_witness != nv - 5 || rd->n_constraints != nv - 3) return ZL_EINVAL;
+    if (count == 0) return ZL_OK;
+    G16BatchSource src;
+    src.fill_dev = [=](size_t c0, size_t ch, void* d_rows) {
+        return zl_ed_scalar_mul_trace_rows(ctx, (int)curve, bits, points_xy + c0 * point_stride * 8, point_stride, scalars + c0 * 4, ch, d_rows, nv,
+                                           results_out ? results_out + c0 * 8 : nullptr);
+    };
+    src.fill_host = [=](size_t c0, size_t ch, uint64_t* rows) {
+        const int rc = zl_ed_scalar_mul_assignments(ctx, curve, bits, points_xy + c0 * point_stride * 8, point_stride, scalars + c0 * 4, ch, rows);
+        for (size_t j = 0; rc == ZL_OK && results_out && j < ch; j++) memcpy(results_out + (c0 + j) * 8, rows + j * nv * 4 + 12, 64);
         return rc;
     };
     return groth16_prove_batch_any(ctx, pk, rd, src, 0, r, s, count, proofs);

@@ -194,6 +194,16 @@ public:
         C_.push_back(out.lc.add(neg_f));
         return out;
     }
+    // out = b / a for a divisor the circuit knows to be non-zero: one fresh witness whose VALUE the caller supplies (a field division made on the host) and
+    // the row a * out = b.  No constant folding: it ALWAYS allocates, in every mode, like select and new_boolean_witness.
+    FpVar<FrP> mul_equals(const FpVar<FrP>& a, const FpVar<FrP>& b, const F& out_value_mont) {
+        FpVar<FrP> out = new_witness(out_value_mont);
+        if (witness_only()) return out;
+        A_.push_back(a.lc);
+        B_.push_back(out.lc);
+        C_.push_back(b.lc);
+        return out;
+    }
     static F minus_one() { return zl::sub(F::zero(), F::one()); }
     bool equalities_hold() const { return equal_ok_; }  // witness-only: every enforce_equal saw equal values
     // full compiler: every multiplication folded constants the way a witness-only run of the same circuit code will (see mul)
@@ -478,6 +488,73 @@ Fp<FrP> duplex_decrypt(const Constants<FrP, W>& c, Fp<FrP> state[W], const Fp<Fr
     return state[1];
 }
 }  // namespace poseidon
+
+// ---- the embedded twisted Edwards curve in circuit ----------------------------------------------------------------------------------------
+// r1cs-std's affine twisted-Edwards variable (ark-r1cs-std groups/curves/twisted_edwards: AffineVar double / add) and its default double-and-add
+// scalar_mul_le, RESTATED from the published formulas over this compiler -- as zl_edwards.h restates the curve constants.  It is NOT compared with arkworks
+// matrices: the reference holds none.  a x^2 + y^2 = 1 + d x^2 y^2 with `a` a square and `d` not: both denominators below are non-zero for on-curve inputs,
+// the law is complete and the identity is the ordinary point (0, 1).  Every quotient is a mul_equals: its value is a host division, its row a product.
+//   double (x, y) -> (x3, y3): 5 rows, 5 witnesses, in this order
+//       xy = x y    xx = x x    yy = y y    (a xx + yy) x3 = 2 xy    (2 - a xx - yy) y3 = yy - a xx
+//   add (x1, y1) + (x2, y2): 6 rows, 6 witnesses, in this order
+//       u = (y1 - a x1)(x2 + y2)    v0 = x1 y2    v1 = x2 y1    w = v0 v1    (1 + d w) x3 = v0 + v1    (1 - d w) y3 = u + a v0 - v1
+//       (u + a v0 - v1 = y1 y2 - a x1 x2)
+//   scalar_mul over `bits` bits b_0 .. b_{bits - 1} (Boolean witnesses, least significant first) of a point P whose coordinates are VARIABLES:
+//       R_1 = (select(b_0, P.x, 0), select(b_0, P.y, 1)); for i = 1 .. bits - 1: M_i = double(M_{i-1}) with M_0 = P, T = R_i + M_i,
+//       R_{i+1} = (select(b_i, T.x, R_i.x), select(b_i, T.y, R_i.y)): 13 rows and 13 witnesses a step, 2 in front.
+//   The ladder does NOT start from the constant identity and add to it: a product by the constant 0 is a linear combination the full compiler folds and the
+//   witness-only compiler does not (the konst note in R1CS::mul), and the rows of the two would stop lining up.  In the form above every operand of a
+//   product is a variable, so R1CS::witness_only_compatible() holds.
+namespace edwards {
+template <class FrP>
+struct Coeffs {
+    Fp<FrP> a, d;  // Montgomery
+};
+template <class FrP>
+struct PointVar {
+    FpVar<FrP> x, y;
+};
+template <class FrP>
+PointVar<FrP> double_point(const Coeffs<FrP>& k, const PointVar<FrP>& p, R1CS<FrP>& cs) {
+    using F = Fp<FrP>;
+    using V = FpVar<FrP>;
+    const F m1 = R1CS<FrP>::minus_one();
+    const V xy = cs.mul(p.x, p.y), xx = cs.mul(p.x, p.x), yy = cs.mul(p.y, p.y);
+    const V axx = cs.mul_const(xx, k.a);
+    const V den_x = cs.add(axx, yy), num_x = cs.add(xy, xy);
+    const V x3 = cs.mul_equals(den_x, num_x, zl::mul(num_x.value, zl::inv(den_x.value)));
+    const V den_y = cs.add_const(cs.mul_const(den_x, m1), zl::from_u64<FrP>(2)), num_y = cs.add(yy, cs.mul_const(axx, m1));
+    const V y3 = cs.mul_equals(den_y, num_y, zl::mul(num_y.value, zl::inv(den_y.value)));
+    return PointVar<FrP>{x3, y3};
+}
+template <class FrP>
+PointVar<FrP> add_points(const Coeffs<FrP>& k, const PointVar<FrP>& p, const PointVar<FrP>& q, R1CS<FrP>& cs) {
+    using F = Fp<FrP>;
+    using V = FpVar<FrP>;
+    const F m1 = R1CS<FrP>::minus_one();
+    const V u = cs.mul(cs.add(p.y, cs.mul_const(p.x, zl::mul(k.a, m1))), cs.add(q.x, q.y));
+    const V v0 = cs.mul(p.x, q.y), v1 = cs.mul(q.x, p.y), w = cs.mul(v0, v1);
+    const V dw = cs.mul_const(w, k.d);
+    const V den_x = cs.add_const(dw, F::one()), num_x = cs.add(v0, v1);
+    const V x3 = cs.mul_equals(den_x, num_x, zl::mul(num_x.value, zl::inv(den_x.value)));
+    const V den_y = cs.add_const(cs.mul_const(dw, m1), F::one()), num_y = cs.add(cs.add(u, cs.mul_const(v0, k.a)), cs.mul_const(v1, m1));
+    const V y3 = cs.mul_equals(den_y, num_y, zl::mul(num_y.value, zl::inv(den_y.value)));
+    return PointVar<FrP>{x3, y3};
+}
+// bits: the Boolean witnesses of the scalar, least significant first, at least one
+template <class FrP>
+PointVar<FrP> scalar_mul_le(const Coeffs<FrP>& k, const PointVar<FrP>& p, const std::vector<FpVar<FrP>>& bits, R1CS<FrP>& cs) {
+    using F = Fp<FrP>;
+    PointVar<FrP> r{cs.select(bits[0], p.x, cs.constant(F::zero())), cs.select(bits[0], p.y, cs.constant(F::one()))};
+    PointVar<FrP> m = p;
+    for (size_t i = 1; i < bits.size(); i++) {
+        m = double_point(k, m, cs);
+        const PointVar<FrP> t = add_points(k, r, m, cs);
+        r = PointVar<FrP>{cs.select(bits[i], t.x, r.x), cs.select(bits[i], t.y, r.y)};
+    }
+    return r;
+}
+}  // namespace edwards
 
 // ---- pairing-engine configs ---------------------------------------------------------------------------------------------------
 struct Bls12_381 {

@@ -772,6 +772,38 @@ static R1CS<FrP> poseidon_encrypt(bool witness_only, const Fp<FrP>* init_canon, 
     return cs;
 }
 
+// "Q = s P on the embedded curve, for a secret scalar s": the gadget of zl_host.h (edwards::scalar_mul_le) behind four public inputs P.x, P.y, Q.x, Q.y.
+// Witnesses: s, its `bits` Boolean witnesses b_0 .. (least significant first), then what the gadget allocates: the two first selects and 13 records a step.
+// Rows: the bits' Booleanity, sum 2^i b_i = s, the gadget's, Q.x and Q.y bound last.  P is NOT checked to be on the curve: it is public, the verifier checks it.
+// Shape: n_witness = 1 + bits + 2 + 13 (bits - 1) = 14 bits - 10; n_constraints = bits + 1 + 2 + 13 (bits - 1) + 2 = 14 bits - 8; n_instance = 5.  Both
+// compilers allocate the public inputs first: Q is known before the circuit runs (the caller computed it natively).  p, q canonical and below r; s below 2^bits.
+template <class FrP>
+static R1CS<FrP> ed_scalar_mul_circuit(bool witness_only, unsigned bits, const Fp<FrP>* p_canon, const uint64_t* s_words, const Fp<FrP>* q_canon, const Fp<FrP>& a_canon,
+                                       const Fp<FrP>& d_canon) {
+    using F = Fp<FrP>;
+    using V = FpVar<FrP>;
+    R1CS<FrP> cs = witness_only ? R1CS<FrP>::for_witness() : R1CS<FrP>::for_proofs();
+    const edwards::Coeffs<FrP> k{zl::to_mont(a_canon), zl::to_mont(d_canon)};
+    const edwards::PointVar<FrP> p{cs.new_input(zl::to_mont(p_canon[0])), cs.new_input(zl::to_mont(p_canon[1]))};
+    const V qx = cs.new_input(zl::to_mont(q_canon[0])), qy = cs.new_input(zl::to_mont(q_canon[1]));
+    F s_canon;
+    memcpy(s_canon.l, s_words, 32);
+    const V s = cs.new_witness(zl::to_mont(s_canon));
+    std::vector<V> b(bits);
+    for (unsigned i = 0; i < bits; i++) b[i] = cs.new_boolean_witness((s_words[i >> 6] >> (i & 63)) & 1);
+    V sum = b[0];
+    F pow2 = F::one();
+    for (unsigned i = 1; i < bits; i++) {
+        pow2 = zl::add(pow2, pow2);
+        sum = cs.add(sum, cs.mul_const(b[i], pow2));
+    }
+    cs.enforce_equal(sum, s);
+    const edwards::PointVar<FrP> r = edwards::scalar_mul_le(k, p, b, cs);
+    cs.enforce_equal(r.x, qx);
+    cs.enforce_equal(r.y, qy);
+    return cs;
+}
+
 }  // namespace openzl
 
 // ------------------------------------------------------------------------------------------------ C-ABI hooks
@@ -904,8 +936,46 @@ static int circuit_encrypt(zl_curve_t curve, unsigned width, const uint64_t* ini
     return ZL_OK;
 }
 
+template <class FrP>
+static int circuit_ed_mul_t(zl_circuit* c, unsigned bits, const uint64_t* point_xy, const uint64_t* scalar, const uint64_t* q_xy, const uint64_t* a, const uint64_t* d,
+                            bool witness_only) {
+    std::vector<Fp<FrP>> p, q, ka, kd;
+    if (!elems_below_r<FrP>(point_xy, 2, p) || !elems_below_r<FrP>(q_xy, 2, q) || !elems_below_r<FrP>(a, 1, ka) || !elems_below_r<FrP>(d, 1, kd)) return ZL_EINVAL;
+    circuit_set(c, ed_scalar_mul_circuit<FrP>(witness_only, bits, p.data(), scalar, q.data(), ka[0], kd[0]));
+    return ZL_OK;
+}
+// Q = s P natively first (zl_ed_scalar_mul: it refuses a coordinate >= q, a point off the curve and a scalar >= l), then the circuit around it
+static int circuit_ed_mul(zl_curve_t curve, unsigned bits, const uint64_t* point_xy, const uint64_t* scalar, bool witness_only, zl_circuit** out) {
+    if (!out || !point_xy || !scalar || zl_ed_scalar_mul_assignment_elems(curve, bits) == 0) return ZL_EINVAL;
+    for (unsigned i = bits; i < 256; i++)
+        if ((scalar[i >> 6] >> (i & 63)) & 1) return ZL_EINVAL;  // s >= 2^bits
+    uint64_t q[8], a[4], d[4];
+    if (zl_ed_scalar_mul(curve, point_xy, scalar, q) || zl_ed_params(curve, a, d, nullptr, nullptr)) return ZL_EINVAL;
+    zl_circuit* c = new (std::nothrow) zl_circuit();
+    if (!c) return ZL_ENOMEM;
+    c->curve = curve;
+    const int rc = curve == ZL_BLS12_381 ? circuit_ed_mul_t<BLS12_381_Fr>(c, bits, point_xy, scalar, q, a, d, witness_only)
+                                         : circuit_ed_mul_t<BN254_Fr>(c, bits, point_xy, scalar, q, a, d, witness_only);
+    if (rc) {
+        zl_circuit_free(c);
+        return rc;
+    }
+    *out = c;
+    return ZL_OK;
+}
+
 extern "C" {
 
+int zl_circuit_ed_scalar_mul(zl_curve_t curve, unsigned bits, const uint64_t* point_xy, const uint64_t* scalar, zl_circuit** out) {
+    return circuit_ed_mul(curve, bits, point_xy, scalar, false, out);
+}
+int zl_circuit_ed_scalar_mul_witness(zl_curve_t curve, unsigned bits, const uint64_t* point_xy, const uint64_t* scalar, zl_circuit** out) {
+    return circuit_ed_mul(curve, bits, point_xy, scalar, true, out);
+}
+int zl_circuit_witness_only_compatible(const zl_circuit* c) {
+    if (!c) return ZL_EINVAL;
+    return c->curve == ZL_BLS12_381 ? (c->bls->witness_only_compatible() ? 1 : 0) : (c->bn->witness_only_compatible() ? 1 : 0);
+}
 int zl_circuit_poseidon_encrypt(zl_curve_t curve, unsigned width, const uint64_t* initial_state, const uint64_t* key, size_t key_len, const uint64_t* header,
                                 size_t header_len, const uint64_t* plaintext, size_t blocks, zl_circuit** out) {
     return circuit_encrypt(curve, width, initial_state, key, key_len, header, header_len, plaintext, blocks, false, out);
