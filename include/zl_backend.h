@@ -129,7 +129,11 @@ typedef struct zl_g16_proof {
     uint8_t a_inf, b_inf, c_inf;
 } zl_g16_proof;
 /* assignment: (n_instance + n_witness) x 4 u64 canonical (z = 1, public..., witness...); r, s: the two blinding
- * scalars ark samples from the rng (explicit here so that proofs are reproducible, SURVEY.md §8 note N3).
+ * scalars ark samples from the rng (explicit here so that proofs are reproducible, SURVEY.md §8 note N3), 4 u64
+ * canonical each.  Every prover of this library (this one, _resident, _sharded, the batched and the fused ones of
+ * zl_backend_ext.h) refuses an r or s at or above the scalar field's modulus with ZL_EINVAL, before any device work;
+ * 0 and modulus - 1 are accepted.  A proof point may be the point at infinity (r = -(alpha + sum z_i a_i) / delta
+ * makes A one): its words are all zero and its *_inf flag is 1.
  * Runs witness_map (3 iFFT, 3 coset FFT, 1 coset iFFT on the device) and the 4 G1 + 1 G2 MSMs. */
 int zl_groth16_prove(zl_ctx* ctx, const zl_g16_pk* pk, const zl_r1cs* cs, const uint64_t* assignment, const uint64_t* r,
                      const uint64_t* s, zl_g16_proof* out);

@@ -46,7 +46,10 @@ int zl_msm_multi_dev(zl_ctx* ctx, uint64_t bases, size_t first, const void* d_sc
  * zl_groth16_prove_resident returns for (assignment j, r[j], s[j]), byte for byte.  Domains up to 2^ZL_TUNE_G16_BATCH_LOG_N with at least
  * ZL_TUNE_G16_BATCH_MIN proofs keep the whole batch on the device (witness map with a batch dimension, A, B and C as three zl_msm_multi passes over
  * extended queries cached with the key, no point arithmetic on the host); everything else loops the resident prover.  The first failing proof's
- * error is returned.  zl_groth16_last_h after a device batch returns ZL_EINVAL. */
+ * error is returned.  zl_groth16_last_h after a device batch returns ZL_EINVAL.
+ * r, s: canonical, as for zl_groth16_prove.  One r[j] or s[j] at or above the scalar field's modulus refuses the whole call with ZL_EINVAL before any device
+ * work, on either path and whatever its index; no proof is written.  The same holds for every batched prover below (_batch_dev, _poseidon_chains, _merkle_*,
+ * _forest_members, _poseidon_hashes, _merkle_leaf_*, _poseidon_encryptions, _ed_scalar_muls) and for zl_groth16_prove_sharded. */
 int zl_groth16_prove_batch(zl_ctx* ctx, const zl_g16_pk* pk, uint64_t r1cs_handle, const uint64_t* assignments, unsigned flags, const uint64_t* r,
                            const uint64_t* s, size_t count, zl_g16_proof* proofs);
 /* The same with the assignments in DEVICE memory (count x (n_instance + n_witness) elements, densely): on the device path every chunk is one device-to-device

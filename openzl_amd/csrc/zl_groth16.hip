@@ -351,11 +351,34 @@ static int g16_key_handles(const zl_ctx* ctx, const zl_g16_pk* pk, const G16Shap
     if (bs[0]->n < sh.nv || bs[1]->n < sh.nv || bs[4]->n < sh.nv || bs[2]->n < (size_t)sh.N - 1 || bs[3]->n < sh.nw) return ZL_EINVAL;
     return ZL_OK;
 }
-// what every entry point asks of (pk, r1cs handle) after its own argument checks: the key's five points are there, the circuit is resident and of the key's curve
-static int g16_entry(const zl_ctx* ctx, const zl_g16_pk* pk, uint64_t r1cs_handle, const zl_r1cs_dev** rd_out) {
+// The blinding-scalar contract of every prover: r[j], s[j] (4 u64 words each) are below the scalar field's modulus.  A scalar at or above it is not one value
+// here: the fixed-base tables walk its 256 bits as they stand, to_mont / mul take reduced operands only (g16_rs, k_g16_fold_scalars, k_g16_batch_scalars), and
+// the multi-MSMs of a device batch refuse high bits -- so the paths would disagree.  A plain word comparison (the verifier's, zl_verify.hip: publics_canonical).
+template <class FrP>
+static bool g16_scalars_canonical(const uint64_t* v, size_t n) {
+    static_assert(FrP::N == 8, "scalar fields are 8 x 32 bits");
+    for (size_t i = 0; i < n; i++) {
+        const uint64_t* w = v + 4 * i;
+        uint64_t br = 0;
+        for (int j = 0; j < 8; j++) br = (((w[j / 2] >> (32 * (j % 2))) & 0xffffffffu) - FrP::mod(j) - br) >> 63;
+        if (!br) return false;  // no borrow out of w - modulus: w >= modulus
+    }
+    return true;
+}
+static int g16_blinding_ok(zl_curve_t curve, const uint64_t* r, const uint64_t* s, size_t count) {
+    if (count == 0) return ZL_OK;
+    if (curve == ZL_BLS12_381) return g16_scalars_canonical<BLS12_381_Fr>(r, count) && g16_scalars_canonical<BLS12_381_Fr>(s, count) ? ZL_OK : ZL_EINVAL;
+    if (curve == ZL_BN254) return g16_scalars_canonical<BN254_Fr>(r, count) && g16_scalars_canonical<BN254_Fr>(s, count) ? ZL_OK : ZL_EINVAL;
+    return ZL_EINVAL;
+}
+// what every entry point asks of (pk, r1cs handle, blinding scalars) after its own argument checks, before any device work or thread start: the key's five
+// points are there, the circuit is resident and of the key's curve, and all `count` pairs (r[j], s[j]) are canonical -- one bad pair refuses the whole call
+static int g16_entry(const zl_ctx* ctx, const zl_g16_pk* pk, uint64_t r1cs_handle, const uint64_t* r, const uint64_t* s, size_t count, const zl_r1cs_dev** rd_out) {
     if (!pk->alpha_g1 || !pk->beta_g1 || !pk->delta_g1 || !pk->beta_g2 || !pk->delta_g2) return ZL_EINVAL;
     const zl_r1cs_dev* rd = zl_find_r1cs(ctx, r1cs_handle);
     if (!rd || rd->curve != (int)pk->curve) return ZL_EHANDLE;
+    const int rc = g16_blinding_ok(pk->curve, r, s, count);
+    if (rc) return rc;
     *rd_out = rd;
     return ZL_OK;
 }
@@ -876,7 +899,7 @@ extern "C" int zl_groth16_prove_sharded(zl_mctx* m, const zl_g16_pk* pk, const z
     zl_ctx* ctx0 = zl_mctx_ctx(m, 0);
     if (!ctx0) return ZL_EINVAL;
     const zl_r1cs_dev* rd = nullptr;
-    const int rc = g16_entry(ctx0, pk, r1cs_handle_rank0, &rd);
+    const int rc = g16_entry(ctx0, pk, r1cs_handle_rank0, r, s, 1, &rd);
     if (rc) return rc;
     if (pk->curve == ZL_BLS12_381) return groth16_prove_sharded_t<BlsG1, BlsG2>(m, pk, shards, rd, assignment, flags, r, s, out);
     if (pk->curve == ZL_BN254) return groth16_prove_sharded_t<BnG1, BnG2>(m, pk, shards, rd, assignment, flags, r, s, out);
@@ -933,7 +956,7 @@ extern "C" int zl_groth16_prove_resident(zl_ctx* ctx, const zl_g16_pk* pk, uint6
                                          const uint64_t* r, const uint64_t* s, zl_g16_proof* out) {
     if (!ctx || !pk || !assignment || !r || !s || !out || (flags & ~ZL_MONT)) return ZL_EINVAL;
     const zl_r1cs_dev* rd = nullptr;
-    const int rc = g16_entry(ctx, pk, r1cs_handle, &rd);
+    const int rc = g16_entry(ctx, pk, r1cs_handle, r, s, 1, &rd);
     if (rc) return rc;
     ZL_HIP(ctx, hipSetDevice(ctx->device));
     if (pk->curve == ZL_BLS12_381) return groth16_prove_t<BlsG1, BlsG2>(ctx, pk, rd, assignment, flags, r, s, out);
@@ -945,7 +968,7 @@ int zl_groth16_prove_split(zl_ctx* ctx, const zl_g16_pk* pk, uint64_t r1cs_handl
                            const uint64_t* s, zl_g16_proof* out) {
     if (!ctx || !pk || !instance || !r || !s || !out) return ZL_EINVAL;
     const zl_r1cs_dev* rd = nullptr;
-    const int rc = g16_entry(ctx, pk, r1cs_handle, &rd);
+    const int rc = g16_entry(ctx, pk, r1cs_handle, r, s, 1, &rd);
     if (rc) return rc;
     if (rd->n_witness && !witness) return ZL_EINVAL;
     ZL_HIP(ctx, hipSetDevice(ctx->device));
@@ -956,9 +979,11 @@ int zl_groth16_prove_split(zl_ctx* ctx, const zl_g16_pk* pk, uint64_t r1cs_handl
 }
 extern "C" int zl_groth16_prove(zl_ctx* ctx, const zl_g16_pk* pk, const zl_r1cs* cs, const uint64_t* assignment, const uint64_t* r, const uint64_t* s,
                                 zl_g16_proof* out) {
-    if (!ctx || !pk || !r1cs_view_ok(cs)) return ZL_EINVAL;
+    if (!ctx || !pk || !r || !s || !r1cs_view_ok(cs)) return ZL_EINVAL;
+    int rc = g16_blinding_ok(pk->curve, r, s, 1);  // (also in zl_groth16_prove_resident: here before the matrices go up)
+    if (rc) return rc;
     uint64_t h = 0;
-    int rc = zl_r1cs_upload(ctx, pk->curve, cs, &h);
+    rc = zl_r1cs_upload(ctx, pk->curve, cs, &h);
     if (rc) return rc;
     rc = zl_groth16_prove_resident(ctx, pk, h, assignment, ZL_CANON, r, s, out);
     (void)zl_r1cs_free(ctx, h);
@@ -1219,7 +1244,7 @@ static int groth16_prove_batch_rows(zl_ctx* ctx, const zl_g16_pk* pk, uint64_t r
                                     const uint64_t* s, size_t count, zl_g16_proof* proofs) {
     if (!ctx || !pk || (flags & ~ZL_MONT) || (count && (!rows || !r || !s || !proofs))) return ZL_EINVAL;
     const zl_r1cs_dev* rd = nullptr;
-    const int rc = g16_entry(ctx, pk, r1cs_handle, &rd);
+    const int rc = g16_entry(ctx, pk, r1cs_handle, r, s, count, &rd);
     if (rc || count == 0) return rc;
     G16BatchSource src;
     (on_device ? src.dev : src.host) = static_cast<const uint64_t*>(rows);
@@ -1238,7 +1263,7 @@ extern "C" int zl_groth16_prove_poseidon_chains(zl_ctx* ctx, const zl_g16_pk* pk
     const size_t nv = zl_poseidon_chain_assignment_elems(k);
     if (!ctx || !pk || nv == 0 || (count && (!x0 || !x1 || !r || !s || !proofs))) return ZL_EINVAL;
     const zl_r1cs_dev* rd = nullptr;
-    const int rc0 = g16_entry(ctx, pk, r1cs_handle, &rd);
+    const int rc0 = g16_entry(ctx, pk, r1cs_handle, r, s, count, &rd);
     if (rc0) return rc0;
     if (pk->curve != ZL_BLS12_381 && pk->curve != ZL_BN254) return ZL_EINVAL;
     // the shape of a k-link chain; what the matrices say cannot be checked, as with a witness-only compiler
@@ -1258,11 +1283,12 @@ extern "C" int zl_groth16_prove_poseidon_chains(zl_ctx* ctx, const zl_g16_pk* pk
     return groth16_prove_batch_any(ctx, pk, rd, src, 0, r, s, count, proofs);
 }
 // the checks the two membership provers share, in zl_groth16_prove_batch's order; *rd_out = the resident circuit
-static int g16_merkle_checks(zl_ctx* ctx, const zl_g16_pk* pk, uint64_t r1cs_handle, unsigned depth, bool args_ok, const zl_r1cs_dev** rd_out) {
+static int g16_merkle_checks(zl_ctx* ctx, const zl_g16_pk* pk, uint64_t r1cs_handle, unsigned depth, bool args_ok, const uint64_t* r, const uint64_t* s, size_t count,
+                             const zl_r1cs_dev** rd_out) {
     const size_t nv = zl_poseidon_merkle_assignment_elems(depth);
     if (!ctx || !pk || nv == 0 || !args_ok) return ZL_EINVAL;
     const zl_r1cs_dev* rd = nullptr;
-    const int rc = g16_entry(ctx, pk, r1cs_handle, &rd);
+    const int rc = g16_entry(ctx, pk, r1cs_handle, r, s, count, &rd);
     if (rc) return rc;
     if (pk->curve != ZL_BLS12_381 && pk->curve != ZL_BN254) return ZL_EINVAL;
     // the shape of a depth-d membership circuit; what the matrices say cannot be checked, as with a witness-only compiler
@@ -1273,7 +1299,7 @@ static int g16_merkle_checks(zl_ctx* ctx, const zl_g16_pk* pk, uint64_t r1cs_han
 extern "C" int zl_groth16_prove_merkle_paths(zl_ctx* ctx, const zl_g16_pk* pk, uint64_t r1cs_handle, unsigned depth, const uint64_t* leaves, const uint64_t* indices,
                                              const uint64_t* paths, const uint64_t* r, const uint64_t* s, size_t count, zl_g16_proof* proofs, uint64_t* roots_out) {
     const zl_r1cs_dev* rd = nullptr;
-    const int rc0 = g16_merkle_checks(ctx, pk, r1cs_handle, depth, !(count && (!leaves || !indices || !paths || !r || !s || !proofs)), &rd);
+    const int rc0 = g16_merkle_checks(ctx, pk, r1cs_handle, depth, !(count && (!leaves || !indices || !paths || !r || !s || !proofs)), r, s, count, &rd);
     if (rc0) return rc0;
     for (size_t i = 0; i < count; i++)
         if (indices[i] >> depth) return ZL_EINVAL;
@@ -1295,7 +1321,7 @@ extern "C" int zl_groth16_prove_merkle_paths(zl_ctx* ctx, const zl_g16_pk* pk, u
 extern "C" int zl_groth16_prove_merkle_members(zl_ctx* ctx, const zl_g16_pk* pk, uint64_t r1cs_handle, const void* d_nodes, size_t n, unsigned depth, const uint64_t* indices,
                                                const uint64_t* r, const uint64_t* s, size_t count, zl_g16_proof* proofs, uint64_t* root_out) {
     const zl_r1cs_dev* rd = nullptr;
-    const int rc0 = g16_merkle_checks(ctx, pk, r1cs_handle, depth, !(count && (!d_nodes || !indices || !r || !s || !proofs)), &rd);
+    const int rc0 = g16_merkle_checks(ctx, pk, r1cs_handle, depth, !(count && (!d_nodes || !indices || !r || !s || !proofs)), r, s, count, &rd);
     if (rc0) return rc0;
     if (zl_poseidon_merkle_nodes(n, depth) == 0 && n != 0) return ZL_EINVAL;  // (n > 2^depth)
     for (size_t i = 0; i < count; i++)
@@ -1320,7 +1346,7 @@ extern "C" int zl_groth16_prove_forest_members(zl_ctx* ctx, const zl_g16_pk* pk,
     unsigned depth = 0;
     if (zl_merkle_forest_prover_view(f, ctx, &fcurve, &depth)) return ZL_EINVAL;
     const zl_r1cs_dev* rd = nullptr;
-    const int rc0 = g16_merkle_checks(ctx, pk, r1cs_handle, depth, !(count && (!tree_of || !indices || !r || !s || !proofs)), &rd);
+    const int rc0 = g16_merkle_checks(ctx, pk, r1cs_handle, depth, !(count && (!tree_of || !indices || !r || !s || !proofs)), r, s, count, &rd);
     if (rc0) return rc0;
     if ((int)pk->curve != fcurve || zl_merkle_forest_members_ok(f, tree_of, indices, count)) return ZL_EINVAL;
     if (count == 0) return ZL_OK;
@@ -1336,11 +1362,11 @@ extern "C" int zl_groth16_prove_forest_members(zl_ctx* ctx, const zl_g16_pk* pk,
 }
 // the checks the three arity-general provers share, in zl_groth16_prove_batch's order; nv = the row length of the stated (arity, depth), depth == 0 for the
 // hash circuit; *rd_out = the resident circuit
-static int g16_arity_checks(zl_ctx* ctx, const zl_g16_pk* pk, uint64_t r1cs_handle, unsigned arity, size_t nv, unsigned depth, bool args_ok,
-                            const zl_r1cs_dev** rd_out) {
+static int g16_arity_checks(zl_ctx* ctx, const zl_g16_pk* pk, uint64_t r1cs_handle, unsigned arity, size_t nv, unsigned depth, bool args_ok, const uint64_t* r,
+                            const uint64_t* s, size_t count, const zl_r1cs_dev** rd_out) {
     if (!ctx || !pk || nv == 0 || !args_ok) return ZL_EINVAL;
     const zl_r1cs_dev* rd = nullptr;
-    const int rc = g16_entry(ctx, pk, r1cs_handle, &rd);
+    const int rc = g16_entry(ctx, pk, r1cs_handle, r, s, count, &rd);
     if (rc) return rc;
     if (pk->curve != ZL_BLS12_381 && pk->curve != ZL_BN254) return ZL_EINVAL;
     // the shape (2, a + 3 S(a) + 238 d, 3 S(a) + 237 d + 1) with nv = 2 + a + 3 S(a) + 238 d; what the matrices say cannot be checked, as with a witness-only compiler
@@ -1352,7 +1378,7 @@ extern "C" int zl_groth16_prove_poseidon_hashes(zl_ctx* ctx, const zl_g16_pk* pk
                                                 const uint64_t* s, size_t count, zl_g16_proof* proofs, uint64_t* public_out) {
     const size_t nv = zl_poseidon_hash_assignment_elems(arity);
     const zl_r1cs_dev* rd = nullptr;
-    const int rc0 = g16_arity_checks(ctx, pk, r1cs_handle, arity, nv, 0, !(count && (!in || !r || !s || !proofs)), &rd);
+    const int rc0 = g16_arity_checks(ctx, pk, r1cs_handle, arity, nv, 0, !(count && (!in || !r || !s || !proofs)), r, s, count, &rd);
     if (rc0 || count == 0) return rc0;
     const zl_curve_t curve = pk->curve;
     G16BatchSource src;
@@ -1372,7 +1398,7 @@ extern "C" int zl_groth16_prove_merkle_leaf_paths(zl_ctx* ctx, const zl_g16_pk* 
                                                   uint64_t* roots_out) {
     const size_t nv = zl_poseidon_merkle_leaf_assignment_elems(arity, depth);
     const zl_r1cs_dev* rd = nullptr;
-    const int rc0 = g16_arity_checks(ctx, pk, r1cs_handle, arity, nv, depth, !(count && (!preimages || !indices || !paths || !r || !s || !proofs)), &rd);
+    const int rc0 = g16_arity_checks(ctx, pk, r1cs_handle, arity, nv, depth, !(count && (!preimages || !indices || !paths || !r || !s || !proofs)), r, s, count, &rd);
     if (rc0) return rc0;
     for (size_t i = 0; i < count; i++)
         if (indices[i] >> depth) return ZL_EINVAL;
@@ -1396,7 +1422,7 @@ extern "C" int zl_groth16_prove_merkle_leaf_members(zl_ctx* ctx, const zl_g16_pk
                                                     zl_g16_proof* proofs, uint64_t* root_out) {
     const size_t nv = zl_poseidon_merkle_leaf_assignment_elems(arity, depth);
     const zl_r1cs_dev* rd = nullptr;
-    const int rc0 = g16_arity_checks(ctx, pk, r1cs_handle, arity, nv, depth, !(count && (!d_nodes || !d_preimages || !indices || !r || !s || !proofs)), &rd);
+    const int rc0 = g16_arity_checks(ctx, pk, r1cs_handle, arity, nv, depth, !(count && (!d_nodes || !d_preimages || !indices || !r || !s || !proofs)), r, s, count, &rd);
     if (rc0) return rc0;
     if (zl_poseidon_merkle_nodes(n, depth) == 0 && n != 0) return ZL_EINVAL;  // (n > 2^depth)
     for (size_t i = 0; i < count; i++)
@@ -1424,7 +1450,7 @@ extern "C" int zl_groth16_prove_poseidon_encryptions(zl_ctx* ctx, const zl_g16_p
     const size_t nv = zl_poseidon_encrypt_assignment_elems(width, key_len, header_len, blocks);
     if (!ctx || !pk || nv == 0 || (count && (!keys || (header_len && !headers) || !plaintexts || !r || !s || !proofs))) return ZL_EINVAL;
     const zl_r1cs_dev* rd = nullptr;
-    const int rc0 = g16_entry(ctx, pk, r1cs_handle, &rd);
+    const int rc0 = g16_entry(ctx, pk, r1cs_handle, r, s, count, &rd);
     if (rc0) return rc0;
     if (pk->curve != ZL_BLS12_381 && pk->curve != ZL_BN254) return ZL_EINVAL;
     // the shape (2 + N rate + H, K + N rate + 3 S, 3 S + 1 + N rate) with nv = 2 + 2 N rate + H + K + 3 S; what the matrices say cannot be checked, as with a
@@ -1457,7 +1483,7 @@ extern "C" int zl_groth16_prove_ed_scalar_muls(zl_ctx* ctx, const zl_g16_pk* pk,
                                                const uint64_t* scalars, const uint64_t* r, const uint64_t* s, size_t count, zl_g16_proof* proofs, uint64_t* results_out) {
     if (!ctx || !pk || point_stride > 1 || (count && (!points_xy || !scalars || !r || !s || !proofs))) return ZL_EINVAL;
     const zl_r1cs_dev* rd = nullptr;
-    const int rc0 = g16_entry(ctx, pk, r1cs_handle, &rd);
+    const int rc0 = g16_entry(ctx, pk, r1cs_handle, r, s, count, &rd);
     if (rc0) return rc0;
     const zl_curve_t curve = pk->curve;
     const size_t nv = zl_ed_scalar_mul_assignment_elems(curve, bits);  // (0 for an unknown curve as well)
