@@ -635,6 +635,58 @@ int zl_ed_scalar_mul_assignments_dev(zl_ctx* ctx, zl_curve_t curve, unsigned bit
                                      void* d_out, size_t stride_elems);
 int zl_groth16_prove_ed_scalar_muls(zl_ctx* ctx, const zl_g16_pk* pk, uint64_t r1cs_handle, unsigned bits, const uint64_t* points_xy, size_t point_stride,
                                     const uint64_t* scalars, const uint64_t* r, const uint64_t* s, size_t count, zl_g16_proof* proofs, uint64_t* results_out);
+/* The hybrid encryption in circuit (host compilers): "this ciphertext is the hybrid encryption, to the public key pk, of a plaintext I know" -- what the
+ * reference's encryption::hybrid::Hybrid<DiffieHellman, FixedDuplexer>::encrypt (openzl-crypto/src/encryption/hybrid.rs, impl Encrypt) runs under a compiler:
+ * epk = derive_ephemeral(esk) = esk G, S = generate_secret(pk, esk) = esk pk, then the base cipher under S -- here zl_circuit_poseidon_encrypt's duplex with the
+ * key (S.x, S.y), key_len = 2, the convention zl_hybrid_encrypt_batch fixed.  It JOINS the two circuits above: the cipher's key variables ARE the pk ladder's
+ * output, which two separate proofs could not bind.  width 3..6 (rate = width - 1), 1 <= bits <= the bit length of l, header_len H <= 64, blocks N in 1..1024,
+ * initial_state NULL = zero; T = N rate.
+ * Public inputs, after the leading 1 (Ciphertext::extend: epk, then the base ciphertext = tag, then message): G.x G.y, pk.x pk.y, epk.x epk.y, tag, the T
+ * ciphertext elements, the H header elements.  G and pk are public variables, as P is above: the verifier checks that they are the generator and on the curve,
+ * the circuit does not; no in-circuit subgroup test.  Every operand of a product stays a variable: zl_circuit_witness_only_compatible is 1.
+ * Witnesses: esk; its `bits` Boolean bits, least significant first, allocated ONCE and shared by both ladders; the ladder over G -- R_1, then 13 records per step
+ * exactly as in zl_circuit_ed_scalar_mul; the ladder over pk in the same form, whose last R is S: bound to nothing public, it is the cipher's key; the T
+ * plaintext elements; the 3 S records of the cipher as zl_circuit_poseidon_encrypt orders them at K = 2, S = (F - 1 - Z) + (SB + N - 1) F with Z = max(0,
+ * rate - 2).  Rows: one per bit, sum 2^i b_i = esk, the G ladder's 2 + 13 (bits - 1), epk.x and epk.y bound, the pk ladder's, the cipher's 3 S, tag = public tag,
+ * one per ciphertext element.
+ * SHAPE, derived again: n_instance = 1 + 7 + T + H = 8 + T + H; n_witness = 1 + bits + 2 (13 bits - 11) + T + 3 S = 27 bits - 21 + T + 3 S; n_constraints =
+ * bits + 1 + (13 bits - 11) + 2 + (13 bits - 11) + 3 S + 1 + T = 27 bits - 18 + 3 S + T (27 bits - 19 rows in front of the cipher's 3 S + 1 + T); assignment
+ * row length 27 bits - 13 + 2 T + H + 3 S.  FAMILIES: n_witness - (n_constraints - 1) = -2 and n_instance >= 10 here; the scalar multiplications have -1 and 5, the
+ * encryptions K >= 1, every other family n_instance = 2: no other family's keys pass this family's shape check and these keys pass no other's.  WITHIN the
+ * family the shape fixes T + H and 27 bits + T + 3 S and does not separate bits from S: distinct tuples of one shape are different circuits of one shape, as
+ * the encryption family's one pair is; tests/test_hybrid_circuit_host.py walks the tuples within the limits and records which collide.
+ * _witness: the same circuit in the witness-only compiler, assignments equal word for word.
+ * ZL_EINVAL: an unknown curve, a parameter out of range, a coordinate >= q, G or pk off the curve, esk >= l or >= 2^bits, a header, plaintext or initial-state
+ * element >= r, a null pointer.
+ * The complete ASSIGNMENTS, word for word what both compilers export:
+ *   [0] = 1  [1..3) G  [3..5) pk  [5..7) epk  [7] tag  [8 .. 8 + T) ciphertext  [.. + H) header  esk  the bits  the G ladder  the pk ladder  plaintext  records
+ * On the device a chunk is TWO launches on one stream: k_ed_hybrid_ladders, one lane per (row, ladder) -- the two ladders depend only on esk's bits, and a lane
+ * running both in series would pay the latency twice -- and k_pos_duplex_trace_in, the cipher keyed from the row's own S cells.
+ * zl_hybrid_encrypt_assignment_elems: the row length; 0 for a parameter out of range.  The host-pointer form writes count dense rows; generator_xy is ONE host
+ * point for the call, pk_stride 0 (one key for all) or 1; count == 0 is ZL_OK; ctx == NULL or a count below ZL_TUNE_ED_DEV_MIN runs the byte-identical host mirror
+ * over the host pool; otherwise staged in chunks of ZL_TUNE_ED_CHUNK rows under the 256 MiB budget of the embedded-curve unit's slot; finished on return; an
+ * item the circuit would refuse is ZL_EINVAL through the flag word; G and initial_state are checked on the host before any work.  The _dev form takes DEVICE
+ * pointers for esk, pks, headers, plaintexts and d_out and never the host path (ctx == NULL is ZL_EINVAL): row i starts at d_out + i * stride_elems elements,
+ * stride_elems >= the row length, elements behind the row are not written, d_out must be 16-byte aligned and must not overlap the inputs.
+ * zl_groth16_prove_hybrid_encryptions: from HOST inputs to proofs -- proofs[j] is byte for byte what zl_groth16_prove_resident returns for row j with (r[j],
+ * s[j]); epks_out (count x 8 words), tags_out (count x 4) and ciphertexts_out (count x T x 4), each may be NULL; the agreement and the cipher run ONCE.  The
+ * resident circuit must have the shape above, else ZL_EINVAL; error order and dispatch bounds are zl_groth16_prove_batch's and are not moved; off the device
+ * batch path the rows come through host staging of at most 64 MiB at a time. */
+int zl_circuit_hybrid_encrypt(zl_curve_t curve, unsigned width, unsigned bits, const uint64_t* initial_state, const uint64_t* generator_xy, const uint64_t* esk,
+                              const uint64_t* pk_xy, const uint64_t* header, size_t header_len, const uint64_t* plaintext, size_t blocks, zl_circuit** out);
+int zl_circuit_hybrid_encrypt_witness(zl_curve_t curve, unsigned width, unsigned bits, const uint64_t* initial_state, const uint64_t* generator_xy, const uint64_t* esk,
+                                      const uint64_t* pk_xy, const uint64_t* header, size_t header_len, const uint64_t* plaintext, size_t blocks, zl_circuit** out);
+size_t zl_hybrid_encrypt_assignment_elems(zl_curve_t curve, unsigned width, unsigned bits, size_t header_len, size_t blocks);
+int zl_hybrid_encrypt_assignments(zl_ctx* ctx, zl_curve_t curve, unsigned width, unsigned bits, const uint64_t* initial_state, const uint64_t* generator_xy, const uint64_t* esk,
+                                  const uint64_t* pks_xy, size_t pk_stride, const uint64_t* headers, size_t header_len, const uint64_t* plaintexts, size_t blocks, size_t count,
+                                  uint64_t* out);
+int zl_hybrid_encrypt_assignments_dev(zl_ctx* ctx, zl_curve_t curve, unsigned width, unsigned bits, const uint64_t* initial_state, const uint64_t* generator_xy,
+                                      const void* d_esk, const void* d_pks_xy, size_t pk_stride, const void* d_headers, size_t header_len, const void* d_plaintexts,
+                                      size_t blocks, size_t count, void* d_out, size_t stride_elems);
+int zl_groth16_prove_hybrid_encryptions(zl_ctx* ctx, const zl_g16_pk* pk, uint64_t r1cs_handle, unsigned width, unsigned bits, const uint64_t* initial_state,
+                                        const uint64_t* generator_xy, const uint64_t* esk, const uint64_t* pks_xy, size_t pk_stride, const uint64_t* headers,
+                                        size_t header_len, const uint64_t* plaintexts, size_t blocks, const uint64_t* r, const uint64_t* s, size_t count,
+                                        zl_g16_proof* proofs, uint64_t* epks_out, uint64_t* tags_out, uint64_t* ciphertexts_out);
 
 /* ---- per-call device timing (HIP events on the ctx's stream) -------------------------------------------- */
 typedef struct zl_timing {

@@ -16,3 +16,4 @@ from .backend import poseidon_duplex_permutations, poseidon_duplex_encrypt_host,
 from .backend import poseidon_encrypt_assignment_elems, poseidon_encrypt_assignments_host  # noqa: F401
 from .backend import ZL_ED_CHECK_SUBGROUP, ed_params, ed_add_host, ed_scalar_mul_host, hybrid_encrypt_host, hybrid_decrypt_host  # noqa: F401
 from .backend import ed_order_bits, ed_scalar_mul_assignment_elems, ed_scalar_mul_assignments_host  # noqa: F401
+from .backend import hybrid_encrypt_assignment_elems, hybrid_encrypt_assignments_host  # noqa: F401

@@ -57,6 +57,8 @@ ABI_SYMBOLS = [
     "zl_hybrid_encrypt_batch", "zl_hybrid_encrypt_batch_dev", "zl_hybrid_decrypt_batch", "zl_hybrid_decrypt_batch_dev",
     "zl_circuit_ed_scalar_mul", "zl_circuit_ed_scalar_mul_witness", "zl_circuit_witness_only_compatible", "zl_ed_scalar_mul_assignment_elems",
     "zl_ed_scalar_mul_assignments", "zl_ed_scalar_mul_assignments_dev", "zl_groth16_prove_ed_scalar_muls",
+    "zl_circuit_hybrid_encrypt", "zl_circuit_hybrid_encrypt_witness", "zl_hybrid_encrypt_assignment_elems", "zl_hybrid_encrypt_assignments",
+    "zl_hybrid_encrypt_assignments_dev", "zl_groth16_prove_hybrid_encryptions",
 ]
 ZL_ED_CHECK_SUBGROUP = 1
 
@@ -185,6 +187,14 @@ def load_library(path: Optional[str] = None):
     L.zl_ed_scalar_mul_assignments.argtypes = [vp, C.c_int, C.c_uint, u64p, C.c_size_t, u64p, C.c_size_t, u64p]
     L.zl_ed_scalar_mul_assignments_dev.argtypes = [vp, C.c_int, C.c_uint, vp, C.c_size_t, vp, C.c_size_t, vp, C.c_size_t]
     L.zl_groth16_prove_ed_scalar_muls.argtypes = [vp, C.POINTER(G16PkC), C.c_uint64, C.c_uint, u64p, C.c_size_t, u64p, u64p, u64p, C.c_size_t, C.POINTER(G16ProofC), u64p]
+    L.zl_circuit_hybrid_encrypt.argtypes = [C.c_int, C.c_uint, C.c_uint, u64p, u64p, u64p, u64p, u64p, C.c_size_t, u64p, C.c_size_t, C.POINTER(vp)]
+    L.zl_circuit_hybrid_encrypt_witness.argtypes = L.zl_circuit_hybrid_encrypt.argtypes
+    L.zl_hybrid_encrypt_assignment_elems.argtypes = [C.c_int, C.c_uint, C.c_uint, C.c_size_t, C.c_size_t]
+    L.zl_hybrid_encrypt_assignment_elems.restype = C.c_size_t
+    L.zl_hybrid_encrypt_assignments.argtypes = [vp, C.c_int, C.c_uint, C.c_uint, u64p, u64p, u64p, u64p, C.c_size_t, u64p, C.c_size_t, u64p, C.c_size_t, C.c_size_t, u64p]
+    L.zl_hybrid_encrypt_assignments_dev.argtypes = [vp, C.c_int, C.c_uint, C.c_uint, u64p, u64p, vp, vp, C.c_size_t, vp, C.c_size_t, vp, C.c_size_t, C.c_size_t, vp, C.c_size_t]
+    L.zl_groth16_prove_hybrid_encryptions.argtypes = [vp, C.POINTER(G16PkC), C.c_uint64, C.c_uint, C.c_uint, u64p, u64p, u64p, u64p, C.c_size_t, u64p, C.c_size_t, u64p,
+                                                      C.c_size_t, u64p, u64p, C.c_size_t, C.POINTER(G16ProofC), u64p, u64p, u64p]
     L.zl_circuit_poseidon_encrypt.argtypes = [C.c_int, C.c_uint, u64p, u64p, C.c_size_t, u64p, C.c_size_t, u64p, C.c_size_t, C.POINTER(vp)]
     L.zl_circuit_poseidon_encrypt_witness.argtypes = L.zl_circuit_poseidon_encrypt.argtypes
     L.zl_poseidon_encrypt_assignment_elems.argtypes = [C.c_uint, C.c_size_t, C.c_size_t, C.c_size_t]
@@ -683,6 +693,40 @@ class Backend:
         public inputs of proof j are points[j] and Q[j]"""
         pkc, keep_pk = _pk_struct(curve, pk)
         return self._prove_scalar_muls(pkc, curve, r1cs_handle, bits, points, scalars, r, s)
+
+    def hybrid_encrypt_assignments(self, curve: int, initial_state, generator, esk, pks, headers, plaintexts, bits: Optional[int] = None) -> np.ndarray:
+        """zl_hybrid_encrypt_assignments: operands as hybrid_encrypt -> (count, hybrid_encrypt_assignment_elems(curve, W, bits, H, N), 4) canonical words, row i the
+        complete assignment of Circuit.hybrid_encrypt(curve, initial_state, generator, esk[i], pks[i], headers[i], plaintexts[i], bits); bits None: the full width"""
+        return _hybrid_encrypt_assignments(self.L, self._ctx, curve, initial_state, generator, esk, pks, headers, plaintexts, bits)
+
+    def hybrid_encrypt_assignments_dev(self, curve: int, width: int, bits: int, initial_state, generator, d_esk: int, d_pks: int, pk_stride: int, d_headers: int,
+                                       header_len: int, d_plaintexts: int, blocks: int, count: int, d_out: int, stride_elems: Optional[int] = None):
+        """zl_hybrid_encrypt_assignments_dev on device addresses -> row i at d_out + i * stride_elems elements (default: the row length); generator and
+        initial_state stay host memory; finished on return"""
+        st = _duplex_state(initial_state, width)
+        g = np.ascontiguousarray(np.asarray(generator, dtype=np.uint64).reshape(2, 4))
+        stride = self.L.zl_hybrid_encrypt_assignment_elems(curve, width, bits, header_len, blocks) if stride_elems is None else stride_elems
+        self._check(self.L.zl_hybrid_encrypt_assignments_dev(self._ctx, curve, width, bits, None if st is None else _p64(st), _p64(g), C.c_void_p(d_esk), C.c_void_p(d_pks),
+                                                             pk_stride, C.c_void_p(d_headers), header_len, C.c_void_p(d_plaintexts), blocks, count, C.c_void_p(d_out), stride),
+                    "zl_hybrid_encrypt_assignments_dev")
+
+    def _prove_hybrid_encryptions(self, pkc, curve: int, r1cs_handle: int, bits: int, initial_state, generator, esk, pks, headers, plaintexts, r: np.ndarray, s: np.ndarray):
+        st, g, e, pk, ps, h, t = _hybrid_operands(initial_state, generator, esk, pks, headers, plaintexts)
+        count, blocks, width = t.shape[0], t.shape[1], t.shape[2] + 1
+        r, s = np.ascontiguousarray(r, dtype=np.uint64).reshape(count, 4), np.ascontiguousarray(s, dtype=np.uint64).reshape(count, 4)
+        out = (G16ProofC * max(1, count))()
+        epks, tags, cts = np.zeros((count, 2, 4), dtype=np.uint64), np.zeros((count, 4), dtype=np.uint64), np.zeros_like(t)
+        self._check(self.L.zl_groth16_prove_hybrid_encryptions(self._ctx, C.byref(pkc), r1cs_handle, width, bits, None if st is None else _p64(st), _p64(g), _ptr_or_none(e),
+                                                               _p64(pk), ps, _ptr_or_none(h), h.shape[1], _ptr_or_none(t), blocks, _ptr_or_none(r), _ptr_or_none(s), count, out,
+                                                               _ptr_or_none(epks), _ptr_or_none(tags), _ptr_or_none(cts)), "zl_groth16_prove_hybrid_encryptions")
+        return [_proof_tuple(curve, p) for p in out[:count]], epks, tags, cts
+
+    def groth16_prove_hybrid_encryptions(self, curve: int, pk: dict, r1cs_handle: int, bits: int, initial_state, generator, esk, pks, headers, plaintexts, r: np.ndarray,
+                                         s: np.ndarray):
+        """zl_groth16_prove_hybrid_encryptions: operands as hybrid_encrypt and blinding scalars -> (`count` proofs, epks (count, 2, 4), tags (count, 4), ciphertexts):
+        the public inputs of proof j are the generator, pks[j], epks[j], tags[j], ciphertexts[j] and headers[j]"""
+        pkc, keep_pk = _pk_struct(curve, pk)
+        return self._prove_hybrid_encryptions(pkc, curve, r1cs_handle, bits, initial_state, generator, esk, pks, headers, plaintexts, r, s)
 
     def hybrid_encrypt(self, curve: int, initial_state, generator, esk, pks, headers, plaintexts, check_subgroup: bool = False):
         """zl_hybrid_encrypt_batch: generator (2, 4), esk (count, 4), pks (count, 2, 4) or one (2, 4), headers (count, H, 4), plaintexts (count, N, W - 1, 4) ->
@@ -1797,6 +1841,42 @@ def ed_scalar_mul_assignments_host(curve: int, points, scalars, bits=None) -> np
     return _ed_scalar_mul_assignments(load_library(), None, curve, points, scalars, bits)
 
 
+def _hybrid_operands(initial_state, generator, esk, pks, headers, plaintexts):
+    t = np.ascontiguousarray(np.asarray(plaintexts, dtype=np.uint64))
+    h = np.ascontiguousarray(np.asarray(headers, dtype=np.uint64))
+    if t.ndim != 4 or t.shape[3] != 4 or h.ndim != 3 or h.shape[2] != 4 or h.shape[0] != t.shape[0]:
+        raise ValueError("plaintexts are (count, N, W - 1, 4), headers (count, H, 4) uint64 words")
+    count = t.shape[0]
+    g = np.ascontiguousarray(np.asarray(generator, dtype=np.uint64).reshape(2, 4))
+    e = np.ascontiguousarray(np.asarray(esk, dtype=np.uint64).reshape(count, 4))
+    pk, ps = _ed_operand(pks, 2, "pks")
+    if ps and pk.shape[0] != count:
+        raise ValueError("one public key per item, or one for all")
+    return _duplex_state(initial_state, t.shape[2] + 1), g, e, pk, ps, h, t
+
+
+def hybrid_encrypt_assignment_elems(curve: int, width: int, bits: int, header_len: int, blocks: int) -> int:
+    """elements of one hybrid-encryption assignment: 27 bits - 13 + 2 N (W - 1) + H + 3 S (0 for a parameter out of range)"""
+    if not (0 <= width < 2**32 and 0 <= bits < 2**32 and 0 <= header_len < 2**63 and 0 <= blocks < 2**63):
+        return 0
+    return int(load_library().zl_hybrid_encrypt_assignment_elems(curve, width, bits, header_len, blocks))
+
+
+def _hybrid_encrypt_assignments(L, ctx, curve: int, initial_state, generator, esk, pks, headers, plaintexts, bits) -> np.ndarray:
+    st, g, e, pk, ps, h, t = _hybrid_operands(initial_state, generator, esk, pks, headers, plaintexts)
+    count, blocks, width = t.shape[0], t.shape[1], t.shape[2] + 1
+    bits = ed_order_bits(curve) if bits is None else bits
+    out = np.zeros((count, hybrid_encrypt_assignment_elems(curve, width, bits, h.shape[1], blocks), 4), dtype=np.uint64)
+    _pos_check(L, L.zl_hybrid_encrypt_assignments(ctx, curve, width, bits, None if st is None else _p64(st), _p64(g), _ptr_or_none(e), _p64(pk), ps, _ptr_or_none(h),
+                                                  h.shape[1], _ptr_or_none(t), blocks, count, _ptr_or_none(out)), "zl_hybrid_encrypt_assignments")
+    return out
+
+
+def hybrid_encrypt_assignments_host(curve: int, initial_state, generator, esk, pks, headers, plaintexts, bits=None) -> np.ndarray:
+    """Backend.hybrid_encrypt_assignments on the host mirror"""
+    return _hybrid_encrypt_assignments(load_library(), None, curve, initial_state, generator, esk, pks, headers, plaintexts, bits)
+
+
 def _hybrid_encrypt(L, ctx, curve: int, initial_state, generator, esk, pks, headers, plaintexts, check_subgroup: bool):
     t = np.ascontiguousarray(np.asarray(plaintexts, dtype=np.uint64))
     h = np.ascontiguousarray(np.asarray(headers, dtype=np.uint64))
@@ -2318,6 +2398,37 @@ class Circuit:
         return self
 
     @classmethod
+    def hybrid_encrypt(cls, curve: int, initial_state, generator, esk: int, pk, header, plaintext, bits: Optional[int] = None, witness_only: bool = False) -> "Circuit":
+        """the hybrid-encryption circuit (zl_circuit_hybrid_encrypt): the public (epk, tag, ciphertext) is the hybrid encryption, to the public key `pk` (x, y) over
+        the public `generator` (x, y), of the secret `plaintext` -- N blocks of W - 1 integers each, which fixes the width W -- under the secret ephemeral key
+        `esk` (below the subgroup order and below 2^bits; bits None: the full width) and the public `header`; initial_state: W integers or None (zero).  Public
+        inputs: G, pk, epk, tag, ciphertext, header.  witness_only: as in the constructor."""
+        what = "zl_circuit_hybrid_encrypt"
+        self = cls.__new__(cls)
+        self.L = load_library()
+        self.curve = curve
+        self.witness_only = witness_only
+        self._c = C.c_void_p()
+        bits = ed_order_bits(curve) if bits is None else bits
+        blocks = [list(b) for b in plaintext]
+        width = len(blocks[0]) + 1 if blocks else 0
+        flat = [v for b in blocks for v in b]
+        st = None if initial_state is None else list(initial_state)
+        pts = [int(generator[0]), int(generator[1]), int(pk[0]), int(pk[1]), int(esk)]
+        if any(len(b) != width - 1 for b in blocks) or (st is not None and len(st) != width) or not 0 <= bits < 2**32 or any(
+                not 0 <= int(v) < 2**256 for v in flat + list(header) + (st or []) + pts):
+            raise BackendError(-1, what)
+        arr = lambda vs: np.array([[(int(v) >> (64 * j)) & (2**64 - 1) for j in range(4)] for v in vs], dtype=np.uint64).reshape(-1, 4)
+        w, h, p, s0 = arr(pts), arr(header), arr(flat), arr(st or [])
+        fn = self.L.zl_circuit_hybrid_encrypt_witness if witness_only else self.L.zl_circuit_hybrid_encrypt
+        rc = fn(curve, width, bits, None if st is None else _p64(s0), _p64(w[:2]), _p64(w[4]), _p64(w[2:4]), _ptr_or_none(h), h.shape[0], _ptr_or_none(p), len(blocks),
+                C.byref(self._c))
+        if rc:
+            raise BackendError(rc, what)
+        self._export()
+        return self
+
+    @classmethod
     def ed_scalar_mul(cls, curve: int, point, scalar: int, bits: Optional[int] = None, witness_only: bool = False) -> "Circuit":
         """the scalar-multiplication circuit (zl_circuit_ed_scalar_mul): the public point Q is `scalar` times the public `point` (x, y) of the embedded curve, for a
         secret scalar below the subgroup order and below 2^bits; bits None: the full width of the curve.  Public inputs: P.x, P.y, Q.x, Q.y.  witness_only: as
@@ -2547,6 +2658,15 @@ class Groth16Keys:
         headers[j], plaintexts[j]).  Keys of a circuit that has not the shape of the operands' (W, K, H, N) are refused by the library (ZL_EINVAL)."""
         self._upload_r1cs()
         return (lane or self.backend)._prove_encryptions(self.pk, self.circuit.curve, self._r1cs, initial_state, keys, headers, plaintexts, r, s)
+
+    def prove_hybrid_encryptions(self, initial_state, generator, esk, pks, headers, plaintexts, r: np.ndarray, s: np.ndarray, bits: Optional[int] = None,
+                                 lane: Optional[Backend] = None):
+        """zl_groth16_prove_hybrid_encryptions over this key: operands as Backend.hybrid_encrypt and blinding scalars r, s (count, 4) -> (proofs, epks (count, 2, 4),
+        tags (count, 4), ciphertexts (count, N, W - 1, 4)); proof j is prove_batch's for the assignment of Circuit.hybrid_encrypt(curve, initial_state, generator,
+        esk[j], pks[j], headers[j], plaintexts[j], bits).  bits None: the full width.  Keys of a circuit of another shape are refused by the library (ZL_EINVAL)."""
+        self._upload_r1cs()
+        bits = ed_order_bits(self.circuit.curve) if bits is None else bits
+        return (lane or self.backend)._prove_hybrid_encryptions(self.pk, self.circuit.curve, self._r1cs, bits, initial_state, generator, esk, pks, headers, plaintexts, r, s)
 
     def prove_scalar_muls(self, points, scalars, r: np.ndarray, s: np.ndarray, bits: Optional[int] = None, lane: Optional[Backend] = None):
         """zl_groth16_prove_ed_scalar_muls over this key: points (count, 2, 4) or one point (2, 4), scalars (count, 4) and blinding scalars r, s (count, 4) ->

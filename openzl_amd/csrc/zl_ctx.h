@@ -141,6 +141,9 @@ struct zl_scratch {
 //     The assignment trace (k_ed_mul_trace) takes NO bytes of it for its kernel: the points it keeps between its passes live in the row's own step cells
 //     (8 elements of 48 B in the 416 B of a step).  Only its staged operands count: 64 + 32 B of inputs, and, in the host-pointer form, the row itself
 //     (14 bits - 5 elements: 112 736 B at 252 bits, so some 2 300 rows a chunk under the 256 MiB budget) and 64 B for Q.
+//     The hybrid-encryption trace (k_ed_hybrid_ladders, then k_pos_duplex_trace_in) likewise: staged operands and, in the host-pointer form, the row (27 bits -
+//     13 + 2 T + H + 3 S elements: 247 680 B at 252 bits and (3; 0, 1), some 1 000 rows a chunk); its cipher launch stages nothing and takes no byte of
+//     ZL_SLOT_POSEIDON while this slot holds the chunk.
 enum zl_slot : int {
     ZL_SLOT_SET0_COUNTS = 0, ZL_SLOT_SET0_ENTRIES = 1, ZL_SLOT_SET0_BUCKETS = 2, ZL_SLOT_SET0_PARTIALS = 3, ZL_SLOT_SET0_TAIL = 4,
     ZL_SLOT_SORT_A = 5, ZL_SLOT_SORT_B = 6,

@@ -417,25 +417,13 @@ template <class FrP>
 ZL_HD Pt<FrP> pick(bool take, const Pt<FrP>& a, const Pt<FrP>& b) {
     return Pt<FrP>{pick<FrP>(take, a.X, b.X), pick<FrP>(take, a.Y, b.Y), pick<FrP>(take, a.Z, b.Z), pick<FrP>(take, a.T, b.T)};
 }
+// The ladder body of one multiplication k P: the cells of R_1 (sel0: 2 elements) and of the bits - 1 steps (13 elements each), written by the three passes
+// above with one inversion; the kept elements live in the step's own cells.  x, y: P loaded; p_xy: its canonical words (copied into R_1 when b_0 is set).  The
+// cells of the result -- the last select records, or R_1 when bits = 1 -- are ladder_result's.  Shared by zl_circuit_ed_scalar_mul's rows (trace_item) and the
+// two ladders of zl_circuit_hybrid_encrypt's (hybrid_ladder_item).
 template <class FrP>
-ZL_HD bool trace_item(const uint64_t* p_xy, const uint64_t* k, unsigned bits, uint64_t* row, uint64_t* q_out) {
+ZL_HD void ladder_cells(const El<FrP>& x, const El<FrP>& y, const uint64_t* p_xy, const uint64_t* k, unsigned bits, uint64_t* sel0, uint64_t* steps) {
     using B = EdBounds<FrP>;
-    El<FrP> x, y;
-    bool ok = load<FrP>(p_xy, x);
-    ok &= load<FrP>(p_xy + 4, y);
-    ok &= on_curve<FrP>(x, y);
-    ok &= scalar_ok<FrP>(k);
-#pragma unroll 1
-    for (unsigned i = bits; i < 256; i++) ok &= !scalar_bit(k, i);
-    uint64_t* bit_cells = row + 24;
-    uint64_t* sel0 = bit_cells + (size_t)bits * 4;
-    uint64_t* steps = sel0 + 8;
-    put_cell(row, 1, 0, 0, 0);
-    put_cell(row + 4, p_xy[0], p_xy[1], p_xy[2], p_xy[3]);
-    put_cell(row + 8, p_xy[4], p_xy[5], p_xy[6], p_xy[7]);
-    put_cell(row + 20, k[0], k[1], k[2], k[3]);
-#pragma unroll 1
-    for (unsigned i = 0; i < bits; i++) put_cell(bit_cells + (size_t)i * 4, scalar_bit(k, i) ? 1 : 0, 0, 0, 0);
     const bool b0 = scalar_bit(k, 0);
     if (b0) {
         put_cell(sel0, p_xy[0], p_xy[1], p_xy[2], p_xy[3]);
@@ -516,6 +504,35 @@ ZL_HD bool trace_item(const uint64_t* p_xy, const uint64_t* k, unsigned bits, ui
             py = my;
         }
     }
+}
+ZL_HD const uint64_t* ladder_result(const uint64_t* sel0, const uint64_t* steps, unsigned bits) {  // 8 words: (x, y) of k P
+    return bits > 1 ? steps + ((size_t)(bits - 2) * STEP_RECORDS + 11) * 4 : sel0;
+}
+ZL_HD bool scalar_fits(const uint64_t* k, unsigned bits) {  // below 2^bits
+    bool ok = true;
+#pragma unroll 1
+    for (unsigned i = bits; i < 256; i++) ok &= !scalar_bit(k, i);
+    return ok;
+}
+template <class FrP>
+ZL_HD bool trace_item(const uint64_t* p_xy, const uint64_t* k, unsigned bits, uint64_t* row, uint64_t* q_out) {
+    El<FrP> x, y;
+    bool ok = load<FrP>(p_xy, x);
+    ok &= load<FrP>(p_xy + 4, y);
+    ok &= on_curve<FrP>(x, y);
+    ok &= scalar_ok<FrP>(k);
+#pragma unroll 1
+    for (unsigned i = bits; i < 256; i++) ok &= !scalar_bit(k, i);
+    uint64_t* bit_cells = row + 24;
+    uint64_t* sel0 = bit_cells + (size_t)bits * 4;
+    uint64_t* steps = sel0 + 8;
+    put_cell(row, 1, 0, 0, 0);
+    put_cell(row + 4, p_xy[0], p_xy[1], p_xy[2], p_xy[3]);
+    put_cell(row + 8, p_xy[4], p_xy[5], p_xy[6], p_xy[7]);
+    put_cell(row + 20, k[0], k[1], k[2], k[3]);
+#pragma unroll 1
+    for (unsigned i = 0; i < bits; i++) put_cell(bit_cells + (size_t)i * 4, scalar_bit(k, i) ? 1 : 0, 0, 0, 0);
+    ladder_cells<FrP>(x, y, p_xy, k, bits, sel0, steps);
     const uint64_t* q = bits > 1 ? steps + ((size_t)(bits - 2) * STEP_RECORDS + 11) * 4 : sel0;
     uint64_t qw[8];
     for (int i = 0; i < 8; i++) qw[i] = q[i];
@@ -523,6 +540,66 @@ ZL_HD bool trace_item(const uint64_t* p_xy, const uint64_t* k, unsigned bits, ui
     put_cell(row + 16, qw[4], qw[5], qw[6], qw[7]);
     if (q_out)
         for (int i = 0; i < 8; i++) q_out[i] = qw[i];
+    return ok;
+}
+
+// ---- the complete assignment of zl_circuit_hybrid_encrypt (zl_host.hip hybrid_encrypt_circuit), its embedded-curve part.  T = N rate text elements, H header
+// elements, L = 13 bits - 11 elements a ladder, S the cipher's recorded S-boxes at K = 2; row = 27 bits - 13 + 2 T + H + 3 S elements of 4 canonical words:
+//   [0] 1   [1..3) G   [3..5) pk   [5..7) epk   [7] tag   [8 .. 8 + T) ciphertext   [.. + H) header   | esk   the bits   the G ladder (R_1, the steps)
+//   the pk ladder in the same form   [.. + T) plaintext   then the 3 S records.
+// One ITEM here is one (row, ladder), w the canonical words of the ladder's own point: ladder 0 multiplies G and also writes [0], G, pk, esk, the bit cells and epk (and epk_out, may be null); ladder 1
+// multiplies pk and writes nothing outside its ladder's cells -- its result cells are S, which the cipher launch reads as its key.  The two items of a row
+// touch disjoint cells and neither reads what the other writes, so they may run in any order or at once.  tag, ciphertext, header, plaintext and records are
+// the cipher's to write (zl_poseidon_dev.h, DuplexRowLayout).  Ladder 0 answers for esk (below l and below 2^bits), ladder 1 for pk (coordinates below q, on
+// the curve); G is the caller's to check, once per call.  No new arithmetic: every bound is trace_item's.
+struct HybridRow {
+    unsigned bits;
+    size_t T, H, S;
+    ZL_HD constexpr size_t ladder() const { return 13 * (size_t)bits - 11; }
+    ZL_HD constexpr size_t esk_at() const { return 8 + T + H; }
+    ZL_HD constexpr size_t bits_at() const { return esk_at() + 1; }
+    ZL_HD constexpr size_t ladder_at(int which) const { return bits_at() + bits + (which ? ladder() : 0); }
+    ZL_HD constexpr size_t plain_at() const { return ladder_at(1) + ladder(); }
+    ZL_HD constexpr size_t key_at() const { return plain_at() - 2; }  // S = the pk ladder's result: its last two cells, the last select records or R_1
+    ZL_HD constexpr size_t rec_at() const { return plain_at() + T; }
+    ZL_HD constexpr size_t elems() const { return rec_at() + 3 * S; }
+};
+static_assert(HybridRow{1, 2, 0, 0}.elems() == 27 - 13 + 4 && HybridRow{252, 2, 0, 315}.elems() == 27 * 252 - 13 + 4 + 945, "27 bits - 13 + 2 T + H + 3 S");
+static_assert(HybridRow{1, 2, 0, 0}.key_at() == HybridRow{1, 2, 0, 0}.ladder_at(1) &&
+                  HybridRow{9, 2, 0, 0}.key_at() == HybridRow{9, 2, 0, 0}.ladder_at(1) + 2 + (9 - 2) * STEP_RECORDS + 11,
+              "the key cells are R_1 at one bit, else ladder_result's: records 11 and 12 of the last step");
+template <class FrP>
+ZL_HD bool hybrid_ladder_item(const uint64_t* w, const uint64_t* pk_xy, const uint64_t* esk, const HybridRow& lay, int which, uint64_t* row, uint64_t* epk_out) {
+    El<FrP> x, y;
+    bool ok = load<FrP>(w, x);
+    ok &= load<FrP>(w + 4, y);
+    uint64_t* sel0 = row + lay.ladder_at(which) * 4;
+    uint64_t* steps = sel0 + 8;
+    if (which) {
+        ok &= on_curve<FrP>(x, y);
+    } else {
+        ok = scalar_ok<FrP>(esk);  // (G was checked on the host)
+        ok &= scalar_fits(esk, lay.bits);
+        put_cell(row, 1, 0, 0, 0);
+        put_cell(row + 4, w[0], w[1], w[2], w[3]);
+        put_cell(row + 8, w[4], w[5], w[6], w[7]);
+        put_cell(row + 12, pk_xy[0], pk_xy[1], pk_xy[2], pk_xy[3]);
+        put_cell(row + 16, pk_xy[4], pk_xy[5], pk_xy[6], pk_xy[7]);
+        put_cell(row + lay.esk_at() * 4, esk[0], esk[1], esk[2], esk[3]);
+        uint64_t* bit_cells = row + lay.bits_at() * 4;
+#pragma unroll 1
+        for (unsigned i = 0; i < lay.bits; i++) put_cell(bit_cells + (size_t)i * 4, scalar_bit(esk, i) ? 1 : 0, 0, 0, 0);
+    }
+    ladder_cells<FrP>(x, y, w, esk, lay.bits, sel0, steps);
+    if (!which) {
+        const uint64_t* q = ladder_result(sel0, steps, lay.bits);
+        uint64_t qw[8];
+        for (int i = 0; i < 8; i++) qw[i] = q[i];
+        put_cell(row + 20, qw[0], qw[1], qw[2], qw[3]);
+        put_cell(row + 24, qw[4], qw[5], qw[6], qw[7]);
+        if (epk_out)
+            for (int i = 0; i < 8; i++) epk_out[i] = qw[i];
+    }
     return ok;
 }
 

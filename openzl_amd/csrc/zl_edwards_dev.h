@@ -11,3 +11,12 @@
 struct zl_ctx;
 int zl_ed_scalar_mul_trace_rows(zl_ctx* ctx, int curve, unsigned bits, const uint64_t* points_xy, size_t point_stride, const uint64_t* scalars, size_t count, void* d_rows,
                                 size_t stride_elems, uint64_t* results_out);
+// The hybrid-encryption producer of the fused prover (zl_groth16_prove_hybrid_encryptions), under the same rules: HOST generator (one point), ephemeral keys
+// (count x 4 words), public keys (count x pk_stride x 8 words, pk_stride 0 or 1), headers (count x header_len) and plaintexts (count x blocks x (width - 1)) ->
+// the assignments of zl_circuit_hybrid_encrypt as rows in DEVICE memory; epks_out / tags_out / ciphertexts_out (host, each may be null) receive epk, tag and
+// ciphertext of every item.  Two launches a chunk on ctx's stream -- the ladders, one lane per (row, ladder), then the cipher keyed from the row's own cells
+// (zl_poseidon_duplex_row_launch) -- both through ZL_SLOT_EDWARDS.  Curve, width, bits, the lengths, initial_state and the generator are checked here as
+// zl_hybrid_encrypt_assignments does.
+int zl_hybrid_encrypt_trace_rows(zl_ctx* ctx, int curve, unsigned width, unsigned bits, const uint64_t* initial_state, const uint64_t* generator_xy, const uint64_t* esk,
+                                 const uint64_t* pks_xy, size_t pk_stride, const uint64_t* headers, size_t header_len, const uint64_t* plaintexts, size_t blocks, size_t count,
+                                 void* d_rows, size_t stride_elems, uint64_t* epks_out, uint64_t* tags_out, uint64_t* ciphertexts_out);

@@ -14,6 +14,9 @@
 //                    precomputed (batch-inverted: one inversion), uploads it once, and every lane does 63 mixed additions and no doubling.
 //   k_ed_mul_trace<FrP>  the complete assignment of zl_circuit_ed_scalar_mul per item (ed::trace_item): the double-and-add ladder of the in-circuit gadget in extended
 //                    coordinates, ONE inversion a lane, every affine record by Montgomery's trick; no table, no scratch slot.
+//   k_ed_hybrid_ladders<FrP>  the embedded-curve part of zl_circuit_hybrid_encrypt's assignment: ONE LANE PER (row, ladder) -- blockIdx.y says which, so it is wave-uniform:
+//                    the ladder over G (and the row's head: 1, G, pk, esk, the bits, epk) or the ladder over pk, whose result cells are the cipher's key.  Both run
+//                    ed::ladder_cells, k_ed_mul_trace's body; the cipher's cells are k_pos_duplex_trace_in's, launched behind it on the same stream.
 // A lane at or above the item count returns before it reads or writes anything; a table is only touched by the lane that owns it.
 #include <string.h>
 #include <atomic>
@@ -22,6 +25,7 @@
 #include "zl_ctx.h"
 #include "zl_edwards.h"
 #include "zl_edwards_dev.h"
+#include "zl_poseidon_dev.h"
 
 using namespace openzl;
 
@@ -129,6 +133,31 @@ __global__ __launch_bounds__(BLOCK) void k_ed_mul_trace(const uint64_t* __restri
     const size_t p = (size_t)blockIdx.x * BLOCK + threadIdx.x;
     if (p >= n) return;
     const bool ok = ed::trace_item<FrP>(points + p * point_stride * 8, scalars + p * 4, bits, out + p * stride * 4, q_out ? q_out + p * 8 : nullptr);
+    if (!ok) atomicOr(flag, 1u);
+}
+
+// The two ladders of zl_circuit_hybrid_encrypt's rows (ed::hybrid_ladder_item), one lane per (row, ladder): the grid is blocks_of(n) x 2 and blockIdx.y is the
+// ladder, so a wave runs one ladder only and the shared G comes through uniform loads (the branch below is on a wave-uniform value; the body is ONE copy).  A
+// lane that ran both ladders in series would pay the launch's latency twice: the two depend only on esk's bits.  The G lane (y = 0) also writes the row's head and
+// epk (and epk_out, may be null, densely); the pk lane (y = 1) writes its ladder's cells and nothing else.  Row p = out + p * stride elements, 16-byte aligned;
+// cells behind the pk ladder are the cipher launch's.  No scratch slot, as k_ed_mul_trace.
+template <class FrP>
+__global__ __launch_bounds__(BLOCK) void k_ed_hybrid_ladders(const uint64_t* __restrict__ g, const uint64_t* __restrict__ pks, uint32_t pk_stride, const uint64_t* __restrict__ esk,
+                                                             const ed::HybridRow lay, size_t n, uint64_t* __restrict__ out, size_t stride, uint64_t* __restrict__ epk_out,
+                                                             uint32_t* __restrict__ flag) {
+    const size_t p = (size_t)blockIdx.x * BLOCK + threadIdx.x;
+    if (p >= n) return;
+    const int which = (int)blockIdx.y;
+    const uint64_t* pk = pks + p * pk_stride * 8;
+    uint64_t w[8];
+    if (which == 0) {
+#pragma unroll
+        for (int i = 0; i < 8; i++) w[i] = g[i];
+    } else {
+#pragma unroll
+        for (int i = 0; i < 8; i++) w[i] = pk[i];
+    }
+    const bool ok = ed::hybrid_ladder_item<FrP>(w, pk, esk + p * 4, lay, which, out + p * stride * 4, epk_out ? epk_out + p * 8 : nullptr);
     if (!ok) atomicOr(flag, 1u);
 }
 
@@ -423,6 +452,83 @@ size_t trace_elems(unsigned bits) {
     return bits >= 1 && bits <= ed::order_bits<FrP>() ? ed::trace_row_elems(bits) : 0;
 }
 
+// ---- the hybrid-encryption circuit's assignments.  What a call is, beside its operands: checked by hybrid_trace_params, init the W canonical elements
+struct HybridTrace {
+    zl_curve_t curve;
+    unsigned width;
+    uint64_t init[4 * poseidon_dev::MAX_WIDTH];
+    size_t H, N;
+    ed::HybridRow row;
+    zl_duplex_row_layout cipher() const { return zl_duplex_row_layout{7, 8, 8 + row.T, row.key_at(), row.plain_at(), row.rec_at()}; }
+};
+// 0 elements for a parameter out of range: the curve, the cipher's limits at key_len = 2, 1 <= bits <= the order's length
+size_t hybrid_trace_elems(zl_curve_t curve, unsigned width, unsigned bits, size_t H, size_t N, ed::HybridRow* row_out) {
+    namespace pd = poseidon_dev;
+    if (!valid_curve(curve) || !pd::encrypt_shape_ok(width, 2, H, N) || bits < 1 || bits > (curve == ZL_BLS12_381 ? ed::order_bits<BLS12_381_Fr>() : ed::order_bits<BN254_Fr>()))
+        return 0;
+    const ed::HybridRow row{bits, N * (width - 1), H, pd::encrypt_sboxes(width, 2, H, N)};
+    if (row_out) *row_out = row;
+    return row.elems();
+}
+static_assert(27 * 252 - 13 + 2 * 1024 * 5 + 64 + 3 * poseidon_dev::encrypt_sboxes(6, 2, 64, 1024) < ((size_t)1 << 31), "the longest row fits 31 bits");
+template <class FrP>
+bool generator_ok(const uint64_t* g) {
+    ed::El<FrP> x, y;
+    bool ok = ed::load<FrP>(g, x);
+    ok &= ed::load<FrP>(g + 4, y);
+    return ok && ed::on_curve<FrP>(x, y);
+}
+// the parameters, the initial state and G, on the host before any work
+int hybrid_trace_params(zl_curve_t curve, unsigned width, unsigned bits, const uint64_t* initial_state, const uint64_t* g, size_t H, size_t N, HybridTrace* c) {
+    c->curve = curve;
+    c->width = width;
+    c->H = H;
+    c->N = N;
+    if (hybrid_trace_elems(curve, width, bits, H, N, &c->row) == 0 || !g) return ZL_EINVAL;
+    if (zl_poseidon_duplex_row_params((int)curve, width, initial_state, 2, H, N, c->init)) return ZL_EINVAL;
+    return (curve == ZL_BLS12_381 ? generator_ok<BLS12_381_Fr>(g) : generator_ok<BN254_Fr>(g)) ? ZL_OK : ZL_EINVAL;
+}
+// host mirror: the 2 count ladders over the pool (the kernel's text), then the cipher's host rows with the key read from each row's S cells
+template <class FrP>
+int host_hybrid_trace(const HybridTrace& c, const uint64_t* g, const uint64_t* esk, const uint64_t* pks, size_t ps, const uint64_t* headers, const uint64_t* texts, size_t count,
+                      uint64_t* out) {
+    const size_t nv = c.row.elems();
+    std::atomic<int> bad{0};
+    host_for(2 * count, [&](size_t j) {
+        const size_t i = j >> 1;
+        const int which = (int)(j & 1);
+        const uint64_t* pk = pks + i * ps * 8;
+        if (!ed::hybrid_ladder_item<FrP>(which ? pk : g, pk, esk + i * 4, c.row, which, out + i * nv * 4, nullptr)) bad.store(1);
+    });
+    const int rc = zl_poseidon_duplex_row_host((int)c.curve, c.width, c.init, c.cipher(), 2, headers, c.H, texts, c.N, count, out, nv);
+    return rc ? rc : bad.load() ? ZL_EINVAL : ZL_OK;
+}
+// Every device form.  esk / pks / headers / texts: staged per chunk when in_on_host, else device memory; g: host memory in every form, uploaded once;
+// host_rows != null: the rows are staged, dense, and downloaded (d_rows and stride are ignored), otherwise row i goes to d_rows + i * stride elements; host_epk /
+// host_tags / host_cts != null: epk, tag and ciphertext of every item are staged and downloaded.  A chunk is two launches on the ctx's stream: the ladders
+// (2 m lanes), then the cipher over the same rows -- through ZL_SLOT_EDWARDS alone: the cipher launch stages nothing.
+template <class FrP>
+int hybrid_trace_run(zl_ctx* ctx, const HybridTrace& c, const uint64_t* g, const uint64_t* esk, const uint64_t* pks, size_t ps, const uint64_t* headers, const uint64_t* texts,
+                     bool in_on_host, size_t count, uint64_t* d_rows, size_t stride, uint64_t* host_rows, uint64_t* host_epk, uint64_t* host_tags, uint64_t* host_cts) {
+    const size_t nv = c.row.elems(), T = c.row.T;
+    std::vector<Seg> segs;
+    if (in_on_host) segs = {staged(32, esk, nullptr), ps ? staged(64, pks, nullptr) : staged_once(64, pks), staged(c.H * 32, headers, nullptr), staged(T * 32, texts, nullptr)};
+    else segs = {device(32, esk), device(ps * 64, pks), device(c.H * 32, headers), device(T * 32, texts)};
+    segs.push_back(staged_once(64, g));                                                                      // 4
+    segs.push_back(host_rows ? staged(nv * 32, nullptr, host_rows) : device(stride * 32, d_rows));           // 5
+    segs.push_back(staged(host_epk ? 64 : 0, nullptr, host_epk));                                            // 6
+    segs.push_back(staged(host_tags ? 32 : 0, nullptr, host_tags));                                          // 7
+    segs.push_back(staged(host_cts ? T * 32 : 0, nullptr, host_cts));                                        // 8
+    const zl_duplex_row_layout lay = c.cipher();
+    return run_chunks(ctx, count, false, segs, [&](size_t, size_t m, void* const* d, uint32_t*, uint32_t* flag) -> int {
+        const size_t st = host_rows ? nv : stride;
+        hipLaunchKernelGGL((k_ed_hybrid_ladders<FrP>), dim3(blocks_of(m), 2), dim3(BLOCK), 0, ctx->stream, u64(d[4]), u64(d[1]), (uint32_t)ps, u64(d[0]), c.row, m, u64(d[5]), st,
+                           u64(d[6]), flag);
+        ZL_HIP(ctx, hipGetLastError());
+        return zl_poseidon_duplex_row_launch(ctx, (int)c.curve, c.width, c.init, lay, 2, d[2], c.H, d[3], c.N, m, d[5], st, d[7], d[8], flag);
+    });
+}
+
 // ---- hybrid encryption.  What a call is, beside its operands (checked by the entry points)
 struct HybridCall {
     zl_curve_t curve;
@@ -545,7 +651,47 @@ int zl_ed_scalar_mul_trace_rows(zl_ctx* ctx, int curve, unsigned bits, const uin
     return ZL_ED_CURVE(curve, trace_run, ctx, points_xy, point_stride, scalars, true, bits, count, static_cast<uint64_t*>(d_rows), stride_elems, nullptr, results_out);
 }
 
+int zl_hybrid_encrypt_trace_rows(zl_ctx* ctx, int curve, unsigned width, unsigned bits, const uint64_t* initial_state, const uint64_t* generator_xy, const uint64_t* esk,
+                                 const uint64_t* pks_xy, size_t pk_stride, const uint64_t* headers, size_t header_len, const uint64_t* plaintexts, size_t blocks, size_t count,
+                                 void* d_rows, size_t stride_elems, uint64_t* epks_out, uint64_t* tags_out, uint64_t* ciphertexts_out) {
+    HybridTrace c;
+    const int rc = hybrid_trace_params((zl_curve_t)curve, width, bits, initial_state, generator_xy, header_len, blocks, &c);
+    if (rc) return rc;
+    return ZL_ED_CURVE(curve, hybrid_trace_run, ctx, c, generator_xy, esk, pks_xy, pk_stride, headers, plaintexts, true, count, static_cast<uint64_t*>(d_rows), stride_elems,
+                       nullptr, epks_out, tags_out, ciphertexts_out);
+}
+
 extern "C" {
+
+size_t zl_hybrid_encrypt_assignment_elems(zl_curve_t curve, unsigned width, unsigned bits, size_t header_len, size_t blocks) {
+    return hybrid_trace_elems(curve, width, bits, header_len, blocks, nullptr);
+}
+int zl_hybrid_encrypt_assignments(zl_ctx* ctx, zl_curve_t curve, unsigned width, unsigned bits, const uint64_t* initial_state, const uint64_t* generator_xy, const uint64_t* esk,
+                                  const uint64_t* pks_xy, size_t pk_stride, const uint64_t* headers, size_t header_len, const uint64_t* plaintexts, size_t blocks, size_t count,
+                                  uint64_t* out) {
+    HybridTrace c;
+    const int rc = hybrid_trace_params(curve, width, bits, initial_state, generator_xy, header_len, blocks, &c);
+    if (rc) return rc;
+    if (pk_stride > 1 || (count && (!esk || !pks_xy || (header_len && !headers) || !plaintexts || !out))) return ZL_EINVAL;
+    if (count == 0) return ZL_OK;
+    if (on_host(ctx, count)) return ZL_ED_CURVE(curve, host_hybrid_trace, c, generator_xy, esk, pks_xy, pk_stride, headers, plaintexts, count, out);
+    ZL_HIP(ctx, hipSetDevice(ctx->device));
+    return ZL_ED_CURVE(curve, hybrid_trace_run, ctx, c, generator_xy, esk, pks_xy, pk_stride, headers, plaintexts, true, count, nullptr, 0, out, nullptr, nullptr, nullptr);
+}
+int zl_hybrid_encrypt_assignments_dev(zl_ctx* ctx, zl_curve_t curve, unsigned width, unsigned bits, const uint64_t* initial_state, const uint64_t* generator_xy,
+                                      const void* d_esk, const void* d_pks_xy, size_t pk_stride, const void* d_headers, size_t header_len, const void* d_plaintexts,
+                                      size_t blocks, size_t count, void* d_out, size_t stride_elems) {
+    HybridTrace c;
+    const int rc = ctx ? hybrid_trace_params(curve, width, bits, initial_state, generator_xy, header_len, blocks, &c) : ZL_EINVAL;
+    if (rc) return rc;
+    if (pk_stride > 1 || stride_elems < c.row.elems() || ((uintptr_t)d_out & 15) || (count && (!d_esk || !d_pks_xy || (header_len && !d_headers) || !d_plaintexts || !d_out)))
+        return ZL_EINVAL;
+    if (count == 0) return ZL_OK;
+    ZL_HIP(ctx, hipSetDevice(ctx->device));
+    return ZL_ED_CURVE(curve, hybrid_trace_run, ctx, c, generator_xy, static_cast<const uint64_t*>(d_esk), static_cast<const uint64_t*>(d_pks_xy), pk_stride,
+                       static_cast<const uint64_t*>(d_headers), static_cast<const uint64_t*>(d_plaintexts), false, count, static_cast<uint64_t*>(d_out), stride_elems, nullptr,
+                       nullptr, nullptr, nullptr);
+}
 
 size_t zl_ed_scalar_mul_assignment_elems(zl_curve_t curve, unsigned bits) {
     if (!valid_curve(curve)) return 0;

@@ -1502,6 +1502,47 @@ extern "C" int zl_groth16_prove_ed_scalar_muls(zl_ctx* ctx, const zl_g16_pk* pk,
     };
     return groth16_prove_batch_any(ctx, pk, rd, src, 0, r, s, count, proofs);
 }
+// Hybrid encryptions from generator, ephemeral keys, public keys, headers and plaintexts: the ladder launch and the cipher launch write each chunk's rows into
+// the chunk's block; epk, tag and ciphertext come out beside the proofs.  The agreement and the cipher run once.
+extern "C" int zl_groth16_prove_hybrid_encryptions(zl_ctx* ctx, const zl_g16_pk* pk, uint64_t r1cs_handle, unsigned width, unsigned bits, const uint64_t* initial_state,
+                                                   const uint64_t* generator_xy, const uint64_t* esk, const uint64_t* pks_xy, size_t pk_stride, const uint64_t* headers,
+                                                   size_t header_len, const uint64_t* plaintexts, size_t blocks, const uint64_t* r, const uint64_t* s, size_t count,
+                                                   zl_g16_proof* proofs, uint64_t* epks_out, uint64_t* tags_out, uint64_t* ciphertexts_out) {
+    if (!ctx || !pk || !generator_xy || pk_stride > 1 || (count && (!esk || !pks_xy || (header_len && !headers) || !plaintexts || !r || !s || !proofs))) return ZL_EINVAL;
+    const zl_r1cs_dev* rd = nullptr;
+    const int rc0 = g16_entry(ctx, pk, r1cs_handle, r, s, count, &rd);
+    if (rc0) return rc0;
+    const zl_curve_t curve = pk->curve;
+    const size_t nv = zl_hybrid_encrypt_assignment_elems(curve, width, bits, header_len, blocks);  // (0 for an unknown curve as well)
+    if (nv == 0) return ZL_EINVAL;
+    // the shape: n_instance = 8 + T + H fixes where the witnesses begin, n_witness = nv - n_instance, and the family's n_witness - (n_constraints - 1) = -2; what
+    // the matrices say cannot be checked, as with a witness-only compiler
+    const size_t T = blocks * (width - 1), ni = 8 + T + header_len;
+    if (rd->n_instance != ni || rd->n_witness != nv - ni || rd->n_constraints != rd->n_witness + 3) return ZL_EINVAL;
+    // the initial state and the generator, before any work (and at count == 0)
+    const int rc1 = zl_hybrid_encrypt_assignments(nullptr, curve, width, bits, initial_state, generator_xy, nullptr, nullptr, 0, nullptr, header_len, nullptr, blocks, 0, nullptr);
+    if (rc1) return rc1;
+    if (count == 0) return ZL_OK;
+    const size_t H = header_len;
+    G16BatchSource src;
+    src.fill_dev = [=](size_t c0, size_t ch, void* d_rows) {
+        return zl_hybrid_encrypt_trace_rows(ctx, (int)curve, width, bits, initial_state, generator_xy, esk + c0 * 4, pks_xy + c0 * pk_stride * 8, pk_stride, headers + c0 * H * 4, H,
+                                            plaintexts + c0 * T * 4, blocks, ch, d_rows, nv, epks_out ? epks_out + c0 * 8 : nullptr, tags_out ? tags_out + c0 * 4 : nullptr,
+                                            ciphertexts_out ? ciphertexts_out + c0 * T * 4 : nullptr);
+    };
+    src.fill_host = [=](size_t c0, size_t ch, uint64_t* rows) {
+        const int rc = zl_hybrid_encrypt_assignments(ctx, curve, width, bits, initial_state, generator_xy, esk + c0 * 4, pks_xy + c0 * pk_stride * 8, pk_stride, headers + c0 * H * 4,
+                                                     H, plaintexts + c0 * T * 4, blocks, ch, rows);
+        for (size_t j = 0; rc == ZL_OK && j < ch; j++) {  // [5..7) epk, [7] tag, [8 .. 8 + T) ciphertext
+            const uint64_t* row = rows + j * nv * 4;
+            if (epks_out) memcpy(epks_out + (c0 + j) * 8, row + 20, 64);
+            if (tags_out) memcpy(tags_out + (c0 + j) * 4, row + 28, 32);
+            if (ciphertexts_out) memcpy(ciphertexts_out + (c0 + j) * T * 4, row + 32, T * 32);
+        }
+        return rc;
+    };
+    return groth16_prove_batch_any(ctx, pk, rd, src, 0, r, s, count, proofs);
+}
 extern "C" int zl_groth16_last_h(zl_ctx* ctx, uint64_t* out, size_t n) {
     if (!ctx || !out || !ctx->g16_h || n > ctx->g16_h_n) return ZL_EINVAL;
     ZL_HIP(ctx, hipMemcpyAsync(out, ctx->g16_h, n * 32, hipMemcpyDeviceToHost, ctx->stream));

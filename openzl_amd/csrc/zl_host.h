@@ -487,6 +487,27 @@ Fp<FrP> duplex_decrypt(const Constants<FrP, W>& c, Fp<FrP> state[W], const Fp<Fr
     }
     return state[1];
 }
+// The cipher in circuit over a running state of W variables or constants: duplex_setup's and duplex_encrypt's block walk on variables.  `key` may be fresh
+// witnesses (zl_circuit_poseidon_encrypt) or variables the circuit already holds (zl_circuit_hybrid_encrypt: the agreed point's coordinates); additions into
+// the rate are linear and allocate nothing, so the only witnesses are the S-box records of the permutations, in execution order.  ct[j] receives the rate lane
+// read before the permutation of message block j / rate; the state is left as the cipher leaves it: the tag is state[1].
+template <class FrP, int W>
+void duplex_encrypt_circuit(const Constants<FrP, W>& c, FpVar<FrP> state[W], const std::vector<FpVar<FrP>>& key, const std::vector<FpVar<FrP>>& header,
+                            const std::vector<FpVar<FrP>>& text, std::vector<FpVar<FrP>>& ct, R1CS<FrP>& cs) {
+    constexpr size_t rate = W - 1;
+    for (int part = 0; part < 2; part++) {
+        const std::vector<FpVar<FrP>>& src = part ? header : key;
+        for (size_t b = 0; b <= src.size() / rate; b++) {
+            for (size_t i = 0; i < rate && b * rate + i < src.size(); i++) state[1 + i] = cs.add(state[1 + i], src[b * rate + i]);
+            permute<FrP, W>(c, state, cs);
+        }
+    }
+    ct.resize(text.size());
+    for (size_t j = 0; j < text.size() / rate; j++) {
+        for (size_t i = 0; i < rate; i++) ct[j * rate + i] = state[1 + i] = cs.add(state[1 + i], text[j * rate + i]);
+        permute<FrP, W>(c, state, cs);
+    }
+}
 }  // namespace poseidon
 
 // ---- the embedded twisted Edwards curve in circuit ----------------------------------------------------------------------------------------
@@ -541,7 +562,23 @@ PointVar<FrP> add_points(const Coeffs<FrP>& k, const PointVar<FrP>& p, const Poi
     const V y3 = cs.mul_equals(den_y, num_y, zl::mul(num_y.value, zl::inv(den_y.value)));
     return PointVar<FrP>{x3, y3};
 }
-// bits: the Boolean witnesses of the scalar, least significant first, at least one
+// The scalar's side of a multiplication: `bits` Boolean witnesses b_0 .. (least significant first, one row each) of the words s_words, and the row
+// sum 2^i b_i = s for a variable s the circuit already holds.  One decomposition may feed several ladders (zl_circuit_hybrid_encrypt: esk G and esk pk).
+template <class FrP>
+std::vector<FpVar<FrP>> scalar_bits(const FpVar<FrP>& s, const uint64_t* s_words, unsigned bits, R1CS<FrP>& cs) {
+    using F = Fp<FrP>;
+    std::vector<FpVar<FrP>> b(bits);
+    for (unsigned i = 0; i < bits; i++) b[i] = cs.new_boolean_witness((s_words[i >> 6] >> (i & 63)) & 1);
+    FpVar<FrP> sum = b[0];
+    F pow2 = F::one();
+    for (unsigned i = 1; i < bits; i++) {
+        pow2 = zl::add(pow2, pow2);
+        sum = cs.add(sum, cs.mul_const(b[i], pow2));
+    }
+    cs.enforce_equal(sum, s);
+    return b;
+}
+// the ladder over given bits from a point whose coordinates are variables.  bits: the Boolean witnesses of the scalar, least significant first, at least one
 template <class FrP>
 PointVar<FrP> scalar_mul_le(const Coeffs<FrP>& k, const PointVar<FrP>& p, const std::vector<FpVar<FrP>>& bits, R1CS<FrP>& cs) {
     using F = Fp<FrP>;

@@ -751,17 +751,7 @@ static R1CS<FrP> poseidon_encrypt(bool witness_only, const Fp<FrP>* init_canon, 
         for (size_t i = 0; i < header_len; i++) hv[i] = V{typename R1CS<FrP>::LC{}, header[i], false};
     V state[W];
     for (int i = 0; i < W; i++) state[i] = cs.constant(zl::to_mont(init_canon[i]));
-    for (int part = 0; part < 2; part++) {
-        const std::vector<V>& src = part ? hv : kv;
-        for (size_t b = 0; b <= src.size() / rate; b++) {
-            for (size_t i = 0; i < rate && b * rate + i < src.size(); i++) state[1 + i] = cs.add(state[1 + i], src[b * rate + i]);
-            poseidon::permute<FrP, W>(consts, state, cs);
-        }
-    }
-    for (size_t j = 0; j < blocks; j++) {
-        for (size_t i = 0; i < rate; i++) cv[j * rate + i] = state[1 + i] = cs.add(state[1 + i], pv[j * rate + i]);
-        poseidon::permute<FrP, W>(consts, state, cs);
-    }
+    poseidon::duplex_encrypt_circuit<FrP, W>(consts, state, kv, hv, pv, cv, cs);
     if (witness_only) {
         pub_tag = cs.new_input(state[1].value);
         for (size_t i = 0; i < n_text; i++) pub_ct[i] = cs.new_input(cv[i].value);
@@ -789,18 +779,58 @@ static R1CS<FrP> ed_scalar_mul_circuit(bool witness_only, unsigned bits, const F
     F s_canon;
     memcpy(s_canon.l, s_words, 32);
     const V s = cs.new_witness(zl::to_mont(s_canon));
-    std::vector<V> b(bits);
-    for (unsigned i = 0; i < bits; i++) b[i] = cs.new_boolean_witness((s_words[i >> 6] >> (i & 63)) & 1);
-    V sum = b[0];
-    F pow2 = F::one();
-    for (unsigned i = 1; i < bits; i++) {
-        pow2 = zl::add(pow2, pow2);
-        sum = cs.add(sum, cs.mul_const(b[i], pow2));
-    }
-    cs.enforce_equal(sum, s);
+    const std::vector<V> b = edwards::scalar_bits(s, s_words, bits, cs);
     const edwards::PointVar<FrP> r = edwards::scalar_mul_le(k, p, b, cs);
     cs.enforce_equal(r.x, qx);
     cs.enforce_equal(r.y, qy);
+    return cs;
+}
+
+// Hybrid<DiffieHellman, FixedDuplexer>::encrypt in circuit (openzl-crypto/src/encryption/hybrid.rs, impl Encrypt): "this ciphertext is the hybrid encryption,
+// to the public key pk, of a plaintext I know" -- epk = esk G, S = esk pk, then the duplex cipher under the key (S.x, S.y): the two gadgets above joined, so
+// that the cipher's key IS the agreement's output (two separate proofs would not bind them).
+// Public inputs (Ciphertext::extend: epk, then tag, then message): G.x G.y pk.x pk.y epk.x epk.y tag, the N rate ciphertext elements, the H header elements.
+// Witnesses: esk; its `bits` Boolean witnesses, allocated ONCE and shared by both ladders; the ladder over G (R_1 and 13 records a step); the ladder over pk in
+// the same form -- its last R is S, bound to nothing public; the N rate plaintext elements; the 3 S records of the cipher as poseidon_encrypt orders them at
+// K = 2.  Rows: the bits', sum 2^i b_i = esk, the G ladder's, epk.x and epk.y bound, the pk ladder's, the cipher's records, tag = public tag, one per ciphertext
+// element.  G and pk are public variables and not checked to be on the curve: the verifier checks them.
+// Shape, derived again (T = N rate, L = 2 + 13 (bits - 1) = 13 bits - 11 per ladder):
+//   n_instance    = 1 + 2 + 2 + 2 + 1 + T + H                       = 8 + T + H
+//   n_witness     = 1 + bits + 2 L + T + 3 S                        = 27 bits - 21 + T + 3 S
+//   n_constraints = bits + 1 + L + 2 + L + 3 S + 1 + T              = 27 bits - 18 + 3 S + T
+// (the rows in front of the cipher's are 27 bits - 19; the cipher adds its 3 S + 1 + T, tag row included), so n_witness - (n_constraints - 1) = -2.
+// Both compilers allocate the public inputs first: epk, tag and ciphertext are known before the circuit runs (computed natively).  All elements canonical.
+template <class FrP, int W>
+static R1CS<FrP> hybrid_encrypt_circuit(bool witness_only, unsigned bits, const Fp<FrP>* init_canon, const Fp<FrP>* g_canon, const uint64_t* esk_words, const Fp<FrP>* pk_canon,
+                                        const Fp<FrP>* epk_canon, const Fp<FrP>& tag_canon, const Fp<FrP>* ct_canon, const Fp<FrP>* header_canon, size_t header_len,
+                                        const Fp<FrP>* text_canon, size_t blocks, const Fp<FrP>& a_canon, const Fp<FrP>& d_canon) {
+    using F = Fp<FrP>;
+    using V = FpVar<FrP>;
+    static const poseidon::Constants<FrP, W> consts;
+    const size_t n_text = blocks * (W - 1);
+    R1CS<FrP> cs = witness_only ? R1CS<FrP>::for_witness() : R1CS<FrP>::for_proofs();
+    const edwards::Coeffs<FrP> k{zl::to_mont(a_canon), zl::to_mont(d_canon)};
+    const edwards::PointVar<FrP> g{cs.new_input(zl::to_mont(g_canon[0])), cs.new_input(zl::to_mont(g_canon[1]))};
+    const edwards::PointVar<FrP> pk{cs.new_input(zl::to_mont(pk_canon[0])), cs.new_input(zl::to_mont(pk_canon[1]))};
+    const V epk_x = cs.new_input(zl::to_mont(epk_canon[0])), epk_y = cs.new_input(zl::to_mont(epk_canon[1]));
+    const V pub_tag = cs.new_input(zl::to_mont(tag_canon));
+    std::vector<V> pub_ct(n_text), hv(header_len), pv(n_text), cv;
+    for (size_t i = 0; i < n_text; i++) pub_ct[i] = cs.new_input(zl::to_mont(ct_canon[i]));
+    for (size_t i = 0; i < header_len; i++) hv[i] = cs.new_input(zl::to_mont(header_canon[i]));
+    F esk_canon;
+    memcpy(esk_canon.l, esk_words, 32);
+    const V esk = cs.new_witness(zl::to_mont(esk_canon));
+    const std::vector<V> b = edwards::scalar_bits(esk, esk_words, bits, cs);
+    const edwards::PointVar<FrP> epk = edwards::scalar_mul_le(k, g, b, cs);
+    cs.enforce_equal(epk.x, epk_x);
+    cs.enforce_equal(epk.y, epk_y);
+    const edwards::PointVar<FrP> shared = edwards::scalar_mul_le(k, pk, b, cs);
+    for (size_t i = 0; i < n_text; i++) pv[i] = cs.new_witness(zl::to_mont(text_canon[i]));
+    V state[W];
+    for (int i = 0; i < W; i++) state[i] = cs.constant(zl::to_mont(init_canon[i]));
+    poseidon::duplex_encrypt_circuit<FrP, W>(consts, state, std::vector<V>{shared.x, shared.y}, hv, pv, cv, cs);
+    cs.enforce_equal(state[1], pub_tag);
+    for (size_t i = 0; i < n_text; i++) cs.enforce_equal(cv[i], pub_ct[i]);
     return cs;
 }
 
@@ -964,8 +994,69 @@ static int circuit_ed_mul(zl_curve_t curve, unsigned bits, const uint64_t* point
     return ZL_OK;
 }
 
+struct HybridCircuitIn {
+    unsigned width, bits;
+    const uint64_t *initial_state, *generator_xy, *esk, *pk_xy, *header, *plaintext;
+    size_t header_len, blocks;
+    bool witness_only;
+};
+template <class FrP>
+static int circuit_hybrid_t(zl_circuit* c, const HybridCircuitIn& in, const uint64_t* epk, const uint64_t* tag, const uint64_t* ct, const uint64_t* a, const uint64_t* d) {
+    std::vector<Fp<FrP>> st, g, pk, e, tg, cv, h, p, ka, kd;
+    const uint64_t zero_state[4 * 6] = {0};
+    const size_t n_text = in.blocks * (in.width - 1);
+    if (!elems_below_r<FrP>(in.initial_state ? in.initial_state : zero_state, in.width, st) || !elems_below_r<FrP>(in.generator_xy, 2, g) ||
+        !elems_below_r<FrP>(in.pk_xy, 2, pk) || !elems_below_r<FrP>(epk, 2, e) || !elems_below_r<FrP>(tag, 1, tg) || !elems_below_r<FrP>(ct, n_text, cv) ||
+        !elems_below_r<FrP>(in.header, in.header_len, h) || !elems_below_r<FrP>(in.plaintext, n_text, p) || !elems_below_r<FrP>(a, 1, ka) || !elems_below_r<FrP>(d, 1, kd))
+        return ZL_EINVAL;
+#define ZL_HYBRID_W(W)                                                                                                                                                  \
+    circuit_set(c, hybrid_encrypt_circuit<FrP, W>(in.witness_only, in.bits, st.data(), g.data(), in.esk, pk.data(), e.data(), tg[0], cv.data(), h.data(), in.header_len, \
+                                                  p.data(), in.blocks, ka[0], kd[0]))
+    switch (in.width) {
+    case 3: ZL_HYBRID_W(3); break;
+    case 4: ZL_HYBRID_W(4); break;
+    case 5: ZL_HYBRID_W(5); break;
+    default: ZL_HYBRID_W(6); break;
+    }
+#undef ZL_HYBRID_W
+    return ZL_OK;
+}
+// epk, tag and ciphertext natively first (zl_hybrid_encrypt_batch's host mirror: it refuses a coordinate >= q, a point off the curve, esk >= l and an element
+// >= r), then the circuit around them
+static int circuit_hybrid(zl_curve_t curve, const HybridCircuitIn& in, zl_circuit** out) {
+    if (!out || !in.generator_xy || !in.esk || !in.pk_xy || (in.header_len && !in.header) || !in.plaintext ||
+        zl_hybrid_encrypt_assignment_elems(curve, in.width, in.bits, in.header_len, in.blocks) == 0)
+        return ZL_EINVAL;
+    for (unsigned i = in.bits; i < 256; i++)
+        if ((in.esk[i >> 6] >> (i & 63)) & 1) return ZL_EINVAL;  // esk >= 2^bits
+    uint64_t epk[8], tag[4], a[4], d[4];
+    std::vector<uint64_t> ct(in.blocks * (in.width - 1) * 4);
+    if (zl_hybrid_encrypt_batch(nullptr, curve, in.width, in.initial_state, in.generator_xy, in.esk, in.pk_xy, 1, in.header, in.header_len, in.plaintext, in.blocks, 1, 0, epk,
+                                ct.data(), tag, nullptr) ||
+        zl_ed_params(curve, a, d, nullptr, nullptr))
+        return ZL_EINVAL;
+    zl_circuit* c = new (std::nothrow) zl_circuit();
+    if (!c) return ZL_ENOMEM;
+    c->curve = curve;
+    const int rc = curve == ZL_BLS12_381 ? circuit_hybrid_t<BLS12_381_Fr>(c, in, epk, tag, ct.data(), a, d) : circuit_hybrid_t<BN254_Fr>(c, in, epk, tag, ct.data(), a, d);
+    if (rc) {
+        zl_circuit_free(c);
+        return rc;
+    }
+    *out = c;
+    return ZL_OK;
+}
+
 extern "C" {
 
+int zl_circuit_hybrid_encrypt(zl_curve_t curve, unsigned width, unsigned bits, const uint64_t* initial_state, const uint64_t* generator_xy, const uint64_t* esk,
+                              const uint64_t* pk_xy, const uint64_t* header, size_t header_len, const uint64_t* plaintext, size_t blocks, zl_circuit** out) {
+    return circuit_hybrid(curve, HybridCircuitIn{width, bits, initial_state, generator_xy, esk, pk_xy, header, plaintext, header_len, blocks, false}, out);
+}
+int zl_circuit_hybrid_encrypt_witness(zl_curve_t curve, unsigned width, unsigned bits, const uint64_t* initial_state, const uint64_t* generator_xy, const uint64_t* esk,
+                                      const uint64_t* pk_xy, const uint64_t* header, size_t header_len, const uint64_t* plaintext, size_t blocks, zl_circuit** out) {
+    return circuit_hybrid(curve, HybridCircuitIn{width, bits, initial_state, generator_xy, esk, pk_xy, header, plaintext, header_len, blocks, true}, out);
+}
 int zl_circuit_ed_scalar_mul(zl_curve_t curve, unsigned bits, const uint64_t* point_xy, const uint64_t* scalar, zl_circuit** out) {
     return circuit_ed_mul(curve, bits, point_xy, scalar, false, out);
 }

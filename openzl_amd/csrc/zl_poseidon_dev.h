@@ -119,6 +119,25 @@ int zl_poseidon_merkle_leaf_member_rows(zl_ctx* ctx, int curve, unsigned arity, 
 int zl_poseidon_encrypt_trace_rows(zl_ctx* ctx, int curve, unsigned width, const uint64_t* initial_state, const uint64_t* keys, size_t key_len, const uint64_t* headers,
                                    size_t header_len, const uint64_t* plaintexts, size_t blocks, size_t count, void* d_rows, size_t stride_elems, uint64_t* tags_out,
                                    uint64_t* ciphertexts_out);
+// The encryption trace inside ANOTHER circuit's rows (zl_circuit_hybrid_encrypt: the embedded-curve unit owns the row and its chunk).  Where the cipher's cells
+// lie in such a row, in elements from the row's start: the tag, the N rate ciphertext elements, the H header elements, the N rate plaintext elements and the 3 S
+// records are WRITTEN there; the key -- key_len elements, key_len >= 1 -- is READ from the row's own cells at `key` (some earlier launch on the stream wrote
+// them) and not copied anywhere; [0] is not written.  zl_poseidon_encrypt_assignments' own row is the other layout of the same kernel body: key read from the
+// call's keys and copied into cells, [0] = 1 written.
+struct zl_duplex_row_layout {
+    size_t tag, ct, header, key, plain, rec;
+};
+// _params: the cipher's validation (curve, width, lengths, initial_state -- NULL = zero, each element below r) -> init_out, 4 * MAX_WIDTH words.
+// _launch: ONE launch of m rows on ctx's stream, no staging and no slot of this unit (the caller's chunk holds everything): row i at d_rows + i * stride_elems
+// elements (16-byte aligned), headers and plaintexts dense in DEVICE memory, d_tags / d_cts (device, may be null) receive the tag and the ciphertext of every
+// row, d_flag is the caller's flag word (bit 0 raised for a header, plaintext or key element >= r).  Not finished on return.  m is the caller's to bound.
+// _host: the byte-identical host mirror over the host pool, rows, headers and plaintexts in HOST memory; ZL_EINVAL for an element >= r.
+int zl_poseidon_duplex_row_params(int curve, unsigned width, const uint64_t* initial_state, size_t key_len, size_t header_len, size_t blocks, uint64_t* init_out);
+int zl_poseidon_duplex_row_launch(zl_ctx* ctx, int curve, unsigned width, const uint64_t* init, const zl_duplex_row_layout& lay, size_t key_len, const void* d_headers,
+                                  size_t header_len, const void* d_plaintexts, size_t blocks, size_t m, void* d_rows, size_t stride_elems, void* d_tags, void* d_cts,
+                                  uint32_t* d_flag);
+int zl_poseidon_duplex_row_host(int curve, unsigned width, const uint64_t* init, const zl_duplex_row_layout& lay, size_t key_len, const uint64_t* headers, size_t header_len,
+                                const uint64_t* plaintexts, size_t blocks, size_t count, uint64_t* rows, size_t stride_elems);
 // The forest producer of the fused prover (zl_groth16_prove_forest_members).  _prover_view: ZL_EINVAL for a null or host-mirror forest or a ctx of another
 // device, else the forest's curve and depth.  _members_ok: ZL_EINVAL unless every (tree_of[i], indices[i]) names a leaf the forest holds.  _member_rows:
 // zl_poseidon_merkle_member_rows with a tree per item, issued on ctx (the forest's own ctx or another lane of its device); roots_out (host, may be null)

@@ -30,6 +30,8 @@
 //   k_pos_duplex     the duplex-sponge cipher (zl_poseidon_duplex_*), widths 3..6: one lane per message, its key, header and message blocks absorbed into the rate
 //                    between the SB + N dependent permutations of ONE launch (permute_any); encrypt and decrypt are one template with a wave-uniform mode.  The
 //                    absorbed lanes are outside the permutations' bound arguments and are reduced weakly at once (DuplexBounds).
+//   k_pos_duplex_trace_in   k_pos_duplex_trace's body (duplex_trace_row) inside the rows of a circuit that holds the cipher: the cells where a row-layout
+//                    descriptor says, the key read from the row itself (zl_circuit_hybrid_encrypt's agreed point), launched for the embedded-curve unit.
 //   k_pos_duplex_trace   k_pos_duplex, encrypting, with the witness written out: the complete assignment of zl_circuit_poseidon_encrypt per message -- 1, tag,
 //                    ciphertext, header, key, plaintext, then the records of the SB + N permutations -- under the circuit's round-0 record mask (rec0_mask): the
 //                    first permutation drops lane 0 and the rate lanes without a key element, every later one records all of its S-boxes (DuplexTraceBounds).
@@ -972,17 +974,18 @@ ZL_HD uint32_t rec0_mask(unsigned width, size_t key_len, bool first) {
     return 1u | (((1u << width) - 1u) ^ ((1u << (1 + kk)) - 1u));
 }
 // rate lanes I .. W - 2 of one block under the trace (duplex_lanes, encrypting): lane i takes element i of the block when i < avail, the element's words go to
-// cell i of `in_cells` (16-byte aligned) as they are, and a message block's reduced sum -- the ciphertext -- to cell i of ct_cells and, densely, to ct_pub
-// (may be null): one canonical store, written twice.
+// cell i of `in_cells` (16-byte aligned) as they are -- unless `copy` is false: the block is read from the row's own cells (a key another circuit's launch
+// left there) -- and a message block's reduced sum -- the ciphertext -- to cell i of ct_cells and, densely, to ct_pub (may be null): one canonical store,
+// written twice.
 template <class FrP, int W, int I>
 __device__ __forceinline__ void duplex_trace_lanes(El<FrP> (&s)[W], const uint64_t* src, uint64_t* in_cells, uint64_t* ct_cells, uint64_t* ct_pub, uint32_t avail, bool message,
-                                                   bool& ok) {
+                                                   bool copy, bool& ok) {
     if constexpr (I < W - 1) {
         if ((uint32_t)I < avail) {
             const uint64_t* x = src + 4 * I;
             El<FrP> e;
             ok &= dload<FrP>(x, e);
-            copy16(in_cells + 4 * I, x[0], x[1], x[2], x[3]);
+            if (copy) copy16(in_cells + 4 * I, x[0], x[1], x[2], x[3]);
             s[1 + I] = zl::wred(zl::add(s[1 + I], e));
             if (message) {
                 uint64_t c[4];
@@ -994,37 +997,28 @@ __device__ __forceinline__ void duplex_trace_lanes(El<FrP> (&s)[W], const uint64
                 }
             }
         }
-        duplex_trace_lanes<FrP, W, I + 1>(s, src, in_cells, ct_cells, ct_pub, avail, message, ok);
+        duplex_trace_lanes<FrP, W, I + 1>(s, src, in_cells, ct_cells, ct_pub, avail, message, copy, ok);
     }
 }
-// k_pos_duplex, encrypting, with the witness written out: the complete assignment of zl_circuit_poseidon_encrypt(curve, W, init, key, header, plaintext) per
-// message, one lane each, the SB + N dependent permutations in one launch.  Row p = out + p * stride elements (16-byte aligned), rate = W - 1:
-//   [0] = 1   [1] = tag   [2 .. 2 + N rate) ciphertext   [.. + H) header   [.. + K) key   [.. + N rate) plaintext   then 3 S record elements in execution order;
-// elements behind the row are not touched.  The lane writes the input cells and the ciphertext cells as it absorbs their blocks, the records as the
-// permutations run, [0] and [1] last.  Rows and inputs do not overlap.  tags / cts (may be null) receive the tag and the N rate ciphertext elements, densely.
-// K >= 1; block selection as in k_pos_duplex, all wave-uniform, and so is the record mask.
-template <class FrP, int W>
-__global__ __launch_bounds__(BLOCK) void k_pos_duplex_trace(const uint32_t* __restrict__ tab, const DuplexInit init, const uint64_t* __restrict__ keys, uint32_t K,
-                                                            const uint64_t* __restrict__ headers, uint32_t H, const uint64_t* __restrict__ texts, uint32_t N, size_t n,
-                                                            uint64_t* __restrict__ out, size_t stride, uint64_t* __restrict__ tags, uint64_t* __restrict__ cts,
-                                                            uint32_t* __restrict__ flag) {
-    const size_t p = (size_t)blockIdx.x * BLOCK + threadIdx.x;
-    if (p >= n) return;
+// Where one lane's row keeps the cipher's cells (16-byte aligned each), and where its key is read from.  The row-layout descriptor of the trace body: the
+// encryption circuit's own row (k_pos_duplex_trace) and a row of a circuit that holds the cipher inside it (k_pos_duplex_trace_in: zl_duplex_row_layout).
+struct DuplexRowCells {
+    uint64_t *one, *tag, *ct, *header, *key, *plain, *rec;  // one: [0] = 1 is written there, or null; key: where the key is copied TO (unused when KEY_IN_ROW)
+    const uint64_t* key_from;                               // K elements: the call's keys, or cells of the row itself
+};
+// The body of both trace kernels, one lane a row: k_pos_duplex's chain, encrypting, under a recorder.  The lane writes the input cells and the ciphertext
+// cells as it absorbs their blocks, the records as the permutations run, [0] and the tag last.  KEY_IN_ROW: the key blocks are read from the row and copied
+// nowhere.  tag_pub / ct_pub (may be null): the lane's dense tag and ciphertext.  K >= 1; block selection as in k_pos_duplex, all wave-uniform, and so is the
+// record mask.  No new arithmetic over DuplexTraceBounds: a key read from the row is a canonical element like one read from the call's keys.
+template <class FrP, int W, bool KEY_IN_ROW>
+__device__ __forceinline__ void duplex_trace_row(const uint32_t* __restrict__ tab, const DuplexInit& init, const DuplexRowCells& c, uint32_t K, const uint64_t* header, uint32_t H,
+                                                 const uint64_t* text, uint32_t N, uint64_t* tag_pub, uint64_t* ct_pub, uint32_t* __restrict__ flag) {
     constexpr uint32_t RATE = W - 1;
     El<FrP> s[W];
 #pragma unroll
     for (int i = 0; i < W; i++) (void)dload<FrP>(init.w + 4 * i, s[i]);  // (checked on the host)
     const uint32_t kb = K / RATE + 1, sb = kb + H / RATE + 1, total = sb + N, T = N * RATE;
-    const uint64_t* key = keys + p * K * 4;
-    const uint64_t* header = headers + p * H * 4;
-    const uint64_t* text = texts + p * T * 4;
-    uint64_t* row = out + p * stride * 4;
-    uint64_t* ct_cells = row + 8;
-    uint64_t* h_cells = ct_cells + (size_t)T * 4;
-    uint64_t* k_cells = h_cells + (size_t)H * 4;
-    uint64_t* p_cells = k_cells + (size_t)K * 4;
-    uint64_t* ct_pub = cts ? cts + p * T * 4 : nullptr;
-    RowRec<FrP> rec{p_cells + (size_t)T * 4};
+    RowRec<FrP> rec{c.rec};
     bool ok = true;
 #pragma unroll 1
     for (uint32_t t = 0; t < total; t++) {
@@ -1032,21 +1026,70 @@ __global__ __launch_bounds__(BLOCK) void k_pos_duplex_trace(const uint32_t* __re
         const uint32_t b = message ? t - sb : t < kb ? t : t - kb;       // the block's number within its sequence
         const uint32_t len = message ? T : t < kb ? K : H;                // ... and the sequence's length: b * RATE <= len
         const size_t at = (size_t)b * RATE * 4;
-        const uint64_t* src = (message ? text : t < kb ? key : header) + at;
-        uint64_t* in_cells = (message ? p_cells : t < kb ? k_cells : h_cells) + at;
+        const uint64_t* src = (message ? text : t < kb ? c.key_from : header) + at;
+        uint64_t* in_cells = (message ? c.plain : t < kb ? c.key : c.header) + at;
         const uint32_t left = len - b * RATE;
-        duplex_trace_lanes<FrP, W, 0>(s, src, in_cells, message ? ct_cells + at : nullptr, message && ct_pub ? ct_pub + at : nullptr, left < RATE ? left : RATE, message, ok);
+        duplex_trace_lanes<FrP, W, 0>(s, src, in_cells, message ? c.ct + at : nullptr, message && ct_pub ? ct_pub + at : nullptr, left < RATE ? left : RATE, message,
+                                      !KEY_IN_ROW || t >= kb, ok);
         permute_any<FrP, W>(tab, s, rec, rec0_mask(W, K, t == 0));
     }
     if (!ok) atomicOr(flag, 1u);
     uint64_t tg[4];
     dstore<FrP>(tg, s[1]);
-    copy16(row, 1, 0, 0, 0);
-    copy16(row + 4, tg[0], tg[1], tg[2], tg[3]);
-    if (tags) {
+    if (!KEY_IN_ROW) copy16(c.one, 1, 0, 0, 0);
+    copy16(c.tag, tg[0], tg[1], tg[2], tg[3]);
+    if (tag_pub) {
 #pragma unroll
-        for (int i = 0; i < 4; i++) tags[p * 4 + i] = tg[i];
+        for (int i = 0; i < 4; i++) tag_pub[i] = tg[i];
     }
+}
+// k_pos_duplex, encrypting, with the witness written out: the complete assignment of zl_circuit_poseidon_encrypt(curve, W, init, key, header, plaintext) per
+// message, one lane each, the SB + N dependent permutations in one launch.  Row p = out + p * stride elements (16-byte aligned), rate = W - 1:
+//   [0] = 1   [1] = tag   [2 .. 2 + N rate) ciphertext   [.. + H) header   [.. + K) key   [.. + N rate) plaintext   then 3 S record elements in execution order;
+// elements behind the row are not touched.  Rows and inputs do not overlap.  tags / cts (may be null) receive the tag and the N rate ciphertext elements,
+// densely.  The body is duplex_trace_row's.
+template <class FrP, int W>
+__global__ __launch_bounds__(BLOCK) void k_pos_duplex_trace(const uint32_t* __restrict__ tab, const DuplexInit init, const uint64_t* __restrict__ keys, uint32_t K,
+                                                            const uint64_t* __restrict__ headers, uint32_t H, const uint64_t* __restrict__ texts, uint32_t N, size_t n,
+                                                            uint64_t* __restrict__ out, size_t stride, uint64_t* __restrict__ tags, uint64_t* __restrict__ cts,
+                                                            uint32_t* __restrict__ flag) {
+    const size_t p = (size_t)blockIdx.x * BLOCK + threadIdx.x;
+    if (p >= n) return;
+    const uint32_t T = N * (W - 1);
+    uint64_t* row = out + p * stride * 4;
+    DuplexRowCells c;
+    c.one = row;
+    c.tag = row + 4;
+    c.ct = row + 8;
+    c.header = c.ct + (size_t)T * 4;
+    c.key = c.header + (size_t)H * 4;
+    c.plain = c.key + (size_t)K * 4;
+    c.rec = c.plain + (size_t)T * 4;
+    c.key_from = keys + p * K * 4;
+    duplex_trace_row<FrP, W, false>(tab, init, c, K, headers + p * H * 4, H, texts + p * T * 4, N, tags ? tags + p * 4 : nullptr, cts ? cts + p * T * 4 : nullptr, flag);
+}
+// The same body inside another circuit's rows (zl_poseidon_duplex_row_launch; zl_circuit_hybrid_encrypt's: the key is the agreed point the pk ladder of
+// k_ed_hybrid_ladders left in the row, earlier on the stream).  lay: element offsets within the row; [0] is not written; the key is read from the row, so
+// `out` is read and written and carries no __restrict__.
+template <class FrP, int W>
+__global__ __launch_bounds__(BLOCK) void k_pos_duplex_trace_in(const uint32_t* __restrict__ tab, const DuplexInit init, const zl_duplex_row_layout lay, uint32_t K,
+                                                               const uint64_t* __restrict__ headers, uint32_t H, const uint64_t* __restrict__ texts, uint32_t N, size_t n,
+                                                               uint64_t* out, size_t stride, uint64_t* __restrict__ tags, uint64_t* __restrict__ cts,
+                                                               uint32_t* __restrict__ flag) {
+    const size_t p = (size_t)blockIdx.x * BLOCK + threadIdx.x;
+    if (p >= n) return;
+    const uint32_t T = N * (W - 1);
+    uint64_t* row = out + p * stride * 4;
+    DuplexRowCells c;
+    c.one = nullptr;
+    c.tag = row + lay.tag * 4;
+    c.ct = row + lay.ct * 4;
+    c.header = row + lay.header * 4;
+    c.key = nullptr;
+    c.plain = row + lay.plain * 4;
+    c.rec = row + lay.rec * 4;
+    c.key_from = row + lay.key * 4;
+    duplex_trace_row<FrP, W, true>(tab, init, c, K, headers + p * H * 4, H, texts + p * T * 4, N, tags ? tags + p * 4 : nullptr, cts ? cts + p * T * 4 : nullptr, flag);
 }
 
 // ---------------------------------------------------------------------------------------------------------------- host path
@@ -1333,14 +1376,56 @@ int host_duplex(const uint64_t* init, const uint64_t* keys, size_t K, const uint
         return ok;
     }) ? ZL_OK : ZL_EINVAL;
 }
-// row i = the assignment of encryption i (nv = pd::encrypt_row_elems elements): what poseidon_encrypt (zl_host.hip) allocates -- duplex_setup's and
-// duplex_encrypt's block walk with permute_native_record in place of permute_native, under the circuit's round-0 mask (rec0_mask)
+// One row of the encryption trace on the host, the mirror of duplex_trace_row: what poseidon_encrypt (zl_host.hip) allocates -- duplex_setup's and
+// duplex_encrypt's block walk with permute_native_record in place of permute_native, under the circuit's round-0 mask (rec0_mask).  The header and plaintext
+// cells hold their inputs already; the key is read from key_from (the row's key cells, or cells another circuit's gadget filled); the ciphertext cells, the
+// records and the tag cell are written.  False for an element >= r.
+template <class FrP, int W>
+bool host_encrypt_row(const Fp<FrP> (&st0)[W], const uint64_t* key_from, size_t K, const uint64_t* h_cells, size_t H, const uint64_t* p_cells, size_t N, uint64_t* ct_cells,
+                      uint64_t* rec_cells, uint64_t* tag_cell) {
+    constexpr size_t rate = W - 1;
+    Fp<FrP> st[W];
+    for (int e = 0; e < W; e++) st[e] = st0[e];
+    std::vector<Fp<FrP>> rec;
+    rec.reserve(3 * (size_t)(consts<FrP, W>().FULL_ROUNDS * W + consts<FrP, W>().PARTIAL_ROUNDS));
+    bool ok = true, first = true;
+    auto permute = [&]() {
+        rec.clear();
+        poseidon::permute_native_record(consts<FrP, W>(), st, rec, rec0_mask(W, K, first));
+        first = false;
+        for (size_t t = 0; t < rec.size(); t++) store_canon<FrP>(rec_cells + 4 * t, rec[t]);
+        rec_cells += 4 * rec.size();
+    };
+    for (int part = 0; part < 2; part++) {
+        const uint64_t* src = part ? h_cells : key_from;
+        const size_t len = part ? H : K;
+        for (size_t b = 0; b <= len / rate; b++) {
+            for (size_t l = 0; l < rate && b * rate + l < len; l++) {
+                Fp<FrP> e;
+                ok &= load_canon<FrP>(src + (b * rate + l) * 4, e);
+                st[1 + l] = zl::add(st[1 + l], e);
+            }
+            permute();
+        }
+    }
+    for (size_t j = 0; j < N; j++) {
+        for (size_t l = 0; l < rate; l++) {
+            Fp<FrP> e;
+            ok &= load_canon<FrP>(p_cells + (j * rate + l) * 4, e);
+            st[1 + l] = zl::add(st[1 + l], e);
+            store_canon<FrP>(ct_cells + (j * rate + l) * 4, st[1 + l]);
+        }
+        permute();
+    }
+    store_canon<FrP>(tag_cell, st[1]);
+    return ok;
+}
+// row i = the assignment of encryption i (nv = pd::encrypt_row_elems elements)
 template <class FrP, int W>
 int host_encrypt_assignments(const uint64_t* init, const uint64_t* keys, size_t K, const uint64_t* headers, size_t H, const uint64_t* texts, size_t N, size_t count,
                              uint64_t* out, size_t nv) {
     consts<FrP, W>();
-    constexpr size_t rate = W - 1;
-    const size_t T = N * rate;
+    const size_t T = N * (W - 1);
     Fp<FrP> st0[W];
     for (int e = 0; e < W; e++) (void)load_canon<FrP>(init + 4 * e, st0[e]);
     return host_for(count, [&](size_t i) {
@@ -1349,47 +1434,27 @@ int host_encrypt_assignments(const uint64_t* init, const uint64_t* keys, size_t 
         uint64_t* h_cells = ct_cells + T * 4;
         uint64_t* k_cells = h_cells + H * 4;
         uint64_t* p_cells = k_cells + K * 4;
-        uint64_t* rec_cells = p_cells + T * 4;
         if (H) memcpy(h_cells, headers + i * H * 4, H * 32);
         memcpy(k_cells, keys + i * K * 4, K * 32);
         memcpy(p_cells, texts + i * T * 4, T * 32);
-        Fp<FrP> st[W];
-        for (int e = 0; e < W; e++) st[e] = st0[e];
-        std::vector<Fp<FrP>> rec;
-        rec.reserve(3 * (size_t)(consts<FrP, W>().FULL_ROUNDS * W + consts<FrP, W>().PARTIAL_ROUNDS));
-        bool ok = true, first = true;
-        auto permute = [&]() {
-            rec.clear();
-            poseidon::permute_native_record(consts<FrP, W>(), st, rec, rec0_mask(W, K, first));
-            first = false;
-            for (size_t t = 0; t < rec.size(); t++) store_canon<FrP>(rec_cells + 4 * t, rec[t]);
-            rec_cells += 4 * rec.size();
-        };
-        for (int part = 0; part < 2; part++) {
-            const uint64_t* src = part ? h_cells : k_cells;
-            const size_t len = part ? H : K;
-            for (size_t b = 0; b <= len / rate; b++) {
-                for (size_t l = 0; l < rate && b * rate + l < len; l++) {
-                    Fp<FrP> e;
-                    ok &= load_canon<FrP>(src + (b * rate + l) * 4, e);
-                    st[1 + l] = zl::add(st[1 + l], e);
-                }
-                permute();
-            }
-        }
-        for (size_t j = 0; j < N; j++) {
-            for (size_t l = 0; l < rate; l++) {
-                Fp<FrP> e;
-                ok &= load_canon<FrP>(p_cells + (j * rate + l) * 4, e);
-                st[1 + l] = zl::add(st[1 + l], e);
-                store_canon<FrP>(ct_cells + (j * rate + l) * 4, st[1 + l]);
-            }
-            permute();
-        }
         row[0] = 1;
         row[1] = row[2] = row[3] = 0;
-        store_canon<FrP>(row + 4, st[1]);
-        return ok;
+        return host_encrypt_row<FrP, W>(st0, k_cells, K, h_cells, H, p_cells, N, ct_cells, p_cells + T * 4, row + 4);
+    }) ? ZL_OK : ZL_EINVAL;
+}
+// the same walk inside another circuit's rows (zl_poseidon_duplex_row_host): header and plaintext copied to their cells, the key read where the layout says
+template <class FrP, int W>
+int host_encrypt_rows_in(const uint64_t* init, const zl_duplex_row_layout& lay, size_t K, const uint64_t* headers, size_t H, const uint64_t* texts, size_t N, size_t count,
+                         uint64_t* rows, size_t stride) {
+    consts<FrP, W>();
+    const size_t T = N * (W - 1);
+    Fp<FrP> st0[W];
+    for (int e = 0; e < W; e++) (void)load_canon<FrP>(init + 4 * e, st0[e]);
+    return host_for(count, [&](size_t i) {
+        uint64_t* row = rows + i * stride * 4;
+        if (H) memcpy(row + lay.header * 4, headers + i * H * 4, H * 32);
+        memcpy(row + lay.plain * 4, texts + i * T * 4, T * 32);
+        return host_encrypt_row<FrP, W>(st0, row + lay.key * 4, K, row + lay.header * 4, H, row + lay.plain * 4, N, row + lay.ct * 4, row + lay.rec * 4, row + lay.tag * 4);
     }) ? ZL_OK : ZL_EINVAL;
 }
 
@@ -2100,6 +2165,31 @@ int zl_poseidon_encrypt_trace_rows(zl_ctx* ctx, int curve, unsigned width, const
     const DuplexCall c{init, key_len, header_len, blocks, false};
     return ZL_POS_ANYW(curve, width, encrypt_trace_run, ctx, c, keys, headers, plaintexts, true, count, static_cast<uint64_t*>(d_rows), stride_elems, nullptr, tags_out,
                        ciphertexts_out);
+}
+int zl_poseidon_duplex_row_params(int curve, unsigned width, const uint64_t* initial_state, size_t key_len, size_t header_len, size_t blocks, uint64_t* init_out) {
+    return encrypt_params((zl_curve_t)curve, width, initial_state, key_len, header_len, blocks, init_out);
+}
+template <class FrP, int W>
+static int duplex_row_launch(zl_ctx* ctx, const uint64_t* init_words, const zl_duplex_row_layout& lay, size_t K, const uint64_t* d_headers, size_t H, const uint64_t* d_texts,
+                             size_t N, size_t m, uint64_t* d_rows, size_t stride, uint64_t* d_tags, uint64_t* d_cts, uint32_t* d_flag) {
+    const uint32_t* tab;
+    const int rc = get_table<FrP, W>(ctx, &tab);
+    if (rc) return rc;
+    DuplexInit init{};
+    memcpy(init.w, init_words, 32 * W);
+    ZL_POS_LAUNCH(ctx, (k_pos_duplex_trace_in<FrP, W>), blocks_of(m), BLOCK, 0, tab, init, lay, (uint32_t)K, d_headers, (uint32_t)H, d_texts, (uint32_t)N, m, d_rows, stride, d_tags,
+                  d_cts, d_flag);
+    return ZL_OK;
+}
+int zl_poseidon_duplex_row_launch(zl_ctx* ctx, int curve, unsigned width, const uint64_t* init, const zl_duplex_row_layout& lay, size_t key_len, const void* d_headers,
+                                  size_t header_len, const void* d_plaintexts, size_t blocks, size_t m, void* d_rows, size_t stride_elems, void* d_tags, void* d_cts,
+                                  uint32_t* d_flag) {
+    return ZL_POS_ANYW(curve, width, duplex_row_launch, ctx, init, lay, key_len, static_cast<const uint64_t*>(d_headers), header_len, static_cast<const uint64_t*>(d_plaintexts),
+                       blocks, m, static_cast<uint64_t*>(d_rows), stride_elems, static_cast<uint64_t*>(d_tags), static_cast<uint64_t*>(d_cts), d_flag);
+}
+int zl_poseidon_duplex_row_host(int curve, unsigned width, const uint64_t* init, const zl_duplex_row_layout& lay, size_t key_len, const uint64_t* headers, size_t header_len,
+                                const uint64_t* plaintexts, size_t blocks, size_t count, uint64_t* rows, size_t stride_elems) {
+    return ZL_POS_ANYW(curve, width, host_encrypt_rows_in, init, lay, key_len, headers, header_len, plaintexts, blocks, count, rows, stride_elems);
 }
 
 extern "C" {
